@@ -16,7 +16,10 @@ Workloads (BASELINE.json configs; SURVEY.md 8d scenes, ~25 % colliding trajector
 `python bench.py --gpus N` starts its own N ranks (torch.distributed.run, before anything here
 touches a GPU); launched under torch.distributed.run it reads RANK / WORLD_SIZE from the env.
 
-Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times --steps ticks, writes the last tick's outputs if --dump-outputs is given and
+prints ONE JSON line on rank 0: the headline (value, ms_per_step, ...).  Everything else -- the parity spot check
+against the CPU oracle, roofline, stream ceiling, CPU baseline, moving / end-to-end / shipped-size extras, the other
+marking schedule, the synchronous multi-rank latencies -- runs only with --full.
 """
 import argparse
 import json
@@ -41,11 +44,20 @@ def parse():
     ap.add_argument("--inputs", default="static", choices=["static", "moving"],
                     help="static (default, the headline): every tick sees the same pose / twist / cloud; moving: the robot "
                          "advances along the prune plan every tick and the cloud is replaced every --replace-every ticks "
-                         "(always measured as config.moving_value on one GPU; --inputs moving makes it the headline value)")
+                         "(measured as config.moving_value on one GPU with --full; --inputs moving makes it the headline value, "
+                         "timed over --steps ticks)")
     ap.add_argument("--replace-every", type=int, default=10)
     ap.add_argument("--marking-schedule", choices=["overlapped", "serial"], default="overlapped",
                     help="C5M: tick_begin -> marking update -> tick_end (the update on its own stream next to the tick's kernels, "
                          "as the reference's perception and planner threads run side by side) or feed -> update -> tick one after the other")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, also measure and check everything else: parity spot check against the oracle, "
+                         "roofline, stream ceiling, CPU baseline, moving / end_to_end / shipped-latency extras, the other "
+                         "marking schedule, the synchronous multi-rank latencies (the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step delivered (result, per-trajectory costs / "
+                         "steps / samples, best trajectory; the feed's cloud and the marking layer where the workload has "
+                         "them) as DIR/<name>.npy, float32 / float64")
     ap.add_argument("--no-extras", action="store_true", help="skip end_to_end / moving / shipped-latency measurements")
     ap.add_argument("--scene-layout", default=None, choices=["r02", "r01"],
                     help="r02 (default): ~25 %% colliding trajectories as SURVEY 8d specifies; r01: the round-1 scenes (69-86 %%)")
@@ -152,6 +164,44 @@ def shipped_latencies(np, scenes, configs, LocalPlanner, gpu):
     return out
 
 
+DUMP_LIMIT = 64 << 20      # bytes, all arrays of one --dump-outputs together
+
+
+def dump_outputs(np, out_dir, lp, res, marking=None, feed=False):
+    """--dump-outputs: what the last timed step delivered, read back from the context after the timed loop, one .npy per
+    array in float32 / float64 so that two builds can be compared output for output.  Rows of the feed's cloud and of the
+    marking voxels are sorted (their device order is not part of the contract); an array above an eighth of the limit
+    keeps a fixed, seeded sample of its rows.  Everything else is bit-identical from run to run except the marking dGraph
+    (C5M): a few of its entries differ at ~1e-6 relative between identical runs, so compare it with a tolerance."""
+    costs, steps, samples = lp.debug()
+    arrays = {
+        "result": np.array([res.planner_state, res.best_index, res.best_cost, res.vx, res.vy, res.wz,
+                            res.n_samples, res.n_local], dtype=np.float64),
+        "costs": costs.astype(np.float64),
+        "steps": steps.astype(np.float64),
+        "samples": samples.astype(np.float32),
+        "best_poses": lp.best_poses().astype(np.float64),
+    }
+    if feed:
+        cloud = lp.get_cloud().astype(np.float32)
+        arrays["cloud"] = cloud[np.lexsort(cloud.T[::-1])]
+    if marking is not None:
+        vox = marking.layer.voxels().astype(np.float64)
+        arrays["marking_voxels"] = vox[np.lexsort(vox.T[::-1])]
+        arrays["marking_dgraph"] = marking.layer.dgraph().astype(np.float64)
+        arrays["marking_lethal"] = marking.layer.lethal().astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for key, a in arrays.items():
+        if a.nbytes > DUMP_LIMIT // 8:
+            rows = np.sort(np.random.default_rng(0).choice(len(a), size=(DUMP_LIMIT // 8) // (a.nbytes // len(a)), replace=False))
+            a = a[rows]
+        total += a.nbytes
+        assert total <= DUMP_LIMIT, "--dump-outputs: over the size limit"
+        np.save(os.path.join(out_dir, key + ".npy"), a)
+    print(f"[bench] wrote {len(arrays)} arrays ({total} bytes) to {out_dir}", file=sys.stderr, flush=True)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -215,6 +265,8 @@ def main():
     if workload == "shipped":
         if world > 1:
             raise SystemExit("--workload shipped is a single-GPU latency measurement")
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: --workload shipped times three contexts, there is no single last step to write")
         sh = shipped_latencies(np, scenes, configs, LocalPlanner, gpu)
         n0, t0 = sh[0]["n_trajectories"], sh[0]["warm_tick_ms"]
         json_out.write(json.dumps({
@@ -296,7 +348,7 @@ def main():
 
     # Which exchange the TIMED loop uses.  torch (default, `auto`): the host hides the all-reduce behind the
     # next tick (throughput; winners arrive two ticks late).  inlib: k_score -> ncclAllReduce -> k_resolve on
-    # the tick's stream, every tick synchronous.  With `auto` the in-library path is measured as well, AFTER the
+    # the tick's stream, every tick synchronous.  With `auto` and --full the in-library path is measured as well, AFTER the
     # timed loop and under a watchdog (a collective that never returns must not cost the run its line).
     reduce_mode = "none"
     if world > 1:
@@ -312,7 +364,7 @@ def main():
     # issuing the one of tick i-1 -- happens between tick_begin(i) and tick_end(i), i.e. while the
     # GPU computes tick i.  The winner of a tick is delivered two ticks later; every all-reduce
     # completes inside the timed region (fence() issues and collects the last ones).  The
-    # synchronous tick -> all-reduce -> resolve latency is reported separately below.
+    # synchronous tick -> all-reduce -> resolve latency is reported separately below (--full).
     slot_host = [torch.full((2 * world,), sharding.INT64_MAX, dtype=torch.int64).pin_memory() for _ in range(2)]
     slot_bufs = [torch.full((2 * world,), sharding.INT64_MAX, dtype=torch.int64, device=red_dev) for _ in range(2)]
     pending = []          # [(work handle, buffer)]
@@ -353,6 +405,8 @@ def main():
             inflight.append(False)
     last_res = [None]
     overlap_marking = [marking is not None and args.marking_schedule == "overlapped"]
+    # --inputs moving makes the moving-input loop below the headline (one GPU, resident cloud, one context)
+    moving_headline = (args.inputs == "moving" and world == 1 and scans is None and len(lps) == 1 and not args.no_extras)
 
     def step():
         if len(lps) > 1:
@@ -414,8 +468,11 @@ def main():
             dev_ms.append(lr.device_ms)               # ... and of the whole tick's kernels
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and not moving_headline:
+        timed_res = resolved[0] if reduce_mode == "torch" else (last_res[0] if len(lps) > 1 else res)
+        dump_outputs(np, args.dump_outputs, lps[-1], timed_res, marking, feed=scans is not None)
     serial_ms, marking_summary = None, None
-    if marking is not None:
+    if marking is not None and args.full:
         # the other schedule, and the update's HIP-event times with nothing else on the GPU (right away: the GPU is warm)
         was = overlap_marking[0]
         overlap_marking[0] = False
@@ -445,7 +502,7 @@ def main():
 
     # ---- synchronous latency of one tick incl. the exchange (what a control loop can use) ----
     sync_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         lat = []
         for _ in range(60):
             dist.barrier()
@@ -466,18 +523,18 @@ def main():
         res = r1
 
     ceiling = None
-    if rank == 0 and not args.no_ceiling:
+    if rank == 0 and args.full and not args.no_ceiling:
         cp, rd = lp.stream_ceiling(1 << 30, 10)
         ceiling = {"copy_GBps": round(cp, 1), "read_GBps": round(rd, 1), "buffer_bytes": 1 << 30,
                    "note": "float4 grid-stride kernels of this library on this GPU (copy counts read + write bytes)"}
 
     # ---- what a control loop sees (one GPU, resident-cloud workloads): inputs that move, the host boundary, the shipped sizes ----
     extras = {}
-    if rank == 0 and world == 1 and scans is None and len(lps) == 1 and not args.no_extras:
-        import oracle as _oracle
+    # (a) alone when it is the headline (--inputs moving), all three with --full
+    if moving_headline or (args.full and rank == 0 and world == 1 and scans is None and len(lps) == 1 and not args.no_extras):
         # (a) moving inputs: pose / twist advance along the prune plan every tick, the cloud is replaced every k ticks
-        #     (set_cloud of the other variant, H2D included); the last tick is checked against the oracle
-        n_mv = max(60, min(args.steps, 200))
+        #     (set_cloud of the other variant, H2D included); the last tick is checked against the oracle (--full)
+        n_mv = args.steps if moving_headline else max(60, min(args.steps, 200))
         mv_ticks, mv_clouds = moving_inputs(scenes, sc, n_mv + 10)
         for k in range(10):
             lp.tick(name, mv_ticks[k])
@@ -493,41 +550,48 @@ def main():
             t_ticks += time.perf_counter() - t1
             n_sum += int(mv_res.n_samples)
         t_mv = time.perf_counter() - t0
-        mo = _oracle.tick(theory, mv_clouds[which], sc.plan, mv_ticks[n_mv + 9], n_threads=os.cpu_count() or 1).result
-        mv_ok = bool(mv_res.planner_state == mo.planner_state and int(mv_res.best_index) == int(mo.best_index) and
-                     abs(mv_res.vx - mo.vx) <= 1e-4 and abs(mv_res.vy - mo.vy) <= 1e-4 and abs(mv_res.wz - mo.wz) <= 1e-4 and
-                     (mv_res.best_index < 0 or abs(mv_res.best_cost - mo.best_cost) <= 1e-4))
+        if moving_headline and args.dump_outputs:
+            dump_outputs(np, args.dump_outputs, lp, mv_res)
+        mv_ok, mo_best = None, None
+        if args.full:
+            import oracle as _oracle
+            mo = _oracle.tick(theory, mv_clouds[which], sc.plan, mv_ticks[n_mv + 9], n_threads=os.cpu_count() or 1).result
+            mv_ok = bool(mv_res.planner_state == mo.planner_state and int(mv_res.best_index) == int(mo.best_index) and
+                         abs(mv_res.vx - mo.vx) <= 1e-4 and abs(mv_res.vy - mo.vy) <= 1e-4 and abs(mv_res.wz - mo.wz) <= 1e-4 and
+                         (mv_res.best_index < 0 or abs(mv_res.best_cost - mo.best_cost) <= 1e-4))
+            mo_best = int(mo.best_index)
         extras["moving"] = {
             "value": round(n_sum / t_mv, 1), "ticks_only_value": round(n_sum / t_ticks, 1), "unit": "trajectories/s",
             "ticks": n_mv, "ms_per_tick": round(t_mv / n_mv * 1e3, 5), "ms_per_tick_ticks_only": round(t_ticks / n_mv * 1e3, 5),
             "mean_trajectories_per_tick": round(n_sum / n_mv, 1), "cloud_replaced_every": args.replace_every,
-            "last_tick_matches_oracle": mv_ok, "last_tick_best_index": int(mv_res.best_index), "oracle_best_index": int(mo.best_index),
+            "last_tick_matches_oracle": mv_ok, "last_tick_best_index": int(mv_res.best_index), "oracle_best_index": mo_best,
             "note": "pose / twist advance along the prune plan every tick; set_cloud (H2D of the other cloud variant) every "
                     f"{args.replace_every} ticks is inside `value`, outside `ticks_only_value`"}
         lp.set_cloud(sc.cloud)
-        # (b) end to end through the host boundary: the reference re-aggregates the cloud every tick
-        #     (local_planner.cpp:498-511), so: set_cloud from pageable 32-byte pcl::PointXYZI records + tick + result
-        xyzi32 = np.zeros((len(sc.cloud), 8), np.float32)
-        xyzi32[:, :4] = sc.cloud
-        for _ in range(3):
-            lp.set_cloud(xyzi32); lp.tick(name, sc.tick)
-        n_e2e = 30
-        t_set = 0.0
-        t0 = time.perf_counter()
-        for _ in range(n_e2e):
-            t1 = time.perf_counter()
-            lp.set_cloud(xyzi32)
-            t_set += time.perf_counter() - t1
-            e_res = lp.tick(name, sc.tick)
-        t_e2e = (time.perf_counter() - t0) / n_e2e
-        extras["end_to_end"] = {
-            "ms": round(t_e2e * 1e3, 5), "value": round(int(e_res.n_samples) / t_e2e, 1), "unit": "trajectories/s",
-            "set_cloud_ms": round(t_set / n_e2e * 1e3, 5), "cloud_bytes": int(xyzi32.nbytes),
-            "what": "set_cloud from pageable host memory, 32-byte pcl::PointXYZI records (repack + H2D) + tick + result on the host, every tick"}
-        lp.set_cloud(sc.cloud)
-        lp.tick(name, sc.tick)
-        # (c) the sizes the reference ships (55 / 275 / 2 x 126), warm and after 100 ms of idling
-        extras["shipped_tick_latency"] = shipped_latencies(np, scenes, configs, LocalPlanner, gpu)
+        if args.full:
+            # (b) end to end through the host boundary: the reference re-aggregates the cloud every tick
+            #     (local_planner.cpp:498-511), so: set_cloud from pageable 32-byte pcl::PointXYZI records + tick + result
+            xyzi32 = np.zeros((len(sc.cloud), 8), np.float32)
+            xyzi32[:, :4] = sc.cloud
+            for _ in range(3):
+                lp.set_cloud(xyzi32); lp.tick(name, sc.tick)
+            n_e2e = 30
+            t_set = 0.0
+            t0 = time.perf_counter()
+            for _ in range(n_e2e):
+                t1 = time.perf_counter()
+                lp.set_cloud(xyzi32)
+                t_set += time.perf_counter() - t1
+                e_res = lp.tick(name, sc.tick)
+            t_e2e = (time.perf_counter() - t0) / n_e2e
+            extras["end_to_end"] = {
+                "ms": round(t_e2e * 1e3, 5), "value": round(int(e_res.n_samples) / t_e2e, 1), "unit": "trajectories/s",
+                "set_cloud_ms": round(t_set / n_e2e * 1e3, 5), "cloud_bytes": int(xyzi32.nbytes),
+                "what": "set_cloud from pageable host memory, 32-byte pcl::PointXYZI records (repack + H2D) + tick + result on the host, every tick"}
+            lp.set_cloud(sc.cloud)
+            lp.tick(name, sc.tick)
+            # (c) the sizes the reference ships (55 / 275 / 2 x 126), warm and after 100 ms of idling
+            extras["shipped_tick_latency"] = shipped_latencies(np, scenes, configs, LocalPlanner, gpu)
 
     rank_info = None
     if world > 1:
@@ -543,89 +607,91 @@ def main():
 
     out = None
     if rank == 0:
-        import oracle
         ncpu = os.cpu_count() or 1
         ocloud = sc.cloud
         if scans is not None:       # the cloud the last tick actually scored
             ocloud = np.ascontiguousarray(lp.get_cloud())
-        # ---- parity spot check of what was just timed: the oracle on the WHOLE batch ----
-        ofull = oracle.tick(theory, ocloud, sc.plan, sc.tick, n_threads=ncpu)
-        rf = ofull.result
-        same_index = int(res.best_index) == int(rf.best_index)
-        near_tie = (not same_index and res.best_index >= 0 and rf.best_index >= 0 and
-                    abs(res.best_cost - rf.best_cost) <= 1e-6)
-        # strict: the same winner AND its command / cost within 1e-4 (a near-tie that picked another index is reported
-        # by winner_near_tie_within_1e-6 alone, never as a match)
-        parity_ok = bool(res.planner_state == rf.planner_state and same_index and
-                         abs(res.vx - rf.vx) <= 1e-4 and abs(res.vy - rf.vy) <= 1e-4 and abs(res.wz - rf.wz) <= 1e-4 and
-                         (res.best_index < 0 or abs(res.best_cost - rf.best_cost) <= 1e-4))
-        # ---- roofline of the dominant kernel (k_score) ----
-        # (a) HBM roofline with the bytes THIS kernel must move once (compulsory traffic): the
-        #     rollout state it reads (24 B per trajectory-step), the cell-sorted tile points (12 B),
-        #     the row-run index, headers in / costs, steps, samples, load out (32 + 32 B per trajectory).
-        # (b) SURVEY 8d's reference-equivalent gather bytes (32 per evaluated step + 16 per
-        #     radius-search neighbour the reference materialises), which this design never moves:
-        #     reported as a work rate, NOT as a fraction of HBM (it exceeded 1 in round 1).
-        b0, e0 = sharding.shard_range(0, world, n_global)
-        o = ofull if world == 1 else oracle.tick(theory, ocloud, sc.plan, sc.tick, begin=b0, end=e0, n_threads=ncpu)
-        r = o.result
-        units = int(r.steps_total)                         # trajectory-steps per launch (rank 0's shard)
-        n_tile = int(lp.last_result.n_points_binned)
-        compulsory = 24 * units + 12 * n_tile + 4 * 4096 + 64 * n_local + 16 * len(sc.plan)
-        ref_bytes = 32 * int(r.steps_eval) + 16 * int(r.k_sum) + 16 * len(ocloud) + 32 * len(sc.plan) + 32 * n_local   # SURVEY 8d B_alg, 16 P included
-        k_ms = float(np.mean(score_ms)) if score_ms else float("nan")
-        t_ms = float(np.mean(dev_ms)) if dev_ms else float("nan")
-        achieved = compulsory / (k_ms * 1e-3) / 1e9
-        prof = {}
-        prof_src = {}
-        for fn, cands in (("traffic.json", ("traffic.json",)), ("pmc.json", ("r03_pmc.json", "r02_pmc.json")),
-                          ("kernel_avg.json", ("r03_kernel_avg.json", "r02_kernel_avg.json"))):
-            prof[fn] = {}
-            for cand in cands:                                # the newest round's table that has this workload
-                pth = os.path.join(ROOT, "profiles", cand)
-                if not os.path.exists(pth):
-                    continue
-                try:
-                    got = json.load(open(pth)).get(f"{workload}" if layout == scenes.DEFAULT_LAYOUT else f"{workload}_{layout}", {})
-                except Exception:
-                    got = {}
-                if got:
-                    prof[fn], prof_src[fn] = got, "profiles/" + cand
-                    break
-        traffic = prof.get("traffic.json", {}).get("k_score_hbm_bytes_per_launch") if world == 1 else None
-        pmc = prof.get("pmc.json", {})
-        roofline = {
-            "bound": "hbm", "kernel": "k_score",
-            "achieved": round(achieved, 2), "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 4),
-            "traffic": traffic,
-            "traffic_static": {"static": True, "source": "profiles/traffic.json (PMC passes of an earlier run of this workload, not this run)"},
-            # SURVEY 8d's own fraction: B_alg (what the reference's radius searches gather: 32 B per evaluated step + 16 B per
-            # neighbour + 16 P + 32 M + 32 N) over the tick / the kernel, / 8 TB/s.  A work rate against the HBM peak: this
-            # design never moves those bytes (frac above is the physical one).
-            "frac_alg_tick": round(ref_bytes / (elapsed / args.steps) / 8.0e12, 4),
-            "frac_alg_kernel": round(ref_bytes / (k_ms * 1e-3) / 8.0e12, 4) if k_ms == k_ms else None,
-            "b_alg_bytes": ref_bytes,
-            "bytes_per_launch": compulsory, "units_per_launch": units,
-            "bytes_per_unit": round(compulsory / max(units, 1), 2),
-            "kernel_ms": round(k_ms, 5), "kernel_ms_rocprofv3": prof.get("kernel_avg.json", {}).get("k_score_ms"),
-            "kernel_ms_rocprofv3_static": True, "kernel_ms_rocprofv3_source": prof_src.get("kernel_avg.json"),
-            "tick_device_ms": round(t_ms, 5),
-            "what_binds_it": {
-                "name": "VALU issue + memory/LDS latency (not HBM: the working set is L2/MALL resident)",
-                "valu_busy_frac_of_issue_cycles": pmc.get("valu_busy_frac"),
-                "waves_waiting_frac": pmc.get("waves_waiting_frac"),
-                "static": True, "source": (prof_src.get("pmc.json", "") + " (an earlier run, not this one)") if pmc else None},
-            "stream_ceiling": ceiling,
-            "frac_of_copy_ceiling": round(achieved / ceiling["copy_GBps"], 4) if ceiling else None,
-            "reference_equivalent_gather": {
-                "bytes_per_launch": ref_bytes, "bytes_per_unit": round(ref_bytes / max(units, 1), 2),
-                "GBps": round(ref_bytes / (k_ms * 1e-3) / 1e9, 1),
-                "note": "SURVEY 8d B_alg (k_sum radius-search neighbours x 16 B + 32 B per evaluated step): what the "
-                        "reference's kd-tree gathers would stream; the grid walk never materialises them, so this "
-                        "is a work rate and may exceed the HBM peak"},
-        }
-        cpu = None
-        if world == 1 and not args.no_cpu_baseline and scans is None:
+        rf, parity_ok, near_tie, roofline, cpu, colliding = None, None, None, None, None, None
+        if args.full:
+            import oracle
+            # ---- parity spot check of what was just timed: the oracle on the WHOLE batch ----
+            ofull = oracle.tick(theory, ocloud, sc.plan, sc.tick, n_threads=ncpu)
+            rf = ofull.result
+            same_index = int(res.best_index) == int(rf.best_index)
+            near_tie = (not same_index and res.best_index >= 0 and rf.best_index >= 0 and
+                        abs(res.best_cost - rf.best_cost) <= 1e-6)
+            # strict: the same winner AND its command / cost within 1e-4 (a near-tie that picked another index is reported
+            # by winner_near_tie_within_1e-6 alone, never as a match)
+            parity_ok = bool(res.planner_state == rf.planner_state and same_index and
+                             abs(res.vx - rf.vx) <= 1e-4 and abs(res.vy - rf.vy) <= 1e-4 and abs(res.wz - rf.wz) <= 1e-4 and
+                             (res.best_index < 0 or abs(res.best_cost - rf.best_cost) <= 1e-4))
+            # ---- roofline of the dominant kernel (k_score) ----
+            # (a) HBM roofline with the bytes THIS kernel must move once (compulsory traffic): the
+            #     rollout state it reads (24 B per trajectory-step), the cell-sorted tile points (12 B),
+            #     the row-run index, headers in / costs, steps, samples, load out (32 + 32 B per trajectory).
+            # (b) SURVEY 8d's reference-equivalent gather bytes (32 per evaluated step + 16 per
+            #     radius-search neighbour the reference materialises), which this design never moves:
+            #     reported as a work rate, NOT as a fraction of HBM (it exceeded 1 in round 1).
+            b0, e0 = sharding.shard_range(0, world, n_global)
+            o = ofull if world == 1 else oracle.tick(theory, ocloud, sc.plan, sc.tick, begin=b0, end=e0, n_threads=ncpu)
+            r = o.result
+            units = int(r.steps_total)                         # trajectory-steps per launch (rank 0's shard)
+            n_tile = int(lp.last_result.n_points_binned)
+            compulsory = 24 * units + 12 * n_tile + 4 * 4096 + 64 * n_local + 16 * len(sc.plan)
+            ref_bytes = 32 * int(r.steps_eval) + 16 * int(r.k_sum) + 16 * len(ocloud) + 32 * len(sc.plan) + 32 * n_local   # SURVEY 8d B_alg, 16 P included
+            k_ms = float(np.mean(score_ms)) if score_ms else float("nan")
+            t_ms = float(np.mean(dev_ms)) if dev_ms else float("nan")
+            achieved = compulsory / (k_ms * 1e-3) / 1e9
+            prof = {}
+            prof_src = {}
+            for fn, cands in (("traffic.json", ("traffic.json",)), ("pmc.json", ("r03_pmc.json", "r02_pmc.json")),
+                              ("kernel_avg.json", ("r03_kernel_avg.json", "r02_kernel_avg.json"))):
+                prof[fn] = {}
+                for cand in cands:                                # the newest round's table that has this workload
+                    pth = os.path.join(ROOT, "profiles", cand)
+                    if not os.path.exists(pth):
+                        continue
+                    try:
+                        got = json.load(open(pth)).get(f"{workload}" if layout == scenes.DEFAULT_LAYOUT else f"{workload}_{layout}", {})
+                    except Exception:
+                        got = {}
+                    if got:
+                        prof[fn], prof_src[fn] = got, "profiles/" + cand
+                        break
+            traffic = prof.get("traffic.json", {}).get("k_score_hbm_bytes_per_launch") if world == 1 else None
+            pmc = prof.get("pmc.json", {})
+            roofline = {
+                "bound": "hbm", "kernel": "k_score",
+                "achieved": round(achieved, 2), "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 4),
+                "traffic": traffic,
+                "traffic_static": {"static": True, "source": "profiles/traffic.json (PMC passes of an earlier run of this workload, not this run)"},
+                # SURVEY 8d's own fraction: B_alg (what the reference's radius searches gather: 32 B per evaluated step + 16 B per
+                # neighbour + 16 P + 32 M + 32 N) over the tick / the kernel, / 8 TB/s.  A work rate against the HBM peak: this
+                # design never moves those bytes (frac above is the physical one).
+                "frac_alg_tick": round(ref_bytes / (elapsed / args.steps) / 8.0e12, 4),
+                "frac_alg_kernel": round(ref_bytes / (k_ms * 1e-3) / 8.0e12, 4) if k_ms == k_ms else None,
+                "b_alg_bytes": ref_bytes,
+                "bytes_per_launch": compulsory, "units_per_launch": units,
+                "bytes_per_unit": round(compulsory / max(units, 1), 2),
+                "kernel_ms": round(k_ms, 5), "kernel_ms_rocprofv3": prof.get("kernel_avg.json", {}).get("k_score_ms"),
+                "kernel_ms_rocprofv3_static": True, "kernel_ms_rocprofv3_source": prof_src.get("kernel_avg.json"),
+                "tick_device_ms": round(t_ms, 5),
+                "what_binds_it": {
+                    "name": "VALU issue + memory/LDS latency (not HBM: the working set is L2/MALL resident)",
+                    "valu_busy_frac_of_issue_cycles": pmc.get("valu_busy_frac"),
+                    "waves_waiting_frac": pmc.get("waves_waiting_frac"),
+                    "static": True, "source": (prof_src.get("pmc.json", "") + " (an earlier run, not this one)") if pmc else None},
+                "stream_ceiling": ceiling,
+                "frac_of_copy_ceiling": round(achieved / ceiling["copy_GBps"], 4) if ceiling else None,
+                "reference_equivalent_gather": {
+                    "bytes_per_launch": ref_bytes, "bytes_per_unit": round(ref_bytes / max(units, 1), 2),
+                    "GBps": round(ref_bytes / (k_ms * 1e-3) / 1e9, 1),
+                    "note": "SURVEY 8d B_alg (k_sum radius-search neighbours x 16 B + 32 B per evaluated step): what the "
+                            "reference's kd-tree gathers would stream; the grid walk never materialises them, so this "
+                            "is a work rate and may exceed the HBM peak"},
+            }
+            colliding = float((ofull.costs == -1.0).mean())
+        if world == 1 and args.full and not args.no_cpu_baseline and scans is None:
             # the oracle ("port"), ONE core like the reference's loops A and B
             # (local_planner.cpp:549-557, 456-469); median tick of a bounded sample
             for _ in range(1 if base in ("C3", "C3P", "C4") else 3):
@@ -652,7 +718,7 @@ def main():
                    "rollout_ms": round(median(gen) * 1e3, 2), "scoring_ms": round(median(scr) * 1e3, 2),
                    "all_cores_value": round(n_global / median(alls), 1), "all_cores": ncpu,
                    "all_cores_note": "rollout + scoring threaded over trajectories, kd-tree build serial"}
-        if world == 1 and not args.no_cpu_baseline and scans is not None:
+        if world == 1 and args.full and not args.no_cpu_baseline and scans is not None:
             # C5 / C5M: the oracle's whole step on ONE core -- cbSensor feed (crop + VoxelGrid) + [selfClear / selfMark of the
             # marking layer] + the C2 tick on the resulting cloud -- over the same scans, a bounded sample
             mo = None
@@ -682,7 +748,6 @@ def main():
                    "step_ms": round(median(steps_cpu) * 1e3, 2), "feed_ms": round(median(t_feed) * 1e3, 2),
                    "marking_update_ms": round(median(t_mark) * 1e3, 2) if mo is not None else None,
                    "tick_ms": round(median(t_tick) * 1e3, 2)}
-        colliding = float((ofull.costs == -1.0).mean())
         out = {
             "metric": "scored trajectories/sec (N_traj x N_steps)", "value": round(value, 1),
             "unit": "trajectories/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -692,7 +757,7 @@ def main():
                                    f"{len(ocloud)}-point cloud, {len(sc.plan)}-pose prune plan, shipped critic stack"
                                    + (", 16x1800 LiDAR scan -> set_scan (voxel-hash feed) fused into every step" if scans is not None else "")
                                    + (" + global-mode mark/clear layer on the same scan" if marking is not None else ""),
-                       "scene_layout": layout, "colliding_share": round(colliding, 4),
+                       "scene_layout": layout, "colliding_share": None if colliding is None else round(colliding, 4),
                        "trajectories_per_gpu": n_local, "steps_per_trajectory": n_steps_traj,
                        "trajectory_steps_per_s": round(value * n_steps_traj, 1),
                        "parallelism": f"traj-shard x{world}" if world > 1 else ("single" if len(lps) == 1 else f"{len(lps)} independent contexts on one GPU, one tick in flight each"),
@@ -703,11 +768,11 @@ def main():
                            + f", {16 * world} bytes per tick (cost bits, -index per rank)"),
                        "sync_tick_latency_ms": None if sync_ms is None else round(sync_ms, 5),
                        "cmd_vel": [res.vx, res.vy, res.wz], "best_index": int(res.best_index),
-                       "oracle_best_index": int(rf.best_index),
-                       "cmd_vel_matches_oracle": parity_ok, "winner_near_tie_within_1e-6": bool(near_tie)},
+                       "oracle_best_index": None if rf is None else int(rf.best_index),
+                       "cmd_vel_matches_oracle": parity_ok, "winner_near_tie_within_1e-6": None if near_tie is None else bool(near_tie)},
             "roofline": roofline, "cpu_baseline": cpu,
         }
-        if marking is not None:
+        if marking is not None and args.full:
             ms = marking_summary
             ms["schedule"] = args.marking_schedule
             ms["serial_schedule_ms_per_step"] = round(serial_ms, 5)
@@ -740,11 +805,11 @@ def main():
                                            "distinct_gpus": len({g["pci"] for g in rank_info}),
                                            "inlib_communicator_ranks": lp.comm_ranks() if reduce_mode == "inlib" else None}
 
-    # ---- the in-library RCCL exchange, measured after the timed loop (`--reduce auto`, RCCL backend) ----
+    # ---- the in-library RCCL exchange, measured after the timed loop (`--reduce auto`, RCCL backend, --full) ----
     # k_score -> ncclAllReduce(min) -> k_resolve on the tick's stream: the synchronous tick a C++ host gets without
     # any collective code of its own.  A watchdog prints the line gathered so far and leaves if the bootstrap or a
     # collective never returns (first use of this path on a multi-GPU node).
-    if world > 1 and reduce_mode == "torch" and args.reduce == "auto" and args.backend == "nccl":
+    if world > 1 and args.full and reduce_mode == "torch" and args.reduce == "auto" and args.backend == "nccl":
         import threading
         done = threading.Event()
 
