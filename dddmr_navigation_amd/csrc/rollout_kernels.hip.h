@@ -536,7 +536,9 @@ __device__ __forceinline__ void rollout_block(const DevTick& k, const int block,
       if (k.max_vel_x >= 0 && vmag - eps > k.max_vel_x) ok = false;
     } else if (omni) {
       // omni_simple_trajectory_generator_theory.cpp:387-411
-      vmag = hypot((double)vx, (double)vy);
+      // `hypot(float, float)` there resolves to the float overload (<math.h> via tf2: ASSUMPTIONS.md row 18): glibc's
+      // hypotf, i.e. the double sqrt of the exact double sum of squares, rounded to float
+      vmag = (double)(float)sqrt((double)vx * (double)vx + (double)vy * (double)vy);
       if ((k.min_vel_trans >= 0 && vmag + eps < k.min_vel_trans) &&
           (k.min_vel_theta >= 0 && fabs((double)w) + eps < k.min_vel_theta)) ok = false;
       if (k.max_vel_trans >= 0 && vmag - eps > k.max_vel_trans) ok = false;

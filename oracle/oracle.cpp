@@ -6,9 +6,14 @@
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg may use it, and only
  * as the checker / reported baseline.
  *
- * PARITY UNPINNED: the reference has no tests, fixtures or golden vectors for
- * this path and cannot be built here (needs ROS 2 Humble,
- * PCL 1.15, FLANN, Eigen, tf2 -- none present, no network).  This file is a
+ * PINNED to the reference's own code: oracle/ref/ compiles the reference's
+ * theories, base_trajectory, critics, StackedScoringModel, VelocityIterator and
+ * DynamicGraph against small stand-ins for rclcpp / pluginlib / Eigen / tf2 /
+ * PCL, and tests/test_reference_pin_cpu.py holds this file to it bit for bit
+ * (tests/golden/REF_*.npz carry the recorded outputs).  Pinned under the
+ * stand-ins' stated library semantics; NOT pinned: those semantics themselves
+ * (oracle/ASSUMPTIONS.md rows 1-18), the perception plugins and the argmin of
+ * local_planner.cpp.  This file is a
  * literal restatement of the cited reference source with the reference's mixed
  * float/double arithmetic; the third-party arithmetic it depends on (Eigen
  * Affine3d/AngleAxisd/Quaterniond, PCL transformPointCloud / KdTreeFLANN,
@@ -191,7 +196,10 @@ static bool generate_trajectory(const dddmr_theory_config& c, const dddmr_tick_i
       return false;
     if (c.max_vel_x >= 0 && vmag - eps > c.max_vel_x) return false;
   } else if (c.kind == DDDMR_THEORY_OMNI_SIMPLE) {
-    vmag = std::hypot((double)sv0, (double)sv1);
+    // omni_simple...cpp:387 `hypot(sample_target_vel[0], sample_target_vel[1])`: float arguments, and <math.h> (via
+    // tf2/LinearMath/Scalar.h) brings the float overload into the global namespace, so vmag is a FLOAT hypot widened
+    // to double (ASSUMPTIONS.md row 18; found by the reference pin).
+    vmag = (double)std::hypot(sv0, sv1);
     if ((c.min_vel_trans >= 0 && vmag + eps < c.min_vel_trans) &&
         (c.min_vel_theta >= 0 && std::fabs((double)sv2) + eps < c.min_vel_theta))
       return false;

@@ -66,6 +66,10 @@ int oracle_marking_update(oracle_marking* m, const float* obs_gbl_xyz, size_t n,
 size_t oracle_marking_get_voxels(oracle_marking* m, int32_t* xyz_out, size_t capacity);
 size_t oracle_marking_get_points(oracle_marking* m, float* xyz_out, int32_t* voxel_out, size_t capacity);
 size_t oracle_marking_get_dgraph(oracle_marking* m, double* out, size_t capacity);
+/* trace of DynamicGraph calls (op, key, value) since oracle_marking_trace_dgraph(m, 1); op 0 = initial(n, value),
+   1 = setValue, 2 = clearValue.  Enabling it first records initial(n, max) (the graph must then be in that state). */
+void oracle_marking_trace_dgraph(oracle_marking* m, int on);
+size_t oracle_marking_get_dgraph_trace(oracle_marking* m, double* out, size_t capacity);
 size_t oracle_marking_get_lethal(oracle_marking* m, uint8_t* flags, size_t capacity);
 size_t oracle_marking_get_decisions(oracle_marking* m, int which, int32_t* voxels, float* margins, uint8_t* flags,
                                     size_t capacity);

@@ -115,12 +115,15 @@ inline Affine inverse(const Affine& A) {
   cof[0][0] = m[1][1] * m[2][2] - m[1][2] * m[2][1];
   cof[1][0] = m[1][2] * m[2][0] - m[1][0] * m[2][2];
   cof[2][0] = m[1][0] * m[2][1] - m[1][1] * m[2][0];
-  const double det = m[0][0] * cof[0][0] + m[0][1] * cof[1][0] + m[0][2] * cof[2][0];
-  const double invdet = 1.0 / det;
   cof[0][1] = m[0][2] * m[2][1] - m[0][1] * m[2][2];
+  cof[0][2] = m[0][1] * m[1][2] - m[0][2] * m[1][1];
+  // Eigen expands the determinant down the FIRST COLUMN (cofactors_col0 . matrix.col(0)), not along the first row:
+  // the row expansion differs in the last ulp, which the reference pin found in the pure-pursuit distance
+  // 
+  const double det = cof[0][0] * m[0][0] + cof[0][1] * m[1][0] + cof[0][2] * m[2][0];
+  const double invdet = 1.0 / det;
   cof[1][1] = m[0][0] * m[2][2] - m[0][2] * m[2][0];
   cof[2][1] = m[0][1] * m[2][0] - m[0][0] * m[2][1];
-  cof[0][2] = m[0][1] * m[1][2] - m[0][2] * m[1][1];
   cof[1][2] = m[0][2] * m[1][0] - m[0][0] * m[1][2];
   cof[2][2] = m[0][0] * m[1][1] - m[0][1] * m[1][0];
   for (int i = 0; i < 3; ++i)

@@ -162,6 +162,11 @@ struct oracle_marking {
   std::vector<float> ground, map_pts;      // xyz
   KdTree kd_ground, kd_map;
   std::vector<double> dgraph;              // DynamicGraph::graph_, keys 0..n_ground
+  // optional record of the DynamicGraph calls the restatement stands for, (op, key, value) per call with op
+  // 0 = initial(key = n, value), 1 = setValue, 2 = clearValue (tests/test_reference_pin_cpu.py replays it into the
+  // reference class)
+  bool trace_on = false;
+  std::vector<double> dgraph_trace;
   std::map<int, double> lethal_map;
   std::map<int, std::map<int, std::map<int, PerMarking>>> marking;
   std::vector<float> obs_prev;             // pcl_msg_gbl_ of the last selfMark (xyz)
@@ -273,6 +278,13 @@ void min_distance_to_ground_nodes(const oracle_marking& M, const std::vector<F4>
   }
 }
 
+void trace_dgraph(oracle_marking& M, int op, size_t key, double value) {
+  if (!M.trace_on) return;
+  M.dgraph_trace.push_back(op);
+  M.dgraph_trace.push_back((double)key);
+  M.dgraph_trace.push_back(value);
+}
+
 void add_pc(oracle_marking& M, double cx, double cy, double cz, const std::vector<F4>& pc, const float mc[4]) {
   const int x = (int)(cx / M.cfg.xy_resolution), y = (int)(cy / M.cfg.xy_resolution), z = (int)(cz / M.cfg.height_resolution);
   PerMarking& pm = M.marking[x][y][z];
@@ -284,6 +296,7 @@ void add_pc(oracle_marking& M, double cx, double cy, double cz, const std::vecto
   pm.nodes_of_min_distance = nodes;
   for (const auto& kv : nodes) {
     M.dgraph[(size_t)kv.first] = std::min(M.dgraph[(size_t)kv.first], (double)kv.second);   // DynamicGraph::setValue
+    trace_dgraph(M, 1, (size_t)kv.first, (double)kv.second);
     if (kv.second <= M.cfg.inscribed_radius) M.lethal_map[kv.first] = kv.second;
   }
 }
@@ -291,6 +304,7 @@ void add_pc(oracle_marking& M, double cx, double cy, double cz, const std::vecto
 void remove_pc(oracle_marking& M, PerMarking& pm) {
   for (const auto& kv : pm.nodes_of_min_distance) {
     M.dgraph[(size_t)kv.first] = 9999.0;                         // DynamicGraph::clearValue(key, 9999.0)
+    trace_dgraph(M, 2, (size_t)kv.first, 9999.0);
     if (kv.second <= M.cfg.inscribed_radius) M.lethal_map.erase(kv.first);
   }
   pm.has_pc = false;
@@ -525,6 +539,19 @@ void oracle_marking_reset(oracle_marking* M) {
   M->marking.clear();
   M->lethal_map.clear();
   M->dgraph.assign(M->dgraph.size(), M->cfg.max_obstacle_distance);
+  trace_dgraph(*M, 0, M->dgraph.size() - 1, M->cfg.max_obstacle_distance);
+}
+
+void oracle_marking_trace_dgraph(oracle_marking* M, int on) {
+  M->trace_on = on != 0;
+  M->dgraph_trace.clear();
+  if (M->trace_on) trace_dgraph(*M, 0, M->dgraph.size() - 1, M->cfg.max_obstacle_distance);  // the state so far
+}
+
+size_t oracle_marking_get_dgraph_trace(oracle_marking* M, double* out, size_t capacity) {
+  const size_t n = M->dgraph_trace.size() / 3;
+  if (out) std::memcpy(out, M->dgraph_trace.data(), 3 * std::min(n, capacity) * sizeof(double));
+  return n;
 }
 
 // One StackedPerception::doClear_then_Mark pass of the lidar plugin (stacked_perception.cpp:72-90):

@@ -192,6 +192,9 @@ class MarkingOracle:
             f.restype = C.c_size_t
         lib.oracle_marking_get_decisions.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         lib.oracle_marking_get_decisions.restype = C.c_size_t
+        lib.oracle_marking_trace_dgraph.argtypes = [C.c_void_p, C.c_int]
+        lib.oracle_marking_get_dgraph_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.oracle_marking_get_dgraph_trace.restype = C.c_size_t
         self._lib = lib
         g = np.ascontiguousarray(ground, dtype=np.float32)
         m = np.ascontiguousarray(static_map, dtype=np.float32)
@@ -211,6 +214,17 @@ class MarkingOracle:
 
     def reset(self):
         self._lib.oracle_marking_reset(self._h)
+
+    def trace_dgraph(self, on: bool = True):
+        """Record the DynamicGraph calls from here on (the graph must be in its initial state)."""
+        self._lib.oracle_marking_trace_dgraph(self._h, int(on))
+
+    def dgraph_trace(self) -> np.ndarray:
+        """-> [T, 3] float64 (op, key, value): op 0 = initial(n = key, value), 1 = setValue, 2 = clearValue."""
+        n = self._lib.oracle_marking_get_dgraph_trace(self._h, None, 0)
+        out = np.zeros((max(n, 1), 3), dtype=np.float64)
+        self._lib.oracle_marking_get_dgraph_trace(self._h, _ptr(out), n)
+        return out[:n]
 
     def update(self, obs_gbl_xyz: np.ndarray, T_base_sensor, T_gbl_base) -> K.MarkingStats:
         obs = np.ascontiguousarray(np.asarray(obs_gbl_xyz, dtype=np.float32)[:, :3])

@@ -1,9 +1,14 @@
 """Generates tests/golden/*.npz from the CPU oracle (oracle/oracle.cpp).
 
-PARITY UNPINNED: the reference holds no golden vectors for this path and cannot
-be built here, so these vectors are outputs of the build's own restatement of
-the cited reference source, frozen so that (a) the oracle cannot drift silently
-and (b) the HIP path is checked against bytes committed to the repo.  Inputs
+These vectors are outputs of the oracle, the build's own restatement of the
+cited reference source, frozen so that (a) the oracle cannot drift silently and
+(b) the HIP path is checked against bytes committed to the repo.  The oracle's
+rollout logic is pinned to the reference's own code compiled with library
+stand-ins (tests/test_reference_pin_cpu.py; recorded reference outputs in
+REF_*.npz, make_ref_golden.py); the library semantics themselves are not
+(oracle/ASSUMPTIONS.md).  F9 was regenerated when the pin found the oracle's
+3x3 determinant expanded along the first row where Eigen expands down the
+first column.  Inputs
 are the deterministic scenes of dddmr_navigation_amd/scenes.py (F1 = the
 reference's playground scenario, local_planner_play_ground_node.cpp:206-298).
 

@@ -1,0 +1,469 @@
+"""The oracle against the reference's own rollout code, compiled from a reference checkout (`make -C oracle ref`:
+theories, base_trajectory, the seven critics, StackedScoringModel, VelocityIterator, DynamicGraph) against the
+library stand-ins of oracle/ref/shim/, at -O0 and -O2.  Bit equality throughout: what is pinned is the oracle's
+restatement of the reference's logic, under the stand-ins' stated library semantics (oracle/ASSUMPTIONS.md)."""
+import math
+
+import numpy as np
+import pytest
+
+from dddmr_navigation_amd import _capi as K, configs, scenes
+import oracle
+from oracle import ref_py as R
+
+@pytest.fixture(params=R.BUILDS)
+def build(request):
+    if not R.available():
+        pytest.skip("no compiled reference and no reference checkout: run `make -C oracle ref REFERENCE=<checkout>`")
+    R.load(request.param)
+    return request.param
+
+
+def reference_semantics(th):
+    """The reference has no bench-mode extensions: compare with them off."""
+    th.bench_fixed_steps = 0
+    th.bench_no_zero_insert = 0
+    return th
+
+
+# ---- VelocityIterator ---------------------------------------------------------
+def test_velocity_iterator(build):
+    rng = np.random.default_rng(11)
+    cases = [(0.0, 0.0, 3), (-1.0, 1.0, 0), (-1.0, 1.0, 1), (-1.0, 1.0, 2), (-0.3, 0.3, 10), (-0.7, -0.1, 4),
+             (0.2, 0.2, 0), (-0.2, -0.2, 5), (1.0, -1.0, 5), (-0.1, 0.0, 3), (0.0, 0.5, 3)]
+    for _ in range(100_000):
+        kind = rng.integers(0, 4)
+        a, b = rng.uniform(-2, 2, 2)
+        if kind == 1:
+            b = a                                   # min == max
+        elif kind == 2:
+            a, b = -abs(a), -abs(b) * 0.5           # all negative
+        elif kind == 3:
+            a, b = -abs(a), abs(b)                  # straddles 0
+        cases.append((float(a), float(b), int(rng.integers(0, 12))))
+    for mn, mx, n in cases:
+        r = R.velocity_iterator(mn, mx, n, build=build)
+        o = oracle.velocity_iterator(mn, mx, n)
+        assert np.array_equal(r, o), (mn, mx, n)
+
+
+# ---- generation -----------------------------------------------------------------
+def _random_theory(rng, kind):
+    kw = dict(min_vel_x=float(rng.uniform(-0.5, 0.3)), max_vel_x=float(rng.uniform(0.1, 1.5)),
+              min_vel_y=float(rng.uniform(-1, 0)), max_vel_y=float(rng.uniform(0, 1)),
+              min_vel_trans=float(rng.uniform(0, 0.3)), max_vel_trans=float(rng.uniform(0.3, 1.5)),
+              min_vel_theta=float(rng.uniform(0, 0.5)), max_vel_theta=float(rng.uniform(0.1, 1.5)),
+              acc_lim_x=float(rng.uniform(0.1, 3)), acc_lim_y=float(rng.uniform(0.1, 3)),
+              acc_lim_theta=float(rng.uniform(0.1, 5)), deceleration_ratio=float(rng.uniform(1, 5)),
+              use_motor_constraint=int(rng.integers(0, 2)), max_motor_shaft_rpm=float(rng.uniform(300, 4000)),
+              wheel_diameter=float(rng.uniform(0.1, 0.3)), gear_ratio=float(rng.uniform(10, 40)),
+              robot_radius=float(rng.uniform(0.1, 0.5)), controller_frequency=float(rng.uniform(5, 20)),
+              sim_time=float(rng.uniform(0.5, 3)), linear_x_sample=float(rng.integers(0, 8)),
+              linear_y_sample=float(rng.integers(0, 6)), angular_z_sample=float(rng.integers(0, 8)),
+              sim_granularity=float(rng.uniform(0.02, 0.2)), angular_sim_granularity=float(rng.uniform(0.02, 0.2)),
+              rotation_speed=float(rng.uniform(0.1, 1.5)))
+    return configs.theory(f"random_{kind}", kind, configs.shipped_dd_critics(), **kw)
+
+
+def _random_tick(rng):
+    yaw = float(rng.choice([rng.uniform(-math.pi, math.pi), math.pi - 1e-7, -math.pi + 1e-7, math.pi]))
+    far = float(rng.choice([0.0, 1e3, 7.5e3]))
+    q = scenes.quat_from_rpy(float(rng.uniform(-0.3, 0.3)), float(rng.uniform(-0.3, 0.3)), yaw)
+    lim = float(rng.choice([-1.0, rng.uniform(0.0, 1.2)]))
+    twist = rng.uniform(-1.0, 1.0, 3) * rng.choice([0.5, 2.0, 5.0])    # at and beyond the limits
+    return scenes.tick_input(pose=(far + rng.uniform(-5, 5), -far + rng.uniform(-5, 5), rng.uniform(-1, 1)) + tuple(q),
+                             twist=tuple(float(v) for v in twist), allowed_max=lim,
+                             heading_deviation=float(rng.uniform(-math.pi, math.pi)))
+
+
+def _all_fixture_theories():
+    """(theory, ticks) of every configuration of configs.py / scenes.py, bench extensions off."""
+    out = [(th, []) for th in list(configs.shipped_theories()) + [configs.omni_simple_shipped()]]
+    for c in configs.BENCH:
+        sc = scenes.bench_scene(c) if c != "C4" else None
+        out.append((reference_semantics(configs.bench_theory(c)), [sc.tick] if sc is not None else []))
+    return out
+
+
+def _check_generation(th, ti, build, every=1):
+    """-> number of generated trajectories compared."""
+    so = oracle.samples(th, ti)
+    sr = R.samples(th, ti, build=build)
+    assert np.array_equal(so, sr)
+    n_gen = 0
+    for s in sr[::every]:
+        po, co, mo = oracle.generate(th, ti, s, capacity=8192)
+        pr, cr, mr = R.generate(th, ti, s, build=build)
+        assert len(po) == len(pr), ("steps / gate", s)
+        if build == "O2":
+            assert np.array_equal(po, pr) and np.array_equal(co, cr) and np.array_equal(mo, mr), s
+        else:
+            # At -O0 GCC does not fuse Eigen's sin(angle) / cos(angle) into one sincos() call, and glibc 2.35's sin /
+            # cos differ from its sincos in the last ulp for about 0.1 % of arguments (ASSUMPTIONS.md row 17): the
+            # reference's own -O0 and -O2 builds differ there.  Positions and the step chain stay exact.
+            assert np.array_equal(po[:, :3], pr[:, :3]), s
+            np.testing.assert_allclose(po[:, 3:], pr[:, 3:], rtol=0, atol=1e-15)
+            np.testing.assert_array_max_ulp(co, cr, maxulp=4)
+            np.testing.assert_array_max_ulp(mo, mr, maxulp=4)
+        n_gen += len(pr) > 0
+    return n_gen
+
+
+def test_generation_fixture_configs(build):
+    rng = np.random.default_rng(3)
+    n_gen = 0
+    for th, ticks in _all_fixture_theories():
+        for ti in ticks + [scenes.tick_input(), scenes.tick_input(twist=(0.4, 0.0, 0.0))] + [_random_tick(rng) for _ in range(3)]:
+            n = len(oracle.samples(th, ti))
+            n_gen += _check_generation(th, ti, build, every=max(3, n // 40))
+    for sc in (scenes.playground_scene(), scenes.playground_scene((3.0, -1.0), 2.0)):
+        n_gen += _check_generation(sc.theory, sc.tick, build)
+    assert n_gen >= 400
+
+
+def test_generation_random_configs(build):
+    """2000 random theories with a non-empty sample list (empty ones are drawn again)."""
+    rng = np.random.default_rng(2024)
+    n_cfg = n_gen = 0
+    i = 0
+    while n_cfg < 2000:
+        th = _random_theory(rng, i % 3)
+        ti = _random_tick(rng)
+        i += 1
+        n = len(oracle.samples(th, ti))
+        if n == 0:
+            assert len(R.samples(th, ti, build=build)) == 0
+            continue
+        n_cfg += 1
+        n_gen += _check_generation(th, ti, build, every=max(1, n // 3))
+    assert n_gen >= 4000, n_gen
+
+
+# ---- critics ---------------------------------------------------------------------
+CRITICS = [K.CRITIC_COLLISION, K.CRITIC_COLLISION_MIN_MAX, K.CRITIC_STICK_PATH, K.CRITIC_PURE_PURSUIT,
+           K.CRITIC_TOWARD_GLOBAL_PLAN, K.CRITIC_SHORTEST_ANGLE, K.CRITIC_TWIRLING]
+
+
+def _with_critics(th, critics):
+    t = K.TheoryConfig.from_buffer_copy(th)
+    t.n_critics = len(critics)
+    for i, c in enumerate(critics):
+        t.critics[i] = c
+    return t
+
+
+def _box_projection(cub, p):
+    """collision_model.cpp:83-139 in float32, operation by operation -> (|dot(p - centre, axis)| per axis, half sizes
+    sqrtf(...) / 2 as the reference computes them, the same half sizes with sqrt in double)."""
+    f = np.float32
+    c = np.zeros(3, f)
+    for v in cub:
+        c = (c + v).astype(f)
+    c = (c / f(8)).astype(f)
+    xs, halves, halves_double = [], [], []
+    for a, b in ((3, 0), (1, 0), (2, 0)):
+        d = (cub[a] - cub[b]).astype(f)
+        ss = f(f(f(d[0] * d[0]) + f(d[1] * d[1])) + f(d[2] * d[2]))
+        half = float(np.sqrt(ss)) / 2.0
+        u = (d.astype(np.float64) / (2.0 * half)).astype(f)
+        dp = (p - c).astype(f)
+        xs.append(abs(float(f(f(f(dp[0] * u[0]) + f(dp[1] * u[1])) + f(dp[2] * u[2])))))
+        halves.append(half)
+        halves_double.append(math.sqrt(float(ss)) / 2.0)
+    return xs, halves, halves_double
+
+
+def _one_step_theory(rng):
+    """DD theory with one sample (v, 0) and one step, and a random box: every scene scores exactly one cuboid."""
+    hx, hy, hz = rng.uniform(0.12, 0.3, 3)
+    x0, v = float(rng.uniform(-0.25, 0.0)), float(rng.uniform(0.1, 0.3))
+    box = {"flb": (x0 + 2 * hx, hy, 0.0), "frb": (x0 + 2 * hx, -hy, 0.0), "flt": (x0 + 2 * hx, hy, 2 * hz),
+           "frt": (x0 + 2 * hx, -hy, 2 * hz), "blb": (x0, hy, 0.0), "brb": (x0, -hy, 0.0), "blt": (x0, hy, 2 * hz),
+           "brt": (x0, -hy, 2 * hz)}
+    crit = [configs.critic(k) for k in (K.CRITIC_COLLISION, K.CRITIC_COLLISION_MIN_MAX)]
+    th = configs.theory("one_step", K.THEORY_DD_SIMPLE, crit, cuboid=configs.cuboid_vertices(box), min_vel_x=v,
+                        max_vel_x=v, min_vel_theta=0.0, max_vel_theta=0.0, acc_lim_x=10.0, acc_lim_theta=1.0,
+                        linear_x_sample=1.0, angular_z_sample=1.0, sim_time=1.0, sim_granularity=10.0,
+                        angular_sim_granularity=10.0)
+    ti = scenes.tick_input(pose=(float(rng.uniform(-1, 1)), float(rng.uniform(-1, 1)), 0.0, 0.0, 0.0, 0.0, 1.0),
+                           twist=(v, 0.0, 0.0))
+    return th, ti
+
+
+def _face_point(rng, cub, pose, axis, side, outside):
+    """A float point on the face `side` (+1 / -1) of `axis` of the (axis-aligned) cuboid, well inside the other two
+    axes and within the critic's 1 m ball: the critic's own projection equals the float half size exactly
+    (outside=False: inside for sqrtf), or is the first float beyond it (outside=True)."""
+    xs0, halves, _ = _box_projection(cub, cub[0])
+    c = cub.astype(np.float64).mean(0)
+    p = c.copy()
+    for o in range(3):
+        if o != axis:
+            p[o] += rng.uniform(-0.5, 0.5) * halves[o]
+    p[axis] += side * halves[axis]
+    q = p.astype(np.float32)
+    for _ in range(64):
+        xs, h, _ = _box_projection(cub, q)
+        if xs[axis] == h[axis] and not outside or xs[axis] > h[axis] and outside:
+            break
+        step = np.float32(np.inf * side) if xs[axis] < h[axis] else np.float32(-np.inf * side)
+        q[axis] = np.nextafter(q[axis], step)
+    else:
+        return None
+    xs, h, _ = _box_projection(cub, q)
+    if (xs[axis] == h[axis]) == outside or np.linalg.norm(q.astype(np.float64) - pose) >= 0.95:
+        return None
+    return q
+
+
+def _planted_scenes(rng, n=24):
+    """One-step scenes whose cloud holds points ON that cuboid's faces, where the face test itself decides.
+    'boundary': the projection equals the float half size exactly on an axis whose half size in double would be
+    smaller (the reference's sqrtf -> inside -> rejected); 'outside': the first float beyond each face (accepted);
+    'sparse': a boundary scene cut to 4 points (no kd-tree: accepted).  -> [(kind, theory, cloud, plan, tick)]"""
+    out = []
+    while len(out) < n:
+        th, ti = _one_step_theory(rng)
+        _, cub, mm = R.generate(th, ti, R.samples(th, ti)[0])
+        assert len(cub) == 1
+        cub, pose = cub[0], np.array(ti.robot_pose[:3]) + [th.max_vel_x * 1.0, 0.0, 0.0]
+        _, halves, halves_double = _box_projection(cub, cub[0])
+        kind = ["boundary", "outside", "sparse"][len(out) % 3]
+        axes = [a for a in range(3) if halves_double[a] < halves[a]] if kind != "outside" else [0, 1, 2]
+        pts = []
+        for a in axes:
+            for side in (1, -1):
+                q = _face_point(rng, cub, pose, a, side, kind == "outside")
+                if q is not None:
+                    pts.append(q)
+        if kind == "outside":
+            # and the first float beyond each face of the min / max box (collision_min_max_model.cpp:70-78)
+            for a in range(3):
+                for side, lim in ((1, mm[0, 1, a]), (-1, mm[0, 0, a])):
+                    q = cub.astype(np.float64).mean(0).astype(np.float32)
+                    q[a] = np.nextafter(lim, np.float32(np.inf * side))
+                    if np.linalg.norm(q.astype(np.float64) - pose) < 0.95 and _box_projection(cub, q)[0][a] > halves[a]:
+                        pts.append(q)
+        if not pts:
+            continue
+        cloud = np.full((max(len(pts), 5), 4), 1e4, np.float32)
+        cloud[:, 3] = 0
+        cloud[: len(pts), :3] = np.array(pts)
+        if kind == "sparse":
+            cloud = cloud[:4]
+        out.append((kind, th, cloud, np.zeros((0, 7)), ti))
+    return out
+
+
+def _random_cloud(rng, ti, n=300):
+    c = np.zeros((n, 4), np.float32)
+    c[:, :3] = np.array(ti.robot_pose[:3]) + rng.uniform([-2.5, -2.5, -0.2], [2.5, 2.5, 1.0], (n, 3))
+    return c
+
+
+def _scenes_for_critics():
+    out = []
+    for goal in ((3.0, 1.0), (3.0, -1.0)):
+        for st in (5.0, 2.0):
+            sc = scenes.playground_scene(goal, st)
+            out.append((sc.theory, sc.cloud, sc.plan, sc.tick))
+    sc = scenes.bench_scene("C1")
+    out.append((reference_semantics(sc.theory), sc.cloud, sc.plan, sc.tick))
+    rng = np.random.default_rng(77)
+    i = 0
+    while len(out) < 5 + 12:
+        kind = [K.THEORY_DD_SIMPLE, K.THEORY_OMNI_SIMPLE, K.THEORY_DD_ROTATE_INPLACE][i % 3]
+        th = _random_theory(rng, kind)
+        th.linear_x_sample, th.linear_y_sample, th.angular_z_sample = 4.0, 3.0, 5.0
+        ti = _random_tick(rng)
+        ti.heading_deviation = float(rng.choice([math.pi, -math.pi, 0.0, -0.0, rng.uniform(-3, 3)]))
+        if (oracle.tick(th, np.zeros((0, 4), np.float32), np.zeros((0, 7)), ti).steps > 0).sum() < 2:
+            continue                                                   # draw again: scenes must generate
+        cloud = _random_cloud(rng, ti)
+        if i % 4 == 3:
+            cloud = cloud[: int(rng.integers(0, 5))]                  # fewer than 5 points: no kd-tree
+        m = [0, 1, 2, 3, 20][i % 5]
+        plan = np.zeros((m, 7))
+        p0 = np.array(ti.robot_pose[:3])
+        for j in range(m):
+            plan[j, :3] = p0 + [0.1 * j, 0.05 * j, 0.0]
+            plan[j, 3:] = scenes.quat_from_rpy(0.0, 0.0, float(rng.choice([math.pi, -math.pi, rng.uniform(-3, 3)])))
+        out.append((th, cloud, plan, ti))
+        i += 1
+    return out
+
+
+def test_critics_alone_and_stacked(build):
+    rng = np.random.default_rng(5)
+    n_gen = n_rej = n_acc = 0
+    for th, cloud, plan, ti in _scenes_for_critics():
+        crit = [configs.critic(k, weight=float(rng.uniform(0.1, 3)), translation_weight=float(rng.uniform(0, 2)),
+                               orientation_weight=float(rng.uniform(0, 2))) for k in CRITICS]
+        full = _with_critics(th, crit)
+        per, _, steps, gen = R.score(full, cloud, plan, ti, build=build)
+        n_gen += int(gen.sum())
+        n_rej += int((gen & (per[:, 0] < 0)).sum())
+        n_acc += int((gen & (per[:, 0] >= 0)).sum())
+        for k in range(len(CRITICS)):
+            o = oracle.tick(_with_critics(th, [crit[k]]), cloud, plan, ti)
+            assert np.array_equal(o.steps, steps)
+            assert np.array_equal(o.costs, per[:, k]), CRITICS[k]
+        for _ in range(3):
+            order = rng.permutation(len(CRITICS))[: int(rng.integers(1, len(CRITICS) + 1))]
+            stack = _with_critics(th, [crit[j] for j in order])
+            o = oracle.tick(stack, cloud, plan, ti)
+            r, costs, rsteps, _ = R.tick(stack, cloud, plan, ti, build=build)
+            _, stacked, _, _ = R.score(full, cloud, plan, ti, order=order, build=build)
+            assert np.array_equal(o.costs, costs) and np.array_equal(stacked, costs)
+            assert r.best_index == o.result.best_index and r.best_cost == o.result.best_cost
+    assert n_gen >= 500 and n_rej >= 100 and n_acc >= 200, (n_gen, n_rej, n_acc)
+
+
+def test_collision_critics_on_planted_face_points(build):
+    """Both collision critics on one-step scenes whose verdict is decided by points exactly on a face: the oracle
+    must give the reference's verdict on each, and the scenes must show both verdicts."""
+    rng = np.random.default_rng(31)
+    verdicts = {"boundary": [], "outside": [], "sparse": []}
+    for kind, th, cloud, plan, ti in _planted_scenes(rng):
+        per, _, steps, gen = R.score(th, cloud, plan, ti, build=build)
+        assert gen.tolist() == [True] and steps.tolist() == [1]
+        for k in range(th.n_critics):
+            o = oracle.tick(_with_critics(th, [th.critics[k]]), cloud, plan, ti)
+            assert np.array_equal(o.costs, per[:, k]), (kind, th.critics[k].kind, o.costs, per[:, k])
+        verdicts[kind].append(per[0, 0])
+    assert verdicts["boundary"] and all(v == -1.0 for v in verdicts["boundary"])
+    assert verdicts["outside"] and all(v == 0.0 for v in verdicts["outside"])
+    assert verdicts["sparse"] and all(v == 0.0 for v in verdicts["sparse"])
+
+
+def test_critics_on_c2_in_full(build):
+    """F7's scene (reference semantics: 17 x 17 x 17 samples) in full, stacked critics and winner."""
+    sc = scenes.bench_scene("C2")
+    th = reference_semantics(sc.theory)
+    o = oracle.tick(th, sc.cloud, sc.plan, sc.tick, n_threads=8)
+    r, costs, steps, _ = R.tick(th, sc.cloud, sc.plan, sc.tick, build=build)
+    assert len(costs) == 17 ** 3
+    assert np.array_equal(o.steps, steps) and np.array_equal(o.costs, costs)
+    assert r.best_index == o.result.best_index and r.best_cost == o.result.best_cost
+
+
+@pytest.mark.parametrize("cfg", ["C3", "C3P"])
+def test_critics_on_c3_subranges(build, cfg):
+    """F8 / F9's scenes (reference semantics; F9's robot pitched 10 degrees) on subranges of their samples: every
+    critic alone and the stack."""
+    sc = scenes.bench_scene(cfg)
+    th = reference_semantics(sc.theory)
+    crit = [configs.critic(k) for k in CRITICS]
+    full = _with_critics(th, crit)
+    n = len(oracle.samples(th, sc.tick))
+    verdicts = set()
+    for b in (0, n // 2 - 20, n - 40):
+        per, stacked, steps, gen = R.score(full, sc.cloud, sc.plan, sc.tick, begin=b, end=b + 40, build=build)
+        assert gen.sum() >= 30
+        verdicts.update((per[gen, 0] < 0).tolist())
+        for k in range(len(CRITICS)):
+            o = oracle.tick(_with_critics(th, [crit[k]]), sc.cloud, sc.plan, sc.tick, begin=b, end=b + 40)
+            assert np.array_equal(o.steps, steps) and np.array_equal(o.costs, per[:, k]), CRITICS[k]
+        o = oracle.tick(full, sc.cloud, sc.plan, sc.tick, begin=b, end=b + 40)
+        assert np.array_equal(o.costs, stacked)
+    assert verdicts == {True, False}
+
+
+# ---- DynamicGraph ------------------------------------------------------------------
+def test_dynamic_graph_against_oracle_semantics(build):
+    """oracle_marking.cpp keeps the graph as a vector of n + 1 values: initial(n) fills keys 0..n inclusive,
+    setValue keeps the minimum, clearValue overwrites."""
+    rng = np.random.default_rng(9)
+    for _ in range(200):
+        g = R.DynamicGraph(build)
+        n = int(rng.integers(0, 50))
+        dmax = float(rng.uniform(0.5, 10))
+        g.initial(n, dmax)
+        model = np.full(n + 1, dmax)
+        for _ in range(int(rng.integers(0, 200))):
+            op, key, d = rng.integers(0, 3), int(rng.integers(0, n + 1)), float(rng.uniform(0, 12))
+            if op == 0:
+                g.set_value(key, d)
+                model[key] = min(model[key], d)
+            elif op == 1:
+                g.clear_value(key, 9999.0)
+                model[key] = 9999.0
+            else:
+                g.initial(n, dmax)
+                model[:] = dmax
+        keys, vals = g.items()
+        assert np.array_equal(keys, np.arange(n + 1)) and np.array_equal(vals, model)
+
+
+def test_dynamic_graph_replays_the_marking_oracle(build):
+    """The DynamicGraph calls oracle_marking.cpp stands for (its trace), replayed into the reference class, must leave
+    the graph the oracle reports (oracle_marking_get_dgraph), over random marking / clearing sequences."""
+    from dddmr_navigation_amd import marking
+    rng = np.random.default_rng(13)
+    g = np.array([[-5 + 0.25 * i, -5 + 0.25 * j, 0.0] for i in range(41) for j in range(41)], dtype=np.float32)
+    cfg = marking.shipped_config(euclidean_cluster_extraction_tolerance=0.25, max_markings=1024,
+                                 max_cluster_points=1 << 16)
+    tbs, tgb = (0, 0, 0.5, 0, 0, 0, 1), (0, 0, 0, 0, 0, 0, 1)
+
+    def blob(cx, cy):
+        return np.array([[np.float32(cx) + np.float32(0.03) * a, np.float32(cy) + np.float32(0.03) * b,
+                          np.float32(0.1) * z] for z in range(2, 10) for a in (-1, 1) for b in (-1, 1)], np.float32)
+
+    n_set = n_clear = 0
+    for _ in range(12):
+        mo = oracle.MarkingOracle(cfg, g, np.zeros((0, 3), np.float32))
+        mo.trace_dgraph(True)
+        centres = [tuple(rng.uniform(-4, 4, 2)) for _ in range(int(rng.integers(1, 5)))]
+        for _ in range(int(rng.integers(2, 7))):
+            keep = [c for c in centres if rng.random() < 0.6]               # what is not seen again may be cleared
+            if rng.random() < 0.4:
+                keep.append(tuple(rng.uniform(-4, 4, 2)))
+            centres = keep
+            obs = np.concatenate([blob(*c) for c in centres]) if centres else np.zeros((0, 3), np.float32)
+            mo.update(obs, tbs, tgb)
+        tr = mo.dgraph_trace()
+        ref = R.DynamicGraph(build)
+        for op, key, val in tr:
+            if op == 0:
+                ref.initial(int(key), val)
+            elif op == 1:
+                ref.set_value(int(key), val)
+                n_set += 1
+            else:
+                ref.clear_value(int(key), val)
+                n_clear += 1
+        keys, vals = ref.items()
+        want = mo.dgraph()
+        assert np.array_equal(keys, np.arange(len(want))) and np.array_equal(vals, want)
+    assert n_set > 100 and n_clear > 10, (n_set, n_clear)
+
+
+# ---- the recorded reference outputs (tests/golden/REF_*.npz): need neither _ref nor the reference ------------------
+def _ref_files():
+    import glob
+    import os
+    return sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "REF_*.npz")))
+
+
+def test_oracle_reproduces_recorded_reference():
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location(
+        "make_ref_golden", os.path.join(os.path.dirname(__file__), "golden", "make_ref_golden.py"))
+    files = _ref_files()
+    assert len(files) >= 10
+    mk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mk)
+    for f in files:
+        th, ti, cloud, plan, g = mk.load(f)
+        o = oracle.tick(th, cloud, plan, ti)
+        r = o.result
+        assert np.array_equal(o.samples, g["samples"]) and np.array_equal(o.steps, g["steps"]), f
+        assert np.array_equal(o.costs, g["costs"]), f
+        assert [r.planner_state, r.best_index, r.n_samples, r.n_generated] == g["summary"].tolist(), f
+        assert [r.best_cost, r.vx, r.vy, r.wz] == g["best"].tolist(), f
+        at = 0
+        for i, n in zip(g["poses_index"], g["poses_count"]):
+            p, _, _ = oracle.generate(th, ti, g["samples"][i], capacity=8192)
+            assert np.array_equal(p, g["poses"][at:at + n]), (f, i)
+            at += n
