@@ -6,6 +6,8 @@
 //                                                    src/stacked_perception.cpp:72-90)               -> MarkingLayerBridge
 //   ... get_dGraphValue / updateLethalPointCloud    (:838-841, :283-304)                             -> MarkingLayerBridge
 //   PathBlockedStrategy::selfMark                   (plugins/path_blocked_strategy.cpp:56-100)       -> pathBlocked()
+//   DepthCameraObservationBuffer::bufferCloud, local mode
+//                                    (plugins/depth_camera/depth_camera_observation_buffer.cpp:78-187) -> feedDepthFrame()
 //
 // Everything here is a template over the ROS / PCL types it is handed (geometry_msgs TransformStamped,
 // pcl::PointCloud<...>): this header includes neither, so it is syntax-checked in a plain C++ toolchain
@@ -77,6 +79,30 @@ inline int feedScanSource(
   rc = dddmr_rollout_set_scan_source(
     ctx, source, n ? &scan_sensor_frame.points[0].x : nullptr, n, sizeof(scan_sensor_frame.points[0]), b2s, g2b,
     perception_window_size, marking_height, n_source_out, n_aggregate_out);
+  if (rc == DDDMR_OK) {SharedContext::noteDeviceFeed();}
+  return rc;
+}
+
+// DepthCameraObservationBuffer::bufferCloud for the local planner: the raw frame in the SENSOR frame (pcl::fromROSMsg
+// output) goes to depth source `source` of the device, which transforms, applies the obstacle-height band, voxelises
+// above 20000 points, stamps the observation with stamp_ns (the buffer's clock_->now() in nanoseconds) and purges
+// stale frames.  `source` must have been configured with dddmr_rollout_set_depth_source (the buffer's
+// min/max_obstacle_height and observation_persistence); sources are numbered in plugin order, the cameras of one
+// layer in topic-name order (the std::map order getObservation() concatenates them in).
+template<class Cloud, class TransformStamped>
+inline int feedDepthFrame(
+  dddmr_rollout_ctx * ctx, int source, const Cloud & frame_sensor_frame, const TransformStamped & trans_b2s,
+  const TransformStamped & trans_gbl2b, int64_t stamp_ns, uint32_t * n_frame_out = nullptr,
+  uint32_t * n_source_out = nullptr, uint32_t * n_aggregate_out = nullptr)
+{
+  if (!ctx) {return DDDMR_ERR_BAD_ARG;}
+  double b2s[7], g2b[7];
+  toPose7(trans_b2s, b2s);
+  toPose7(trans_gbl2b, g2b);
+  const size_t n = frame_sensor_frame.points.size();
+  const int rc = dddmr_rollout_set_depth_frame(
+    ctx, source, n ? &frame_sensor_frame.points[0].x : nullptr, n, sizeof(frame_sensor_frame.points[0]), b2s, g2b,
+    stamp_ns, n_frame_out, n_source_out, n_aggregate_out);
   if (rc == DDDMR_OK) {SharedContext::noteDeviceFeed();}
   return rc;
 }

@@ -164,6 +164,14 @@ class MarkingStats(C.Structure):
     ]
 
 
+class DepthSourceConfig(C.Structure):
+    _fields_ = [
+        ("min_obstacle_height", C.c_double), ("max_obstacle_height", C.c_double),
+        ("observation_persistence_ns", C.c_int64),
+        ("max_frame_points", C.c_uint32), ("max_frames", C.c_uint32),
+    ]
+
+
 class RolloutDebug(C.Structure):
     _fields_ = [
         ("costs", C.POINTER(C.c_double)),
@@ -212,6 +220,8 @@ EXPORTED_SYMBOLS = (
     "dddmr_rollout_marking_route_counts",
     "dddmr_rollout_set_scan_source",
     "dddmr_rollout_set_stitcher_source",
+    "dddmr_rollout_set_depth_source",
+    "dddmr_rollout_set_depth_frame",
     "dddmr_rollout_stream_ceiling",
     "dddmr_rollout_selftest_sincos",
     "dddmr_rollout_last_error",
@@ -322,6 +332,12 @@ def load_library() -> C.CDLL:
     lib.dddmr_rollout_set_scan_source.restype = C.c_int
     lib.dddmr_rollout_set_stitcher_source.argtypes = [ctx_p, C.c_int32, C.c_int32]
     lib.dddmr_rollout_set_stitcher_source.restype = C.c_int
+    lib.dddmr_rollout_set_depth_source.argtypes = [ctx_p, C.c_int32, C.POINTER(DepthSourceConfig)]
+    lib.dddmr_rollout_set_depth_source.restype = C.c_int
+    lib.dddmr_rollout_set_depth_frame.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_double),
+                                                  C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                  C.POINTER(C.c_uint32)]
+    lib.dddmr_rollout_set_depth_frame.restype = C.c_int
     lib.dddmr_rollout_stream_ceiling.argtypes = [ctx_p, C.c_size_t, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.dddmr_rollout_stream_ceiling.restype = C.c_int
     lib.dddmr_rollout_selftest_sincos.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]

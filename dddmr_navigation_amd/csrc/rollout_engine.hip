@@ -26,6 +26,7 @@
 
 #include "rollout_kernels.hip.h"
 #include "perception_kernels.hip.h"
+#include "depth_feed.hip.h"
 #include "measure_kernels.hip.h"
 
 using namespace dddmr;
@@ -214,6 +215,9 @@ struct dddmr_rollout_ctx {
   float4* src_cloud[kMaxSources] = {};                 // latest observation of a source, allocated on first use
   uint32_t src_n[kMaxSources] = {};
   bool multi_source = false;
+  // depth camera sources (dddmr_rollout_set_depth_source): src_cloud[i] then aliases the source's current frame buffer
+  DepthSource* depth[kMaxSources] = {};
+  bool src_is_lidar[kMaxSources] = {};                 // a scan has been fed under this id
 
   // pinned host memory
   float4* cloud_stage[kCloudBufs] = {nullptr, nullptr, nullptr};   // pinned staging, one per device cloud buffer
@@ -456,6 +460,7 @@ size_t dddmr_rollout_sizeof(int which) {
     case 5: return sizeof(dddmr_rollout_debug);
     case 6: return sizeof(dddmr_marking_config);
     case 7: return sizeof(dddmr_marking_stats);
+    case 8: return sizeof(dddmr_depth_source_config);
     default: return 0;
   }
 }
@@ -499,6 +504,7 @@ void dddmr_rollout_destroy(dddmr_rollout_ctx* ctx) {
     if (p) (void)hipFree(p);
   perception_free(ctx->feed);
   for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) {
+    if (ctx->depth[i]) { depth_free(*ctx->depth[i]); delete ctx->depth[i]; ctx->src_cloud[i] = nullptr; }
     if (ctx->src_feed[i]) { perception_free(*ctx->src_feed[i]); delete ctx->src_feed[i]; }
     if (ctx->src_cloud[i]) (void)hipFree(ctx->src_cloud[i]);
   }
@@ -717,6 +723,8 @@ static int set_scan_impl(dddmr_rollout_ctx* ctx, int source, const float* xyz, s
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
   if (source < 0 && ctx->multi_source) source = 0;              // once several sensors feed, plain set_scan is sensor 0
+  if (source >= 0 && ctx->depth[source]) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_scan: source %d is a depth camera source", source);
+  if (source < 0) ctx->src_is_lidar[0] = true;                  // the single-producer form is the lidar of source 0
   PerceptionScratch* scratch = &ctx->feed;
   if (source > 0) {
     if (!ctx->src_feed[source]) {
@@ -729,6 +737,7 @@ static int set_scan_impl(dddmr_rollout_ctx* ctx, int source, const float* xyz, s
   if (scratch->stitcher_num > 0 && n_points == 0) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_scan: empty scan with the stitcher on");
   if (source >= 0) {
     ctx->multi_source = true;
+    ctx->src_is_lidar[source] = true;
     if (!ctx->src_cloud[source]) HIPCHK(ctx, hipMalloc(&ctx->src_cloud[source], (size_t)std::max<uint32_t>(ctx->cfg.max_points, 1) * sizeof(float4)));
   }
   const int back = acquire_back(ctx);
@@ -789,6 +798,7 @@ int dddmr_rollout_set_scan_source(dddmr_rollout_ctx* ctx, int32_t source_id, con
 int dddmr_rollout_set_stitcher(dddmr_rollout_ctx* ctx, int32_t stitcher_num) {
   if (!ctx || stitcher_num < 0) return DDDMR_ERR_BAD_ARG;
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  if (ctx->depth[0]) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_stitcher: source 0 is a depth camera source");
   ctx->feed.stitcher_num = stitcher_num;
   ctx->feed.stitched.clear();
   return DDDMR_OK;
@@ -799,6 +809,7 @@ int dddmr_rollout_set_stitcher_source(dddmr_rollout_ctx* ctx, int32_t source_id,
   if (source_id == 0) return dddmr_rollout_set_stitcher(ctx, stitcher_num);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  if (ctx->depth[source_id]) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_stitcher: source %d is a depth camera source", source_id);
   if (!ctx->src_feed[source_id]) {
     auto* ps = new PerceptionScratch();
     if (perception_alloc(*ps, ctx->cfg.max_points) != 0) { perception_free(*ps); delete ps; return fail(ctx, DDDMR_ERR_HIP, "set_stitcher: scratch of source %d", source_id); }
@@ -806,6 +817,156 @@ int dddmr_rollout_set_stitcher_source(dddmr_rollout_ctx* ctx, int32_t source_id,
   }
   ctx->src_feed[source_id]->stitcher_num = stitcher_num;
   ctx->src_feed[source_id]->stitched.clear();
+  return DDDMR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Depth camera sources: DepthCameraLayer::getObservation in local mode (depth_feed.hip.h)
+// ---------------------------------------------------------------------------
+// The aggregate = every source's current observation in source order, into a back buffer, published.
+// producer_mu held; *n_aggregate = sum of src_n[] (the caller has checked it against max_points).
+static int publish_sources(dddmr_rollout_ctx* ctx, uint32_t* n_aggregate) {
+  const int back = acquire_back(ctx);
+  size_t at = 0;
+  for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) {
+    if (!ctx->src_n[i]) continue;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->cloud_dev[back] + at, ctx->src_cloud[i], (size_t)ctx->src_n[i] * sizeof(float4), hipMemcpyDeviceToDevice, ctx->copy_stream));
+    at += ctx->src_n[i];
+  }
+  HIPCHK(ctx, hipEventRecord(ctx->cloud_ready[back], ctx->copy_stream));
+  publish_cloud(ctx, back, (uint32_t)at);
+  *n_aggregate = (uint32_t)at;
+  return DDDMR_OK;
+}
+
+int dddmr_rollout_set_depth_source(dddmr_rollout_ctx* ctx, int32_t source_id, const dddmr_depth_source_config* cfg) {
+  if (!ctx) return DDDMR_ERR_BAD_ARG;
+  if (!cfg || source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_source: source %d (at most %d sensors) / null config", source_id, dddmr_rollout_ctx::kMaxSources);
+  if (!(cfg->min_obstacle_height <= cfg->max_obstacle_height) || cfg->observation_persistence_ns < 0 || cfg->max_frame_points == 0 ||
+      cfg->max_frames == 0)
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_source: bad height band / persistence / capacities");
+  if (cfg->max_frame_points > (1u << 28)) return fail(ctx, DDDMR_ERR_CAPACITY, "set_depth_source: max_frame_points %u", cfg->max_frame_points);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  if (ctx->src_is_lidar[source_id] || ctx->src_feed[source_id] || (source_id == 0 && ctx->feed.stitcher_num > 0))
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_source: source %d is a lidar source", source_id);
+  const bool had_points = ctx->src_n[source_id] != 0;
+  if (ctx->depth[source_id]) {                       // re-configuring empties the source
+    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+    depth_free(*ctx->depth[source_id]);
+    delete ctx->depth[source_id];
+    ctx->depth[source_id] = nullptr;
+    ctx->src_cloud[source_id] = nullptr;
+    ctx->src_n[source_id] = 0;
+  }
+  auto* ds = new DepthSource();
+  ds->zmin = cfg->min_obstacle_height;
+  ds->zmax = cfg->max_obstacle_height;
+  ds->persistence_ns = cfg->observation_persistence_ns;
+  ds->max_frame_points = cfg->max_frame_points;
+  ds->max_frames = cfg->max_frames;
+  int rc = DDDMR_OK;
+  if (depth_alloc(*ds, ctx->cfg.max_points) != 0) {
+    depth_free(*ds);
+    delete ds;
+    rc = fail(ctx, DDDMR_ERR_HIP, "set_depth_source: scratch of source %d", source_id);
+  } else {
+    ctx->depth[source_id] = ds;
+    ctx->src_cloud[source_id] = ds->buf[ds->cur];
+    ctx->multi_source = true;
+  }
+  if (had_points) {                                  // the aggregate loses the emptied source's segment
+    uint32_t n_all;
+    const int prc = publish_sources(ctx, &n_all);
+    if (rc == DDDMR_OK) rc = prc;
+  }
+  return rc;
+}
+
+int dddmr_rollout_set_depth_frame(dddmr_rollout_ctx* ctx, int32_t source_id, const float* xyz, size_t n_points,
+                                  size_t stride_bytes, const double T_base_sensor[7], const double T_gbl_base[7],
+                                  int64_t stamp_ns, uint32_t* n_frame_points, uint32_t* n_source_points,
+                                  uint32_t* n_aggregate_points) {
+  if (!ctx || !T_base_sensor || !T_gbl_base) return DDDMR_ERR_BAD_ARG;
+  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_frame: source %d (at most %d sensors)", source_id, dddmr_rollout_ctx::kMaxSources);
+  if (n_points > 0 && (!xyz || stride_bytes < 12 || stride_bytes % 4 != 0))
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_frame: bad pointer/stride");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  DepthSource* ds = ctx->depth[source_id];
+  if (!ds) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_frame: source %d is not a configured depth source", source_id);
+  if (n_points > ds->max_frame_points)
+    return fail(ctx, DDDMR_ERR_CAPACITY, "set_depth_frame: %zu points > max_frame_points %u", n_points, ds->max_frame_points);
+  // purgeStaleObservations (depth_camera_observation_buffer.cpp:203-231) with last_updated_ = stamp_ns decides from
+  // the stamps alone, so which observations stay is known before the frame is processed
+  const int64_t stamp_us = stamp_ns / 1000;          // pcl_conversions::toPCL keeps whole microseconds
+  auto stays = [&](int64_t us, bool newest) {
+    if (ds->persistence_ns == 0) return newest;      // "keeping observations for no time": only the newest one
+    return !(stamp_ns - us * 1000 > ds->persistence_ns);
+  };
+  std::vector<DepthFrame> kept;
+  size_t kept_points = 0;
+  for (const DepthFrame& fr : ds->frames)
+    if (stays(fr.stamp_us, false)) { kept.push_back(fr); kept_points += fr.n; }
+  const bool none_leaves = kept.size() == ds->frames.size();
+  const bool new_alive = stays(stamp_us, true);
+  if (kept.size() + (new_alive ? 1 : 0) > ds->max_frames)
+    return fail(ctx, DDDMR_ERR_CAPACITY, "set_depth_frame: %zu observations alive > max_frames %u", kept.size() + 1, ds->max_frames);
+  // Nothing leaves: the frame is appended behind the alive ones.  Otherwise the ones that stay are copied to the
+  // other buffer (device to device) and the frame is built behind them; the buffers swap on success only.
+  const int dst_buf = none_leaves ? ds->cur : ds->cur ^ 1;
+  if (!none_leaves) {
+    size_t src_at = 0, dst_at = 0;
+    for (const DepthFrame& fr : ds->frames) {        // the caller's stamps need not be monotonic: any frame may be the one to leave
+      if (stays(fr.stamp_us, false) && fr.n) {
+        HIPCHK(ctx, hipMemcpyAsync(ds->buf[dst_buf] + dst_at, ds->buf[ds->cur] + src_at, (size_t)fr.n * sizeof(float4), hipMemcpyDeviceToDevice, ctx->copy_stream));
+        dst_at += fr.n;
+      }
+      src_at += fr.n;
+    }
+  }
+  DepthParams dp;
+  quat_to_rot(T_base_sensor, dp.Rbs);
+  quat_to_rot(T_gbl_base, dp.Rgb);
+  for (int i = 0; i < 3; ++i) {
+    dp.tbs[i] = T_base_sensor[i];
+    dp.tgb[i] = T_gbl_base[i];
+  }
+  dp.zmin = ds->zmin;
+  dp.zmax = ds->zmax;
+  dp.n = (int)n_points;
+  uint32_t n_out = 0;
+  const int rc = depth_feed(*ds, dp, xyz, stride_bytes, ds->buf[dst_buf] + kept_points, ctx->copy_stream, &n_out);
+  if (rc != 0) return fail(ctx, DDDMR_ERR_HIP, "set_depth_frame: depth feed failed (%d)", rc);
+  const size_t n_source = kept_points + (new_alive ? n_out : 0);
+  size_t total = n_source;
+  for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i)
+    if (i != source_id) total += ctx->src_n[i];
+  if (total > ctx->cfg.max_points)
+    return fail(ctx, DDDMR_ERR_CAPACITY, "set_depth_frame: the sensors' observations together (%zu points) exceed max_points %u", total, ctx->cfg.max_points);
+  // commit: from here on nothing fails before the aggregate is rebuilt from the new state
+  const std::vector<DepthFrame> old_frames = ds->frames;
+  const int old_cur = ds->cur;
+  const uint32_t old_n = ctx->src_n[source_id];
+  if (new_alive) kept.push_back(DepthFrame{n_out, stamp_us});
+  ds->frames.swap(kept);
+  ds->cur = dst_buf;
+  ctx->src_cloud[source_id] = ds->buf[ds->cur];
+  ctx->src_n[source_id] = (uint32_t)n_source;
+  uint32_t n_all = 0;
+  const int prc = publish_sources(ctx, &n_all);
+  if (prc != DDDMR_OK) {                             // a failed copy: the source goes back to what the published aggregate holds
+    ds->frames = old_frames;
+    ds->cur = old_cur;
+    ctx->src_cloud[source_id] = ds->buf[ds->cur];
+    ctx->src_n[source_id] = old_n;
+    return prc;
+  }
+  if (n_frame_points) *n_frame_points = n_out;
+  if (n_source_points) *n_source_points = (uint32_t)n_source;
+  if (n_aggregate_points) *n_aggregate_points = n_all;
   return DDDMR_OK;
 }
 

@@ -150,6 +150,28 @@ class LocalPlanner:
     def set_stitcher_source(self, source_id: int, stitcher_num: int):
         self._check(self._lib.dddmr_rollout_set_stitcher_source(self._ctx, int(source_id), int(stitcher_num)))
 
+    def set_depth_source(self, source_id: int, min_obstacle_height: float, max_obstacle_height: float,
+                         observation_persistence_ns: int = 0, max_frame_points: int = 848 * 480, max_frames: int = 1):
+        """Make `source_id` a depth camera source (DepthCameraObservationBuffer's parameters); empties a configured one."""
+        cfg = K.DepthSourceConfig(float(min_obstacle_height), float(max_obstacle_height), int(observation_persistence_ns),
+                                  int(max_frame_points), int(max_frames))
+        self._check(self._lib.dddmr_rollout_set_depth_source(self._ctx, int(source_id), C.byref(cfg)))
+
+    def set_depth_frame(self, source_id: int, frame_xyz: np.ndarray, T_base_sensor, T_gbl_base, stamp_ns: int):
+        """One depth frame through bufferCloud's local-mode steps (depth_camera_observation_buffer.cpp:78-187): returns
+        (points of this frame's observation, points of the source's alive frames, points of the aggregate)."""
+        frame = np.ascontiguousarray(frame_xyz, dtype=np.float32)
+        if frame.ndim != 2 or (frame.shape[0] and frame.shape[1] < 3):
+            raise ValueError("frame must be [P, >=3] float32")
+        tbs = (C.c_double * 7)(*[float(v) for v in T_base_sensor])
+        tgb = (C.c_double * 7)(*[float(v) for v in T_gbl_base])
+        n_frame, n_src, n_all = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        stride = frame.strides[0] if frame.shape[0] else 12
+        self._check(self._lib.dddmr_rollout_set_depth_frame(self._ctx, int(source_id), frame.ctypes.data_as(C.c_void_p), frame.shape[0],
+                                                            stride, tbs, tgb, int(stamp_ns), C.byref(n_frame), C.byref(n_src),
+                                                            C.byref(n_all)))
+        return int(n_frame.value), int(n_src.value), int(n_all.value)
+
     def set_stitcher(self, stitcher_num: int):
         """cbSensor's `stitcher_num` (multilayer_spinning_lidar.cpp:185-200): feed the last N raw scans together."""
         self._check(self._lib.dddmr_rollout_set_stitcher(self._ctx, int(stitcher_num)))

@@ -288,3 +288,51 @@ def lidar_scan(cloud_xyz: np.ndarray, sensor_xyz=(0.0, 0.0, 0.5), seed: int = 0,
     noisy = dist + rng.normal(0.0, sigma, size=dist.shape)
     pts = rel * (noisy / dist)[:, None]
     return pts.astype(np.float32)
+
+
+def depth_frame(cloud_xyz: np.ndarray, T_gbl_sensor, width: int = 640, height: int = 480, fov_w: float = 1.5,
+                fov_v: float = 1.0, max_range: float = 8.0, seed: int = 0, sigma: float = 0.003,
+                patch: float = 0.075) -> np.ndarray:
+    """The scene seen by a depth camera at T_gbl_sensor (x y z qx qy qz qw; camera_link axes: x forward, y left,
+    z up), fov_w x fov_v radians, as a camera driver delivers it: an organised [height * width, 3] float32 cloud in
+    the SENSOR frame, row-major from the top-left pixel, NaN where a pixel has no return.  Every scene point is a
+    square patch of `patch` metres facing the camera (the lattice spacing plus its jitter, so surfaces close up);
+    per pixel the nearest patch wins and the return lies on the pixel's own ray at that depth, with gaussian depth
+    noise from the seed (sigma metres at 1 m, growing with depth squared as stereo depth does).  CPU only."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    T = np.asarray(T_gbl_sensor, dtype=np.float64)
+    x, y, z, w = T[3], T[4], T[5], T[6]
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                  [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                  [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+    rel = (cloud_xyz[:, :3].astype(np.float64) - T[:3]) @ R          # sensor <- global (rows times R = R^T p)
+    tw, tv = math.tan(0.5 * fov_w), math.tan(0.5 * fov_v)
+    d = rel[:, 0]
+    ok = (d > 0.3) & (d < max_range)
+    rel, d = rel[ok], d[ok]
+    # pixel coordinates (continuous): column grows to the right (-y), row grows downwards (-z)
+    fx, fy = 0.5 * width / tw, 0.5 * height / tv
+    cc = 0.5 * width - fx * rel[:, 1] / d
+    rr = 0.5 * height - fy * rel[:, 2] / d
+    half_c, half_r = 0.5 * patch * fx / d, 0.5 * patch * fy / d
+    c0 = np.floor(cc - half_c + 0.5).astype(np.int64)
+    c1 = np.floor(cc + half_c - 0.5).astype(np.int64)
+    r0 = np.floor(rr - half_r + 0.5).astype(np.int64)
+    r1 = np.floor(rr + half_r - 0.5).astype(np.int64)
+    depth = np.full(height * width, np.inf)
+    nr, nc = r1 - r0, c1 - c0
+    for dr in range(int(nr.max(initial=-1)) + 1):
+        rows_left = np.flatnonzero(nr >= dr)                 # near points cover many pixels, far ones one or none
+        for dc in range(int(nc[rows_left].max(initial=-1)) + 1):
+            k = rows_left[nc[rows_left] >= dc]
+            r, c = r0[k] + dr, c0[k] + dc
+            m = (r >= 0) & (r < height) & (c >= 0) & (c < width)
+            np.minimum.at(depth, r[m] * width + c[m], d[k][m])
+    hit = np.isfinite(depth)
+    depth = depth + rng.normal(0.0, 1.0, size=depth.shape) * sigma * np.where(hit, depth, 0.0) ** 2
+    cols = (np.arange(width) + 0.5 - 0.5 * width) / fx
+    rows = (np.arange(height) + 0.5 - 0.5 * height) / fy
+    out = np.full((height * width, 3), np.nan, dtype=np.float32)
+    px = np.stack([depth, -depth * np.tile(cols, height), -depth * np.repeat(rows, width)], axis=1)
+    out[hit] = px[hit].astype(np.float32)
+    return out

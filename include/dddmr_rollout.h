@@ -254,6 +254,51 @@ int dddmr_rollout_set_scan_source(dddmr_rollout_ctx* ctx, int32_t source_id, con
                                   uint32_t* n_aggregate_points);
 int dddmr_rollout_set_stitcher_source(dddmr_rollout_ctx* ctx, int32_t source_id, int32_t stitcher_num);
 
+/* Depth camera as one more source of the aggregate = the local-mode side of DepthCameraLayer
+   (dddmr_perception_3d/plugins/depth_camera/): what getObservation() (depth_camera_layer.cpp:618-663)
+   hands the local planner.  Per frame, DepthCameraObservationBuffer::bufferCloud
+   (depth_camera_observation_buffer.cpp:78-187) runs on the device: sensor->base transform, keep
+   min_obstacle_height <= z <= max_obstacle_height (no x/y window, no range filter), only if more than
+   20000 points survive a 0.05 m VoxelGrid centroid downsample in the base frame, base->global transform
+   with the transform of THIS frame.  The observation is stamped stamp_ns (the caller's clock->now())
+   truncated to whole microseconds, and purgeStaleObservations (:203-231) is applied literally with
+   last_updated_ = stamp_ns: observation_persistence_ns == 0 keeps the newest frame only, otherwise a
+   frame leaves when stamp_ns - its_stamp_truncated_to_us > observation_persistence_ns (int64, strict >).
+   The source's observation = its alive frames, oldest first (older frames keep the global coordinates
+   of their arrival); the aggregate = all sources in source order, as for dddmr_rollout_set_scan_source.
+   The order of points inside one frame is unspecified.
+
+   A raw frame is bounded by max_frame_points, not by max_points; the sources' observations together
+   must fit max_points.  DDDMR_ERR_CAPACITY: frame > max_frame_points, more than max_frames observations
+   alive, or the aggregate > max_points.  DDDMR_ERR_BAD_ARG: bad source id / stride, a frame for an
+   unconfigured source, a depth call on a source that has been fed scans or given a stitcher, and
+   dddmr_rollout_set_scan_source / set_stitcher_source on a depth source.  A failed call changes nothing:
+   the source's frames, every source's size and the published aggregate stay what they were.
+   dddmr_rollout_set_depth_source on a configured source empties it (the aggregate is republished without
+   its points).  Configuring a depth source switches the context to the several-sensors mode: plain
+   dddmr_rollout_set_scan then means source 0.
+
+   Differences from the reference, on purpose: a record with ANY non-finite coordinate is dropped (as
+   dddmr_rollout_set_scan does); the reference drops NaN z only and would keep a finite-z point with an
+   infinite x.  Base-frame coordinates must stay within +-52 km (2^20 voxels of 0.05 m per axis).
+   Limitation: dddmr_rollout_marking_update reads the context's aggregate as "the lidar observation";
+   a context that feeds a marking layer must not carry depth sources. */
+typedef struct {
+  double min_obstacle_height, max_obstacle_height;
+  int64_t observation_persistence_ns; /* 0 = newest frame only; the seconds -> Duration conversion stays with the caller */
+  uint32_t max_frame_points;          /* raw points per frame, e.g. 848 * 480 */
+  uint32_t max_frames;                /* observations alive at once */
+} dddmr_depth_source_config;
+
+int dddmr_rollout_set_depth_source(dddmr_rollout_ctx* ctx, int32_t source_id,
+                                   const dddmr_depth_source_config* cfg);
+/* *n_frame_points: points of this frame's observation; *n_source_points: the source's alive frames
+   together; *n_aggregate_points: the published aggregate (each may be NULL). */
+int dddmr_rollout_set_depth_frame(dddmr_rollout_ctx* ctx, int32_t source_id, const float* xyz,
+                                  size_t n_points, size_t stride_bytes, const double T_base_sensor[7],
+                                  const double T_gbl_base[7], int64_t stamp_ns, uint32_t* n_frame_points,
+                                  uint32_t* n_source_points, uint32_t* n_aggregate_points);
+
 /* Copy the current aggregate observation back (debug / parity of set_scan). */
 int dddmr_rollout_get_cloud(dddmr_rollout_ctx* ctx, float* xyzi_out, size_t capacity,
                             size_t* n_points);

@@ -86,6 +86,18 @@ class LocalPlanner {
                                  perception_window_size, marking_height, &n_out));
     return n_out;
   }
+  // depth camera as one more source of the aggregate (DepthCameraLayer::getObservation in local mode)
+  void setDepthSource(int32_t source_id, const dddmr_depth_source_config& cfg) {
+    check(dddmr_rollout_set_depth_source(ctx_, source_id, &cfg));
+  }
+  struct DepthFrameCounts { uint32_t frame, source, aggregate; };
+  DepthFrameCounts setDepthFrame(int32_t source_id, const float* xyz, size_t n_points, size_t stride_bytes,
+                                 const double T_base_sensor[7], const double T_gbl_base[7], int64_t stamp_ns) {
+    DepthFrameCounts c{};
+    check(dddmr_rollout_set_depth_frame(ctx_, source_id, xyz, n_points, stride_bytes, T_base_sensor, T_gbl_base, stamp_ns,
+                                        &c.frame, &c.source, &c.aggregate));
+    return c;
+  }
   // prune plan poses, x y z qx qy qz qw each (output of Local_Planner::prunePlan)
   void setPlan(const double* poses_xyz_qxyzw, size_t n_poses) {
     check(dddmr_rollout_set_prune_plan(ctx_, poses_xyz_qxyzw, n_poses));
