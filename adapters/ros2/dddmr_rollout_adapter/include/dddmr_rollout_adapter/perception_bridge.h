@@ -8,6 +8,7 @@
 //   PathBlockedStrategy::selfMark                   (plugins/path_blocked_strategy.cpp:56-100)       -> pathBlocked()
 //   DepthCameraObservationBuffer::bufferCloud, local mode
 //                                    (plugins/depth_camera/depth_camera_observation_buffer.cpp:78-187) -> feedDepthFrame()
+//   DepthImg2PointCloud::cbDepthImg + bufferCloud   (utils/depthimg2pointcloud_node.cpp:96-157)      -> feedDepthImage()
 //
 // Everything here is a template over the ROS / PCL types it is handed (geometry_msgs TransformStamped,
 // pcl::PointCloud<...>): this header includes neither, so it is syntax-checked in a plain C++ toolchain
@@ -103,6 +104,31 @@ inline int feedDepthFrame(
   const int rc = dddmr_rollout_set_depth_frame(
     ctx, source, n ? &frame_sensor_frame.points[0].x : nullptr, n, sizeof(frame_sensor_frame.points[0]), b2s, g2b,
     stamp_ns, n_frame_out, n_source_out, n_aggregate_out);
+  if (rc == DDDMR_OK) {SharedContext::noteDeviceFeed();}
+  return rc;
+}
+
+// DepthImg2PointCloud::cbDepthImg and bufferCloud in one call: the 16UC1 image as sensor_msgs::msg::Image carries it
+// (data = msg.data.data(), width, height, step) goes to depth image source `source`, configured with
+// dddmr_rollout_set_depth_image_source from the camera_info topic and the node's parameters.  trans_b2o takes the image's
+// optical frame (msg.header.frame_id) to the base frame.  width / height are checked against nothing here: the source
+// was configured with them and the library refuses a step below 2 * width.  Returns the library's code and notes a
+// device feed on DDDMR_OK only; on any other code nothing on the device has changed and the caller runs its CPU path
+// (the node's cloud into bufferCloud) for this image.
+template<class TransformStamped>
+inline int feedDepthImage(
+  dddmr_rollout_ctx * ctx, int source, const uint8_t * data, uint32_t width, uint32_t height, uint32_t step,
+  const TransformStamped & trans_b2o, const TransformStamped & trans_gbl2b, int64_t stamp_ns,
+  uint32_t * n_camera_out = nullptr, uint32_t * n_frame_out = nullptr, uint32_t * n_source_out = nullptr,
+  uint32_t * n_aggregate_out = nullptr)
+{
+  if (!ctx || !data || width == 0 || height == 0) {return DDDMR_ERR_BAD_ARG;}
+  double b2o[7], g2b[7];
+  toPose7(trans_b2o, b2o);
+  toPose7(trans_gbl2b, g2b);
+  const int rc = dddmr_rollout_set_depth_image(
+    ctx, source, reinterpret_cast<const uint16_t *>(data), step, b2o, g2b, stamp_ns, n_camera_out, n_frame_out,
+    n_source_out, n_aggregate_out);
   if (rc == DDDMR_OK) {SharedContext::noteDeviceFeed();}
   return rc;
 }

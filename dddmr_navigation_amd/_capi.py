@@ -172,6 +172,19 @@ class DepthSourceConfig(C.Structure):
     ]
 
 
+DEPTH_IMAGE_DROP_ZERO = 1
+
+
+class DepthImageConfig(C.Structure):
+    """dddmr_depth_image_config: the image geometry, CameraInfo K and DepthImg2PointCloud's node parameters."""
+    _fields_ = [
+        ("width", C.c_uint32), ("height", C.c_uint32),
+        ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+        ("max_distance", C.c_double), ("leaf_size", C.c_double),
+        ("sample_step", C.c_uint32), ("flags", C.c_uint32),
+    ]
+
+
 class RolloutDebug(C.Structure):
     _fields_ = [
         ("costs", C.POINTER(C.c_double)),
@@ -222,6 +235,9 @@ EXPORTED_SYMBOLS = (
     "dddmr_rollout_set_stitcher_source",
     "dddmr_rollout_set_depth_source",
     "dddmr_rollout_set_depth_frame",
+    "dddmr_rollout_set_depth_image_source",
+    "dddmr_rollout_set_depth_image",
+    "dddmr_rollout_get_depth_image_cloud",
     "dddmr_rollout_stream_ceiling",
     "dddmr_rollout_selftest_sincos",
     "dddmr_rollout_last_error",
@@ -338,6 +354,14 @@ def load_library() -> C.CDLL:
                                                   C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                                   C.POINTER(C.c_uint32)]
     lib.dddmr_rollout_set_depth_frame.restype = C.c_int
+    lib.dddmr_rollout_set_depth_image_source.argtypes = [ctx_p, C.c_int32, C.POINTER(DepthSourceConfig), C.POINTER(DepthImageConfig)]
+    lib.dddmr_rollout_set_depth_image_source.restype = C.c_int
+    lib.dddmr_rollout_set_depth_image.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                  C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                  C.POINTER(C.c_uint32)]
+    lib.dddmr_rollout_set_depth_image.restype = C.c_int
+    lib.dddmr_rollout_get_depth_image_cloud.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.dddmr_rollout_get_depth_image_cloud.restype = C.c_int
     lib.dddmr_rollout_stream_ceiling.argtypes = [ctx_p, C.c_size_t, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.dddmr_rollout_stream_ceiling.restype = C.c_int
     lib.dddmr_rollout_selftest_sincos.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]

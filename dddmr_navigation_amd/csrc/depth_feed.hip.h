@@ -92,24 +92,22 @@ __device__ __forceinline__ unsigned long long depth_voxel_key(float x, float y, 
          (unsigned long long)((uint32_t)(iz + (1 << 20)) & 0x1FFFFFu);
 }
 
-__global__ __launch_bounds__(256) void k_depth_insert(DepthParams f, const float* __restrict__ raw, int stride_floats,
-                                                      float4* __restrict__ surv, unsigned long long* __restrict__ keys,
-                                                      double* __restrict__ sums, uint32_t* __restrict__ counts,
-                                                      uint32_t slot_mask, uint32_t* __restrict__ claimed,
-                                                      uint32_t* __restrict__ counters) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+// One raw record per lane (valid = the lane has one), every lane of the wave calls it: bufferCloud's transform and
+// height band, the wave-aggregated append of the survivors and their voxel sums.  The body of k_depth_insert; the depth
+// image path (depth_image.hip.h) calls it on its stage-one centroids.
+__device__ __forceinline__ void depth_insert_record(const DepthParams& f, bool valid, float sx, float sy, float sz,
+                                                    float4* __restrict__ surv, unsigned long long* __restrict__ keys,
+                                                    double* __restrict__ sums, uint32_t* __restrict__ counts,
+                                                    uint32_t slot_mask, uint32_t* __restrict__ claimed,
+                                                    uint32_t* __restrict__ counters) {
   bool keep = false;
   float x = 0.f, y = 0.f, z = 0.f;
-  if (i < f.n) {
-    const float* sp = raw + (size_t)i * stride_floats;
-    const float sx = sp[0], sy = sp[1], sz = sp[2];
-    if (isfinite(sx) && isfinite(sy) && isfinite(sz)) {
-      // pcl::transformPointCloud(cloud, cloud, Affine3d): double multiply-add, float result
-      x = (float)(f.Rbs[0] * sx + f.Rbs[1] * sy + f.Rbs[2] * sz + f.tbs[0]);
-      y = (float)(f.Rbs[3] * sx + f.Rbs[4] * sy + f.Rbs[5] * sz + f.tbs[1]);
-      z = (float)(f.Rbs[6] * sx + f.Rbs[7] * sy + f.Rbs[8] * sz + f.tbs[2]);
-      keep = (double)z <= f.zmax && (double)z >= f.zmin;
-    }
+  if (valid && isfinite(sx) && isfinite(sy) && isfinite(sz)) {
+    // pcl::transformPointCloud(cloud, cloud, Affine3d): double multiply-add, float result
+    x = (float)(f.Rbs[0] * sx + f.Rbs[1] * sy + f.Rbs[2] * sz + f.tbs[0]);
+    y = (float)(f.Rbs[3] * sx + f.Rbs[4] * sy + f.Rbs[5] * sz + f.tbs[1]);
+    z = (float)(f.Rbs[6] * sx + f.Rbs[7] * sy + f.Rbs[8] * sz + f.tbs[2]);
+    keep = (double)z <= f.zmax && (double)z >= f.zmin;
   }
   // wave-aggregated append of the survivors: one atomic per wave, lanes keep their pixel order
   const unsigned long long mask = __ballot(keep);
@@ -137,6 +135,21 @@ __global__ __launch_bounds__(256) void k_depth_insert(DepthParams f, const float
     }
     slot = (slot + 1) & slot_mask;
   }
+}
+
+__global__ __launch_bounds__(256) void k_depth_insert(DepthParams f, const float* __restrict__ raw, int stride_floats,
+                                                      float4* __restrict__ surv, unsigned long long* __restrict__ keys,
+                                                      double* __restrict__ sums, uint32_t* __restrict__ counts,
+                                                      uint32_t slot_mask, uint32_t* __restrict__ claimed,
+                                                      uint32_t* __restrict__ counters) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = i < f.n;
+  float sx = 0.f, sy = 0.f, sz = 0.f;
+  if (valid) {
+    const float* sp = raw + (size_t)i * stride_floats;
+    sx = sp[0], sy = sp[1], sz = sp[2];
+  }
+  depth_insert_record(f, valid, sx, sy, sz, surv, keys, sums, counts, slot_mask, claimed, counters);
 }
 
 // Grid-stride over max(survivors, claimed slots): the branch is decided here, from the device's own count.
@@ -220,8 +233,9 @@ inline void depth_free(DepthSource& s) {
   s = DepthSource();
 }
 
-// max_points bounds what the source may publish; a frame under construction sits behind it
-inline int depth_alloc(DepthSource& s, size_t max_points) {
+// max_points bounds what the source may publish; a frame under construction sits behind it.  raw_stage = false: a
+// source fed depth images, which stages those itself (depth_image.hip.h)
+inline int depth_alloc(DepthSource& s, size_t max_points, bool raw_stage = true) {
   const size_t F = s.max_frame_points;
   size_t slots = 1024;
   while (slots < 2 * F) slots <<= 1;
@@ -237,8 +251,10 @@ inline int depth_alloc(DepthSource& s, size_t max_points) {
   if (hipHostMalloc(&s.res_host, sizeof(DepthResult), hipHostMallocMapped) != hipSuccess) return -1;
   if (hipHostGetDevicePointer(reinterpret_cast<void**>(&s.res_dev), s.res_host, 0) != hipSuccess) return -1;
   // k_depth_transform reads the raw frame straight from this pinned, device-mapped buffer
-  if (hipHostMalloc(&s.stage, F * 4 * sizeof(float), hipHostMallocMapped) != hipSuccess) return -1;
-  if (hipHostGetDevicePointer(reinterpret_cast<void**>(&s.stage_dev), s.stage, 0) != hipSuccess) return -1;
+  if (raw_stage) {
+    if (hipHostMalloc(&s.stage, F * 4 * sizeof(float), hipHostMallocMapped) != hipSuccess) return -1;
+    if (hipHostGetDevicePointer(reinterpret_cast<void**>(&s.stage_dev), s.stage, 0) != hipSuccess) return -1;
+  }
   std::memset(s.res_host, 0, sizeof(DepthResult));
   return 0;
 }

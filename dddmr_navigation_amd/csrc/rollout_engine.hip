@@ -27,6 +27,7 @@
 #include "rollout_kernels.hip.h"
 #include "perception_kernels.hip.h"
 #include "depth_feed.hip.h"
+#include "depth_image.hip.h"
 #include "measure_kernels.hip.h"
 
 using namespace dddmr;
@@ -217,6 +218,8 @@ struct dddmr_rollout_ctx {
   bool multi_source = false;
   // depth camera sources (dddmr_rollout_set_depth_source): src_cloud[i] then aliases the source's current frame buffer
   DepthSource* depth[kMaxSources] = {};
+  // non-null for a depth source that is fed images (dddmr_rollout_set_depth_image_source); depth[i] is set as well
+  DepthImage* dimg[kMaxSources] = {};
   bool src_is_lidar[kMaxSources] = {};                 // a scan has been fed under this id
 
   // pinned host memory
@@ -461,6 +464,7 @@ size_t dddmr_rollout_sizeof(int which) {
     case 6: return sizeof(dddmr_marking_config);
     case 7: return sizeof(dddmr_marking_stats);
     case 8: return sizeof(dddmr_depth_source_config);
+    case 9: return sizeof(dddmr_depth_image_config);
     default: return 0;
   }
 }
@@ -505,6 +509,7 @@ void dddmr_rollout_destroy(dddmr_rollout_ctx* ctx) {
   perception_free(ctx->feed);
   for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) {
     if (ctx->depth[i]) { depth_free(*ctx->depth[i]); delete ctx->depth[i]; ctx->src_cloud[i] = nullptr; }
+    if (ctx->dimg[i]) { dimg_free(*ctx->dimg[i]); delete ctx->dimg[i]; }
     if (ctx->src_feed[i]) { perception_free(*ctx->src_feed[i]); delete ctx->src_feed[i]; }
     if (ctx->src_cloud[i]) (void)hipFree(ctx->src_cloud[i]);
   }
@@ -839,24 +844,58 @@ static int publish_sources(dddmr_rollout_ctx* ctx, uint32_t* n_aggregate) {
   return DDDMR_OK;
 }
 
-int dddmr_rollout_set_depth_source(dddmr_rollout_ctx* ctx, int32_t source_id, const dddmr_depth_source_config* cfg) {
+// icfg == nullptr: a source fed point clouds; otherwise one fed depth images
+static int set_depth_source_impl(dddmr_rollout_ctx* ctx, const char* what, int32_t source_id, const dddmr_depth_source_config* cfg,
+                                 const dddmr_depth_image_config* icfg) {
   if (!ctx) return DDDMR_ERR_BAD_ARG;
   if (!cfg || source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_source: source %d (at most %d sensors) / null config", source_id, dddmr_rollout_ctx::kMaxSources);
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d (at most %d sensors) / null config", what, source_id, dddmr_rollout_ctx::kMaxSources);
   if (!(cfg->min_obstacle_height <= cfg->max_obstacle_height) || cfg->observation_persistence_ns < 0 || cfg->max_frame_points == 0 ||
       cfg->max_frames == 0)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_source: bad height band / persistence / capacities");
-  if (cfg->max_frame_points > (1u << 28)) return fail(ctx, DDDMR_ERR_CAPACITY, "set_depth_source: max_frame_points %u", cfg->max_frame_points);
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: bad height band / persistence / capacities", what);
+  if (cfg->max_frame_points > (1u << 28)) return fail(ctx, DDDMR_ERR_CAPACITY, "%s: max_frame_points %u", what, cfg->max_frame_points);
+  DimgParams ip{};
+  if (icfg) {
+    if (icfg->width == 0 || icfg->height == 0 || icfg->width > 16384 || icfg->height > 16384 || icfg->sample_step == 0 ||
+        (icfg->flags & ~DDDMR_DEPTH_IMAGE_DROP_ZERO) != 0)
+      return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: image %u x %u, sample_step %u, flags %#x", what, icfg->width, icfg->height,
+                  icfg->sample_step, icfg->flags);
+    if (!std::isfinite(icfg->fx) || !std::isfinite(icfg->fy) || icfg->fx == 0.0 || icfg->fy == 0.0 || !std::isfinite(icfg->cx) ||
+        !std::isfinite(icfg->cy) || !(icfg->max_distance > 0.0) || !(icfg->leaf_size > 0.0) || !std::isfinite(icfg->leaf_size))
+      return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: bad intrinsics / max_distance / leaf_size", what);
+    // cbDepthImg:111-114: float cx = K[2], cy = K[5], fx = 1.0f / K[0], fy = 1.0f / K[4] (double division, float result)
+    ip.cx = (float)icfg->cx;
+    ip.cy = (float)icfg->cy;
+    ip.fx = (float)(1.0 / icfg->fx);
+    ip.fy = (float)(1.0 / icfg->fy);
+    ip.inv_leaf = 1.0f / (float)icfg->leaf_size;      // pcl::VoxelGrid::setLeafSize(float ...): inverse_leaf_size_ = 1 / leaf_size_
+    ip.drop_zero = (icfg->flags & DDDMR_DEPTH_IMAGE_DROP_ZERO) ? 1u : 0u;
+    ip.max_distance = icfg->max_distance;
+    ip.width = icfg->width;
+    ip.step = icfg->sample_step;
+    ip.cols = (icfg->width + icfg->sample_step - 1) / icfg->sample_step;
+    ip.rows = (icfg->height + icfg->sample_step - 1) / icfg->sample_step;
+    if (!std::isfinite(ip.inv_leaf) || !std::isfinite(ip.fx) || !std::isfinite(ip.fy) || !dimg_box_ok(ip, icfg->height))
+      return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: the frustum's voxel box (intrinsics, max_distance %g, leaf_size %g) could reach 2^31 cells",
+                  what, icfg->max_distance, icfg->leaf_size);
+    if ((uint64_t)ip.rows * ip.cols > cfg->max_frame_points)
+      return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: max_frame_points %u < the %u x %u sampled pixels", what, cfg->max_frame_points, ip.rows, ip.cols);
+  }
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
   if (ctx->src_is_lidar[source_id] || ctx->src_feed[source_id] || (source_id == 0 && ctx->feed.stitcher_num > 0))
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_source: source %d is a lidar source", source_id);
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d is a lidar source", what, source_id);
   const bool had_points = ctx->src_n[source_id] != 0;
   if (ctx->depth[source_id]) {                       // re-configuring empties the source
     HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
     depth_free(*ctx->depth[source_id]);
     delete ctx->depth[source_id];
     ctx->depth[source_id] = nullptr;
+    if (ctx->dimg[source_id]) {
+      dimg_free(*ctx->dimg[source_id]);
+      delete ctx->dimg[source_id];
+      ctx->dimg[source_id] = nullptr;
+    }
     ctx->src_cloud[source_id] = nullptr;
     ctx->src_n[source_id] = 0;
   }
@@ -866,13 +905,24 @@ int dddmr_rollout_set_depth_source(dddmr_rollout_ctx* ctx, int32_t source_id, co
   ds->persistence_ns = cfg->observation_persistence_ns;
   ds->max_frame_points = cfg->max_frame_points;
   ds->max_frames = cfg->max_frames;
+  DepthImage* di = nullptr;
+  if (icfg) {
+    di = new DepthImage();
+    di->p = ip;
+    di->height = icfg->height;
+  }
   int rc = DDDMR_OK;
-  if (depth_alloc(*ds, ctx->cfg.max_points) != 0) {
+  if (depth_alloc(*ds, ctx->cfg.max_points, icfg == nullptr) != 0 || (di && dimg_alloc(*di) != 0)) {
     depth_free(*ds);
     delete ds;
-    rc = fail(ctx, DDDMR_ERR_HIP, "set_depth_source: scratch of source %d", source_id);
+    if (di) {
+      dimg_free(*di);
+      delete di;
+    }
+    rc = fail(ctx, DDDMR_ERR_HIP, "%s: scratch of source %d", what, source_id);
   } else {
     ctx->depth[source_id] = ds;
+    ctx->dimg[source_id] = di;
     ctx->src_cloud[source_id] = ds->buf[ds->cur];
     ctx->multi_source = true;
   }
@@ -884,21 +934,34 @@ int dddmr_rollout_set_depth_source(dddmr_rollout_ctx* ctx, int32_t source_id, co
   return rc;
 }
 
-int dddmr_rollout_set_depth_frame(dddmr_rollout_ctx* ctx, int32_t source_id, const float* xyz, size_t n_points,
-                                  size_t stride_bytes, const double T_base_sensor[7], const double T_gbl_base[7],
-                                  int64_t stamp_ns, uint32_t* n_frame_points, uint32_t* n_source_points,
-                                  uint32_t* n_aggregate_points) {
-  if (!ctx || !T_base_sensor || !T_gbl_base) return DDDMR_ERR_BAD_ARG;
-  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_frame: source %d (at most %d sensors)", source_id, dddmr_rollout_ctx::kMaxSources);
-  if (n_points > 0 && (!xyz || stride_bytes < 12 || stride_bytes % 4 != 0))
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_frame: bad pointer/stride");
+int dddmr_rollout_set_depth_source(dddmr_rollout_ctx* ctx, int32_t source_id, const dddmr_depth_source_config* cfg) {
+  return set_depth_source_impl(ctx, "set_depth_source", source_id, cfg, nullptr);
+}
+
+int dddmr_rollout_set_depth_image_source(dddmr_rollout_ctx* ctx, int32_t source_id, const dddmr_depth_source_config* cfg,
+                                         const dddmr_depth_image_config* image_cfg) {
+  if (!ctx) return DDDMR_ERR_BAD_ARG;
+  if (!image_cfg) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_image_source: null image config");
+  return set_depth_source_impl(ctx, "set_depth_image_source", source_id, cfg, image_cfg);
+}
+
+// One frame of either kind: xyz (a cloud source) or depth_mm (an image source) is set.  bufferCloud's bookkeeping around
+// the device work is the same for both.
+static int set_depth_impl(dddmr_rollout_ctx* ctx, const char* what, int32_t source_id, const float* xyz, size_t n_points,
+                          const uint16_t* depth_mm, size_t stride_bytes, const double T_base_sensor[7], const double T_gbl_base[7],
+                          int64_t stamp_ns, uint32_t* n_camera_points, uint32_t* n_frame_points, uint32_t* n_source_points,
+                          uint32_t* n_aggregate_points) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
   DepthSource* ds = ctx->depth[source_id];
-  if (!ds) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_frame: source %d is not a configured depth source", source_id);
+  if (!ds) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d is not a configured depth source", what, source_id);
+  DepthImage* di = ctx->dimg[source_id];
+  if (depth_mm && !di) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d is configured for point clouds", what, source_id);
+  if (!depth_mm && di) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d is configured for depth images", what, source_id);
+  if (depth_mm && stride_bytes < 2 * (size_t)di->p.width)
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: row stride %zu < 2 * width %u", what, stride_bytes, di->p.width);
   if (n_points > ds->max_frame_points)
-    return fail(ctx, DDDMR_ERR_CAPACITY, "set_depth_frame: %zu points > max_frame_points %u", n_points, ds->max_frame_points);
+    return fail(ctx, DDDMR_ERR_CAPACITY, "%s: %zu points > max_frame_points %u", what, n_points, ds->max_frame_points);
   // purgeStaleObservations (depth_camera_observation_buffer.cpp:203-231) with last_updated_ = stamp_ns decides from
   // the stamps alone, so which observations stay is known before the frame is processed
   const int64_t stamp_us = stamp_ns / 1000;          // pcl_conversions::toPCL keeps whole microseconds
@@ -913,7 +976,7 @@ int dddmr_rollout_set_depth_frame(dddmr_rollout_ctx* ctx, int32_t source_id, con
   const bool none_leaves = kept.size() == ds->frames.size();
   const bool new_alive = stays(stamp_us, true);
   if (kept.size() + (new_alive ? 1 : 0) > ds->max_frames)
-    return fail(ctx, DDDMR_ERR_CAPACITY, "set_depth_frame: %zu observations alive > max_frames %u", kept.size() + 1, ds->max_frames);
+    return fail(ctx, DDDMR_ERR_CAPACITY, "%s: %zu observations alive > max_frames %u", what, kept.size() + 1, ds->max_frames);
   // Nothing leaves: the frame is appended behind the alive ones.  Otherwise the ones that stay are copied to the
   // other buffer (device to device) and the frame is built behind them; the buffers swap on success only.
   const int dst_buf = none_leaves ? ds->cur : ds->cur ^ 1;
@@ -937,15 +1000,16 @@ int dddmr_rollout_set_depth_frame(dddmr_rollout_ctx* ctx, int32_t source_id, con
   dp.zmin = ds->zmin;
   dp.zmax = ds->zmax;
   dp.n = (int)n_points;
-  uint32_t n_out = 0;
-  const int rc = depth_feed(*ds, dp, xyz, stride_bytes, ds->buf[dst_buf] + kept_points, ctx->copy_stream, &n_out);
-  if (rc != 0) return fail(ctx, DDDMR_ERR_HIP, "set_depth_frame: depth feed failed (%d)", rc);
+  uint32_t n_out = 0, n_camera = 0;
+  const int rc = di ? depth_image_feed(*ds, *di, dp, depth_mm, stride_bytes, ds->buf[dst_buf] + kept_points, ctx->copy_stream, &n_camera, &n_out)
+                    : depth_feed(*ds, dp, xyz, stride_bytes, ds->buf[dst_buf] + kept_points, ctx->copy_stream, &n_out);
+  if (rc != 0) return fail(ctx, DDDMR_ERR_HIP, "%s: depth feed failed (%d)", what, rc);
   const size_t n_source = kept_points + (new_alive ? n_out : 0);
   size_t total = n_source;
   for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i)
     if (i != source_id) total += ctx->src_n[i];
   if (total > ctx->cfg.max_points)
-    return fail(ctx, DDDMR_ERR_CAPACITY, "set_depth_frame: the sensors' observations together (%zu points) exceed max_points %u", total, ctx->cfg.max_points);
+    return fail(ctx, DDDMR_ERR_CAPACITY, "%s: the sensors' observations together (%zu points) exceed max_points %u", what, total, ctx->cfg.max_points);
   // commit: from here on nothing fails before the aggregate is rebuilt from the new state
   const std::vector<DepthFrame> old_frames = ds->frames;
   const int old_cur = ds->cur;
@@ -964,9 +1028,57 @@ int dddmr_rollout_set_depth_frame(dddmr_rollout_ctx* ctx, int32_t source_id, con
     ctx->src_n[source_id] = old_n;
     return prc;
   }
+  if (di) {                                          // the stage-one cloud of an accepted image becomes the source's latest
+    di->cur ^= 1;
+    di->n_cloud = n_camera;
+  }
+  if (n_camera_points) *n_camera_points = n_camera;
   if (n_frame_points) *n_frame_points = n_out;
   if (n_source_points) *n_source_points = (uint32_t)n_source;
   if (n_aggregate_points) *n_aggregate_points = n_all;
+  return DDDMR_OK;
+}
+
+int dddmr_rollout_set_depth_frame(dddmr_rollout_ctx* ctx, int32_t source_id, const float* xyz, size_t n_points,
+                                  size_t stride_bytes, const double T_base_sensor[7], const double T_gbl_base[7],
+                                  int64_t stamp_ns, uint32_t* n_frame_points, uint32_t* n_source_points,
+                                  uint32_t* n_aggregate_points) {
+  if (!ctx || !T_base_sensor || !T_gbl_base) return DDDMR_ERR_BAD_ARG;
+  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_frame: source %d (at most %d sensors)", source_id, dddmr_rollout_ctx::kMaxSources);
+  if (n_points > 0 && (!xyz || stride_bytes < 12 || stride_bytes % 4 != 0))
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_frame: bad pointer/stride");
+  return set_depth_impl(ctx, "set_depth_frame", source_id, xyz, n_points, nullptr, stride_bytes, T_base_sensor, T_gbl_base, stamp_ns,
+                        nullptr, n_frame_points, n_source_points, n_aggregate_points);
+}
+
+int dddmr_rollout_set_depth_image(dddmr_rollout_ctx* ctx, int32_t source_id, const uint16_t* depth_mm, size_t row_stride_bytes,
+                                  const double T_base_optical[7], const double T_gbl_base[7], int64_t stamp_ns,
+                                  uint32_t* n_camera_points, uint32_t* n_frame_points, uint32_t* n_source_points,
+                                  uint32_t* n_aggregate_points) {
+  if (!ctx || !T_base_optical || !T_gbl_base) return DDDMR_ERR_BAD_ARG;
+  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_image: source %d (at most %d sensors)", source_id, dddmr_rollout_ctx::kMaxSources);
+  if (!depth_mm) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_image: null image");
+  return set_depth_impl(ctx, "set_depth_image", source_id, nullptr, 0, depth_mm, row_stride_bytes, T_base_optical, T_gbl_base, stamp_ns,
+                        n_camera_points, n_frame_points, n_source_points, n_aggregate_points);
+}
+
+int dddmr_rollout_get_depth_image_cloud(dddmr_rollout_ctx* ctx, int32_t source_id, float* xyz_out, size_t capacity, size_t* n_points) {
+  if (!ctx || !n_points) return DDDMR_ERR_BAD_ARG;
+  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "get_depth_image_cloud: source %d (at most %d sensors)", source_id, dddmr_rollout_ctx::kMaxSources);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  const DepthImage* di = ctx->dimg[source_id];
+  if (!di) return fail(ctx, DDDMR_ERR_BAD_ARG, "get_depth_image_cloud: source %d is not a depth image source", source_id);
+  *n_points = di->n_cloud;
+  if (!xyz_out) return DDDMR_OK;
+  if (capacity < di->n_cloud) return fail(ctx, DDDMR_ERR_CAPACITY, "get_depth_image_cloud: capacity %zu < %u", capacity, di->n_cloud);
+  if (di->n_cloud) {
+    HIPCHK(ctx, hipMemcpyAsync(xyz_out, di->cloud[di->cur], (size_t)di->n_cloud * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->copy_stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+  }
   return DDDMR_OK;
 }
 

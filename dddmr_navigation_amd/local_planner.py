@@ -172,6 +172,48 @@ class LocalPlanner:
                                                             C.byref(n_all)))
         return int(n_frame.value), int(n_src.value), int(n_all.value)
 
+    def set_depth_image_source(self, source_id: int, min_obstacle_height: float, max_obstacle_height: float, width: int, height: int,
+                               fx: float, fy: float, cx: float, cy: float, max_distance: float = 4.0, leaf_size: float = 0.05,
+                               sample_step: int = 2, observation_persistence_ns: int = 0, max_frame_points: Optional[int] = None,
+                               max_frames: int = 1, drop_zero: bool = False):
+        """Make `source_id` a depth camera source fed 16UC1 images: DepthImg2PointCloud's parameters (defaults: the
+        node's own) in front of DepthCameraObservationBuffer's.  max_frame_points bounds the sampled pixels."""
+        if max_frame_points is None:
+            step = max(int(sample_step), 1)
+            max_frame_points = -(-int(height) // step) * -(-int(width) // step)
+        cfg = K.DepthSourceConfig(float(min_obstacle_height), float(max_obstacle_height), int(observation_persistence_ns),
+                                  int(max_frame_points), int(max_frames))
+        icfg = K.DepthImageConfig(int(width), int(height), float(fx), float(fy), float(cx), float(cy), float(max_distance),
+                                  float(leaf_size), int(sample_step), K.DEPTH_IMAGE_DROP_ZERO if drop_zero else 0)
+        self._check(self._lib.dddmr_rollout_set_depth_image_source(self._ctx, int(source_id), C.byref(cfg), C.byref(icfg)))
+
+    def set_depth_image(self, source_id: int, depth_mm: np.ndarray, T_base_optical, T_gbl_base, stamp_ns: int):
+        """One [height, width] uint16 millimetre image (rows may be padded: any array whose pixels of a row are adjacent is
+        passed as it is) through cbDepthImg and bufferCloud: returns (stage-one points = what the node would publish,
+        points of this frame's observation, points of the source's alive frames, points of the aggregate)."""
+        img = np.asarray(depth_mm)
+        if img.dtype != np.uint16 or img.ndim != 2:
+            raise ValueError("depth image must be [height, width] uint16")
+        if img.shape[1] > 1 and img.strides[1] != 2 or img.strides[0] < 2 * img.shape[1]:
+            img = np.ascontiguousarray(img)
+        tbo = (C.c_double * 7)(*[float(v) for v in T_base_optical])
+        tgb = (C.c_double * 7)(*[float(v) for v in T_gbl_base])
+        n_cam, n_frame, n_src, n_all = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.dddmr_rollout_set_depth_image(self._ctx, int(source_id), img.ctypes.data_as(C.c_void_p), img.strides[0],
+                                                            tbo, tgb, int(stamp_ns), C.byref(n_cam), C.byref(n_frame),
+                                                            C.byref(n_src), C.byref(n_all)))
+        return int(n_cam.value), int(n_frame.value), int(n_src.value), int(n_all.value)
+
+    def get_depth_image_cloud(self, source_id: int) -> np.ndarray:
+        """The stage-one cloud of the source's latest image, [K,3] float32 in the optical frame (the node's
+        point_cloud_from_depth topic)."""
+        n = C.c_size_t(0)
+        self._check(self._lib.dddmr_rollout_get_depth_image_cloud(self._ctx, int(source_id), None, 0, C.byref(n)))
+        out = np.zeros((max(n.value, 1), 3), dtype=np.float32)
+        self._check(self._lib.dddmr_rollout_get_depth_image_cloud(self._ctx, int(source_id), out.ctypes.data_as(C.c_void_p),
+                                                                  out.shape[0], C.byref(n)))
+        return out[: n.value]
+
     def set_stitcher(self, stitcher_num: int):
         """cbSensor's `stitcher_num` (multilayer_spinning_lidar.cpp:185-200): feed the last N raw scans together."""
         self._check(self._lib.dddmr_rollout_set_stitcher(self._ctx, int(stitcher_num)))

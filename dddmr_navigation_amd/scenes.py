@@ -290,15 +290,9 @@ def lidar_scan(cloud_xyz: np.ndarray, sensor_xyz=(0.0, 0.0, 0.5), seed: int = 0,
     return pts.astype(np.float32)
 
 
-def depth_frame(cloud_xyz: np.ndarray, T_gbl_sensor, width: int = 640, height: int = 480, fov_w: float = 1.5,
-                fov_v: float = 1.0, max_range: float = 8.0, seed: int = 0, sigma: float = 0.003,
-                patch: float = 0.075) -> np.ndarray:
-    """The scene seen by a depth camera at T_gbl_sensor (x y z qx qy qz qw; camera_link axes: x forward, y left,
-    z up), fov_w x fov_v radians, as a camera driver delivers it: an organised [height * width, 3] float32 cloud in
-    the SENSOR frame, row-major from the top-left pixel, NaN where a pixel has no return.  Every scene point is a
-    square patch of `patch` metres facing the camera (the lattice spacing plus its jitter, so surfaces close up);
-    per pixel the nearest patch wins and the return lies on the pixel's own ray at that depth, with gaussian depth
-    noise from the seed (sigma metres at 1 m, growing with depth squared as stereo depth does).  CPU only."""
+def _depth_raycast(cloud_xyz, T_gbl_sensor, width, height, fov_w, fov_v, max_range, seed, sigma, patch):
+    """The ray caster behind depth_frame and depth_image: per pixel (row-major from the top-left) the noisy depth along
+    camera_link x of the nearest patch, inf where nothing is hit -> (depth [height * width], hit, fx, fy in pixels)."""
     rng = np.random.Generator(np.random.PCG64(seed))
     T = np.asarray(T_gbl_sensor, dtype=np.float64)
     x, y, z, w = T[3], T[4], T[5], T[6]
@@ -330,9 +324,39 @@ def depth_frame(cloud_xyz: np.ndarray, T_gbl_sensor, width: int = 640, height: i
             np.minimum.at(depth, r[m] * width + c[m], d[k][m])
     hit = np.isfinite(depth)
     depth = depth + rng.normal(0.0, 1.0, size=depth.shape) * sigma * np.where(hit, depth, 0.0) ** 2
+    return depth, hit, fx, fy
+
+
+def depth_frame(cloud_xyz: np.ndarray, T_gbl_sensor, width: int = 640, height: int = 480, fov_w: float = 1.5,
+                fov_v: float = 1.0, max_range: float = 8.0, seed: int = 0, sigma: float = 0.003,
+                patch: float = 0.075) -> np.ndarray:
+    """The scene seen by a depth camera at T_gbl_sensor (x y z qx qy qz qw; camera_link axes: x forward, y left,
+    z up), fov_w x fov_v radians, as a camera driver delivers it: an organised [height * width, 3] float32 cloud in
+    the SENSOR frame, row-major from the top-left pixel, NaN where a pixel has no return.  Every scene point is a
+    square patch of `patch` metres facing the camera (the lattice spacing plus its jitter, so surfaces close up);
+    per pixel the nearest patch wins and the return lies on the pixel's own ray at that depth, with gaussian depth
+    noise from the seed (sigma metres at 1 m, growing with depth squared as stereo depth does).  CPU only."""
+    depth, hit, fx, fy = _depth_raycast(cloud_xyz, T_gbl_sensor, width, height, fov_w, fov_v, max_range, seed, sigma, patch)
     cols = (np.arange(width) + 0.5 - 0.5 * width) / fx
     rows = (np.arange(height) + 0.5 - 0.5 * height) / fy
     out = np.full((height * width, 3), np.nan, dtype=np.float32)
     px = np.stack([depth, -depth * np.tile(cols, height), -depth * np.repeat(rows, width)], axis=1)
     out[hit] = px[hit].astype(np.float32)
     return out
+
+
+# camera_link (x forward, y left, z up) <- optical frame (z forward, x right, y down), x y z qx qy qz qw: the fixed
+# rotation between a camera's body frame and the frame its depth image is deprojected in
+T_LINK_OPTICAL = (0.0, 0.0, 0.0, -0.5, 0.5, -0.5, 0.5)
+
+
+def depth_image(cloud_xyz: np.ndarray, T_gbl_sensor, width: int = 640, height: int = 480, fov_w: float = 1.5,
+                fov_v: float = 1.0, max_range: float = 8.0, seed: int = 0, sigma: float = 0.003, patch: float = 0.075):
+    """The view depth_frame renders, as the camera publishes it: ([height, width] uint16 depth along the optical axis
+    in millimetres, 0 where a pixel has no return; (fx, fy, cx, cy) = CameraInfo K[0], K[4], K[2], K[5]).  depth_frame
+    puts pixel centres at u + 0.5 - width / 2, so cx = width / 2 - 0.5, cy = height / 2 - 0.5.  The optical frame is
+    T_gbl_sensor * T_LINK_OPTICAL.  CPU only."""
+    depth, hit, fx, fy = _depth_raycast(cloud_xyz, T_gbl_sensor, width, height, fov_w, fov_v, max_range, seed, sigma, patch)
+    mm = np.rint(np.where(hit, depth, 0.0) * 1000.0)
+    img = np.clip(mm, 0, 65535).astype(np.uint16).reshape(height, width)
+    return img, (float(fx), float(fy), 0.5 * width - 0.5, 0.5 * height - 0.5)

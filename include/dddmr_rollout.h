@@ -299,6 +299,59 @@ int dddmr_rollout_set_depth_frame(dddmr_rollout_ctx* ctx, int32_t source_id, con
                                   const double T_gbl_base[7], int64_t stamp_ns, uint32_t* n_frame_points,
                                   uint32_t* n_source_points, uint32_t* n_aggregate_points);
 
+/* Depth IMAGE sources: the image as the camera publishes it goes to the device, which does what the
+   reference's own node in front of the layer does (DepthImg2PointCloud::cbDepthImg,
+   dddmr_perception_3d/utils/depthimg2pointcloud_node.cpp:96-157) and then bufferCloud as above, in one call.
+   Stage one, per image: 16UC1 only (the node reads unsigned shorts whatever the encoding says), rows may
+   be padded; float cx = K[2], cy = K[5], fx = 1 / K[0], fy = 1 / K[4] (double division, float result);
+   for v = 0, step, ... < height and u = 0, step, ... < width: float z = d * 0.001 (double product), the
+   pixel is skipped when (double)z > max_distance, else x = ((float)u - cx) * z * fx,
+   y = ((float)v - cy) * z * fy in float, nothing fused; then pcl::VoxelGrid with leaf_size in the optical
+   frame (membership floor(p * (1.0f / (float)leaf_size)), centroid = sum / count; the device sums in
+   double).  The order of the points is unspecified.  Stage two: exactly what dddmr_rollout_set_depth_frame
+   does with a cloud, applied to stage one's centroids, T_base_optical taking them to the base frame.
+   Every rule stated above for cloud frames holds for images.
+
+   A pixel of depth 0 is KEPT, as the node keeps it (it only tests isnan(z) || z > max_distance): every
+   pixel without a return becomes the point (0, 0, 0) of the optical frame, all of them end in one voxel,
+   and only the height band removes that point, when the camera sits outside the band.
+   Difference from the reference, on purpose: with DDDMR_DEPTH_IMAGE_DROP_ZERO such pixels are dropped.
+   pcl::VoxelGrid returns its input unchanged when its voxel box has more than INT_MAX cells; that is not
+   restated: dddmr_rollout_set_depth_image_source refuses (DDDMR_ERR_BAD_ARG) any intrinsics, max_distance
+   and leaf_size whose worst-case frustum box (every pixel anywhere between depth 0 and
+   min(max_distance, 65.535 m)) could reach 2^31 cells or 2^20 cells from the origin along an axis.
+
+   A source is configured either for clouds (dddmr_rollout_set_depth_source) or for images; feeding it the
+   other kind is DDDMR_ERR_BAD_ARG, as are sample_step 0, unknown flags, a row stride below 2 * width and
+   a max_frame_points (of dddmr_depth_source_config: for an image source it bounds the sampled pixels)
+   below ceil(height / sample_step) * ceil(width / sample_step).  Re-configuring a source with either
+   call empties it. */
+#define DDDMR_DEPTH_IMAGE_DROP_ZERO 1u
+typedef struct {
+  uint32_t width, height;        /* pixels */
+  double fx, fy, cx, cy;         /* CameraInfo K[0], K[4], K[2], K[5] */
+  double max_distance;           /* node parameter, default 4.0 (shipped launch: 6.0) */
+  double leaf_size;              /* node parameter, default 0.05 */
+  uint32_t sample_step;          /* node parameter, default 2 (shipped launch: 4); >= 1 */
+  uint32_t flags;                /* DDDMR_DEPTH_IMAGE_* */
+} dddmr_depth_image_config;
+
+int dddmr_rollout_set_depth_image_source(dddmr_rollout_ctx* ctx, int32_t source_id,
+                                         const dddmr_depth_source_config* cfg,
+                                         const dddmr_depth_image_config* image_cfg);
+/* depth_mm: height rows of row_stride_bytes, width uint16 millimetres each.  *n_camera_points: stage
+   one's points (what the node would publish); the other counts as for dddmr_rollout_set_depth_frame
+   (each may be NULL). */
+int dddmr_rollout_set_depth_image(dddmr_rollout_ctx* ctx, int32_t source_id, const uint16_t* depth_mm,
+                                  size_t row_stride_bytes, const double T_base_optical[7],
+                                  const double T_gbl_base[7], int64_t stamp_ns, uint32_t* n_camera_points,
+                                  uint32_t* n_frame_points, uint32_t* n_source_points,
+                                  uint32_t* n_aggregate_points);
+/* The stage-one cloud of the source's latest accepted image, optical frame, packed x y z: the node's
+   point_cloud_from_depth topic.  xyz_out == NULL only reports *n_points. */
+int dddmr_rollout_get_depth_image_cloud(dddmr_rollout_ctx* ctx, int32_t source_id, float* xyz_out,
+                                        size_t capacity, size_t* n_points);
+
 /* Copy the current aggregate observation back (debug / parity of set_scan). */
 int dddmr_rollout_get_cloud(dddmr_rollout_ctx* ctx, float* xyzi_out, size_t capacity,
                             size_t* n_points);

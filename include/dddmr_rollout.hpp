@@ -98,6 +98,26 @@ class LocalPlanner {
                                         &c.frame, &c.source, &c.aggregate));
     return c;
   }
+  // depth IMAGE source: the 16UC1 image through DepthImg2PointCloud::cbDepthImg and bufferCloud on the device
+  void setDepthImageSource(int32_t source_id, const dddmr_depth_source_config& cfg, const dddmr_depth_image_config& image_cfg) {
+    check(dddmr_rollout_set_depth_image_source(ctx_, source_id, &cfg, &image_cfg));
+  }
+  struct DepthImageCounts { uint32_t camera, frame, source, aggregate; };
+  DepthImageCounts setDepthImage(int32_t source_id, const uint16_t* depth_mm, size_t row_stride_bytes,
+                                 const double T_base_optical[7], const double T_gbl_base[7], int64_t stamp_ns) {
+    DepthImageCounts c{};
+    check(dddmr_rollout_set_depth_image(ctx_, source_id, depth_mm, row_stride_bytes, T_base_optical, T_gbl_base, stamp_ns,
+                                        &c.camera, &c.frame, &c.source, &c.aggregate));
+    return c;
+  }
+  // the stage-one cloud of the source's latest image, optical frame (the node's point_cloud_from_depth topic)
+  std::vector<std::array<float, 3>> getDepthImageCloud(int32_t source_id) {
+    size_t n = 0;
+    check(dddmr_rollout_get_depth_image_cloud(ctx_, source_id, nullptr, 0, &n));
+    std::vector<std::array<float, 3>> out(n);
+    if (n) check(dddmr_rollout_get_depth_image_cloud(ctx_, source_id, &out[0][0], n, &n));
+    return out;
+  }
   // prune plan poses, x y z qx qy qz qw each (output of Local_Planner::prunePlan)
   void setPlan(const double* poses_xyz_qxyzw, size_t n_poses) {
     check(dddmr_rollout_set_prune_plan(ctx_, poses_xyz_qxyzw, n_poses));
