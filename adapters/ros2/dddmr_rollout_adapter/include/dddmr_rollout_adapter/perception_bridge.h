@@ -9,6 +9,8 @@
 //   DepthCameraObservationBuffer::bufferCloud, local mode
 //                                    (plugins/depth_camera/depth_camera_observation_buffer.cpp:78-187) -> feedDepthFrame()
 //   DepthImg2PointCloud::cbDepthImg + bufferCloud   (utils/depthimg2pointcloud_node.cpp:96-157)      -> feedDepthImage()
+//   ... bufferCloud's frustum                       (depth_camera_observation_buffer.cpp:134-174)    -> feedDepthFrustum()
+//   DepthCameraLayer::selfClear's decision tree     (plugins/depth_camera/depth_camera_layer.cpp:324-422) -> depthClearVerdicts()
 //
 // Everything here is a template over the ROS / PCL types it is handed (geometry_msgs TransformStamped,
 // pcl::PointCloud<...>): this header includes neither, so it is syntax-checked in a plain C++ toolchain
@@ -130,6 +132,74 @@ inline int feedDepthImage(
     ctx, source, reinterpret_cast<const uint16_t *>(data), step, b2o, g2b, stamp_ns, n_camera_out, n_frame_out,
     n_source_out, n_aggregate_out);
   if (rc == DDDMR_OK) {SharedContext::noteDeviceFeed();}
+  return rc;
+}
+
+// The frustum half of bufferCloud: call beside feedDepthFrame / feedDepthImage with m2s = lookupTransform(global_frame_,
+// origin_frame) and the buffer's FOV_W_ / FOV_V_ / min_ / max_detect_distance_.  Replaces the source's frustum; no feed
+// is noted (the aggregate does not change).  Cameras are numbered in the order of their names in observation_buffers_.
+template<class TransformStamped>
+inline int feedDepthFrustum(
+  dddmr_rollout_ctx * ctx, int source, double FOV_W, double FOV_V, double min_detect_distance,
+  double max_detect_distance, const TransformStamped & trans_m2s)
+{
+  if (!ctx) {return DDDMR_ERR_BAD_ARG;}
+  double m2s[7];
+  toPose7(trans_m2s, m2s);
+  dddmr_depth_frustum_config cfg;
+  cfg.FOV_W = FOV_W; cfg.FOV_V = FOV_V;
+  cfg.obstacle_min_range = min_detect_distance; cfg.obstacle_max_range = max_detect_distance;
+  return dddmr_rollout_set_depth_frustum(ctx, source, &cfg, m2s);
+}
+
+// One marking selfClear's window loop selected: its voxel key (the three map keys) and its stored cluster pc_.
+template<class Cloud>
+struct DepthMarkingRef
+{
+  int32_t x, y, z;
+  const Cloud * pc;
+};
+
+// selfClear's decision tree for the markings of the current window, on the device: kept[i] != 0 means "push to
+// current_observation_ptr", 0 means removePCPtr.  The caller keeps what selfClear does around it: the early returns,
+// trans_gbl2b_, the window bounds and the getXIter / lower_bound walk that collects `markings` (skipping null pc_),
+// and afterwards removePCPtr / pc_current_window_ / the casting markers for the verdicts.  branch (optional) receives
+// 1 outside the frustums, 2 attached, 3 inside.  On any code but DDDMR_OK nothing is written and the caller runs the
+// reference's CPU loop for this pass.
+template<class Cloud>
+inline int depthClearVerdicts(
+  dddmr_rollout_ctx * ctx, double resolution, double height_resolution,
+  const std::vector<DepthMarkingRef<Cloud>> & markings, std::vector<uint8_t> & kept,
+  std::vector<uint8_t> * branch = nullptr, std::vector<uint32_t> * engaged = nullptr)
+{
+  if (!ctx) {return DDDMR_ERR_BAD_ARG;}
+  const size_t m = markings.size();
+  std::vector<int32_t> voxel(3 * m);
+  std::vector<uint32_t> offsets(m + 1, 0u);
+  for (size_t i = 0; i < m; ++i) {
+    if (!markings[i].pc) {return DDDMR_ERR_BAD_ARG;}
+    voxel[3 * i] = markings[i].x; voxel[3 * i + 1] = markings[i].y; voxel[3 * i + 2] = markings[i].z;
+    offsets[i + 1] = offsets[i] + static_cast<uint32_t>(markings[i].pc->points.size());
+  }
+  std::vector<float> xyz(3 * static_cast<size_t>(offsets[m]));
+  size_t at = 0;
+  for (size_t i = 0; i < m; ++i) {
+    for (const auto & p : markings[i].pc->points) {
+      xyz[at++] = p.x; xyz[at++] = p.y; xyz[at++] = p.z;
+    }
+  }
+  std::vector<uint8_t> verdict(m);
+  std::vector<uint32_t> eng(m);
+  const int rc = dddmr_rollout_depth_clear_verdicts(
+    ctx, resolution, height_resolution, voxel.data(), offsets.data(), xyz.data(), m, verdict.data(), eng.data());
+  if (rc != DDDMR_OK) {return rc;}
+  kept.resize(m);
+  if (branch) {branch->resize(m);}
+  for (size_t i = 0; i < m; ++i) {
+    kept[i] = verdict[i] & 1u;
+    if (branch) {(*branch)[i] = (verdict[i] >> 1) & 3u;}
+  }
+  if (engaged) {engaged->swap(eng);}
   return rc;
 }
 

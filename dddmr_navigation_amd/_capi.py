@@ -185,6 +185,19 @@ class DepthImageConfig(C.Structure):
     ]
 
 
+class DepthFrustumConfig(C.Structure):
+    """dddmr_depth_frustum_config: the depth buffer's FOV_W / FOV_V (radians) and obstacle_min_range / obstacle_max_range."""
+    _fields_ = [
+        ("FOV_W", C.c_double), ("FOV_V", C.c_double),
+        ("obstacle_min_range", C.c_double), ("obstacle_max_range", C.c_double),
+    ]
+
+
+# dddmr_rollout_depth_clear_verdicts: bit 0 of a verdict = kept, bits 1-2 = the branch that decided
+DEPTH_CLEAR_KEPT = 1
+DEPTH_CLEAR_OUTSIDE, DEPTH_CLEAR_ATTACHED, DEPTH_CLEAR_INSIDE = 1, 2, 3
+
+
 class RolloutDebug(C.Structure):
     _fields_ = [
         ("costs", C.POINTER(C.c_double)),
@@ -238,6 +251,11 @@ EXPORTED_SYMBOLS = (
     "dddmr_rollout_set_depth_image_source",
     "dddmr_rollout_set_depth_image",
     "dddmr_rollout_get_depth_image_cloud",
+    "dddmr_rollout_set_depth_frustum",
+    "dddmr_rollout_get_depth_frustum",
+    "dddmr_rollout_depth_frustum_test",
+    "dddmr_rollout_depth_clear_verdicts",
+    "dddmr_rollout_depth_clear_launches",
     "dddmr_rollout_stream_ceiling",
     "dddmr_rollout_selftest_sincos",
     "dddmr_rollout_last_error",
@@ -362,6 +380,17 @@ def load_library() -> C.CDLL:
     lib.dddmr_rollout_set_depth_image.restype = C.c_int
     lib.dddmr_rollout_get_depth_image_cloud.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.dddmr_rollout_get_depth_image_cloud.restype = C.c_int
+    lib.dddmr_rollout_set_depth_frustum.argtypes = [ctx_p, C.c_int32, C.POINTER(DepthFrustumConfig), C.POINTER(C.c_double)]
+    lib.dddmr_rollout_set_depth_frustum.restype = C.c_int
+    lib.dddmr_rollout_get_depth_frustum.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.dddmr_rollout_get_depth_frustum.restype = C.c_int
+    lib.dddmr_rollout_depth_frustum_test.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
+    lib.dddmr_rollout_depth_frustum_test.restype = C.c_int
+    lib.dddmr_rollout_depth_clear_verdicts.argtypes = [ctx_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                       C.c_void_p, C.c_void_p]
+    lib.dddmr_rollout_depth_clear_verdicts.restype = C.c_int
+    lib.dddmr_rollout_depth_clear_launches.argtypes = [ctx_p, C.POINTER(C.c_uint32)]
+    lib.dddmr_rollout_depth_clear_launches.restype = C.c_int
     lib.dddmr_rollout_stream_ceiling.argtypes = [ctx_p, C.c_size_t, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.dddmr_rollout_stream_ceiling.restype = C.c_int
     lib.dddmr_rollout_selftest_sincos.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]

@@ -28,6 +28,7 @@
 #include "perception_kernels.hip.h"
 #include "depth_feed.hip.h"
 #include "depth_image.hip.h"
+#include "depth_clear.hip.h"
 #include "measure_kernels.hip.h"
 
 using namespace dddmr;
@@ -221,6 +222,11 @@ struct dddmr_rollout_ctx {
   // non-null for a depth source that is fed images (dddmr_rollout_set_depth_image_source); depth[i] is set as well
   DepthImage* dimg[kMaxSources] = {};
   bool src_is_lidar[kMaxSources] = {};                 // a scan has been fed under this id
+  // frustums of the depth sources (dddmr_rollout_set_depth_frustum) and the clearing verdicts' scratch (depth_clear.hip.h)
+  DcFrustum frustum[kMaxSources] = {};
+  bool has_frustum[kMaxSources] = {};
+  DepthClear* dclear = nullptr;                        // allocated by the first verdict / point-test call
+  uint64_t depth_epoch = 1;                            // bumped whenever a depth source's observation changes
 
   // pinned host memory
   float4* cloud_stage[kCloudBufs] = {nullptr, nullptr, nullptr};   // pinned staging, one per device cloud buffer
@@ -465,6 +471,7 @@ size_t dddmr_rollout_sizeof(int which) {
     case 7: return sizeof(dddmr_marking_stats);
     case 8: return sizeof(dddmr_depth_source_config);
     case 9: return sizeof(dddmr_depth_image_config);
+    case 10: return sizeof(dddmr_depth_frustum_config);
     default: return 0;
   }
 }
@@ -507,6 +514,7 @@ void dddmr_rollout_destroy(dddmr_rollout_ctx* ctx) {
   for (void* p : dev)
     if (p) (void)hipFree(p);
   perception_free(ctx->feed);
+  if (ctx->dclear) { dc_free(*ctx->dclear); delete ctx->dclear; }
   for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) {
     if (ctx->depth[i]) { depth_free(*ctx->depth[i]); delete ctx->depth[i]; ctx->src_cloud[i] = nullptr; }
     if (ctx->dimg[i]) { dimg_free(*ctx->dimg[i]); delete ctx->dimg[i]; }
@@ -898,6 +906,8 @@ static int set_depth_source_impl(dddmr_rollout_ctx* ctx, const char* what, int32
     }
     ctx->src_cloud[source_id] = nullptr;
     ctx->src_n[source_id] = 0;
+    ctx->has_frustum[source_id] = false;               // the frustum belongs to the observations that just left
+    ++ctx->depth_epoch;
   }
   auto* ds = new DepthSource();
   ds->zmin = cfg->min_obstacle_height;
@@ -1019,6 +1029,7 @@ static int set_depth_impl(dddmr_rollout_ctx* ctx, const char* what, int32_t sour
   ds->cur = dst_buf;
   ctx->src_cloud[source_id] = ds->buf[ds->cur];
   ctx->src_n[source_id] = (uint32_t)n_source;
+  ++ctx->depth_epoch;                                // the clearing verdicts' grid is rebuilt by the next call that needs it
   uint32_t n_all = 0;
   const int prc = publish_sources(ctx, &n_all);
   if (prc != DDDMR_OK) {                             // a failed copy: the source goes back to what the published aggregate holds
@@ -1079,6 +1090,193 @@ int dddmr_rollout_get_depth_image_cloud(dddmr_rollout_ctx* ctx, int32_t source_i
     HIPCHK(ctx, hipMemcpyAsync(xyz_out, di->cloud[di->cur], (size_t)di->n_cloud * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->copy_stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
   }
+  return DDDMR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Depth camera frustums, point tests and selfClear's clearing verdicts (depth_clear.hip.h)
+// ---------------------------------------------------------------------------
+int dddmr_rollout_set_depth_frustum(dddmr_rollout_ctx* ctx, int32_t source_id, const dddmr_depth_frustum_config* cfg,
+                                    const double T_gbl_sensor[7]) {
+  if (!ctx) return DDDMR_ERR_BAD_ARG;
+  if (!cfg || !T_gbl_sensor || source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_frustum: source %d (at most %d sensors) / null argument", source_id, dddmr_rollout_ctx::kMaxSources);
+  const double kPi = 3.14159265358979323846;
+  if (!(cfg->FOV_W > 0.0 && cfg->FOV_W < kPi) || !(cfg->FOV_V > 0.0 && cfg->FOV_V < kPi) || !(cfg->obstacle_min_range > 0.0) ||
+      !(cfg->obstacle_max_range > cfg->obstacle_min_range) || !std::isfinite(cfg->obstacle_max_range))
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_frustum: FOV %g x %g rad, range %g .. %g m", cfg->FOV_W, cfg->FOV_V, cfg->obstacle_min_range,
+                cfg->obstacle_max_range);
+  for (int i = 0; i < 7; ++i)
+    if (!std::isfinite(T_gbl_sensor[i])) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_frustum: non-finite transform");
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  if (!ctx->depth[source_id]) return fail(ctx, DDDMR_ERR_STATE, "set_depth_frustum: source %d is not a depth camera source", source_id);
+  double R[9];
+  quat_to_rot(T_gbl_sensor, R);
+  frustum_build(ctx->frustum[source_id], cfg->FOV_W, cfg->FOV_V, cfg->obstacle_min_range, cfg->obstacle_max_range, R, T_gbl_sensor);
+  ctx->has_frustum[source_id] = true;
+  return DDDMR_OK;
+}
+
+int dddmr_rollout_get_depth_frustum(dddmr_rollout_ctx* ctx, int32_t source_id, float vertices[8][3], float normals[6][3],
+                                    float planes[6][4], float origin[3]) {
+  if (!ctx) return DDDMR_ERR_BAD_ARG;
+  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "get_depth_frustum: source %d (at most %d sensors)", source_id, dddmr_rollout_ctx::kMaxSources);
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  if (!ctx->depth[source_id] || !ctx->has_frustum[source_id])
+    return fail(ctx, DDDMR_ERR_STATE, "get_depth_frustum: source %d has no frustum", source_id);
+  const DcFrustum& F = ctx->frustum[source_id];
+  if (vertices) std::memcpy(vertices, F.vtx, sizeof(F.vtx));
+  if (normals) std::memcpy(normals, F.nrm, sizeof(F.nrm));
+  if (planes) std::memcpy(planes, F.pl, sizeof(F.pl));
+  if (origin)
+    for (int a = 0; a < 3; ++a) origin[a] = (float)F.origin[a];
+  return DDDMR_OK;
+}
+
+// The frustums of all depth sources in source order; every depth source must have one.  producer_mu held.
+static int depth_frustums(dddmr_rollout_ctx* ctx, const char* what, DcFrustums* S) {
+  S->n = 0;
+  for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) {
+    if (!ctx->depth[i]) continue;
+    if (!ctx->has_frustum[i]) return fail(ctx, DDDMR_ERR_STATE, "%s: depth source %d has no frustum yet", what, i);
+    S->f[S->n++] = ctx->frustum[i];
+  }
+  if (S->n == 0) return fail(ctx, DDDMR_ERR_STATE, "%s: the context has no depth camera source", what);
+  return DDDMR_OK;
+}
+
+static int depth_clear_scratch(dddmr_rollout_ctx* ctx, const char* what) {
+  if (ctx->dclear) return DDDMR_OK;
+  auto* d = new DepthClear();
+  if (dc_alloc(*d, ctx->cfg.max_points) != 0) {
+    dc_free(*d);
+    delete d;
+    return fail(ctx, DDDMR_ERR_HIP, "%s: scratch allocation failed", what);
+  }
+  ctx->dclear = d;
+  return DDDMR_OK;
+}
+
+int dddmr_rollout_depth_frustum_test(dddmr_rollout_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes,
+                                     uint8_t* in_frustums_out, uint8_t* attach_out) {
+  if (!ctx) return DDDMR_ERR_BAD_ARG;
+  if (n > 0 && (!xyz || stride_bytes < 12 || stride_bytes % 4 != 0)) return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_frustum_test: bad pointer/stride");
+  if (n > (1u << 28)) return fail(ctx, DDDMR_ERR_CAPACITY, "depth_frustum_test: %zu points", n);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  DcFrustums S;
+  int rc = depth_frustums(ctx, "depth_frustum_test", &S);
+  if (rc != DDDMR_OK) return rc;
+  if (n == 0) return DDDMR_OK;
+  if ((rc = depth_clear_scratch(ctx, "depth_frustum_test")) != DDDMR_OK) return rc;
+  DepthClear& d = *ctx->dclear;
+  if (dc_reserve(&d.in_host, &d.in_dev, &d.in_cap, n * 12) != 0 || dc_reserve(&d.out_host, &d.out_dev, &d.out_cap, n) != 0)
+    return fail(ctx, DDDMR_ERR_HIP, "depth_frustum_test: staging for %zu points", n);
+  float* st = static_cast<float*>(d.in_host);
+  if (stride_bytes == 12) {
+    std::memcpy(st, xyz, n * 12);
+  } else {
+    const size_t sf = stride_bytes / 4;
+    for (size_t i = 0; i < n; ++i) {
+      st[3 * i + 0] = xyz[i * sf + 0];
+      st[3 * i + 1] = xyz[i * sf + 1];
+      st[3 * i + 2] = xyz[i * sf + 2];
+    }
+  }
+  hipLaunchKernelGGL(k_dc_frustum_test, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->copy_stream, S,
+                     static_cast<const float*>(d.in_dev), (uint32_t)n, static_cast<uint8_t*>(d.out_dev));
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+  const uint8_t* o = static_cast<const uint8_t*>(d.out_host);
+  for (size_t i = 0; i < n; ++i) {
+    if (in_frustums_out) in_frustums_out[i] = o[i] & 1u;
+    if (attach_out) attach_out[i] = (o[i] >> 1) & 1u;
+  }
+  return DDDMR_OK;
+}
+
+int dddmr_rollout_depth_clear_verdicts(dddmr_rollout_ctx* ctx, double xy_resolution, double height_resolution,
+                                       const int32_t* voxel_xyz, const uint32_t* offsets, const float* cluster_xyz, size_t m,
+                                       uint8_t* verdict_out, uint32_t* engaged_out) {
+  if (!ctx) return DDDMR_ERR_BAD_ARG;
+  if (!(xy_resolution > 0.0) || !(height_resolution > 0.0) || !std::isfinite(xy_resolution) || !std::isfinite(height_resolution))
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_clear_verdicts: resolutions %g / %g", xy_resolution, height_resolution);
+  if (m > 0 && (!voxel_xyz || !offsets || !verdict_out)) return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_clear_verdicts: null argument");
+  if (m > (1u << 24)) return fail(ctx, DDDMR_ERR_CAPACITY, "depth_clear_verdicts: %zu markings", m);
+  if (m > 0) {
+    if (offsets[0] != 0) return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_clear_verdicts: offsets[0] = %u", offsets[0]);
+    for (size_t i = 0; i < m; ++i)
+      if (offsets[i + 1] < offsets[i]) return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_clear_verdicts: offsets decrease at marking %zu", i);
+    if (offsets[m] > 0 && !cluster_xyz) return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_clear_verdicts: null cluster points");
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  DcFrustums S;
+  int rc = depth_frustums(ctx, "depth_clear_verdicts", &S);
+  if (rc != DDDMR_OK) return rc;
+  if (m == 0) return DDDMR_OK;
+  if ((rc = depth_clear_scratch(ctx, "depth_clear_verdicts")) != DDDMR_OK) return rc;
+  DepthClear& d = *ctx->dclear;
+  hipStream_t st = ctx->copy_stream;      // the stream the depth feeds ran on: their frames are complete before this work
+  uint32_t ops = 0;
+  // aggregatePointCloudFromObservations: the depth sources' alive frames, in source order (lidar sources stay out)
+  size_t n_obs = 0;
+  for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i)
+    if (ctx->depth[i]) n_obs += ctx->src_n[i];
+  const bool observation_clear = !(n_obs > 5);       // depth_camera_layer.cpp:258-264
+  if (!observation_clear && !(d.built && d.built_epoch == ctx->depth_epoch)) {
+    size_t at = 0;
+    for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) {
+      if (!ctx->depth[i] || !ctx->src_n[i]) continue;
+      HIPCHK(ctx, hipMemcpyAsync(d.pts + at, ctx->src_cloud[i], (size_t)ctx->src_n[i] * sizeof(float4), hipMemcpyDeviceToDevice, st));
+      at += ctx->src_n[i];
+      ++ops;
+    }
+    d.built = false;
+    const int b = dc_build_grid(d, (uint32_t)n_obs, st);
+    if (b < 0) return fail(ctx, DDDMR_ERR_HIP, "depth_clear_verdicts: grid build failed");
+    ops += (uint32_t)b;
+    d.built = true;
+    d.built_epoch = ctx->depth_epoch;
+  }
+  const size_t total = offsets[m];
+  const size_t vox_bytes = m * 3 * sizeof(int32_t), off_bytes = (m + 1) * sizeof(uint32_t);
+  if (dc_reserve(&d.in_host, &d.in_dev, &d.in_cap, vox_bytes + off_bytes + total * 12) != 0 ||
+      dc_reserve(&d.out_host, &d.out_dev, &d.out_cap, m * sizeof(uint2)) != 0)
+    return fail(ctx, DDDMR_ERR_HIP, "depth_clear_verdicts: staging for %zu markings, %zu cluster points", m, total);
+  char* in = static_cast<char*>(d.in_host);
+  std::memcpy(in, voxel_xyz, vox_bytes);
+  std::memcpy(in + vox_bytes, offsets, off_bytes);
+  if (total) std::memcpy(in + vox_bytes + off_bytes, cluster_xyz, total * 12);
+  const char* dev = static_cast<const char*>(d.in_dev);
+  DcVerdictParams k;
+  k.res = xy_resolution;
+  k.hres = height_resolution;
+  k.m = (uint32_t)m;
+  k.observation_clear = observation_clear ? 1u : 0u;
+  hipLaunchKernelGGL(k_dc_verdicts, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, k, S, d.hdr, reinterpret_cast<const int32_t*>(dev),
+                     reinterpret_cast<const uint32_t*>(dev + vox_bytes), reinterpret_cast<const float*>(dev + vox_bytes + off_bytes),
+                     static_cast<uint2*>(d.out_dev));
+  ++ops;
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipStreamSynchronize(st));           // the call's one host wait
+  d.launches_last = ops;
+  const uint2* o = static_cast<const uint2*>(d.out_host);
+  for (size_t i = 0; i < m; ++i)
+    if (o[i].x & kDcEmptyCluster)
+      return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_clear_verdicts: marking %zu reaches the engagement ratio with an empty cluster", i);
+  for (size_t i = 0; i < m; ++i) {
+    verdict_out[i] = (uint8_t)o[i].x;
+    if (engaged_out) engaged_out[i] = o[i].y;
+  }
+  return DDDMR_OK;
+}
+
+int dddmr_rollout_depth_clear_launches(dddmr_rollout_ctx* ctx, uint32_t* launches_last_call) {
+  if (!ctx || !launches_last_call) return DDDMR_ERR_BAD_ARG;
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  *launches_last_call = ctx->dclear ? ctx->dclear->launches_last : 0u;
   return DDDMR_OK;
 }
 

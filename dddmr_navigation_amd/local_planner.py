@@ -214,6 +214,59 @@ class LocalPlanner:
                                                                   out.shape[0], C.byref(n)))
         return out[: n.value]
 
+    def set_depth_frustum(self, source_id: int, fov_w: float, fov_v: float, obstacle_min_range: float, obstacle_max_range: float,
+                          T_gbl_sensor):
+        """The frustum half of bufferCloud (depth_camera_observation_buffer.cpp:134-174) for this frame of the source:
+        FOV in radians, T_gbl_sensor = m2s (x y z qx qy qz qw).  Replaces the source's frustum."""
+        cfg = K.DepthFrustumConfig(float(fov_w), float(fov_v), float(obstacle_min_range), float(obstacle_max_range))
+        m2s = (C.c_double * 7)(*[float(v) for v in T_gbl_sensor])
+        self._check(self._lib.dddmr_rollout_set_depth_frustum(self._ctx, int(source_id), C.byref(cfg), m2s))
+
+    def get_depth_frustum(self, source_id: int):
+        """-> (vertices [8,3] TLNear TRNear BLNear BRNear TLFar TRFar BLFar BRFar, normals [6,3] near right bottom left
+        far top, planes [6,4], origin [3]), float32, global frame."""
+        vtx, nrm = np.zeros((8, 3), np.float32), np.zeros((6, 3), np.float32)
+        pl, org = np.zeros((6, 4), np.float32), np.zeros(3, np.float32)
+        self._check(self._lib.dddmr_rollout_get_depth_frustum(self._ctx, int(source_id), vtx.ctypes.data, nrm.ctypes.data,
+                                                              pl.ctypes.data, org.ctypes.data))
+        return vtx, nrm, pl, org
+
+    def depth_frustum_test(self, points_xyz: np.ndarray):
+        """FrustumUtils::isinFrustumsObservations / isAttachFRUSTUMs (frustum_utils.cpp:124-290) for [N, >=3] float32
+        points over all depth sources' frustums -> (in_frustums [N] bool, attach [N] bool)."""
+        pts = np.ascontiguousarray(points_xyz, dtype=np.float32)
+        if pts.ndim != 2 or (pts.shape[0] and pts.shape[1] < 3):
+            raise ValueError("points must be [N, >=3] float32")
+        n = pts.shape[0]
+        inside, attach = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+        stride = pts.strides[0] if n else 12
+        self._check(self._lib.dddmr_rollout_depth_frustum_test(self._ctx, pts.ctypes.data, n, stride, inside.ctypes.data,
+                                                               attach.ctypes.data))
+        return inside[:n].astype(bool), attach[:n].astype(bool)
+
+    def depth_clear_verdicts(self, xy_resolution: float, height_resolution: float, voxels: np.ndarray, offsets: np.ndarray,
+                             cluster_xyz: np.ndarray):
+        """The decision tree of DepthCameraLayer::selfClear (depth_camera_layer.cpp:324-422) for the markings
+        voxels [M,3] int32 with stored clusters cluster_xyz[offsets[i]:offsets[i+1]] ([T,3] float32), against the depth
+        sources' current observation -> (verdict [M] uint8: bit 0 kept, bits 1-2 branch; engaged [M] uint32)."""
+        vox = np.ascontiguousarray(voxels, dtype=np.int32).reshape(-1, 3)
+        off = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+        pts = np.ascontiguousarray(cluster_xyz, dtype=np.float32).reshape(-1, 3)
+        m = vox.shape[0]
+        if off.shape[0] != m + 1 or (m and int(off[-1]) != pts.shape[0]):
+            raise ValueError("offsets must be [M + 1] and end at the number of cluster points")
+        verdict, engaged = np.zeros(max(m, 1), np.uint8), np.zeros(max(m, 1), np.uint32)
+        self._check(self._lib.dddmr_rollout_depth_clear_verdicts(self._ctx, float(xy_resolution), float(height_resolution),
+                                                                 vox.ctypes.data, off.ctypes.data, pts.ctypes.data, m,
+                                                                 verdict.ctypes.data, engaged.ctypes.data))
+        return verdict[:m], engaged[:m]
+
+    def depth_clear_launches(self) -> int:
+        """Device operations (kernels, memsets, copies) the last depth_clear_verdicts call enqueued."""
+        n = C.c_uint32(0)
+        self._check(self._lib.dddmr_rollout_depth_clear_launches(self._ctx, C.byref(n)))
+        return int(n.value)
+
     def set_stitcher(self, stitcher_num: int):
         """cbSensor's `stitcher_num` (multilayer_spinning_lidar.cpp:185-200): feed the last N raw scans together."""
         self._check(self._lib.dddmr_rollout_set_stitcher(self._ctx, int(stitcher_num)))

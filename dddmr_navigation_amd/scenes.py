@@ -360,3 +360,119 @@ def depth_image(cloud_xyz: np.ndarray, T_gbl_sensor, width: int = 640, height: i
     mm = np.rint(np.where(hit, depth, 0.0) * 1000.0)
     img = np.clip(mm, 0, 65535).astype(np.uint16).reshape(height, width)
     return img, (float(fx), float(fy), 0.5 * width - 0.5, 0.5 * height - 0.5)
+
+
+# ---- depth camera clearing: the two-camera scene and the marking generator ---------------------------------------------
+def _pose_matrix(T):
+    x, y, z, w = (float(v) for v in T[3:7])
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                  [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                  [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+    return R, np.asarray(T[:3], dtype=np.float64)
+
+
+def pose_compose(Ta, Tb):
+    """Ta * Tb, poses x y z qx qy qz qw (global<-sensor = global<-base * base<-sensor)."""
+    ax, ay, az, aw = (float(v) for v in Ta[3:7])
+    bx, by, bz, bw = (float(v) for v in Tb[3:7])
+    q = (aw * bx + ax * bw + ay * bz - az * by, aw * by - ax * bz + ay * bw + az * bx,
+         aw * bz + ax * by - ay * bx + az * bw, aw * bw - ax * bx - ay * by - az * bz)
+    R, t = _pose_matrix(Ta)
+    p = R @ np.asarray(Tb[:3], dtype=np.float64) + t
+    return (float(p[0]), float(p[1]), float(p[2])) + q
+
+
+def frustum_side_points(T_gbl_sensor, fov_w, fov_v, d_min, d_max, n, seed, inset=0.05):
+    """n points just inside the four side planes of a camera's frustum (camera_link: x forward, y left, z up), `inset`
+    metres from the plane: where a marking attaches the frustum.  Plain double geometry for drawing inputs only."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    tw, tv = math.tan(0.5 * fov_w), math.tan(0.5 * fov_v)
+    d = rng.uniform(d_min + 0.2, d_max - 0.2, n)
+    side = rng.integers(0, 4, n)
+    u = rng.uniform(-0.9, 0.9, n)
+    y = np.where(side == 0, d * tw - inset * math.hypot(1.0, tw), np.where(side == 1, -d * tw + inset * math.hypot(1.0, tw), u * d * tw))
+    z = np.where(side == 2, d * tv - inset * math.hypot(1.0, tv), np.where(side == 3, -d * tv + inset * math.hypot(1.0, tv), u * d * tv))
+    R, t = _pose_matrix(T_gbl_sensor)
+    return np.stack([d, y, z], axis=1) @ R.T + t
+
+
+def depth_clear_markings(obs_xyz, centre_xyz, n, seed, res=0.05, hres=0.05, max_cluster=200, window=6.0, anchors=None):
+    """n markings as a DepthCameraLayer would hold them around `centre_xyz`, drawn deterministically from the seed and the
+    observation (sorted first, so the order of its points does not matter): voxel keys [n,3] int32, offsets [n+1] uint32,
+    cluster points [T,3] float32 (1 .. max_cluster per marking).  About half sit on the observation, with a chosen share
+    of their cluster points still observed (copied from it) and the rest scattered within 0.12 m; a sixth sit a little off
+    it; the others anywhere in the window or, when `anchors` are given, at one of them.  CPU only."""
+    from scipy.spatial import cKDTree
+    rng = np.random.Generator(np.random.PCG64(seed))
+    obs = np.asarray(obs_xyz, dtype=np.float32).reshape(-1, 3)
+    obs = obs[np.lexsort((obs[:, 2], obs[:, 1], obs[:, 0]))].astype(np.float64)
+    tree = cKDTree(obs) if len(obs) else None
+    centre_xyz = np.asarray(centre_xyz, dtype=np.float64)
+    voxels = np.zeros((n, 3), np.int32)
+    offsets = np.zeros(n + 1, np.uint32)
+    parts = []
+    shares = (0.0, 0.04, 0.08, 0.15, 0.3, 0.6, 1.0)
+    for i in range(n):
+        kind = rng.random()
+        size = int(rng.integers(1, max_cluster + 1))
+        share = shares[int(rng.integers(0, len(shares)))]
+        if tree is not None and kind < 0.45:
+            c = obs[int(rng.integers(0, len(obs)))]
+        elif tree is not None and kind < 0.6:
+            v = rng.normal(size=3)
+            c = obs[int(rng.integers(0, len(obs)))] + v / np.linalg.norm(v) * rng.uniform(0.03, 0.3)
+            share *= 0.5
+        elif anchors is not None and len(anchors) and kind < 0.8:
+            c = np.asarray(anchors[int(rng.integers(0, len(anchors)))], dtype=np.float64)
+        else:
+            c = centre_xyz + np.array([rng.uniform(-window, window), rng.uniform(-window, window), rng.uniform(0.0, 2.0)])
+        k = 0
+        seen = np.zeros((0, 3))
+        if tree is not None and share > 0.0:
+            want = min(int(round(share * size)), len(obs))
+            if want:
+                dist, idx = tree.query(c, k=want)
+                idx = np.atleast_1d(idx)[np.atleast_1d(dist) < 0.2]
+                seen, k = obs[idx], len(idx)
+        rest = c + rng.uniform(-0.12, 0.12, (size - k, 3))
+        parts.append(np.concatenate([seen, rest], axis=0))
+        voxels[i] = (int(np.rint(c[0] / res)), int(np.rint(c[1] / res)), int(np.rint(c[2] / hres)))
+        offsets[i + 1] = offsets[i] + size
+    cluster = np.concatenate(parts, axis=0).astype(np.float32) if parts else np.zeros((0, 3), np.float32)
+    return voxels, offsets, cluster
+
+
+@dataclass
+class DepthClearScene:
+    cloud: np.ndarray            # the world, [P,4] float32
+    T_gbl_base: tuple
+    T_base_cam: tuple            # (left, right): base <- camera_link
+    fov_w: float
+    fov_v: float
+    d_min: float
+    d_max: float
+    z_min: float
+    z_max: float
+    res: float
+    hres: float
+    frames: tuple                # (left, right): organised [120 * 160, 3] float32 clouds in the camera frames
+
+    def T_gbl_cam(self, i):
+        return pose_compose(self.T_gbl_base, self.T_base_cam[i])
+
+    def markings(self, obs_xyz, n=600, seed=5):
+        anchors = np.concatenate([frustum_side_points(self.T_gbl_cam(i), self.fov_w, self.fov_v, self.d_min, self.d_max, 64, 40 + i)
+                                  for i in range(2)], axis=0)
+        return depth_clear_markings(obs_xyz, self.T_gbl_base[:3], n, seed, self.res, self.hres, anchors=anchors)
+
+
+def depth_clear_scene() -> DepthClearScene:
+    """The left / right depth cameras of the reference's multi_depth_camera_3d_ros.yaml (FOV_W 1.5184, FOV_V 1.0123 rad,
+    obstacle range 0.3 .. 5.0 m, obstacle height 0.1 .. 2.0 m, 0.05 m voxels) on a robot in the C2 corridor, toed out by
+    0.6 rad so that their frustums overlap ahead of the robot, each with one rendered 160 x 120 frame.  Deterministic."""
+    cloud = cloud_c2()
+    t_gb = (0.0, 0.0, 0.0) + tuple(quat_from_rpy(0.0, 0.0, 0.05))
+    t_bc = ((0.25, 0.12, 0.35) + tuple(quat_from_rpy(0.0, 0.05, 0.6)), (0.25, -0.12, 0.35) + tuple(quat_from_rpy(0.0, 0.05, -0.6)))
+    fov_w, fov_v, d_min, d_max = 1.5184, 1.0123, 0.3, 5.0
+    frames = tuple(depth_frame(cloud, pose_compose(t_gb, t_bc[i]), 160, 120, fov_w, fov_v, d_max, seed=21 + i) for i in range(2))
+    return DepthClearScene(cloud, t_gb, t_bc, fov_w, fov_v, d_min, d_max, 0.1, 2.0, 0.05, 0.05, frames)

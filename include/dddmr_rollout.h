@@ -352,6 +352,72 @@ int dddmr_rollout_set_depth_image(dddmr_rollout_ctx* ctx, int32_t source_id, con
 int dddmr_rollout_get_depth_image_cloud(dddmr_rollout_ctx* ctx, int32_t source_id, float* xyz_out,
                                         size_t capacity, size_t* n_points);
 
+/* Depth camera frustums and selfClear's clearing verdicts: the global-mode side of DepthCameraLayer, first slice
+   (additions to ABI version 2; no existing struct or entry changes).
+
+   dddmr_rollout_set_depth_frustum is the second half of DepthCameraObservationBuffer::bufferCloud
+   (depth_camera_observation_buffer.cpp:134-174): call it once per frame beside dddmr_rollout_set_depth_frame /
+   _set_depth_image with m2s = lookupTransform(global, origin_frame), which the reference looks up on its own (it is
+   not derived from the frame call's transforms).  It REPLACES the source's frustum (the reference's tests only read
+   observations.back()): findFrustumVertex (depth_camera_observation.cpp:114-127: d * tan(FOV / 2.0) in double, rounded
+   into floats, order TLNear TRNear BLNear BRNear TLFar TRFar BLFar BRFar), pcl::transformPointCloud by the Affine3d of
+   m2s (double multiply-add, float result), findFrustumNormal (:130-200, order near right bottom left far top),
+   findFrustumPlane (:202-239), BRNear_ = vertex 3, TLFar_ = vertex 4, origin_ = m2s' translation (kept in double;
+   dddmr_rollout_get_depth_frustum reports it rounded to float).  FOV_W / FOV_V in radians, inside (0, pi);
+   0 < obstacle_min_range < obstacle_max_range (the plugin's parameter names; the reference's min_ / max_detect_distance_).
+   DDDMR_ERR_STATE: the source is not a depth source (get: or has no frustum).  A refused call changes nothing.
+   Re-configuring a source (dddmr_rollout_set_depth_source / _set_depth_image_source) drops its frustum with its frames.
+
+   dddmr_rollout_depth_frustum_test: FrustumUtils::isinFrustumsObservations and isAttachFRUSTUMs (frustum_utils.cpp:124-290)
+   for n points (records stride_bytes apart, float x y z first), one byte per point each (either output may be NULL),
+   over the frustums of ALL depth sources in source order.  The reference iterates a std::map keyed by the source's
+   name, so the caller numbers its depth sources in the order of their names.  The arithmetic is the reference's: every
+   operand of the six `test` dot products, of the plane distance and of its fabs / sqrt is a float, so they are float
+   expressions (`test` is widened to double only for `< 0`; fabs / sqrt are the float overloads, oracle/ASSUMPTIONS.md
+   row 18); hypot(float - double, float - double) < max_detect_distance_ + 0.5 is double; dis2rej = (float)0.12.
+   isAttachFRUSTUMs is decided by the first plane of the first source that attaches: true unless another source holds
+   the point inside its frustum and unattached (isInsideFRUSTUMwoAttach); later planes and sources are not asked.
+
+   dddmr_rollout_depth_clear_verdicts: the decision tree of DepthCameraLayer::selfClear (depth_camera_layer.cpp:324-422)
+   for m markings the caller selected from its own pct_marking_ map (getXIter / lower_bound stay with the caller).
+   Marking i has the voxel key voxel_xyz[i] and the stored cluster (pc_) cluster_xyz[offsets[i] .. offsets[i + 1]),
+   packed x y z; offsets[0] = 0, offsets non-decreasing.  pt = (x * xy_resolution, y * xy_resolution,
+   z * height_resolution), int times double rounded to float.  The observation is the concatenation of the DEPTH
+   sources' alive frames as the context holds them now (aggregatePointCloudFromObservations; lidar sources of the same
+   context do not enter); with <= 5 points it counts as clear and nothing is searched (:258-264).
+     pt in no frustum (the branch at :333; its comment says the opposite): kept iff radiusSearch(pt, 0.05, 1) > 0.
+     otherwise, attached (isAttachFRUSTUMs) or not, the same test: removed when the observation is clear, else
+     engage = cluster points with radiusSearch(point, 0.01, 1) > 0, kept iff 1.0 * engage / size > 0.1 (double).
+   radiusSearch is FLANN's float squared distance against static_cast<float>(r * r), strict < (oracle/ASSUMPTIONS.md row 1).
+   verdict_out[i]: bit 0 = kept (the marking would be pushed to current_observation_ptr; 0 = removePCPtr), bits 1-2 =
+   the branch that decided: 1 outside the frustums, 2 attached, 3 inside.  engaged_out[i] (may be NULL) = the
+   engagement count where the branch computes one, else 0.  DDDMR_ERR_BAD_ARG when a marking reaches the ratio with
+   an empty cluster (the reference would divide by zero); no output is written then.
+
+   Both calls: DDDMR_ERR_STATE without a depth source or while a depth source has no frustum yet (the reference returns
+   early until isFirstScanReady() of every buffer).  Both may be called between dddmr_rollout_tick_begin and _tick_end
+   and give the same answer as outside: they work on the feeds' stream and read the depth sources, which a tick never
+   touches.  They are serialised with the feeds (one producer at a time).  The observation grid is rebuilt only when a
+   depth source has published since the last verdict call; dddmr_rollout_depth_clear_launches reports how many device
+   operations (kernels, memsets, copies) the last verdict call enqueued.  Each call makes one host wait. */
+typedef struct {
+  double FOV_W, FOV_V;                            /* radians */
+  double obstacle_min_range, obstacle_max_range;  /* metres */
+} dddmr_depth_frustum_config;
+
+int dddmr_rollout_set_depth_frustum(dddmr_rollout_ctx* ctx, int32_t source_id, const dddmr_depth_frustum_config* cfg,
+                                    const double T_gbl_sensor[7]);
+/* any output may be NULL */
+int dddmr_rollout_get_depth_frustum(dddmr_rollout_ctx* ctx, int32_t source_id, float vertices[8][3], float normals[6][3],
+                                    float planes[6][4], float origin[3]);
+int dddmr_rollout_depth_frustum_test(dddmr_rollout_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes,
+                                     uint8_t* in_frustums_out, uint8_t* attach_out);
+int dddmr_rollout_depth_clear_verdicts(dddmr_rollout_ctx* ctx, double xy_resolution, double height_resolution,
+                                       const int32_t* voxel_xyz /* [m][3] */, const uint32_t* offsets /* [m + 1] */,
+                                       const float* cluster_xyz /* [offsets[m]][3] */, size_t m,
+                                       uint8_t* verdict_out /* [m] */, uint32_t* engaged_out /* [m], may be NULL */);
+int dddmr_rollout_depth_clear_launches(dddmr_rollout_ctx* ctx, uint32_t* launches_last_call);
+
 /* Copy the current aggregate observation back (debug / parity of set_scan). */
 int dddmr_rollout_get_cloud(dddmr_rollout_ctx* ctx, float* xyzi_out, size_t capacity,
                             size_t* n_points);

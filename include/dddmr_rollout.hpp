@@ -118,6 +118,30 @@ class LocalPlanner {
     if (n) check(dddmr_rollout_get_depth_image_cloud(ctx_, source_id, &out[0][0], n, &n));
     return out;
   }
+  // the frustum of a depth source (bufferCloud's second half), the two point tests and selfClear's clearing verdicts
+  void setDepthFrustum(int32_t source_id, const dddmr_depth_frustum_config& cfg, const double T_gbl_sensor[7]) {
+    check(dddmr_rollout_set_depth_frustum(ctx_, source_id, &cfg, T_gbl_sensor));
+  }
+  struct DepthFrustum { float vertices[8][3], normals[6][3], planes[6][4], origin[3]; };
+  DepthFrustum getDepthFrustum(int32_t source_id) {
+    DepthFrustum f{};
+    check(dddmr_rollout_get_depth_frustum(ctx_, source_id, f.vertices, f.normals, f.planes, f.origin));
+    return f;
+  }
+  // in_frustums / attach: one byte per point (isinFrustumsObservations, isAttachFRUSTUMs)
+  void depthFrustumTest(const float* xyz, size_t n, size_t stride_bytes, std::vector<uint8_t>& in_frustums, std::vector<uint8_t>& attach) {
+    in_frustums.assign(n, 0);
+    attach.assign(n, 0);
+    check(dddmr_rollout_depth_frustum_test(ctx_, xyz, n, stride_bytes, in_frustums.data(), attach.data()));
+  }
+  // verdict[i]: bit 0 kept, bits 1-2 branch (1 outside the frustums, 2 attached, 3 inside); engaged[i]: engagement count
+  void depthClearVerdicts(double xy_resolution, double height_resolution, const int32_t* voxel_xyz, const uint32_t* offsets,
+                          const float* cluster_xyz, size_t m, std::vector<uint8_t>& verdict, std::vector<uint32_t>& engaged) {
+    verdict.assign(m, 0);
+    engaged.assign(m, 0);
+    check(dddmr_rollout_depth_clear_verdicts(ctx_, xy_resolution, height_resolution, voxel_xyz, offsets, cluster_xyz, m,
+                                             verdict.data(), engaged.data()));
+  }
   // prune plan poses, x y z qx qy qz qw each (output of Local_Planner::prunePlan)
   void setPlan(const double* poses_xyz_qxyzw, size_t n_poses) {
     check(dddmr_rollout_set_prune_plan(ctx_, poses_xyz_qxyzw, n_poses));
