@@ -377,8 +377,7 @@ inline int dc_reserve(void** host, void** dev, size_t* cap, size_t bytes) {
   *host = nullptr;
   *dev = nullptr;
   *cap = 0;
-  if (hipHostMalloc(host, want, hipHostMallocMapped) != hipSuccess) return -1;
-  if (hipHostGetDevicePointer(dev, *host, 0) != hipSuccess) return -1;
+  if (host_mapped_alloc(host, dev, want) != 0) return -1;
   *cap = want;
   return 0;
 }

@@ -22,8 +22,8 @@
 //                    (depth_insert_record of depth_feed.hip.h: transform, height band, compaction, base-frame table).
 //                    The number of centroids is only known on the device, hence a fixed grid that strides over it.
 //   k_depth_emit     unchanged.
-// Built with -DDDDMR_DIMG_UNFUSED the centroid pass only stores the cloud and a fourth kernel, k_dimg_stage_two, reads
-// it back for stage two (its count from device memory); kept for the measurement in profiles/r05_depth_image.json.
+// Stage two as a fourth kernel that reads the stage-one cloud back was measured beside the fused pass and lost
+// (profiles/r05_depth_image.json); it is in the history.
 //
 // Voxel membership is floor(p * (1.0f / (float)leaf)) per axis in float; centroid sums are double where PCL sums in
 // float in input order, so stage-one centroids agree with PCL's to the spread of PCL's own summation orders.
@@ -64,23 +64,14 @@ struct DepthImage {
   uint32_t height = 0;
   uint16_t* stage = nullptr;          // pinned + mapped: the sampled rows, packed
   uint16_t* stage_dev = nullptr;
-  unsigned char* table = nullptr;     // camera-frame voxels, layout as DepthSource::table; k_dimg_centroid leaves it clean
-  uint32_t* claimed = nullptr;
+  VoxelTable table;                   // camera-frame voxels; k_dimg_centroid leaves it clean
   uint32_t* counters = nullptr;       // [0] claimed slots, [1] ticket
   float* cloud[2] = {nullptr, nullptr};   // stage-one cloud, packed xyz; cloud[cur] belongs to the latest accepted image
   int cur = 0;
   uint32_t n_cloud = 0;
   DimgResult* res_host = nullptr;
   DimgResult* res_dev = nullptr;
-  size_t cap_slots = 0;
 };
-
-__device__ __forceinline__ unsigned long long dimg_voxel_key(float x, float y, float z, float inv_leaf) {
-  const int ix = (int)floorf(x * inv_leaf), iy = (int)floorf(y * inv_leaf), iz = (int)floorf(z * inv_leaf);
-  return (1ull << 63) | ((unsigned long long)((uint32_t)(ix + (1 << 20)) & 0x1FFFFFu) << 42) |
-         ((unsigned long long)((uint32_t)(iy + (1 << 20)) & 0x1FFFFFu) << 21) |
-         (unsigned long long)((uint32_t)(iz + (1 << 20)) & 0x1FFFFFu);
-}
 
 __device__ __forceinline__ double dimg_shfl_up(double v, int delta) {
   return __shfl_up(v, (unsigned)delta, 64);
@@ -89,9 +80,7 @@ __device__ __forceinline__ double dimg_shfl_up(double v, int delta) {
 // 64 consecutive sampled pixels, one per lane (valid = the lane has one): deproject, sum the runs, update the table.
 // Every lane of the wave calls it.
 __device__ __forceinline__ void dimg_wave_pixels(const DimgParams& p, bool valid, uint32_t u, uint32_t v, uint32_t d,
-                                                 unsigned long long* __restrict__ keys, double* __restrict__ sums,
-                                                 uint32_t* __restrict__ counts, uint32_t slot_mask,
-                                                 uint32_t* __restrict__ claimed, uint32_t* __restrict__ counters) {
+                                                 const VoxelView& table) {
   const int lane = threadIdx.x & 63;
   // cbDepthImg:132-146.  `float z = at<unsigned short>(v, u) * 0.001`: double product, float result;
   // `z > max_distance_` compares in double; x and y in float, left to right
@@ -99,7 +88,7 @@ __device__ __forceinline__ void dimg_wave_pixels(const DimgParams& p, bool valid
   const bool keep = valid && !((double)z > p.max_distance) && !(p.drop_zero && d == 0u);
   const float x = ((float)u - p.cx) * z * p.fx;
   const float y = ((float)v - p.cy) * z * p.fy;
-  const unsigned long long key = keep ? dimg_voxel_key(x, y, z, p.inv_leaf) : 0ull;   // 0 is no key: bit 63 marks one
+  const unsigned long long key = keep ? voxel_key(x, y, z, p.inv_leaf) : 0ull;   // 0 is no key: bit 63 marks one
   // runs of equal keys among consecutive lanes
   const unsigned long long prev_key = __shfl_up(key, 1u, 64);
   const bool head = lane == 0 || prev_key != key;
@@ -115,24 +104,9 @@ __device__ __forceinline__ void dimg_wave_pixels(const DimgParams& p, bool valid
   }
   const bool tail = lane == 63 || ((heads >> (lane + 1)) & 1ull);
   if (!(tail && keep)) return;
-  // all-zero sums need no add (x + 0.0 == x): a region without a return costs one counter add per run.  A run may mix
-  // depth 0 with a tiny depth of the same voxel, so the test is on the sums, not on this lane's pixel.
-  const bool sums_zero = sx == 0.0 && sy == 0.0 && sz == 0.0;
-  uint32_t slot = hash_key(key) & slot_mask;
-  for (uint32_t probe = 0; probe <= slot_mask; ++probe) {
-    const unsigned long long prev = atomicCAS(&keys[slot], 0ull, key);
-    if (prev == 0ull || prev == key) {
-      if (prev == 0ull) claimed[atomicAdd(&counters[0], 1u)] = slot;
-      if (!sums_zero) {
-        atomicAdd(&sums[3 * (size_t)slot + 0], sx);
-        atomicAdd(&sums[3 * (size_t)slot + 1], sy);
-        atomicAdd(&sums[3 * (size_t)slot + 2], sz);
-      }
-      atomicAdd(&counts[slot], cnt);
-      return;
-    }
-    slot = (slot + 1) & slot_mask;
-  }
+  // A region without a return costs one counter add per run: all-zero sums are not added.  A run may mix depth 0
+  // with a tiny depth of the same voxel, so that test is on the sums, not on this lane's pixel.
+  voxel_insert(table, key, sx, sy, sz, cnt);
 }
 
 // PX == 1: lane i = sampled pixel i (row i / cols, column i % cols), any step.
@@ -140,10 +114,7 @@ __device__ __forceinline__ void dimg_wave_pixels(const DimgParams& p, bool valid
 // pixels are then processed in 4 rounds of 64 consecutive ones (round j, lane L: pixel 64 j + L, held by lane
 // 16 j + L / 4), so the runs of equal keys are found among neighbours exactly as for PX == 1.
 template <int PX>
-__global__ __launch_bounds__(256) void k_dimg_insert(DimgParams p, const uint16_t* __restrict__ img,
-                                                     unsigned long long* __restrict__ keys, double* __restrict__ sums,
-                                                     uint32_t* __restrict__ counts, uint32_t slot_mask,
-                                                     uint32_t* __restrict__ claimed, uint32_t* __restrict__ counters) {
+__global__ __launch_bounds__(256) void k_dimg_insert(DimgParams p, const uint16_t* __restrict__ img, VoxelView table) {
   const uint32_t n = p.rows * p.cols;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if constexpr (PX == 1) {
@@ -151,7 +122,7 @@ __global__ __launch_bounds__(256) void k_dimg_insert(DimgParams p, const uint16_
     const uint32_t r = valid ? i / p.cols : 0u, c = valid ? i - r * p.cols : 0u;
     const uint32_t u = c * p.step, v = r * p.step;
     const uint32_t d = valid ? (uint32_t)img[(size_t)r * p.width + u] : 0u;
-    dimg_wave_pixels(p, valid, u, v, d, keys, sums, counts, slot_mask, claimed, counters);
+    dimg_wave_pixels(p, valid, u, v, d, table);
   } else {
     static_assert(PX == 4, "1 or 4 pixels per lane");
     const int lane = threadIdx.x & 63;
@@ -167,78 +138,41 @@ __global__ __launch_bounds__(256) void k_dimg_insert(DimgParams p, const uint16_
       const uint32_t px = wave_first + 64u * (uint32_t)j + (uint32_t)lane;
       const bool valid = px < n;
       const uint32_t v = px / p.width, u = px - v * p.width;    // step 1: cols == width
-      dimg_wave_pixels(p, valid, u, v, valid ? d : 0u, keys, sums, counts, slot_mask, claimed, counters);
+      dimg_wave_pixels(p, valid, u, v, valid ? d : 0u, table);
     }
   }
 }
 
-// One lane per claimed camera-frame voxel, fixed grid striding over the device's own count.  FUSED: stage two's insert
-// in the same pass.  The last workgroup hands the count on and zeroes the counters for the next image.
-template <bool FUSED>
-__global__ __launch_bounds__(256) void k_dimg_centroid(DepthParams f, unsigned long long* __restrict__ ikeys,
-                                                       double* __restrict__ isums, uint32_t* __restrict__ icounts,
-                                                       const uint32_t* __restrict__ iclaimed, uint32_t* __restrict__ icounters,
+// One lane per claimed camera-frame voxel, fixed grid striding over the device's own count, stage two's insert in the
+// same pass.  The last workgroup hands the count on and zeroes the counters for the next image.
+__global__ __launch_bounds__(256) void k_dimg_centroid(DepthParams f, VoxelView cam, uint32_t* __restrict__ icounters,
                                                        float* __restrict__ cloud, DimgResult* __restrict__ ires,
-                                                       uint32_t* __restrict__ n_cloud_dev, float4* __restrict__ surv,
-                                                       unsigned long long* __restrict__ keys, double* __restrict__ sums,
-                                                       uint32_t* __restrict__ counts, uint32_t slot_mask,
-                                                       uint32_t* __restrict__ claimed, uint32_t* __restrict__ counters) {
+                                                       float4* __restrict__ surv, VoxelView table,
+                                                       uint32_t* __restrict__ counters) {
   const uint32_t n_claimed = icounters[0];
   for (uint32_t idx0 = blockIdx.x * blockDim.x; idx0 < n_claimed; idx0 += gridDim.x * blockDim.x) {   // uniform per workgroup
     const uint32_t idx = idx0 + threadIdx.x;
     const bool occ = idx < n_claimed;
-    float cx = 0.f, cy = 0.f, cz = 0.f;
+    float3 c = make_float3(0.f, 0.f, 0.f);
     if (occ) {
-      const uint32_t slot = iclaimed[idx];
-      const double n = (double)icounts[slot];
-      cx = (float)(isums[3 * (size_t)slot + 0] / n);
-      cy = (float)(isums[3 * (size_t)slot + 1] / n);
-      cz = (float)(isums[3 * (size_t)slot + 2] / n);
-      cloud[3 * (size_t)idx + 0] = cx;
-      cloud[3 * (size_t)idx + 1] = cy;
-      cloud[3 * (size_t)idx + 2] = cz;
-      ikeys[slot] = 0ull;                              // leave the table empty for the next image
-      isums[3 * (size_t)slot + 0] = 0.0;
-      isums[3 * (size_t)slot + 1] = 0.0;
-      isums[3 * (size_t)slot + 2] = 0.0;
-      icounts[slot] = 0u;
+      c = voxel_take(cam, cam.claimed[idx]);
+      cloud[3 * (size_t)idx + 0] = c.x;
+      cloud[3 * (size_t)idx + 1] = c.y;
+      cloud[3 * (size_t)idx + 2] = c.z;
     }
-    if constexpr (FUSED) depth_insert_record(f, occ, cx, cy, cz, surv, keys, sums, counts, slot_mask, claimed, counters);
+    depth_insert_record(f, occ, c.x, c.y, c.z, surv, table, counters);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t t = __hip_atomic_fetch_add(&icounters[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t == gridDim.x - 1) {                          // every workgroup has read icounters[0]
-      ires->n_camera = n_claimed;                      // the host reads it after k_depth_emit's release of its own word
-      *n_cloud_dev = n_claimed;
-      icounters[0] = 0;
-      icounters[1] = 0;
-      __threadfence_system();
-    }
-  }
-}
-
-// The unfused variant's stage two: k_depth_insert's work on the stage-one cloud, its count read from device memory.
-__global__ __launch_bounds__(256) void k_dimg_stage_two(DepthParams f, const float* __restrict__ cloud,
-                                                        const uint32_t* __restrict__ n_cloud_dev, float4* __restrict__ surv,
-                                                        unsigned long long* __restrict__ keys, double* __restrict__ sums,
-                                                        uint32_t* __restrict__ counts, uint32_t slot_mask,
-                                                        uint32_t* __restrict__ claimed, uint32_t* __restrict__ counters) {
-  const uint32_t n = *n_cloud_dev;
-  for (uint32_t idx0 = blockIdx.x * blockDim.x; idx0 < n; idx0 += gridDim.x * blockDim.x) {
-    const uint32_t idx = idx0 + threadIdx.x;
-    const bool occ = idx < n;
-    const float cx = occ ? cloud[3 * (size_t)idx + 0] : 0.f, cy = occ ? cloud[3 * (size_t)idx + 1] : 0.f,
-                cz = occ ? cloud[3 * (size_t)idx + 2] : 0.f;
-    depth_insert_record(f, occ, cx, cy, cz, surv, keys, sums, counts, slot_mask, claimed, counters);
+  if (last_block(&icounters[1])) {                     // every workgroup has read icounters[0]
+    ires->n_camera = n_claimed;                        // the host reads it after k_depth_emit's release of its own word
+    icounters[0] = 0;
+    icounters[1] = 0;
+    __threadfence_system();
   }
 }
 
 inline void dimg_free(DepthImage& d) {
   if (d.stage) (void)hipHostFree(d.stage);
-  if (d.table) (void)hipFree(d.table);
-  if (d.claimed) (void)hipFree(d.claimed);
+  d.table.free();
   if (d.counters) (void)hipFree(d.counters);
   for (float* c : d.cloud)
     if (c) (void)hipFree(c);
@@ -249,20 +183,13 @@ inline void dimg_free(DepthImage& d) {
 // d.p and d.height are set; the tables hold every sampled pixel in a voxel of its own at load <= 0.5
 inline int dimg_alloc(DepthImage& d) {
   const size_t n = (size_t)d.p.rows * d.p.cols;
-  size_t slots = 1024;
-  while (slots < 2 * n) slots <<= 1;
-  d.cap_slots = slots;
-  if (hipHostMalloc(&d.stage, (size_t)d.p.rows * d.p.width * sizeof(uint16_t) + 8, hipHostMallocMapped) != hipSuccess) return -1;
-  if (hipHostGetDevicePointer(reinterpret_cast<void**>(&d.stage_dev), d.stage, 0) != hipSuccess) return -1;
-  if (hipMalloc(&d.table, feed_table_bytes(slots)) != hipSuccess) return -1;
-  if (hipMalloc(&d.claimed, n * sizeof(uint32_t)) != hipSuccess) return -1;
+  if (host_mapped_alloc(&d.stage, &d.stage_dev, (size_t)d.p.rows * d.p.width * sizeof(uint16_t) + 8) != 0) return -1;
+  if (d.table.alloc(n) != 0) return -1;
   if (hipMalloc(&d.counters, 4 * sizeof(uint32_t)) != hipSuccess) return -1;
   for (float*& c : d.cloud)
     if (hipMalloc(&c, n * 3 * sizeof(float)) != hipSuccess) return -1;
-  if (hipMemset(d.table, 0, feed_table_bytes(slots)) != hipSuccess) return -1;
   if (hipMemset(d.counters, 0, 4 * sizeof(uint32_t)) != hipSuccess) return -1;
-  if (hipHostMalloc(&d.res_host, sizeof(DimgResult), hipHostMallocMapped) != hipSuccess) return -1;
-  if (hipHostGetDevicePointer(reinterpret_cast<void**>(&d.res_dev), d.res_host, 0) != hipSuccess) return -1;
+  if (host_mapped_alloc(&d.res_host, &d.res_dev, sizeof(DimgResult)) != 0) return -1;
   std::memset(d.res_host, 0, sizeof(DimgResult));
   return 0;
 }
@@ -301,46 +228,22 @@ inline int depth_image_feed(DepthSource& s, DepthImage& d, DepthParams f, const 
       std::memcpy(d.stage + (size_t)r * p.width, reinterpret_cast<const unsigned char*>(img) + (size_t)r * p.step * row_stride_bytes,
                   row_bytes);
   }
-  unsigned long long* ikeys = reinterpret_cast<unsigned long long*>(d.table);
-  double* isums = reinterpret_cast<double*>(d.table + d.cap_slots * 8);
-  uint32_t* icounts = reinterpret_cast<uint32_t*>(d.table + d.cap_slots * 32);
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(s.table);
-  double* sums = reinterpret_cast<double*>(s.table + s.cap_slots * 8);
-  uint32_t* counts = reinterpret_cast<uint32_t*>(s.table + s.cap_slots * 32);
+  // both tables in full: neither stage knows its voxel count before its kernel has run
+  const VoxelView cam = d.table.view(d.table.slots, d.counters + 0);
+  const VoxelView table = s.table.view(s.table.slots, s.counters + 2);
   const uint32_t seq = ++s.seq ? s.seq : ++s.seq;
   const uint32_t n = p.rows * p.cols;
   const dim3 block(256);
-  const bool wide = DDDMR_DIMG_PX == 4 && p.step == 1 && p.width % 4 == 0;
-  if (wide) {
-    hipLaunchKernelGGL(k_dimg_insert<4>, dim3((n / 4 + 255) / 256), block, 0, stream, p, d.stage_dev, ikeys, isums, icounts,
-                       (uint32_t)(d.cap_slots - 1), d.claimed, d.counters);
-  } else {
-    hipLaunchKernelGGL(k_dimg_insert<1>, dim3((n + 255) / 256), block, 0, stream, p, d.stage_dev, ikeys, isums, icounts,
-                       (uint32_t)(d.cap_slots - 1), d.claimed, d.counters);
-  }
+  if (DDDMR_DIMG_PX == 4 && p.step == 1 && p.width % 4 == 0)
+    hipLaunchKernelGGL(k_dimg_insert<4>, dim3((n / 4 + 255) / 256), block, 0, stream, p, d.stage_dev, cam);
+  else
+    hipLaunchKernelGGL(k_dimg_insert<1>, dim3((n + 255) / 256), block, 0, stream, p, d.stage_dev, cam);
   const dim3 walk(std::min<unsigned>((n + 255) / 256, kDepthEmitBlocks));
-  float* cloud = d.cloud[d.cur ^ 1];
-  uint32_t* n_cloud_dev = d.counters + 2;
-#ifndef DDDMR_DIMG_UNFUSED
-  hipLaunchKernelGGL(k_dimg_centroid<true>, walk, block, 0, stream, f, ikeys, isums, icounts, d.claimed, d.counters, cloud, d.res_dev,
-                     n_cloud_dev, s.surv, keys, sums, counts, (uint32_t)(s.cap_slots - 1), s.claimed, s.counters);
-#else
-  hipLaunchKernelGGL(k_dimg_centroid<false>, walk, block, 0, stream, f, ikeys, isums, icounts, d.claimed, d.counters, cloud, d.res_dev,
-                     n_cloud_dev, s.surv, keys, sums, counts, (uint32_t)(s.cap_slots - 1), s.claimed, s.counters);
-  hipLaunchKernelGGL(k_dimg_stage_two, walk, block, 0, stream, f, cloud, n_cloud_dev, s.surv, keys, sums, counts,
-                     (uint32_t)(s.cap_slots - 1), s.claimed, s.counters);
-#endif
-  hipLaunchKernelGGL(k_depth_emit, walk, block, 0, stream, f, s.surv, keys, sums, counts, s.claimed, out_dev, s.counters, s.res_dev, seq);
+  hipLaunchKernelGGL(k_dimg_centroid, walk, block, 0, stream, f, cam, d.counters, d.cloud[d.cur ^ 1], d.res_dev, s.surv, table,
+                     s.counters);
+  hipLaunchKernelGGL(k_depth_emit, walk, block, 0, stream, f, s.surv, table, out_dev, s.counters, s.res_dev, seq);
   if (hipGetLastError() != hipSuccess) return -5;
-  volatile uint32_t* seq_p = &s.res_host->seq;
-  bool seen = false;
-  for (uint64_t spins = 0; spins < (1ull << 26); ++spins) {
-    if (*seq_p == seq) { seen = true; break; }
-#if defined(__x86_64__)
-    __builtin_ia32_pause();
-#endif
-  }
-  if (!seen && hipStreamSynchronize(stream) != hipSuccess) return -4;
+  if (!wait_seq(&s.res_host->seq, seq) && hipStreamSynchronize(stream) != hipSuccess) return -4;
   *n_out = s.res_host->n_out;
   *n_camera = *reinterpret_cast<volatile uint32_t*>(&d.res_host->n_camera);
   return 0;

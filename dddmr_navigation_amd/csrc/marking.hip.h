@@ -35,6 +35,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "rollout_kernels.hip.h"
+#include "voxel_table.hip.h"   // voxel_key, voxel_unkey, voxel_hash: the store below is a table of its own
 
 #pragma clang fp contract(off)
 
@@ -206,21 +207,6 @@ __device__ inline bool in_lidar_observation(const MarkParams& k, const float pcx
   if (yaw >= 0 && (yaw < k.ps || yaw > k.pe)) return false;
   else if (yaw < 0 && (yaw > k.ns || yaw < k.ne)) return false;
   return true;
-}
-
-__device__ __forceinline__ unsigned long long voxel_key(int x, int y, int z) {   // bit 63 set: 0 = empty slot
-  return (1ull << 63) | ((unsigned long long)((uint32_t)(x + (1 << 20)) & 0x1FFFFFu) << 42) |
-         ((unsigned long long)((uint32_t)(y + (1 << 20)) & 0x1FFFFFu) << 21) |
-         (unsigned long long)((uint32_t)(z + (1 << 20)) & 0x1FFFFFu);
-}
-__host__ __device__ __forceinline__ void voxel_unkey(unsigned long long key, int* x, int* y, int* z) {
-  *x = (int)((key >> 42) & 0x1FFFFFu) - (1 << 20);
-  *y = (int)((key >> 21) & 0x1FFFFFu) - (1 << 20);
-  *z = (int)(key & 0x1FFFFFu) - (1 << 20);
-}
-__device__ __forceinline__ uint32_t mk_hash(unsigned long long k) {
-  k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-  return (uint32_t)k;
 }
 
 struct MarkStore {            // the persistent store (device pointers)
@@ -608,7 +594,7 @@ __global__ __launch_bounds__(64) void k_mk_slots(MarkParams k, const MarkCounter
   const uint32_t ci = blockIdx.x * 64 + threadIdx.x;
   if (ci >= cnt_in->n_clusters || c.state[ci] != 2u) return;
   const unsigned long long key = voxel_key(c.vkey[3 * ci], c.vkey[3 * ci + 1], c.vkey[3 * ci + 2]);
-  uint32_t slot = mk_hash(key) & k.table_mask;
+  uint32_t slot = voxel_hash(key) & k.table_mask;
   bool found = false;
   for (uint32_t probe = 0; probe <= k.table_mask; ++probe) {
     const unsigned long long prev = atomicCAS(&s.keys[slot], 0ull, key);
@@ -704,7 +690,7 @@ __global__ __launch_bounds__(256) void k_mk_rehash(uint32_t table_mask, MarkStor
   const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
   if (slot > table_mask || !s.alive[slot]) return;
   const unsigned long long key = s.keys[slot];
-  uint32_t ns = mk_hash(key) & table_mask;
+  uint32_t ns = voxel_hash(key) & table_mask;
   for (uint32_t probe = 0; probe <= table_mask; ++probe) {          // (alive markings are fewer than slots: always ends)
     if (atomicCAS(&keys_new[ns], 0ull, key) == 0ull) break;
     ns = (ns + 1) & table_mask;

@@ -1166,7 +1166,7 @@ __device__ __forceinline__ void fuse_partition(const MarkParams& k, const FuseBu
     uint32_t st = L.state[ci];
     if (st == 2u) {
       const unsigned long long vk = voxel_key(c.vkey[3 * gi], c.vkey[3 * gi + 1], c.vkey[3 * gi + 2]);
-      uint32_t slot = mk_hash(vk) & k.table_mask;
+      uint32_t slot = voxel_hash(vk) & k.table_mask;
       bool found = false;
       for (uint32_t probe = 0; probe <= k.table_mask; ++probe) {
         const unsigned long long prev = atomicCAS(&s.keys[slot], 0ull, vk);

@@ -19,6 +19,8 @@
 #include <cstring>
 #include <deque>
 
+#include "voxel_table.hip.h"
+
 // The reference is an x86-64 build without FMA contraction: every multiply and add below
 // rounds separately, in float and in double (hipcc's default would fuse them).
 #pragma clang fp contract(off)
@@ -40,144 +42,71 @@ struct FeedResult {          // host-mapped: written by the last k_feed_emit wor
 
 struct PerceptionScratch {
   float* stage_dev = nullptr;          // device address of `stage` (raw scan records, stride_floats apart)
-  uint32_t* claimed = nullptr;         // table slots claimed by this scan's voxels
-  unsigned char* table = nullptr;      // [keys 8B | sums 3x8B | counts 4B] x slots, one memset clears it
+  VoxelTable table;                    // base-frame voxels of one scan; k_feed_emit leaves it clean
   uint32_t* counters = nullptr;        // [0] n_out, [1] ticket, [2] claimed slots
   FeedResult* res_host = nullptr;      // pinned + mapped
   FeedResult* res_dev = nullptr;
   float* stage = nullptr;              // pinned staging for the raw scan
   size_t cap_points = 0;
-  size_t cap_slots = 0;
   uint32_t seq = 0;
   // stitcher (cbSensor :185-200): the last stitcher_num raw scans, oldest first, packed xyz in `stage`
   int stitcher_num = 0;
   std::deque<uint32_t> stitched;       // point counts of the queued scans
 };
 
-// key 0 = empty slot (a real key always has bit 63 set)
-__device__ __forceinline__ uint32_t hash_key(unsigned long long k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  k ^= k >> 33;
-  return (uint32_t)k;
-}
-
 __global__ __launch_bounds__(256) void k_feed_insert(FeedParams f, const float* __restrict__ scan, int stride_floats,
-                                                     unsigned long long* __restrict__ keys,
-                                                     double* __restrict__ sums, uint32_t* __restrict__ counts,
-                                                     uint32_t slot_mask, uint32_t* __restrict__ claimed,
-                                                     uint32_t* __restrict__ counters) {
+                                                     VoxelView table) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= f.n) return;
   const float* sp = scan + (size_t)i * stride_floats;
   const float sx = sp[0], sy = sp[1], sz = sp[2];
   if (!(isfinite(sx) && isfinite(sy) && isfinite(sz))) return;
-  // pcl::transformPointCloud(cloud, cloud, Affine3d): double multiply-add, float result
-  const float x = (float)(f.Rbs[0] * sx + f.Rbs[1] * sy + f.Rbs[2] * sz + f.tbs[0]);
-  const float y = (float)(f.Rbs[3] * sx + f.Rbs[4] * sy + f.Rbs[5] * sz + f.tbs[1]);
-  const float z = (float)(f.Rbs[6] * sx + f.Rbs[7] * sy + f.Rbs[8] * sz + f.tbs[2]);
+  const float3 p = affine_to_float(f.Rbs, f.tbs, sx, sy, sz);
   // pcl::PassThrough keeps limit_min <= v <= limit_max
-  if (x < -f.window || x > f.window || y < -f.window || y > f.window || z < 0.0f || z > f.height) return;
-  // pcl::VoxelGrid: ijk = floor(p * inverse_leaf_size), leaf 0.1f -> inverse 10.0f
-  const float inv_leaf = 1.0f / 0.1f;
-  const int ix = (int)floorf(x * inv_leaf), iy = (int)floorf(y * inv_leaf), iz = (int)floorf(z * inv_leaf);
-  const unsigned long long key = (1ull << 63) | ((unsigned long long)((uint32_t)(ix + (1 << 20)) & 0x1FFFFFu) << 42) |
-                                 ((unsigned long long)((uint32_t)(iy + (1 << 20)) & 0x1FFFFFu) << 21) |
-                                 (unsigned long long)((uint32_t)(iz + (1 << 20)) & 0x1FFFFFu);
-  uint32_t slot = hash_key(key) & slot_mask;
-  for (uint32_t probe = 0; probe <= slot_mask; ++probe) {
-    const unsigned long long prev = atomicCAS(&keys[slot], 0ull, key);
-    if (prev == 0ull || prev == key) {
-      if (prev == 0ull) claimed[atomicAdd(&counters[2], 1u)] = slot;   // first point of a voxel: list its slot for the emit pass
-      atomicAdd(&sums[3 * (size_t)slot + 0], (double)x);
-      atomicAdd(&sums[3 * (size_t)slot + 1], (double)y);
-      atomicAdd(&sums[3 * (size_t)slot + 2], (double)z);
-      atomicAdd(&counts[slot], 1u);
-      return;
-    }
-    slot = (slot + 1) & slot_mask;
-  }
+  if (p.x < -f.window || p.x > f.window || p.y < -f.window || p.y > f.window || p.z < 0.0f || p.z > f.height) return;
+  // pcl::VoxelGrid with a 0.1f leaf -> inverse 10.0f
+  voxel_insert(table, voxel_key(p.x, p.y, p.z, 1.0f / 0.1f), (double)p.x, (double)p.y, (double)p.z, 1u);
 }
 
-__global__ __launch_bounds__(256) void k_feed_emit(FeedParams f, unsigned long long* __restrict__ keys,
-                                                   double* __restrict__ sums,
-                                                   uint32_t* __restrict__ counts, const uint32_t* __restrict__ claimed,
-                                                   float4* __restrict__ out, uint32_t* __restrict__ counters,
-                                                   FeedResult* __restrict__ res, uint32_t seq) {
+__global__ __launch_bounds__(256) void k_feed_emit(FeedParams f, VoxelView table, float4* __restrict__ out,
+                                                   uint32_t* __restrict__ counters, FeedResult* __restrict__ res,
+                                                   uint32_t seq) {
   // one lane per occupied voxel (the slots k_feed_insert listed), not per table slot
   const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
   const bool occ = idx < counters[2];
-  const uint32_t slot = occ ? claimed[idx] : 0u;
-  // wave-aggregated append: one atomic per wave
-  const unsigned long long mask = __ballot(occ);
-  const int lane = threadIdx.x & 63;
-  uint32_t base = 0;
-  if (mask) {
-    if (lane == (__ffsll((long long)mask) - 1)) base = atomicAdd(&counters[0], (uint32_t)__popcll(mask));
-    base = __shfl(base, __ffsll((long long)mask) - 1, 64);
-  }
+  const uint32_t o = wave_append(occ, &counters[0]);
   if (occ) {
-    const double n = (double)counts[slot];
-    const float cx = (float)(sums[3 * (size_t)slot + 0] / n);
-    const float cy = (float)(sums[3 * (size_t)slot + 1] / n);
-    const float cz = (float)(sums[3 * (size_t)slot + 2] / n);
-    const float gx = (float)(f.Rgb[0] * cx + f.Rgb[1] * cy + f.Rgb[2] * cz + f.tgb[0]);
-    const float gy = (float)(f.Rgb[3] * cx + f.Rgb[4] * cy + f.Rgb[5] * cz + f.tgb[1]);
-    const float gz = (float)(f.Rgb[6] * cx + f.Rgb[7] * cy + f.Rgb[8] * cz + f.tgb[2]);
-    const uint32_t o = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-    out[o] = make_float4(gx, gy, gz, 0.f);
-    // leave the table empty for the next scan (saves a 2 MB memset per call)
-    keys[slot] = 0ull;
-    sums[3 * (size_t)slot + 0] = 0.0;
-    sums[3 * (size_t)slot + 1] = 0.0;
-    sums[3 * (size_t)slot + 2] = 0.0;
-    counts[slot] = 0u;
+    const float3 c = voxel_take(table, table.claimed[idx]);
+    const float3 g = affine_to_float(f.Rgb, f.tgb, c.x, c.y, c.z);
+    out[o] = make_float4(g.x, g.y, g.z, 0.f);
   }
-  // last workgroup publishes the count to the host (device-scope ticket; the count is
-  // only touched by device-scope atomics)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t t = __hip_atomic_fetch_add(&counters[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t == gridDim.x - 1) {
-      res->n_out = __hip_atomic_load(&counters[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      counters[0] = 0;         // next call
-      counters[1] = 0;
-      counters[2] = 0;
-      __threadfence_system();
-      __hip_atomic_store(&res->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+  // last workgroup publishes the count to the host (the count is only touched by device-scope atomics)
+  if (last_block(&counters[1])) {
+    res->n_out = __hip_atomic_load(&counters[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    counters[0] = 0;         // next call
+    counters[1] = 0;
+    counters[2] = 0;
+    __threadfence_system();
+    __hip_atomic_store(&res->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
-inline size_t feed_table_bytes(size_t slots) { return slots * (8 + 24 + 4) + 64; }
-
 inline int perception_alloc(PerceptionScratch& s, size_t max_points) {
   s.cap_points = max_points;
-  size_t slots = 1024;
-  while (slots < 2 * max_points) slots <<= 1;
-  s.cap_slots = slots;
-  if (hipMalloc(&s.claimed, max_points * sizeof(uint32_t)) != hipSuccess) return -1;
-  if (hipMalloc(&s.table, feed_table_bytes(slots)) != hipSuccess) return -1;
+  if (s.table.alloc(max_points) != 0) return -1;
   if (hipMalloc(&s.counters, 4 * sizeof(uint32_t)) != hipSuccess) return -1;
-  if (hipMemset(s.table, 0, feed_table_bytes(slots)) != hipSuccess) return -1;   // k_feed_emit keeps it clean afterwards
   if (hipMemset(s.counters, 0, 4 * sizeof(uint32_t)) != hipSuccess) return -1;
-  if (hipHostMalloc(&s.res_host, sizeof(FeedResult), hipHostMallocMapped) != hipSuccess) return -1;
-  if (hipHostGetDevicePointer(reinterpret_cast<void**>(&s.res_dev), s.res_host, 0) != hipSuccess) return -1;
+  if (host_mapped_alloc(&s.res_host, &s.res_dev, sizeof(FeedResult)) != 0) return -1;
   // the raw scan is read by k_feed_insert straight from this pinned, device-mapped buffer
   // (no separate H2D copy: the kernel's coalesced reads stream it over PCIe)
-  if (hipHostMalloc(&s.stage, max_points * 4 * sizeof(float), hipHostMallocMapped) != hipSuccess) return -1;
-  if (hipHostGetDevicePointer(reinterpret_cast<void**>(&s.stage_dev), s.stage, 0) != hipSuccess) return -1;
+  if (host_mapped_alloc(&s.stage, &s.stage_dev, max_points * 4 * sizeof(float)) != 0) return -1;
   s.res_host->n_out = 0;
   s.res_host->seq = 0;
   return 0;
 }
 
 inline void perception_free(PerceptionScratch& s) {
-  if (s.claimed) (void)hipFree(s.claimed);
-  if (s.table) (void)hipFree(s.table);
+  s.table.free();
   if (s.counters) (void)hipFree(s.counters);
   if (s.res_host) (void)hipHostFree(s.res_host);
   if (s.stage) (void)hipHostFree(s.stage);
@@ -191,8 +120,8 @@ inline void perception_free(PerceptionScratch& s) {
 inline int perception_feed(PerceptionScratch& s, FeedParams f, const float* scan, size_t stride_bytes,
                            float4* out_dev, hipStream_t stream, uint32_t* n_out) {
   *n_out = 0;
-  int stride_floats;
-  if (s.stitcher_num > 0) {
+  const bool stitch = s.stitcher_num > 0;
+  if (stitch) {
     if ((int)s.stitched.size() >= s.stitcher_num) {            // pop_front: the later scans move up
       const size_t drop = s.stitched.front();
       s.stitched.pop_front();
@@ -203,56 +132,24 @@ inline int perception_feed(PerceptionScratch& s, FeedParams f, const float* scan
     size_t have = 0;
     for (uint32_t c : s.stitched) have += c;
     if (have + (size_t)f.n > s.cap_points) return -2;
-    const size_t sf = stride_bytes / 4;
-    for (size_t i = 0; i < (size_t)f.n; ++i) {
-      s.stage[3 * (have + i) + 0] = scan[i * sf + 0];
-      s.stage[3 * (have + i) + 1] = scan[i * sf + 1];
-      s.stage[3 * (have + i) + 2] = scan[i * sf + 2];
-    }
+    pack_xyz_records(s.stage + 3 * have, scan, (size_t)f.n, stride_bytes);
     s.stitched.push_back((uint32_t)f.n);
     f.n = (int)(have + (size_t)f.n);
-    stride_floats = 3;
   }
   if (f.n == 0) return 0;
-  size_t slots = 1024;
-  while (slots < 2 * (size_t)f.n) slots <<= 1;
-  if (slots > s.cap_slots) return -2;
-  // stage the raw records in pinned memory: packed xyz(i) records go as they are,
-  // wider ones (PCL: 16/32 bytes) are narrowed to 12 bytes on the way
-  if (s.stitcher_num > 0) {
-    // (already staged above)
-  } else if (stride_bytes == 12 || stride_bytes == 16) {
-    stride_floats = (int)(stride_bytes / 4);
-    std::memcpy(s.stage, scan, (size_t)f.n * stride_bytes);
-  } else {
-    stride_floats = 3;
-    const size_t sf = stride_bytes / 4;
-    for (size_t i = 0; i < (size_t)f.n; ++i) {
-      s.stage[3 * i + 0] = scan[i * sf + 0];
-      s.stage[3 * i + 1] = scan[i * sf + 1];
-      s.stage[3 * i + 2] = scan[i * sf + 2];
-    }
-  }
-  // fixed layout over the full-capacity table; a call only uses its first `slots` entries
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(s.table);
-  double* sums = reinterpret_cast<double*>(s.table + s.cap_slots * 8);
-  uint32_t* counts = reinterpret_cast<uint32_t*>(s.table + s.cap_slots * 32);
+  // a call only uses the first `slots` entries of the full-capacity table
+  const size_t slots = voxel_slots_for((size_t)f.n);
+  if (slots > s.table.slots) return -2;
+  // the raw records go to pinned memory (the stitcher's queue is there already, packed)
+  const int stride_floats = stitch ? 3 : stage_xyz_records(s.stage, scan, (size_t)f.n, stride_bytes);
+  const VoxelView table = s.table.view(slots, s.counters + 2);
   const uint32_t seq = ++s.seq ? s.seq : ++s.seq;
-  hipLaunchKernelGGL(k_feed_insert, dim3((f.n + 255) / 256), dim3(256), 0, stream, f, s.stage_dev, stride_floats, keys,
-                     sums, counts, (uint32_t)(slots - 1), s.claimed, s.counters);
-  hipLaunchKernelGGL(k_feed_emit, dim3((unsigned)((f.n + 255) / 256)), dim3(256), 0, stream, f, keys, sums, counts,
-                     s.claimed, out_dev, s.counters, s.res_dev, seq);
+  hipLaunchKernelGGL(k_feed_insert, dim3((f.n + 255) / 256), dim3(256), 0, stream, f, s.stage_dev, stride_floats, table);
+  hipLaunchKernelGGL(k_feed_emit, dim3((unsigned)((f.n + 255) / 256)), dim3(256), 0, stream, f, table, out_dev, s.counters,
+                     s.res_dev, seq);
   if (hipGetLastError() != hipSuccess) return -5;
   // poll the host-mapped sequence number (bounded), then make sure the stream is idle
-  volatile uint32_t* seq_p = &s.res_host->seq;
-  bool seen = false;
-  for (uint64_t spins = 0; spins < (1ull << 26); ++spins) {
-    if (*seq_p == seq) { seen = true; break; }
-#if defined(__x86_64__)
-    __builtin_ia32_pause();
-#endif
-  }
-  if (!seen && hipStreamSynchronize(stream) != hipSuccess) return -4;
+  if (!wait_seq(&s.res_host->seq, seq) && hipStreamSynchronize(stream) != hipSuccess) return -4;
   *n_out = s.res_host->n_out;
   return 0;
 }

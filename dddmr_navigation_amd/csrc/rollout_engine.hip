@@ -1851,17 +1851,7 @@ int tick_collect(dddmr_rollout_ctx* ctx, dddmr_rollout_result* out) {
   // The last k_score workgroup stores the result into host-mapped memory and then
   // the tick's sequence number (system-scope release): polling it beats a stream
   // synchronise by several microseconds.  Bounded; falls back to the stream sync.
-  bool seen = false;
-  if (ctx->spin) {
-    volatile uint32_t* seq_p = &ctx->result_host->seq;
-    for (uint64_t spins = 0; spins < (1ull << 26); ++spins) {
-      if (*seq_p == k.seq) { seen = true; break; }
-#if defined(__x86_64__)
-      __builtin_ia32_pause();
-#endif
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-  }
+  const bool seen = ctx->spin && wait_seq(&ctx->result_host->seq, k.seq);
   if (!seen) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   if (ctx->pend.timed) {
     HIPCHK(ctx, hipEventSynchronize(ctx->pend.timed_all ? ctx->ev1 : ctx->evs1));

@@ -16,7 +16,7 @@ measures the depth image path (dddmr_rollout_set_depth_image, the uint16 image o
 parent commit's dddmr_rollout_set_depth_frame fed the driver's organised cloud of the same view (every pixel, 16-byte
 records), same protocol.  Reported beside it without a bar: sample_step 2 and 4, the parent's set_depth_frame fed the
 stage-one cloud prepared on the host (with the host time of this tool's NumPy stage one, which is not PCL's), and any
---variant-lib builds (one pixel per lane, unfused stage two) at sample_step 1.
+--variant-lib builds (such as one pixel per lane) at sample_step 1.
 """
 import argparse
 import ctypes as C
