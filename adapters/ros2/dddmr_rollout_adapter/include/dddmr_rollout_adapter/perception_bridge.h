@@ -11,6 +11,7 @@
 //   DepthImg2PointCloud::cbDepthImg + bufferCloud   (utils/depthimg2pointcloud_node.cpp:96-157)      -> feedDepthImage()
 //   ... bufferCloud's frustum                       (depth_camera_observation_buffer.cpp:134-174)    -> feedDepthFrustum()
 //   DepthCameraLayer::selfClear's decision tree     (plugins/depth_camera/depth_camera_layer.cpp:324-422) -> depthClearVerdicts()
+//   DepthCameraLayer::selfMark from the aggregate on (:487-601)                                        -> depthMarkCreate(), depthMarkClusters()
 //
 // Everything here is a template over the ROS / PCL types it is handed (geometry_msgs TransformStamped,
 // pcl::PointCloud<...>): this header includes neither, so it is syntax-checked in a plain C++ toolchain
@@ -201,6 +202,82 @@ inline int depthClearVerdicts(
   }
   if (engaged) {engaged->swap(eng);}
   return rc;
+}
+
+// The depth layer's selfMark state: pcl_ground_ and pcl_map_ (shared_data_) go to the device once, with the layer's
+// resolutions and clustering parameters.  Returns the library's code.  There is no "ready" flag on this side to set too
+// early: until this has returned DDDMR_OK the library answers depthMarkClusters with DDDMR_ERR_STATE and the layer runs
+// its CPU selfMark.
+template<class GroundCloud, class MapCloud>
+inline int depthMarkCreate(
+  dddmr_rollout_ctx * ctx, const GroundCloud & pcl_ground, const MapCloud & pcl_map, double resolution,
+  double height_resolution, double euclidean_cluster_extraction_tolerance,
+  int euclidean_cluster_extraction_min_cluster_size, double segmentation_ignore_ratio, uint32_t max_observation_points)
+{
+  if (!ctx) {return DDDMR_ERR_BAD_ARG;}
+  dddmr_depth_mark_config cfg;
+  std::memset(&cfg, 0, sizeof(cfg));
+  cfg.xy_resolution = resolution; cfg.height_resolution = height_resolution;
+  cfg.euclidean_cluster_extraction_tolerance = euclidean_cluster_extraction_tolerance;
+  cfg.euclidean_cluster_extraction_min_cluster_size = euclidean_cluster_extraction_min_cluster_size;
+  cfg.segmentation_ignore_ratio = segmentation_ignore_ratio;
+  cfg.max_observation_points = max_observation_points;
+  const size_t ng = pcl_ground.points.size(), nm = pcl_map.points.size();
+  return dddmr_rollout_depth_mark_create(
+    ctx, &cfg, ng ? &pcl_ground.points[0].x : nullptr, ng, sizeof(pcl_ground.points[0]),
+    nm ? &pcl_map.points[0].x : nullptr, nm, sizeof(pcl_map.points[0]));
+}
+
+// What one selfMark hands to addPCPtr, in the order the reference would call it.
+template<class Cloud>
+struct DepthMarkClusters
+{
+  struct Cluster
+  {
+    float cx, cy, cz;      // addPCPtr's centroid arguments
+    int32_t voxel[3];      // the key addPCPtr will compute from them
+    uint32_t size;         // points before the 0.2 m VoxelGrid
+    Cloud cloud;           // cloud_cluster: the downsampled points
+  };
+  std::vector<Cluster> clusters;
+  float coefficients[4];   // pcl::ModelCoefficients::values of :568-578, the same for every cluster
+  dddmr_depth_mark_stats stats;
+};
+
+// selfMark from the aggregated observation on (depth_camera_layer.cpp:487-601), on the device.  The caller keeps the
+// early returns and trans_gbl2b_, then walks out.clusters front to back calling
+// pct_marking_->addPCPtr(cx, cy, cz, cloud, coefficients).  The two debug clouds are not produced.  Returns the library's
+// code; on anything but DDDMR_OK `out` holds no cluster and the layer runs its CPU selfMark for this pass.
+template<class Cloud, class TransformStamped>
+inline int depthMarkClusters(dddmr_rollout_ctx * ctx, const TransformStamped & trans_gbl2b, DepthMarkClusters<Cloud> & out)
+{
+  out.clusters.clear();
+  std::memset(&out.stats, 0, sizeof(out.stats));
+  if (!ctx) {return DDDMR_ERR_BAD_ARG;}
+  double g2b[7];
+  toPose7(trans_gbl2b, g2b);
+  int rc = dddmr_rollout_depth_mark_clusters(ctx, g2b, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &out.stats);
+  if (rc != DDDMR_OK) {return rc;}
+  const size_t c = out.stats.n_accepted, p = out.stats.n_points;
+  std::vector<float> centroid(3 * c + 3), xyz(3 * p + 3);
+  std::vector<int32_t> voxel(3 * c + 3);
+  std::vector<uint32_t> size(c + 1), offsets(c + 1);
+  rc = dddmr_rollout_depth_mark_clusters(
+    ctx, g2b, c, p, centroid.data(), voxel.data(), size.data(), offsets.data(), xyz.data(), out.coefficients, &out.stats);
+  if (rc != DDDMR_OK) {return rc;}          // (a frame published between the two calls: capacity; the next pass retries)
+  out.clusters.resize(out.stats.n_accepted);
+  for (size_t i = 0; i < out.clusters.size(); ++i) {
+    auto & cl = out.clusters[i];
+    cl.cx = centroid[3 * i]; cl.cy = centroid[3 * i + 1]; cl.cz = centroid[3 * i + 2];
+    cl.voxel[0] = voxel[3 * i]; cl.voxel[1] = voxel[3 * i + 1]; cl.voxel[2] = voxel[3 * i + 2];
+    cl.size = size[i];
+    cl.cloud.points.resize(offsets[i + 1] - offsets[i]);
+    for (uint32_t j = offsets[i]; j < offsets[i + 1]; ++j) {
+      auto & pt = cl.cloud.points[j - offsets[i]];
+      pt.x = xyz[3 * static_cast<size_t>(j)]; pt.y = xyz[3 * static_cast<size_t>(j) + 1]; pt.z = xyz[3 * static_cast<size_t>(j) + 2];
+    }
+  }
+  return DDDMR_OK;
 }
 
 // PathBlockedStrategy::selfMark on the device's aggregate observation.  pcl_prune_plan is

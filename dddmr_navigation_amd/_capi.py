@@ -193,6 +193,26 @@ class DepthFrustumConfig(C.Structure):
     ]
 
 
+class DepthMarkConfig(C.Structure):
+    """dddmr_depth_mark_config: the depth camera layer's clustering parameters (depth_camera_layer.cpp:52-75)."""
+    _fields_ = [
+        ("xy_resolution", C.c_double), ("height_resolution", C.c_double),
+        ("euclidean_cluster_extraction_tolerance", C.c_double),
+        ("euclidean_cluster_extraction_min_cluster_size", C.c_int32),
+        ("reserved", C.c_int32),
+        ("segmentation_ignore_ratio", C.c_double),
+        ("max_observation_points", C.c_uint32), ("reserved2", C.c_uint32),
+    ]
+
+
+class DepthMarkStats(C.Structure):
+    _fields_ = [
+        ("n_observation", C.c_uint32), ("n_clusters", C.c_uint32), ("n_ground_rejected", C.c_uint32),
+        ("n_static_rejected", C.c_uint32), ("n_outside_frustums", C.c_uint32), ("n_accepted", C.c_uint32),
+        ("n_points", C.c_uint32), ("launches", C.c_uint32),
+    ]
+
+
 # dddmr_rollout_depth_clear_verdicts: bit 0 of a verdict = kept, bits 1-2 = the branch that decided
 DEPTH_CLEAR_KEPT = 1
 DEPTH_CLEAR_OUTSIDE, DEPTH_CLEAR_ATTACHED, DEPTH_CLEAR_INSIDE = 1, 2, 3
@@ -256,6 +276,8 @@ EXPORTED_SYMBOLS = (
     "dddmr_rollout_depth_frustum_test",
     "dddmr_rollout_depth_clear_verdicts",
     "dddmr_rollout_depth_clear_launches",
+    "dddmr_rollout_depth_mark_create",
+    "dddmr_rollout_depth_mark_clusters",
     "dddmr_rollout_stream_ceiling",
     "dddmr_rollout_selftest_sincos",
     "dddmr_rollout_last_error",
@@ -391,6 +413,12 @@ def load_library() -> C.CDLL:
     lib.dddmr_rollout_depth_clear_verdicts.restype = C.c_int
     lib.dddmr_rollout_depth_clear_launches.argtypes = [ctx_p, C.POINTER(C.c_uint32)]
     lib.dddmr_rollout_depth_clear_launches.restype = C.c_int
+    lib.dddmr_rollout_depth_mark_create.argtypes = [ctx_p, C.POINTER(DepthMarkConfig), C.c_void_p, C.c_size_t, C.c_size_t,
+                                                    C.c_void_p, C.c_size_t, C.c_size_t]
+    lib.dddmr_rollout_depth_mark_create.restype = C.c_int
+    lib.dddmr_rollout_depth_mark_clusters.argtypes = [ctx_p, C.POINTER(C.c_double), C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DepthMarkStats)]
+    lib.dddmr_rollout_depth_mark_clusters.restype = C.c_int
     lib.dddmr_rollout_stream_ceiling.argtypes = [ctx_p, C.c_size_t, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.dddmr_rollout_stream_ceiling.restype = C.c_int
     lib.dddmr_rollout_selftest_sincos.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]

@@ -156,6 +156,8 @@ float absmax(const std::vector<float>& v) {
 
 struct MarkingState;                       // global-mode marking / clearing layer, marking_host.hip.h
 void marking_free(MarkingState* m);
+struct DepthMarkState;                     // the depth camera's selfMark, depth_mark.hip.h
+void depth_mark_free(DepthMarkState* s);
 
 }  // namespace
 
@@ -257,6 +259,7 @@ struct dddmr_rollout_ctx {
   DevResult* local_result_dev = nullptr;
 
   MarkingState* marking = nullptr;   // dddmr_rollout_marking_create
+  DepthMarkState* dmark = nullptr;   // dddmr_rollout_depth_mark_create
 
   std::mutex tick_mu;
   std::mutex err_mu;        // last_error is written by tick and sensor threads alike
@@ -472,6 +475,8 @@ size_t dddmr_rollout_sizeof(int which) {
     case 8: return sizeof(dddmr_depth_source_config);
     case 9: return sizeof(dddmr_depth_image_config);
     case 10: return sizeof(dddmr_depth_frustum_config);
+    case 11: return sizeof(dddmr_depth_mark_config);
+    case 12: return sizeof(dddmr_depth_mark_stats);
     default: return 0;
   }
 }
@@ -500,6 +505,7 @@ void dddmr_rollout_destroy(dddmr_rollout_ctx* ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
   if (ctx->marking) { marking_free(ctx->marking); ctx->marking = nullptr; }
+  if (ctx->dmark) { depth_mark_free(ctx->dmark); ctx->dmark = nullptr; }
   if (ctx->comm) (void)rccl().comm_destroy(ctx->comm);
   if (ctx->slots_dev) (void)hipFree(ctx->slots_dev);
   if (ctx->slots_red) (void)hipFree(ctx->slots_red);
@@ -1158,6 +1164,26 @@ static int depth_clear_scratch(dddmr_rollout_ctx* ctx, const char* what) {
   return DDDMR_OK;
 }
 
+// The grid over the depth sources' observation (n_obs points in all), rebuilt only when a depth source has published
+// since it was last built: the clearing verdicts and selfMark's clusters share it.  producer_mu held.
+static int depth_observation_grid(dddmr_rollout_ctx* ctx, DepthClear& d, size_t n_obs, hipStream_t st, uint32_t* ops) {
+  if (d.built && d.built_epoch == ctx->depth_epoch) return DDDMR_OK;
+  size_t at = 0;
+  for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) {
+    if (!ctx->depth[i] || !ctx->src_n[i]) continue;
+    HIPCHK(ctx, hipMemcpyAsync(d.pts + at, ctx->src_cloud[i], (size_t)ctx->src_n[i] * sizeof(float4), hipMemcpyDeviceToDevice, st));
+    at += ctx->src_n[i];
+    ++*ops;
+  }
+  d.built = false;
+  const int b = dc_build_grid(d, (uint32_t)n_obs, st);
+  if (b < 0) return fail(ctx, DDDMR_ERR_HIP, "depth observation grid: build failed");
+  *ops += (uint32_t)b;
+  d.built = true;
+  d.built_epoch = ctx->depth_epoch;
+  return DDDMR_OK;
+}
+
 int dddmr_rollout_depth_frustum_test(dddmr_rollout_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes,
                                      uint8_t* in_frustums_out, uint8_t* attach_out) {
   if (!ctx) return DDDMR_ERR_BAD_ARG;
@@ -1225,21 +1251,7 @@ int dddmr_rollout_depth_clear_verdicts(dddmr_rollout_ctx* ctx, double xy_resolut
   for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i)
     if (ctx->depth[i]) n_obs += ctx->src_n[i];
   const bool observation_clear = !(n_obs > 5);       // depth_camera_layer.cpp:258-264
-  if (!observation_clear && !(d.built && d.built_epoch == ctx->depth_epoch)) {
-    size_t at = 0;
-    for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) {
-      if (!ctx->depth[i] || !ctx->src_n[i]) continue;
-      HIPCHK(ctx, hipMemcpyAsync(d.pts + at, ctx->src_cloud[i], (size_t)ctx->src_n[i] * sizeof(float4), hipMemcpyDeviceToDevice, st));
-      at += ctx->src_n[i];
-      ++ops;
-    }
-    d.built = false;
-    const int b = dc_build_grid(d, (uint32_t)n_obs, st);
-    if (b < 0) return fail(ctx, DDDMR_ERR_HIP, "depth_clear_verdicts: grid build failed");
-    ops += (uint32_t)b;
-    d.built = true;
-    d.built_epoch = ctx->depth_epoch;
-  }
+  if (!observation_clear && (rc = depth_observation_grid(ctx, d, n_obs, st, &ops)) != DDDMR_OK) return rc;
   const size_t total = offsets[m];
   const size_t vox_bytes = m * 3 * sizeof(int32_t), off_bytes = (m + 1) * sizeof(uint32_t);
   if (dc_reserve(&d.in_host, &d.in_dev, &d.in_cap, vox_bytes + off_bytes + total * 12) != 0 ||
@@ -2333,3 +2345,4 @@ int dddmr_rollout_get_best_cuboids(dddmr_rollout_ctx* ctx, float* vertices_out, 
 }  // extern "C"
 
 #include "marking_host.hip.h"
+#include "depth_mark.hip.h"

@@ -267,6 +267,39 @@ class LocalPlanner:
         self._check(self._lib.dddmr_rollout_depth_clear_launches(self._ctx, C.byref(n)))
         return int(n.value)
 
+    def depth_mark_create(self, xy_resolution: float, height_resolution: float, ground_xyz: np.ndarray, map_xyz: np.ndarray,
+                          tolerance: float = 0.1, min_cluster_size: int = 1, segmentation_ignore_ratio: float = 0.2,
+                          max_observation_points: int = 1 << 16):
+        """The depth camera layer's selfMark state: pcl_ground_ / pcl_map_ ([N, >=3] float32, the map may be empty) go to
+        the device once.  Independent of the lidar marking layer; calling it again replaces the state."""
+        ground = np.ascontiguousarray(ground_xyz, dtype=np.float32)
+        smap = np.ascontiguousarray(map_xyz, dtype=np.float32)
+        for a in (ground, smap):
+            if a.ndim != 2 or (a.shape[0] and a.shape[1] < 3):
+                raise ValueError("ground / map must be [N, >=3] float32")
+        cfg = K.DepthMarkConfig(float(xy_resolution), float(height_resolution), float(tolerance), int(min_cluster_size), 0,
+                                float(segmentation_ignore_ratio), int(max_observation_points), 0)
+        self._check(self._lib.dddmr_rollout_depth_mark_create(
+            self._ctx, C.byref(cfg), ground.ctypes.data if ground.shape[0] else None, ground.shape[0],
+            ground.strides[0] if ground.shape[0] else 12, smap.ctypes.data if smap.shape[0] else None, smap.shape[0],
+            smap.strides[0] if smap.shape[0] else 12))
+
+    def depth_mark_clusters(self, T_gbl_base):
+        """One DepthCameraLayer::selfMark (depth_camera_layer.cpp:487-601) on the depth sources' current observation ->
+        (centroids [C,3] float32, voxels [C,3] int32, sizes [C] uint32, offsets [C+1] uint32, points [P,3] float32,
+        plane [4] float32, stats): what addPCPtr is to be called with, in the reference's order.  The buffers are sized
+        by a count-only call first."""
+        tgb = (C.c_double * 7)(*[float(v) for v in T_gbl_base])
+        st = K.DepthMarkStats()
+        self._check(self._lib.dddmr_rollout_depth_mark_clusters(self._ctx, tgb, 0, 0, None, None, None, None, None, None, C.byref(st)))
+        c, p = int(st.n_accepted), int(st.n_points)
+        cen, vox = np.zeros((max(c, 1), 3), np.float32), np.zeros((max(c, 1), 3), np.int32)
+        size, off = np.zeros(max(c, 1), np.uint32), np.zeros(c + 1, np.uint32)
+        pts, plane = np.zeros((max(p, 1), 3), np.float32), np.zeros(4, np.float32)
+        self._check(self._lib.dddmr_rollout_depth_mark_clusters(self._ctx, tgb, c, p, cen.ctypes.data, vox.ctypes.data, size.ctypes.data,
+                                                                off.ctypes.data, pts.ctypes.data, plane.ctypes.data, C.byref(st)))
+        return cen[:c], vox[:c], size[:c], off, pts[:p], plane, st
+
     def set_stitcher(self, stitcher_num: int):
         """cbSensor's `stitcher_num` (multilayer_spinning_lidar.cpp:185-200): feed the last N raw scans together."""
         self._check(self._lib.dddmr_rollout_set_stitcher(self._ctx, int(stitcher_num)))

@@ -418,6 +418,74 @@ int dddmr_rollout_depth_clear_verdicts(dddmr_rollout_ctx* ctx, double xy_resolut
                                        uint8_t* verdict_out /* [m] */, uint32_t* engaged_out /* [m], may be NULL */);
 int dddmr_rollout_depth_clear_launches(dddmr_rollout_ctx* ctx, uint32_t* launches_last_call);
 
+/* Depth camera selfMark: the clusters addPCPtr is to be called with (additions to ABI version 2; no existing struct or
+   entry changes).  The host keeps pct_marking_, addPCPtr and its dGraph; nothing is stored on the device between calls.
+
+   dddmr_rollout_depth_mark_create copies pcl_ground_ and pcl_map_ to the device once and builds their search grids (the
+   inputs of dddmr_rollout_marking_create; n_map may be 0).  It is independent of dddmr_rollout_marking_create: a context
+   may have either, both or neither.  Calling it again replaces the state, which is freed with the context.
+   DDDMR_ERR_BAD_ARG: a resolution or the tolerance is not positive and finite, a negative minimum cluster size,
+   max_observation_points 0, a bad pointer / stride; DDDMR_ERR_CAPACITY: max_observation_points above 2^20;
+   DDDMR_ERR_STATE: a dddmr_rollout_tick_begin is pending.  A refused call leaves the earlier state in place.
+
+   dddmr_rollout_depth_mark_clusters is one DepthCameraLayer::selfMark from depth_camera_layer.cpp:487 on (the early
+   returns above it stay with the caller, except isFirstScanReady: DDDMR_ERR_STATE before depth_mark_create, without
+   a depth source or while a depth source has no frustum).  The observation is the DEPTH sources' alive frames in source
+   order, exactly the one dddmr_rollout_depth_clear_verdicts searches; lidar sources of the context stay out.  With
+   <= 5 points (:491) the call returns DDDMR_OK with n_accepted = 0; with more than max_observation_points,
+   DDDMR_ERR_CAPACITY.  Then, as the reference does it:
+     1. pcl::extractEuclideanClusters (oracle/ASSUMPTIONS.md rows 1, 2, 9): FLANN's float squared distance against
+        static_cast<float>(tol * tol), strict <; clusters in order of their lowest point index, each cluster's indices
+        ascending; kept iff min_cluster_size <= size (the maximum is the observation's size).
+     2. the outputs follow std::sort(clusters.rbegin(), clusters.rend(), comparePointClusters) (row 10), replayed on the
+        host over the kept clusters' sizes in creation order: a caller that walks them front to back and calls addPCPtr
+        ends with the reference's map, contested voxels included.
+     3. centroid: float running sums of x, y, z in ascending point index, each divided by (float)size.
+     4. dropped if a ground node lies within 0.1 of the centroid (:539; the lidar layer uses 0.05).
+     5. pcl::VoxelGrid at 0.2 m (rows 7, 8): cell floorf(p * (1.0f / 0.2f)), output in voxel index order (x fastest), each
+        point the float sum of its voxel's points in input order divided by the count.  This is cloud_cluster, the pc_ the
+        verdict call is later fed.
+     6. static map (:552-562): with segmentation_ignore_ratio <= 0.999 the loop searches with the CENTROID (radius 0.1) for
+        every downsampled point and breaks once hit > size * ratio; kept iff hit <= size * ratio (size_t against double).
+     7. isinFrustumsObservations(centroid) on the raw float centroid (:591), not on the voxel centre.
+   Per accepted cluster i: centroid_out[i], voxel_out[i] = ((int)(cx / xy_resolution), (int)(cy / xy_resolution),
+   (int)(cz / height_resolution)) (float divided by double, truncated, as addPCPtr does), size_out[i] = its size before
+   downsampling, cluster_xyz_out[offsets_out[i] .. offsets_out[i + 1]) = its downsampled points.  plane_out = the
+   ModelCoefficients of :568-578 (tf2::quatRotate(q, (0, 0, 1)) and d in double, rounded to float), the same for all.
+   stats is always required.  The other outputs are all given or all NULL ("count only": stats alone is filled).  Too small
+   a capacity: DDDMR_ERR_CAPACITY with stats filled (n_accepted, n_points are what is needed) and no other output written.
+   A refused call changes nothing a later call can see.  One host wait; the call runs on the feeds' stream, serialised
+   with the feeds, and may be made between dddmr_rollout_tick_begin and _tick_end with the serial answer.  It shares the
+   observation grid of the verdict call: the two together rebuild it at most once per published frame. */
+typedef struct {
+  double xy_resolution, height_resolution;                 /* the layer's, for the voxel key only */
+  double euclidean_cluster_extraction_tolerance;           /* plugin default 0.1 */
+  int32_t euclidean_cluster_extraction_min_cluster_size;   /* plugin default 1 */
+  int32_t reserved;
+  double segmentation_ignore_ratio;
+  uint32_t max_observation_points;                          /* depth observation the scratch is sized for */
+  uint32_t reserved2;
+} dddmr_depth_mark_config;
+
+typedef struct {
+  uint32_t n_observation;       /* points of the depth observation clustered */
+  uint32_t n_clusters;          /* clusters extractEuclideanClusters returns (min size applied) */
+  uint32_t n_ground_rejected;   /* centroid within 0.1 m of a ground node (:539) */
+  uint32_t n_static_rejected;   /* hit > size * segmentation_ignore_ratio (:562) */
+  uint32_t n_outside_frustums;  /* passed both, isinFrustumsObservations(centroid) false (:591) */
+  uint32_t n_accepted;          /* clusters written */
+  uint32_t n_points;            /* 0.2 m downsampled points written (= offsets[n_accepted]) */
+  uint32_t launches;            /* device operations the call enqueued */
+} dddmr_depth_mark_stats;
+
+int dddmr_rollout_depth_mark_create(dddmr_rollout_ctx* ctx, const dddmr_depth_mark_config* cfg, const float* ground_xyz,
+                                    size_t n_ground, size_t ground_stride_bytes, const float* map_xyz, size_t n_map,
+                                    size_t map_stride_bytes);
+int dddmr_rollout_depth_mark_clusters(dddmr_rollout_ctx* ctx, const double T_gbl_base[7], size_t capacity_clusters,
+                                      size_t capacity_points, float* centroid_out /* [c][3] */, int32_t* voxel_out /* [c][3] */,
+                                      uint32_t* size_out /* [c] */, uint32_t* offsets_out /* [c + 1] */,
+                                      float* cluster_xyz_out /* [p][3] */, float plane_out[4], dddmr_depth_mark_stats* stats);
+
 /* Copy the current aggregate observation back (debug / parity of set_scan). */
 int dddmr_rollout_get_cloud(dddmr_rollout_ctx* ctx, float* xyzi_out, size_t capacity,
                             size_t* n_points);

@@ -142,6 +142,41 @@ class LocalPlanner {
     check(dddmr_rollout_depth_clear_verdicts(ctx_, xy_resolution, height_resolution, voxel_xyz, offsets, cluster_xyz, m,
                                              verdict.data(), engaged.data()));
   }
+  // the depth camera's selfMark: pcl_ground_ / pcl_map_ to the device once, then per update the clusters addPCPtr is
+  // to be called with, in the reference's order
+  void depthMarkCreate(const dddmr_depth_mark_config& cfg, const float* ground_xyz, size_t n_ground, size_t ground_stride_bytes,
+                       const float* map_xyz, size_t n_map, size_t map_stride_bytes) {
+    check(dddmr_rollout_depth_mark_create(ctx_, &cfg, ground_xyz, n_ground, ground_stride_bytes, map_xyz, n_map, map_stride_bytes));
+  }
+  struct DepthMarkClusters {
+    std::vector<float> centroid;      // [c][3]
+    std::vector<int32_t> voxel;       // [c][3]
+    std::vector<uint32_t> size;       // [c] points before the 0.2 m VoxelGrid
+    std::vector<uint32_t> offsets;    // [c + 1] into cluster_xyz
+    std::vector<float> cluster_xyz;   // [p][3]
+    float plane[4];
+    dddmr_depth_mark_stats stats;
+  };
+  // the library's code (DDDMR_OK or a refusal: the caller then runs its CPU selfMark); buffers sized by a count-only call
+  int depthMarkClusters(const double T_gbl_base[7], DepthMarkClusters& out) {
+    out.stats = dddmr_depth_mark_stats{};
+    int rc = dddmr_rollout_depth_mark_clusters(ctx_, T_gbl_base, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &out.stats);
+    if (rc != DDDMR_OK) return rc;
+    const size_t c = out.stats.n_accepted, p = out.stats.n_points;
+    out.centroid.assign(3 * c + 3, 0.f);
+    out.voxel.assign(3 * c + 3, 0);
+    out.size.assign(c + 1, 0u);
+    out.offsets.assign(c + 1, 0u);
+    out.cluster_xyz.assign(3 * p + 3, 0.f);
+    rc = dddmr_rollout_depth_mark_clusters(ctx_, T_gbl_base, c, p, out.centroid.data(), out.voxel.data(), out.size.data(),
+                                           out.offsets.data(), out.cluster_xyz.data(), out.plane, &out.stats);
+    if (rc != DDDMR_OK) return rc;
+    out.centroid.resize(3 * c);
+    out.voxel.resize(3 * c);
+    out.size.resize(c);
+    out.cluster_xyz.resize(3 * p);
+    return DDDMR_OK;
+  }
   // prune plan poses, x y z qx qy qz qw each (output of Local_Planner::prunePlan)
   void setPlan(const double* poses_xyz_qxyzw, size_t n_poses) {
     check(dddmr_rollout_set_prune_plan(ctx_, poses_xyz_qxyzw, n_poses));

@@ -1,0 +1,46 @@
+"""depthMarkCreate() / depthMarkClusters() of perception_bridge.h: compiled without ROS against a fake C-ABI and run
+(tests/cpp/depth_mark_bridge_test.cpp), and syntax-checked with the stand-in ROS / PCL headers of tests/stubs/."""
+import os
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+
+from conftest import ROOT
+
+INC = ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "adapters", "ros2", "dddmr_rollout_adapter", "include")]
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_depth_mark_bridge_against_a_fake_abi():
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "depth_mark_bridge_test")
+        r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", *INC,
+                            os.path.join(ROOT, "tests", "cpp", "depth_mark_bridge_test.cpp"), "-o", exe], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        r = subprocess.run([exe], capture_output=True, text=True)
+        assert r.returncode == 0 and "depth mark bridge OK" in r.stdout, (r.stdout, r.stderr)
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_depth_mark_bridge_syntax_with_the_stand_in_pcl_types():
+    src = """
+#include <pcl/point_cloud.h>
+#include <pcl/point_types.h>
+#include <geometry_msgs/msg/transform_stamped.hpp>
+#include "dddmr_rollout_adapter/perception_bridge.h"
+int use(dddmr_rollout_ctx* ctx, const pcl::PointCloud<pcl::PointXYZ>& ground, const pcl::PointCloud<pcl::PointXYZI>& map,
+        const geometry_msgs::msg::TransformStamped& gbl2b) {
+  int rc = dddmr_rollout_adapter::depthMarkCreate(ctx, ground, map, 0.05, 0.05, 0.1, 1, 0.2, 1u << 16);
+  dddmr_rollout_adapter::DepthMarkClusters<pcl::PointCloud<pcl::PointXYZI>> out;
+  if (rc == DDDMR_OK) rc = dddmr_rollout_adapter::depthMarkClusters(ctx, gbl2b, out);
+  return rc + (int)out.clusters.size();
+}
+"""
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "use.cpp")
+        open(path, "w").write(src)
+        r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-I", os.path.join(ROOT, "tests", "stubs"), *INC, path],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
