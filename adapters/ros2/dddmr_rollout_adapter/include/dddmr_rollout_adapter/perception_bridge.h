@@ -12,6 +12,7 @@
 //   ... bufferCloud's frustum                       (depth_camera_observation_buffer.cpp:134-174)    -> feedDepthFrustum()
 //   DepthCameraLayer::selfClear's decision tree     (plugins/depth_camera/depth_camera_layer.cpp:324-422) -> depthClearVerdicts()
 //   DepthCameraLayer::selfMark from the aggregate on (:487-601)                                        -> depthMarkCreate(), depthMarkClusters()
+//   DepthCameraLayer::selfClear + selfMark + updateLethalPointCloud with the store on the device      -> DepthLayerBridge
 //
 // Everything here is a template over the ROS / PCL types it is handed (geometry_msgs TransformStamped,
 // pcl::PointCloud<...>): this header includes neither, so it is syntax-checked in a plain C++ toolchain
@@ -424,6 +425,109 @@ inline dddmr_marking_config markingConfig(
   c.max_cluster_points = static_cast<uint32_t>(markings * 16 > (1u << 26) ? (1u << 26) : markings * 16);
   return c;
 }
+
+// The global-mode DepthCameraLayer with its marking store, dGraph and lethal set on the device
+// (the depth_layer entries of dddmr_rollout.h): what selfClear / selfMark / resetdGraph / updateLethalPointCloud / get_dGraphValue of
+// a patched layer call.  ready() is true only after a create that returned DDDMR_OK and goes false again on ANY failure
+// of create, reset or clearThenMark: the caller then runs its CPU pass and must not read this bridge's copies until a
+// later create has succeeded (the device state no longer follows the layer's history).
+class DepthLayerBridge
+{
+public:
+  template<class GroundCloud, class MapCloud>
+  int create(
+    dddmr_rollout_ctx * ctx, const dddmr_depth_layer_config & cfg, const GroundCloud & pcl_ground, size_t static_ground_size,
+    const MapCloud & pcl_map)
+  {
+    ready_ = false;
+    if (!ctx) {return DDDMR_ERR_BAD_ARG;}
+    const size_t nm = pcl_map.points.size();
+    const int rc = dddmr_rollout_depth_layer_create(
+      ctx, &cfg, static_ground_size ? &pcl_ground.points[0].x : nullptr, static_ground_size, sizeof(pcl_ground.points[0]),
+      nm ? &pcl_map.points[0].x : nullptr, nm, nm ? sizeof(pcl_map.points[0]) : 16);
+    if (rc != DDDMR_OK) {return rc;}
+    ctx_ = ctx;
+    n_ground_ = static_ground_size;
+    max_obstacle_distance_ = cfg.max_obstacle_distance;
+    dgraph_.assign(n_ground_ + 1, max_obstacle_distance_);
+    lethal_.assign(n_ground_ + 1, 0);
+    ready_ = true;
+    return DDDMR_OK;
+  }
+  bool ready() const {return ready_;}
+
+  // resetdGraph
+  int reset()
+  {
+    if (!ready_) {return DDDMR_ERR_STATE;}
+    const int rc = dddmr_rollout_depth_layer_reset(ctx_);
+    if (rc != DDDMR_OK) {ready_ = false; return rc;}
+    dgraph_.assign(n_ground_ + 1, max_obstacle_distance_);
+    lethal_.assign(n_ground_ + 1, 0);
+    return DDDMR_OK;
+  }
+
+  // one selfClear + selfMark pass on the observation the depth feeds left on the device, then the host copies of the
+  // dGraph and the lethal flags are refreshed.  Any code but DDDMR_OK: run the CPU pass; ready() is false from then on.
+  template<class TransformStamped>
+  int clearThenMark(const TransformStamped & trans_gbl2b, dddmr_depth_layer_stats * stats = nullptr)
+  {
+    if (!ready_) {return DDDMR_ERR_STATE;}
+    double g2b[7];
+    toPose7(trans_gbl2b, g2b);
+    dddmr_depth_layer_stats local;
+    int rc = dddmr_rollout_depth_layer_update(ctx_, g2b, stats ? stats : &local);
+    if (rc == DDDMR_OK) {rc = dddmr_rollout_depth_layer_get_dgraph(ctx_, dgraph_.data(), dgraph_.size());}
+    if (rc == DDDMR_OK) {rc = dddmr_rollout_depth_layer_get_lethal(ctx_, lethal_.data(), lethal_.size());}
+    if (rc != DDDMR_OK) {ready_ = false;}
+    return rc;
+  }
+
+  // Marking::get_dGraphValue(index)
+  double dGraphValue(unsigned int index) const {return index < dgraph_.size() ? dgraph_[index] : 9999.0;}
+
+  // updateLethalPointCloud: the ground nodes of lethal_map_ as points of `out`
+  template<class GroundCloud, class LethalCloud>
+  void lethalPointCloud(const GroundCloud & pcl_ground, LethalCloud & out) const
+  {
+    for (size_t i = 0; i < n_ground_ && i < lethal_.size() && i < pcl_ground.points.size(); ++i) {
+      if (!lethal_[i]) {continue;}
+      typename LethalCloud::PointType ipt;
+      ipt.x = pcl_ground.points[i].x; ipt.y = pcl_ground.points[i].y; ipt.z = pcl_ground.points[i].z;
+      out.push_back(ipt);
+    }
+  }
+
+  // the marking topic: every alive marking's stored cluster pc_ (its 0.2 m-downsampled points), as the reference
+  // publishes it.  Fetched on demand only (call it when the topic has subscribers).
+  template<class MarkingCloud>
+  int markingPointCloud(MarkingCloud & out) const
+  {
+    if (!ready_) {return DDDMR_ERR_STATE;}
+    size_t m = 0, p = 0;
+    int rc = dddmr_rollout_depth_layer_get_clusters(ctx_, nullptr, nullptr, nullptr, 0, 0, &m, &p);
+    if (rc != DDDMR_OK || p == 0) {return rc;}
+    std::vector<int32_t> voxel(3 * m);
+    std::vector<uint32_t> offsets(m + 1);
+    std::vector<float> xyz(3 * p);
+    rc = dddmr_rollout_depth_layer_get_clusters(ctx_, voxel.data(), offsets.data(), xyz.data(), m, p, &m, &p);
+    if (rc != DDDMR_OK) {return rc;}
+    for (size_t i = 0; i < p; ++i) {
+      typename MarkingCloud::PointType ipt;
+      ipt.x = xyz[3 * i]; ipt.y = xyz[3 * i + 1]; ipt.z = xyz[3 * i + 2];
+      out.push_back(ipt);
+    }
+    return DDDMR_OK;
+  }
+
+private:
+  dddmr_rollout_ctx * ctx_ = nullptr;
+  bool ready_ = false;
+  size_t n_ground_ = 0;
+  double max_obstacle_distance_ = 9999.0;
+  std::vector<double> dgraph_;
+  std::vector<uint8_t> lethal_;
+};
 
 }  // namespace dddmr_rollout_adapter
 #endif

@@ -213,6 +213,29 @@ class DepthMarkStats(C.Structure):
     ]
 
 
+class DepthLayerConfig(C.Structure):
+    """dddmr_depth_layer_config: the global-mode depth camera layer (depth_camera_layer.cpp:52-75 and the Marking's radii)."""
+    _fields_ = [
+        ("xy_resolution", C.c_double), ("height_resolution", C.c_double),
+        ("marking_height", C.c_double), ("perception_window_size", C.c_double),
+        ("euclidean_cluster_extraction_tolerance", C.c_double),
+        ("euclidean_cluster_extraction_min_cluster_size", C.c_int32),
+        ("reserved", C.c_int32),
+        ("segmentation_ignore_ratio", C.c_double),
+        ("inscribed_radius", C.c_double), ("inflation_radius", C.c_double), ("max_obstacle_distance", C.c_double),
+        ("max_observation_points", C.c_uint32), ("max_markings", C.c_uint32), ("max_cluster_points", C.c_uint32),
+        ("reserved2", C.c_uint32),
+    ]
+
+
+class DepthLayerStats(C.Structure):
+    _fields_ = [
+        ("n_observation", C.c_uint32), ("n_in_window", C.c_uint32), ("n_cleared", C.c_uint32), ("n_clusters", C.c_uint32),
+        ("n_accepted", C.c_uint32), ("n_contested", C.c_uint32), ("n_alive", C.c_uint32), ("gc_runs", C.c_uint32),
+        ("launches", C.c_uint32), ("host_waits", C.c_uint32),
+    ]
+
+
 # dddmr_rollout_depth_clear_verdicts: bit 0 of a verdict = kept, bits 1-2 = the branch that decided
 DEPTH_CLEAR_KEPT = 1
 DEPTH_CLEAR_OUTSIDE, DEPTH_CLEAR_ATTACHED, DEPTH_CLEAR_INSIDE = 1, 2, 3
@@ -278,6 +301,13 @@ EXPORTED_SYMBOLS = (
     "dddmr_rollout_depth_clear_launches",
     "dddmr_rollout_depth_mark_create",
     "dddmr_rollout_depth_mark_clusters",
+    "dddmr_rollout_depth_layer_create",
+    "dddmr_rollout_depth_layer_update",
+    "dddmr_rollout_depth_layer_reset",
+    "dddmr_rollout_depth_layer_get_voxels",
+    "dddmr_rollout_depth_layer_get_clusters",
+    "dddmr_rollout_depth_layer_get_dgraph",
+    "dddmr_rollout_depth_layer_get_lethal",
     "dddmr_rollout_stream_ceiling",
     "dddmr_rollout_selftest_sincos",
     "dddmr_rollout_last_error",
@@ -419,6 +449,22 @@ def load_library() -> C.CDLL:
     lib.dddmr_rollout_depth_mark_clusters.argtypes = [ctx_p, C.POINTER(C.c_double), C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DepthMarkStats)]
     lib.dddmr_rollout_depth_mark_clusters.restype = C.c_int
+    lib.dddmr_rollout_depth_layer_create.argtypes = [ctx_p, C.POINTER(DepthLayerConfig), C.c_void_p, C.c_size_t, C.c_size_t,
+                                                     C.c_void_p, C.c_size_t, C.c_size_t]
+    lib.dddmr_rollout_depth_layer_create.restype = C.c_int
+    lib.dddmr_rollout_depth_layer_update.argtypes = [ctx_p, C.POINTER(C.c_double), C.POINTER(DepthLayerStats)]
+    lib.dddmr_rollout_depth_layer_update.restype = C.c_int
+    lib.dddmr_rollout_depth_layer_reset.argtypes = [ctx_p]
+    lib.dddmr_rollout_depth_layer_reset.restype = C.c_int
+    lib.dddmr_rollout_depth_layer_get_voxels.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.dddmr_rollout_depth_layer_get_voxels.restype = C.c_int
+    lib.dddmr_rollout_depth_layer_get_clusters.argtypes = [ctx_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                           C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    lib.dddmr_rollout_depth_layer_get_clusters.restype = C.c_int
+    lib.dddmr_rollout_depth_layer_get_dgraph.argtypes = [ctx_p, C.c_void_p, C.c_size_t]
+    lib.dddmr_rollout_depth_layer_get_dgraph.restype = C.c_int
+    lib.dddmr_rollout_depth_layer_get_lethal.argtypes = [ctx_p, C.c_void_p, C.c_size_t]
+    lib.dddmr_rollout_depth_layer_get_lethal.restype = C.c_int
     lib.dddmr_rollout_stream_ceiling.argtypes = [ctx_p, C.c_size_t, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.dddmr_rollout_stream_ceiling.restype = C.c_int
     lib.dddmr_rollout_selftest_sincos.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]

@@ -264,20 +264,19 @@ struct DcVerdictParams {
   uint32_t observation_clear;   // the observation has <= 5 points (depth_camera_layer.cpp:258-264): no search is made
 };
 
-// One wave per marking.  voxel / offsets / cluster are host-mapped (each is read once), out is host-mapped:
-// out[i].x = verdict (bit 0 kept, bits 1-2 branch: 1 outside the frustums, 2 attached, 3 inside; kDcEmptyCluster),
-// out[i].y = engagement count where the branch computes one.
-__global__ __launch_bounds__(256) void k_dc_verdicts(DcVerdictParams k, DcFrustums S, const PointGrid* __restrict__ hdr,
-                                                     const int32_t* __restrict__ voxel, const uint32_t* __restrict__ offsets,
-                                                     const float* __restrict__ cluster, uint2* __restrict__ out) {
-  const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= k.m) return;                                  // wave-uniform
-  const int lane = threadIdx.x & 63;
+// selfClear's decision tree for one marking by one wave (:324-422), shared by k_dc_verdicts (markings shipped by the host)
+// and k_dl_verdicts (markings in the device store, depth_layer.hip.h).  vx / vy / vz: the marking's voxel key; n_pts and
+// point(j) -> float3: its stored cluster pc_.  Every argument but `lane` is wave-uniform, and so is the result:
+// .x = verdict (bit 0 kept, bits 1-2 branch: 1 outside the frustums, 2 attached, 3 inside; kDcEmptyCluster),
+// .y = engagement count where the branch computes one.
+template <class P>
+__device__ __forceinline__ uint2 dc_marking_verdict(double res, double hres, bool clear, const DcFrustums& S,
+                                                    const PointGrid* __restrict__ hdr, int vx, int vy, int vz, uint32_t n_pts,
+                                                    int lane, P&& point) {
   // pt.x = (*it_x).first * resolution_ (:325-327): int times double, rounded to the float of pcl::PointXYZI
-  const float px = (float)(voxel[3 * (size_t)i + 0] * k.res);
-  const float py = (float)(voxel[3 * (size_t)i + 1] * k.res);
-  const float pz = (float)(voxel[3 * (size_t)i + 2] * k.hres);
-  const bool clear = k.observation_clear != 0;
+  const float px = (float)(vx * res);
+  const float py = (float)(vy * res);
+  const float pz = (float)(vz * hres);
   uint32_t verdict = 0, engaged = 0;
   if (!dc_in_frustums(S, px, py, pz)) {
     // :333-351 (taken when the voxel is in NO frustum, whatever the comment above it says)
@@ -292,27 +291,43 @@ __global__ __launch_bounds__(256) void k_dc_verdicts(DcVerdictParams k, DcFrustu
     const uint32_t branch = dc_attach(S, px, py, pz) ? 2u : 3u;
     verdict = branch << 1;
     if (!clear) {
-      const uint32_t b = offsets[i], e = offsets[i + 1];
-      if (e == b) {
+      if (n_pts == 0) {
         verdict |= kDcEmptyCluster;
       } else {
         const PointGrid g = *hdr;
         const float r2 = static_cast<float>(0.01 * 0.01);
-        for (uint32_t j0 = b; j0 < e; j0 += 64) {          // wave-uniform bounds
+        for (uint32_t j0 = 0; j0 < n_pts; j0 += 64) {          // wave-uniform bounds
           const uint32_t j = j0 + (uint32_t)lane;
           bool hit = false;
-          if (j < e) {
-            const float qx = cluster[3 * (size_t)j + 0], qy = cluster[3 * (size_t)j + 1], qz = cluster[3 * (size_t)j + 2];
-            hit = grid_radius_count(g, qx, qy, qz, 0.01f + kDcPad, r2, 1) > 0;
+          if (j < n_pts) {
+            const float3 q = point(j);
+            hit = grid_radius_count(g, q.x, q.y, q.z, 0.01f + kDcPad, r2, 1) > 0;
           }
           engaged += (uint32_t)__popcll(__ballot(hit));
         }
         // 1.0 * engage_count / pc_->points.size() > 0.1 (:374, :406)
-        if (1.0 * (double)engaged / (double)(e - b) > 0.1) verdict |= 1u;
+        if (1.0 * (double)engaged / (double)n_pts > 0.1) verdict |= 1u;
       }
     }
   }
-  if (lane == 0) out[i] = make_uint2(verdict, engaged);
+  return make_uint2(verdict, engaged);
+}
+
+// One wave per marking.  voxel / offsets / cluster are host-mapped (each is read once), out is host-mapped:
+// out[i] = dc_marking_verdict's result.
+__global__ __launch_bounds__(256) void k_dc_verdicts(DcVerdictParams k, DcFrustums S, const PointGrid* __restrict__ hdr,
+                                                     const int32_t* __restrict__ voxel, const uint32_t* __restrict__ offsets,
+                                                     const float* __restrict__ cluster, uint2* __restrict__ out) {
+  const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= k.m) return;                                  // wave-uniform
+  const int lane = threadIdx.x & 63;
+  const uint32_t b = offsets[i], e = offsets[i + 1];
+  const uint2 v = dc_marking_verdict(k.res, k.hres, k.observation_clear != 0, S, hdr, voxel[3 * (size_t)i + 0],
+                                     voxel[3 * (size_t)i + 1], voxel[3 * (size_t)i + 2], e - b, lane, [&](uint32_t j) {
+                                       const size_t r = 3 * ((size_t)b + j);
+                                       return make_float3(cluster[r + 0], cluster[r + 1], cluster[r + 2]);
+                                     });
+  if (lane == 0) out[i] = v;
 }
 
 // ---- host: scratch ------------------------------------------------------------------------------------------------

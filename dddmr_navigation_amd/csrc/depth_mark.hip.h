@@ -249,6 +249,64 @@ int depth_mark_init(dddmr_rollout_ctx* ctx, DepthMarkState* s, const float* grou
   return DDDMR_OK;
 }
 
+// The enqueue part of one selfMark, shared by depth_mark_clusters and the depth layer's update (depth_layer.hip.h): from
+// the Euclidean clusters to k_dm_stage2 on `st`, over the n points of the observation grid `d` holds.  Afterwards
+// s->counters->n_clusters, s->cl (start, size, centroid, ds_count, vkey), s->fate, s->ds, s->ds_first and s->n_groups are what
+// the launch sequence at the top of this file leaves.  *ops grows by the kernels enqueued (rocPRIM's are the caller's to add).
+#define DM_LAUNCH(...) do { hipLaunchKernelGGL(__VA_ARGS__); ++*ops; } while (0)
+int depth_mark_enqueue(dddmr_rollout_ctx* ctx, DepthMarkState* s, const double T_gbl_base[7], DepthClear& d, uint32_t n,
+                       const DcFrustums& S, hipStream_t st, uint32_t* ops) {
+  DmParams k;
+  k.res = s->cfg.xy_resolution;
+  k.hres = s->cfg.height_resolution;
+  k.ignore_ratio = s->cfg.segmentation_ignore_ratio;
+  k.tol = (float)s->cfg.euclidean_cluster_extraction_tolerance;
+  k.tol2 = static_cast<float>(s->cfg.euclidean_cluster_extraction_tolerance * s->cfg.euclidean_cluster_extraction_tolerance);
+  k.min_cluster = s->cfg.euclidean_cluster_extraction_min_cluster_size;
+  k.n_obs = n;
+  k.n_map = s->n_map;
+  MarkParams mk{};                        // what the general route's kernels read of it
+  mk.n_obs = n;
+  const float4* pts = d.pts;
+  const dim3 pb((n + 255) / 256), cb((n + 63) / 64);
+  HIPCHK(ctx, hipMemsetAsync(s->counters, 0, sizeof(MarkCounters), st));
+  // Euclidean clusters
+  DM_LAUNCH(k_mk_cc_init, pb, dim3(256), 0, st, n, s->parent);
+  DM_LAUNCH(k_dm_cc_union, pb, dim3(256), 0, st, k, d.hdr, pts, s->parent);
+  DM_LAUNCH(k_mk_cc_keys, pb, dim3(256), 0, st, n, s->parent, s->keys_a);
+  size_t tb = s->temp_bytes;
+  HIPCHK(ctx, rocprim::radix_sort_keys(s->temp, tb, s->keys_a, s->keys1, (size_t)n, 0, 40, st));
+  DM_LAUNCH(k_mk_flags, pb, dim3(256), 0, st, n, s->keys1, 20, s->flags);
+  tb = s->temp_bytes;
+  HIPCHK(ctx, rocprim::inclusive_scan(s->temp, tb, s->flags, s->cid_incl, (size_t)n, rocprim::plus<uint32_t>(), st));
+  DM_LAUNCH(k_mk_cluster_starts, pb, dim3(256), 0, st, n, s->flags, s->cid_incl, s->cl, s->counters);
+  DM_LAUNCH(k_dm_stage1, cb, dim3(64), 0, st, k, s->counters, s->cl, s->keys1, pts, s->ground.g, s->fate);
+  // 0.2 m VoxelGrid of every cluster that is still in: stable sort by (cluster, voxel), one lane per voxel.  The voxel
+  // indices are keyed relative to the robot's voxel - half the key range (+-6.5 km in x / y, +-102 m in z).
+  const int ox = (int)std::floor((float)T_gbl_base[0] / 0.2f) - kVgHalfXY, oy = (int)std::floor((float)T_gbl_base[1] / 0.2f) - kVgHalfXY,
+            oz = (int)std::floor((float)T_gbl_base[2] / 0.2f) - kVgHalfZ;
+  DM_LAUNCH(k_mk_ds_keys, pb, dim3(256), 0, st, mk, s->keys1, s->cid_incl, s->cl, pts, ox, oy, oz, s->keys_a, s->vals_a, s->counters);
+  tb = s->temp_bytes;
+  HIPCHK(ctx, rocprim::radix_sort_pairs(s->temp, tb, s->keys_a, s->keys_b, s->vals_a, s->vals_b, (size_t)n, 0, 62, st));
+  DM_LAUNCH(k_mk_flags, pb, dim3(256), 0, st, n, s->keys_b, 0, s->flags);
+  tb = s->temp_bytes;
+  HIPCHK(ctx, rocprim::inclusive_scan(s->temp, tb, s->flags, s->incl, (size_t)n, rocprim::plus<uint32_t>(), st));
+  HIPCHK(ctx, hipMemsetAsync(s->ds_first, 0xFF, (size_t)n * sizeof(uint32_t), st));
+  DM_LAUNCH(k_mk_group_reduce, cb, dim3(64), 0, st, n, s->keys_b, s->vals_b, s->flags, s->incl, 0, s->keys1, pts, s->ds,
+            s->cl.ds_count, s->ds_first, s->n_groups);
+  DM_LAUNCH(k_dm_stage2, cb, dim3(64), 0, st, k, S, s->counters, s->cl, s->map.g, s->fate);
+  return DDDMR_OK;
+}
+#undef DM_LAUNCH
+
+// What extractEuclideanClusters hands to the sort is the clusters of at least min_cluster_size points in creation order;
+// this is the reference's std::sort(clusters.rbegin(), clusters.rend(), comparePointClusters) over them, sizes only
+// (oracle/ASSUMPTIONS.md row 10): the order addPCPtr is called in.
+struct DmItem { uint32_t size, ci; };
+void dm_replay_sort(std::vector<DmItem>& order) {
+  std::sort(order.rbegin(), order.rend(), [](const DmItem& a, const DmItem& b) { return a.size < b.size; });
+}
+
 }  // namespace
 
 extern "C" {
@@ -340,46 +398,9 @@ int dddmr_rollout_depth_mark_clusters(dddmr_rollout_ctx* ctx, const double T_gbl
   if (dc_reserve(&s->out_host, &s->out_dev, &s->out_cap, pts_at + (size_t)n * 12) != 0)
     return fail(ctx, DDDMR_ERR_HIP, "depth_mark_clusters: staging for %u observation points", n);
 
-  DmParams k;
-  k.res = s->cfg.xy_resolution;
-  k.hres = s->cfg.height_resolution;
-  k.ignore_ratio = s->cfg.segmentation_ignore_ratio;
-  k.tol = (float)s->cfg.euclidean_cluster_extraction_tolerance;
-  k.tol2 = static_cast<float>(s->cfg.euclidean_cluster_extraction_tolerance * s->cfg.euclidean_cluster_extraction_tolerance);
-  k.min_cluster = s->cfg.euclidean_cluster_extraction_min_cluster_size;
-  k.n_obs = n;
-  k.n_map = s->n_map;
-  MarkParams mk{};                        // what the general route's kernels read of it
-  mk.n_obs = n;
-  const float4* pts = d.pts;
-  const dim3 pb((n + 255) / 256), cb((n + 63) / 64);
+  if ((rc = depth_mark_enqueue(ctx, s, T_gbl_base, d, n, S, st, &ops)) != DDDMR_OK) return rc;
+  const dim3 pb((n + 255) / 256);
 #define DM_LAUNCH(...) do { hipLaunchKernelGGL(__VA_ARGS__); ++ops; } while (0)
-  HIPCHK(ctx, hipMemsetAsync(s->counters, 0, sizeof(MarkCounters), st));
-  // Euclidean clusters
-  DM_LAUNCH(k_mk_cc_init, pb, dim3(256), 0, st, n, s->parent);
-  DM_LAUNCH(k_dm_cc_union, pb, dim3(256), 0, st, k, d.hdr, pts, s->parent);
-  DM_LAUNCH(k_mk_cc_keys, pb, dim3(256), 0, st, n, s->parent, s->keys_a);
-  size_t tb = s->temp_bytes;
-  HIPCHK(ctx, rocprim::radix_sort_keys(s->temp, tb, s->keys_a, s->keys1, (size_t)n, 0, 40, st));
-  DM_LAUNCH(k_mk_flags, pb, dim3(256), 0, st, n, s->keys1, 20, s->flags);
-  tb = s->temp_bytes;
-  HIPCHK(ctx, rocprim::inclusive_scan(s->temp, tb, s->flags, s->cid_incl, (size_t)n, rocprim::plus<uint32_t>(), st));
-  DM_LAUNCH(k_mk_cluster_starts, pb, dim3(256), 0, st, n, s->flags, s->cid_incl, s->cl, s->counters);
-  DM_LAUNCH(k_dm_stage1, cb, dim3(64), 0, st, k, s->counters, s->cl, s->keys1, pts, s->ground.g, s->fate);
-  // 0.2 m VoxelGrid of every cluster that is still in: stable sort by (cluster, voxel), one lane per voxel.  The voxel
-  // indices are keyed relative to the robot's voxel - half the key range (+-6.5 km in x / y, +-102 m in z).
-  const int ox = (int)std::floor((float)T_gbl_base[0] / 0.2f) - kVgHalfXY, oy = (int)std::floor((float)T_gbl_base[1] / 0.2f) - kVgHalfXY,
-            oz = (int)std::floor((float)T_gbl_base[2] / 0.2f) - kVgHalfZ;
-  DM_LAUNCH(k_mk_ds_keys, pb, dim3(256), 0, st, mk, s->keys1, s->cid_incl, s->cl, pts, ox, oy, oz, s->keys_a, s->vals_a, s->counters);
-  tb = s->temp_bytes;
-  HIPCHK(ctx, rocprim::radix_sort_pairs(s->temp, tb, s->keys_a, s->keys_b, s->vals_a, s->vals_b, (size_t)n, 0, 62, st));
-  DM_LAUNCH(k_mk_flags, pb, dim3(256), 0, st, n, s->keys_b, 0, s->flags);
-  tb = s->temp_bytes;
-  HIPCHK(ctx, rocprim::inclusive_scan(s->temp, tb, s->flags, s->incl, (size_t)n, rocprim::plus<uint32_t>(), st));
-  HIPCHK(ctx, hipMemsetAsync(s->ds_first, 0xFF, (size_t)n * sizeof(uint32_t), st));
-  DM_LAUNCH(k_mk_group_reduce, cb, dim3(64), 0, st, n, s->keys_b, s->vals_b, s->flags, s->incl, 0, s->keys1, pts, s->ds,
-            s->cl.ds_count, s->ds_first, s->n_groups);
-  DM_LAUNCH(k_dm_stage2, cb, dim3(64), 0, st, k, S, s->counters, s->cl, s->map.g, s->fate);
   char* dev = static_cast<char*>(s->out_dev);
   DM_LAUNCH(k_dm_pack, pb, dim3(256), 0, st, n, s->counters, s->n_groups, s->cl, s->fate, s->ds_first, s->ds,
             reinterpret_cast<DmHeader*>(dev), reinterpret_cast<DmRecord*>(dev + rec_at), reinterpret_cast<float*>(dev + pts_at));
@@ -399,8 +420,7 @@ int dddmr_rollout_depth_mark_clusters(dddmr_rollout_ctx* ctx, const double T_gbl
   }
   // what extractEuclideanClusters hands to the sort: the clusters of at least min_cluster_size points, in creation
   // order; then the reference's std::sort(clusters.rbegin(), clusters.rend(), comparePointClusters), sizes only
-  struct Item { uint32_t size, ci; };
-  std::vector<Item> order;
+  std::vector<DmItem> order;
   order.reserve(hd.n_clusters);
   for (uint32_t ci = 0; ci < hd.n_clusters; ++ci) {
     switch (rec[ci].fate) {
@@ -410,7 +430,7 @@ int dddmr_rollout_depth_mark_clusters(dddmr_rollout_ctx* ctx, const double T_gbl
       case kDmOutside: ++out.n_outside_frustums; break;
       default: ++out.n_accepted; out.n_points += rec[ci].ds_count; break;
     }
-    order.push_back(Item{rec[ci].size, ci});
+    order.push_back(DmItem{rec[ci].size, ci});
   }
   out.n_clusters = (uint32_t)order.size();
   *stats = out;
@@ -418,10 +438,10 @@ int dddmr_rollout_depth_mark_clusters(dddmr_rollout_ctx* ctx, const double T_gbl
   if (out.n_accepted > capacity_clusters || out.n_points > capacity_points)
     return fail(ctx, DDDMR_ERR_CAPACITY, "depth_mark_clusters: %u clusters / %u points, capacity %zu / %zu", out.n_accepted, out.n_points,
                 capacity_clusters, capacity_points);
-  std::sort(order.rbegin(), order.rend(), [](const Item& a, const Item& b) { return a.size < b.size; });
+  dm_replay_sort(order);
   size_t c = 0, p = 0;
   offsets_out[0] = 0;
-  for (const Item& it : order) {
+  for (const DmItem& it : order) {
     const DmRecord& r = rec[it.ci];
     if (r.fate != kDmAccepted) continue;
     centroid_out[3 * c + 0] = r.cx; centroid_out[3 * c + 1] = r.cy; centroid_out[3 * c + 2] = r.cz;

@@ -158,6 +158,8 @@ struct MarkingState;                       // global-mode marking / clearing lay
 void marking_free(MarkingState* m);
 struct DepthMarkState;                     // the depth camera's selfMark, depth_mark.hip.h
 void depth_mark_free(DepthMarkState* s);
+struct DepthLayerState;                    // the depth camera layer's store, dGraph and lethal set, depth_layer.hip.h
+void depth_layer_free(DepthLayerState* s);
 
 }  // namespace
 
@@ -260,6 +262,7 @@ struct dddmr_rollout_ctx {
 
   MarkingState* marking = nullptr;   // dddmr_rollout_marking_create
   DepthMarkState* dmark = nullptr;   // dddmr_rollout_depth_mark_create
+  DepthLayerState* dlayer = nullptr; // dddmr_rollout_depth_layer_create
 
   std::mutex tick_mu;
   std::mutex err_mu;        // last_error is written by tick and sensor threads alike
@@ -506,6 +509,7 @@ void dddmr_rollout_destroy(dddmr_rollout_ctx* ctx) {
   if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
   if (ctx->marking) { marking_free(ctx->marking); ctx->marking = nullptr; }
   if (ctx->dmark) { depth_mark_free(ctx->dmark); ctx->dmark = nullptr; }
+  if (ctx->dlayer) { depth_layer_free(ctx->dlayer); ctx->dlayer = nullptr; }
   if (ctx->comm) (void)rccl().comm_destroy(ctx->comm);
   if (ctx->slots_dev) (void)hipFree(ctx->slots_dev);
   if (ctx->slots_red) (void)hipFree(ctx->slots_red);
@@ -2346,3 +2350,4 @@ int dddmr_rollout_get_best_cuboids(dddmr_rollout_ctx* ctx, float* vertices_out, 
 
 #include "marking_host.hip.h"
 #include "depth_mark.hip.h"
+#include "depth_layer.hip.h"

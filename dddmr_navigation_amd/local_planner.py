@@ -300,6 +300,56 @@ class LocalPlanner:
                                                                 off.ctypes.data, pts.ctypes.data, plane.ctypes.data, C.byref(st)))
         return cen[:c], vox[:c], size[:c], off, pts[:p], plane, st
 
+    def depth_layer_create(self, cfg: "K.DepthLayerConfig", ground_xyz: np.ndarray, map_xyz: np.ndarray):
+        """The depth camera layer's device state (store, dGraph, lethal set): pcl_ground_ / pcl_map_ ([N, >=3] float32, the
+        map may be empty) go to the device once.  See dddmr_navigation_amd.depth_layer.DepthLayer."""
+        ground = np.ascontiguousarray(ground_xyz, dtype=np.float32)
+        smap = np.ascontiguousarray(map_xyz, dtype=np.float32)
+        for a in (ground, smap):
+            if a.ndim != 2 or (a.shape[0] and a.shape[1] < 3):
+                raise ValueError("ground / map must be [N, >=3] float32")
+        self._check(self._lib.dddmr_rollout_depth_layer_create(
+            self._ctx, C.byref(cfg), ground.ctypes.data if ground.shape[0] else None, ground.shape[0],
+            ground.strides[0] if ground.shape[0] else 12, smap.ctypes.data if smap.shape[0] else None, smap.shape[0],
+            smap.strides[0] if smap.shape[0] else 12))
+
+    def depth_layer_update(self, T_gbl_base) -> "K.DepthLayerStats":
+        """One selfClear + selfMark pass of the depth camera layer on the depth sources' current observation."""
+        tgb = (C.c_double * 7)(*[float(v) for v in T_gbl_base])
+        st = K.DepthLayerStats()
+        self._check(self._lib.dddmr_rollout_depth_layer_update(self._ctx, tgb, C.byref(st)))
+        return st
+
+    def depth_layer_reset(self):
+        self._check(self._lib.dddmr_rollout_depth_layer_reset(self._ctx))
+
+    def depth_layer_voxels(self) -> np.ndarray:
+        n = C.c_size_t(0)
+        self._check(self._lib.dddmr_rollout_depth_layer_get_voxels(self._ctx, None, 0, C.byref(n)))
+        out = np.zeros((max(n.value, 1), 3), dtype=np.int32)
+        self._check(self._lib.dddmr_rollout_depth_layer_get_voxels(self._ctx, out.ctypes.data, out.shape[0], C.byref(n)))
+        return out[: n.value]
+
+    def depth_layer_clusters(self):
+        """The alive markings with their stored pc_ -> (voxels [M,3] int32, offsets [M+1] uint32, points [P,3] float32)."""
+        m, p = C.c_size_t(0), C.c_size_t(0)
+        self._check(self._lib.dddmr_rollout_depth_layer_get_clusters(self._ctx, None, None, None, 0, 0, C.byref(m), C.byref(p)))
+        vox, off = np.zeros((max(m.value, 1), 3), np.int32), np.zeros(m.value + 1, np.uint32)
+        pts = np.zeros((max(p.value, 1), 3), np.float32)
+        self._check(self._lib.dddmr_rollout_depth_layer_get_clusters(self._ctx, vox.ctypes.data, off.ctypes.data, pts.ctypes.data,
+                                                                     m.value, p.value, C.byref(m), C.byref(p)))
+        return vox[: m.value], off, pts[: p.value]
+
+    def depth_layer_dgraph(self, n_ground: int) -> np.ndarray:
+        out = np.zeros(int(n_ground) + 1, dtype=np.float64)
+        self._check(self._lib.dddmr_rollout_depth_layer_get_dgraph(self._ctx, out.ctypes.data, out.size))
+        return out
+
+    def depth_layer_lethal(self, n_ground: int) -> np.ndarray:
+        out = np.zeros(int(n_ground) + 1, dtype=np.uint8)
+        self._check(self._lib.dddmr_rollout_depth_layer_get_lethal(self._ctx, out.ctypes.data, out.size))
+        return out.astype(bool)
+
     def set_stitcher(self, stitcher_num: int):
         """cbSensor's `stitcher_num` (multilayer_spinning_lidar.cpp:185-200): feed the last N raw scans together."""
         self._check(self._lib.dddmr_rollout_set_stitcher(self._ctx, int(stitcher_num)))

@@ -486,6 +486,103 @@ int dddmr_rollout_depth_mark_clusters(dddmr_rollout_ctx* ctx, const double T_gbl
                                       uint32_t* size_out /* [c] */, uint32_t* offsets_out /* [c + 1] */,
                                       float* cluster_xyz_out /* [p][3] */, float plane_out[4], dddmr_depth_mark_stats* stats);
 
+/* Depth camera layer on the device: marking store, dGraph and lethal set (additions to ABI version 2; no existing
+   struct or entry changes).  One dddmr_rollout_depth_layer_update is one selfClear + selfMark + updateLethalPointCloud
+   pass of the global-mode DepthCameraLayer (stacked_perception.cpp:82-88) with pct_marking_, its dGraph and lethal_map_
+   kept in device memory between calls: only parameters go in and counters come out.
+
+   dddmr_rollout_depth_layer_create takes the inputs of dddmr_rollout_depth_mark_create plus the layer's window, radii and
+   capacities.  It is independent of depth_mark_create and of marking_create: a context may have any of them (the
+   documented limit stays: no depth sources in a context that feeds a lidar marking layer).  DDDMR_ERR_BAD_ARG: a
+   resolution, the tolerance, the inflation radius, the window or the marking height is not positive and finite, a
+   negative minimum cluster size, a capacity of 0, a bad pointer / stride; DDDMR_ERR_CAPACITY: max_observation_points
+   above 2^20 or max_markings above 2^24; DDDMR_ERR_STATE: a dddmr_rollout_tick_begin is pending.  A refused call leaves
+   the earlier state in place; a successful one replaces it (empty store, dGraph = max_obstacle_distance).
+
+   dddmr_rollout_depth_layer_update runs on the feeds' stream, serialised with the feeds, and may be made between
+   dddmr_rollout_tick_begin and _tick_end with the serial answer.  DDDMR_ERR_STATE before depth_layer_create, without a
+   depth source or while a depth source has no frustum (the isFirstScanReady returns of depth_camera_layer.cpp:266-269 /
+   :482-485; the other early returns stay with the caller).  More than max_observation_points: DDDMR_ERR_CAPACITY,
+   nothing changed.
+     selfClear (:252-426) against the CURRENT aggregated depth observation (the one depth_clear_verdicts searches, its
+       grid rebuilt at most once per published frame; the lidar layer uses the previous one).  The window is in voxel
+       keys, half open because of lower_bound: x, y in [(int)((t -+ perception_window_size) / xy_resolution)), z in
+       [(int)((t.z -+ marking_height) / height_resolution)), double division, truncated.  Only alive markings
+       (pc_ != nullptr) are looked at.  The verdict per marking is exactly dddmr_rollout_depth_clear_verdicts' (an
+       observation of <= 5 points clears everything in the window); it reads the voxel key and the stored pc_ from the
+       device store.
+     removePCPtr (cluster_marking.cpp:125-138) for every marking not kept: every node of its nodes_of_min_distance_ gets
+       clearValue(node, 9999.0), whether or not another alive marking covers the node, and leaves the lethal set where
+       this marking's stored distance is <= inscribed_radius.  nodes_of_min_distance_ is recomputed from the marking's
+       stored generator points.
+     selfMark (:487-601): the pipeline of dddmr_rollout_depth_mark_clusters (with <= 5 observation points nothing is
+       marked although selfClear ran).  Every accepted cluster then goes through addPCPtr (:100-123): the voxel slot
+       (int)(c / resolution) is created or found; its pc_ (the 0.2 m cloud) and generator points are replaced by this
+       cluster's, without a clearValue of the old ones; generator points = ProjectInliers on the plane of :568-578
+       (float, Eigen's reduction order (a0 + a2) + (a1 + a3), the normal normalised) then the 0.1 m VoxelGrid; for
+       every ground node within inflation_radius of one (FLANN float distance, strict <): setValue(node,
+       sqrtf(dx^2 + dy^2)) as a minimum in double, lethal where <= inscribed_radius.  EVERY accepted cluster
+       contributes to the dGraph and the lethal set, the losers of a contested voxel included.  A contested voxel keeps
+       the cluster the reference processes last: std::sort(rbegin, rend) by size (oracle/ASSUMPTIONS.md row 10) -- a
+       device priority (smaller size, then higher index) and, only in updates that have a contested voxel, the host's
+       replay of that very sort (the code depth_mark_clusters orders its outputs with).
+     updateLethalPointCloud is dddmr_rollout_depth_layer_get_lethal: ground points whose flag is set.
+   Housekeeping as in the lidar layer: a cleared voxel keeps its key until half the table holds keys (then the alive
+   markings move to a fresh table); overwritten pc_ / generator ranges are pool garbage until the pool is half used
+   (then it is compacted).  DDDMR_ERR_CAPACITY from an update: the store (max_markings) or the pool (max_cluster_points)
+   overflowed, or a cluster point lies beyond the VoxelGrid key range around the robot.  The update has then run to its
+   end: selfClear is complete, every accepted cluster has contributed to the dGraph and the lethal set, but a cluster
+   that found no slot or no pool space is not stored, so a later selfClear cannot take its contribution back; its voxel
+   is not alive afterwards, ALSO where a marking stored by an earlier update was alive on that voxel: that marking is
+   gone without a clearValue.  dddmr_rollout_depth_layer_reset recovers a usable, empty layer.
+   An update makes ONE host wait, a second one only when two accepted clusters contest a voxel (stats.host_waits).
+
+   The getters take the same lock and order themselves after the update's stream.  get_voxels: the alive markings' voxel
+   keys (xyz_out NULL: count only).  get_clusters: the alive markings with their stored pc_, voxel_out[i] and
+   xyz_out[offsets_out[i] .. offsets_out[i + 1]); all outputs NULL: counts only; too small a capacity:
+   DDDMR_ERR_CAPACITY with the counts filled.  Order: by store slot.  get_dgraph: n_ground + 1 doubles; get_lethal: one
+   byte per ground node (n_ground + 1, the last unused). */
+typedef struct {
+  double xy_resolution, height_resolution;
+  double marking_height, perception_window_size;
+  double euclidean_cluster_extraction_tolerance;           /* plugin default 0.1 */
+  int32_t euclidean_cluster_extraction_min_cluster_size;   /* plugin default 1 */
+  int32_t reserved;
+  double segmentation_ignore_ratio;
+  double inscribed_radius, inflation_radius, max_obstacle_distance;
+  uint32_t max_observation_points;                          /* depth observation the scratch is sized for */
+  uint32_t max_markings;                                    /* voxels of the store */
+  uint32_t max_cluster_points;                              /* pool: stored pc_ + generator points */
+  uint32_t reserved2;
+} dddmr_depth_layer_config;
+
+typedef struct {
+  uint32_t n_observation;       /* points of the depth observation */
+  uint32_t n_in_window;         /* alive markings selfClear looked at */
+  uint32_t n_cleared;           /* of them removed */
+  uint32_t n_clusters;          /* clusters extractEuclideanClusters returns (min size applied) */
+  uint32_t n_accepted;          /* addPCPtr calls */
+  uint32_t n_contested;         /* of them on a voxel another cluster of this update had already claimed */
+  uint32_t n_alive;             /* alive markings after the update */
+  uint32_t gc_runs;             /* store rehash / pool compaction done by this update */
+  uint32_t launches;            /* device operations the update enqueued; approximate: the library's own launches are
+                                   counted, rocPRIM's sorts and scans are entered with an estimate */
+  uint32_t host_waits;
+} dddmr_depth_layer_stats;
+
+int dddmr_rollout_depth_layer_create(dddmr_rollout_ctx* ctx, const dddmr_depth_layer_config* cfg, const float* ground_xyz,
+                                     size_t n_ground, size_t ground_stride_bytes, const float* map_xyz, size_t n_map,
+                                     size_t map_stride_bytes);
+int dddmr_rollout_depth_layer_update(dddmr_rollout_ctx* ctx, const double T_gbl_base[7], dddmr_depth_layer_stats* stats);
+/* resetdGraph: empty store, dGraph = max_obstacle_distance */
+int dddmr_rollout_depth_layer_reset(dddmr_rollout_ctx* ctx);
+int dddmr_rollout_depth_layer_get_voxels(dddmr_rollout_ctx* ctx, int32_t* xyz_out /* [capacity][3] */, size_t capacity, size_t* n);
+int dddmr_rollout_depth_layer_get_clusters(dddmr_rollout_ctx* ctx, int32_t* voxel_out /* [m][3] */, uint32_t* offsets_out /* [m + 1] */,
+                                           float* xyz_out /* [p][3] */, size_t cap_markings, size_t cap_points,
+                                           size_t* n_markings, size_t* n_points);
+int dddmr_rollout_depth_layer_get_dgraph(dddmr_rollout_ctx* ctx, double* values_out, size_t capacity);
+int dddmr_rollout_depth_layer_get_lethal(dddmr_rollout_ctx* ctx, uint8_t* flags_out, size_t capacity);
+
 /* Copy the current aggregate observation back (debug / parity of set_scan). */
 int dddmr_rollout_get_cloud(dddmr_rollout_ctx* ctx, float* xyzi_out, size_t capacity,
                             size_t* n_points);

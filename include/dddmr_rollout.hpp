@@ -177,6 +177,39 @@ class LocalPlanner {
     out.cluster_xyz.resize(3 * p);
     return DDDMR_OK;
   }
+  // the depth camera layer on the device (store, dGraph, lethal set): the library's codes are returned, not thrown, so
+  // that a caller can fall back to its CPU pass
+  int depthLayerCreate(const dddmr_depth_layer_config& cfg, const float* ground_xyz, size_t n_ground, size_t ground_stride_bytes,
+                       const float* map_xyz, size_t n_map, size_t map_stride_bytes) {
+    return dddmr_rollout_depth_layer_create(ctx_, &cfg, ground_xyz, n_ground, ground_stride_bytes, map_xyz, n_map, map_stride_bytes);
+  }
+  int depthLayerUpdate(const double T_gbl_base[7], dddmr_depth_layer_stats& stats) {
+    stats = dddmr_depth_layer_stats{};
+    return dddmr_rollout_depth_layer_update(ctx_, T_gbl_base, &stats);
+  }
+  int depthLayerReset() { return dddmr_rollout_depth_layer_reset(ctx_); }
+  int depthLayerDGraph(std::vector<double>& values, size_t n_ground) {
+    values.assign(n_ground + 1, 0.0);
+    return dddmr_rollout_depth_layer_get_dgraph(ctx_, values.data(), values.size());
+  }
+  int depthLayerLethal(std::vector<uint8_t>& flags, size_t n_ground) {
+    flags.assign(n_ground + 1, 0);
+    return dddmr_rollout_depth_layer_get_lethal(ctx_, flags.data(), flags.size());
+  }
+  // the alive markings with their stored pc_: voxel [m][3], offsets [m + 1], xyz [p][3]
+  int depthLayerClusters(std::vector<int32_t>& voxel, std::vector<uint32_t>& offsets, std::vector<float>& xyz) {
+    size_t m = 0, p = 0;
+    int rc = dddmr_rollout_depth_layer_get_clusters(ctx_, nullptr, nullptr, nullptr, 0, 0, &m, &p);
+    if (rc != DDDMR_OK) return rc;
+    voxel.assign(3 * m + 3, 0);
+    offsets.assign(m + 1, 0u);
+    xyz.assign(3 * p + 3, 0.f);
+    rc = dddmr_rollout_depth_layer_get_clusters(ctx_, voxel.data(), offsets.data(), xyz.data(), m, p, &m, &p);
+    if (rc != DDDMR_OK) return rc;
+    voxel.resize(3 * m);
+    xyz.resize(3 * p);
+    return DDDMR_OK;
+  }
   // prune plan poses, x y z qx qy qz qw each (output of Local_Planner::prunePlan)
   void setPlan(const double* poses_xyz_qxyzw, size_t n_poses) {
     check(dddmr_rollout_set_prune_plan(ctx_, poses_xyz_qxyzw, n_poses));
