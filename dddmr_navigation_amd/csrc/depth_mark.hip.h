@@ -171,20 +171,12 @@ namespace {
 
 struct DepthMarkState {
   dddmr_depth_mark_config cfg{};
-  uint32_t n_ground = 0, n_map = 0, max_obs = 0;
-  float4 *ground_pts = nullptr, *map_pts = nullptr;
-  GridBuf ground, map;
-  // scratch of one call (sized for max_obs)
-  uint32_t* parent = nullptr;
-  unsigned long long *keys_a = nullptr, *keys_b = nullptr, *keys1 = nullptr;
-  uint32_t *vals_a = nullptr, *vals_b = nullptr, *flags = nullptr, *incl = nullptr, *cid_incl = nullptr;
-  float4* ds = nullptr;
-  uint32_t *ds_first = nullptr, *fate = nullptr;
-  ClusterArrays cl{};
+  uint32_t max_obs = 0;
+  StaticGrids grids;
+  ClusterScratch sc;                       // scratch of one call (sized for max_obs), with fate and the counters below
+  uint32_t* fate = nullptr;
   MarkCounters* counters = nullptr;
-  uint32_t* n_groups = nullptr;
-  void* temp = nullptr;
-  size_t temp_bytes = 0;
+  DevAllocs mem;                           // (of the two above)
   // pinned + mapped results, grown on demand
   void* out_host = nullptr;
   void* out_dev = nullptr;
@@ -193,65 +185,28 @@ struct DepthMarkState {
 
 void depth_mark_free(DepthMarkState* s) {
   if (!s) return;
-  void* p[] = {s->ground_pts, s->map_pts, s->parent, s->keys_a, s->keys_b, s->keys1, s->vals_a, s->vals_b, s->flags, s->incl,
-               s->cid_incl, s->ds, s->ds_first, s->fate, s->cl.start, s->cl.size, s->cl.centroid, s->cl.state, s->cl.ds_count,
-               s->cl.vkey, s->counters, s->n_groups, s->temp};
-  for (void* q : p)
-    if (q) (void)hipFree(q);
+  dev_free(s->mem);
+  dev_free(s->sc.mem);
+  dev_free(s->grids.mem);
   if (s->out_host) (void)hipHostFree(s->out_host);
-  free_grid(s->ground);
-  free_grid(s->map);
   delete s;
 }
 
-int depth_mark_init(dddmr_rollout_ctx* ctx, DepthMarkState* s, const float* ground_xyz, size_t n_ground, size_t ground_stride_bytes,
+// `table`: slots of the marking store that does its housekeeping with this state's rocPRIM storage (depth_layer.hip.h), 0: none
+int depth_mark_init(dddmr_rollout_ctx* ctx, DepthMarkState* s, size_t table, const float* ground_xyz, size_t n_ground, size_t ground_stride_bytes,
                     const float* map_xyz, size_t n_map, size_t map_stride_bytes) {
-  const size_t N = s->max_obs;
-  {
-    size_t a = 0, b = 0, c = 0, d = 0;
-    unsigned long long* k = nullptr;
-    uint32_t* v = nullptr;
-    HIPCHK(ctx, rocprim::radix_sort_keys(nullptr, a, k, k, N, 0, 40, ctx->stream));
-    HIPCHK(ctx, rocprim::radix_sort_pairs(nullptr, b, k, k, v, v, N, 0, 62, ctx->stream));
-    HIPCHK(ctx, rocprim::exclusive_scan(nullptr, c, v, v, 0u, (size_t)(1u << 22) + 1, rocprim::plus<uint32_t>(), ctx->stream));
-    HIPCHK(ctx, rocprim::inclusive_scan(nullptr, d, v, v, N, rocprim::plus<uint32_t>(), ctx->stream));
-    s->temp_bytes = std::max({a, b, c, d, (size_t)4096}) + 256;
-    HIPCHK(ctx, hipMalloc(&s->temp, s->temp_bytes));
-  }
-  // the static-grid builder of the marking layer, as it is: it only takes its rocPRIM scratch from a MarkingState
-  MarkingState builder;
-  builder.temp = s->temp;
-  builder.temp_bytes = s->temp_bytes;
-  int rc = upload_static(ctx, &builder, s->ground, &s->ground_pts, ground_xyz, n_ground, ground_stride_bytes, 0.5f, 1e6f);
+  int rc = cluster_scratch_alloc(ctx, s->sc, s->max_obs, table);
   if (rc != DDDMR_OK) return rc;
-  rc = upload_static(ctx, &builder, s->map, &s->map_pts, map_xyz, n_map, map_stride_bytes, 0.25f, 0.25f);
+  rc = static_grids_upload(ctx, s->grids, s->sc.temp, s->sc.temp_bytes, ground_xyz, n_ground, ground_stride_bytes, map_xyz, n_map, map_stride_bytes);
   if (rc != DDDMR_OK) return rc;
-  HIPCHK(ctx, hipMalloc(&s->parent, N * sizeof(uint32_t)));
-  HIPCHK(ctx, hipMalloc(&s->keys_a, N * sizeof(unsigned long long)));
-  HIPCHK(ctx, hipMalloc(&s->keys_b, N * sizeof(unsigned long long)));
-  HIPCHK(ctx, hipMalloc(&s->keys1, N * sizeof(unsigned long long)));
-  HIPCHK(ctx, hipMalloc(&s->vals_a, N * sizeof(uint32_t)));
-  HIPCHK(ctx, hipMalloc(&s->vals_b, N * sizeof(uint32_t)));
-  HIPCHK(ctx, hipMalloc(&s->flags, N * sizeof(uint32_t)));
-  HIPCHK(ctx, hipMalloc(&s->incl, N * sizeof(uint32_t)));
-  HIPCHK(ctx, hipMalloc(&s->cid_incl, N * sizeof(uint32_t)));
-  HIPCHK(ctx, hipMalloc(&s->ds, N * sizeof(float4)));
-  HIPCHK(ctx, hipMalloc(&s->ds_first, N * sizeof(uint32_t)));
-  HIPCHK(ctx, hipMalloc(&s->fate, N * sizeof(uint32_t)));
-  HIPCHK(ctx, hipMalloc(&s->cl.start, (N + 1) * sizeof(uint32_t)));
-  HIPCHK(ctx, hipMalloc(&s->cl.size, N * sizeof(uint32_t)));
-  HIPCHK(ctx, hipMalloc(&s->cl.centroid, N * sizeof(float4)));
-  HIPCHK(ctx, hipMalloc(&s->cl.state, N * sizeof(uint32_t)));
-  HIPCHK(ctx, hipMalloc(&s->cl.ds_count, N * sizeof(uint32_t)));
-  HIPCHK(ctx, hipMalloc(&s->cl.vkey, 3 * N * sizeof(int)));
-  HIPCHK(ctx, hipMalloc(&s->counters, sizeof(MarkCounters)));
-  HIPCHK(ctx, hipMalloc(&s->n_groups, sizeof(uint32_t)));
+  HIPCHK(ctx, dev_alloc(s->mem, &s->fate, s->max_obs));
+  HIPCHK(ctx, dev_alloc(s->mem, &s->counters, 1));
   return DDDMR_OK;
 }
 
 // The enqueue part of one selfMark, shared by depth_mark_clusters and the depth layer's update (depth_layer.hip.h): from
 // the Euclidean clusters to k_dm_stage2 on `st`, over the n points of the observation grid `d` holds.  Afterwards
-// s->counters->n_clusters, s->cl (start, size, centroid, ds_count, vkey), s->fate, s->ds, s->ds_first and s->n_groups are what
+// s->counters->n_clusters, s->sc.cl (start, size, centroid, ds_count, vkey), s->fate, s->sc.ds, s->sc.ds_first and s->sc.n_groups are what
 // the launch sequence at the top of this file leaves.  *ops grows by the kernels enqueued (rocPRIM's are the caller's to add).
 #define DM_LAUNCH(...) do { hipLaunchKernelGGL(__VA_ARGS__); ++*ops; } while (0)
 int depth_mark_enqueue(dddmr_rollout_ctx* ctx, DepthMarkState* s, const double T_gbl_base[7], DepthClear& d, uint32_t n,
@@ -264,48 +219,40 @@ int depth_mark_enqueue(dddmr_rollout_ctx* ctx, DepthMarkState* s, const double T
   k.tol2 = static_cast<float>(s->cfg.euclidean_cluster_extraction_tolerance * s->cfg.euclidean_cluster_extraction_tolerance);
   k.min_cluster = s->cfg.euclidean_cluster_extraction_min_cluster_size;
   k.n_obs = n;
-  k.n_map = s->n_map;
+  k.n_map = s->grids.n_map;
   MarkParams mk{};                        // what the general route's kernels read of it
   mk.n_obs = n;
   const float4* pts = d.pts;
   const dim3 pb((n + 255) / 256), cb((n + 63) / 64);
   HIPCHK(ctx, hipMemsetAsync(s->counters, 0, sizeof(MarkCounters), st));
   // Euclidean clusters
-  DM_LAUNCH(k_mk_cc_init, pb, dim3(256), 0, st, n, s->parent);
-  DM_LAUNCH(k_dm_cc_union, pb, dim3(256), 0, st, k, d.hdr, pts, s->parent);
-  DM_LAUNCH(k_mk_cc_keys, pb, dim3(256), 0, st, n, s->parent, s->keys_a);
-  size_t tb = s->temp_bytes;
-  HIPCHK(ctx, rocprim::radix_sort_keys(s->temp, tb, s->keys_a, s->keys1, (size_t)n, 0, 40, st));
-  DM_LAUNCH(k_mk_flags, pb, dim3(256), 0, st, n, s->keys1, 20, s->flags);
-  tb = s->temp_bytes;
-  HIPCHK(ctx, rocprim::inclusive_scan(s->temp, tb, s->flags, s->cid_incl, (size_t)n, rocprim::plus<uint32_t>(), st));
-  DM_LAUNCH(k_mk_cluster_starts, pb, dim3(256), 0, st, n, s->flags, s->cid_incl, s->cl, s->counters);
-  DM_LAUNCH(k_dm_stage1, cb, dim3(64), 0, st, k, s->counters, s->cl, s->keys1, pts, s->ground.g, s->fate);
+  DM_LAUNCH(k_mk_cc_init, pb, dim3(256), 0, st, n, s->sc.parent);
+  DM_LAUNCH(k_dm_cc_union, pb, dim3(256), 0, st, k, d.hdr, pts, s->sc.parent);
+  DM_LAUNCH(k_mk_cc_keys, pb, dim3(256), 0, st, n, s->sc.parent, s->sc.keys_a);
+  size_t tb = s->sc.temp_bytes;
+  HIPCHK(ctx, rocprim::radix_sort_keys(s->sc.temp, tb, s->sc.keys_a, s->sc.keys1, (size_t)n, 0, 40, st));
+  DM_LAUNCH(k_mk_flags, pb, dim3(256), 0, st, n, s->sc.keys1, 20, s->sc.flags);
+  tb = s->sc.temp_bytes;
+  HIPCHK(ctx, rocprim::inclusive_scan(s->sc.temp, tb, s->sc.flags, s->sc.cid_incl, (size_t)n, rocprim::plus<uint32_t>(), st));
+  DM_LAUNCH(k_mk_cluster_starts, pb, dim3(256), 0, st, n, s->sc.flags, s->sc.cid_incl, s->sc.cl, s->counters);
+  DM_LAUNCH(k_dm_stage1, cb, dim3(64), 0, st, k, s->counters, s->sc.cl, s->sc.keys1, pts, s->grids.ground.g, s->fate);
   // 0.2 m VoxelGrid of every cluster that is still in: stable sort by (cluster, voxel), one lane per voxel.  The voxel
   // indices are keyed relative to the robot's voxel - half the key range (+-6.5 km in x / y, +-102 m in z).
   const int ox = (int)std::floor((float)T_gbl_base[0] / 0.2f) - kVgHalfXY, oy = (int)std::floor((float)T_gbl_base[1] / 0.2f) - kVgHalfXY,
             oz = (int)std::floor((float)T_gbl_base[2] / 0.2f) - kVgHalfZ;
-  DM_LAUNCH(k_mk_ds_keys, pb, dim3(256), 0, st, mk, s->keys1, s->cid_incl, s->cl, pts, ox, oy, oz, s->keys_a, s->vals_a, s->counters);
-  tb = s->temp_bytes;
-  HIPCHK(ctx, rocprim::radix_sort_pairs(s->temp, tb, s->keys_a, s->keys_b, s->vals_a, s->vals_b, (size_t)n, 0, 62, st));
-  DM_LAUNCH(k_mk_flags, pb, dim3(256), 0, st, n, s->keys_b, 0, s->flags);
-  tb = s->temp_bytes;
-  HIPCHK(ctx, rocprim::inclusive_scan(s->temp, tb, s->flags, s->incl, (size_t)n, rocprim::plus<uint32_t>(), st));
-  HIPCHK(ctx, hipMemsetAsync(s->ds_first, 0xFF, (size_t)n * sizeof(uint32_t), st));
-  DM_LAUNCH(k_mk_group_reduce, cb, dim3(64), 0, st, n, s->keys_b, s->vals_b, s->flags, s->incl, 0, s->keys1, pts, s->ds,
-            s->cl.ds_count, s->ds_first, s->n_groups);
-  DM_LAUNCH(k_dm_stage2, cb, dim3(64), 0, st, k, S, s->counters, s->cl, s->map.g, s->fate);
+  DM_LAUNCH(k_mk_ds_keys, pb, dim3(256), 0, st, mk, s->sc.keys1, s->sc.cid_incl, s->sc.cl, pts, ox, oy, oz, s->sc.keys_a, s->sc.vals_a, s->counters);
+  tb = s->sc.temp_bytes;
+  HIPCHK(ctx, rocprim::radix_sort_pairs(s->sc.temp, tb, s->sc.keys_a, s->sc.keys_b, s->sc.vals_a, s->sc.vals_b, (size_t)n, 0, 62, st));
+  DM_LAUNCH(k_mk_flags, pb, dim3(256), 0, st, n, s->sc.keys_b, 0, s->sc.flags);
+  tb = s->sc.temp_bytes;
+  HIPCHK(ctx, rocprim::inclusive_scan(s->sc.temp, tb, s->sc.flags, s->sc.incl, (size_t)n, rocprim::plus<uint32_t>(), st));
+  HIPCHK(ctx, hipMemsetAsync(s->sc.ds_first, 0xFF, (size_t)n * sizeof(uint32_t), st));
+  DM_LAUNCH(k_mk_group_reduce, cb, dim3(64), 0, st, n, s->sc.keys_b, s->sc.vals_b, s->sc.flags, s->sc.incl, 0, s->sc.keys1, pts, s->sc.ds,
+            s->sc.cl.ds_count, s->sc.ds_first, s->sc.n_groups);
+  DM_LAUNCH(k_dm_stage2, cb, dim3(64), 0, st, k, S, s->counters, s->sc.cl, s->grids.map.g, s->fate);
   return DDDMR_OK;
 }
 #undef DM_LAUNCH
-
-// What extractEuclideanClusters hands to the sort is the clusters of at least min_cluster_size points in creation order;
-// this is the reference's std::sort(clusters.rbegin(), clusters.rend(), comparePointClusters) over them, sizes only
-// (oracle/ASSUMPTIONS.md row 10): the order addPCPtr is called in.
-struct DmItem { uint32_t size, ci; };
-void dm_replay_sort(std::vector<DmItem>& order) {
-  std::sort(order.rbegin(), order.rend(), [](const DmItem& a, const DmItem& b) { return a.size < b.size; });
-}
 
 }  // namespace
 
@@ -334,10 +281,8 @@ int dddmr_rollout_depth_mark_create(dddmr_rollout_ctx* ctx, const dddmr_depth_ma
   if (ctx->dmark) { depth_mark_free(ctx->dmark); ctx->dmark = nullptr; }
   auto* s = new DepthMarkState();
   s->cfg = *cfg;
-  s->n_ground = (uint32_t)n_ground;
-  s->n_map = (uint32_t)n_map;
   s->max_obs = cfg->max_observation_points;
-  const int rc = depth_mark_init(ctx, s, ground_xyz, n_ground, ground_stride_bytes, map_xyz, n_map, map_stride_bytes);
+  const int rc = depth_mark_init(ctx, s, 0, ground_xyz, n_ground, ground_stride_bytes, map_xyz, n_map, map_stride_bytes);
   if (rc != DDDMR_OK) { depth_mark_free(s); return rc; }
   ctx->dmark = s;                                        // only a complete state is ever visible
   return DDDMR_OK;
@@ -372,14 +317,7 @@ int dddmr_rollout_depth_mark_clusters(dddmr_rollout_ctx* ctx, const double T_gbl
   out.n_observation = (uint32_t)n_obs;
   // coefficients (:568-578): tf2::quatRotate(q, (0, 0, 1)) and d in double, each rounded to float
   float plane[4];
-  {
-    const double qb[4] = {T_gbl_base[3], T_gbl_base[4], T_gbl_base[5], T_gbl_base[6]};
-    double nb[3];
-    quat_rotate_z(qb, nb);
-    plane[0] = (float)nb[0]; plane[1] = (float)nb[1]; plane[2] = (float)nb[2];
-    const double d = -T_gbl_base[0] * nb[0] - T_gbl_base[1] * nb[1] - T_gbl_base[2] * nb[2];
-    plane[3] = (float)d;
-  }
+  base_plane(T_gbl_base, plane);
   if (!(n_obs > 5)) {                                    // :491-492
     if (!count_only) {
       std::memcpy(plane_out, plane, sizeof(plane));
@@ -402,7 +340,7 @@ int dddmr_rollout_depth_mark_clusters(dddmr_rollout_ctx* ctx, const double T_gbl
   const dim3 pb((n + 255) / 256);
 #define DM_LAUNCH(...) do { hipLaunchKernelGGL(__VA_ARGS__); ++ops; } while (0)
   char* dev = static_cast<char*>(s->out_dev);
-  DM_LAUNCH(k_dm_pack, pb, dim3(256), 0, st, n, s->counters, s->n_groups, s->cl, s->fate, s->ds_first, s->ds,
+  DM_LAUNCH(k_dm_pack, pb, dim3(256), 0, st, n, s->counters, s->sc.n_groups, s->sc.cl, s->fate, s->sc.ds_first, s->sc.ds,
             reinterpret_cast<DmHeader*>(dev), reinterpret_cast<DmRecord*>(dev + rec_at), reinterpret_cast<float*>(dev + pts_at));
 #undef DM_LAUNCH
   ops += 2 * 10 + 2 * 3 + 2;              // rocPRIM: two sorts (block sort + ~8 merge passes + id wrapper), two scans; two memsets

@@ -168,7 +168,7 @@ struct MarkParams {
 struct MarkCounters {         // device counters of one update (copied back for dddmr_marking_stats)
   uint32_t n_clusters, n_marked, n_in_window, n_cleared, n_alive, pool_used, overflow, n_groups2, n_groups3, n_clusters_kept;
   uint32_t n_removed;
-  uint32_t n_dup;   // clusters of this update that found their voxel already claimed by another one (marking_fix_ties)
+  uint32_t n_dup;   // clusters of this update that found their voxel already claimed by another one (store_tie_fixes)
   uint32_t n_new_keys;   // voxels that entered the store for the first time in this update (store garbage collection)
   uint32_t n_rehashed;   // alive markings moved by this update's garbage collection
   uint32_t fallback;     // fused route: a partition or its voxel sort keys did not fit, the mark phase has to take the general route
@@ -223,6 +223,14 @@ struct MarkStore {            // the persistent store (device pointers)
   double* dgraph;             // [n_ground + 1]
   uint8_t* lethal;            // [n_ground + 1]
 };
+// What a slot owns in the pool directly IN FRONT of its generator points: pool[pc_ofs .. pc_ofs + pc_n), with
+// pts_ofs = pc_ofs + pc_n for every alive slot.  The depth camera layer keeps the stored cluster pc_ there; the lidar
+// layer has no head and passes both pointers null.  The kernels that move a slot or give it pool space take it along.
+struct MarkHead {
+  uint32_t* pc_ofs;           // [table]
+  uint32_t* pc_n;             // [table]
+};
+__device__ __forceinline__ uint32_t mark_head_n(const MarkHead& h, uint32_t slot) { return h.pc_n ? h.pc_n[slot] : 0u; }
 
 // ---------------------------------------------------------------------------------------------
 // selfClear: one wave per store slot
@@ -588,7 +596,7 @@ __global__ __launch_bounds__(256) void k_mk_proj_keys(MarkParams k, const uint32
 // same voxel the last one in PCL's order (clusters sorted by size, descending) keeps the slot.  Among clusters of
 // EQUAL size that order is whatever libstdc++'s introsort leaves (std::sort over reverse iterators,
 // pcl/segmentation/impl/extract_clusters.hpp): the priority below breaks such ties by cluster index, and the host
-// replays the very sort for the updates that have a contested voxel at all (n_dup > 0, marking_fix_ties).
+// replays the very sort for the updates that have a contested voxel at all (n_dup > 0, store_tie_fixes).
 __global__ __launch_bounds__(64) void k_mk_slots(MarkParams k, const MarkCounters* __restrict__ cnt_in, ClusterArrays c, MarkStore s,
                                                  MarkCounters* __restrict__ cnt) {
   const uint32_t ci = blockIdx.x * 64 + threadIdx.x;
@@ -608,21 +616,31 @@ __global__ __launch_bounds__(64) void k_mk_slots(MarkParams k, const MarkCounter
   if (atomicMax(&s.owner[slot], pr) != 0ull) atomicAdd(&cnt->n_dup, 1u);
   atomicAdd(&cnt->n_marked, 1u);
 }
-// ... storage part: the winning cluster's generator points go to the pool
+// ... storage part: the winning cluster gets pool space for its generator points, behind its head where the store
+// keeps one (the cluster's 0.2 m points; pc_dst[ci] = where they go).  The ranges the slot had before become pool
+// garbage.  pc_dst is null without a head.
 __global__ __launch_bounds__(64) void k_mk_commit(MarkParams k, const MarkCounters* __restrict__ cnt_in, ClusterArrays c, MarkStore s,
-                                                  MarkCounters* __restrict__ cnt, uint32_t* __restrict__ pool_ofs) {
+                                                  MarkHead h, MarkCounters* __restrict__ cnt, uint32_t* __restrict__ pc_dst,
+                                                  uint32_t* __restrict__ pool_ofs) {
   const uint32_t ci = blockIdx.x * 64 + threadIdx.x;
   if (ci >= cnt_in->n_clusters) return;
+  if (h.pc_n) pc_dst[ci] = 0xFFFFFFFFu;
   pool_ofs[ci] = 0xFFFFFFFFu;
   if (c.state[ci] != 2u) return;
   const uint32_t slot = c.slot[ci];
   const unsigned long long pr = ((unsigned long long)((1u << 20) - min(c.size[ci], (1u << 20) - 1u)) << 20) | (unsigned long long)(ci + 1u);
   if (s.owner[slot] != pr) return;
-  const uint32_t n = c.gen_count[ci];
-  const uint32_t ofs = atomicAdd(&cnt->pool_used, n);
-  if (ofs + n > k.pool_cap) { atomicOr(&cnt->overflow, 2u); s.alive[slot] = 0; s.pts_n[slot] = 0; return; }
-  pool_ofs[ci] = ofs;
-  s.pts_ofs[slot] = ofs;
+  const uint32_t npc = h.pc_n ? c.ds_count[ci] : 0u, n = c.gen_count[ci];
+  const uint32_t ofs = atomicAdd(&cnt->pool_used, npc + n);
+  if ((unsigned long long)ofs + npc + n > (unsigned long long)k.pool_cap) {
+    atomicOr(&cnt->overflow, 2u);
+    s.alive[slot] = 0; s.pts_n[slot] = 0;
+    if (h.pc_n) h.pc_n[slot] = 0;
+    return;
+  }
+  if (h.pc_n) { pc_dst[ci] = ofs; h.pc_ofs[slot] = ofs; h.pc_n[slot] = npc; }
+  pool_ofs[ci] = ofs + npc;
+  s.pts_ofs[slot] = ofs + npc;
   s.pts_n[slot] = n;
   s.alive[slot] = 1;
 }
@@ -650,28 +668,42 @@ __global__ __launch_bounds__(256) void k_mk_dgraph(MarkParams k, const uint32_t*
     }
   });
 }
-// marking_fix_ties: the generator points of the cluster that keeps a contested voxel in the reference's order replace
-// the ones k_mk_commit stored (those become pool garbage).  One wave per (slot, cluster) pair.
+// store_tie_fixes: the cluster that keeps a contested voxel in the reference's order replaces what k_mk_commit stored
+// (that becomes pool garbage): its generator points and, where the store keeps a head, its 0.2 m points
+// ds[ds_first[ci] ..) in front of them (ds, ds_first: null without a head).  One wave per (slot, cluster) pair.
 __global__ __launch_bounds__(256) void k_mk_fix_owner(MarkParams k, uint32_t n_fix, const uint2* __restrict__ fix,
-                                                      const float4* __restrict__ gen, ClusterArrays c, MarkStore s,
+                                                      const float4* __restrict__ ds, const uint32_t* __restrict__ ds_first,
+                                                      const float4* __restrict__ gen, ClusterArrays c, MarkStore s, MarkHead h,
                                                       MarkCounters* __restrict__ cnt) {
   const uint32_t f = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (f >= n_fix) return;
   const uint32_t slot = fix[f].x, ci = fix[f].y;
+  const uint32_t npc = h.pc_n ? c.ds_count[ci] : 0u, pc_first = h.pc_n ? ds_first[ci] : 0u;
   const uint32_t n = c.gen_count[ci], first = c.gen_first[ci];
   uint32_t ofs = 0;
-  if (lane == 0) ofs = atomicAdd(&cnt->pool_used, n);
+  if (lane == 0) ofs = atomicAdd(&cnt->pool_used, npc + n);
   ofs = (uint32_t)__builtin_amdgcn_readfirstlane((int)ofs);
-  if (ofs + n > k.pool_cap) {
-    if (lane == 0) { atomicOr(&cnt->overflow, 2u); s.alive[slot] = 0; s.pts_n[slot] = 0; }
+  if ((unsigned long long)ofs + npc + n > (unsigned long long)k.pool_cap) {
+    if (lane == 0) {
+      atomicOr(&cnt->overflow, 2u);
+      s.alive[slot] = 0; s.pts_n[slot] = 0;
+      if (h.pc_n) h.pc_n[slot] = 0;
+    }
     return;
+  }
+  for (uint32_t i = lane; i < npc; i += 64) {
+    const float4 p = ds[pc_first + i];
+    s.pool[ofs + i] = make_float4(p.x, p.y, p.z, 0.f);
   }
   for (uint32_t i = lane; i < n; i += 64) {
     const float4 p = gen[first + i];
-    s.pool[ofs + i] = make_float4(p.x, p.y, p.z, 0.f);
+    s.pool[ofs + npc + i] = make_float4(p.x, p.y, p.z, 0.f);
   }
-  if (lane == 0) { s.pts_ofs[slot] = ofs; s.pts_n[slot] = n; s.alive[slot] = 1; }
+  if (lane == 0) {
+    if (h.pc_n) { h.pc_ofs[slot] = ofs; h.pc_n[slot] = npc; }
+    s.pts_ofs[slot] = ofs + npc; s.pts_n[slot] = n; s.alive[slot] = 1;
+  }
 }
 __global__ __launch_bounds__(256) void k_mk_finish(MarkParams k, MarkStore s, MarkCounters* __restrict__ cnt) {
   const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
@@ -684,9 +716,9 @@ __global__ __launch_bounds__(256) void k_mk_finish(MarkParams k, MarkStore s, Ma
 // table with keys nothing reads any more.  When half the table is used the alive markings move to a fresh table;
 // the dropped keys change nothing the reference can observe.  One lane per old slot; the new alive list is built
 // on the way (its order is irrelevant: selfClear treats every marking on its own).
-__global__ __launch_bounds__(256) void k_mk_rehash(uint32_t table_mask, MarkStore s, unsigned long long* __restrict__ keys_new,
+__global__ __launch_bounds__(256) void k_mk_rehash(uint32_t table_mask, MarkStore s, MarkHead h, unsigned long long* __restrict__ keys_new,
                                                    uint32_t* __restrict__ alive_new, uint32_t* __restrict__ pts_ofs_new,
-                                                   uint32_t* __restrict__ pts_n_new, MarkCounters* __restrict__ cnt) {
+                                                   uint32_t* __restrict__ pts_n_new, MarkHead h_new, MarkCounters* __restrict__ cnt) {
   const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
   if (slot > table_mask || !s.alive[slot]) return;
   const unsigned long long key = s.keys[slot];
@@ -698,22 +730,25 @@ __global__ __launch_bounds__(256) void k_mk_rehash(uint32_t table_mask, MarkStor
   alive_new[ns] = 1;
   pts_ofs_new[ns] = s.pts_ofs[slot];
   pts_n_new[ns] = s.pts_n[slot];
+  if (h.pc_n) { h_new.pc_ofs[ns] = h.pc_ofs[slot]; h_new.pc_n[ns] = h.pc_n[slot]; }
   s.alive_list[atomicAdd(&cnt->n_rehashed, 1u)] = ns;
 }
-// pool compaction: generator points of the alive markings move to the front of the other pool buffer
-__global__ __launch_bounds__(256) void k_mk_compact_sizes(uint32_t table, MarkStore s, uint32_t* __restrict__ sizes) {
+// pool compaction: head and generator points of the alive markings move, as one range each, to the front of the other
+// pool buffer
+__global__ __launch_bounds__(256) void k_mk_compact_sizes(uint32_t table, MarkStore s, MarkHead h, uint32_t* __restrict__ sizes) {
   const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
-  if (slot < table) sizes[slot] = s.alive[slot] ? s.pts_n[slot] : 0u;
+  if (slot < table) sizes[slot] = s.alive[slot] ? mark_head_n(h, slot) + s.pts_n[slot] : 0u;
 }
-__global__ __launch_bounds__(256) void k_mk_compact_move(uint32_t table, MarkStore s, const uint32_t* __restrict__ new_ofs,
+__global__ __launch_bounds__(256) void k_mk_compact_move(uint32_t table, MarkStore s, MarkHead h, const uint32_t* __restrict__ new_ofs,
                                                          float4* __restrict__ dst, MarkCounters* __restrict__ cnt) {
   const uint32_t slot = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (slot >= table || !s.alive[slot]) return;
-  const uint32_t n = s.pts_n[slot], from = s.pts_ofs[slot], to = new_ofs[slot];
+  const uint32_t npc = mark_head_n(h, slot), n = npc + s.pts_n[slot], from = s.pts_ofs[slot] - npc, to = new_ofs[slot];
   for (uint32_t i = lane; i < n; i += 64) dst[to + i] = s.pool[from + i];
   if (lane == 0) {
-    s.pts_ofs[slot] = to;
+    if (h.pc_n) h.pc_ofs[slot] = to;
+    s.pts_ofs[slot] = to + npc;
     atomicMax(&cnt->pool_used, to + n);
   }
 }

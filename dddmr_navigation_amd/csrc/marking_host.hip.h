@@ -3,10 +3,9 @@
 // launch sequence and the dddmr_rollout_marking_* entry points of include/dddmr_rollout.h.
 #pragma once
 
-#include <unordered_map>
-
 #include "marking.hip.h"
 #include "marking_fused.hip.h"
+#include "marking_store.hip.h"
 
 namespace {
 
@@ -20,32 +19,78 @@ struct GridBuf {              // a PointGrid with its storage
   uint32_t max_row = 0;       // static grids: points of the fullest (y, z) row of cells
 };
 
-struct MarkingState {
-  dddmr_marking_config cfg{};
-  uint32_t n_ground = 0, n_map = 0, table = 0, pool_cap = 0, max_obs = 0;
+// The ground and the static map: the points and a grid over each, uploaded once (static_grids_upload).
+struct StaticGrids {
+  uint32_t n_ground = 0, n_map = 0;
   float4 *ground_pts = nullptr, *map_pts = nullptr;
-  GridBuf ground, map, obs[2];
-  int prev = -1;              // obs[] entry holding pcl_msg_gbl_ of the last selfMark, -1 = none yet
-  uint32_t n_prev = 0;
-  float4* obs_copy[2] = {nullptr, nullptr};
-  MarkStore store{};
-  float4* pool_alt = nullptr;
-  // second set of the per-slot arrays for the store's garbage collection (k_mk_rehash)
-  unsigned long long* keys_alt = nullptr;
-  uint32_t *alive_alt = nullptr, *pts_ofs_alt = nullptr, *pts_n_alt = nullptr;
-  uint32_t pool_used_host = 0, n_alive_host = 0, keys_used_host = 0;
-  // scratch of one update (sized for max_obs)
-  uint2* gslot = nullptr;
+  GridBuf ground, map;
+  DevAllocs mem;
+};
+
+// Scratch of the cluster pipeline for one observation of up to N points (the general route's kernels of marking.hip.h,
+// the depth camera's selfMark of depth_mark.hip.h).
+struct ClusterScratch {
   uint32_t* parent = nullptr;
   unsigned long long *keys_a = nullptr, *keys_b = nullptr, *keys1 = nullptr;
   uint32_t *vals_a = nullptr, *vals_b = nullptr, *flags = nullptr, *incl = nullptr, *cid_incl = nullptr;
-  float4 *ds = nullptr, *proj = nullptr, *gen = nullptr;
-  uint32_t *ds_first = nullptr, *pool_ofs = nullptr, *compact_sizes = nullptr, *compact_ofs = nullptr;
-  ClusterArrays cl{};
-  MarkCounters* counters = nullptr;        // device
-  uint32_t* n_groups = nullptr;            // [2] device: groups of the 0.2 m and of the 0.1 m VoxelGrid
-  void* temp = nullptr;
+  float4* ds = nullptr;
+  uint32_t* ds_first = nullptr;
+  ClusterArrays cl{};                      // start, size, centroid, state, ds_count, vkey (the rest is the marking layers' own)
+  uint32_t* n_groups = nullptr;            // [2]: groups of the 0.2 m and of the 0.1 m VoxelGrid
+  char* temp = nullptr;                    // rocPRIM temporary storage
   size_t temp_bytes = 0;
+  DevAllocs mem;
+};
+
+// `table`: slots of the marking store whose housekeeping scans with this scratch's rocPRIM storage (0: none)
+int cluster_scratch_alloc(dddmr_rollout_ctx* ctx, ClusterScratch& c, size_t N, size_t table) {
+  // rocPRIM temporary storage: the largest request among the sorts and scans of the cluster pipeline, the static grids'
+  // builder (up to 2^22 cells) and the store's housekeeping
+  {
+    size_t a = 0, b = 0, e = 0, d = 0;
+    unsigned long long* k = nullptr;
+    uint32_t* v = nullptr;
+    HIPCHK(ctx, rocprim::radix_sort_keys(nullptr, a, k, k, N, 0, 40, ctx->stream));
+    HIPCHK(ctx, rocprim::radix_sort_pairs(nullptr, b, k, k, v, v, N, 0, 62, ctx->stream));
+    HIPCHK(ctx, rocprim::exclusive_scan(nullptr, e, v, v, 0u, std::max((size_t)(1u << 22) + 1, table), rocprim::plus<uint32_t>(), ctx->stream));
+    HIPCHK(ctx, rocprim::inclusive_scan(nullptr, d, v, v, std::max(N, table), rocprim::plus<uint32_t>(), ctx->stream));
+    c.temp_bytes = std::max({a, b, e, d, (size_t)4096}) + 256;
+    HIPCHK(ctx, dev_alloc(c.mem, &c.temp, c.temp_bytes));
+  }
+  HIPCHK(ctx, dev_alloc(c.mem, &c.parent, N));
+  HIPCHK(ctx, dev_alloc(c.mem, &c.keys_a, N));
+  HIPCHK(ctx, dev_alloc(c.mem, &c.keys_b, N));
+  HIPCHK(ctx, dev_alloc(c.mem, &c.keys1, N));
+  HIPCHK(ctx, dev_alloc(c.mem, &c.vals_a, N));
+  HIPCHK(ctx, dev_alloc(c.mem, &c.vals_b, N));
+  HIPCHK(ctx, dev_alloc(c.mem, &c.flags, N));
+  HIPCHK(ctx, dev_alloc(c.mem, &c.incl, N));
+  HIPCHK(ctx, dev_alloc(c.mem, &c.cid_incl, N));
+  HIPCHK(ctx, dev_alloc(c.mem, &c.ds, N));
+  HIPCHK(ctx, dev_alloc(c.mem, &c.ds_first, N));
+  HIPCHK(ctx, dev_alloc(c.mem, &c.cl.start, N + 1));
+  HIPCHK(ctx, dev_alloc(c.mem, &c.cl.size, N));
+  HIPCHK(ctx, dev_alloc(c.mem, &c.cl.centroid, N));
+  HIPCHK(ctx, dev_alloc(c.mem, &c.cl.state, N));
+  HIPCHK(ctx, dev_alloc(c.mem, &c.cl.ds_count, N));
+  HIPCHK(ctx, dev_alloc(c.mem, &c.cl.vkey, 3 * N));
+  HIPCHK(ctx, dev_alloc(c.mem, &c.n_groups, 2));
+  return DDDMR_OK;
+}
+
+struct MarkingState {
+  dddmr_marking_config cfg{};
+  uint32_t max_obs = 0;
+  StaticGrids grids;
+  GridBuf obs[2];
+  int prev = -1;              // obs[] entry holding pcl_msg_gbl_ of the last selfMark, -1 = none yet
+  uint32_t n_prev = 0;
+  StoreBuf store;             // its counters also count the update's clusters
+  ClusterScratch sc;          // scratch of one update (sized for max_obs), with the layer's own below
+  uint2* gslot = nullptr;
+  float4 *proj = nullptr, *gen = nullptr;
+  uint32_t* pool_ofs = nullptr;
+  DevAllocs mem;              // the device allocations of this struct itself
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
   uint32_t seq = 0;
   // fused route (marking_fused.hip.h)
@@ -53,7 +98,6 @@ struct MarkingState {
   float4* band_pts = nullptr;              // [2][kBandMax * kBandCap]: generator points of this update / of removed markings, by row of ground cells
   uint32_t* band_cnt = nullptr;            // [2][kBandMax], all zero between updates
   uint32_t* hi_rank = nullptr;             // [8][kFuseMaxObs - kFuseRegObs] grid builder scratch for observations past kFuseRegObs points
-  uint32_t* clear_list = nullptr;          // [table]
   uint32_t* cell_count = nullptr;          // [kFuseMaxCells], all zero between updates
   bool alive_list_stale = false;           // the fused route keeps no alive list: the general route rebuilds it first
   uint32_t* ticket = nullptr;              // [2]
@@ -74,36 +118,13 @@ struct MarkingState {
   uint32_t fuse_cells = kFuseMaxCells;     // DDDMR_MKF_CELLS: cells of the fused route's observation grid (tuning)
 };
 
-void free_grid(GridBuf& b) {
-  if (b.g.cell_start) (void)hipFree(b.g.cell_start);
-  if (b.g.sorted) (void)hipFree(b.g.sorted);
-  b = GridBuf();
-}
-
-// Contested voxels.  When several accepted clusters of one scan have their centroid in the same voxel, the reference
-// keeps the generator points of the one processed LAST, and it processes the clusters in the order
-// std::sort(clusters.rbegin(), clusters.rend(), comparePointClusters) leaves them in (EuclideanClusterExtraction::
-// extract): descending size, equal sizes in the order libstdc++'s introsort happens to produce.  k_mk_slots breaks
-// equal sizes by cluster index; for the (rare) updates that have a contested voxel this replays the reference's sort on
-// the host -- the same std::sort, on the same sizes in the same creation order (ascending first point index =
-// ascending cluster index), with a comparator that compares sizes only -- and re-commits the voxels whose keeper
-// differs.  The dGraph and the lethal set do not depend on the keeper (every cluster contributes its minimum); what does
-// is which node set a later selfClear of the voxel resets.
-int marking_fix_ties(dddmr_rollout_ctx* ctx, MarkingState* m, const MarkParams& k, const MarkStore& s, MarkCounters& out);
-
 void marking_free(MarkingState* m) {
   if (!m) return;
-  void* p[] = {m->ground_pts, m->map_pts, m->obs_copy[0], m->obs_copy[1], m->store.keys, m->store.alive, m->store.pts_ofs,
-               m->store.pts_n, m->store.removed_seq, m->store.owner, m->store.alive_list, m->store.removed_list, m->store.fov_flag,
-               m->store.pool, m->pool_alt, m->store.dgraph, m->store.lethal, m->keys_alt, m->alive_alt, m->pts_ofs_alt, m->pts_n_alt,
-               m->gslot, m->parent, m->keys_a, m->keys_b, m->keys1, m->vals_a, m->vals_b, m->flags, m->incl, m->cid_incl, m->ds,
-               m->proj, m->gen, m->ds_first, m->pool_ofs, m->compact_sizes, m->compact_ofs, m->cl.start, m->cl.size, m->cl.centroid,
-               m->cl.state, m->cl.ds_count, m->cl.gen_first, m->cl.gen_count, m->cl.slot, m->cl.vkey, m->counters, m->n_groups,
-               m->temp, m->unmark_pts, m->ticket, m->clear_list, m->cell_count, m->band_pts, m->band_cnt, m->hi_rank};
-  for (void* q : p)
-    if (q) (void)hipFree(q);
+  dev_free(m->mem);
+  dev_free(m->sc.mem);
+  dev_free(m->grids.mem);
+  store_free(m->store);
   if (m->host_out) (void)hipHostFree(m->host_out);
-  free_grid(m->ground); free_grid(m->map); free_grid(m->obs[0]); free_grid(m->obs[1]);
   if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
   if (m->e0) (void)hipEventDestroy(m->e0);
   if (m->e1) (void)hipEventDestroy(m->e1);
@@ -131,24 +152,24 @@ int host_cx(const PointGrid& g, float x) { return std::min(std::max((int)std::fl
 int host_cy(const PointGrid& g, float y) { return std::min(std::max((int)std::floor((y - g.oy) * g.inv_xy), 0), g.ny - 1); }
 int host_cz(const PointGrid& g, float z) { return std::min(std::max((int)std::floor((z - g.oz) * g.inv_z), 0), g.nz - 1); }
 
-int grid_alloc(dddmr_rollout_ctx* ctx, GridBuf& b, uint32_t cap_cells, uint32_t cap_points) {
+int grid_alloc(dddmr_rollout_ctx* ctx, DevAllocs& mem, GridBuf& b, uint32_t cap_cells, uint32_t cap_points) {
   b.cap_cells = cap_cells;
   b.cap_points = cap_points;
-  HIPCHK(ctx, hipMalloc(&b.g.cell_start, ((size_t)cap_cells + 1) * sizeof(uint32_t)));
-  HIPCHK(ctx, hipMalloc(&b.g.sorted, (size_t)std::max<uint32_t>(cap_points, 1) * sizeof(float4)));
+  HIPCHK(ctx, dev_alloc(mem, &b.g.cell_start, (size_t)cap_cells + 1));
+  HIPCHK(ctx, dev_alloc(mem, &b.g.sorted, std::max<uint32_t>(cap_points, 1)));
   return DDDMR_OK;
 }
 
-// count -> exclusive scan -> scatter on `stream`; `counts` doubles as cell_start
-int grid_build(dddmr_rollout_ctx* ctx, MarkingState* m, GridBuf& b, const float4* pts, uint32_t n, uint2* slot, hipStream_t stream) {
+// count -> exclusive scan (rocPRIM storage `temp`) -> scatter on `stream`; `counts` doubles as cell_start
+int grid_build(dddmr_rollout_ctx* ctx, void* temp, size_t temp_bytes, GridBuf& b, const float4* pts, uint32_t n, uint2* slot,
+               hipStream_t stream) {
   PointGrid& g = b.g;
   g.n = n;
   const size_t cells = (size_t)g.nx * g.ny * g.nz;
   HIPCHK(ctx, hipMemsetAsync(g.cell_start, 0, (cells + 1) * sizeof(uint32_t), stream));
   if (n == 0) return DDDMR_OK;
   hipLaunchKernelGGL(k_grid_count, dim3((n + 255) / 256), dim3(256), 0, stream, g, pts, g.cell_start, slot);
-  size_t need = m->temp_bytes;
-  HIPCHK(ctx, rocprim::exclusive_scan(m->temp, need, g.cell_start, g.cell_start, 0u, cells + 1, rocprim::plus<uint32_t>(), stream));
+  HIPCHK(ctx, rocprim::exclusive_scan(temp, temp_bytes, g.cell_start, g.cell_start, 0u, cells + 1, rocprim::plus<uint32_t>(), stream));
   hipLaunchKernelGGL(k_grid_scatter, dim3((n + 255) / 256), dim3(256), 0, stream, g, pts, slot);
   return DDDMR_OK;
 }
@@ -161,6 +182,28 @@ void quat_rotate_z(const double q[4], double out[3]) {   // tf2::quatRotate(q, (
   out[0] = aw * bx + ax * bw + ay * bz - az * by;
   out[1] = aw * by + ay * bw + az * bx - ax * bz;
   out[2] = aw * bz + az * bw + ax * by - ay * bx;
+}
+
+// ModelCoefficients of the plane through base_link with base z as its normal (:401-409; depth camera :568-578):
+// tf2::quatRotate(q, (0, 0, 1)) and d in double, each rounded to float
+void base_plane(const double T_gbl_base[7], float mc[4]) {
+  const double qb[4] = {T_gbl_base[3], T_gbl_base[4], T_gbl_base[5], T_gbl_base[6]};
+  double nb[3];
+  quat_rotate_z(qb, nb);
+  mc[0] = (float)nb[0]; mc[1] = (float)nb[1]; mc[2] = (float)nb[2];
+  const double d = -T_gbl_base[0] * nb[0] - T_gbl_base[1] * nb[1] - T_gbl_base[2] * nb[2];
+  mc[3] = (float)d;
+}
+// what an update's MarkParams take from the robot's pose: the base plane and selfClear's window in voxel keys
+// (lidar :489-496, depth camera :280-287), from k's own res / hres / window / marking_height
+void mark_params_pose(MarkParams& k, const double T_gbl_base[7]) {
+  base_plane(T_gbl_base, k.mc);
+  k.wx0 = (int)((T_gbl_base[0] - k.window) / k.res);
+  k.wx1 = (int)((T_gbl_base[0] + k.window) / k.res);
+  k.wy0 = (int)((T_gbl_base[1] - k.window) / k.res);
+  k.wy1 = (int)((T_gbl_base[1] + k.window) / k.res);
+  k.wz0 = (int)((T_gbl_base[2] - k.marking_height) / k.hres);
+  k.wz1 = (int)((T_gbl_base[2] + k.marking_height) / k.hres);
 }
 
 // Eigen quaternion of a rotation matrix (row-major R), as tf2::eigenToTransform forms trans_gbl2s_'s rotation
@@ -199,8 +242,8 @@ void tf2_set_rotation(const double q[4], double R[9]) {
   R[6] = xz - wy; R[7] = yz + wx; R[8] = 1.0 - (xx + yy);
 }
 
-int upload_static(dddmr_rollout_ctx* ctx, MarkingState* m, GridBuf& b, float4** dev, const float* xyz, size_t n, size_t stride_bytes,
-                  float cell_xy, float cell_z) {
+int upload_static(dddmr_rollout_ctx* ctx, DevAllocs& mem, void* temp, size_t temp_bytes, GridBuf& b, float4** dev, const float* xyz, size_t n,
+                  size_t stride_bytes, float cell_xy, float cell_z) {
   std::vector<float4> h(std::max<size_t>(n, 1));
   float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
   const size_t sf = stride_bytes / sizeof(float);
@@ -212,10 +255,10 @@ int upload_static(dddmr_rollout_ctx* ctx, MarkingState* m, GridBuf& b, float4** 
       hi[a] = i ? std::max(hi[a], p[a]) : p[a];
     }
   }
-  HIPCHK(ctx, hipMalloc(dev, h.size() * sizeof(float4)));
+  HIPCHK(ctx, dev_alloc(mem, dev, h.size()));
   HIPCHK(ctx, hipMemcpy(*dev, h.data(), h.size() * sizeof(float4), hipMemcpyHostToDevice));
   grid_shape(b.g, lo, hi, cell_xy, cell_z, 1u << 22);
-  const int rc = grid_alloc(ctx, b, (uint32_t)((size_t)b.g.nx * b.g.ny * b.g.nz), (uint32_t)n);
+  const int rc = grid_alloc(ctx, mem, b, (uint32_t)((size_t)b.g.nx * b.g.ny * b.g.nz), (uint32_t)n);
   if (rc != DDDMR_OK) return rc;
   {
     std::vector<uint32_t> rows((size_t)b.g.ny * b.g.nz, 0u);
@@ -225,58 +268,50 @@ int upload_static(dddmr_rollout_ctx* ctx, MarkingState* m, GridBuf& b, float4** 
   }
   uint2* slot = nullptr;
   HIPCHK(ctx, hipMalloc(&slot, std::max<size_t>(n, 1) * sizeof(uint2)));
-  const int rb = grid_build(ctx, m, b, *dev, (uint32_t)n, slot, ctx->stream);
+  const int rb = grid_build(ctx, temp, temp_bytes, b, *dev, (uint32_t)n, slot, ctx->stream);
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   (void)hipFree(slot);
   return rb;
 }
 
-int marking_fix_ties(dddmr_rollout_ctx* ctx, MarkingState* m, const MarkParams& k, const MarkStore& s, MarkCounters& out) {
+// the ground (0.5 m cells, one layer in z) and the static map (0.25 m cells)
+int static_grids_upload(dddmr_rollout_ctx* ctx, StaticGrids& g, void* temp, size_t temp_bytes, const float* ground_xyz, size_t n_ground,
+                        size_t ground_stride_bytes, const float* map_xyz, size_t n_map, size_t map_stride_bytes) {
+  g.n_ground = (uint32_t)n_ground;
+  g.n_map = (uint32_t)n_map;
+  const int rc = upload_static(ctx, g.mem, temp, temp_bytes, g.ground, &g.ground_pts, ground_xyz, n_ground, ground_stride_bytes, 0.5f, 1e6f);
+  if (rc != DDDMR_OK) return rc;
+  return upload_static(ctx, g.mem, temp, temp_bytes, g.map, &g.map_pts, map_xyz, n_map, map_stride_bytes, 0.25f, 0.25f);
+}
+
+// Contested voxels (store_tie_fixes): the clusters' sizes, states and slots come to the host with three copies, and the
+// voxels whose keeper differs are re-committed.
+int marking_fix_ties(dddmr_rollout_ctx* ctx, MarkingState* m, const MarkParams& k, MarkCounters& out) {
   const uint32_t nc = out.n_clusters;
   if (nc == 0) return DDDMR_OK;
   hipStream_t st = m->cur;
   std::vector<uint32_t> size(nc), state(nc), slot(nc);
-  HIPCHK(ctx, hipMemcpyAsync(size.data(), m->cl.size, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(ctx, hipMemcpyAsync(state.data(), m->cl.state, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(ctx, hipMemcpyAsync(slot.data(), m->cl.slot, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(size.data(), m->sc.cl.size, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(state.data(), m->sc.cl.state, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(slot.data(), m->sc.cl.slot, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  // what extractEuclideanClusters hands to the sort: the clusters of at least min_cluster_size points, in creation order
-  struct Item { uint32_t size, ci; };
-  std::vector<Item> order;
-  order.reserve(nc);
-  for (uint32_t ci = 0; ci < nc; ++ci)     // (size 0: a point index that seeds no cluster, fused route)
-    if (size[ci] > 0 && (int)size[ci] >= m->cfg.euclidean_cluster_extraction_min_cluster_size) order.push_back(Item{size[ci], ci});
-  std::sort(order.rbegin(), order.rend(), [](const Item& a, const Item& b) { return a.size < b.size; });
-  // per contested voxel: the accepted cluster the reference processes last, against the one the device kept
-  struct Keep { uint32_t ref_ci, dev_ci, dev_size, claims; };
-  std::unordered_map<uint32_t, Keep> keep;
-  for (const Item& it : order) {                      // (processing order)
-    if (state[it.ci] != 2u) continue;
-    auto ins = keep.insert(std::make_pair(slot[it.ci], Keep{it.ci, it.ci, it.size, 1u}));
-    if (ins.second) continue;
-    Keep& kp = ins.first->second;
-    kp.ref_ci = it.ci;
-    ++kp.claims;
-    if (it.size < kp.dev_size || (it.size == kp.dev_size && it.ci > kp.dev_ci)) { kp.dev_ci = it.ci; kp.dev_size = it.size; }   // k_mk_slots' priority
-  }
   std::vector<uint2> fix;
-  for (const auto& kv : keep)
-    if (kv.second.claims > 1 && kv.second.ref_ci != kv.second.dev_ci) fix.push_back(make_uint2(kv.first, kv.second.ref_ci));
-  if (fix.empty()) return DDDMR_OK;
-  // (vals_a is scratch of the update that just finished: >= max_obs words)
-  uint2* fix_dev = reinterpret_cast<uint2*>(m->vals_b);
-  if (fix.size() * 2 > (size_t)m->max_obs) return fail(ctx, DDDMR_ERR_CAPACITY, "marking_update: %zu contested voxels", fix.size());
+  const int rc = store_tie_fixes(ctx, "marking_update", m->max_obs, m->cfg.euclidean_cluster_extraction_min_cluster_size, nc, size.data(),
+                                 state.data(), slot.data(), fix);
+  if (rc != DDDMR_OK || fix.empty()) return rc;
+  // (vals_b is scratch of the update that just finished: >= max_obs words)
+  uint2* fix_dev = reinterpret_cast<uint2*>(m->sc.vals_b);
   HIPCHK(ctx, hipMemcpyAsync(fix_dev, fix.data(), fix.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_mk_fix_owner, dim3((unsigned)((fix.size() + 3) / 4)), dim3(256), 0, st, k, (uint32_t)fix.size(), fix_dev,
-                     m->gen, m->cl, s, m->counters);
+                     (const float4*)nullptr, (const uint32_t*)nullptr, m->gen, m->sc.cl, m->store.s, m->store.head, m->store.counters);
   MarkCounters after{};                                // (on the fused route the device copy holds only what k_mk_fix_owner touches)
-  HIPCHK(ctx, hipMemcpyAsync(&after, m->counters, sizeof(after), hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(&after, m->store.counters, sizeof(after), hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));               // (also keeps `fix` alive until the copy has run)
   HIPCHK(ctx, hipGetLastError());
   out.pool_used = after.pool_used;
   out.overflow |= after.overflow;
   if (after.overflow) m->counters_clean = false;
-  m->pool_used_host = out.pool_used;
+  m->store.pool_used = out.pool_used;
   return DDDMR_OK;
 }
 
@@ -308,93 +343,33 @@ int dddmr_rollout_marking_create(dddmr_rollout_ctx* ctx, const dddmr_marking_con
   auto* m = new MarkingState();
   ctx->marking = m;
   m->cfg = *cfg;
-  m->n_ground = (uint32_t)n_ground;
-  m->n_map = (uint32_t)n_map;
   m->max_obs = ctx->cfg.max_points;
-  uint32_t table = 1024;
-  while (table < 2 * cfg->max_markings) table <<= 1;
-  m->table = table;
-  m->pool_cap = cfg->max_cluster_points;
   auto init = [&]() -> int {
     const size_t N = m->max_obs;
-    // rocPRIM temporary storage: the largest request among the sorts and scans used below
-    {
-      size_t a = 0, b = 0, c = 0, d = 0;
-      unsigned long long* k = nullptr;
-      uint32_t* v = nullptr;
-      HIPCHK(ctx, rocprim::radix_sort_keys(nullptr, a, k, k, N, 0, 40, ctx->stream));
-      HIPCHK(ctx, rocprim::radix_sort_pairs(nullptr, b, k, k, v, v, N, 0, 62, ctx->stream));
-      HIPCHK(ctx, rocprim::exclusive_scan(nullptr, c, v, v, 0u, (size_t)(1u << 22) + 1, rocprim::plus<uint32_t>(), ctx->stream));
-      HIPCHK(ctx, rocprim::inclusive_scan(nullptr, d, v, v, std::max<size_t>(N, m->table), rocprim::plus<uint32_t>(), ctx->stream));
-      m->temp_bytes = std::max({a, b, c, d, (size_t)4096}) + 256;
-      HIPCHK(ctx, hipMalloc(&m->temp, m->temp_bytes));
-    }
-    int rc = upload_static(ctx, m, m->ground, &m->ground_pts, ground_xyz, n_ground, ground_stride_bytes, 0.5f, 1e6f);
+    int rc = store_alloc(ctx, m->store, 1024, cfg->max_markings, cfg->max_cluster_points, (uint32_t)n_ground, true, false);
     if (rc != DDDMR_OK) return rc;
-    rc = upload_static(ctx, m, m->map, &m->map_pts, map_xyz, n_map, map_stride_bytes, 0.25f, 0.25f);
+    if ((rc = cluster_scratch_alloc(ctx, m->sc, N, m->store.table)) != DDDMR_OK) return rc;
+    rc = static_grids_upload(ctx, m->grids, m->sc.temp, m->sc.temp_bytes, ground_xyz, n_ground, ground_stride_bytes, map_xyz, n_map,
+                             map_stride_bytes);
     if (rc != DDDMR_OK) return rc;
-    for (int i = 0; i < 2; ++i) {
-      rc = grid_alloc(ctx, m->obs[i], 1u << 21, (uint32_t)N);
-      if (rc != DDDMR_OK) return rc;
-      HIPCHK(ctx, hipMalloc(&m->obs_copy[i], N * sizeof(float4)));
-    }
-    MarkStore& s = m->store;
-    HIPCHK(ctx, hipMalloc(&s.keys, (size_t)table * sizeof(unsigned long long)));
-    HIPCHK(ctx, hipMalloc(&s.alive, (size_t)table * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&s.pts_ofs, (size_t)table * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&s.pts_n, (size_t)table * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&s.removed_seq, (size_t)table * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&s.owner, (size_t)table * sizeof(unsigned long long)));
-    HIPCHK(ctx, hipMalloc(&s.alive_list, (size_t)table * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&s.removed_list, (size_t)table * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&s.fov_flag, (size_t)table * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&s.pool, (size_t)m->pool_cap * sizeof(float4)));
-    HIPCHK(ctx, hipMalloc(&m->pool_alt, (size_t)m->pool_cap * sizeof(float4)));
-    HIPCHK(ctx, hipMalloc(&m->keys_alt, (size_t)table * sizeof(unsigned long long)));
-    HIPCHK(ctx, hipMalloc(&m->alive_alt, (size_t)table * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->pts_ofs_alt, (size_t)table * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->pts_n_alt, (size_t)table * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&s.dgraph, ((size_t)n_ground + 1) * sizeof(double)));
-    HIPCHK(ctx, hipMalloc(&s.lethal, (size_t)n_ground + 1));
-    HIPCHK(ctx, hipMalloc(&m->gslot, N * sizeof(uint2)));
-    HIPCHK(ctx, hipMalloc(&m->parent, N * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->keys_a, N * sizeof(unsigned long long)));
-    HIPCHK(ctx, hipMalloc(&m->keys_b, N * sizeof(unsigned long long)));
-    HIPCHK(ctx, hipMalloc(&m->keys1, N * sizeof(unsigned long long)));
-    HIPCHK(ctx, hipMalloc(&m->vals_a, N * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->vals_b, N * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->flags, N * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->incl, N * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->cid_incl, N * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->ds, N * sizeof(float4)));
-    HIPCHK(ctx, hipMalloc(&m->proj, N * sizeof(float4)));
-    HIPCHK(ctx, hipMalloc(&m->gen, N * sizeof(float4)));
-    HIPCHK(ctx, hipMalloc(&m->ds_first, N * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->pool_ofs, N * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->compact_sizes, (size_t)table * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->compact_ofs, (size_t)table * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->cl.start, (N + 1) * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->cl.size, N * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->cl.centroid, N * sizeof(float4)));
-    HIPCHK(ctx, hipMalloc(&m->cl.state, N * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->cl.ds_count, N * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->cl.gen_first, N * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->cl.gen_count, N * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->cl.slot, N * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->cl.vkey, 3 * N * sizeof(int)));
-    HIPCHK(ctx, hipMalloc(&m->counters, sizeof(MarkCounters)));
-    HIPCHK(ctx, hipMalloc(&m->n_groups, 2 * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->unmark_pts, (size_t)m->pool_cap * sizeof(float4)));
-    HIPCHK(ctx, hipMalloc(&m->band_pts, (size_t)2 * kBandMax * kBandCap * sizeof(float4)));
-    HIPCHK(ctx, hipMalloc(&m->band_cnt, (size_t)2 * kBandMax * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->hi_rank, (size_t)8 * (kFuseMaxObs - kFuseRegObs) * sizeof(uint32_t)));
+    for (int i = 0; i < 2; ++i)
+      if ((rc = grid_alloc(ctx, m->mem, m->obs[i], 1u << 21, (uint32_t)N)) != DDDMR_OK) return rc;
+    HIPCHK(ctx, dev_alloc(m->mem, &m->sc.cl.gen_first, N));
+    HIPCHK(ctx, dev_alloc(m->mem, &m->sc.cl.gen_count, N));
+    HIPCHK(ctx, dev_alloc(m->mem, &m->sc.cl.slot, N));
+    HIPCHK(ctx, dev_alloc(m->mem, &m->gslot, N));
+    HIPCHK(ctx, dev_alloc(m->mem, &m->proj, N));
+    HIPCHK(ctx, dev_alloc(m->mem, &m->gen, N));
+    HIPCHK(ctx, dev_alloc(m->mem, &m->pool_ofs, N));
+    HIPCHK(ctx, dev_alloc(m->mem, &m->unmark_pts, m->store.pool_cap));
+    HIPCHK(ctx, dev_alloc(m->mem, &m->band_pts, (size_t)2 * kBandMax * kBandCap));
+    HIPCHK(ctx, dev_alloc(m->mem, &m->band_cnt, (size_t)2 * kBandMax));
+    HIPCHK(ctx, dev_alloc(m->mem, &m->hi_rank, (size_t)8 * (kFuseMaxObs - kFuseRegObs)));
     HIPCHK(ctx, hipMemset(m->band_cnt, 0, (size_t)2 * kBandMax * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->clear_list, (size_t)table * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->cell_count, (size_t)kFuseMaxCells * sizeof(uint32_t)));
+    HIPCHK(ctx, dev_alloc(m->mem, &m->cell_count, kFuseMaxCells));
     HIPCHK(ctx, hipMemset(m->cell_count, 0, (size_t)kFuseMaxCells * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&m->ticket, 34 * sizeof(uint32_t)));
+    HIPCHK(ctx, dev_alloc(m->mem, &m->ticket, 34));
     HIPCHK(ctx, hipMemset(m->ticket, 0, 34 * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMemset(m->counters, 0, sizeof(MarkCounters)));
     HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&m->host_out), sizeof(MarkCounters), hipHostMallocMapped));
     HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&m->host_out_dev), m->host_out, 0));
     if (const char* e = std::getenv("DDDMR_MKF_UNMARK")) m->unmark_with_groups = std::strcmp(e, "roots") != 0;
@@ -425,26 +400,13 @@ int dddmr_rollout_marking_reset(dddmr_rollout_ctx* ctx) {
 }  // extern "C"
 
 namespace {
-// MultiLayerSpinningLidar::resetdGraph (:831-839): empty store, dGraph = max_obstacle_distance on keys 0..n_ground
+// MultiLayerSpinningLidar::resetdGraph (:831-839)
 int marking_reset_locked(dddmr_rollout_ctx* ctx) {
   MarkingState* m = ctx->marking;
   if (!m) return fail(ctx, DDDMR_ERR_STATE, "marking_reset before marking_create");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  MarkStore& s = m->store;
-  const size_t t = m->table;
-  HIPCHK(ctx, hipMemsetAsync(s.keys, 0, t * sizeof(unsigned long long), ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(s.alive, 0, t * sizeof(uint32_t), ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(s.pts_ofs, 0, t * sizeof(uint32_t), ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(s.pts_n, 0, t * sizeof(uint32_t), ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(s.removed_seq, 0, t * sizeof(uint32_t), ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(s.owner, 0, t * sizeof(unsigned long long), ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(s.lethal, 0, (size_t)m->n_ground + 1, ctx->stream));
-  hipLaunchKernelGGL(k_mk_fill_dgraph, dim3((m->n_ground + 1 + 255) / 256), dim3(256), 0, ctx->stream, m->n_ground + 1, s.dgraph,
-                     m->cfg.max_obstacle_distance);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  m->pool_used_host = 0;
-  m->n_alive_host = 0;
-  m->keys_used_host = 0;
+  const int rc = store_reset(ctx, m->store, ctx->stream, m->cfg.max_obstacle_distance);
+  if (rc != DDDMR_OK) return rc;
   m->counters_clean = false;
   m->alive_list_stale = false;               // (nothing alive: the empty list is right)
   // (pcl_msg_gbl_ is untouched by resetdGraph: the previous observation stays)
@@ -459,33 +421,12 @@ struct UpdateFrame {          // host-side inputs of one update besides the kern
 
 #define MK_LAUNCH(m, ...) do { hipLaunchKernelGGL(__VA_ARGS__); ++(m)->launches_last; } while (0)
 
-// Store garbage collection when half the table holds keys and a good part of them is dead; pool compaction when half
-// of the pool is garbage-or-used.  Both rare; both leave the device counters consistent for either route.
-int store_maintenance(dddmr_rollout_ctx* ctx, MarkingState* m, hipStream_t st) {
-  MarkStore& s = m->store;
-  if (m->keys_used_host > m->table / 2 && m->keys_used_host > m->n_alive_host + m->table / 8) {
-    const size_t t = m->table;
-    HIPCHK(ctx, hipMemsetAsync(m->keys_alt, 0, t * sizeof(unsigned long long), st));
-    HIPCHK(ctx, hipMemsetAsync(m->alive_alt, 0, t * sizeof(uint32_t), st));
-    HIPCHK(ctx, hipMemsetAsync(m->pts_ofs_alt, 0, t * sizeof(uint32_t), st));
-    HIPCHK(ctx, hipMemsetAsync(m->pts_n_alt, 0, t * sizeof(uint32_t), st));
-    MK_LAUNCH(m, k_mk_rehash, dim3((m->table + 255) / 256), dim3(256), 0, st, m->table - 1, s, m->keys_alt, m->alive_alt,
-              m->pts_ofs_alt, m->pts_n_alt, m->counters);
-    std::swap(s.keys, m->keys_alt);
-    std::swap(s.alive, m->alive_alt);
-    std::swap(s.pts_ofs, m->pts_ofs_alt);
-    std::swap(s.pts_n, m->pts_n_alt);
-    m->keys_used_host = m->n_alive_host;
-  }
-  if (m->pool_used_host > m->pool_cap / 2) {
-    MK_LAUNCH(m, k_mk_compact_sizes, dim3((m->table + 255) / 256), dim3(256), 0, st, m->table, s, m->compact_sizes);
-    size_t tb = m->temp_bytes;
-    HIPCHK(ctx, rocprim::exclusive_scan(m->temp, tb, m->compact_sizes, m->compact_ofs, 0u, (size_t)m->table, rocprim::plus<uint32_t>(), st));
-    HIPCHK(ctx, hipMemsetAsync(&m->counters->pool_used, 0, sizeof(uint32_t), st));
-    MK_LAUNCH(m, k_mk_compact_move, dim3((m->table + 3) / 4), dim3(256), 0, st, m->table, s, m->compact_ofs, m->pool_alt, m->counters);
-    std::swap(s.pool, m->pool_alt);
-  }
-  return DDDMR_OK;
+// the store's housekeeping (rare); its kernels count as launches of the update
+int marking_maintenance(dddmr_rollout_ctx* ctx, MarkingState* m, hipStream_t st) {
+  StoreOps ops;
+  const int runs = store_maintenance(ctx, m->store, st, m->sc.temp, m->sc.temp_bytes, ops);
+  m->launches_last += ops.kernels;
+  return runs < 0 ? runs : DDDMR_OK;
 }
 
 // the crop box of the feed (base frame |x|,|y| <= window, z in [0, marking_height]) in the global frame, + 0.3 m
@@ -513,57 +454,57 @@ void obs_grid_shape(const MarkingState* m, const UpdateFrame& f, uint32_t cap_ce
 // selfMark of this observation, general route: rocPRIM sorts, any observation size (marking.hip.h)
 int mark_general(dddmr_rollout_ctx* ctx, MarkingState* m, const UpdateFrame& f, const float4* obs, uint32_t n_obs, hipStream_t st) {
   const MarkParams& k = f.k;
-  MarkStore& s = m->store;
+  MarkStore& s = m->store.s;
   const int cur = m->prev >= 0 ? 1 - m->prev : 0;
   GridBuf& gb = m->obs[cur];
   float lo[3], hi[3];
   obs_grid_shape(m, f, gb.cap_cells, gb.g, lo, hi);
   const float4* pts = obs;                   // (the cloud buffer stays pinned until the update returns)
-  int rc = grid_build(ctx, m, gb, pts, n_obs, m->gslot, st);
+  int rc = grid_build(ctx, m->sc.temp, m->sc.temp_bytes, gb, pts, n_obs, m->gslot, st);
   m->launches_last += 5;                     // memset, count, rocPRIM scan (2 kernels), scatter
   if (rc != DDDMR_OK) return rc;
   const dim3 pb((n_obs + 255) / 256), cb((n_obs + 63) / 64);
   // Euclidean clusters
-  MK_LAUNCH(m, k_mk_cc_init, pb, dim3(256), 0, st, n_obs, m->parent);
-  MK_LAUNCH(m, k_mk_cc_union, pb, dim3(256), 0, st, k, gb.g, pts, m->parent);
-  MK_LAUNCH(m, k_mk_cc_keys, pb, dim3(256), 0, st, n_obs, m->parent, m->keys_a);
-  size_t tb = m->temp_bytes;
-  HIPCHK(ctx, rocprim::radix_sort_keys(m->temp, tb, m->keys_a, m->keys1, (size_t)n_obs, 0, 40, st));
-  MK_LAUNCH(m, k_mk_flags, pb, dim3(256), 0, st, n_obs, m->keys1, 20, m->flags);
-  tb = m->temp_bytes;
-  HIPCHK(ctx, rocprim::inclusive_scan(m->temp, tb, m->flags, m->cid_incl, (size_t)n_obs, rocprim::plus<uint32_t>(), st));
-  MK_LAUNCH(m, k_mk_cluster_starts, pb, dim3(256), 0, st, n_obs, m->flags, m->cid_incl, m->cl, m->counters);
-  MK_LAUNCH(m, k_mk_cluster_stage1, cb, dim3(64), 0, st, k, m->counters, m->cl, m->keys1, pts, m->ground.g);
+  MK_LAUNCH(m, k_mk_cc_init, pb, dim3(256), 0, st, n_obs, m->sc.parent);
+  MK_LAUNCH(m, k_mk_cc_union, pb, dim3(256), 0, st, k, gb.g, pts, m->sc.parent);
+  MK_LAUNCH(m, k_mk_cc_keys, pb, dim3(256), 0, st, n_obs, m->sc.parent, m->sc.keys_a);
+  size_t tb = m->sc.temp_bytes;
+  HIPCHK(ctx, rocprim::radix_sort_keys(m->sc.temp, tb, m->sc.keys_a, m->sc.keys1, (size_t)n_obs, 0, 40, st));
+  MK_LAUNCH(m, k_mk_flags, pb, dim3(256), 0, st, n_obs, m->sc.keys1, 20, m->sc.flags);
+  tb = m->sc.temp_bytes;
+  HIPCHK(ctx, rocprim::inclusive_scan(m->sc.temp, tb, m->sc.flags, m->sc.cid_incl, (size_t)n_obs, rocprim::plus<uint32_t>(), st));
+  MK_LAUNCH(m, k_mk_cluster_starts, pb, dim3(256), 0, st, n_obs, m->sc.flags, m->sc.cid_incl, m->sc.cl, m->store.counters);
+  MK_LAUNCH(m, k_mk_cluster_stage1, cb, dim3(64), 0, st, k, m->store.counters, m->sc.cl, m->sc.keys1, pts, m->grids.ground.g);
   // 0.2 m VoxelGrid of every surviving cluster: stable sort by (cluster, voxel), one lane per voxel
   // (voxel indices are keyed relative to the window's centre - half the key range: an observation handed over uncropped may reach far
   // beyond the window -- a margin of 16 voxels around the crop box used to drop such points without a word)
   const float mid[3] = {0.5f * (lo[0] + hi[0]), 0.5f * (lo[1] + hi[1]), 0.5f * (lo[2] + hi[2])};
   const int ox2 = (int)std::floor(mid[0] / 0.2f) - kVgHalfXY, oy2 = (int)std::floor(mid[1] / 0.2f) - kVgHalfXY, oz2 = (int)std::floor(mid[2] / 0.2f) - kVgHalfZ;
-  MK_LAUNCH(m, k_mk_ds_keys, pb, dim3(256), 0, st, k, m->keys1, m->cid_incl, m->cl, pts, ox2, oy2, oz2, m->keys_a, m->vals_a, m->counters);
-  tb = m->temp_bytes;
-  HIPCHK(ctx, rocprim::radix_sort_pairs(m->temp, tb, m->keys_a, m->keys_b, m->vals_a, m->vals_b, (size_t)n_obs, 0, 62, st));
-  MK_LAUNCH(m, k_mk_flags, pb, dim3(256), 0, st, n_obs, m->keys_b, 0, m->flags);
-  tb = m->temp_bytes;
-  HIPCHK(ctx, rocprim::inclusive_scan(m->temp, tb, m->flags, m->incl, (size_t)n_obs, rocprim::plus<uint32_t>(), st));
-  HIPCHK(ctx, hipMemsetAsync(m->ds_first, 0xFF, (size_t)n_obs * sizeof(uint32_t), st));
-  MK_LAUNCH(m, k_mk_group_reduce, cb, dim3(64), 0, st, n_obs, m->keys_b, m->vals_b, m->flags, m->incl, 0, m->keys1, pts, m->ds,
-            m->cl.ds_count, m->ds_first, m->n_groups);
-  MK_LAUNCH(m, k_mk_cluster_stage2, cb, dim3(64), 0, st, k, m->counters, m->cl, m->map.g, m->n_map);
+  MK_LAUNCH(m, k_mk_ds_keys, pb, dim3(256), 0, st, k, m->sc.keys1, m->sc.cid_incl, m->sc.cl, pts, ox2, oy2, oz2, m->sc.keys_a, m->sc.vals_a, m->store.counters);
+  tb = m->sc.temp_bytes;
+  HIPCHK(ctx, rocprim::radix_sort_pairs(m->sc.temp, tb, m->sc.keys_a, m->sc.keys_b, m->sc.vals_a, m->sc.vals_b, (size_t)n_obs, 0, 62, st));
+  MK_LAUNCH(m, k_mk_flags, pb, dim3(256), 0, st, n_obs, m->sc.keys_b, 0, m->sc.flags);
+  tb = m->sc.temp_bytes;
+  HIPCHK(ctx, rocprim::inclusive_scan(m->sc.temp, tb, m->sc.flags, m->sc.incl, (size_t)n_obs, rocprim::plus<uint32_t>(), st));
+  HIPCHK(ctx, hipMemsetAsync(m->sc.ds_first, 0xFF, (size_t)n_obs * sizeof(uint32_t), st));
+  MK_LAUNCH(m, k_mk_group_reduce, cb, dim3(64), 0, st, n_obs, m->sc.keys_b, m->sc.vals_b, m->sc.flags, m->sc.incl, 0, m->sc.keys1, pts, m->sc.ds,
+            m->sc.cl.ds_count, m->sc.ds_first, m->sc.n_groups);
+  MK_LAUNCH(m, k_mk_cluster_stage2, cb, dim3(64), 0, st, k, m->store.counters, m->sc.cl, m->grids.map.g, m->grids.n_map);
   // projection on the base plane + 0.1 m VoxelGrid of the accepted clusters -> generator points
   const int ox3 = (int)std::floor(mid[0] / 0.1f) - kVgHalfXY, oy3 = (int)std::floor(mid[1] / 0.1f) - kVgHalfXY, oz3 = (int)std::floor(mid[2] / 0.1f) - kVgHalfZ;
-  MK_LAUNCH(m, k_mk_proj_keys, pb, dim3(256), 0, st, k, m->n_groups, m->ds, m->cl, ox3, oy3, oz3, m->proj, m->keys_a, m->vals_a, n_obs, m->counters);
-  tb = m->temp_bytes;
-  HIPCHK(ctx, rocprim::radix_sort_pairs(m->temp, tb, m->keys_a, m->keys_b, m->vals_a, m->vals_b, (size_t)n_obs, 0, 62, st));
-  MK_LAUNCH(m, k_mk_flags, pb, dim3(256), 0, st, n_obs, m->keys_b, 0, m->flags);
-  tb = m->temp_bytes;
-  HIPCHK(ctx, rocprim::inclusive_scan(m->temp, tb, m->flags, m->incl, (size_t)n_obs, rocprim::plus<uint32_t>(), st));
-  MK_LAUNCH(m, k_mk_group_reduce, cb, dim3(64), 0, st, n_obs, m->keys_b, m->vals_b, m->flags, m->incl, 1, m->keys1, m->proj, m->gen,
-            m->cl.gen_count, m->cl.gen_first, m->n_groups + 1);
+  MK_LAUNCH(m, k_mk_proj_keys, pb, dim3(256), 0, st, k, m->sc.n_groups, m->sc.ds, m->sc.cl, ox3, oy3, oz3, m->proj, m->sc.keys_a, m->sc.vals_a, n_obs, m->store.counters);
+  tb = m->sc.temp_bytes;
+  HIPCHK(ctx, rocprim::radix_sort_pairs(m->sc.temp, tb, m->sc.keys_a, m->sc.keys_b, m->sc.vals_a, m->sc.vals_b, (size_t)n_obs, 0, 62, st));
+  MK_LAUNCH(m, k_mk_flags, pb, dim3(256), 0, st, n_obs, m->sc.keys_b, 0, m->sc.flags);
+  tb = m->sc.temp_bytes;
+  HIPCHK(ctx, rocprim::inclusive_scan(m->sc.temp, tb, m->sc.flags, m->sc.incl, (size_t)n_obs, rocprim::plus<uint32_t>(), st));
+  MK_LAUNCH(m, k_mk_group_reduce, cb, dim3(64), 0, st, n_obs, m->sc.keys_b, m->sc.vals_b, m->sc.flags, m->sc.incl, 1, m->sc.keys1, m->proj, m->gen,
+            m->sc.cl.gen_count, m->sc.cl.gen_first, m->sc.n_groups + 1);
   m->launches_last += 3 * 10 + 2 * 3 + 1;   // rocPRIM: three sorts (block sort + ~8 merge passes + id wrapper), three scans, memset
   // addPCPtr
-  MK_LAUNCH(m, k_mk_slots, cb, dim3(64), 0, st, k, m->counters, m->cl, s, m->counters);
-  MK_LAUNCH(m, k_mk_commit, cb, dim3(64), 0, st, k, m->counters, m->cl, s, m->counters, m->pool_ofs);
-  MK_LAUNCH(m, k_mk_dgraph, dim3((n_obs + 3) / 4), dim3(256), 0, st, k, m->n_groups + 1, m->gen, m->cl, m->pool_ofs, s, m->ground.g);
+  MK_LAUNCH(m, k_mk_slots, cb, dim3(64), 0, st, k, m->store.counters, m->sc.cl, s, m->store.counters);
+  MK_LAUNCH(m, k_mk_commit, cb, dim3(64), 0, st, k, m->store.counters, m->sc.cl, s, m->store.head, m->store.counters, (uint32_t*)nullptr, m->pool_ofs);
+  MK_LAUNCH(m, k_mk_dgraph, dim3((n_obs + 3) / 4), dim3(256), 0, st, k, m->sc.n_groups + 1, m->gen, m->sc.cl, m->pool_ofs, s, m->grids.ground.g);
   m->prev = cur;                                                               // pcl_msg_gbl_ of this selfMark
   m->n_prev = n_obs;
   return DDDMR_OK;
@@ -574,35 +515,35 @@ int update_general(dddmr_rollout_ctx* ctx, MarkingState* m, const UpdateFrame& f
                    MarkCounters& out) {
   hipStream_t st = m->cur;
   const MarkParams& k = f.k;
-  MarkStore& s = m->store;
+  MarkStore& s = m->store.s;
   MarkCounters zero{};
-  zero.pool_used = m->pool_used_host;
-  HIPCHK(ctx, hipMemcpyAsync(m->counters, &zero, sizeof(zero), hipMemcpyHostToDevice, st));   // (pageable source: copied before return)
+  zero.pool_used = m->store.pool_used;
+  HIPCHK(ctx, hipMemcpyAsync(m->store.counters, &zero, sizeof(zero), hipMemcpyHostToDevice, st));   // (pageable source: copied before return)
   m->counters_clean = false;
   if (timed) HIPCHK(ctx, hipEventRecord(m->e0, st));
-  int rc = store_maintenance(ctx, m, st);
+  int rc = marking_maintenance(ctx, m, st);
   if (rc != DDDMR_OK) return rc;
   if (m->alive_list_stale) {                 // the last update ran fused: what selfClear walks has to be listed first
-    MK_LAUNCH(m, k_mk_finish, dim3((m->table + 255) / 256), dim3(256), 0, st, k, s, m->counters);
-    HIPCHK(ctx, hipMemsetAsync(&m->counters->n_alive, 0, sizeof(uint32_t), st));
+    MK_LAUNCH(m, k_mk_finish, dim3((m->store.table + 255) / 256), dim3(256), 0, st, k, s, m->store.counters);
+    HIPCHK(ctx, hipMemsetAsync(&m->store.counters->n_alive, 0, sizeof(uint32_t), st));
     m->alive_list_stale = false;
   }
   // ---- selfClear against the previous observation ----
   const PointGrid empty_grid = m->obs[0].g;
   const PointGrid& prev_grid = m->prev >= 0 ? m->obs[m->prev].g : empty_grid;
-  if (m->n_alive_host > 0) {
-    MK_LAUNCH(m, k_mk_fov, dim3((m->n_alive_host + 255) / 256), dim3(256), 0, st, k, s, m->counters);
-    MK_LAUNCH(m, k_mk_clear, dim3((m->n_alive_host + 3) / 4), dim3(256), 0, st, k, s, prev_grid, m->counters);
-    MK_LAUNCH(m, k_mk_unmark, dim3((m->n_alive_host + 3) / 4), dim3(256), 0, st, k, s, m->ground.g, m->counters);
+  if (m->store.n_alive > 0) {
+    MK_LAUNCH(m, k_mk_fov, dim3((m->store.n_alive + 255) / 256), dim3(256), 0, st, k, s, m->store.counters);
+    MK_LAUNCH(m, k_mk_clear, dim3((m->store.n_alive + 3) / 4), dim3(256), 0, st, k, s, prev_grid, m->store.counters);
+    MK_LAUNCH(m, k_mk_unmark, dim3((m->store.n_alive + 3) / 4), dim3(256), 0, st, k, s, m->grids.ground.g, m->store.counters);
   }
   if (timed) HIPCHK(ctx, hipEventRecord(m->e1, st));
   if (n_obs > 5) {                                                               // :320-321
     rc = mark_general(ctx, m, f, obs, n_obs, st);
     if (rc != DDDMR_OK) return rc;
   }
-  MK_LAUNCH(m, k_mk_finish, dim3((m->table + 255) / 256), dim3(256), 0, st, k, s, m->counters);
+  MK_LAUNCH(m, k_mk_finish, dim3((m->store.table + 255) / 256), dim3(256), 0, st, k, s, m->store.counters);
   if (timed) HIPCHK(ctx, hipEventRecord(m->e2, st));
-  HIPCHK(ctx, hipMemcpyAsync(&out, m->counters, sizeof(out), hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(&out, m->store.counters, sizeof(out), hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
   HIPCHK(ctx, hipGetLastError());
   ++m->updates_general;
@@ -614,16 +555,16 @@ int update_fused(dddmr_rollout_ctx* ctx, MarkingState* m, const UpdateFrame& f, 
                  MarkCounters& out) {
   hipStream_t st = m->cur;
   const MarkParams& k = f.k;
-  MarkStore& s = m->store;
+  MarkStore& s = m->store.s;
   if (!m->counters_clean) {
     MarkCounters zero{};
-    zero.pool_used = m->pool_used_host;
-    HIPCHK(ctx, hipMemcpyAsync(m->counters, &zero, sizeof(zero), hipMemcpyHostToDevice, st));
+    zero.pool_used = m->store.pool_used;
+    HIPCHK(ctx, hipMemcpyAsync(m->store.counters, &zero, sizeof(zero), hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemsetAsync(m->ticket, 0, 34 * sizeof(uint32_t), st));
   }
   m->counters_clean = false;                 // (until this update's last block has run)
   if (timed) HIPCHK(ctx, hipEventRecord(m->e0, st));
-  int rc = store_maintenance(ctx, m, st);
+  int rc = marking_maintenance(ctx, m, st);
   if (rc != DDDMR_OK) return rc;
   const bool mark = n_obs > 5;                                                   // :320-321
   const int cur = m->prev >= 0 ? 1 - m->prev : 0;
@@ -636,24 +577,24 @@ int update_fused(dddmr_rollout_ctx* ctx, MarkingState* m, const UpdateFrame& f, 
     obs_grid_shape(m, f, cap, gb.g, lo, hi);
     gb.g.n = n_obs;
   }
-  const uint32_t n_alive = m->n_alive_host;
+  const uint32_t n_alive = m->store.n_alive;
   // ground cells of the window + inflation radius: the nodes the node-by-node dGraph updates look at
   SplatRange rg{};
   {
     float lo[3], hi[3];
     crop_box(m, f, lo, hi);
-    const PointGrid& gg = m->ground.g;
+    const PointGrid& gg = m->grids.ground.g;
     const float pad = (float)m->cfg.inflation_radius + 0.05f;
     rg.cx0 = host_cx(gg, lo[0] - pad); rg.cx1 = host_cx(gg, hi[0] + pad);
     rg.cy0 = host_cy(gg, lo[1] - pad); rg.cy1 = host_cy(gg, hi[1] + pad);
     rg.rows = (uint32_t)(rg.cy1 - rg.cy0 + 1) * (uint32_t)gg.nz;
-    rg.segs = std::max(1u, (m->ground.max_row + 63u) / 64u);
+    rg.segs = std::max(1u, (m->grids.ground.max_row + 63u) / 64u);
     rg.delta = (int)std::floor(((float)m->cfg.inflation_radius + 1e-3f) * gg.inv_xy) + 1;
-    rg.bands = (m->n_ground && (uint32_t)(rg.cy1 - rg.cy0 + 1) <= kBandMax) ? (uint32_t)(rg.cy1 - rg.cy0 + 1) : 0u;
+    rg.bands = (m->grids.n_ground && (uint32_t)(rg.cy1 - rg.cy0 + 1) <= kBandMax) ? (uint32_t)(rg.cy1 - rg.cy0 + 1) : 0u;
   }
-  FuseBufs fb{obs, m->parent, m->ds, m->gen, m->clear_list, m->unmark_pts,
+  FuseBufs fb{obs, m->sc.parent, m->sc.ds, m->gen, m->store.clear_list, m->unmark_pts,
               BandList{m->band_pts, m->band_cnt}, BandList{m->band_pts + (size_t)kBandMax * kBandCap, m->band_cnt + kBandMax}, rg,
-              m->ticket, m->cell_count, m->keys_a, m->host_out_dev, m->grid_in_lds ? 1u : 0u, m->hi_rank};
+              m->ticket, m->cell_count, m->sc.keys_a, m->host_out_dev, m->grid_in_lds ? 1u : 0u, m->hi_rank};
   // Blocks that share one row segment's bands in the commit launch: a block takes every n_part-th 256-point chunk of the
   // 2 delta + 1 bands in reach, so more blocks than chunks only add blocks that read the band counts and leave (measured at
   // C5M, ~110 points per band, 9 bands in reach: n_part 48 / 24 / 16 / 12 / 8 -> mark phase 80 / 68 / 68 / 66 / 67 us).
@@ -667,7 +608,7 @@ int update_fused(dddmr_rollout_ctx* ctx, MarkingState* m, const UpdateFrame& f, 
   const uint32_t seg_groups = (rg.segs + 3u) / 4u;
   if (m->seq == 3 && std::getenv("DDDMR_DEBUG_GRID"))
     std::fprintf(stderr, "[dddmr] marking update: %u points, %u alive; window rows %u x %u segments, %u bands, delta %d -> %u blocks per row segment\n",
-                 n_obs, m->n_alive_host, rg.rows, rg.segs, rg.bands, rg.delta, n_part);
+                 n_obs, m->store.n_alive, rg.rows, rg.segs, rg.bands, rg.delta, n_part);
   const uint32_t nb_band = rg.bands ? rg.rows * seg_groups * n_part : 0u;
   // (DDDMR_MKF_GRID=global only) cell counts of the observation grid
   const bool big = n_obs > kFuseRegObs;          // (the count launch's form of the grid only takes kFuseRegObs points)
@@ -675,8 +616,8 @@ int update_fused(dddmr_rollout_ctx* ctx, MarkingState* m, const UpdateFrame& f, 
   // grid launch: the observation grid (built in LDS by the first grid_parts workgroups) | every store slot: window + FOV test -> ray-test list
   {
     const uint32_t nb_grid = mark ? ((m->grid_in_lds || big) ? m->grid_parts : 1u) : 0u;
-    if (big) MK_LAUNCH(m, k_mkf_grid_fov<true>, dim3(nb_grid + (m->table + 1023) / 1024), dim3(1024), 0, st, k, s, gb.g, fb, m->counters, nb_grid);
-    else MK_LAUNCH(m, k_mkf_grid_fov<false>, dim3(nb_grid + (m->table + 1023) / 1024), dim3(1024), 0, st, k, s, gb.g, fb, m->counters, nb_grid);
+    if (big) MK_LAUNCH(m, k_mkf_grid_fov<true>, dim3(nb_grid + (m->store.table + 1023) / 1024), dim3(1024), 0, st, k, s, gb.g, fb, m->store.counters, nb_grid);
+    else MK_LAUNCH(m, k_mkf_grid_fov<false>, dim3(nb_grid + (m->store.table + 1023) / 1024), dim3(1024), 0, st, k, s, gb.g, fb, m->store.counters, nb_grid);
   }
 #ifdef DDDMR_PHASE_STAMPS
   if (const char* e = std::getenv("DDDMR_MKF_EXP")) { const int v = (std::atoi(e) & 128) ? 1 : 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(dddmr::g_mk_exp_noprobe), &v, sizeof(v)); }
@@ -688,7 +629,7 @@ int update_fused(dddmr_rollout_ctx* ctx, MarkingState* m, const UpdateFrame& f, 
   if (const char* e = std::getenv("DDDMR_MKF_EXP")) { if (std::atoi(e) & 1) nb_cc = 0; if (std::atoi(e) & 2) nb_clear = 0; }
 #endif
   if (nb_clear + nb_cc)
-    MK_LAUNCH(m, k_mkf_clear_cc, dim3(nb_clear + nb_cc), dim3(256), 0, st, k, s, prev_grid, gb.g, m->ground.g, fb, m->counters, nb_clear);
+    MK_LAUNCH(m, k_mkf_clear_cc, dim3(nb_clear + nb_cc), dim3(256), 0, st, k, s, prev_grid, gb.g, m->grids.ground.g, fb, m->store.counters, nb_clear);
   if (timed) HIPCHK(ctx, hipEventRecord(m->e1, st));
   uint32_t nb_un_groups = 0, nb_band_groups = 0;
   // seed launch: seeds (| removePCPtr of the cleared markings when it does not ride in the partition launch)
@@ -701,20 +642,20 @@ int update_fused(dddmr_rollout_ctx* ctx, MarkingState* m, const UpdateFrame& f, 
 #endif
     if (mark && m->unmark_with_groups) { nb_un_groups = nb_un + nb_walk; nb_band_groups = nb_un; nb_un = 0; nb_walk = 0; }
     if (nb_roots + nb_un + nb_walk)
-      MK_LAUNCH(m, k_mkf_roots_unmark, dim3(nb_roots + nb_un + nb_walk), dim3(256), 0, st, k, fb, m->cl, s, m->ground.g, m->counters, nb_roots,
+      MK_LAUNCH(m, k_mkf_roots_unmark, dim3(nb_roots + nb_un + nb_walk), dim3(256), 0, st, k, fb, m->sc.cl, s, m->grids.ground.g, m->store.counters, nb_roots,
                 nb_un, seg_groups, n_part_un);
   }
   // partition launch: 64 partitions of the clusters | removePCPtr: ground node by ground node, point by point for the points that found no band
   if (mark)
-    MK_LAUNCH(m, k_mkf_groups, dim3(kFuseParts + nb_un_groups), dim3(kPartThreads), kPartLdsBytes, st, k, fb, m->cl, s, m->ground.g, m->map.g, m->n_map,
-              m->counters, nb_band_groups, seg_groups, m->unmark_parts);
+    MK_LAUNCH(m, k_mkf_groups, dim3(kFuseParts + nb_un_groups), dim3(kPartThreads), kPartLdsBytes, st, k, fb, m->sc.cl, s, m->grids.ground.g, m->grids.map.g, m->grids.n_map,
+              m->store.counters, nb_band_groups, seg_groups, m->unmark_parts);
   // commit launch: keepers -> pool | dGraph of the new generator points (node by node); the last block publishes the counters
   {
     uint32_t nb_commit = mark ? (n_obs + 255) / 256 : 0, nb_b = mark ? nb_band : 0u, nb_walk = mark ? 256u : 1u;
 #ifdef DDDMR_PHASE_STAMPS
     if (const char* e = std::getenv("DDDMR_MKF_EXP")) { if (std::atoi(e) & 4) nb_commit = 0; if (std::atoi(e) & 8) nb_b = 0; if (std::atoi(e) & 16) nb_walk = 1; }
 #endif
-    MK_LAUNCH(m, k_mkf_commit_dgraph, dim3(nb_commit + nb_b + nb_walk), dim3(256), 0, st, k, fb, m->cl, s, m->ground.g, m->counters, nb_commit,
+    MK_LAUNCH(m, k_mkf_commit_dgraph, dim3(nb_commit + nb_b + nb_walk), dim3(256), 0, st, k, fb, m->sc.cl, s, m->grids.ground.g, m->store.counters, nb_commit,
               nb_b, seg_groups, n_part);
   }
   if (timed) HIPCHK(ctx, hipEventRecord(m->e2, st));
@@ -737,16 +678,16 @@ int update_fused(dddmr_rollout_ctx* ctx, MarkingState* m, const UpdateFrame& f, 
   // has reached the store but keys and claims, and the mark phase is redone on the general route.
   --m->updates_fused;
   m->counters_clean = false;
-  HIPCHK(ctx, hipMemsetAsync(s.owner, 0, (size_t)m->table * sizeof(unsigned long long), st));
+  HIPCHK(ctx, hipMemsetAsync(s.owner, 0, (size_t)m->store.table * sizeof(unsigned long long), st));
   MarkCounters zero{};
   zero.pool_used = out.pool_used;
-  HIPCHK(ctx, hipMemcpyAsync(m->counters, &zero, sizeof(zero), hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(m->store.counters, &zero, sizeof(zero), hipMemcpyHostToDevice, st));
   rc = mark_general(ctx, m, f, obs, n_obs, st);
   if (rc != DDDMR_OK) return rc;
-  MK_LAUNCH(m, k_mk_finish, dim3((m->table + 255) / 256), dim3(256), 0, st, k, s, m->counters);
+  MK_LAUNCH(m, k_mk_finish, dim3((m->store.table + 255) / 256), dim3(256), 0, st, k, s, m->store.counters);
   if (timed) HIPCHK(ctx, hipEventRecord(m->e2, st));
   MarkCounters g{};
-  HIPCHK(ctx, hipMemcpyAsync(&g, m->counters, sizeof(g), hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(&g, m->store.counters, sizeof(g), hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
   HIPCHK(ctx, hipGetLastError());
   g.n_in_window = out.n_in_window; g.n_cleared = out.n_cleared; g.n_removed = out.n_removed; g.n_rehashed = out.n_rehashed;
@@ -819,14 +760,6 @@ int dddmr_rollout_marking_update(dddmr_rollout_ctx* ctx, const double T_base_sen
   quat_rotate_z(qs, k.sn);
   for (int i = 0; i < 3; ++i) k.st[i] = ts[i];
   k.sd = -ts[0] * k.sn[0] - ts[1] * k.sn[1] - ts[2] * k.sn[2];
-  {
-    const double qb[4] = {T_gbl_base[3], T_gbl_base[4], T_gbl_base[5], T_gbl_base[6]};
-    double nb[3];
-    quat_rotate_z(qb, nb);
-    k.mc[0] = (float)nb[0]; k.mc[1] = (float)nb[1]; k.mc[2] = (float)nb[2];
-    const double d = -T_gbl_base[0] * nb[0] - T_gbl_base[1] * nb[1] - T_gbl_base[2] * nb[2];
-    k.mc[3] = (float)d;
-  }
   k.res = c.xy_resolution; k.hres = c.height_resolution; k.marking_height = c.marking_height; k.window = c.perception_window_size;
   k.fov_top = c.vertical_FOV_top; k.fov_bottom = c.vertical_FOV_bottom;
   k.ps = c.scan_effective_positive_start; k.pe = c.scan_effective_positive_end;
@@ -835,20 +768,15 @@ int dddmr_rollout_marking_update(dddmr_rollout_ctx* ctx, const double T_base_sen
   k.tol = (float)c.euclidean_cluster_extraction_tolerance;
   k.tol2 = static_cast<float>(c.euclidean_cluster_extraction_tolerance * c.euclidean_cluster_extraction_tolerance);
   k.min_cluster = c.euclidean_cluster_extraction_min_cluster_size;
-  k.wx0 = (int)((T_gbl_base[0] - c.perception_window_size) / c.xy_resolution);      // :489-496
-  k.wx1 = (int)((T_gbl_base[0] + c.perception_window_size) / c.xy_resolution);
-  k.wy0 = (int)((T_gbl_base[1] - c.perception_window_size) / c.xy_resolution);
-  k.wy1 = (int)((T_gbl_base[1] + c.perception_window_size) / c.xy_resolution);
-  k.wz0 = (int)((T_gbl_base[2] - c.marking_height) / c.height_resolution);
-  k.wz1 = (int)((T_gbl_base[2] + c.marking_height) / c.height_resolution);
+  mark_params_pose(k, T_gbl_base);
   k.n_obs = n_obs;
   k.n_prev = m->prev >= 0 ? m->n_prev : 0;
   k.pad = 1e-4f;
   if (const char* e = std::getenv("DDDMR_MK_PAD")) k.pad = (float)std::atof(e);      // (diagnosis)
-  k.table_mask = m->table - 1;
-  k.pool_cap = m->pool_cap;
-  k.n_ground = m->n_ground;
-  k.n_alive_prev = m->n_alive_host;
+  k.table_mask = m->store.table - 1;
+  k.pool_cap = m->store.pool_cap;
+  k.n_ground = m->grids.n_ground;
+  k.n_alive_prev = m->store.n_alive;
   k.seq = ++m->seq;
   if (k.seq == 0) k.seq = m->seq = 1;
 
@@ -861,11 +789,11 @@ int dddmr_rollout_marking_update(dddmr_rollout_ctx* ctx, const double T_base_sen
     return fail(ctx, DDDMR_ERR_CAPACITY, "marking_update: DDDMR_MARKING_ROUTE=fused, observation of %u points > %u", n_obs, kFuseMaxObs);
   const int rc = fused ? update_fused(ctx, m, f, obs, n_obs, timed, out) : update_general(ctx, m, f, obs, n_obs, timed, out);
   if (rc != DDDMR_OK) return rc;
-  m->pool_used_host = out.pool_used;
-  m->n_alive_host = out.n_alive;
-  m->keys_used_host += out.n_new_keys;
+  m->store.pool_used = out.pool_used;
+  m->store.n_alive = out.n_alive;
+  m->store.keys_used += out.n_new_keys;
   if (out.n_dup > 0 && !out.overflow) {
-    const int rt = marking_fix_ties(ctx, m, k, m->store, out);
+    const int rt = marking_fix_ties(ctx, m, k, out);
     if (rt != DDDMR_OK) return rt;
   }
   if (timed) {
@@ -920,23 +848,7 @@ int dddmr_rollout_marking_get_voxels(dddmr_rollout_ctx* ctx, int32_t* xyz_out, s
   MarkingState* m = ctx->marking;
   if (!m) return fail(ctx, DDDMR_ERR_STATE, "marking_get_voxels before marking_create");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::vector<unsigned long long> keys(m->table);
-  std::vector<uint32_t> alive(m->table);
-  HIPCHK(ctx, hipMemcpy(keys.data(), m->store.keys, keys.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  HIPCHK(ctx, hipMemcpy(alive.data(), m->store.alive, alive.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  size_t cnt = 0;
-  for (size_t i = 0; i < keys.size(); ++i) {
-    if (!alive[i] || !keys[i]) continue;
-    if (xyz_out) {
-      if (cnt >= capacity) return fail(ctx, DDDMR_ERR_CAPACITY, "marking_get_voxels: capacity %zu too small", capacity);
-      int x, y, z;
-      voxel_unkey(keys[i], &x, &y, &z);
-      xyz_out[3 * cnt] = x; xyz_out[3 * cnt + 1] = y; xyz_out[3 * cnt + 2] = z;
-    }
-    ++cnt;
-  }
-  *n = cnt;
-  return DDDMR_OK;
+  return store_read_voxels(ctx, m->store, "marking_get_voxels", xyz_out, capacity, n);
 }
 
 // The generator points of every alive marking (the cluster projected on the robot's ground plane, 0.1 m VoxelGrid): what
@@ -948,28 +860,23 @@ int dddmr_rollout_marking_get_points(dddmr_rollout_ctx* ctx, float* xyz_out, int
   MarkingState* m = ctx->marking;
   if (!m) return fail(ctx, DDDMR_ERR_STATE, "marking_get_points before marking_create");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::vector<uint32_t> alive(m->table), ofs(m->table), cnt(m->table);
-  std::vector<unsigned long long> keys(m->table);
-  HIPCHK(ctx, hipMemcpy(keys.data(), m->store.keys, keys.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  HIPCHK(ctx, hipMemcpy(alive.data(), m->store.alive, alive.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  HIPCHK(ctx, hipMemcpy(ofs.data(), m->store.pts_ofs, ofs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  HIPCHK(ctx, hipMemcpy(cnt.data(), m->store.pts_n, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  std::vector<StoreSlot> slots;
+  int rc = store_read_slots(ctx, m->store, false, slots);
+  if (rc != DDDMR_OK) return rc;
   size_t total = 0;
-  for (size_t i = 0; i < alive.size(); ++i)
-    if (alive[i]) total += cnt[i];
+  for (const StoreSlot& sl : slots) total += sl.n;
   *n = total;
   if (!xyz_out) return DDDMR_OK;
   if (total > capacity) return fail(ctx, DDDMR_ERR_CAPACITY, "marking_get_points: capacity %zu < %zu", capacity, total);
-  std::vector<float4> pool(m->pool_used_host);
-  if (!pool.empty()) HIPCHK(ctx, hipMemcpy(pool.data(), m->store.pool, pool.size() * sizeof(float4), hipMemcpyDeviceToHost));
+  std::vector<float4> pool;
+  if ((rc = store_read_pool(ctx, m->store, pool)) != DDDMR_OK) return rc;
   size_t at = 0;
-  for (size_t i = 0; i < alive.size(); ++i) {
-    if (!alive[i]) continue;
-    for (uint32_t j = 0; j < cnt[i]; ++j, ++at) {
-      if ((size_t)ofs[i] + j >= pool.size()) return fail(ctx, DDDMR_ERR_STATE, "marking_get_points: slot %zu points past the pool", i);
-      const float4 p = pool[(size_t)ofs[i] + j];
+  for (const StoreSlot& sl : slots) {
+    if ((size_t)sl.ofs + sl.n > pool.size()) return fail(ctx, DDDMR_ERR_STATE, "marking_get_points: slot %zu points past the pool", sl.slot);
+    for (uint32_t j = 0; j < sl.n; ++j, ++at) {
+      const float4 p = pool[(size_t)sl.ofs + j];
       xyz_out[3 * at] = p.x; xyz_out[3 * at + 1] = p.y; xyz_out[3 * at + 2] = p.z;
-      if (voxel_out) voxel_unkey(keys[i], &voxel_out[3 * at], &voxel_out[3 * at + 1], &voxel_out[3 * at + 2]);
+      if (voxel_out) voxel_unkey(sl.key, &voxel_out[3 * at], &voxel_out[3 * at + 1], &voxel_out[3 * at + 2]);
     }
   }
   return DDDMR_OK;
@@ -980,10 +887,8 @@ int dddmr_rollout_marking_get_dgraph(dddmr_rollout_ctx* ctx, double* values_out,
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   MarkingState* m = ctx->marking;
   if (!m) return fail(ctx, DDDMR_ERR_STATE, "marking_get_dgraph before marking_create");
-  if (capacity < (size_t)m->n_ground + 1) return fail(ctx, DDDMR_ERR_CAPACITY, "marking_get_dgraph: capacity %zu < %u", capacity, m->n_ground + 1);
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, hipMemcpy(values_out, m->store.dgraph, ((size_t)m->n_ground + 1) * sizeof(double), hipMemcpyDeviceToHost));
-  return DDDMR_OK;
+  return store_read_dgraph(ctx, m->store, "marking_get_dgraph", values_out, capacity);
 }
 
 int dddmr_rollout_marking_get_lethal(dddmr_rollout_ctx* ctx, uint8_t* flags_out, size_t capacity) {
@@ -991,10 +896,8 @@ int dddmr_rollout_marking_get_lethal(dddmr_rollout_ctx* ctx, uint8_t* flags_out,
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   MarkingState* m = ctx->marking;
   if (!m) return fail(ctx, DDDMR_ERR_STATE, "marking_get_lethal before marking_create");
-  if (capacity < (size_t)m->n_ground + 1) return fail(ctx, DDDMR_ERR_CAPACITY, "marking_get_lethal: capacity %zu < %u", capacity, m->n_ground + 1);
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, hipMemcpy(flags_out, m->store.lethal, (size_t)m->n_ground + 1, hipMemcpyDeviceToHost));
-  return DDDMR_OK;
+  return store_read_lethal(ctx, m->store, "marking_get_lethal", flags_out, capacity);
 }
 
 }  // extern "C"

@@ -11,9 +11,10 @@ import sys
 import numpy as np
 import pytest
 
-from dddmr_navigation_amd import _capi as K, configs, depth_layer, scenes
+from dddmr_navigation_amd import _capi as K, configs, depth_layer, marking, scenes
 from dddmr_navigation_amd.local_planner import LocalPlanner, RolloutError
 from conftest import ROOT
+import oracle
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 import depth_clear_cases as dcases  # noqa: E402
@@ -123,6 +124,47 @@ def test_every_update_equals_the_restatement(name):
     if name == "housekeeping":
         # an update runs each kind of housekeeping at most once: 2 in one update = the store rehash AND the pool compaction
         assert max(int(st.gc_runs) for st, _ in got) == 2
+
+
+def test_a_lidar_layer_and_a_depth_layer_in_one_context_keep_their_stores_apart():
+    """Both layers run the same store code (marking_store.hip.h).  One context holds one of each, updated in turn on the
+    same aggregate, each against its own restatement after every update, with stores small enough for housekeeping.
+
+    Sizes, from the restatements' own counts for the first three updates of one_camera (they do not depend on the
+    capacities).  Depth layer: 101 / 198 / 271 voxels have entered the store after update 0 / 1 / 2 with 124 alive after
+    update 1, and the pool takes 818 + 856 + 847 points (pc_ + generator points).  max_markings 128 (table 256) makes
+    198 > 128 and > 124 + 32 before update 2: the store is rehashed there.  max_cluster_points 3072 makes 1674 > 1536
+    before update 2: the pool is compacted there (937 alive points + 847 fit).  Lidar layer: its pool takes 200 points
+    in update 0, 199 .. 240 in update 1 and at most 294 in update 2, 240 are alive after update 1: with 768 it is
+    compacted before update 2 (399 > 384; 240 + 294 fit)."""
+    case, ups, ground, _ = cases.built("one_camera")
+    t_bs = (0.0, 0.0, 0.5, 0, 0, 0, 1)
+    no_map = np.zeros((0, 3), np.float32)
+    mcfg = marking.shipped_config(max_markings=256, max_cluster_points=768)
+    mo = oracle.MarkingOracle(mcfg, ground, no_map)
+    ref = cases.layer_ref(case, ground)
+    with planner() as lp:
+        configure(lp, case)
+        dl = depth_layer.DepthLayer(lp, depth_layer.shipped_config(max_markings=128, max_cluster_points=3072, **case.layer_kw()), ground, no_map)
+        ml = marking.MarkingLayer(lp, mcfg, ground, no_map)
+        frs, gc_runs = {}, 0
+        for k, u in enumerate(ups[:3]):
+            for st in u["feeds"]:
+                feed(lp, st)
+                frs[st["sid"]] = R.Frustum(dcases.FOV_W, dcases.FOV_V, dcases.D_MIN, dcases.D_MAX, st["m2s"])
+            obs = lp.get_cloud()
+            st = dl.update(u["t_gb"])
+            res = ref.update([frs[s] for s in sorted(frs)], obs[:, :3], u["t_gb"])
+            assert_state(dl, st, ref, res, f"depth layer beside a lidar layer, update {k}")
+            gc_runs += int(st.gc_runs)
+            sm = ml.update(t_bs, u["t_gb"])
+            so = mo.update(obs[:, :3], t_bs, u["t_gb"])
+            assert (sm.n_observation, sm.n_clusters, sm.n_marked, sm.n_in_window, sm.n_cleared, sm.n_alive) == \
+                   (so.n_observation, so.n_clusters, so.n_marked, so.n_in_window, so.n_cleared, so.n_alive), k
+            assert set(map(tuple, ml.voxels().tolist())) == set(map(tuple, mo.voxels().tolist())), k
+            np.testing.assert_array_equal(ml.dgraph(), mo.dgraph(), err_msg=f"lidar layer update {k}")
+            np.testing.assert_array_equal(ml.lethal(), mo.lethal(), err_msg=f"lidar layer update {k}")
+        assert gc_runs > 0
 
 
 def host_split_replay(lp, case, t_gb, store):
