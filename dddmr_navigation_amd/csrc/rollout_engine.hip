@@ -1,10 +1,8 @@
 // rollout_engine.hip -- context, host-side theory initialisation and the C-ABI
 // (include/dddmr_rollout.h) of the MI355X local-planner rollout engine.
 //
-// Host responsibilities (cheap, per tick): the dynamic-window sample axes of the
-// theory's initialise() (dd_simple_trajectory_generator_theory.cpp:236-295,
-// omni_simple_...cpp:260-332, dd_rotate_inplace_theory.cpp:229-274), the local
-// costmap tile's extent, and launching the five kernels of rollout_kernels.hip.h.
+// Host responsibilities (cheap, per tick): planning the tick (tick_plan.hip.h: the theory's initialise(), the local
+// costmap tile, the launch shapes) and launching the five kernels of rollout_kernels.hip.h.
 // Everything proportional to N_traj x N_steps or to the cloud runs on the GPU.
 //
 // Citations are relative to /root/reference/src/dddmr_local_planner/.
@@ -25,6 +23,7 @@
 #include <vector>
 
 #include "rollout_kernels.hip.h"
+#include "tick_plan.hip.h"
 #include "perception_kernels.hip.h"
 #include "depth_feed.hip.h"
 #include "depth_image.hip.h"
@@ -35,124 +34,7 @@ using namespace dddmr;
 
 namespace {
 
-constexpr uint32_t kCapCells = 1u << 20;
-constexpr int kMaxAxis = 4096;
-constexpr int kScoreLdsMax = 150 * 1024;   // dynamic LDS one k_score workgroup may use
 constexpr int kCloudBufs = 3;              // front / busy / free, see dddmr_rollout_ctx
-
-struct Window {              // result of a theory's initialise()
-  std::vector<float> ax, ay, ath;
-  bool list_mode = false;
-  std::vector<float4> list;  // explicit samples (rotate-in-place, motor-constraint filter)
-  size_t count() const { return list_mode ? list.size() : ax.size() * ay.size() * ath.size(); }
-};
-
-// velocity_iterator.h:44-69 -- even samples in [lo,hi], max(2,n) of them, an
-// extra 0.0 where the range straddles zero, last sample forced to hi.
-void velocity_samples(double lo, double hi, int n, bool insert_zero, std::vector<float>& out) {
-  out.clear();
-  if (lo == hi) {
-    out.push_back((float)lo);
-    return;
-  }
-  n = std::max(2, n);
-  const double step = (hi - lo) / double(std::max(1, n - 1));
-  double next = lo;
-  for (int j = 0; j < n - 1; ++j) {
-    const double cur = next;
-    next += step;
-    out.push_back((float)cur);
-    if (insert_zero && cur < 0 && next > 0) out.push_back(0.0f);
-  }
-  out.push_back((float)hi);
-}
-
-bool motor_rpm_ok(const dddmr_theory_config& c, float v, float w) {
-  // dd_simple...cpp:297-312, dd_rotate_inplace_theory.cpp:276-286
-  const double vr = v + c.robot_radius * w;
-  const double vl = v - c.robot_radius * w;
-  const double rpm_r = vr * c.gear_ratio * 60. / 3.1415926 / c.wheel_diameter;
-  const double rpm_l = vl * c.gear_ratio * 60. / 3.1415926 / c.wheel_diameter;
-  return !(std::fabs(rpm_r) >= c.max_motor_shaft_rpm || std::fabs(rpm_l) >= c.max_motor_shaft_rpm);
-}
-
-// The dynamic window is computed in float (Eigen::Vector3f max_vel/min_vel) from
-// double limits, exactly like the theories' initialise().
-void make_window(const dddmr_theory_config& c, const dddmr_tick_input& in, Window& w) {
-  w = Window();
-  if (!(c.linear_x_sample * c.angular_z_sample > 0)) {
-    w.list_mode = true;  // no samples at all
-    return;
-  }
-  const bool zero = c.bench_no_zero_insert == 0;
-  const double period = 1.0 / c.controller_frequency;
-  const double vx = in.robot_twist[0], vy = in.robot_twist[1], wz = in.robot_twist[2];
-  const float accx = (float)c.acc_lim_x, accy = (float)c.acc_lim_y, acct = (float)c.acc_lim_theta;
-  const double max_th = c.max_vel_theta, min_th = -1.0 * c.max_vel_theta;
-
-  if (c.kind == DDDMR_THEORY_DD_ROTATE_INPLACE) {
-    w.list_mode = true;
-    const float sp = (float)c.rotation_speed, sn = (float)(-1.0 * c.rotation_speed);
-    if (motor_rpm_ok(c, 0.f, sp)) w.list.push_back(make_float4(0.f, 0.f, sp, 0.f));
-    if (motor_rpm_ok(c, 0.f, sn)) w.list.push_back(make_float4(0.f, 0.f, sn, 0.f));
-    return;
-  }
-
-  float hi_x, lo_x, hi_t, lo_t;
-  hi_t = (float)std::min(max_th, wz + acct * period);
-  lo_t = (float)std::max(min_th, wz - acct * period);
-  if (c.kind == DDDMR_THEORY_DD_SIMPLE) {
-    double cap_x = c.max_vel_x;
-    if (in.allowed_max_linear_speed > 0.0) cap_x = std::min(cap_x, in.allowed_max_linear_speed);
-    hi_x = (float)std::min(cap_x, vx + accx * period);
-    lo_x = (float)std::max(c.min_vel_x, vx / c.deceleration_ratio);
-    if (hi_x < lo_x) {  // speed zone tighter than the robot can decelerate (:273-276)
-      lo_x = (float)(vx / c.deceleration_ratio);
-      hi_x = (float)(vx / c.deceleration_ratio);
-    }
-    velocity_samples(lo_x, hi_x, (int)c.linear_x_sample, zero, w.ax);
-    velocity_samples(lo_t, hi_t, (int)c.angular_z_sample, zero, w.ath);
-    w.ay.assign(1, 0.0f);
-    if (c.use_motor_constraint) {  // filtered list keeps the x-major / theta-minor order
-      w.list_mode = true;
-      for (float x : w.ax)
-        for (float t : w.ath)
-          if (motor_rpm_ok(c, x, t)) w.list.push_back(make_float4(x, 0.f, t, 0.f));
-    }
-    return;
-  }
-  // omni (omni_simple...cpp:283-312)
-  float hi_y, lo_y;
-  hi_x = (float)std::min(c.max_vel_x, vx + accx * period);
-  hi_y = (float)std::min(c.max_vel_y, vy + accy * period);
-  lo_x = (float)std::max(c.min_vel_x, vx - accx * period);
-  lo_y = (float)std::max(c.min_vel_y, vy - accy * period);
-  if (vx >= c.max_vel_x / c.deceleration_ratio) lo_x = (float)std::max(c.min_vel_x, vx / c.deceleration_ratio);
-  else if (vx <= c.min_vel_x / c.deceleration_ratio) hi_x = (float)std::min(c.max_vel_x, vx / c.deceleration_ratio);
-  if (vy >= c.max_vel_y / c.deceleration_ratio) lo_y = (float)std::max(c.min_vel_y, vy / c.deceleration_ratio);
-  else if (vy <= c.min_vel_y / c.deceleration_ratio) hi_y = (float)std::min(c.max_vel_y, vy / c.deceleration_ratio);
-  velocity_samples(lo_x, hi_x, (int)c.linear_x_sample, zero, w.ax);
-  velocity_samples(lo_y, hi_y, (int)c.linear_y_sample, zero, w.ay);
-  velocity_samples(lo_t, hi_t, (int)c.angular_z_sample, zero, w.ath);
-}
-
-void quat_to_rot(const double p[7], double R[9]) {
-  // Eigen::Quaterniond(w,x,y,z).toRotationMatrix(), as tf2::transformToEigen builds it
-  const double x = p[3], y = p[4], z = p[5], w = p[6];
-  const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-  const double twx = tx * w, twy = ty * w, twz = tz * w;
-  const double txx = tx * x, txy = ty * x, txz = tz * x;
-  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-  R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
-  R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-  R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
-}
-
-float absmax(const std::vector<float>& v) {
-  float m = 0.f;
-  for (float x : v) m = std::max(m, std::fabs(x));
-  return m;
-}
 
 struct MarkingState;                       // global-mode marking / clearing layer, marking_host.hip.h
 void marking_free(MarkingState* m);
@@ -197,12 +79,8 @@ struct dddmr_rollout_ctx {
   uint32_t* blocked_flags = nullptr;
   uint32_t* traj_load = nullptr;
   uint32_t* assign = nullptr;
-  int load_theory = -1, load_nlocal = -1;   // what traj_load describes
-  float collided_share = 1.0f;              // share of the last tick's trajectories the collision critics rejected
-  int probe_mode = -1;                      // DDDMR_PROBE: 1 / 0 force the walk's probe round on / off, -1 by collided_share
-  bool no_assign = false;
-  bool no_boxfast = false;   // DDDMR_NO_BOXFAST: always take the general vertex transform
-  bool no_tab = false;       // DDDMR_NO_TAB: k_score reads the row-run index from L2 instead of staging it in LDS
+  TickFeedback feedback;     // what traj_load describes, and the collided share of the last tick
+  TickKnobs knobs;           // what create read from the environment and the device for plan_tick
   // DDDMR_POISON=1 (tests): fill the per-trajectory outputs with NaN / -1 patterns before every
   // tick, so a trajectory the scorer skipped cannot pass for scored with last tick's values
   bool poison = false;
@@ -210,7 +88,6 @@ struct dddmr_rollout_ctx {
   bool host_prof = false;
   double prof_ns[4] = {0, 0, 0, 0};
   uint64_t prof_n = 0;
-  bool gnz_one = false;
   double* poses_dev = nullptr;
   // perception feed scratch
   PerceptionScratch feed{};
@@ -272,27 +149,17 @@ struct dddmr_rollout_ctx {
   DevTick last{};
   bool have_last = false;
   Window last_window;
-  float cell_size = 0.25f;
-  bool cell_forced = false;   // DDDMR_CELL given: no automatic growth on big shards
-  int tile_override = 0;
-  int rt_override = 0;        // DDDMR_RT: trajectories per rollout workgroup
-  int threads_override = 0;   // DDDMR_THREADS: force the 256- or 512-lane k_score
-  int n_cu = 256;   // compute units of the device
-  bool tail_round = false;      // DDDMR_TAIL_ROUND=1: one last round of short k_score workgroups (measured: C3 +3 us, C4 -7 us; off)
   int timing = 1;   // DDDMR_TIMING: 0 no HIP events, 1 around k_score (score_ms), 2 also around the whole tick
   int timing_every = 1;   // DDDMR_TIMING_EVERY: record the events on every n-th tick only
   int spin = 1;     // DDDMR_SPIN: poll the host-mapped result instead of hipStreamSynchronize
-  int final_mode = -1;   // DDDMR_FINAL: 1 always decode in k_finalize, 0 always in k_score's last workgroup, -1 by shard size
   uint32_t seq = 0;
   DevResult last_result{};   // host copy of the last COLLECTED tick's result
   float last_score_ms = 0.f, last_device_ms = 0.f;
   // a tick whose kernels are enqueued but whose result has not been collected yet
   struct Pending {
     bool active = false;
-    DevTick k{};
-    int s_tick = 0;
+    TickPlan plan;                 // what the tick's kernels were launched with
     bool timed = false, timed_all = false;
-    dddmr_rollout_result head{};   // n_samples / shard fields known at enqueue time
     Window window;                 // becomes last_window when the tick is collected
   } pend;
 };
@@ -367,85 +234,6 @@ const dddmr_theory_config* find_theory(const dddmr_rollout_ctx* ctx, const char*
   for (const auto& t : ctx->theories)
     if (std::strncmp(t.name, name, DDDMR_NAME_LEN) == 0) return &t;
   return nullptr;
-}
-
-// The points the collision critics look at around one pose, in the body frame: the 8 cuboid vertices (the min-max
-// critic tests their bounding box) AND the 8 corners of the region CollisionModel tests, { d : |d . a_i| <= h_i } around
-// the mean of the vertices with a_i, h_i from the edges e_i = v_i - v_0 (collision_model.cpp:85-115).  For a cuboid
-// that is a body-frame box that region is the cuboid; for any other vertex list the three slabs meet in the DUAL
-// parallelepiped, centre +- g_1 +- g_2 +- g_3, g_i = (e_j x e_k) |e_i|^2 / (2 det), which reaches beyond the vertices'
-// hull -- a tile / candidate range sized by the vertices alone never looks at the points in between (found by a soak).
-// A degenerate vertex list leaves the region unbounded: the corners then go to the 1 m search ball's box.
-void collision_extent_points(const dddmr_theory_config& c, double out[16][3]) {
-  double ctr[3] = {0, 0, 0}, e[3][3], g[3][3];
-  for (int k = 0; k < 8; ++k)
-    for (int a = 0; a < 3; ++a) { out[k][a] = c.cuboid[k][a]; ctr[a] += c.cuboid[k][a] / 8.0; }
-  for (int i = 0; i < 3; ++i)
-    for (int a = 0; a < 3; ++a) e[i][a] = (double)c.cuboid[i + 1][a] - (double)c.cuboid[0][a];
-  auto cross = [](const double* u, const double* v, double* w) {
-    w[0] = u[1] * v[2] - u[2] * v[1]; w[1] = u[2] * v[0] - u[0] * v[2]; w[2] = u[0] * v[1] - u[1] * v[0];
-  };
-  double cr[3][3];
-  cross(e[1], e[2], cr[0]); cross(e[2], e[0], cr[1]); cross(e[0], e[1], cr[2]);
-  const double det = e[0][0] * cr[0][0] + e[0][1] * cr[0][1] + e[0][2] * cr[0][2];
-  const bool ok = std::fabs(det) > 1e-12;
-  for (int i = 0; i < 3; ++i) {
-    const double n2 = e[i][0] * e[i][0] + e[i][1] * e[i][1] + e[i][2] * e[i][2];
-    for (int a = 0; a < 3; ++a) g[i][a] = ok ? cr[i][a] * n2 / (2.0 * det) : 0.0;
-  }
-  for (int corner = 0; corner < 8; ++corner)
-    for (int a = 0; a < 3; ++a) {
-      double v = ctr[a];
-      for (int i = 0; i < 3; ++i) v += ((corner >> i) & 1) ? g[i][a] : -g[i][a];
-      if (!ok) v = ((corner >> a) & 1) ? 1.0 : -1.0;
-      out[8 + corner][a] = std::max(-3.0, std::min(3.0, v));
-    }
-}
-
-// Extent of the local costmap tile: every cloud point that can be inside any
-// cuboid of any trajectory of this tick.  A pose stays within rho =
-// max speed * sim_time of base_link in the body xy-plane, a cuboid vertex
-// within rv of its pose (any yaw), so the body-frame box
-// [-(rho+rv), rho+rv]^2 x [vz_min, vz_max] bounds all vertices; points further
-// than 1 m from every pose are ignored by the critic's radius search anyway
-// (collision_model.cpp:122).
-void tile_extent(const dddmr_theory_config& c, const Window& w, const double R[9], const double t[3],
-                 double sim_time, float rmin[3], float rmax[3]) {
-  double rho;
-  if (c.kind == DDDMR_THEORY_DD_ROTATE_INPLACE) {
-    rho = 0.0;
-  } else if (w.list_mode) {
-    double m = 0;
-    for (const auto& s : w.list) m = std::max(m, std::hypot((double)s.x, (double)s.y));
-    rho = m * sim_time;
-  } else {
-    rho = std::hypot((double)absmax(w.ax), (double)absmax(w.ay)) * sim_time;
-  }
-  rho = rho * 1.001 + 0.01;  // float state rounding
-  double rv = 0, vz0 = 1e30, vz1 = -1e30;
-  double ext[16][3];
-  collision_extent_points(c, ext);
-  for (int k = 0; k < 16; ++k) {
-    rv = std::max(rv, std::hypot(ext[k][0], ext[k][1]));
-    vz0 = std::min(vz0, ext[k][2]);
-    vz1 = std::max(vz1, ext[k][2]);
-  }
-  const double e = rho + rv;
-  const double margin = 0.02;
-  for (int i = 0; i < 3; ++i) {
-    double lo = 1e30, hi = -1e30;
-    for (int corner = 0; corner < 8; ++corner) {
-      const double bx = (corner & 1) ? e : -e, by = (corner & 2) ? e : -e, bz = (corner & 4) ? vz1 : vz0;
-      const double v = R[3 * i + 0] * bx + R[3 * i + 1] * by + R[3 * i + 2] * bz + t[i];
-      lo = std::min(lo, v);
-      hi = std::max(hi, v);
-    }
-    // radius criterion: within 1 m of some pose, poses within rho of base_link
-    lo = std::max(lo, t[i] - (rho + 1.0));
-    hi = std::min(hi, t[i] + (rho + 1.0));
-    rmin[i] = (float)(lo - margin);
-    rmax[i] = (float)(hi + margin);
-  }
 }
 
 }  // namespace
@@ -573,24 +361,24 @@ int dddmr_rollout_create(const dddmr_rollout_config* cfg, dddmr_rollout_ctx** ou
   ctx->device = cfg->device;
   if (const char* e = std::getenv("DDDMR_CELL")) {
     const float v = (float)std::atof(e);
-    if (v > 0.01f && v < 10.f) { ctx->cell_size = v; ctx->cell_forced = true; }
+    if (v > 0.01f && v < 10.f) { ctx->knobs.cell_size = v; ctx->knobs.cell_forced = true; }
   }
-  if (const char* e = std::getenv("DDDMR_TILE")) ctx->tile_override = std::atoi(e);
-  if (const char* e = std::getenv("DDDMR_RT")) ctx->rt_override = std::atoi(e);
-  if (const char* e = std::getenv("DDDMR_THREADS")) ctx->threads_override = std::atoi(e) == 512 ? 512 : 256;
-  if (const char* e = std::getenv("DDDMR_TAIL_ROUND")) ctx->tail_round = std::atoi(e) != 0;
+  if (const char* e = std::getenv("DDDMR_TILE")) ctx->knobs.tile_override = std::atoi(e);
+  if (const char* e = std::getenv("DDDMR_RT")) ctx->knobs.rt_override = std::atoi(e);
+  if (const char* e = std::getenv("DDDMR_THREADS")) ctx->knobs.threads_override = std::atoi(e) == 512 ? 512 : 256;
+  if (const char* e = std::getenv("DDDMR_TAIL_ROUND")) ctx->knobs.tail_round = std::atoi(e) != 0;
   if (const char* e = std::getenv("DDDMR_TIMING")) ctx->timing = std::atoi(e);
   if (const char* e = std::getenv("DDDMR_TIMING_EVERY")) ctx->timing_every = std::max(1, std::atoi(e));
   if (const char* e = std::getenv("DDDMR_SPIN")) ctx->spin = std::atoi(e);
-  if (const char* e = std::getenv("DDDMR_FINAL")) ctx->final_mode = std::atoi(e) ? 1 : 0;
-  if (const char* e = std::getenv("DDDMR_PROBE")) ctx->probe_mode = std::atoi(e) ? 1 : 0;
+  if (const char* e = std::getenv("DDDMR_FINAL")) ctx->knobs.final_mode = std::atoi(e) ? 1 : 0;
+  if (const char* e = std::getenv("DDDMR_PROBE")) ctx->knobs.probe_mode = std::atoi(e) ? 1 : 0;
 
   auto init = [&]() -> int {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     {
       hipDeviceProp_t prop;
       HIPCHK(ctx, hipGetDeviceProperties(&prop, ctx->device));
-      ctx->n_cu = std::max(1, prop.multiProcessorCount);
+      ctx->knobs.n_cu = std::max(1, prop.multiProcessorCount);
     }
     HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
     HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
@@ -623,12 +411,12 @@ int dddmr_rollout_create(const dddmr_rollout_config* cfg, dddmr_rollout_ctx** ou
     HIPCHK(ctx, hipMalloc(&ctx->traj_load, N * sizeof(uint32_t)));
     HIPCHK(ctx, hipMemset(ctx->traj_load, 0, N * sizeof(uint32_t)));
     HIPCHK(ctx, hipMalloc(&ctx->assign, N * sizeof(uint32_t)));
-    ctx->no_assign = std::getenv("DDDMR_NO_ASSIGN") != nullptr;
-    ctx->no_boxfast = std::getenv("DDDMR_NO_BOXFAST") != nullptr;
-    ctx->no_tab = std::getenv("DDDMR_NO_TAB") != nullptr;
+    ctx->knobs.no_assign = std::getenv("DDDMR_NO_ASSIGN") != nullptr;
+    ctx->knobs.no_boxfast = std::getenv("DDDMR_NO_BOXFAST") != nullptr;
+    ctx->knobs.no_tab = std::getenv("DDDMR_NO_TAB") != nullptr;
     ctx->poison = std::getenv("DDDMR_POISON") != nullptr;
     ctx->host_prof = std::getenv("DDDMR_HOST_PROF") != nullptr;
-    ctx->gnz_one = std::getenv("DDDMR_GNZ_ONE") != nullptr;
+    ctx->knobs.gnz_one = std::getenv("DDDMR_GNZ_ONE") != nullptr;
     HIPCHK(ctx, hipMalloc(&ctx->tickets, 2 * sizeof(uint32_t)));
     HIPCHK(ctx, hipMemset(ctx->tickets, 0, 2 * sizeof(uint32_t)));
     HIPCHK(ctx, hipMalloc(&ctx->poses_dev, (size_t)cfg->max_steps * 7 * sizeof(double)));
@@ -1411,108 +1199,29 @@ void release_cloud(dddmr_rollout_ctx* c) {
   c->busy = -1;
 }
 
-// Enqueue one tick (host-side initialise() + 3 launches); tick_mu must be held.
-int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_tick_input* in) {
-  dddmr_rollout_result head_storage;
-  dddmr_rollout_result* out = &head_storage;
+void no_winner(dddmr_rollout_result* out) {
   std::memset(out, 0, sizeof(*out));
   out->planner_state = DDDMR_ALL_TRAJECTORIES_FAIL;
   out->best_index = -1;
   out->best_cost = -1.0;
   out->key = kKeyNone;
+}
+
+// Enqueue one tick: plan it (tick_plan.hip.h, arithmetic alone), then upload and launch what the plan says; tick_mu
+// must be held.
+int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_tick_input* in) {
   const auto prof_t0 = std::chrono::steady_clock::now();
   const dddmr_theory_config* th = find_theory(ctx, theory_name);
   if (!th) return fail(ctx, DDDMR_ERR_UNKNOWN_THEORY, "unknown theory '%s'", theory_name);
   HIPCHK(ctx, hipSetDevice(ctx->device));
-
-  // ---- initialise(): velocity samples of this tick ----
   Window& w = ctx->pend.window;
-  make_window(*th, *in, w);
-  const size_t N = w.count();
-  if (N > ctx->cfg.max_trajectories)
-    return fail(ctx, DDDMR_ERR_CAPACITY, "%zu samples > max_trajectories %u", N, ctx->cfg.max_trajectories);
-  if (!w.list_mode && (w.ax.size() > (size_t)kMaxAxis || w.ay.size() > (size_t)kMaxAxis || w.ath.size() > (size_t)kMaxAxis))
-    return fail(ctx, DDDMR_ERR_CAPACITY, "sample axis longer than %d", kMaxAxis);
-  const int world = std::max(1, ctx->cfg.world_size);
-  const int rank = std::min(std::max(0, ctx->cfg.rank), world - 1);
-  const uint32_t begin = (uint32_t)((uint64_t)rank * N / world);
-  const uint32_t end = (uint32_t)((uint64_t)(rank + 1) * N / world);
-  out->n_samples = (uint32_t)N;
-  out->local_begin = begin;
-  out->n_local = end - begin;
+  make_window(*th, *in, w);   // initialise(): velocity samples of this tick
 
-  DevTick k{};
-  k.kind = th->kind;
-  k.fixed_steps = th->bench_fixed_steps > 0 ? th->bench_fixed_steps : 0;
-  k.list_mode = w.list_mode ? 1 : 0;
-  k.n_global = (int)N;
-  k.begin = (int)begin;
-  k.n_local = (int)(end - begin);
-  k.nx = (int)std::max<size_t>(w.ax.size(), 1);
-  k.ny = (int)std::max<size_t>(w.ay.size(), 1);
-  k.nth = (int)std::max<size_t>(w.ath.size(), 1);
-  k.ay_ofs = kMaxAxis;
-  k.ath_ofs = 2 * kMaxAxis;
-  k.sim_time = th->sim_time;
-  k.sim_gran = th->sim_granularity;
-  k.ang_gran = th->angular_sim_granularity;
-  k.min_vel_x = th->min_vel_x;
-  k.max_vel_x = th->max_vel_x;
-  k.min_vel_theta = th->min_vel_theta;
-  k.min_vel_trans = th->min_vel_trans;
-  k.max_vel_trans = th->max_vel_trans;
-  k.allowed_max = in->allowed_max_linear_speed;
-  quat_to_rot(in->robot_pose, k.R);
-  for (int i = 0; i < 3; ++i) k.t[i] = in->robot_pose[i];
-  for (int v = 0; v < 8; ++v)
-    for (int j = 0; j < 3; ++j) k.cub[3 * v + j] = th->cuboid[v][j];
-  k.m = (int)ctx->plan_m;
-  quat_to_rot(ctx->plan_last, k.planR);
-  for (int i = 0; i < 3; ++i) k.planT[i] = ctx->plan_last[i];
-  k.n_critics = th->n_critics;
-  for (int m = 0; m < th->n_critics; ++m) {
-    k.ckind[m] = th->critics[m].kind;
-    k.cw[m] = th->critics[m].weight;
-    k.ctw[m] = th->critics[m].translation_weight;
-    k.cow[m] = th->critics[m].orientation_weight;
-    if (k.ckind[m] == DDDMR_CRITIC_COLLISION) k.want_collision = 1;
-    if (k.ckind[m] == DDDMR_CRITIC_COLLISION_MIN_MAX) k.want_minmax = 1;
-  }
-  k.heading_dev = in->heading_deviation;
-
-  // horizon of this tick (monotone in |v| and |w|, so the axis extremes bound it)
-  double sim_time_eff = th->sim_time;
-  int s_tick;
-  {
-    double vmax, wmax;
-    if (w.list_mode) {
-      vmax = 0; wmax = 0;
-      for (const auto& s : w.list) {
-        vmax = std::max(vmax, std::hypot((double)s.x, (double)s.y));
-        wmax = std::max(wmax, std::fabs((double)s.z));
-      }
-    } else {
-      vmax = std::hypot((double)absmax(w.ax), (double)absmax(w.ay));
-      wmax = (double)absmax(w.ath);
-    }
-    if (th->bench_fixed_steps > 0) {
-      s_tick = th->bench_fixed_steps;
-    } else if (th->kind == DDDMR_THEORY_DD_ROTATE_INPLACE) {
-      s_tick = (int)std::ceil(std::max(0.0, 6.28 / th->angular_sim_granularity)) + 1;
-      sim_time_eff = 0.0;
-    } else {
-      s_tick = (int)std::ceil(std::max(vmax * th->sim_time / th->sim_granularity,
-                                       wmax * th->sim_time / th->angular_sim_granularity)) + 1;
-    }
-    s_tick = std::max(s_tick, 1);
-  }
-  if ((uint32_t)s_tick > ctx->cfg.max_steps)
-    return fail(ctx, DDDMR_ERR_CAPACITY, "horizon of %d steps > max_steps %u", s_tick, ctx->cfg.max_steps);
-  k.max_steps = s_tick;
-
-  // ---- cloud front buffer + local costmap tile ----
-  // (the "upload still pending" flag is only cleared once the stream wait below is enqueued: an
-  // early error return in between must not lose the ordering against copy_stream)
+  // The cloud's front buffer is pinned before the plan's capacity checks, because the plan needs its size.  No caller
+  // can tell: `busy` is -1 whenever a tick is enqueued (every other pinner holds tick_mu and releases before it
+  // returns, and every entry point refuses while a tick is pending), and the guard releases on any error return.
+  // (The "upload still pending" flag is only cleared once the stream wait below is enqueued: an early error return in
+  // between must not lose the ordering against copy_stream.)
   bool pending;
   const int cidx = pin_front(ctx, &pending);
   struct Unbusy {          // releases the cloud buffer again if enqueueing fails half-way
@@ -1520,209 +1229,44 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
     bool armed = true;
     ~Unbusy() { if (armed) release_cloud(c); }
   } unbusy{ctx};
-  k.n_points = (int)ctx->cloud_n[cidx];
-  tile_extent(*th, w, k.R, k.t, sim_time_eff, k.rmin, k.rmax);
-  // A cuboid's AABB (clipped to the 2 m wide search ball) must not span more than
-  // kRows cell rows: rows <= span / cell + 2.
-  double diam = 0;
-  {
-    double ext[16][3];
-    collision_extent_points(*th, ext);
-    for (int a = 0; a < 16; ++a)
-      for (int b = a + 1; b < 16; ++b) {
-        const double dx = ext[a][0] - ext[b][0], dy = ext[a][1] - ext[b][1], dz = ext[a][2] - ext[b][2];
-        diam = std::max(diam, std::sqrt(dx * dx + dy * dy + dz * dz));
-      }
-    diam += 4e-4;     // the candidate range's margin on both sides (k_score phase D1)
-  }
-  float cell = std::max(ctx->cell_size, (float)(std::min(diam, 2.0) * 1.001 / (kRows - 2)));
-  float cell_z = cell;     // z cells do not grow with the x/y cells below
-  // Big shards run many 256-lane workgroups per CU and are bound by how many (trajectory,
-  // step) slots fit a CU's LDS; a slot's row segments are the largest part of it, so there the
-  // cells grow until a cuboid spans at most 4 rows (C3 k_score 143 -> 122 us, C4 342 -> 298 us
-  // at 0.42 m).  Shards that fit one round of 512-lane workgroups keep the small cells: their
-  // LDS is not the limit and bigger cells make the counting atomics collide (C2 binning
-  // +3 us at 0.42 m, +7 us at 0.5 m).
-  if (!ctx->cell_forced && k.n_local > ctx->n_cu * kMaxTile)
-    cell = std::max(cell, std::min(0.5f, (float)(std::min(diam, 2.0) * 1.001 / 2.9)));
-  for (;;) {
-    k.gnx = std::max(1, (int)std::ceil((k.rmax[0] - k.rmin[0]) / cell));
-    k.gny = std::max(1, (int)std::ceil((k.rmax[1] - k.rmin[1]) / cell));
-    // Candidate runs always take every z of a row, but one cell column per (x, y) makes the
-    // counting atomics of wall points collide (measured: k_bin_count 13 -> 17 us); keep z.
-    k.gnz = ctx->gnz_one ? 1 : std::max(1, (int)std::ceil((k.rmax[2] - k.rmin[2]) / cell_z));
-    const uint64_t nc = (uint64_t)k.gnx * k.gny * k.gnz;
-    if (nc <= kCapCells && k.gnx < 32000 && k.gny < 32000) { k.n_cells = (int)nc; break; }
-    cell *= 1.5f;
-    cell_z *= 1.5f;
-  }
-  k.inv_cell = 1.0f / cell;
-  k.inv_cell_z = 1.0f / cell_z;
-  for (int i = 0; i < 3; ++i) k.gmin[i] = k.rmin[i];
-  // rows <= floor(span / cell) + 2 (span = cuboid diameter clipped to the 2 m search ball)
-  k.rows_cap = std::min(kRows, (int)std::floor(std::min(diam, 2.0) * 1.001 / cell) + 2);
-  {
-    // box in the body frame, vertices in the push order blb brb blt flb brt frt flt frb
-    // (dd_simple_trajectory_generator_theory.cpp:211-218)?  Then k_score shares the products.
-    const float (*c)[3] = th->cuboid;
-    const float X0 = c[0][0], X1 = c[3][0], Y0 = c[0][1], Y1 = c[1][1], Z0 = c[0][2], Z1 = c[2][2];
-    const float want[8][3] = {{X0, Y0, Z0}, {X0, Y1, Z0}, {X0, Y0, Z1}, {X1, Y0, Z0},
-                              {X0, Y1, Z1}, {X1, Y1, Z1}, {X1, Y0, Z1}, {X1, Y1, Z0}};
-    bool box = true;
-    for (int v = 0; v < 8; ++v)
-      for (int a = 0; a < 3; ++a) box = box && (c[v][a] == want[v][a]);
-    k.box_fast = (box && !ctx->no_boxfast) ? 1 : 0;
-  }
 
-  // trajectories per workgroup: ~one (trajectory, step) pair per lane
-  // OBB records carry the pose only if some pair can need the 1 m radius test: a point
-  // inside the box is within max|vertex| of the pose, so a cuboid that lies inside the
-  // search ball never does (the min-max critic always needs it).
-  double vnorm = 0;
-  {
-    double ext[16][3];       // (the corners of the box the collision critic derives count too)
-    collision_extent_points(*th, ext);
-    for (int v = 0; v < 16; ++v) vnorm = std::max(vnorm, std::sqrt(ext[v][0] * ext[v][0] + ext[v][1] * ext[v][1] + ext[v][2] * ext[v][2]));
-  }
-  k.rec_pose = (vnorm >= 0.985 || k.want_minmax) ? 1 : 0;
-  const int rec_words = rec_words_of(k.rec_pose != 0, k.want_minmax != 0);
-  {
-    const long te = (long)(k.gnx + 1) * k.gny;
-    k.tab_entries = (te <= kTabCap && k.n_points >= 5 && (k.want_collision || k.want_minmax) && !ctx->no_tab) ? (int)te : 0;
-  }
-  // Workgroup shape.  Default: 256 lanes and the tile that keeps the most (trajectory, step)
-  // slots resident per CU with the slots of one workgroup fitting its lanes (one pair per
-  // lane in D1/D2) -- measured on the big batches: C4 (50 steps) tile 3 / 4 / 5 / 6
-  // -> 420 / 342 / 364 / 519 us (39 KB of LDS at tile 4: four workgroups per CU, 47 KB at
-  // tile 5: three), C3 (80-step rows) tile 2 / 3 / 4 -> 158 / 143 / 174 us.
-  // When the whole shard fits ONE round of resident 512-lane workgroups (2 per CU at 4 waves
-  // per SIMD and <= 80 KB of LDS), that shape wins instead: the launch is bound by its
-  // heaviest tile's collision walk and 512 lanes both halve it and average over more
-  // trajectories (C2).
-  // Workgroup shape.  Per-workgroup fixed costs (staging the plan and the row-run index, ~13 barriers, the wave-0
-  // scans) make few, fat workgroups win: measured on the r02 scenes, k_score at C3 (80-step rows) 256 lanes x tile
-  // 2 / 3 / 4 -> 222 / 158 / 152 us, 512 lanes x tile 6 -> 132 us; C4 (50-step rows) 256 lanes x tile 3 / 5 / 7 ->
-  // 564 / 344 / 336 us, 512 lanes x tile 8 / 10 / 11 -> 347 / 304 / 320 us.  So: 512 lanes (two workgroups per CU
-  // at 4 waves per SIMD and <= 80 KB of LDS each) and
-  //  - a shard that fits ONE round of resident workgroups is spread evenly over them (C2: tile 8, 512 workgroups);
-  //  - a bigger shard takes the largest tile whose (trajectory, step) pairs still fit the lanes (one pair per lane
-  //    in D1 / D2) and whose LDS fits twice into a CU.
-  // (1024-lane workgroups, one per CU, lose again: C3 143 us at tile 12, C4 390 us at tile 16.)
-  // DDDMR_THREADS=256 / DDDMR_TILE keep the 256-lane shape reachable for experiments.
-  int thr = 512;
-  auto lds_of = [&](int t) { return score_lds_bytes(t, s_tick, k.m, rec_words, k.tab_entries, k.rows_cap); };
-  auto tile_for_256 = [&]() {
-    // most (trajectory, step) slots resident per CU: workgroups per CU (by registers, fewer by LDS) x slots per
-    // workgroup, slots <= lanes
-    int t_best = 1;
-    long best = 0;
-    for (int t = 1; t <= kMaxTile; ++t) {
-      if (t > 1 && t * s_tick > 256) break;
-      const size_t need = lds_of(t) + 1024;   // + static LDS
-      const long wgs = std::min<long>(DDDMR_SCORE_WPE_256, (long)((size_t)(160 * 1024) / need));
-      const long resident = wgs * t * s_tick;
-      if (resident >= best) { best = resident; t_best = t; }
-    }
-    return t_best;
-  };
-  int tile = 1;
-  if (ctx->tile_override > 0) {
-    tile = std::min(ctx->tile_override, kMaxTile);
-    thr = ctx->threads_override > 0 ? ctx->threads_override : 256;
-  } else if (ctx->threads_override == 256) {
-    thr = 256;
-    tile = tile_for_256();
-  } else if (k.n_local > 0) {
-    const int slots512 = ctx->n_cu * 2;
-    const int fit = (k.n_local + slots512 - 1) / slots512;
-    if (fit <= kMaxTile && fit * s_tick <= 2 * 512 && lds_of(fit) <= (size_t)80 * 1024) {
-      tile = std::max(fit, 1);
-    } else {
-      for (int t = 2; t <= kMaxTile; ++t) {
-        if (t * s_tick > 512 || lds_of(t) > (size_t)80 * 1024) break;
-        tile = t;
-      }
-    }
-  }
-  while (tile > 1 && score_lds_bytes(tile, s_tick, k.m, rec_words, k.tab_entries, k.rows_cap) > (size_t)(160 * 1024) / 2) --tile;
-  const size_t lds = score_lds_bytes(tile, s_tick, k.m, rec_words, k.tab_entries, k.rows_cap);
-  if (lds > (size_t)kScoreLdsMax) return fail(ctx, DDDMR_ERR_CAPACITY, "horizon needs %zu bytes of LDS", lds);
+  TickPlan& p = ctx->pend.plan;
+  DevTick& k = p.k;
+  const int theory_id = (int)(th - ctx->theories.data());
+  const bool exchange = ctx->comm || ctx->comm_loopback;
+  std::string err;
+  const int rc = plan_tick(ctx->knobs, ctx->feedback, ctx->cfg, *th, theory_id, *in, w, ctx->cloud_n[cidx], ctx->plan_m,
+                           ctx->plan_last, exchange, &p, &err);
+  if (rc != DDDMR_OK) return fail(ctx, rc, "%s", err.c_str());
   if (ctx->seq == 3 && std::getenv("DDDMR_DEBUG_GRID"))
-    std::fprintf(stderr, "[dddmr] k_score shape: %d lanes, tile %d, %d-step rows, %zu bytes of dynamic LDS (tile+1 would need %zu)\n", thr, tile, s_tick, lds,
-                 score_lds_bytes(tile + 1, s_tick, k.m, rec_words, k.tab_entries, k.rows_cap));
-  k.tile = tile;
-  // Who decodes the winner: shards that run as ONE round of workgroups let the last workgroup do it (a
-  // finalize launch would cost the tick ~3 us); bigger shards run several rounds, where every workgroup's ticket
-  // round trip holds a slot that the next workgroup is waiting for -- there a one-wave k_finalize follows.
-  // The collision walk's probe round (every lane first walks ONE item, spread evenly over the tile's list) settles
-  // colliding trajectories early; when few collide it is a barrier and a scan for nothing.  Measured: 86 %
-  // colliding (C3, r01 scene) k_score 114 us with / 155 us without; 25 % colliding (r02 scenes) C3 126.5 / 124.0 us,
-  // C4 295.6 / 285.2 us.  Decided by the share the previous tick of the same theory and shard measured; either way
-  // gives identical results.
-  const bool same_as_last = ctx->load_theory == (int)(th - ctx->theories.data()) && ctx->load_nlocal == k.n_local;
-  k.probe = ctx->probe_mode >= 0 ? ctx->probe_mode : ((!same_as_last || ctx->collided_share > 0.5f) ? 1 : 0);
-  const bool one_round = k.n_local <= 0 || (k.n_local + tile - 1) / tile <= ctx->n_cu * (thr == 512 ? 2 : 4);
-  k.final_kernel = ctx->final_mode >= 0 ? ctx->final_mode : (one_round ? 0 : 1);
+    std::fprintf(stderr, "[dddmr] k_score shape: %d lanes, tile %d, %d-step rows, %zu bytes of dynamic LDS (tile+1 would need %zu)\n", p.thr, k.tile,
+                 p.s_tick, p.score_lds, plan_score_lds(k, k.tile + 1));
 
-  // small per-tick uploads (sample axes or explicit list).  A rank with an EMPTY shard needs them too when the context
-  // has a communicator: k_resolve decodes the global winner's command from them on every rank (rotate-in-place has two
-  // samples, so rank 0 of three or more ranks owns none).
-  if (k.n_local > 0 || ctx->comm || ctx->comm_loopback) {
-    if (w.list_mode) {
-      std::memcpy(ctx->small_stage, w.list.data(), N * sizeof(float4));
-      HIPCHK(ctx, hipMemcpyAsync(ctx->samples_dev, ctx->small_stage, N * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    } else if (w.ax.size() + w.ay.size() + w.ath.size() <= (size_t)kInlineAxes) {
-      k.axes_inline = 1;                      // axes ride in the kernel arguments
-      k.ay_ofs = (int)w.ax.size();
-      k.ath_ofs = (int)(w.ax.size() + w.ay.size());
-      std::memcpy(k.axes_inl, w.ax.data(), w.ax.size() * sizeof(float));
-      std::memcpy(k.axes_inl + k.ay_ofs, w.ay.data(), w.ay.size() * sizeof(float));
-      std::memcpy(k.axes_inl + k.ath_ofs, w.ath.data(), w.ath.size() * sizeof(float));
-    } else {
-      float* a = ctx->small_stage;
-      std::memcpy(a, w.ax.data(), w.ax.size() * sizeof(float));
-      std::memcpy(a + k.ay_ofs, w.ay.data(), w.ay.size() * sizeof(float));
-      std::memcpy(a + k.ath_ofs, w.ath.data(), w.ath.size() * sizeof(float));
-      HIPCHK(ctx, hipMemcpyAsync(ctx->axes_dev, a, 3 * kMaxAxis * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    }
+  // small per-tick uploads (sample axes or explicit list)
+  if (p.upload == kUploadList) {
+    std::memcpy(ctx->small_stage, w.list.data(), w.list.size() * sizeof(float4));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->samples_dev, ctx->small_stage, w.list.size() * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+  } else if (p.upload == kUploadAxesDev) {
+    float* a = ctx->small_stage;
+    std::memcpy(a, w.ax.data(), w.ax.size() * sizeof(float));
+    std::memcpy(a + k.ay_ofs, w.ay.data(), w.ay.size() * sizeof(float));
+    std::memcpy(a + k.ath_ofs, w.ath.data(), w.ath.size() * sizeof(float));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->axes_dev, a, 3 * kMaxAxis * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   }
   if (k.n_local > 0) {
     // state arrays of the body-frame rollout
-    const size_t need = (size_t)k.n_local * (size_t)s_tick;
+    const size_t need = (size_t)k.n_local * (size_t)p.s_tick;
     if (need > ctx->st_cap || !ctx->traj_info) {
       HIPCHK(ctx, hipDeviceSynchronize());
       if (ctx->st_sc) (void)hipFree(ctx->st_sc);
       if (ctx->st_xy) (void)hipFree(ctx->st_xy);
-          ctx->st_sc = nullptr; ctx->st_xy = nullptr; ctx->st_cap = 0;
+      ctx->st_sc = nullptr; ctx->st_xy = nullptr; ctx->st_cap = 0;
       const size_t cap = need + need / 4 + 1024;
       HIPCHK(ctx, hipMalloc(&ctx->st_sc, cap * sizeof(double2)));
       HIPCHK(ctx, hipMalloc(&ctx->st_xy, cap * sizeof(float2)));
       ctx->st_cap = cap;
       if (!ctx->traj_info) HIPCHK(ctx, hipMalloc(&ctx->traj_info, (size_t)ctx->cfg.max_trajectories * sizeof(TrajInfo)));
     }
-    // Rollout workgroups ride along with k_bin_count.  Few, fat workgroups win: dispatching a
-    // 1024-lane workgroup costs ~12 ns, which is what bounds the launch on big shards (C4:
-    // 64 trajectories per workgroup 44 us, 32: 56 us, 16: 86 us), and on small ones ~128
-    // workgroups are the sweet spot (C2: 16 per workgroup 14.4 us, 32: 12.1 us, 64: 13.2 us).
-    // Round 2: the launch's dynamic LDS (the rollout rows, 16 bytes per pair) is allocated by EVERY workgroup of
-    // k_bin_count, and a CU holds two 1024-lane workgroups at most (wave slots).  Rows sized for two per CU
-    // (<= 74 KB beside ~6 KB of static LDS) keep the whole launch resident in one round at C3 (the rollout
-    // workgroups used to start in two rounds: k_bin_count 28 -> ~18 us).  Within a quarter of that cap the row count
-    // that fills phase B's 1024-lane passes best wins (C3: 50 x 81 pairs = 3.96 passes, C4: 80 x 51 = 3.98).
-    const int s1 = s_tick + 1;
-    const int rt_lds = (int)std::min<size_t>((size_t)kRolloutMax, ((size_t)74 * 1024 - 16) / ((size_t)s1 * 16));
-    int rt = std::min(std::max((k.n_local + 127) / 128, 4), std::max(rt_lds, 1));
-    if (rt == rt_lds && rt > 4) {
-      double best_fill = 0.0;
-      for (int c = rt_lds; c >= rt_lds - rt_lds / 4; --c) {
-        const int items = c * s1;
-        const double fill = (double)items / (double)((items + kBinThreads - 1) / kBinThreads * kBinThreads);
-        if (fill > best_fill + 1e-9) { best_fill = fill; rt = c; }
-      }
-    }
-    if (ctx->rt_override > 0) rt = std::min(ctx->rt_override, kRolloutMax);
-    while (rt > 1 && rollout_lds_bytes(rt, s_tick) > (size_t)128 * 1024) --rt;
-    k.rt = rt;
   }
   if (pending) {
     HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->cloud_ready[cidx], 0));
@@ -1741,58 +1285,21 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
   const bool timed = ctx->timing >= 1 && (ctx->seq % (uint32_t)ctx->timing_every) == 0;
   const bool timed_all = timed && ctx->timing >= 2;
   if (timed_all) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  const int bin_blocks = std::max(1, std::min(2048, (k.n_points + 255) / 256));
-  // one point per lane while that needs few workgroups (latency), kBinPer per lane beyond (dispatch cost)
-  const int per_wg = k.n_points <= 128 * kBinThreads ? kBinThreads : kBinThreads * kBinPer;
-  const int cnt_blocks = std::max(1, std::min(512, (k.n_points + per_wg - 1) / per_wg));
-  const int roll_blocks = k.n_local > 0 ? (k.n_local + k.rt - 1) / k.rt : 0;
-  const size_t roll_lds = k.n_local > 0 ? rollout_lds_bytes(k.rt, s_tick) : 0;
-  k.bin_blocks = cnt_blocks;
-  k.roll_blocks = roll_blocks;
-  // Load feedback: valid when the previous tick scored the same shard of the same theory
-  // (its loads are indexed by local trajectory).  Otherwise this tick deals strided.
-  const int theory_id = (int)(th - ctx->theories.data());
-  k.n_tiles = k.n_local > 0 ? (k.n_local + tile - 1) / tile : 0;
-  k.assign_groups = std::max(1, (k.n_local + kAssignPer * kBinThreads - 1) / (kAssignPer * kBinThreads));
-  k.use_assign = (!ctx->no_assign && k.n_tiles > 1 && k.n_local <= kAssignMax && ctx->load_theory == theory_id &&
-                  ctx->load_nlocal == k.n_local) ? 1 : 0;
-  if (k.use_assign) k.n_tiles = (k.n_tiles + k.assign_groups - 1) / k.assign_groups * k.assign_groups;
-  k.nb_tiles = k.n_tiles;
-  k.r0 = 0;
-  // Several rounds of resident workgroups: full workgroups for the whole rounds, ONE last round of short workgroups
-  // for the rest (rollout_kernels.hip.h, tile_slot()); the lightest trajectories of the load-feedback deal land in it.
-  // Built, bit-identical, measured and left OFF (DDDMR_TAIL_ROUND=1): a k_score workgroup's life is mostly fixed cost
-  // (staging, ~13 barriers, scans), so 512 two-trajectory workgroups cost the C3 launch what its 171 full ones did:
-  // C3 tick 156.2 -> 159.1 us, C4 337.3 -> 330.3 us (profiles/r03_tail_round.txt).
-  if (!one_round && tile > 1 && ctx->tail_round && k.n_local <= kAssignMax) {
-    const int G = k.assign_groups;
-    const long slots = (long)ctx->n_cu * (thr == 512 ? 2 : 4);
-    const long whole = (long)k.n_local / (slots * tile);                         // rounds of full workgroups
-    const long rem = (long)k.n_local - whole * slots * tile;
-    const int t2 = (int)((rem + slots - 1) / slots);                             // trajectories of a short workgroup
-    if (whole >= 1 && rem > 0 && t2 < tile) {
-      const int nb = (int)((whole * slots + G - 1) / G * G), ns = (int)((slots + G - 1) / G * G);
-      if ((long)nb * tile + (long)ns * t2 >= k.n_local) {
-        k.nb_tiles = nb;
-        k.n_tiles = nb + ns;
-        k.r0 = tile - t2;
-      }
-    }
-  }
-  ctx->load_theory = theory_id;
-  ctx->load_nlocal = k.n_local;
+  // traj_load will describe this tick's shard of this theory
+  ctx->feedback.load_theory = theory_id;
+  ctx->feedback.load_nlocal = k.n_local;
   if (k.n_points > 0) {
-    hipLaunchKernelGGL(k_bin_count, dim3(cnt_blocks + roll_blocks + (k.use_assign ? k.assign_groups : 0)), dim3(kBinThreads), roll_lds, ctx->stream,
-                       k, ctx->cloud_dev[cidx], ctx->cell_count, ctx->cell_start, ctx->pt_slot, ctx->tickets,
+    hipLaunchKernelGGL(k_bin_count, dim3(p.cnt_blocks + p.roll_blocks + (k.use_assign ? k.assign_groups : 0)), dim3(kBinThreads), p.roll_lds,
+                       ctx->stream, k, ctx->cloud_dev[cidx], ctx->cell_count, ctx->cell_start, ctx->pt_slot, ctx->tickets,
                        ctx->best_key, ctx->overflow, ctx->axes_dev, ctx->samples_dev, ctx->traj_info, ctx->st_sc,
                        ctx->st_xy, ctx->traj_load, ctx->assign);
-    hipLaunchKernelGGL(k_bin_scatter, dim3(bin_blocks), dim3(256), 0, ctx->stream, k, ctx->cloud_dev[cidx],
+    hipLaunchKernelGGL(k_bin_scatter, dim3(p.bin_blocks), dim3(256), 0, ctx->stream, k, ctx->cloud_dev[cidx],
                        ctx->pt_slot, ctx->cell_start, ctx->sorted, ctx->row_tab);
   } else {
     hipLaunchKernelGGL(k_bin_reset, dim3(1), dim3(256), 0, ctx->stream, k, ctx->cell_count, ctx->cell_start,
                        ctx->best_key, ctx->overflow);
-    if (roll_blocks > 0)
-      hipLaunchKernelGGL(k_rollout, dim3(roll_blocks), dim3(256), roll_lds, ctx->stream, k, ctx->axes_dev,
+    if (p.roll_blocks > 0)
+      hipLaunchKernelGGL(k_rollout, dim3(p.roll_blocks), dim3(256), p.roll_lds, ctx->stream, k, ctx->axes_dev,
                          ctx->samples_dev, ctx->traj_info, ctx->st_sc, ctx->st_xy);
     if (k.use_assign)
       hipLaunchKernelGGL(k_assign, dim3(k.assign_groups), dim3(kBinThreads), 0, ctx->stream, k, ctx->traj_load, ctx->assign);
@@ -1800,12 +1307,11 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
   if (timed) HIPCHK(ctx, hipEventRecord(ctx->evs0, ctx->stream));
   // multi-rank context: k_score leaves the shard's winner on the device (staging record + its slot of
   // the all-reduce), k_resolve publishes the global one
-  const bool exchange = ctx->comm || ctx->comm_loopback;
   DevResult* score_result = exchange ? ctx->local_result_dev : ctx->result_dev;
-  int64_t* score_words = exchange ? ctx->slots_dev + 2 * rank : nullptr;
+  int64_t* score_words = exchange ? ctx->slots_dev + 2 * p.rank : nullptr;
   if (k.n_local > 0) {
     const int wgs = k.n_tiles;
-    const bool lean = !k.want_minmax && !k.rec_pose && k.box_fast;
+    const size_t lds = p.score_lds;
 #define DDDMR_LAUNCH_SCORE(T, L)                                                                                   \
   do { if (k.probe) DDDMR_LAUNCH_SCORE_P(T, L, true); else DDDMR_LAUNCH_SCORE_P(T, L, false); } while (0)
 #define DDDMR_LAUNCH_SCORE_P(T, L, P)                                                                              \
@@ -1813,8 +1319,8 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
                      ctx->st_xy, ctx->plan_dev, ctx->cell_start, ctx->sorted, ctx->costs, ctx->steps,             \
                      ctx->samples_out, ctx->best_key, ctx->overflow, ctx->tickets + 1, score_result, ctx->assign, \
                      ctx->traj_load, score_words, ctx->row_tab)
-    if (thr == 512) { if (lean) DDDMR_LAUNCH_SCORE(512, true); else DDDMR_LAUNCH_SCORE(512, false); }
-    else            { if (lean) DDDMR_LAUNCH_SCORE(256, true); else DDDMR_LAUNCH_SCORE(256, false); }
+    if (p.thr == 512) { if (p.lean) DDDMR_LAUNCH_SCORE(512, true); else DDDMR_LAUNCH_SCORE(512, false); }
+    else              { if (p.lean) DDDMR_LAUNCH_SCORE(256, true); else DDDMR_LAUNCH_SCORE(256, false); }
 #undef DDDMR_LAUNCH_SCORE
 #undef DDDMR_LAUNCH_SCORE_P
   } else {
@@ -1848,11 +1354,8 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
   }
   unbusy.armed = false;   // the cloud buffer stays pinned until tick_collect
   ctx->pend.active = true;
-  ctx->pend.k = k;
-  ctx->pend.s_tick = s_tick;
   ctx->pend.timed = timed;
   ctx->pend.timed_all = timed_all;
-  ctx->pend.head = *out;
   return DDDMR_OK;
 }
 
@@ -1861,8 +1364,12 @@ int tick_collect(dddmr_rollout_ctx* ctx, dddmr_rollout_result* out) {
   if (!ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "tick_end without tick_begin");
   ctx->pend.active = false;
   struct Release { dddmr_rollout_ctx* c; ~Release() { release_cloud(c); } } release{ctx};
-  const DevTick& k = ctx->pend.k;
-  *out = ctx->pend.head;
+  const TickPlan& p = ctx->pend.plan;
+  const DevTick& k = p.k;
+  no_winner(out);
+  out->n_samples = p.n_samples;
+  out->local_begin = p.local_begin;
+  out->n_local = p.n_local;
   const auto prof_c0 = std::chrono::steady_clock::now();
   // The last k_score workgroup stores the result into host-mapped memory and then
   // the tick's sequence number (system-scope release): polling it beats a stream
@@ -1879,13 +1386,13 @@ int tick_collect(dddmr_rollout_ctx* ctx, dddmr_rollout_result* out) {
   if (ctx->host_prof) ctx->prof_ns[2] += std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - prof_c0).count();
   const DevResult r = *ctx->result_host;
   ctx->last_result = r;
-  if (k.n_local > 0) ctx->collided_share = (float)r.n_collided / (float)k.n_local;
+  if (k.n_local > 0) ctx->feedback.collided_share = (float)r.n_collided / (float)k.n_local;
   ctx->last = k;
   ctx->last_window = ctx->pend.window;
   ctx->have_last = true;
   if (r.overflow)
     return fail(ctx, DDDMR_ERR_CAPACITY, "device capacity flag %u (1: trajectory longer than %d steps, 2: cuboid spans more than %d cell rows)",
-                r.overflow, ctx->pend.s_tick, kRows);
+                r.overflow, p.s_tick, kRows);
   out->device_ms = ms;
   out->score_ms = score_ms;
   out->n_points_binned = r.n_binned;
@@ -1908,11 +1415,7 @@ int dddmr_rollout_tick(dddmr_rollout_ctx* ctx, const char* theory_name, const dd
   if (!ctx || !theory_name || !in || !out) return DDDMR_ERR_BAD_ARG;
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "tick while a tick_begin is pending");
-  std::memset(out, 0, sizeof(*out));
-  out->planner_state = DDDMR_ALL_TRAJECTORIES_FAIL;
-  out->best_index = -1;
-  out->best_cost = -1.0;
-  out->key = kKeyNone;
+  no_winner(out);
   const int rc = tick_enqueue(ctx, theory_name, in);
   if (rc != DDDMR_OK) return rc;
   return tick_collect(ctx, out);
@@ -1929,19 +1432,6 @@ int dddmr_rollout_tick_end(dddmr_rollout_ctx* ctx, dddmr_rollout_result* out) {
   if (!ctx || !out) return DDDMR_ERR_BAD_ARG;
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   return tick_collect(ctx, out);
-}
-
-// the command of global sample `idx` of the last collected tick (samples are a closed-form grid, or the
-// tick's explicit list: every rank can recompute the winner's command from its index)
-static void sample_of(const Window& w, int idx, float* vx, float* vy, float* wz) {
-  if (w.list_mode) {
-    *vx = w.list[idx].x; *vy = w.list[idx].y; *wz = w.list[idx].z;
-  } else {
-    const int nth = (int)w.ath.size(), ny = (int)w.ay.size();
-    *vx = w.ax[(idx / nth) / ny];
-    *vy = w.ay[(idx / nth) % ny];
-    *wz = w.ath[idx % nth];
-  }
 }
 
 int dddmr_rollout_resolve(dddmr_rollout_ctx* ctx, int64_t reduced_key, dddmr_rollout_result* inout) {
