@@ -387,7 +387,8 @@ int dddmr_rollout_create(const dddmr_rollout_config* cfg, dddmr_rollout_ctx** ou
     HIPCHK(ctx, hipEventCreate(&ctx->evs0));
     HIPCHK(ctx, hipEventCreate(&ctx->evs1));
     const size_t P = cfg->max_points, N = cfg->max_trajectories;
-    const size_t plan_cap = std::max<uint32_t>(cfg->max_plan_poses, 1);
+    // whole trips of phase P's scalar-load walk plus one chunk of slack for its last request ahead
+    const size_t plan_cap = plan_padded_poses(std::max<uint32_t>(cfg->max_plan_poses, 1));
     for (int i = 0; i < kCloudBufs; ++i) {
       HIPCHK(ctx, hipMalloc(&ctx->cloud_dev[i], P * sizeof(float4)));
       HIPCHK(ctx, hipEventCreateWithFlags(&ctx->cloud_ready[i], hipEventDisableTiming));
@@ -1179,11 +1180,15 @@ int dddmr_rollout_set_prune_plan(dddmr_rollout_ctx* ctx, const double* poses, si
   if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "set_prune_plan while a tick_begin is pending");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   // ModelSharedData::updateData: positions as float PointXYZI (model_shared_data.h:83-91)
-  std::vector<float4> xyz(std::max<size_t>(n_poses, 1));
+  // Behind the poses: copies of the last one up to plan_padded_poses() (k_score's phase P reads whole chunks, and a
+  // duplicate cannot change a minimum).  Written on every call, so a shorter plan after a longer one is padded too.
+  const size_t n_padded = plan_padded_poses(n_poses);
+  std::vector<float4> xyz(n_padded);
   for (size_t i = 0; i < n_poses; ++i)
     xyz[i] = make_float4((float)poses[7 * i + 0], (float)poses[7 * i + 1], (float)poses[7 * i + 2], 0.f);
+  for (size_t i = n_poses; i < n_padded; ++i) xyz[i] = n_poses ? xyz[n_poses - 1] : make_float4(0.f, 0.f, 0.f, 0.f);
   if (n_poses) {
-    HIPCHK(ctx, hipMemcpy(ctx->plan_dev, xyz.data(), n_poses * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(ctx->plan_dev, xyz.data(), n_padded * sizeof(float4), hipMemcpyHostToDevice));
     std::memcpy(ctx->plan_last, poses + 7 * (n_poses - 1), 7 * sizeof(double));
   }
   ctx->plan_m = (uint32_t)n_poses;

@@ -944,6 +944,57 @@ __device__ __forceinline__ f2 l2_simple2(f2 ax, f2 ay, f2 az, float bx, float by
   r = r + d * d;
   return r;
 }
+// ---- phase P, one lane per pose: the prune plan through the scalar unit, one chunk requested ahead ----
+// Every lane walks the whole plan and the plan pose is the same for all lanes, so the poses travel as scalar loads
+// (operands in SGPRs).  The compiler's own schedule was "four s_load_dwordx4, s_waitcnt lgkmcnt(0), 19 VALU" per
+// trip: a full scalar-cache round trip with nothing in flight behind it, 20 times per 80-pose plan.  Here a trip is
+// "request the next chunk, compute on the current one, wait": scalar loads return out of order, lgkmcnt(0) is the only
+// usable wait, so the one wait of a trip falls AFTER its arithmetic.  The compiler does not count loads issued from
+// asm statements, hence the loads and the waits (nothing else) are asm, and every wait names the registers it
+// retires as read-write operands, which keeps their consumers below it and the registers allocated until then.
+// kPlanChunk poses are one request; a trip of the loop is two chunks (two register sets, no copies), so the device
+// copy of the plan is padded with copies of its last pose up to a multiple of kPlanTrip (a duplicate cannot change a
+// minimum) and has kPlanChunk more poses of slack behind that for the last request ahead (plan_padded_poses()).
+constexpr int kPlanChunk = 4;      // (8 poses a chunk: 51 instead of 18 SGPR spills in k_score<512,true,false>)
+constexpr int kPlanTrip = 2 * kPlanChunk;
+__host__ __device__ constexpr size_t plan_padded_poses(size_t m) {
+  return (m + kPlanTrip - 1) / kPlanTrip * kPlanTrip + kPlanChunk;
+}
+typedef float f16v __attribute__((ext_vector_type(16)));    // four float4 poses in 16 consecutive SGPRs
+// issue only: the registers hold nothing until plan_wait() has passed them through
+__device__ __forceinline__ f16v plan_request(const float4* __restrict__ plan_xyz, uint32_t byte_ofs) {
+  f16v c;
+  asm volatile("s_load_dwordx16 %0, %1, %2" : "=s"(c) : "s"(plan_xyz), "s"(byte_ofs));
+  return c;
+}
+// the one wait of a trip.  The empty statement in front of it keeps the arithmetic `best` depends on above the wait
+// (volatile statements keep their order); it is a statement of its own because a VGPR operand on the wait itself
+// makes the compiler treat all its results, the chunk included, as per-lane values.
+__device__ __forceinline__ void plan_wait(f16v& c, float& best) {
+  asm volatile("" : "+v"(best));
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(c));
+}
+// no instruction, placed behind a request: the arithmetic on the current chunk reads it through this statement and
+// so stays below the request (left alone, the compiler issued the request after most of the trip's arithmetic), and
+// the chunk carried round the loop stays in scalar registers (it was moved to VGPRs at the loop's end otherwise).
+__device__ __forceinline__ void plan_current(f16v& c) { asm volatile("" : "+s"(c)); }
+// poses (2i, 2i+1) share the packed lanes; four poses per step exactly as the LDS route pairs them
+__device__ __forceinline__ float plan_chunk_min(float best, const f16v q, float px, float py, float pz) {
+  const f2 da = l2_simple2(f2{q[0], q[4]}, f2{q[1], q[5]}, f2{q[2], q[6]}, px, py, pz);
+  const f2 db = l2_simple2(f2{q[8], q[12]}, f2{q[9], q[13]}, f2{q[10], q[14]}, px, py, pz);
+  return fminf(fminf(best, fminf(da.x, da.y)), fminf(db.x, db.y));
+}
+
+// phase E: the critic stack's kernel arguments as register tuples (8 kinds; 8 doubles = 16 words per weight array)
+typedef int i8v __attribute__((ext_vector_type(8)));
+typedef int i16v __attribute__((ext_vector_type(16)));
+struct StackArgs {
+  i8v kind;
+  i16v w, tw, ow;
+  static __device__ __forceinline__ double weight(const i16v& a, int m) { return __hiloint2double(a[2 * m + 1], a[2 * m]); }
+};
+static_assert(DDDMR_MAX_CRITICS == 8, "StackArgs holds eight slots");
+
 __device__ __forceinline__ f2 dot3_2(f2 dx, f2 dy, f2 dz, float a, float b, float c) {
 #pragma clang fp contract(off)
   return (dx * a + dy * b) + dz * c;
@@ -1646,7 +1697,7 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
   {
     // G lanes share one pair, each scanning a slice of the plan; the minimum is exact
     // whatever the split, so the result does not depend on G.
-    const int alive = alive_pairs_s;
+    const int alive = __builtin_amdgcn_readfirstlane(alive_pairs_s);   // (one value per workgroup: loop bounds in SGPRs)
     int lg = 0;
     while (lg < DDDMR_PSPLIT_MAX && (alive << (lg + 1)) <= kScoreThreads) ++lg;
     const int G = 1 << lg;
@@ -1665,20 +1716,29 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
       }
       // exact 1-NN distance to the prune plan (FLANN float distance)
       float best = 3.402823466e+38f;
-      if (valid && lg == 0) {
+      if (lg == 0) {
         // One lane per pose, every lane walks the WHOLE plan: the plan point is the same for all lanes, so it comes
         // through the scalar unit (uniform index into the kernel argument -> s_load, operands in SGPRs) instead of
         // 64 lanes reading one LDS address -- broadcast 16-byte LDS reads were what bound this phase.
-        int i = 0;
-        for (; i + 4 <= k.m; i += 4) {
-          const float4 p0 = plan_xyz[i], p1 = plan_xyz[i + 1], p2 = plan_xyz[i + 2], p3 = plan_xyz[i + 3];
-          const f2 da = l2_simple2(f2{p0.x, p1.x}, f2{p0.y, p1.y}, f2{p0.z, p1.z}, px, py, pz);
-          const f2 db = l2_simple2(f2{p2.x, p3.x}, f2{p2.y, p3.y}, f2{p2.z, p3.z}, px, py, pz);
-          best = fminf(fminf(best, fminf(da.x, da.y)), fminf(db.x, db.y));
-        }
-        for (; i < k.m; ++i) {
-          const float4 pp = plan_xyz[i];
-          best = fminf(best, l2_simple(pp.x, pp.y, pp.z, px, py, pz));
+        // The next chunk is requested before the arithmetic on the current one (plan_request / plan_wait above); the
+        // device plan is padded to whole trips with copies of its last pose, so there is no remainder and no mask.
+        // The walk sits under wave-uniform conditions only (a wave with one valid lane walks with all its lanes, the
+        // others' minima are never stored): under the per-lane `valid` the compiler carried the chunk in VGPRs.
+        if (k.m > 0 && __ballot(valid) != 0ull) {
+          constexpr uint32_t kChunkBytes = 16u * kPlanChunk;
+          const uint32_t end = 16u * (uint32_t)k.m;
+          f16v ca = plan_request(plan_xyz, 0u);
+          plan_wait(ca, best);
+          for (uint32_t o = 0; o < end; o += 2u * kChunkBytes) {
+            f16v cb = plan_request(plan_xyz, o + kChunkBytes);
+            plan_current(ca);
+            best = plan_chunk_min(best, ca, px, py, pz);
+            plan_wait(cb, best);
+            ca = plan_request(plan_xyz, o + 2u * kChunkBytes);     // (the last one reads the slack)
+            plan_current(cb);
+            best = plan_chunk_min(best, cb, px, py, pz);
+            plan_wait(ca, best);
+          }
         }
       } else if (valid) {
         int i = g * per;
@@ -1741,14 +1801,24 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
       // mpc_critics_ros.cpp:60-81); its non-negative return is then added and thrown away by
       // the collision critic's -1 further down the stack, so 0 stands in for it here.
       const bool dead = cloud_ok && ((need_box && h.hit_box) || (need_mm && h.hit_mm));
-      // (unrolled over the <= 8 stack slots: k.ckind[m] / k.cw[m] with a compile-time m are plain kernel-argument
-      // reads the scalar unit fetches up front, instead of one dependent scalar load chain per loop trip)
+      // The kinds and the three weight arrays of the whole stack are read into locals as ONE group of kernel-argument
+      // loads with one wait (the empty statement makes them opaque there, so no load can sink into the slot chain);
+      // left to itself the compiler loaded ckind[m], waited, branched, loaded the slot's weight and waited again:
+      // two dependent round trips per slot, up to eight slots in series on the one wave the workgroup's end waits for.
+      // The chain below is unrolled over the <= 8 slots, so every index into the locals is a compile-time one.
+      StackArgs sa;
+      __builtin_memcpy(&sa.kind, k.ckind, sizeof(sa.kind));
+      __builtin_memcpy(&sa.w, k.cw, sizeof(sa.w));
+      __builtin_memcpy(&sa.tw, k.ctw, sizeof(sa.tw));
+      __builtin_memcpy(&sa.ow, k.cow, sizeof(sa.ow));
+      asm volatile("" : "+s"(sa.kind), "+s"(sa.w), "+s"(sa.tw), "+s"(sa.ow));
       bool done = false;
 #pragma unroll
       for (int m = 0; m < DDDMR_MAX_CRITICS; ++m) {
         if (m >= k.n_critics || done) continue;
         double r = 0.0;
-        switch (k.ckind[m]) {
+        const double cw_m = sa.weight(sa.w, m);
+        switch (sa.kind[m]) {
           case DDDMR_CRITIC_COLLISION:
             r = (cloud_ok && h.hit_box) ? -1.0 : 0.0;
             break;
@@ -1767,20 +1837,20 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
             break;
           case DDDMR_CRITIC_PURE_PURSUIT:
             if (k.m == 0 || h.steps < 2) r = -4.0;
-            else r = k.ctw[m] * h.pp_dist + k.cow[m] * h.pp_yaw;
+            else r = sa.weight(sa.tw, m) * h.pp_dist + sa.weight(sa.ow, m) * h.pp_yaw;
             break;
           case DDDMR_CRITIC_TOWARD_GLOBAL_PLAN:
             if (k.m < 3) r = 10.0;
             else if (dead) r = 0.0;
-            else r = (double)dr[h.steps - 1] * k.cw[m];
+            else r = (double)dr[h.steps - 1] * cw_m;
             break;
           case DDDMR_CRITIC_SHORTEST_ANGLE: {
             const double thv = (double)h.w;
-            if (k.heading_dev >= 0) r = (thv >= 0) ? k.cw[m] : k.cw[m] * 2;
-            else r = (thv >= 0) ? k.cw[m] * 2 : k.cw[m];
+            if (k.heading_dev >= 0) r = (thv >= 0) ? cw_m : cw_m * 2;
+            else r = (thv >= 0) ? cw_m * 2 : cw_m;
           } break;
           case DDDMR_CRITIC_TWIRLING:
-            r = fabs((double)h.w) * k.cw[m];
+            r = fabs((double)h.w) * cw_m;
             break;
           default:
             r = 0.0;
