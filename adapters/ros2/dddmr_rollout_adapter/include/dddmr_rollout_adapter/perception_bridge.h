@@ -529,5 +529,127 @@ private:
   std::vector<uint8_t> lethal_;
 };
 
+// The perception stack of a context (the stack entries of dddmr_rollout.h): what StackedPerception::doClear_then_Mark,
+// get_min_dGraphValue, aggregateLethal and resetdGraph of a patched Perception3D_ROS call when the lidar layer and the
+// depth camera layer both live on the device.  One pass updates every device layer on its own sensor's observation;
+// the host keeps a mirror of the stacked minimum dGraph and the lethal masks and applies the pass's change list to it
+// (a few hundred nodes around the robot) instead of fetching whole arrays.  When the list overflowed
+// (DDDMR_ERR_CAPACITY) the two full getters resynchronise the mirror.  The layers themselves are created through
+// MarkingLayerBridge::create / DepthLayerBridge::create on the SAME pcl_ground_, before create() here; their own
+// clearThenMark is not called in a context that has a stack.  ready() is false after any failure that leaves the
+// mirror behind the device: the caller then runs its CPU pass until a later create has succeeded.
+class PerceptionStackBridge
+{
+public:
+  int create(dddmr_rollout_ctx * ctx, const dddmr_stack_config & cfg)
+  {
+    ready_ = false;
+    if (!ctx) {return DDDMR_ERR_BAD_ARG;}
+    const int rc = dddmr_rollout_stack_create(ctx, &cfg);
+    if (rc != DDDMR_OK) {return rc;}
+    ctx_ = ctx;
+    cfg_ = cfg;
+    n_ground_ = cfg.n_ground;
+    min_dgraph_.assign(n_ground_ + 1, kStart);
+    mask_.assign(n_ground_ + 1, 0);
+    nodes_.resize(cfg.max_changes ? cfg.max_changes : 1);
+    values_.resize(nodes_.size());
+    masks_.resize(nodes_.size());
+    return resync();                     // the layers may hold state already
+  }
+  bool ready() const {return ready_;}
+
+  // a layer whose dGraph the host computes (static layer, zone layers): values[0 .. n_ground]; shows in the next pass
+  int setHostLayer(int slot, const std::vector<double> & values)
+  {
+    if (!ctx_ || values.size() != n_ground_ + 1) {return DDDMR_ERR_BAD_ARG;}
+    return dddmr_rollout_stack_set_host_layer(ctx_, slot, values.data());
+  }
+
+  // StackedPerception::resetdGraph
+  int reset()
+  {
+    if (!ready_) {return DDDMR_ERR_STATE;}
+    const int rc = dddmr_rollout_stack_reset(ctx_);
+    if (rc != DDDMR_OK) {ready_ = false; return rc;}
+    return resync();
+  }
+
+  // One doClear_then_Mark pass over the device layers, then the mirror follows.  The return code is the pass's: a layer
+  // that failed (its code is in stats) does not stop the mirror from following the stacked arrays, which the device
+  // recomputes whatever the layers returned.  resynced (may be null): the change list overflowed and the full arrays
+  // were fetched.
+  template<class TransformStamped>
+  int clearThenMark(
+    const TransformStamped & trans_b2s, const TransformStamped & trans_gbl2b, dddmr_stack_stats * stats = nullptr,
+    bool * resynced = nullptr)
+  {
+    if (!ready_) {return DDDMR_ERR_STATE;}
+    double b2s[7], g2b[7];
+    toPose7(trans_b2s, b2s);
+    toPose7(trans_gbl2b, g2b);
+    dddmr_stack_stats local;
+    const int rc = dddmr_rollout_stack_update(ctx_, b2s, g2b, stats ? stats : &local);
+    if (resynced) {*resynced = false;}
+    size_t n = 0;
+    int rl = dddmr_rollout_stack_get_changes(ctx_, nodes_.data(), values_.data(), masks_.data(), nodes_.size(), &n);
+    if (rl == DDDMR_ERR_CAPACITY) {
+      if (resynced) {*resynced = true;}
+      rl = resync();
+    } else if (rl == DDDMR_OK) {
+      for (size_t i = 0; i < n; ++i) {
+        if (nodes_[i] >= min_dgraph_.size()) {ready_ = false; return DDDMR_ERR_STATE;}
+        min_dgraph_[nodes_[i]] = values_[i];
+        mask_[nodes_[i]] = masks_[i];
+      }
+    }
+    if (rl != DDDMR_OK) {ready_ = false; return rl;}
+    return rc;
+  }
+
+  // StackedPerception::get_min_dGraphValue(index): the reference's start value beyond the end
+  double minDGraphValue(unsigned int index) const {return index < min_dgraph_.size() ? min_dgraph_[index] : kStart;}
+  uint8_t lethalMask(unsigned int index) const {return index < mask_.size() ? mask_[index] : 0;}
+
+  // StackedPerception::aggregateLethal (:142-155): the device layers' lethal clouds one after the other in plugin order,
+  // each the ground nodes whose flag is set in ascending order; a node lethal in two layers appears twice
+  template<class GroundCloud, class LethalCloud>
+  void aggregateLethal(const GroundCloud & pcl_ground, LethalCloud & out) const
+  {
+    for (int p = 0; p < cfg_.n_order; ++p) {
+      if (cfg_.layer_order[p] >= DDDMR_STACK_HOST0) {continue;}
+      for (size_t i = 0; i < n_ground_ && i < pcl_ground.points.size(); ++i) {
+        if (!((mask_[i] >> p) & 1u)) {continue;}
+        typename LethalCloud::PointType ipt;
+        ipt.x = pcl_ground.points[i].x; ipt.y = pcl_ground.points[i].y; ipt.z = pcl_ground.points[i].z;
+        out.push_back(ipt);
+      }
+    }
+  }
+
+  const std::vector<double> & minDGraph() const {return min_dgraph_;}
+  const std::vector<uint8_t> & lethalMasks() const {return mask_;}
+
+private:
+  static constexpr double kStart = 99999.9;      // stacked_perception.cpp:116
+  int resync()
+  {
+    int rc = dddmr_rollout_stack_get_min_dgraph(ctx_, min_dgraph_.data(), min_dgraph_.size());
+    if (rc == DDDMR_OK) {rc = dddmr_rollout_stack_get_lethal_mask(ctx_, mask_.data(), mask_.size());}
+    ready_ = rc == DDDMR_OK;
+    return rc;
+  }
+
+  dddmr_rollout_ctx * ctx_ = nullptr;
+  bool ready_ = false;
+  dddmr_stack_config cfg_{};
+  size_t n_ground_ = 0;
+  std::vector<double> min_dgraph_;
+  std::vector<uint8_t> mask_;
+  std::vector<uint32_t> nodes_;
+  std::vector<double> values_;
+  std::vector<uint8_t> masks_;
+};
+
 }  // namespace dddmr_rollout_adapter
 #endif

@@ -236,6 +236,25 @@ class DepthLayerStats(C.Structure):
     ]
 
 
+# dddmr_rollout_stack_*: layer ids of dddmr_stack_config.layer_order
+STACK_LIDAR, STACK_DEPTH, STACK_HOST0, STACK_MAX_HOST, STACK_MAX_LAYERS = 0, 1, 2, 4, 6
+STACK_START = 99999.9          # get_min_dGraphValue's start value (stacked_perception.cpp:116)
+
+
+class StackConfig(C.Structure):
+    _fields_ = [
+        ("n_ground", C.c_uint32), ("use_lidar_layer", C.c_int32), ("use_depth_layer", C.c_int32), ("n_host_layers", C.c_int32),
+        ("n_order", C.c_int32), ("layer_order", C.c_int32 * STACK_MAX_LAYERS), ("max_changes", C.c_uint32),
+    ]
+
+
+class StackStats(C.Structure):
+    _fields_ = [
+        ("lidar", MarkingStats), ("depth", DepthLayerStats), ("lidar_rc", C.c_int32), ("depth_rc", C.c_int32),
+        ("depth_skipped", C.c_uint32), ("n_changed", C.c_uint32), ("launches", C.c_uint32), ("host_waits", C.c_uint32),
+    ]
+
+
 # dddmr_rollout_depth_clear_verdicts: bit 0 of a verdict = kept, bits 1-2 = the branch that decided
 DEPTH_CLEAR_KEPT = 1
 DEPTH_CLEAR_OUTSIDE, DEPTH_CLEAR_ATTACHED, DEPTH_CLEAR_INSIDE = 1, 2, 3
@@ -308,6 +327,14 @@ EXPORTED_SYMBOLS = (
     "dddmr_rollout_depth_layer_get_clusters",
     "dddmr_rollout_depth_layer_get_dgraph",
     "dddmr_rollout_depth_layer_get_lethal",
+    "dddmr_rollout_stack_create",
+    "dddmr_rollout_stack_set_host_layer",
+    "dddmr_rollout_stack_update",
+    "dddmr_rollout_stack_get_changes",
+    "dddmr_rollout_stack_get_min_dgraph",
+    "dddmr_rollout_stack_get_lethal_mask",
+    "dddmr_rollout_stack_get_lethal_nodes",
+    "dddmr_rollout_stack_reset",
     "dddmr_rollout_stream_ceiling",
     "dddmr_rollout_selftest_sincos",
     "dddmr_rollout_last_error",
@@ -465,6 +492,25 @@ def load_library() -> C.CDLL:
     lib.dddmr_rollout_depth_layer_get_dgraph.restype = C.c_int
     lib.dddmr_rollout_depth_layer_get_lethal.argtypes = [ctx_p, C.c_void_p, C.c_size_t]
     lib.dddmr_rollout_depth_layer_get_lethal.restype = C.c_int
+    # (a library built from an older commit, which the measurement tools load through DDDMR_LIB_NAME, has no stack entries;
+    # build() and tests/test_capi_cpu.py check that the shipped library exports every symbol, and calling a missing one raises)
+    if hasattr(lib, "dddmr_rollout_stack_create"):
+        lib.dddmr_rollout_stack_create.argtypes = [ctx_p, C.POINTER(StackConfig)]
+        lib.dddmr_rollout_stack_create.restype = C.c_int
+        lib.dddmr_rollout_stack_set_host_layer.argtypes = [ctx_p, C.c_int32, C.c_void_p]
+        lib.dddmr_rollout_stack_set_host_layer.restype = C.c_int
+        lib.dddmr_rollout_stack_update.argtypes = [ctx_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(StackStats)]
+        lib.dddmr_rollout_stack_update.restype = C.c_int
+        lib.dddmr_rollout_stack_get_changes.argtypes = [ctx_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        lib.dddmr_rollout_stack_get_changes.restype = C.c_int
+        lib.dddmr_rollout_stack_get_min_dgraph.argtypes = [ctx_p, C.c_void_p, C.c_size_t]
+        lib.dddmr_rollout_stack_get_min_dgraph.restype = C.c_int
+        lib.dddmr_rollout_stack_get_lethal_mask.argtypes = [ctx_p, C.c_void_p, C.c_size_t]
+        lib.dddmr_rollout_stack_get_lethal_mask.restype = C.c_int
+        lib.dddmr_rollout_stack_get_lethal_nodes.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        lib.dddmr_rollout_stack_get_lethal_nodes.restype = C.c_int
+        lib.dddmr_rollout_stack_reset.argtypes = [ctx_p]
+        lib.dddmr_rollout_stack_reset.restype = C.c_int
     lib.dddmr_rollout_stream_ceiling.argtypes = [ctx_p, C.c_size_t, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.dddmr_rollout_stream_ceiling.restype = C.c_int
     lib.dddmr_rollout_selftest_sincos.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]

@@ -239,6 +239,8 @@ DepthLayerState* depth_layer_of(dddmr_rollout_ctx* ctx, const char* what) {
   return ctx->dlayer;
 }
 
+int depth_layer_update_locked(dddmr_rollout_ctx* ctx, const double T_gbl_base[7], dddmr_depth_layer_stats* stats);
+
 }  // namespace
 
 extern "C" {
@@ -273,6 +275,7 @@ int dddmr_rollout_depth_layer_create(dddmr_rollout_ctx* ctx, const dddmr_depth_l
   s->max_obs = cfg->max_observation_points;
   const int rc = depth_layer_init(ctx, s, ground_xyz, n_ground, ground_stride_bytes, map_xyz, n_map, map_stride_bytes);
   if (rc != DDDMR_OK) { depth_layer_free(s); return rc; }
+  if (ctx->stack) { stack_free(ctx->stack); ctx->stack = nullptr; }      // (a stack holds the layer it was created over)
   if (ctx->dlayer) depth_layer_free(ctx->dlayer);
   ctx->dlayer = s;                                       // only a complete state is ever visible
   return DDDMR_OK;
@@ -294,6 +297,14 @@ int dddmr_rollout_depth_layer_update(dddmr_rollout_ctx* ctx, const double T_gbl_
     if (!std::isfinite(T_gbl_base[i])) return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_layer_update: non-finite transform");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  return depth_layer_update_locked(ctx, T_gbl_base, stats);
+}
+
+}  // extern "C"
+
+namespace {
+// One pass of the layer; producer_mu held, arguments checked.
+int depth_layer_update_locked(dddmr_rollout_ctx* ctx, const double T_gbl_base[7], dddmr_depth_layer_stats* stats) {
   DepthLayerState* s = depth_layer_of(ctx, "depth_layer_update");
   if (!s) return DDDMR_ERR_STATE;
   DcFrustums S;
@@ -419,6 +430,9 @@ int dddmr_rollout_depth_layer_update(dddmr_rollout_ctx* ctx, const double T_gbl_
   return DDDMR_OK;
 }
 #undef DL_LAUNCH
+}  // namespace
+
+extern "C" {
 
 int dddmr_rollout_depth_layer_get_voxels(dddmr_rollout_ctx* ctx, int32_t* xyz_out, size_t capacity, size_t* n) {
   if (!ctx || !n) return DDDMR_ERR_BAD_ARG;

@@ -316,6 +316,8 @@ int marking_fix_ties(dddmr_rollout_ctx* ctx, MarkingState* m, const MarkParams& 
 }
 
 int marking_reset_locked(dddmr_rollout_ctx* ctx);
+int marking_update_on(dddmr_rollout_ctx* ctx, struct MarkingState* m, const float4* obs, uint32_t n_obs, const double T_base_sensor[7],
+                      const double T_gbl_base[7], dddmr_marking_stats* stats);
 
 }  // namespace
 
@@ -339,6 +341,7 @@ int dddmr_rollout_marking_create(dddmr_rollout_ctx* ctx, const dddmr_marking_con
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "marking_create while a tick_begin is pending");
   HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (ctx->stack) { stack_free(ctx->stack); ctx->stack = nullptr; }      // (a stack holds the layer it was created over)
   if (ctx->marking) { marking_free(ctx->marking); ctx->marking = nullptr; }
   auto* m = new MarkingState();
   ctx->marking = m;
@@ -709,7 +712,6 @@ int dddmr_rollout_marking_update(dddmr_rollout_ctx* ctx, const double T_base_sen
   MarkingState* m = ctx->marking;
   if (!m) return fail(ctx, DDDMR_ERR_STATE, "marking_update before marking_create");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const dddmr_marking_config& c = m->cfg;
   // The observation = the context's published aggregate cloud (global frame), pinned like a tick pins it.
   // While a tick_begin is pending -- the reference runs the perception thread's doClear_then_Mark and the planner's
   // tick side by side -- the update runs on a stream of its own, next to the tick's kernels (the two touch disjoint
@@ -739,8 +741,17 @@ int dddmr_rollout_marking_update(dddmr_rollout_ctx* ctx, const double T_base_sen
       cloud_wait_done(ctx, cidx);
     }
   }
-  const uint32_t n_obs = ctx->cloud_n[cidx];
-  const float4* obs = ctx->cloud_dev[cidx];
+  return marking_update_on(ctx, m, ctx->cloud_dev[cidx], ctx->cloud_n[cidx], T_base_sensor, T_gbl_base, stats);
+}
+
+}  // extern "C"
+
+namespace {
+// One doClear_then_Mark pass of the lidar layer on the observation obs[0 .. n_obs) (device, global frame), on m->cur.
+// tick_mu held; the caller keeps `obs` from being recycled until this returns (the update waits for its stream).
+int marking_update_on(dddmr_rollout_ctx* ctx, MarkingState* m, const float4* obs, uint32_t n_obs, const double T_base_sensor[7],
+                      const double T_gbl_base[7], dddmr_marking_stats* stats) {
+  const dddmr_marking_config& c = m->cfg;
   if (n_obs > m->max_obs) return fail(ctx, DDDMR_ERR_CAPACITY, "marking_update: observation of %u points, layer sized for %u", n_obs, m->max_obs);
 
   // ---- transforms (host, double): trans_gbl2s_af3_ = gbl2b * b2s (:236-237), its tf2 form (:238) ----
@@ -814,6 +825,9 @@ int dddmr_rollout_marking_update(dddmr_rollout_ctx* ctx, const double T_base_sen
     return fail(ctx, DDDMR_ERR_CAPACITY, "marking_update: capacity flag %u (1: max_markings, 2: max_cluster_points, 4: a cluster more than 3.2 km (51 m in z) from the window)", out.overflow);
   return DDDMR_OK;
 }
+}  // namespace
+
+extern "C" {
 
 int dddmr_rollout_marking_route_counts(dddmr_rollout_ctx* ctx, uint32_t* updates_fused, uint32_t* updates_general,
                                        uint32_t* launches_last_update) {

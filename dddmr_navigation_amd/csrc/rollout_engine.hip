@@ -42,6 +42,8 @@ struct DepthMarkState;                     // the depth camera's selfMark, depth
 void depth_mark_free(DepthMarkState* s);
 struct DepthLayerState;                    // the depth camera layer's store, dGraph and lethal set, depth_layer.hip.h
 void depth_layer_free(DepthLayerState* s);
+struct StackState;                         // the perception stack over the two layers, perception_stack.hip.h
+void stack_free(StackState* s);
 
 }  // namespace
 
@@ -60,6 +62,12 @@ struct dddmr_rollout_ctx {
   // device memory
   float4* cloud_dev[kCloudBufs] = {nullptr, nullptr, nullptr};
   uint32_t cloud_n[kCloudBufs] = {0, 0, 0};
+  // where a published aggregate came from (recorded by publish_cloud under cloud_mu): the sources' point counts in source
+  // order with the lidar ones flagged, or cloud_from_sources false after a set_cloud.  What the perception stack cuts the
+  // lidar sources' observation out of a pinned aggregate with.
+  uint32_t cloud_src_n[kCloudBufs][DDDMR_MAX_SOURCES] = {};
+  uint8_t cloud_src_lidar[kCloudBufs] = {0, 0, 0};     // bit i: source i is a lidar source
+  bool cloud_from_sources[kCloudBufs] = {true, true, true};   // (nothing published yet: the sources' empty aggregate)
   uint2* pt_slot = nullptr;
   Pt3* sorted = nullptr;
   uint32_t *cell_count = nullptr, *cell_start = nullptr;
@@ -140,6 +148,7 @@ struct dddmr_rollout_ctx {
   MarkingState* marking = nullptr;   // dddmr_rollout_marking_create
   DepthMarkState* dmark = nullptr;   // dddmr_rollout_depth_mark_create
   DepthLayerState* dlayer = nullptr; // dddmr_rollout_depth_layer_create
+  StackState* stack = nullptr;       // dddmr_rollout_stack_create (tick_mu)
 
   std::mutex tick_mu;
   std::mutex err_mu;        // last_error is written by tick and sensor threads alike
@@ -268,6 +277,10 @@ size_t dddmr_rollout_sizeof(int which) {
     case 10: return sizeof(dddmr_depth_frustum_config);
     case 11: return sizeof(dddmr_depth_mark_config);
     case 12: return sizeof(dddmr_depth_mark_stats);
+    case 13: return sizeof(dddmr_depth_layer_config);
+    case 14: return sizeof(dddmr_depth_layer_stats);
+    case 15: return sizeof(dddmr_stack_config);
+    case 16: return sizeof(dddmr_stack_stats);
     default: return 0;
   }
 }
@@ -297,6 +310,7 @@ void dddmr_rollout_destroy(dddmr_rollout_ctx* ctx) {
   if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
   if (ctx->marking) { marking_free(ctx->marking); ctx->marking = nullptr; }
   if (ctx->dmark) { depth_mark_free(ctx->dmark); ctx->dmark = nullptr; }
+  if (ctx->stack) { stack_free(ctx->stack); ctx->stack = nullptr; }
   if (ctx->dlayer) { depth_layer_free(ctx->dlayer); ctx->dlayer = nullptr; }
   if (ctx->comm) (void)rccl().comm_destroy(ctx->comm);
   if (ctx->slots_dev) (void)hipFree(ctx->slots_dev);
@@ -452,10 +466,17 @@ int dddmr_rollout_create(const dddmr_rollout_config* cfg, dddmr_rollout_ctx** ou
   return DDDMR_OK;
 }
 
-// Publish a device-side cloud buffer as the new front buffer.
-static void publish_cloud(dddmr_rollout_ctx* ctx, int idx, uint32_t n) {
+// Publish a device-side cloud buffer as the new front buffer.  producer_mu held.  from_sources: 0 a cloud handed over
+// with set_cloud, 1 the concatenation of src_n[] in source order, 2 the single-producer set_scan (all of it is lidar 0).
+static void publish_cloud(dddmr_rollout_ctx* ctx, int idx, uint32_t n, int from_sources) {
   std::lock_guard<std::mutex> lk(ctx->cloud_mu);
   ctx->cloud_n[idx] = n;
+  ctx->cloud_from_sources[idx] = from_sources != 0;
+  ctx->cloud_src_lidar[idx] = 0;
+  for (int i = 0; i < DDDMR_MAX_SOURCES; ++i) {
+    ctx->cloud_src_n[idx][i] = from_sources == 1 ? ctx->src_n[i] : (from_sources == 2 && i == 0 ? n : 0u);
+    if (from_sources == 2 ? i == 0 : ctx->src_is_lidar[i]) ctx->cloud_src_lidar[idx] |= (uint8_t)(1u << i);
+  }
   ctx->front = idx;
   ctx->wait_pending[idx] = true;
 }
@@ -518,7 +539,7 @@ int dddmr_rollout_set_cloud(dddmr_rollout_ctx* ctx, const float* xyzi, size_t n_
                                  ctx->copy_stream));
   }
   HIPCHK(ctx, hipEventRecord(ctx->cloud_ready[back], ctx->copy_stream));
-  publish_cloud(ctx, back, (uint32_t)n_points);
+  publish_cloud(ctx, back, (uint32_t)n_points, 0);
   return DDDMR_OK;
 }
 
@@ -585,7 +606,7 @@ static int set_scan_impl(dddmr_rollout_ctx* ctx, int source, const float* xyz, s
   }
   // the tick's stream waits on this event, so the feed kernels need not have retired yet
   HIPCHK(ctx, hipEventRecord(ctx->cloud_ready[back], ctx->copy_stream));
-  publish_cloud(ctx, back, n_all);
+  publish_cloud(ctx, back, n_all, source >= 0 ? 1 : 2);
   if (n_out_points) *n_out_points = n_out;
   if (n_aggregate) *n_aggregate = n_all;
   return DDDMR_OK;
@@ -646,7 +667,7 @@ static int publish_sources(dddmr_rollout_ctx* ctx, uint32_t* n_aggregate) {
     at += ctx->src_n[i];
   }
   HIPCHK(ctx, hipEventRecord(ctx->cloud_ready[back], ctx->copy_stream));
-  publish_cloud(ctx, back, (uint32_t)at);
+  publish_cloud(ctx, back, (uint32_t)at, 1);
   *n_aggregate = (uint32_t)at;
   return DDDMR_OK;
 }
@@ -1846,3 +1867,4 @@ int dddmr_rollout_get_best_cuboids(dddmr_rollout_ctx* ctx, float* vertices_out, 
 #include "marking_host.hip.h"
 #include "depth_mark.hip.h"
 #include "depth_layer.hip.h"
+#include "perception_stack.hip.h"

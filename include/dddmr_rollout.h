@@ -492,8 +492,9 @@ int dddmr_rollout_depth_mark_clusters(dddmr_rollout_ctx* ctx, const double T_gbl
    kept in device memory between calls: only parameters go in and counters come out.
 
    dddmr_rollout_depth_layer_create takes the inputs of dddmr_rollout_depth_mark_create plus the layer's window, radii and
-   capacities.  It is independent of depth_mark_create and of marking_create: a context may have any of them (the
-   documented limit stays: no depth sources in a context that feeds a lidar marking layer).  DDDMR_ERR_BAD_ARG: a
+   capacities.  It is independent of depth_mark_create and of marking_create: a context may have any of them (dddmr_rollout_marking_update
+   takes the whole aggregate, depth points included, as the lidar observation: a context with both kinds of sensors
+   updates its layers through dddmr_rollout_stack_update, which gives each layer its own sensor's observation).  DDDMR_ERR_BAD_ARG: a
    resolution, the tolerance, the inflation radius, the window or the marking height is not positive and finite, a
    negative minimum cluster size, a capacity of 0, a bad pointer / stride; DDDMR_ERR_CAPACITY: max_observation_points
    above 2^20 or max_markings above 2^24; DDDMR_ERR_STATE: a dddmr_rollout_tick_begin is pending.  A refused call leaves
@@ -793,6 +794,100 @@ int dddmr_rollout_marking_get_lethal(dddmr_rollout_ctx* ctx, uint8_t* flags_out,
    may be NULL. */
 int dddmr_rollout_marking_route_counts(dddmr_rollout_ctx* ctx, uint32_t* updates_fused,
                                        uint32_t* updates_general, uint32_t* launches_last_update);
+
+/* Perception stack on the device: both layers in one pass, the stacked minimum dGraph, the lethal masks and the list of
+   ground nodes that changed (additions to ABI version 2; no existing struct or entry changes, and the layers' own
+   entries answer exactly as before in a context that has a stack).  The counterpart of StackedPerception
+   (src/dddmr_perception_3d/src/stacked_perception.cpp:72-126,142-155) around "a velodyne plus realsense".
+
+   Layers are named by id: DDDMR_STACK_LIDAR (the dddmr_rollout_marking_* layer), DDDMR_STACK_DEPTH (the
+   dddmr_rollout_depth_layer_* layer) and DDDMR_STACK_HOST0 + slot for up to DDDMR_STACK_MAX_HOST layers whose dGraph
+   the host computes (the static layer, static_layer.cpp:233-285,430-435, whose edge detection runs PCL's RANSAC; the zone
+   layers, no_entry_layer.cpp:225-304).  layer_order[0 .. n_order) is the plugin order: every layer of the stack exactly
+   once.  The minimum is taken in that order, bit i of a lethal mask is the layer at position i (always 0 for a host
+   layer, which has no lethal set), and dddmr_rollout_stack_get_lethal_nodes lists the device layers in that order.
+
+   dddmr_rollout_stack_create: a device layer that is asked for must exist already (DDDMR_ERR_STATE) with cfg.n_ground
+   ground nodes (DDDMR_ERR_BAD_ARG): the caller passes the SAME pcl_ground_ to marking_create and depth_layer_create, as
+   the reference's plugins share shared_data_->pcl_ground_; the stack indexes both dGraphs by the same node number and
+   cannot check more than the count.  A stack of host layers only is allowed.  DDDMR_ERR_BAD_ARG: more than
+   DDDMR_STACK_MAX_HOST host layers, a layer_order that is not a permutation of the stack's layers, n_ground >= 2^30;
+   DDDMR_ERR_CAPACITY: max_changes above 2^28; DDDMR_ERR_STATE: a dddmr_rollout_tick_begin is pending.  A refused call
+   leaves an earlier stack in place; a successful one replaces it, with the stacked arrays recomputed from the layers as
+   they are and an empty change list (host slots start unset).  A later marking_create or depth_layer_create drops the
+   stack: every stack call then answers DDDMR_ERR_STATE until the next stack_create.
+
+   dddmr_rollout_stack_set_host_layer uploads values[0 .. n_ground] once; they stay until the slot is replaced (NULL
+   unsets it).  An unset slot does not take part.  The stacked arrays change with the next stack_update, whose change
+   list shows it.
+
+   dddmr_rollout_stack_update is one doClear_then_Mark pass (stacked_perception.cpp:82-88) over the device layers, each on
+   its own sensor's observation:
+     lidar layer: exactly the pass dddmr_rollout_marking_update runs (both routes, tie fixing, housekeeping), but on the
+       LIDAR SOURCES' observation only: the segments of the published aggregate that came from sources fed with
+       set_scan / set_scan_source, in source order (the aggregate is pinned like a tick pins it and carries the
+       per-source counts recorded when it was published, so a concurrent feed cannot tear it).  A context with several
+       lidar sources gives their concatenation to ONE store; the reference would hold one store per plugin (a limit).
+       DDDMR_ERR_STATE when the published aggregate did not come from the sources (a set_cloud since the last feed).
+     depth layer: exactly the pass dddmr_rollout_depth_layer_update runs (it reads the depth sources only).  Where the
+       reference's plugin returns early -- no depth source, or a camera without a frustum yet
+       (depth_camera_layer.cpp:266-269, :482-485) -- the layer is skipped for this pass: stats.depth_skipped = 1,
+       depth_rc = DDDMR_OK, its state untouched, and the other layer runs.
+     stacked arrays: k_stack_min recomputes them and the change list whatever the layers returned, so they always
+       equal the layers' current arrays: v = 99999.9; for each layer in order: v = (x < v) ? x : v -- std::min(tmp, x)
+       of stacked_perception.cpp:114-126, so a NaN in a host layer leaves v alone and nothing comes out above 99999.9.
+   Returns the first failing layer's code (lidar first), DDDMR_OK otherwise; stats (required) is filled either way.
+   T_base_sensor is the lidar's; both transforms may be NULL in a stack without device layers.  DDDMR_ERR_STATE while a
+   dddmr_rollout_tick_begin is pending (the layers' own entries may run beside a tick; the stack does not yet).
+   host_waits: the lidar pass counts as its one regular wait, the depth pass reports its own, the stack adds one.
+
+   dddmr_rollout_stack_get_changes: the nodes whose stacked value (as a bit pattern) or lethal mask differs from before
+   the last update, each exactly once, in no particular order, with the new value and mask.  Any output may be NULL;
+   all NULL: count only.  More changes than max_changes or than capacity: DDDMR_ERR_CAPACITY with *n the true count and
+   nothing written; dddmr_rollout_stack_get_min_dgraph / _get_lethal_mask (n_ground + 1 entries each, the last node
+   unused by the layers) are then the way to resynchronise.  No device work: the list is in host memory when
+   stack_update returns.
+
+   dddmr_rollout_stack_get_lethal_nodes is aggregateLethal (:142-155): for each device layer in layer_order, that layer's
+   lethal ground nodes (< n_ground) in ascending order, one list after the other; a node lethal in two layers appears
+   twice, as in the reference's concatenated cloud.  node_out NULL: count only.
+
+   dddmr_rollout_stack_reset is StackedPerception::resetdGraph (:92-102): both layers are reset, the stacked arrays
+   recomputed, the change list emptied; host slots keep their values. */
+#define DDDMR_STACK_LIDAR 0
+#define DDDMR_STACK_DEPTH 1
+#define DDDMR_STACK_HOST0 2
+#define DDDMR_STACK_MAX_HOST 4
+#define DDDMR_STACK_MAX_LAYERS 6
+typedef struct {
+  uint32_t n_ground;
+  int32_t use_lidar_layer, use_depth_layer;
+  int32_t n_host_layers;                              /* 0 .. DDDMR_STACK_MAX_HOST: slots 0 .. n_host_layers - 1 */
+  int32_t n_order;                                    /* = the number of layers of the stack */
+  int32_t layer_order[DDDMR_STACK_MAX_LAYERS];
+  uint32_t max_changes;                               /* capacity of the change list */
+} dddmr_stack_config;
+
+typedef struct {
+  dddmr_marking_stats lidar;
+  dddmr_depth_layer_stats depth;
+  int32_t lidar_rc, depth_rc;
+  uint32_t depth_skipped;
+  uint32_t n_changed;                                 /* the true count, also beyond max_changes */
+  uint32_t launches;                                  /* device operations of the pass: the layers' own counts plus the stack's */
+  uint32_t host_waits;
+} dddmr_stack_stats;
+
+int dddmr_rollout_stack_create(dddmr_rollout_ctx* ctx, const dddmr_stack_config* cfg);
+int dddmr_rollout_stack_set_host_layer(dddmr_rollout_ctx* ctx, int32_t slot, const double* values /* [n_ground + 1] or NULL */);
+int dddmr_rollout_stack_update(dddmr_rollout_ctx* ctx, const double T_base_sensor[7], const double T_gbl_base[7],
+                               dddmr_stack_stats* stats);
+int dddmr_rollout_stack_get_changes(dddmr_rollout_ctx* ctx, uint32_t* node_out, double* value_out, uint8_t* lethal_mask_out,
+                                    size_t capacity, size_t* n);
+int dddmr_rollout_stack_get_min_dgraph(dddmr_rollout_ctx* ctx, double* values_out, size_t capacity);
+int dddmr_rollout_stack_get_lethal_mask(dddmr_rollout_ctx* ctx, uint8_t* mask_out, size_t capacity);
+int dddmr_rollout_stack_get_lethal_nodes(dddmr_rollout_ctx* ctx, uint32_t* node_out, size_t capacity, size_t* n);
+int dddmr_rollout_stack_reset(dddmr_rollout_ctx* ctx);
 
 /* Measurement aid ("a measured stream-copy ceiling on the same GPU"): streams
    `bytes` (>= 1 GiB recommended: beyond the 256 MB of MALL) `reps` times through a float4 copy
