@@ -5,6 +5,8 @@
 //   ... selfClear + selfMark, global mode           (:306-628; StackedPerception::doClear_then_Mark,
 //                                                    src/stacked_perception.cpp:72-90)               -> MarkingLayerBridge
 //   ... get_dGraphValue / updateLethalPointCloud    (:838-841, :283-304)                             -> MarkingLayerBridge
+//   ImageProjection::cloudHandler's front half + cbSensor
+//                          (dddmr_lego_loam/lego_loam_bor/src/imageProjection.cpp:280-314, :582-592) -> feedSweep(), sweepCloud()
 //   PathBlockedStrategy::selfMark                   (plugins/path_blocked_strategy.cpp:56-100)       -> pathBlocked()
 //   DepthCameraObservationBuffer::bufferCloud, local mode
 //                                    (plugins/depth_camera/depth_camera_observation_buffer.cpp:78-187) -> feedDepthFrame()
@@ -86,6 +88,55 @@ inline int feedScanSource(
     perception_window_size, marking_height, n_source_out, n_aggregate_out);
   if (rc == DDDMR_OK) {SharedContext::noteDeviceFeed();}
   return rc;
+}
+
+// ImageProjection::cloudHandler's front half and cbSensor in one call: the RAW sweep in the lidar's own frame
+// (pcl::fromROSMsg output of the lidar topic, before the node's pitch removal) goes to lidar sweep source `source`,
+// configured with dddmr_rollout_set_lidar_sweep_source from the node's laser.* / imageProjection.* parameters and the
+// mount pitch.  The plugin's `topic` then names the raw lidar instead of segmented_cloud_pure.  trans_b2s takes the
+// frame "<sensor>_pitch_removed" (the frame the node stamps its clouds with) to the base frame.  There is no stitcher
+// on sweep sources.  Returns the library's code and notes a device feed on DDDMR_OK only; on any other code nothing on
+// the device has changed and the caller runs its CPU path for this sweep.
+template<class Cloud, class TransformStamped>
+inline int feedSweep(
+  dddmr_rollout_ctx * ctx, int source, const Cloud & sweep_sensor_frame, const TransformStamped & trans_b2s,
+  const TransformStamped & trans_gbl2b, double perception_window_size, double marking_height,
+  uint32_t * n_segmented_out = nullptr, uint32_t * n_source_out = nullptr, uint32_t * n_aggregate_out = nullptr)
+{
+  if (!ctx) {return DDDMR_ERR_BAD_ARG;}
+  double b2s[7], g2b[7];
+  toPose7(trans_b2s, b2s);
+  toPose7(trans_gbl2b, g2b);
+  const size_t n = sweep_sensor_frame.points.size();
+  const int rc = dddmr_rollout_set_lidar_sweep(
+    ctx, source, n ? &sweep_sensor_frame.points[0].x : nullptr, n, sizeof(sweep_sensor_frame.points[0]), b2s, g2b,
+    perception_window_size, marking_height, n_segmented_out, n_source_out, n_aggregate_out);
+  if (rc == DDDMR_OK) {SharedContext::noteDeviceFeed();}
+  return rc;
+}
+
+// What the node would have published on segmented_cloud_pure for the source's latest accepted sweep, for a caller
+// that still wants the topic: points in raster order, the segment's label in `intensity` (pcl::PointXYZI).
+template<class Cloud>
+inline int sweepCloud(dddmr_rollout_ctx * ctx, int source, Cloud & out)
+{
+  if (!ctx) {return DDDMR_ERR_BAD_ARG;}
+  size_t n = 0;
+  int rc = dddmr_rollout_get_lidar_sweep_cloud(ctx, source, nullptr, 0, &n);
+  if (rc != DDDMR_OK) {return rc;}
+  std::vector<float> xyzl(4 * n);
+  if (n) {
+    rc = dddmr_rollout_get_lidar_sweep_cloud(ctx, source, xyzl.data(), n, &n);
+    if (rc != DDDMR_OK) {return rc;}
+  }
+  out.points.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    out.points[i].x = xyzl[4 * i + 0];
+    out.points[i].y = xyzl[4 * i + 1];
+    out.points[i].z = xyzl[4 * i + 2];
+    out.points[i].intensity = xyzl[4 * i + 3];
+  }
+  return DDDMR_OK;
 }
 
 // DepthCameraObservationBuffer::bufferCloud for the local planner: the raw frame in the SENSOR frame (pcl::fromROSMsg

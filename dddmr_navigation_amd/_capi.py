@@ -185,6 +185,20 @@ class DepthImageConfig(C.Structure):
     ]
 
 
+class LidarSweepConfig(C.Structure):
+    """dddmr_lidar_sweep_config: ImageProjection's laser.* / imageProjection.* parameters and the mount pitch."""
+    _fields_ = [
+        ("num_vertical_scans", C.c_uint32), ("num_horizontal_scans", C.c_uint32),
+        ("vertical_angle_bottom", C.c_double), ("vertical_angle_top", C.c_double),
+        ("ground_scan_index", C.c_uint32),
+        ("segment_theta", C.c_double),
+        ("segment_valid_point_num", C.c_uint32), ("segment_valid_line_num", C.c_uint32),
+        ("minimum_detection_range", C.c_double), ("maximum_detection_range", C.c_double),
+        ("sensor_mount_angle", C.c_double),
+        ("max_sweep_points", C.c_uint32), ("flags", C.c_uint32),
+    ]
+
+
 class DepthFrustumConfig(C.Structure):
     """dddmr_depth_frustum_config: the depth buffer's FOV_W / FOV_V (radians) and obstacle_min_range / obstacle_max_range."""
     _fields_ = [
@@ -313,6 +327,10 @@ EXPORTED_SYMBOLS = (
     "dddmr_rollout_set_depth_image_source",
     "dddmr_rollout_set_depth_image",
     "dddmr_rollout_get_depth_image_cloud",
+    "dddmr_rollout_set_lidar_sweep_source",
+    "dddmr_rollout_set_lidar_sweep",
+    "dddmr_rollout_get_lidar_sweep_cloud",
+    "dddmr_rollout_get_lidar_sweep_image",
     "dddmr_rollout_set_depth_frustum",
     "dddmr_rollout_get_depth_frustum",
     "dddmr_rollout_depth_frustum_test",
@@ -459,6 +477,18 @@ def load_library() -> C.CDLL:
     lib.dddmr_rollout_set_depth_image.restype = C.c_int
     lib.dddmr_rollout_get_depth_image_cloud.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.dddmr_rollout_get_depth_image_cloud.restype = C.c_int
+    # (a library built from an older commit, loaded through DDDMR_LIB_NAME by tools/lidar_sweep_bench.py, has no sweep entries)
+    if hasattr(lib, "dddmr_rollout_set_lidar_sweep_source"):
+        lib.dddmr_rollout_set_lidar_sweep_source.argtypes = [ctx_p, C.c_int32, C.POINTER(LidarSweepConfig)]
+        lib.dddmr_rollout_set_lidar_sweep_source.restype = C.c_int
+        lib.dddmr_rollout_set_lidar_sweep.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_double),
+                                                      C.POINTER(C.c_double), C.c_double, C.c_double, C.POINTER(C.c_uint32),
+                                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.dddmr_rollout_set_lidar_sweep.restype = C.c_int
+        lib.dddmr_rollout_get_lidar_sweep_cloud.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        lib.dddmr_rollout_get_lidar_sweep_cloud.restype = C.c_int
+        lib.dddmr_rollout_get_lidar_sweep_image.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.dddmr_rollout_get_lidar_sweep_image.restype = C.c_int
     lib.dddmr_rollout_set_depth_frustum.argtypes = [ctx_p, C.c_int32, C.POINTER(DepthFrustumConfig), C.POINTER(C.c_double)]
     lib.dddmr_rollout_set_depth_frustum.restype = C.c_int
     lib.dddmr_rollout_get_depth_frustum.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

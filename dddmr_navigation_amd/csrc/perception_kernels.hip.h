@@ -54,18 +54,22 @@ struct PerceptionScratch {
   std::deque<uint32_t> stitched;       // point counts of the queued scans
 };
 
-__global__ __launch_bounds__(256) void k_feed_insert(FeedParams f, const float* __restrict__ scan, int stride_floats,
-                                                     VoxelView table) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= f.n) return;
-  const float* sp = scan + (size_t)i * stride_floats;
-  const float sx = sp[0], sy = sp[1], sz = sp[2];
+// one raw record through cbSensor's transform, crop and voxel insert
+__device__ __forceinline__ void feed_insert_record(const FeedParams& f, float sx, float sy, float sz, const VoxelView& table) {
   if (!(isfinite(sx) && isfinite(sy) && isfinite(sz))) return;
   const float3 p = affine_to_float(f.Rbs, f.tbs, sx, sy, sz);
   // pcl::PassThrough keeps limit_min <= v <= limit_max
   if (p.x < -f.window || p.x > f.window || p.y < -f.window || p.y > f.window || p.z < 0.0f || p.z > f.height) return;
   // pcl::VoxelGrid with a 0.1f leaf -> inverse 10.0f
   voxel_insert(table, voxel_key(p.x, p.y, p.z, 1.0f / 0.1f), (double)p.x, (double)p.y, (double)p.z, 1u);
+}
+
+__global__ __launch_bounds__(256) void k_feed_insert(FeedParams f, const float* __restrict__ scan, int stride_floats,
+                                                     VoxelView table) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= f.n) return;
+  const float* sp = scan + (size_t)i * stride_floats;
+  feed_insert_record(f, sp[0], sp[1], sp[2], table);
 }
 
 __global__ __launch_bounds__(256) void k_feed_emit(FeedParams f, VoxelView table, float4* __restrict__ out,

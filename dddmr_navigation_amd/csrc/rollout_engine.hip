@@ -28,6 +28,7 @@
 #include "depth_feed.hip.h"
 #include "depth_image.hip.h"
 #include "depth_clear.hip.h"
+#include "lidar_sweep.hip.h"
 #include "measure_kernels.hip.h"
 
 using namespace dddmr;
@@ -110,7 +111,10 @@ struct dddmr_rollout_ctx {
   DepthSource* depth[kMaxSources] = {};
   // non-null for a depth source that is fed images (dddmr_rollout_set_depth_image_source); depth[i] is set as well
   DepthImage* dimg[kMaxSources] = {};
-  bool src_is_lidar[kMaxSources] = {};                 // a scan has been fed under this id
+  bool src_is_lidar[kMaxSources] = {};                 // a scan has been fed under this id, or it is a sweep source
+  // lidar sources fed raw sweeps (dddmr_rollout_set_lidar_sweep_source): src_cloud[i] then aliases the sweep's current
+  // observation buffer and src_is_lidar[i] is set
+  LidarSweep* sweep[kMaxSources] = {};
   // frustums of the depth sources (dddmr_rollout_set_depth_frustum) and the clearing verdicts' scratch (depth_clear.hip.h)
   DcFrustum frustum[kMaxSources] = {};
   bool has_frustum[kMaxSources] = {};
@@ -281,6 +285,7 @@ size_t dddmr_rollout_sizeof(int which) {
     case 14: return sizeof(dddmr_depth_layer_stats);
     case 15: return sizeof(dddmr_stack_config);
     case 16: return sizeof(dddmr_stack_stats);
+    case 17: return sizeof(dddmr_lidar_sweep_config);
     default: return 0;
   }
 }
@@ -329,6 +334,7 @@ void dddmr_rollout_destroy(dddmr_rollout_ctx* ctx) {
   if (ctx->dclear) { dc_free(*ctx->dclear); delete ctx->dclear; }
   for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) {
     if (ctx->depth[i]) { depth_free(*ctx->depth[i]); delete ctx->depth[i]; ctx->src_cloud[i] = nullptr; }
+    if (ctx->sweep[i]) { sweep_free(*ctx->sweep[i]); delete ctx->sweep[i]; ctx->src_cloud[i] = nullptr; }
     if (ctx->dimg[i]) { dimg_free(*ctx->dimg[i]); delete ctx->dimg[i]; }
     if (ctx->src_feed[i]) { perception_free(*ctx->src_feed[i]); delete ctx->src_feed[i]; }
     if (ctx->src_cloud[i]) (void)hipFree(ctx->src_cloud[i]);
@@ -557,6 +563,7 @@ static int set_scan_impl(dddmr_rollout_ctx* ctx, int source, const float* xyz, s
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
   if (source < 0 && ctx->multi_source) source = 0;              // once several sensors feed, plain set_scan is sensor 0
   if (source >= 0 && ctx->depth[source]) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_scan: source %d is a depth camera source", source);
+  if (ctx->sweep[std::max(source, 0)]) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_scan: source %d is a lidar sweep source", std::max(source, 0));
   if (source < 0) ctx->src_is_lidar[0] = true;                  // the single-producer form is the lidar of source 0
   PerceptionScratch* scratch = &ctx->feed;
   if (source > 0) {
@@ -632,6 +639,7 @@ int dddmr_rollout_set_stitcher(dddmr_rollout_ctx* ctx, int32_t stitcher_num) {
   if (!ctx || stitcher_num < 0) return DDDMR_ERR_BAD_ARG;
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
   if (ctx->depth[0]) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_stitcher: source 0 is a depth camera source");
+  if (ctx->sweep[0]) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_stitcher: source 0 is a lidar sweep source (no stitcher on sweeps)");
   ctx->feed.stitcher_num = stitcher_num;
   ctx->feed.stitched.clear();
   return DDDMR_OK;
@@ -643,6 +651,7 @@ int dddmr_rollout_set_stitcher_source(dddmr_rollout_ctx* ctx, int32_t source_id,
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
   if (ctx->depth[source_id]) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_stitcher: source %d is a depth camera source", source_id);
+  if (ctx->sweep[source_id]) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_stitcher: source %d is a lidar sweep source (no stitcher on sweeps)", source_id);
   if (!ctx->src_feed[source_id]) {
     auto* ps = new PerceptionScratch();
     if (perception_alloc(*ps, ctx->cfg.max_points) != 0) { perception_free(*ps); delete ps; return fail(ctx, DDDMR_ERR_HIP, "set_stitcher: scratch of source %d", source_id); }
@@ -910,6 +919,188 @@ int dddmr_rollout_get_depth_image_cloud(dddmr_rollout_ctx* ctx, int32_t source_i
     HIPCHK(ctx, hipMemcpyAsync(xyz_out, di->cloud[di->cur], (size_t)di->n_cloud * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->copy_stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
   }
+  return DDDMR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Lidar sweep sources: the front half of ImageProjection::cloudHandler, then cbSensor (lidar_sweep.hip.h)
+// ---------------------------------------------------------------------------
+int dddmr_rollout_set_lidar_sweep_source(dddmr_rollout_ctx* ctx, int32_t source_id, const dddmr_lidar_sweep_config* cfg) {
+  if (!ctx) return DDDMR_ERR_BAD_ARG;
+  const char* what = "set_lidar_sweep_source";
+  if (!cfg || source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d (at most %d sensors) / null config", what, source_id, dddmr_rollout_ctx::kMaxSources);
+  const uint32_t V = cfg->num_vertical_scans, H = cfg->num_horizontal_scans;
+  if (V < 2 || H < 4 || cfg->ground_scan_index >= V || !(cfg->vertical_angle_top > cfg->vertical_angle_bottom) ||
+      !(cfg->minimum_detection_range < cfg->maximum_detection_range) || cfg->flags != 0)
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: image %u x %u, ground_scan_index %u, angles %g .. %g, range %g .. %g, flags %#x", what, V, H,
+                cfg->ground_scan_index, cfg->vertical_angle_bottom, cfg->vertical_angle_top, cfg->minimum_detection_range,
+                cfg->maximum_detection_range, cfg->flags);
+  if (!std::isfinite(cfg->vertical_angle_bottom) || !std::isfinite(cfg->vertical_angle_top) || !std::isfinite(cfg->segment_theta) ||
+      !std::isfinite(cfg->minimum_detection_range) || !std::isfinite(cfg->maximum_detection_range) || !std::isfinite(cfg->sensor_mount_angle))
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: non-finite parameter", what);
+  if (V > kSweepMaxRows || H > kSweepMaxCols || (uint64_t)V * H > kSweepMaxPixels || cfg->max_sweep_points > kSweepMaxPoints)
+    return fail(ctx, DDDMR_ERR_CAPACITY, "%s: image %u x %u (at most %u x %u, %u pixels), max_sweep_points %u (at most %u)", what, V, H,
+                kSweepMaxRows, kSweepMaxCols, kSweepMaxPixels, cfg->max_sweep_points, kSweepMaxPoints);
+  // the constructor's conversions (imageProjection.cpp:67-125 into the members of imageProjection.h:67-107)
+  const double kDegToRad = M_PI / 180.0;                         // utility.h:51
+  SweepParams k{};
+  const float bottom = (float)cfg->vertical_angle_bottom, top = (float)cfg->vertical_angle_top;
+  k.V = V;
+  k.H = H;
+  k.gsi = cfg->ground_scan_index;
+  k.res_x = (float)((M_PI * 2) / (int)H);
+  k.res_y = (float)(kDegToRad * (double)(top - bottom) / (double)(float)((int)V - 1));
+  k.ang_bottom = (float)(-((double)bottom - 0.1) * kDegToRad);
+  float theta = (float)cfg->segment_theta;
+  theta = (float)((double)theta * kDegToRad);
+  k.tan_theta = std::tan(theta);                                 // float overloads on float arguments
+  k.sin_x = std::sin(k.res_x);
+  k.cos_x = std::cos(k.res_x);
+  k.sin_y = std::sin(k.res_y);
+  k.cos_y = std::cos(k.res_y);
+  k.min_range = (float)cfg->minimum_detection_range;
+  k.max_range = (float)cfg->maximum_detection_range;
+  k.valid_points = cfg->segment_valid_point_num;
+  k.valid_lines = cfg->segment_valid_line_num;
+  k.mount = cfg->sensor_mount_angle;
+  k.ground_limit = 10 * kDegToRad;
+  {
+    // tf2::Quaternion::setRPY(0, mount, 0) = (0, sin(mount / 2), 0, cos(mount / 2)), through transformToEigen
+    const double q[7] = {0, 0, 0, 0, std::sin(cfg->sensor_mount_angle * 0.5), 0, std::cos(cfg->sensor_mount_angle * 0.5)};
+    quat_to_rot(q, k.Rp);
+  }
+  if (!(k.res_y > 0.f) || !std::isfinite(k.max_range))
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: the vertical resolution or the maximum range does not fit a float", what);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  if (ctx->depth[source_id]) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d is a depth camera source", what, source_id);
+  if (!ctx->sweep[source_id] && (ctx->src_is_lidar[source_id] || ctx->src_feed[source_id] || (source_id == 0 && ctx->feed.stitcher_num > 0)))
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d is a scan source", what, source_id);
+  const bool had_points = ctx->src_n[source_id] != 0;
+  if (ctx->sweep[source_id]) {                         // re-configuring empties the source
+    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+    sweep_free(*ctx->sweep[source_id]);
+    delete ctx->sweep[source_id];
+    ctx->sweep[source_id] = nullptr;
+    ctx->src_cloud[source_id] = nullptr;
+    ctx->src_n[source_id] = 0;
+    ctx->src_is_lidar[source_id] = false;
+  }
+  auto* sw = new LidarSweep();
+  sw->p = k;
+  sw->max_points = cfg->max_sweep_points;
+  int rc = DDDMR_OK;
+  if (sweep_alloc(*sw) != 0) {
+    sweep_free(*sw);
+    delete sw;
+    rc = fail(ctx, DDDMR_ERR_HIP, "%s: scratch of source %d", what, source_id);
+  } else {
+    ctx->sweep[source_id] = sw;
+    ctx->src_cloud[source_id] = sw->obs[sw->cur];
+    ctx->src_is_lidar[source_id] = true;
+    ctx->multi_source = true;
+  }
+  if (had_points) {                                    // the aggregate loses the emptied source's segment
+    uint32_t n_all;
+    const int prc = publish_sources(ctx, &n_all);
+    if (rc == DDDMR_OK) rc = prc;
+  }
+  return rc;
+}
+
+int dddmr_rollout_set_lidar_sweep(dddmr_rollout_ctx* ctx, int32_t source_id, const float* xyz, size_t n_points, size_t stride_bytes,
+                                  const double T_base_sensor[7], const double T_gbl_base[7], double perception_window_size,
+                                  double marking_height, uint32_t* n_segmented, uint32_t* n_source_points, uint32_t* n_aggregate_points) {
+  if (!ctx || !T_base_sensor || !T_gbl_base) return DDDMR_ERR_BAD_ARG;
+  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_lidar_sweep: source %d (at most %d sensors)", source_id, dddmr_rollout_ctx::kMaxSources);
+  if (n_points > 0 && (!xyz || stride_bytes < 12 || stride_bytes % 4 != 0)) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_lidar_sweep: bad pointer/stride");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  LidarSweep* sw = ctx->sweep[source_id];
+  if (!sw) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_lidar_sweep: source %d is not a configured lidar sweep source", source_id);
+  if (n_points > sw->max_points) return fail(ctx, DDDMR_ERR_CAPACITY, "set_lidar_sweep: %zu points > max_sweep_points %u", n_points, sw->max_points);
+  FeedParams fp;
+  quat_to_rot(T_base_sensor, fp.Rbs);
+  quat_to_rot(T_gbl_base, fp.Rgb);
+  for (int i = 0; i < 3; ++i) {
+    fp.tbs[i] = T_base_sensor[i];
+    fp.tgb[i] = T_gbl_base[i];
+  }
+  fp.n = 0;                                            // the device knows the count
+  fp.window = (float)perception_window_size;
+  fp.height = (float)marking_height;
+  uint32_t n_seg = 0, n_out = 0;
+  const int rc = sweep_feed(*sw, fp, xyz, n_points, stride_bytes, ctx->copy_stream, &n_seg, &n_out);
+  if (rc != 0) return fail(ctx, DDDMR_ERR_HIP, "set_lidar_sweep: sweep feed failed (%d)", rc);
+  size_t total = n_out;
+  for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i)
+    if (i != source_id) total += ctx->src_n[i];
+  if (total > ctx->cfg.max_points)
+    return fail(ctx, DDDMR_ERR_CAPACITY, "set_lidar_sweep: the sensors' observations together (%zu points) exceed max_points %u", total, ctx->cfg.max_points);
+  // commit: the buffers the sweep was built in become the current ones
+  const uint32_t old_n = ctx->src_n[source_id];
+  sw->cur ^= 1;
+  ctx->src_cloud[source_id] = sw->obs[sw->cur];
+  ctx->src_n[source_id] = n_out;
+  uint32_t n_all = 0;
+  const int prc = publish_sources(ctx, &n_all);
+  if (prc != DDDMR_OK) {                               // a failed copy: back to what the published aggregate holds
+    sw->cur ^= 1;
+    ctx->src_cloud[source_id] = sw->obs[sw->cur];
+    ctx->src_n[source_id] = old_n;
+    return prc;
+  }
+  sw->n_cloud = n_seg;
+  sw->have_sweep = true;
+  if (n_segmented) *n_segmented = n_seg;
+  if (n_source_points) *n_source_points = n_out;
+  if (n_aggregate_points) *n_aggregate_points = n_all;
+  return DDDMR_OK;
+}
+
+int dddmr_rollout_get_lidar_sweep_cloud(dddmr_rollout_ctx* ctx, int32_t source_id, float* xyzl_out, size_t capacity, size_t* n_points) {
+  if (!ctx || !n_points) return DDDMR_ERR_BAD_ARG;
+  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "get_lidar_sweep_cloud: source %d (at most %d sensors)", source_id, dddmr_rollout_ctx::kMaxSources);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  const LidarSweep* sw = ctx->sweep[source_id];
+  if (!sw) return fail(ctx, DDDMR_ERR_STATE, "get_lidar_sweep_cloud: source %d is not a lidar sweep source", source_id);
+  *n_points = sw->n_cloud;
+  if (!xyzl_out) return DDDMR_OK;
+  if (capacity < sw->n_cloud) return fail(ctx, DDDMR_ERR_CAPACITY, "get_lidar_sweep_cloud: capacity %zu < %u", capacity, sw->n_cloud);
+  if (sw->n_cloud) {
+    HIPCHK(ctx, hipMemcpyAsync(xyzl_out, sw->cloud[sw->cur], (size_t)sw->n_cloud * sizeof(float4), hipMemcpyDeviceToHost, ctx->copy_stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+  }
+  return DDDMR_OK;
+}
+
+int dddmr_rollout_get_lidar_sweep_image(dddmr_rollout_ctx* ctx, int32_t source_id, float* range_out, int32_t* label_out, int8_t* ground_out,
+                                        size_t capacity_pixels) {
+  if (!ctx) return DDDMR_ERR_BAD_ARG;
+  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "get_lidar_sweep_image: source %d (at most %d sensors)", source_id, dddmr_rollout_ctx::kMaxSources);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  const LidarSweep* sw = ctx->sweep[source_id];
+  if (!sw) return fail(ctx, DDDMR_ERR_STATE, "get_lidar_sweep_image: source %d is not a lidar sweep source", source_id);
+  const size_t px = (size_t)sw->p.V * sw->p.H;
+  if (capacity_pixels < px) return fail(ctx, DDDMR_ERR_CAPACITY, "get_lidar_sweep_image: capacity %zu < %zu pixels", capacity_pixels, px);
+  if (!sw->have_sweep) {                               // resetParameters' image: nothing projected yet
+    for (size_t i = 0; i < px; ++i) {
+      if (range_out) range_out[i] = FLT_MAX;
+      if (label_out) label_out[i] = -1;
+      if (ground_out) ground_out[i] = 0;
+    }
+    return DDDMR_OK;
+  }
+  if (range_out) HIPCHK(ctx, hipMemcpyAsync(range_out, sw->range_img[sw->cur], px * sizeof(float), hipMemcpyDeviceToHost, ctx->copy_stream));
+  if (label_out) HIPCHK(ctx, hipMemcpyAsync(label_out, sw->label_img[sw->cur], px * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->copy_stream));
+  if (ground_out) HIPCHK(ctx, hipMemcpyAsync(ground_out, sw->ground_img[sw->cur], px, hipMemcpyDeviceToHost, ctx->copy_stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
   return DDDMR_OK;
 }
 

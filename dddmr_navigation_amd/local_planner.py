@@ -214,6 +214,56 @@ class LocalPlanner:
                                                                   out.shape[0], C.byref(n)))
         return out[: n.value]
 
+    def set_lidar_sweep_source(self, source_id: int, num_vertical_scans: int, num_horizontal_scans: int,
+                               vertical_angle_bottom: float, vertical_angle_top: float, ground_scan_index: int,
+                               segment_theta: float = 60.0, segment_valid_point_num: int = 5, segment_valid_line_num: int = 3,
+                               minimum_detection_range: float = 0.3, maximum_detection_range: float = 100.0,
+                               sensor_mount_angle: float = 0.0, max_sweep_points: Optional[int] = None, flags: int = 0):
+        """Make `source_id` a lidar source fed raw sweeps: ImageProjection's laser.* / imageProjection.* parameters (angles
+        in degrees as the YAML gives them) and the mount pitch in radians; empties a configured one."""
+        if max_sweep_points is None:
+            max_sweep_points = 2 * int(num_vertical_scans) * int(num_horizontal_scans)
+        cfg = K.LidarSweepConfig(int(num_vertical_scans), int(num_horizontal_scans), float(vertical_angle_bottom),
+                                 float(vertical_angle_top), int(ground_scan_index), float(segment_theta),
+                                 int(segment_valid_point_num), int(segment_valid_line_num), float(minimum_detection_range),
+                                 float(maximum_detection_range), float(sensor_mount_angle), int(max_sweep_points), int(flags))
+        self._check(self._lib.dddmr_rollout_set_lidar_sweep_source(self._ctx, int(source_id), C.byref(cfg)))
+
+    def set_lidar_sweep(self, source_id: int, sweep_xyz: np.ndarray, T_base_sensor, T_gbl_base, perception_window_size: float,
+                        marking_height: float):
+        """One raw sweep through ImageProjection::cloudHandler's front half and cbSensor: returns (stage-one points = what
+        the node would publish on segmented_cloud_pure, points of this source's observation, points of the aggregate)."""
+        scan = np.ascontiguousarray(sweep_xyz, dtype=np.float32)
+        if scan.ndim != 2 or (scan.shape[0] and scan.shape[1] < 3):
+            raise ValueError("sweep must be [P, >=3] float32")
+        tbs = (C.c_double * 7)(*[float(v) for v in T_base_sensor])
+        tgb = (C.c_double * 7)(*[float(v) for v in T_gbl_base])
+        n_seg, n_src, n_all = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        stride = scan.strides[0] if scan.shape[0] else 12
+        self._check(self._lib.dddmr_rollout_set_lidar_sweep(self._ctx, int(source_id), scan.ctypes.data_as(C.c_void_p), scan.shape[0],
+                                                            stride, tbs, tgb, perception_window_size, marking_height,
+                                                            C.byref(n_seg), C.byref(n_src), C.byref(n_all)))
+        return int(n_seg.value), int(n_src.value), int(n_all.value)
+
+    def get_lidar_sweep_cloud(self, source_id: int) -> np.ndarray:
+        """Stage one's cloud of the source's latest sweep, [K,4] float32: x y z in the pitch-removed frame and the segment
+        label, in raster order (the topic segmented_cloud_pure)."""
+        n = C.c_size_t(0)
+        self._check(self._lib.dddmr_rollout_get_lidar_sweep_cloud(self._ctx, int(source_id), None, 0, C.byref(n)))
+        out = np.zeros((max(n.value, 1), 4), dtype=np.float32)
+        self._check(self._lib.dddmr_rollout_get_lidar_sweep_cloud(self._ctx, int(source_id), out.ctypes.data_as(C.c_void_p),
+                                                                  out.shape[0], C.byref(n)))
+        return out[: n.value]
+
+    def get_lidar_sweep_image(self, source_id: int, num_vertical_scans: int, num_horizontal_scans: int):
+        """(range [V,H] float32 with FLT_MAX where empty, label [V,H] int32, ground [V,H] int8) of the latest sweep."""
+        V, H = int(num_vertical_scans), int(num_horizontal_scans)
+        rng, lab, gnd = np.zeros((V, H), np.float32), np.zeros((V, H), np.int32), np.zeros((V, H), np.int8)
+        self._check(self._lib.dddmr_rollout_get_lidar_sweep_image(self._ctx, int(source_id), rng.ctypes.data_as(C.c_void_p),
+                                                                  lab.ctypes.data_as(C.c_void_p), gnd.ctypes.data_as(C.c_void_p),
+                                                                  V * H))
+        return rng, lab, gnd
+
     def set_depth_frustum(self, source_id: int, fov_w: float, fov_v: float, obstacle_min_range: float, obstacle_max_range: float,
                           T_gbl_sensor):
         """The frustum half of bufferCloud (depth_camera_observation_buffer.cpp:134-174) for this frame of the source:

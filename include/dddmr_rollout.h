@@ -352,6 +352,81 @@ int dddmr_rollout_set_depth_image(dddmr_rollout_ctx* ctx, int32_t source_id, con
 int dddmr_rollout_get_depth_image_cloud(dddmr_rollout_ctx* ctx, int32_t source_id, float* xyz_out,
                                         size_t capacity, size_t* n_points);
 
+/* Lidar SWEEP sources: the raw sweep as the lidar publishes it goes to the device, which does what the reference's
+   own node in front of the lidar plugins does and then cbSensor, in one call (additions to ABI version 2; no
+   existing struct or entry changes).  Every shipped configuration points its multilayer_spinning_lidar plugins at
+   the topic segmented_cloud_pure, which ImageProjection::cloudHandler produces
+   (dddmr_lego_loam/lego_loam_bor/src/imageProjection.cpp:280-314; line numbers below are that file's).
+
+   Stage one, per sweep, with the casts of the member types (imageProjection.h:67-107): the parameters are stored
+   into float members; _ang_resolution_X = (M_PI * 2) / H, _ang_resolution_Y = DEG_TO_RAD * (top - bottom) /
+   float(V - 1) and _ang_bottom = -(bottom - 0.1) * DEG_TO_RAD are computed in double and stored as floats;
+   tan(_segment_theta), sin(alpha) and cos(alpha) are taken once with the float overloads.
+     pitch removal (:297-303)   q.setRPY(0, sensor_mount_angle, 0) as an Affine3d, pcl::transformPointCloud: double
+                                multiply-add, float result, nothing fused.
+     projection (:328-382)      range = float sqrt of float products; rowIdn = int((asin(z / range) + _ang_bottom) /
+                                _ang_resolution_Y), truncated toward zero (quotients in (-1, 0) land in row 0);
+                                columnIdn = int(-round(atan2(x, y) / _ang_resolution_X) + H * 0.5), one -= H wrap;
+                                the bounds tests and minimum <= range <= maximum come before the pixel is written;
+                                among several points of one pixel the LAST in input order wins.
+     ground (:415-443, :519-526) for i < ground_scan_index, pixels (i, j) and (i + 1, j): float
+                                atan2(dZ, sqrt(dX^2 + dY^2 + dZ^2)), ground when (angle + sensor_mount_angle) <=
+                                10 * DEG_TO_RAD in double; an empty pixel holds NaN and makes no ground pair; a
+                                ground pair marks both pixels.  label = -1 where a pixel is ground or empty.
+     segments (:538-540, :595-679) neighbours (0,-1) (-1,0) (1,0) (0,1), columns wrap, rows do not; two pixels join
+                                when d2 * sin(alpha) / (d1 - d2 * cos(alpha)) > tan(theta) in float, d1 / d2 the
+                                larger / smaller range.  Each BFS fills one connected component; it is valid with
+                                >= 30 pixels, or with >= segment_valid_point_num pixels on >= segment_valid_line_num
+                                lines, where the seed's row counts only if the component has a second pixel in it
+                                (lineCountFlag is set for pushed neighbours only).  Valid components are numbered
+                                1, 2, ... in the raster order of their first pixels; invalid ones get 999999.
+     output (:582-592)          the pixels with 0 < label != 999999 in raster order: x y z of the pitch-removed point
+                                and the label as a float, 16 bytes per point = the topic segmented_cloud_pure.
+   Stage two: exactly what dddmr_rollout_set_scan_source does with a cloud, applied to stage one's x y z without the
+   cloud leaving the device.  T_base_sensor takes the frame "<sensor>_pitch_removed" (the frame the node stamps) to
+   the base.  Every rule stated for scan sources holds; a sweep source counts as a lidar source for
+   dddmr_rollout_marking_update and the perception stack.
+
+   Differences from the reference, on purpose: a record with ANY non-finite coordinate is dropped
+   (removeNaNFromPointCloud trusts is_dense); a point whose row quotient is not a number (range 0) is dropped (the
+   reference converts NaN to int); an empty sweep yields an empty cloud (the reference reads points.front()).
+   Left out: the patched ground cloud and its VoxelGrid (:450-514, it feeds mapping), _seg_msg / findStartEndAngle /
+   segmented_cloud / outlier_cloud, the projected image, and the stitcher on sweep sources.
+
+   A source is configured for scans, for sweeps or for depth; feeding it another kind is DDDMR_ERR_BAD_ARG, as are
+   dddmr_rollout_set_stitcher_source on a sweep source (a limit of this version), V < 2, H < 4, ground_scan_index >= V,
+   top <= bottom, minimum range >= maximum range and unknown flags.  DDDMR_ERR_CAPACITY: V > 128, H > 4096,
+   V * H > 2^19 or max_sweep_points > 2^20 at configuration; n_points > max_sweep_points or the aggregate exceeding
+   max_points at a sweep.  A failed call changes nothing.  Re-configuring a source empties it. */
+typedef struct {
+  uint32_t num_vertical_scans, num_horizontal_scans;   /* laser.num_vertical_scans / num_horizontal_scans */
+  double vertical_angle_bottom, vertical_angle_top;    /* degrees, as the YAML gives them */
+  uint32_t ground_scan_index;                          /* < num_vertical_scans */
+  double segment_theta;                                /* degrees */
+  uint32_t segment_valid_point_num, segment_valid_line_num;
+  double minimum_detection_range, maximum_detection_range;
+  double sensor_mount_angle;     /* radians: the pitch the node reads from base->sensor (:212-214); the lookup stays with the caller */
+  uint32_t max_sweep_points;     /* raw points per sweep */
+  uint32_t flags;                /* 0 */
+} dddmr_lidar_sweep_config;
+
+int dddmr_rollout_set_lidar_sweep_source(dddmr_rollout_ctx* ctx, int32_t source_id,
+                                         const dddmr_lidar_sweep_config* cfg);
+/* *n_segmented: stage one's points (what the node would publish); *n_source_points / *n_aggregate_points as for
+   dddmr_rollout_set_scan_source (each may be NULL). */
+int dddmr_rollout_set_lidar_sweep(dddmr_rollout_ctx* ctx, int32_t source_id, const float* xyz, size_t n_points,
+                                  size_t stride_bytes, const double T_base_sensor[7], const double T_gbl_base[7],
+                                  double perception_window_size, double marking_height, uint32_t* n_segmented,
+                                  uint32_t* n_source_points, uint32_t* n_aggregate_points);
+/* Stage one's results for the source's latest accepted sweep; before the first one: zero points, an empty image.
+   DDDMR_ERR_STATE on a source that is not a sweep source.  get_lidar_sweep_cloud: x y z label, 16 bytes per point;
+   xyzl_out == NULL only reports *n_points.  get_lidar_sweep_image: V * H pixels each, row-major; FLT_MAX in the range
+   image means empty, the ground mask is 1 for ground and 0 otherwise; each output may be NULL. */
+int dddmr_rollout_get_lidar_sweep_cloud(dddmr_rollout_ctx* ctx, int32_t source_id, float* xyzl_out, size_t capacity,
+                                        size_t* n_points);
+int dddmr_rollout_get_lidar_sweep_image(dddmr_rollout_ctx* ctx, int32_t source_id, float* range_out,
+                                        int32_t* label_out, int8_t* ground_out, size_t capacity_pixels);
+
 /* Depth camera frustums and selfClear's clearing verdicts: the global-mode side of DepthCameraLayer, first slice
    (additions to ABI version 2; no existing struct or entry changes).
 
