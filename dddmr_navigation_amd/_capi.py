@@ -269,6 +269,23 @@ class StackStats(C.Structure):
     ]
 
 
+class MclConfig(C.Structure):
+    """dddmr_mcl_config: mcl_3dl's likelihood.* parameters (lidar_measurement_model_likelihood.cpp:49-67) and capacities."""
+    _fields_ = [
+        ("match_dist_min", C.c_double), ("match_dist_flat", C.c_double), ("radius_of_ground_search", C.c_double),
+        ("threshold_for_trusted_ground", C.c_int32),
+        ("max_map_points", C.c_uint32), ("max_ground_points", C.c_uint32), ("max_particles", C.c_uint32),
+        ("max_observation_points", C.c_uint32), ("max_ground_neighbours", C.c_uint32), ("reserved", C.c_uint32),
+    ]
+
+
+class MclStats(C.Structure):
+    _fields_ = [
+        ("quality_min", C.c_float), ("quality_max", C.c_float), ("n_bad_states", C.c_uint32), ("n_over_capacity", C.c_uint32),
+        ("max_ground_neighbours_seen", C.c_uint32), ("launches", C.c_uint32), ("host_waits", C.c_uint32), ("reserved", C.c_uint32),
+    ]
+
+
 # dddmr_rollout_depth_clear_verdicts: bit 0 of a verdict = kept, bits 1-2 = the branch that decided
 DEPTH_CLEAR_KEPT = 1
 DEPTH_CLEAR_OUTSIDE, DEPTH_CLEAR_ATTACHED, DEPTH_CLEAR_INSIDE = 1, 2, 3
@@ -353,6 +370,10 @@ EXPORTED_SYMBOLS = (
     "dddmr_rollout_stack_get_lethal_mask",
     "dddmr_rollout_stack_get_lethal_nodes",
     "dddmr_rollout_stack_reset",
+    "dddmr_rollout_mcl_create",
+    "dddmr_rollout_mcl_set_map",
+    "dddmr_rollout_mcl_measure",
+    "dddmr_rollout_mcl_get_terms",
     "dddmr_rollout_stream_ceiling",
     "dddmr_rollout_selftest_sincos",
     "dddmr_rollout_last_error",
@@ -541,6 +562,18 @@ def load_library() -> C.CDLL:
         lib.dddmr_rollout_stack_get_lethal_nodes.restype = C.c_int
         lib.dddmr_rollout_stack_reset.argtypes = [ctx_p]
         lib.dddmr_rollout_stack_reset.restype = C.c_int
+    # (a library built from an older commit, loaded through DDDMR_LIB_NAME by the measurement tools, has no mcl entries)
+    if hasattr(lib, "dddmr_rollout_mcl_create"):
+        lib.dddmr_rollout_mcl_create.argtypes = [ctx_p, C.POINTER(MclConfig)]
+        lib.dddmr_rollout_mcl_create.restype = C.c_int
+        lib.dddmr_rollout_mcl_set_map.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                  C.c_size_t, C.c_size_t]
+        lib.dddmr_rollout_mcl_set_map.restype = C.c_int
+        lib.dddmr_rollout_mcl_measure.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                  C.c_void_p, C.c_void_p, C.POINTER(MclStats)]
+        lib.dddmr_rollout_mcl_measure.restype = C.c_int
+        lib.dddmr_rollout_mcl_get_terms.argtypes = [ctx_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.dddmr_rollout_mcl_get_terms.restype = C.c_int
     lib.dddmr_rollout_stream_ceiling.argtypes = [ctx_p, C.c_size_t, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.dddmr_rollout_stream_ceiling.restype = C.c_int
     lib.dddmr_rollout_selftest_sincos.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]

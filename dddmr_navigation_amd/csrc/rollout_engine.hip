@@ -45,6 +45,8 @@ struct DepthLayerState;                    // the depth camera layer's store, dG
 void depth_layer_free(DepthLayerState* s);
 struct StackState;                         // the perception stack over the two layers, perception_stack.hip.h
 void stack_free(StackState* s);
+struct MclState;                           // the particle filter's lidar likelihood, mcl_measure.hip.h
+void mcl_free(MclState* s);
 
 }  // namespace
 
@@ -153,6 +155,7 @@ struct dddmr_rollout_ctx {
   DepthMarkState* dmark = nullptr;   // dddmr_rollout_depth_mark_create
   DepthLayerState* dlayer = nullptr; // dddmr_rollout_depth_layer_create
   StackState* stack = nullptr;       // dddmr_rollout_stack_create (tick_mu)
+  MclState* mcl = nullptr;           // dddmr_rollout_mcl_create (tick_mu)
 
   std::mutex tick_mu;
   std::mutex err_mu;        // last_error is written by tick and sensor threads alike
@@ -286,6 +289,8 @@ size_t dddmr_rollout_sizeof(int which) {
     case 15: return sizeof(dddmr_stack_config);
     case 16: return sizeof(dddmr_stack_stats);
     case 17: return sizeof(dddmr_lidar_sweep_config);
+    case 18: return sizeof(dddmr_mcl_config);
+    case 19: return sizeof(dddmr_mcl_stats);
     default: return 0;
   }
 }
@@ -317,6 +322,7 @@ void dddmr_rollout_destroy(dddmr_rollout_ctx* ctx) {
   if (ctx->dmark) { depth_mark_free(ctx->dmark); ctx->dmark = nullptr; }
   if (ctx->stack) { stack_free(ctx->stack); ctx->stack = nullptr; }
   if (ctx->dlayer) { depth_layer_free(ctx->dlayer); ctx->dlayer = nullptr; }
+  if (ctx->mcl) { mcl_free(ctx->mcl); ctx->mcl = nullptr; }
   if (ctx->comm) (void)rccl().comm_destroy(ctx->comm);
   if (ctx->slots_dev) (void)hipFree(ctx->slots_dev);
   if (ctx->slots_red) (void)hipFree(ctx->slots_red);
@@ -2059,3 +2065,4 @@ int dddmr_rollout_get_best_cuboids(dddmr_rollout_ctx* ctx, float* vertices_out, 
 #include "depth_mark.hip.h"
 #include "depth_layer.hip.h"
 #include "perception_stack.hip.h"
+#include "mcl_measure.hip.h"

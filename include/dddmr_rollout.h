@@ -964,6 +964,71 @@ int dddmr_rollout_stack_get_lethal_mask(dddmr_rollout_ctx* ctx, uint8_t* mask_ou
 int dddmr_rollout_stack_get_lethal_nodes(dddmr_rollout_ctx* ctx, uint32_t* node_out, size_t capacity, size_t* n);
 int dddmr_rollout_stack_reset(dddmr_rollout_ctx* ctx);
 
+/* ---- Particle filter lidar likelihood: mcl_3dl's LidarMeasurementModelLikelihood::measure for a batch of particles ----
+   (dddmr_mcl_3dl/src/lidar_measurement_model_likelihood.cpp:86-252, called once per particle by pf_->measure,
+   src/mcl_3dl.cpp:466-503).  The one function of the localiser that is a batch kernel; motion prediction, bias,
+   resampling, weight normalisation, sub-map loading and the segmentation of the observation stay on the host.
+
+   dddmr_rollout_mcl_create takes the model's parameters (likelihood.match_dist_min / match_dist_flat /
+   radius_of_ground_search / threshold_for_trusted_ground) and the capacities.  DDDMR_ERR_BAD_ARG: a distance that is
+   not finite, match_dist_min or the ground radius not positive, match_dist_flat negative, a NEGATIVE threshold (the
+   reference compares it as an unsigned number there), a capacity of 0.  DDDMR_ERR_CAPACITY: more than 2^24 map or
+   ground points, 2^20 particles, 2000 observation points (flat + less sharp) or 1024 ground neighbours.  A second
+   create replaces the state (and forgets the map).  The state is freed with the context.
+
+   dddmr_rollout_mcl_set_map is SubMaps::swapKdTree: the sub-map cloud, the ground cloud and one normal per ground
+   point (xyz records, strides in bytes).  The new grids are built beside the current ones and swapped in only on
+   success: a refused call (DDDMR_ERR_CAPACITY above max_map_points / max_ground_points, DDDMR_ERR_BAD_ARG for a
+   non-finite coordinate, one beyond 1e6 m, or a cloud wider than 4096 m on an axis: the search boxes' 1 mm widening
+   covers float rounding up to there) changes nothing, and the next measure answers from the old map.  Either
+   cloud may be empty.
+
+   dddmr_rollout_mcl_measure: flat_xyz [n_flat][3], less_sharp_xyzi [n_less_sharp][4] (the intensity is the weight the
+   reference divides by), states [n_states][7] = pos xyz, rot xyzw, raw and not normalised.  likelihood_out[i] =
+   score_like * pos_weight and quality_out[i] = the match ratio of particle i; stats (may be NULL) carries the minimum
+   and maximum quality as mcl_3dl.cpp:476-498 keeps them (they start at 1 and 0).  The arithmetic is the reference's,
+   float where it is float and double where it is double; score_like and the normal averages are added in the
+   reference's order, so score_like, the counts and the quality are bit-equal to it and pos_weight is within a float ulp
+   (DESIGN.md 4e).  Deliberate differences: a call without any observation point is refused (DDDMR_ERR_BAD_ARG; the
+   reference divides 0 by 0); a state with a non-finite component gets likelihood 0 and quality 0 and is counted in
+   stats.n_bad_states; a non-finite observation point (before or after the transform) matches nothing and still counts
+   in the denominator.  DDDMR_ERR_CAPACITY: more states or points than created for, or a particle with more than
+   max_ground_neighbours ground points inside the radius (nothing is written then but stats).  DDDMR_ERR_STATE: no map
+   yet, or a dddmr_rollout_tick_begin is pending (set_map too: the conservative rule of dddmr_rollout_stack_update).
+
+   dddmr_rollout_mcl_get_terms: the parts of the last successful measure, per particle, for tests and debugging; any
+   output may be NULL.  healthy_out: 1 where the ground was trusted.  DDDMR_ERR_CAPACITY when capacity is below the
+   last call's particle count. */
+typedef struct {
+  double match_dist_min, match_dist_flat;
+  double radius_of_ground_search;
+  int32_t threshold_for_trusted_ground;
+  uint32_t max_map_points, max_ground_points;
+  uint32_t max_particles;
+  uint32_t max_observation_points;                    /* flat + less sharp */
+  uint32_t max_ground_neighbours;
+  uint32_t reserved;
+} dddmr_mcl_config;
+
+typedef struct {
+  float quality_min, quality_max;
+  uint32_t n_bad_states;
+  uint32_t n_over_capacity;                           /* particles beyond max_ground_neighbours */
+  uint32_t max_ground_neighbours_seen;
+  uint32_t launches, host_waits;
+  uint32_t reserved;
+} dddmr_mcl_stats;
+
+int dddmr_rollout_mcl_create(dddmr_rollout_ctx* ctx, const dddmr_mcl_config* cfg);
+int dddmr_rollout_mcl_set_map(dddmr_rollout_ctx* ctx, const float* map_xyz, size_t n_map, size_t map_stride_bytes,
+                              const float* ground_xyz, const float* ground_normals, size_t n_ground, size_t ground_stride_bytes,
+                              size_t normal_stride_bytes);
+int dddmr_rollout_mcl_measure(dddmr_rollout_ctx* ctx, const float* flat_xyz, size_t n_flat, const float* less_sharp_xyzi,
+                              size_t n_less_sharp, const float* states /* [n_states][7] */, size_t n_states, float* likelihood_out,
+                              float* quality_out, dddmr_mcl_stats* stats);
+int dddmr_rollout_mcl_get_terms(dddmr_rollout_ctx* ctx, float* score_like_out, float* pos_weight_out, uint32_t* n_match_out,
+                                uint32_t* n_ground_out, uint8_t* healthy_out, size_t capacity);
+
 /* Measurement aid ("a measured stream-copy ceiling on the same GPU"): streams
    `bytes` (>= 1 GiB recommended: beyond the 256 MB of MALL) `reps` times through a float4 copy
    kernel and a read-only kernel on the context's device; *copy_gbps counts read + write bytes.

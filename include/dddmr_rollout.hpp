@@ -210,6 +210,27 @@ class LocalPlanner {
     xyz.resize(3 * p);
     return DDDMR_OK;
   }
+  // the particle filter's lidar likelihood (mcl_3dl's measure() for a batch of particles): the library's codes are
+  // returned, not thrown, so that a caller can fall back to its CPU loop
+  int mclCreate(const dddmr_mcl_config& cfg) { return dddmr_rollout_mcl_create(ctx_, &cfg); }
+  int mclSetMap(const float* map_xyz, size_t n_map, size_t map_stride_bytes, const float* ground_xyz, const float* ground_normals,
+                size_t n_ground, size_t ground_stride_bytes, size_t normal_stride_bytes) {
+    return dddmr_rollout_mcl_set_map(ctx_, map_xyz, n_map, map_stride_bytes, ground_xyz, ground_normals, n_ground, ground_stride_bytes,
+                                     normal_stride_bytes);
+  }
+  // flat [n][3], less_sharp [n][4], states [n][7] (pos xyz, rot xyzw, raw) -> likelihood and quality per particle
+  int mclMeasure(const std::vector<float>& flat_xyz, const std::vector<float>& less_sharp_xyzi, const std::vector<float>& states,
+                 std::vector<float>& likelihood, std::vector<float>& quality, dddmr_mcl_stats& stats) {
+    const size_t n = states.size() / 7;
+    std::vector<float> like(n), qual(n);
+    stats = dddmr_mcl_stats{};
+    const int rc = dddmr_rollout_mcl_measure(ctx_, flat_xyz.data(), flat_xyz.size() / 3, less_sharp_xyzi.data(), less_sharp_xyzi.size() / 4,
+                                             states.data(), n, like.data(), qual.data(), &stats);
+    if (rc != DDDMR_OK) return rc;
+    likelihood.swap(like);
+    quality.swap(qual);
+    return DDDMR_OK;
+  }
   // prune plan poses, x y z qx qy qz qw each (output of Local_Planner::prunePlan)
   void setPlan(const double* poses_xyz_qxyzw, size_t n_poses) {
     check(dddmr_rollout_set_prune_plan(ctx_, poses_xyz_qxyzw, n_poses));
