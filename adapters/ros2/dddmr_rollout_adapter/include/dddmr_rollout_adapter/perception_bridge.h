@@ -7,6 +7,8 @@
 //   ... get_dGraphValue / updateLethalPointCloud    (:838-841, :283-304)                             -> MarkingLayerBridge
 //   ImageProjection::cloudHandler's front half + cbSensor
 //                          (dddmr_lego_loam/lego_loam_bor/src/imageProjection.cpp:280-314, :582-592) -> feedSweep(), sweepCloud()
+//   mcl_feature_node's laser_cloud_sharp / _less_sharp / _flat
+//                          (lego_loam_bor/src/featureAssociation.cpp:318-491, :1384-1405)             -> sweepFeatures()
 //   PathBlockedStrategy::selfMark                   (plugins/path_blocked_strategy.cpp:56-100)       -> pathBlocked()
 //   DepthCameraObservationBuffer::bufferCloud, local mode
 //                                    (plugins/depth_camera/depth_camera_observation_buffer.cpp:78-187) -> feedDepthFrame()
@@ -135,6 +137,35 @@ inline int sweepCloud(dddmr_rollout_ctx * ctx, int source, Cloud & out)
     out.points[i].y = xyzl[4 * i + 1];
     out.points[i].z = xyzl[4 * i + 2];
     out.points[i].intensity = xyzl[4 * i + 3];
+  }
+  return DDDMR_OK;
+}
+
+// What mcl_feature_node would have published on laser_cloud_sharp (which = 0), laser_cloud_less_sharp (1) or
+// laser_cloud_flat (2) for the source's latest accepted sweep, once dddmr_rollout_set_lidar_sweep_features has switched
+// the features on: points in the reference's push order, the ring in `intensity` (mcl_3dl's cbLeGoFeatureCloud takes
+// flat and less sharp).  The config's T_out is publishCloud's trans_c2s.inverse() as a row-major 3 x 4; with Eigen:
+//   Eigen::Affine3d T = tf2::transformToEigen(trans_c2s).inverse();
+//   for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) cfg.T_out[4 * r + c] = T.matrix()(r, c);
+// Returns the library's code; on any code but DDDMR_OK `out` is what it was.
+template<class Cloud>
+inline int sweepFeatures(dddmr_rollout_ctx * ctx, int source, int which, Cloud & out)
+{
+  if (!ctx) {return DDDMR_ERR_BAD_ARG;}
+  size_t n = 0;
+  int rc = dddmr_rollout_get_lidar_sweep_features(ctx, source, which, nullptr, nullptr, 0, &n);
+  if (rc != DDDMR_OK) {return rc;}
+  std::vector<float> xyzr(4 * n);
+  if (n) {
+    rc = dddmr_rollout_get_lidar_sweep_features(ctx, source, which, xyzr.data(), nullptr, n, &n);
+    if (rc != DDDMR_OK) {return rc;}
+  }
+  out.points.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    out.points[i].x = xyzr[4 * i + 0];
+    out.points[i].y = xyzr[4 * i + 1];
+    out.points[i].z = xyzr[4 * i + 2];
+    out.points[i].intensity = xyzr[4 * i + 3];
   }
   return DDDMR_OK;
 }

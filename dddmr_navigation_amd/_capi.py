@@ -199,6 +199,16 @@ class LidarSweepConfig(C.Structure):
     ]
 
 
+class LidarFeaturesConfig(C.Structure):
+    """dddmr_lidar_features_config: featureAssociation.edge_threshold / surf_threshold and publishCloud's
+    trans_c2s.inverse() as a row-major 3 x 4."""
+    _fields_ = [
+        ("edge_threshold", C.c_double), ("surf_threshold", C.c_double),
+        ("T_out", C.c_double * 12),
+        ("flags", C.c_uint32),
+    ]
+
+
 class DepthFrustumConfig(C.Structure):
     """dddmr_depth_frustum_config: the depth buffer's FOV_W / FOV_V (radians) and obstacle_min_range / obstacle_max_range."""
     _fields_ = [
@@ -348,6 +358,9 @@ EXPORTED_SYMBOLS = (
     "dddmr_rollout_set_lidar_sweep",
     "dddmr_rollout_get_lidar_sweep_cloud",
     "dddmr_rollout_get_lidar_sweep_image",
+    "dddmr_rollout_set_lidar_sweep_features",
+    "dddmr_rollout_get_lidar_sweep_segmented",
+    "dddmr_rollout_get_lidar_sweep_features",
     "dddmr_rollout_set_depth_frustum",
     "dddmr_rollout_get_depth_frustum",
     "dddmr_rollout_depth_frustum_test",
@@ -510,6 +523,14 @@ def load_library() -> C.CDLL:
         lib.dddmr_rollout_get_lidar_sweep_cloud.restype = C.c_int
         lib.dddmr_rollout_get_lidar_sweep_image.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         lib.dddmr_rollout_get_lidar_sweep_image.restype = C.c_int
+    if hasattr(lib, "dddmr_rollout_set_lidar_sweep_features"):         # (absent from a library built from an older commit)
+        lib.dddmr_rollout_set_lidar_sweep_features.argtypes = [ctx_p, C.c_int32, C.POINTER(LidarFeaturesConfig)]
+        lib.dddmr_rollout_set_lidar_sweep_features.restype = C.c_int
+        lib.dddmr_rollout_get_lidar_sweep_segmented.argtypes = [ctx_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_size_t, C.POINTER(C.c_size_t)]
+        lib.dddmr_rollout_get_lidar_sweep_segmented.restype = C.c_int
+        lib.dddmr_rollout_get_lidar_sweep_features.argtypes = [ctx_p, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                               C.POINTER(C.c_size_t)]
+        lib.dddmr_rollout_get_lidar_sweep_features.restype = C.c_int
     lib.dddmr_rollout_set_depth_frustum.argtypes = [ctx_p, C.c_int32, C.POINTER(DepthFrustumConfig), C.POINTER(C.c_double)]
     lib.dddmr_rollout_set_depth_frustum.restype = C.c_int
     lib.dddmr_rollout_get_depth_frustum.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

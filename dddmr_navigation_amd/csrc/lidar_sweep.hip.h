@@ -30,12 +30,13 @@
 //   k_sweep_number    one lane per pixel: label numbers of the roots; size and row mask left zero
 //   k_sweep_output    one lane per pixel: the label image and the ordered output cloud
 // A route that keeps a small image in one workgroup's LDS was not built; DESIGN 4a says why.
+// When the source's features are on (lidar_features.hip.h), their launches follow k_sweep_output on the same stream.
 //
 // Differences from the reference, on purpose: a record with any non-finite coordinate is dropped
 // (removeNaNFromPointCloud trusts is_dense); a point whose row quotient is not a number (range 0) is dropped (the
 // reference converts NaN to int); an empty sweep yields an empty cloud (the reference reads points.front()).
 // Left out: the patched ground cloud and its VoxelGrid (:450-514), _seg_msg / findStartEndAngle / segmented_cloud /
-// outlier_cloud, the projected image.
+// outlier_cloud, the projected image.  (segmented_cloud and _seg_msg's arrays: lidar_features.hip.h, when switched on.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -72,8 +73,13 @@ struct SweepResult {           // host-mapped, written by the last k_sweep_outpu
   uint32_t pad[3];
 };
 
+struct LidarFeatures;           // lidar_features.hip.h
+inline void features_launch(LidarFeatures& f, int b, const int32_t* label_img, const uint8_t* ground_img, const float* range_img,
+                            const float4* pts, hipStream_t stream);
+
 struct LidarSweep {
   SweepParams p;
+  LidarFeatures* features = nullptr;   // not null: the source's features are on; owned by the engine
   uint32_t max_points = 0;             // raw points per sweep
   PerceptionScratch feed;              // stage two's table; its pinned staging holds the raw sweep
   float4* moved = nullptr;             // [max_points] pitch-removed point, range in w
@@ -424,6 +430,7 @@ inline int sweep_feed(LidarSweep& s, FeedParams f, const float* raw, size_t n, s
   hipLaunchKernelGGL(k_sweep_number, per_pixel, block, 0, stream, k, s.parent, s.size, s.rows, s.block_cnt, s.num);
   hipLaunchKernelGGL(k_sweep_output, per_pixel, block, 0, stream, k, s.parent, s.num, s.pts, s.block_cnt, s.label_img[b], s.cloud[b],
                      s.n_dev, s.res_dev);
+  if (s.features) features_launch(*s.features, b, s.label_img[b], s.ground_img[b], s.range_img[b], s.pts, stream);
   // stage two: cbSensor on the device cloud; at most one point per pixel reaches it
   PerceptionScratch& ps = s.feed;
   const VoxelView table = ps.table.view(voxel_slots_for(px), ps.counters + 2);

@@ -29,6 +29,7 @@
 #include "depth_image.hip.h"
 #include "depth_clear.hip.h"
 #include "lidar_sweep.hip.h"
+#include "lidar_features.hip.h"
 #include "measure_kernels.hip.h"
 
 using namespace dddmr;
@@ -267,6 +268,8 @@ int dddmr_rollout_diag_rstamps(unsigned long long* out, size_t n_words) {
 }
 #endif
 
+static void sweep_features_off(LidarSweep& sw);
+
 const char* dddmr_rollout_version(void) { return "dddmr-rollout-mi355x 0.1 (gfx950)"; }
 
 size_t dddmr_rollout_sizeof(int which) {
@@ -291,6 +294,7 @@ size_t dddmr_rollout_sizeof(int which) {
     case 17: return sizeof(dddmr_lidar_sweep_config);
     case 18: return sizeof(dddmr_mcl_config);
     case 19: return sizeof(dddmr_mcl_stats);
+    case 20: return sizeof(dddmr_lidar_features_config);
     default: return 0;
   }
 }
@@ -340,7 +344,7 @@ void dddmr_rollout_destroy(dddmr_rollout_ctx* ctx) {
   if (ctx->dclear) { dc_free(*ctx->dclear); delete ctx->dclear; }
   for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) {
     if (ctx->depth[i]) { depth_free(*ctx->depth[i]); delete ctx->depth[i]; ctx->src_cloud[i] = nullptr; }
-    if (ctx->sweep[i]) { sweep_free(*ctx->sweep[i]); delete ctx->sweep[i]; ctx->src_cloud[i] = nullptr; }
+    if (ctx->sweep[i]) { sweep_features_off(*ctx->sweep[i]); sweep_free(*ctx->sweep[i]); delete ctx->sweep[i]; ctx->src_cloud[i] = nullptr; }
     if (ctx->dimg[i]) { dimg_free(*ctx->dimg[i]); delete ctx->dimg[i]; }
     if (ctx->src_feed[i]) { perception_free(*ctx->src_feed[i]); delete ctx->src_feed[i]; }
     if (ctx->src_cloud[i]) (void)hipFree(ctx->src_cloud[i]);
@@ -986,6 +990,7 @@ int dddmr_rollout_set_lidar_sweep_source(dddmr_rollout_ctx* ctx, int32_t source_
   const bool had_points = ctx->src_n[source_id] != 0;
   if (ctx->sweep[source_id]) {                         // re-configuring empties the source
     HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+    sweep_features_off(*ctx->sweep[source_id]);          // re-configuring turns the features off
     sweep_free(*ctx->sweep[source_id]);
     delete ctx->sweep[source_id];
     ctx->sweep[source_id] = nullptr;
@@ -1040,6 +1045,8 @@ int dddmr_rollout_set_lidar_sweep(dddmr_rollout_ctx* ctx, int32_t source_id, con
   uint32_t n_seg = 0, n_out = 0;
   const int rc = sweep_feed(*sw, fp, xyz, n_points, stride_bytes, ctx->copy_stream, &n_seg, &n_out);
   if (rc != 0) return fail(ctx, DDDMR_ERR_HIP, "set_lidar_sweep: sweep feed failed (%d)", rc);
+  FeatResult feat_counts{};
+  if (sw->features) std::memcpy(&feat_counts, sw->features->res_host, sizeof(feat_counts));   // written before the feed's release
   size_t total = n_out;
   for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i)
     if (i != source_id) total += ctx->src_n[i];
@@ -1060,6 +1067,11 @@ int dddmr_rollout_set_lidar_sweep(dddmr_rollout_ctx* ctx, int32_t source_id, con
   }
   sw->n_cloud = n_seg;
   sw->have_sweep = true;
+  if (LidarFeatures* lf = sw->features) {              // the features were built beside the sweep: they are current with it
+    lf->n_seg[sw->cur] = feat_counts.n_seg;
+    for (int w = 0; w < 3; ++w) lf->n_feat[sw->cur][w] = feat_counts.n_feat[w];
+    lf->have_sweep = true;
+  }
   if (n_segmented) *n_segmented = n_seg;
   if (n_source_points) *n_source_points = n_out;
   if (n_aggregate_points) *n_aggregate_points = n_all;
@@ -1107,6 +1119,135 @@ int dddmr_rollout_get_lidar_sweep_image(dddmr_rollout_ctx* ctx, int32_t source_i
   if (label_out) HIPCHK(ctx, hipMemcpyAsync(label_out, sw->label_img[sw->cur], px * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->copy_stream));
   if (ground_out) HIPCHK(ctx, hipMemcpyAsync(ground_out, sw->ground_img[sw->cur], px, hipMemcpyDeviceToHost, ctx->copy_stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+  return DDDMR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Lidar sweep features: the feature half of mcl_feature_node on a sweep source (lidar_features.hip.h)
+// ---------------------------------------------------------------------------
+static void sweep_features_off(LidarSweep& sw) {
+  if (!sw.features) return;
+  features_free(*sw.features);
+  delete sw.features;
+  sw.features = nullptr;
+}
+
+int dddmr_rollout_set_lidar_sweep_features(dddmr_rollout_ctx* ctx, int32_t source_id, const dddmr_lidar_features_config* cfg) {
+  if (!ctx) return DDDMR_ERR_BAD_ARG;
+  const char* what = "set_lidar_sweep_features";
+  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d (at most %d sensors)", what, source_id, dddmr_rollout_ctx::kMaxSources);
+  if (cfg) {
+    if (!std::isfinite(cfg->edge_threshold) || !std::isfinite(cfg->surf_threshold) || cfg->edge_threshold < 0.0 || cfg->surf_threshold < 0.0 ||
+        cfg->flags != 0)
+      return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: thresholds %g / %g, flags %#x", what, cfg->edge_threshold, cfg->surf_threshold, cfg->flags);
+    for (int i = 0; i < 12; ++i)
+      if (!std::isfinite(cfg->T_out[i])) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: T_out[%d] is not finite", what, i);
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  LidarSweep* sw = ctx->sweep[source_id];
+  if (!sw) return fail(ctx, DDDMR_ERR_STATE, "%s: source %d is not a lidar sweep source", what, source_id);
+  FeatParams k{};
+  if (cfg) {
+    k.edge_threshold = (float)cfg->edge_threshold;     // float members (featureAssociation.h:62-63)
+    k.surf_threshold = (float)cfg->surf_threshold;
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) k.R[3 * r + c] = cfg->T_out[4 * r + c];
+      k.t[r] = cfg->T_out[4 * r + 3];
+    }
+    k.V = sw->p.V;
+    k.H = sw->p.H;
+  }
+  HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+  if (!cfg) {
+    sweep_features_off(*sw);
+    return DDDMR_OK;
+  }
+  if (sw->features) {                                  // new parameters: they hold from the next sweep on; what the getters
+    sw->features->p = k;                               // return stays the latest accepted sweep's
+    return DDDMR_OK;
+  }
+  auto* lf = new LidarFeatures();
+  lf->p = k;
+  if (features_alloc(*lf) != 0) {
+    features_free(*lf);
+    delete lf;
+    return fail(ctx, DDDMR_ERR_HIP, "%s: scratch of source %d", what, source_id);
+  }
+  sw->features = lf;
+  return DDDMR_OK;
+}
+
+static int sweep_features_of(dddmr_rollout_ctx* ctx, int32_t source_id, const char* what, LidarSweep** out) {
+  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d (at most %d sensors)", what, source_id, dddmr_rollout_ctx::kMaxSources);
+  LidarSweep* sw = ctx->sweep[source_id];
+  if (!sw) return fail(ctx, DDDMR_ERR_STATE, "%s: source %d is not a lidar sweep source", what, source_id);
+  if (!sw->features) return fail(ctx, DDDMR_ERR_STATE, "%s: the features of source %d are off", what, source_id);
+  *out = sw;
+  return DDDMR_OK;
+}
+
+int dddmr_rollout_get_lidar_sweep_segmented(dddmr_rollout_ctx* ctx, int32_t source_id, float* xyz, float* range, int32_t* col_ind,
+                                            uint8_t* ground_flag, int32_t* start_ring_index, int32_t* end_ring_index, size_t capacity,
+                                            size_t* n) {
+  if (!ctx || !n) return DDDMR_ERR_BAD_ARG;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  LidarSweep* sw = nullptr;
+  const int rc = sweep_features_of(ctx, source_id, "get_lidar_sweep_segmented", &sw);
+  if (rc != DDDMR_OK) return rc;
+  const LidarFeatures& lf = *sw->features;
+  const int b = sw->cur;
+  const size_t count = lf.n_seg[b], V = sw->p.V;
+  const bool points = xyz || range || col_ind || ground_flag;
+  if (points && capacity < count) return fail(ctx, DDDMR_ERR_CAPACITY, "get_lidar_sweep_segmented: capacity %zu < %zu", capacity, count);
+  *n = count;
+  std::vector<float4> pt;
+  std::vector<uint32_t> cr;
+  std::vector<int32_t> ring(2 * V);
+  if (points && count) {
+    pt.resize(count);
+    cr.resize(count);
+    HIPCHK(ctx, hipMemcpyAsync(pt.data(), lf.seg_pt[b], count * sizeof(float4), hipMemcpyDeviceToHost, ctx->copy_stream));
+    HIPCHK(ctx, hipMemcpyAsync(cr.data(), lf.seg_cr[b], count * 4, hipMemcpyDeviceToHost, ctx->copy_stream));
+  }
+  if (start_ring_index || end_ring_index)
+    HIPCHK(ctx, hipMemcpyAsync(ring.data(), lf.ring[b], 2 * V * 4, hipMemcpyDeviceToHost, ctx->copy_stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+  for (size_t i = 0; i < pt.size(); ++i) {
+    if (xyz) { xyz[3 * i] = pt[i].x; xyz[3 * i + 1] = pt[i].y; xyz[3 * i + 2] = pt[i].z; }
+    if (range) range[i] = pt[i].w;
+    if (col_ind) col_ind[i] = (int32_t)(cr[i] & 0xFFFFu);
+    if (ground_flag) ground_flag[i] = (uint8_t)(cr[i] >> 31);
+  }
+  for (size_t r = 0; r < V; ++r) {                     // before the first sweep: the indices of an empty cloud
+    const bool have = lf.have_sweep;
+    if (start_ring_index) start_ring_index[r] = have ? ring[r] : 4;
+    if (end_ring_index) end_ring_index[r] = have ? ring[V + r] : -6;
+  }
+  return DDDMR_OK;
+}
+
+int dddmr_rollout_get_lidar_sweep_features(dddmr_rollout_ctx* ctx, int32_t source_id, int which, float* xyzr_out, uint32_t* seg_index_out,
+                                           size_t capacity, size_t* n_points) {
+  if (!ctx || !n_points) return DDDMR_ERR_BAD_ARG;
+  if (which < 0 || which > 2) return fail(ctx, DDDMR_ERR_BAD_ARG, "get_lidar_sweep_features: which %d (0 sharp, 1 less sharp, 2 flat)", which);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  LidarSweep* sw = nullptr;
+  const int rc = sweep_features_of(ctx, source_id, "get_lidar_sweep_features", &sw);
+  if (rc != DDDMR_OK) return rc;
+  const LidarFeatures& lf = *sw->features;
+  const int b = sw->cur;
+  const size_t count = lf.n_feat[b][which], off = feat_offset(sw->p.V, which);
+  if ((xyzr_out || seg_index_out) && capacity < count)
+    return fail(ctx, DDDMR_ERR_CAPACITY, "get_lidar_sweep_features: capacity %zu < %zu", capacity, count);
+  *n_points = count;
+  if (count && xyzr_out) HIPCHK(ctx, hipMemcpyAsync(xyzr_out, lf.feat[b] + off, count * sizeof(float4), hipMemcpyDeviceToHost, ctx->copy_stream));
+  if (count && seg_index_out) HIPCHK(ctx, hipMemcpyAsync(seg_index_out, lf.feat_idx[b] + off, count * 4, hipMemcpyDeviceToHost, ctx->copy_stream));
+  if (count && (xyzr_out || seg_index_out)) HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
   return DDDMR_OK;
 }
 

@@ -264,6 +264,46 @@ class LocalPlanner:
                                                                   V * H))
         return rng, lab, gnd
 
+    def set_lidar_sweep_features(self, source_id: int, edge_threshold: float = 0.1, surf_threshold: float = 0.1, T_out=None,
+                                 enable: bool = True, flags: int = 0):
+        """Switch the feature half of mcl_feature_node on for a sweep source (enable=False: off): every accepted sweep then
+        also yields the segmented cloud and LeGO-LOAM's sharp / less sharp / flat points.  T_out: publishCloud's
+        trans_c2s.inverse() as a [3,4] (or [4,4]) float64 matrix applied to the camera-frame point; identity if None."""
+        if not enable:
+            self._check(self._lib.dddmr_rollout_set_lidar_sweep_features(self._ctx, int(source_id), None))
+            return
+        T = np.hstack([np.eye(3), np.zeros((3, 1))]) if T_out is None else np.asarray(T_out, dtype=np.float64)
+        if T.shape not in ((3, 4), (4, 4)):
+            raise ValueError("T_out must be [3,4] or [4,4]")
+        cfg = K.LidarFeaturesConfig(float(edge_threshold), float(surf_threshold), (C.c_double * 12)(*T[:3].reshape(-1).tolist()), int(flags))
+        self._check(self._lib.dddmr_rollout_set_lidar_sweep_features(self._ctx, int(source_id), C.byref(cfg)))
+
+    def get_lidar_sweep_segmented(self, source_id: int, num_vertical_scans: int):
+        """ImageProjection's segmented_cloud and seg_msg of the latest sweep: dict of xyz [n,3] float32, range [n] float32,
+        col [n] int32, ground [n] uint8, start / end [V] int32 (start_ring_index / end_ring_index)."""
+        V, n = int(num_vertical_scans), C.c_size_t(0)
+        none = C.c_void_p(None)
+        self._check(self._lib.dddmr_rollout_get_lidar_sweep_segmented(self._ctx, int(source_id), none, none, none, none, none, none, 0, C.byref(n)))
+        cap = max(n.value, 1)
+        xyz, rng, col, gnd = np.zeros((cap, 3), np.float32), np.zeros(cap, np.float32), np.zeros(cap, np.int32), np.zeros(cap, np.uint8)
+        start, end = np.zeros(V, np.int32), np.zeros(V, np.int32)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._check(self._lib.dddmr_rollout_get_lidar_sweep_segmented(self._ctx, int(source_id), ptr(xyz), ptr(rng), ptr(col), ptr(gnd),
+                                                                      ptr(start), ptr(end), cap, C.byref(n)))
+        k = n.value
+        return dict(xyz=xyz[:k], range=rng[:k], col=col[:k], ground=gnd[:k], start=start, end=end)
+
+    def get_lidar_sweep_features(self, source_id: int, which: int):
+        """One feature list of the latest sweep (which: 0 sharp, 1 less sharp, 2 flat): ([K,4] float32 x y z ring after T_out,
+        [K] uint32 indices into the segmented cloud), in the reference's push order."""
+        n = C.c_size_t(0)
+        self._check(self._lib.dddmr_rollout_get_lidar_sweep_features(self._ctx, int(source_id), int(which), None, None, 0, C.byref(n)))
+        cap = max(n.value, 1)
+        out, idx = np.zeros((cap, 4), np.float32), np.zeros(cap, np.uint32)
+        self._check(self._lib.dddmr_rollout_get_lidar_sweep_features(self._ctx, int(source_id), int(which), out.ctypes.data_as(C.c_void_p),
+                                                                     idx.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
+        return out[: n.value], idx[: n.value]
+
     def set_depth_frustum(self, source_id: int, fov_w: float, fov_v: float, obstacle_min_range: float, obstacle_max_range: float,
                           T_gbl_sensor):
         """The frustum half of bufferCloud (depth_camera_observation_buffer.cpp:134-174) for this frame of the source:

@@ -390,8 +390,9 @@ int dddmr_rollout_get_depth_image_cloud(dddmr_rollout_ctx* ctx, int32_t source_i
    Differences from the reference, on purpose: a record with ANY non-finite coordinate is dropped
    (removeNaNFromPointCloud trusts is_dense); a point whose row quotient is not a number (range 0) is dropped (the
    reference converts NaN to int); an empty sweep yields an empty cloud (the reference reads points.front()).
-   Left out: the patched ground cloud and its VoxelGrid (:450-514, it feeds mapping), _seg_msg / findStartEndAngle /
-   segmented_cloud / outlier_cloud, the projected image, and the stitcher on sweep sources.
+   Left out: the patched ground cloud and its VoxelGrid (:450-514, it feeds mapping), findStartEndAngle, outlier_cloud,
+   the projected image, and the stitcher on sweep sources.  segmented_cloud and _seg_msg's arrays come with the
+   sweep's features (dddmr_rollout_set_lidar_sweep_features below), off unless asked for.
 
    A source is configured for scans, for sweeps or for depth; feeding it another kind is DDDMR_ERR_BAD_ARG, as are
    dddmr_rollout_set_stitcher_source on a sweep source (a limit of this version), V < 2, H < 4, ground_scan_index >= V,
@@ -426,6 +427,71 @@ int dddmr_rollout_get_lidar_sweep_cloud(dddmr_rollout_ctx* ctx, int32_t source_i
                                         size_t* n_points);
 int dddmr_rollout_get_lidar_sweep_image(dddmr_rollout_ctx* ctx, int32_t source_id, float* range_out,
                                         int32_t* label_out, int8_t* ground_out, size_t capacity_pixels);
+
+/* Lidar sweep FEATURES: the feature half of the reference's mcl_feature_node on a sweep source (additions to ABI
+   version 2; no existing struct or entry changes; a sweep source whose features were never switched on runs exactly
+   the launches it ran before).  In localisation mode the reference runs ImageProjection and the first four steps of
+   FeatureAssociation::runFeatureAssociation (dddmr_lego_loam/lego_loam_bor/src/featureAssociation.cpp:1506-1514) and
+   publishes laser_cloud_sharp / _less_sharp / _flat / _less_flat; mcl_3dl's cbLeGoFeatureCloud uses flat and less
+   sharp, which dddmr_rollout_mcl_measure takes.  With features on, each accepted dddmr_rollout_set_lidar_sweep also
+   yields, without a host wait of its own (line numbers: imageProjection.cpp for the first item, featureAssociation.cpp
+   after it; float where the member is float, double where the literal is double, nothing fused):
+     segmented cloud (imageProjection.cpp:542-580)  pixels in raster order with label > 0 or ground, without label
+                                999999 (the outlier cloud is left out) and without the ground pixels with j % 5 != 0 &&
+                                j > 5 && j < H - 5; per point the ground flag, the column, the range and the
+                                pitch-removed point; per row start_ring_index = count_before - 1 + 5 and
+                                end_ring_index = count_after - 1 - 5 (an empty row: start > end).
+     smoothness (:318-341)      for 5 <= i < n - 5 the ten neighbours' ranges and -range[i] * 10 summed left to right
+                                in float, in the source's order; curvature = d * d.
+     occlusion (:343-379)       for 5 <= i < n - 6, columnDiff < 10: float differences against the double 0.3 mark
+                                i - 5 .. i or i + 1 .. i + 6; both neighbour differences above the double 0.02 * range
+                                mark i.  The marks cross ring boundaries.
+     extraction (:381-491)      per ring six sixths sp .. ep with the source's integer divisions, sp >= ep skips one;
+                                std::sort covers [sp, ep) and both walks include k = ep, whose slot is
+                                {curvature[ep], ep}.  Edge walk, descending: not picked, curvature > edge_threshold,
+                                not ground; candidates 1-2 are sharp and less sharp, 3-20 less sharp, the 21st breaks.
+                                Flat walk, ascending: not picked, curvature < surf_threshold, ground; the 4th is
+                                pushed and breaks before it suppresses.  A pick suppresses ind +- 1 .. 5 up to the
+                                first step whose column difference is > 10, across sixths and one index before the
+                                ring's first point.  The cloudLabel / less-flat loop and its VoxelGrid are left out.
+     output (:281-314, :1384-1405) the camera-frame point (y, z, x) of the segmented point through T_out as
+                                pcl::transformPointCloud(Affine3d) applies it (double multiply-add, float result);
+                                the fourth float is the ring, float(int(intensity)); order = the reference's push
+                                order: ring, sixth, walk order.
+   T_out is publishCloud's trans_c2s.inverse(), row-major 3 x 4; the caller computes it (Eigen / NumPy).
+
+   Differences from the reference, on purpose.  Every sweep behaves like the FIRST sweep of a freshly constructed
+   FeatureAssociation: the reference never rewrites slot 4 of cloudSmoothness (ring 0's sp, below calculateSmoothness's
+   range) and carries its sorted leftover from sweep to sweep; here slot 4 is {0.0f, ind 0} every time, so a ground
+   point at segment index 0 is ring 0's first flat pick unless it is occlusion-marked.  Equal curvatures sort by
+   ascending index (std::sort leaves their order undefined).  The relTime part of the intensity and findStartEndAngle
+   are left out (mcl_3dl overwrites or ignores the intensity).  Sharp, less sharp and flat are produced; less flat is
+   not.  What cbLeGoFeatureCloud does with the lists (VoxelGrid, normals, clusters) stays with the host.
+
+   The features are part of the sweep's double-buffered result: built beside the current one and swapped in only when
+   the aggregate accepted the sweep, so after a refused sweep the getters return the previous sweep's.  cfg == NULL
+   switches them off; new parameters on a source that has them on hold from the next sweep.  Re-configuring the sweep
+   source switches them off.  DDDMR_ERR_BAD_ARG: a non-finite or negative threshold, a non-finite T_out entry, unknown
+   flags, `which` outside 0 .. 2.  DDDMR_ERR_STATE: not a sweep source, or its features are off.  The getters follow
+   the sweep getters: NULL outputs only report the count (each output may be NULL on its own), DDDMR_ERR_CAPACITY
+   when a point output is wanted and capacity is below the count, a failed call changes nothing.  start / end ring
+   indices: num_vertical_scans entries each.  Before the first sweep: zero points. */
+typedef struct {
+  double edge_threshold, surf_threshold; /* featureAssociation.*; stored into float members as the node does */
+  double T_out[12];                      /* row-major 3x4, applied to the camera-frame point: publishCloud's
+                                            trans_c2s.inverse(); the caller computes it (Eigen / NumPy) */
+  uint32_t flags;                        /* 0 */
+} dddmr_lidar_features_config;
+
+int dddmr_rollout_set_lidar_sweep_features(dddmr_rollout_ctx* ctx, int32_t source_id,
+                                           const dddmr_lidar_features_config* cfg); /* NULL: off */
+int dddmr_rollout_get_lidar_sweep_segmented(dddmr_rollout_ctx* ctx, int32_t source_id, float* xyz, float* range,
+                                            int32_t* col_ind, uint8_t* ground_flag, int32_t* start_ring_index,
+                                            int32_t* end_ring_index, size_t capacity, size_t* n);
+/* which: 0 sharp, 1 less sharp, 2 flat.  xyzr_out: x y z ring, 16 bytes per point; seg_index_out: the point's index in
+   the segmented cloud. */
+int dddmr_rollout_get_lidar_sweep_features(dddmr_rollout_ctx* ctx, int32_t source_id, int which, float* xyzr_out,
+                                           uint32_t* seg_index_out, size_t capacity, size_t* n_points);
 
 /* Depth camera frustums and selfClear's clearing verdicts: the global-mode side of DepthCameraLayer, first slice
    (additions to ABI version 2; no existing struct or entry changes).

@@ -118,6 +118,35 @@ class LocalPlanner {
     if (n) check(dddmr_rollout_get_depth_image_cloud(ctx_, source_id, &out[0][0], n, &n));
     return out;
   }
+  // lidar sweep features: the feature half of mcl_feature_node on a sweep source (cfg == nullptr: off); which: 0 sharp,
+  // 1 less sharp, 2 flat; x y z ring per point, and optionally the points' indices in the segmented cloud
+  void setLidarSweepFeatures(int32_t source_id, const dddmr_lidar_features_config* cfg) {
+    check(dddmr_rollout_set_lidar_sweep_features(ctx_, source_id, cfg));
+  }
+  std::vector<std::array<float, 4>> getLidarSweepFeatures(int32_t source_id, int which, std::vector<uint32_t>* seg_index = nullptr) {
+    size_t n = 0;
+    check(dddmr_rollout_get_lidar_sweep_features(ctx_, source_id, which, nullptr, nullptr, 0, &n));
+    std::vector<std::array<float, 4>> out(n);
+    if (seg_index) seg_index->resize(n);
+    if (n) check(dddmr_rollout_get_lidar_sweep_features(ctx_, source_id, which, &out[0][0], seg_index ? seg_index->data() : nullptr, n, &n));
+    return out;
+  }
+  struct LidarSweepSegmented {
+    std::vector<std::array<float, 3>> xyz;
+    std::vector<float> range;
+    std::vector<int32_t> col_ind, start_ring_index, end_ring_index;
+    std::vector<uint8_t> ground_flag;
+  };
+  LidarSweepSegmented getLidarSweepSegmented(int32_t source_id, size_t num_vertical_scans) {
+    size_t n = 0;
+    check(dddmr_rollout_get_lidar_sweep_segmented(ctx_, source_id, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &n));
+    LidarSweepSegmented s;
+    s.xyz.resize(n); s.range.resize(n); s.col_ind.resize(n); s.ground_flag.resize(n);
+    s.start_ring_index.resize(num_vertical_scans); s.end_ring_index.resize(num_vertical_scans);
+    check(dddmr_rollout_get_lidar_sweep_segmented(ctx_, source_id, n ? &s.xyz[0][0] : nullptr, s.range.data(), s.col_ind.data(),
+                                                  s.ground_flag.data(), s.start_ring_index.data(), s.end_ring_index.data(), n, &n));
+    return s;
+  }
   // the frustum of a depth source (bufferCloud's second half), the two point tests and selfClear's clearing verdicts
   void setDepthFrustum(int32_t source_id, const dddmr_depth_frustum_config& cfg, const double T_gbl_sensor[7]) {
     check(dddmr_rollout_set_depth_frustum(ctx_, source_id, &cfg, T_gbl_sensor));
