@@ -310,9 +310,7 @@ int depth_layer_update_locked(dddmr_rollout_ctx* ctx, const double T_gbl_base[7]
   DcFrustums S;
   int rc = depth_frustums(ctx, "depth_layer_update", &S);
   if (rc != DDDMR_OK) return rc;
-  size_t n_obs = 0;
-  for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i)
-    if (ctx->depth[i]) n_obs += ctx->src_n[i];
+  const size_t n_obs = ctx->sources.depth_points();
   if (n_obs > s->max_obs)
     return fail(ctx, DDDMR_ERR_CAPACITY, "depth_layer_update: %zu observation points, max_observation_points %u", n_obs, s->max_obs);
   if ((rc = depth_clear_scratch(ctx, "depth_layer_update")) != DDDMR_OK) return rc;

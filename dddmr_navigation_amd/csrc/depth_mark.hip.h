@@ -308,9 +308,7 @@ int dddmr_rollout_depth_mark_clusters(dddmr_rollout_ctx* ctx, const double T_gbl
   DcFrustums S;
   int rc = depth_frustums(ctx, "depth_mark_clusters", &S);
   if (rc != DDDMR_OK) return rc;
-  size_t n_obs = 0;
-  for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i)
-    if (ctx->depth[i]) n_obs += ctx->src_n[i];
+  const size_t n_obs = ctx->sources.depth_points();
   if (n_obs > s->max_obs)
     return fail(ctx, DDDMR_ERR_CAPACITY, "depth_mark_clusters: %zu observation points, max_observation_points %u", n_obs, s->max_obs);
   dddmr_depth_mark_stats out{};

@@ -96,7 +96,7 @@ struct LidarSweep {
   int32_t* label_img[2] = {nullptr, nullptr};
   uint8_t* ground_img[2] = {nullptr, nullptr};
   float4* cloud[2] = {nullptr, nullptr};   // x y z label
-  float4* obs[2] = {nullptr, nullptr};     // stage two's observation; the context's src_cloud aliases obs[cur]
+  float4* obs[2] = {nullptr, nullptr};     // stage two's observation; the source's obs in the context aliases obs[cur]
   int cur = 0;
   uint32_t n_cloud = 0;
   bool have_sweep = false;

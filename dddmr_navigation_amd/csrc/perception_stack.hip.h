@@ -246,28 +246,24 @@ int dddmr_rollout_stack_update(dddmr_rollout_ctx* ctx, const double T_base_senso
         HIPCHK(ctx, hipStreamWaitEvent(m->cur, ctx->cloud_ready[cidx], 0));
         cloud_wait_done(ctx, cidx);
       }
-      uint32_t src_n[DDDMR_MAX_SOURCES];
-      uint32_t lidar_mask;
+      SourceLayout L;
       {
         std::lock_guard<std::mutex> lk(ctx->cloud_mu);
-        if (!ctx->cloud_from_sources[cidx])
-          return fail(ctx, DDDMR_ERR_STATE, "stack_update: the published aggregate did not come from the sources (a set_cloud since the last feed)");
-        for (int i = 0; i < DDDMR_MAX_SOURCES; ++i) src_n[i] = ctx->cloud_src_n[cidx][i];
-        lidar_mask = ctx->cloud_src_lidar[cidx];
+        L = ctx->cloud_layout[cidx];
       }
+      if (!L.from_sources)
+        return fail(ctx, DDDMR_ERR_STATE, "stack_update: the published aggregate did not come from the sources (a set_cloud since the last feed)");
       // maximal runs of lidar points in the aggregate
       struct Run { uint32_t at, n; } runs[DDDMR_MAX_SOURCES];
       int n_runs = 0;
-      uint32_t at = 0, total = 0;
+      uint32_t total = 0;
       for (int i = 0; i < DDDMR_MAX_SOURCES; ++i) {
-        if (((lidar_mask >> i) & 1u) && src_n[i]) {
-          if (n_runs && runs[n_runs - 1].at + runs[n_runs - 1].n == at) runs[n_runs - 1].n += src_n[i];
-          else runs[n_runs++] = Run{at, src_n[i]};
-          total += src_n[i];
-        }
-        at += src_n[i];
+        if (!((L.lidar_mask >> i) & 1u) || !L.n[i]) continue;
+        if (n_runs && runs[n_runs - 1].at + runs[n_runs - 1].n == L.at[i]) runs[n_runs - 1].n += L.n[i];
+        else runs[n_runs++] = Run{L.at[i], L.n[i]};
+        total += L.n[i];
       }
-      if (at > ctx->cloud_n[cidx]) return fail(ctx, DDDMR_ERR_STATE, "stack_update: source counts %u beyond the aggregate's %u points", at, ctx->cloud_n[cidx]);
+      if (L.total > ctx->cloud_n[cidx]) return fail(ctx, DDDMR_ERR_STATE, "stack_update: source counts %u beyond the aggregate's %u points", L.total, ctx->cloud_n[cidx]);
       const float4* obs = ctx->cloud_dev[cidx] + (n_runs ? runs[0].at : 0u);
       if (n_runs > 1) {
         if (!s->lidar_obs) HIPCHK(ctx, dev_alloc(s->mem, &s->lidar_obs, (size_t)std::max<uint32_t>(ctx->cfg.max_points, 1)));
@@ -289,10 +285,7 @@ int dddmr_rollout_stack_update(dddmr_rollout_ctx* ctx, const double T_base_senso
   std::unique_lock<std::mutex> prod(ctx->producer_mu, std::defer_lock);
   if (depth) {
     prod.lock();
-    bool any = false, ready = true;
-    for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i)
-      if (ctx->depth[i]) { any = true; ready = ready && ctx->has_frustum[i]; }
-    if (!any || !ready) {
+    if (!ctx->sources.depth_frustums_ready()) {
       out.depth_skipped = 1;                             // isFirstScanReady: the plugin returns early, the stack goes on
     } else {
       out.depth_rc = depth_layer_update_locked(ctx, T_gbl_base, &out.depth);

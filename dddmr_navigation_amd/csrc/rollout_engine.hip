@@ -31,6 +31,7 @@
 #include "lidar_sweep.hip.h"
 #include "lidar_features.hip.h"
 #include "measure_kernels.hip.h"
+#include "source_table.hip.h"
 
 using namespace dddmr;
 
@@ -49,6 +50,18 @@ void stack_free(StackState* s);
 struct MclState;                           // the particle filter's lidar likelihood, mcl_measure.hip.h
 void mcl_free(MclState* s);
 
+// What a sensor source owns, beside its record in the context's SourceTable (sensor_sources.hip.h keeps the two in step).
+struct SourceOwned {
+  PerceptionScratch* feed = nullptr;       // scan sources above 0: stitcher state and staging (source 0 feeds through ctx->feed)
+  DepthSource* depth = nullptr;            // depth sources
+  DepthImage* dimg = nullptr;              // ... that are fed images
+  LidarSweep* sweep = nullptr;             // sweep sources
+  // the latest observation on the device: a scan source's own allocation (made by its first feed), otherwise an alias of
+  // the depth source's current frame buffer or of the sweep's current observation buffer
+  float4* obs = nullptr;
+  DcFrustum frustum{};                     // depth sources: valid while the record says has_frustum
+};
+
 }  // namespace
 
 struct dddmr_rollout_ctx {
@@ -66,12 +79,9 @@ struct dddmr_rollout_ctx {
   // device memory
   float4* cloud_dev[kCloudBufs] = {nullptr, nullptr, nullptr};
   uint32_t cloud_n[kCloudBufs] = {0, 0, 0};
-  // where a published aggregate came from (recorded by publish_cloud under cloud_mu): the sources' point counts in source
-  // order with the lidar ones flagged, or cloud_from_sources false after a set_cloud.  What the perception stack cuts the
-  // lidar sources' observation out of a pinned aggregate with.
-  uint32_t cloud_src_n[kCloudBufs][DDDMR_MAX_SOURCES] = {};
-  uint8_t cloud_src_lidar[kCloudBufs] = {0, 0, 0};     // bit i: source i is a lidar source
-  bool cloud_from_sources[kCloudBufs] = {true, true, true};   // (nothing published yet: the sources' empty aggregate)
+  // where a published aggregate came from (recorded by publish_cloud under cloud_mu; nothing published yet: the sources'
+  // empty aggregate).  What the perception stack cuts the lidar sources' observation out of a pinned aggregate with.
+  SourceLayout cloud_layout[kCloudBufs];
   uint2* pt_slot = nullptr;
   Pt3* sorted = nullptr;
   uint32_t *cell_count = nullptr, *cell_start = nullptr;
@@ -103,26 +113,12 @@ struct dddmr_rollout_ctx {
   double* poses_dev = nullptr;
   // perception feed scratch
   PerceptionScratch feed{};
-  // several sensors feeding one aggregate (StackedPerception::aggregateObservations, stacked_perception.cpp:128-140):
-  // sources 1.. get their own scratch (stitcher state, staging) and every source its latest observation on the device
+  // The sensor sources feeding one aggregate: the bookkeeping and its rules in source_table.hip.h, the entry points in
+  // sensor_sources.hip.h.  Both under producer_mu.
   static constexpr int kMaxSources = DDDMR_MAX_SOURCES;
-  PerceptionScratch* src_feed[kMaxSources] = {};       // [0] unused (source 0 feeds through `feed`)
-  float4* src_cloud[kMaxSources] = {};                 // latest observation of a source, allocated on first use
-  uint32_t src_n[kMaxSources] = {};
-  bool multi_source = false;
-  // depth camera sources (dddmr_rollout_set_depth_source): src_cloud[i] then aliases the source's current frame buffer
-  DepthSource* depth[kMaxSources] = {};
-  // non-null for a depth source that is fed images (dddmr_rollout_set_depth_image_source); depth[i] is set as well
-  DepthImage* dimg[kMaxSources] = {};
-  bool src_is_lidar[kMaxSources] = {};                 // a scan has been fed under this id, or it is a sweep source
-  // lidar sources fed raw sweeps (dddmr_rollout_set_lidar_sweep_source): src_cloud[i] then aliases the sweep's current
-  // observation buffer and src_is_lidar[i] is set
-  LidarSweep* sweep[kMaxSources] = {};
-  // frustums of the depth sources (dddmr_rollout_set_depth_frustum) and the clearing verdicts' scratch (depth_clear.hip.h)
-  DcFrustum frustum[kMaxSources] = {};
-  bool has_frustum[kMaxSources] = {};
-  DepthClear* dclear = nullptr;                        // allocated by the first verdict / point-test call
-  uint64_t depth_epoch = 1;                            // bumped whenever a depth source's observation changes
+  SourceTable sources;
+  SourceOwned src[kMaxSources];
+  DepthClear* dclear = nullptr;     // the clearing verdicts' scratch (depth_clear.hip.h), allocated by the first verdict / point-test call
 
   // pinned host memory
   float4* cloud_stage[kCloudBufs] = {nullptr, nullptr, nullptr};   // pinned staging, one per device cloud buffer
@@ -184,6 +180,7 @@ struct dddmr_rollout_ctx {
 namespace {
 
 void release_cloud(dddmr_rollout_ctx* c);
+void release_source(dddmr_rollout_ctx* c, int id);   // sensor_sources.hip.h
 
 // RCCL entry points, resolved at run time: the engine has no link-time dependency on librccl (hosts
 // that never call dddmr_rollout_comm_init do not need it), and a process that already holds a copy --
@@ -268,8 +265,6 @@ int dddmr_rollout_diag_rstamps(unsigned long long* out, size_t n_words) {
 }
 #endif
 
-static void sweep_features_off(LidarSweep& sw);
-
 const char* dddmr_rollout_version(void) { return "dddmr-rollout-mi355x 0.1 (gfx950)"; }
 
 size_t dddmr_rollout_sizeof(int which) {
@@ -342,13 +337,7 @@ void dddmr_rollout_destroy(dddmr_rollout_ctx* ctx) {
     if (p) (void)hipFree(p);
   perception_free(ctx->feed);
   if (ctx->dclear) { dc_free(*ctx->dclear); delete ctx->dclear; }
-  for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) {
-    if (ctx->depth[i]) { depth_free(*ctx->depth[i]); delete ctx->depth[i]; ctx->src_cloud[i] = nullptr; }
-    if (ctx->sweep[i]) { sweep_features_off(*ctx->sweep[i]); sweep_free(*ctx->sweep[i]); delete ctx->sweep[i]; ctx->src_cloud[i] = nullptr; }
-    if (ctx->dimg[i]) { dimg_free(*ctx->dimg[i]); delete ctx->dimg[i]; }
-    if (ctx->src_feed[i]) { perception_free(*ctx->src_feed[i]); delete ctx->src_feed[i]; }
-    if (ctx->src_cloud[i]) (void)hipFree(ctx->src_cloud[i]);
-  }
+  for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) release_source(ctx, i);
   for (int i = 0; i < kCloudBufs; ++i)
     if (ctx->cloud_stage[i]) (void)hipHostFree(ctx->cloud_stage[i]);
   if (ctx->small_stage) (void)hipHostFree(ctx->small_stage);
@@ -482,17 +471,12 @@ int dddmr_rollout_create(const dddmr_rollout_config* cfg, dddmr_rollout_ctx** ou
   return DDDMR_OK;
 }
 
-// Publish a device-side cloud buffer as the new front buffer.  producer_mu held.  from_sources: 0 a cloud handed over
-// with set_cloud, 1 the concatenation of src_n[] in source order, 2 the single-producer set_scan (all of it is lidar 0).
-static void publish_cloud(dddmr_rollout_ctx* ctx, int idx, uint32_t n, int from_sources) {
+// Publish a device-side cloud buffer as the new front buffer.  producer_mu held.  layout: where its points came from
+// (the sources' layout(), single_lidar_layout() for the single-producer set_scan, foreign_layout() for a set_cloud).
+static void publish_cloud(dddmr_rollout_ctx* ctx, int idx, uint32_t n, const SourceLayout& layout) {
   std::lock_guard<std::mutex> lk(ctx->cloud_mu);
   ctx->cloud_n[idx] = n;
-  ctx->cloud_from_sources[idx] = from_sources != 0;
-  ctx->cloud_src_lidar[idx] = 0;
-  for (int i = 0; i < DDDMR_MAX_SOURCES; ++i) {
-    ctx->cloud_src_n[idx][i] = from_sources == 1 ? ctx->src_n[i] : (from_sources == 2 && i == 0 ? n : 0u);
-    if (from_sources == 2 ? i == 0 : ctx->src_is_lidar[i]) ctx->cloud_src_lidar[idx] |= (uint8_t)(1u << i);
-  }
+  ctx->cloud_layout[idx] = layout;
   ctx->front = idx;
   ctx->wait_pending[idx] = true;
 }
@@ -555,892 +539,7 @@ int dddmr_rollout_set_cloud(dddmr_rollout_ctx* ctx, const float* xyzi, size_t n_
                                  ctx->copy_stream));
   }
   HIPCHK(ctx, hipEventRecord(ctx->cloud_ready[back], ctx->copy_stream));
-  publish_cloud(ctx, back, (uint32_t)n_points, 0);
-  return DDDMR_OK;
-}
-
-// one sensor's scan through the feed; source < 0: the single-producer form (the result replaces the aggregate)
-static int set_scan_impl(dddmr_rollout_ctx* ctx, int source, const float* xyz, size_t n_points, size_t stride_bytes,
-                         const double T_base_sensor[7], const double T_gbl_base[7], double perception_window_size,
-                         double marking_height, uint32_t* n_out_points, uint32_t* n_aggregate) {
-  if (!ctx || !T_base_sensor || !T_gbl_base) return DDDMR_ERR_BAD_ARG;
-  if (source >= dddmr_rollout_ctx::kMaxSources) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_scan: source %d (at most %d sensors)", source, dddmr_rollout_ctx::kMaxSources);
-  if (n_points > 0 && (!xyz || stride_bytes < 12 || stride_bytes % 4 != 0))
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_scan: bad pointer/stride");
-  if (n_points > ctx->cfg.max_points)
-    return fail(ctx, DDDMR_ERR_CAPACITY, "set_scan: %zu points > max_points %u", n_points, ctx->cfg.max_points);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  if (source < 0 && ctx->multi_source) source = 0;              // once several sensors feed, plain set_scan is sensor 0
-  if (source >= 0 && ctx->depth[source]) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_scan: source %d is a depth camera source", source);
-  if (ctx->sweep[std::max(source, 0)]) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_scan: source %d is a lidar sweep source", std::max(source, 0));
-  if (source < 0) ctx->src_is_lidar[0] = true;                  // the single-producer form is the lidar of source 0
-  PerceptionScratch* scratch = &ctx->feed;
-  if (source > 0) {
-    if (!ctx->src_feed[source]) {
-      auto* ps = new PerceptionScratch();
-      if (perception_alloc(*ps, ctx->cfg.max_points) != 0) { perception_free(*ps); delete ps; return fail(ctx, DDDMR_ERR_HIP, "set_scan: scratch of source %d", source); }
-      ctx->src_feed[source] = ps;
-    }
-    scratch = ctx->src_feed[source];
-  }
-  if (scratch->stitcher_num > 0 && n_points == 0) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_scan: empty scan with the stitcher on");
-  if (source >= 0) {
-    ctx->multi_source = true;
-    ctx->src_is_lidar[source] = true;
-    if (!ctx->src_cloud[source]) HIPCHK(ctx, hipMalloc(&ctx->src_cloud[source], (size_t)std::max<uint32_t>(ctx->cfg.max_points, 1) * sizeof(float4)));
-  }
-  const int back = acquire_back(ctx);
-  FeedParams fp;
-  quat_to_rot(T_base_sensor, fp.Rbs);
-  quat_to_rot(T_gbl_base, fp.Rgb);
-  for (int i = 0; i < 3; ++i) {
-    fp.tbs[i] = T_base_sensor[i];
-    fp.tgb[i] = T_gbl_base[i];
-  }
-  fp.n = (int)n_points;
-  fp.window = (float)perception_window_size;
-  fp.height = (float)marking_height;
-  uint32_t n_out = 0;
-  float4* dst = source >= 0 ? ctx->src_cloud[source] : ctx->cloud_dev[back];
-  const int rc = perception_feed(*scratch, fp, xyz, stride_bytes, dst, ctx->copy_stream, &n_out);
-  if (rc == -2) return fail(ctx, DDDMR_ERR_CAPACITY, "set_scan: the (stitched) scan exceeds max_points %u", ctx->cfg.max_points);
-  if (rc != 0) return fail(ctx, DDDMR_ERR_HIP, "set_scan: perception feed failed (%d)", rc);
-  uint32_t n_all = n_out;
-  if (source >= 0) {
-    // the aggregate = every sensor's latest observation, in sensor order (aggregateObservations' loop over the plugins)
-    ctx->src_n[source] = n_out;
-    size_t total = 0;
-    for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) total += ctx->src_n[i];
-    if (total > ctx->cfg.max_points) return fail(ctx, DDDMR_ERR_CAPACITY, "set_scan: the sensors' observations together (%zu points) exceed max_points %u", total, ctx->cfg.max_points);
-    size_t at = 0;
-    for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) {
-      if (!ctx->src_n[i]) continue;
-      HIPCHK(ctx, hipMemcpyAsync(ctx->cloud_dev[back] + at, ctx->src_cloud[i], (size_t)ctx->src_n[i] * sizeof(float4), hipMemcpyDeviceToDevice, ctx->copy_stream));
-      at += ctx->src_n[i];
-    }
-    n_all = (uint32_t)total;
-  }
-  // the tick's stream waits on this event, so the feed kernels need not have retired yet
-  HIPCHK(ctx, hipEventRecord(ctx->cloud_ready[back], ctx->copy_stream));
-  publish_cloud(ctx, back, n_all, source >= 0 ? 1 : 2);
-  if (n_out_points) *n_out_points = n_out;
-  if (n_aggregate) *n_aggregate = n_all;
-  return DDDMR_OK;
-}
-
-int dddmr_rollout_set_scan(dddmr_rollout_ctx* ctx, const float* xyz, size_t n_points,
-                           size_t stride_bytes, const double T_base_sensor[7],
-                           const double T_gbl_base[7], double perception_window_size,
-                           double marking_height, uint32_t* n_out_points) {
-  return set_scan_impl(ctx, -1, xyz, n_points, stride_bytes, T_base_sensor, T_gbl_base, perception_window_size, marking_height, n_out_points, nullptr);
-}
-
-int dddmr_rollout_set_scan_source(dddmr_rollout_ctx* ctx, int32_t source_id, const float* xyz, size_t n_points,
-                                  size_t stride_bytes, const double T_base_sensor[7], const double T_gbl_base[7],
-                                  double perception_window_size, double marking_height, uint32_t* n_source_points,
-                                  uint32_t* n_aggregate_points) {
-  if (source_id < 0) return ctx ? fail(ctx, DDDMR_ERR_BAD_ARG, "set_scan_source: source %d", source_id) : DDDMR_ERR_BAD_ARG;
-  return set_scan_impl(ctx, source_id, xyz, n_points, stride_bytes, T_base_sensor, T_gbl_base, perception_window_size, marking_height,
-                       n_source_points, n_aggregate_points);
-}
-
-int dddmr_rollout_set_stitcher(dddmr_rollout_ctx* ctx, int32_t stitcher_num) {
-  if (!ctx || stitcher_num < 0) return DDDMR_ERR_BAD_ARG;
-  std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  if (ctx->depth[0]) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_stitcher: source 0 is a depth camera source");
-  if (ctx->sweep[0]) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_stitcher: source 0 is a lidar sweep source (no stitcher on sweeps)");
-  ctx->feed.stitcher_num = stitcher_num;
-  ctx->feed.stitched.clear();
-  return DDDMR_OK;
-}
-
-int dddmr_rollout_set_stitcher_source(dddmr_rollout_ctx* ctx, int32_t source_id, int32_t stitcher_num) {
-  if (!ctx || stitcher_num < 0 || source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources) return DDDMR_ERR_BAD_ARG;
-  if (source_id == 0) return dddmr_rollout_set_stitcher(ctx, stitcher_num);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  if (ctx->depth[source_id]) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_stitcher: source %d is a depth camera source", source_id);
-  if (ctx->sweep[source_id]) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_stitcher: source %d is a lidar sweep source (no stitcher on sweeps)", source_id);
-  if (!ctx->src_feed[source_id]) {
-    auto* ps = new PerceptionScratch();
-    if (perception_alloc(*ps, ctx->cfg.max_points) != 0) { perception_free(*ps); delete ps; return fail(ctx, DDDMR_ERR_HIP, "set_stitcher: scratch of source %d", source_id); }
-    ctx->src_feed[source_id] = ps;
-  }
-  ctx->src_feed[source_id]->stitcher_num = stitcher_num;
-  ctx->src_feed[source_id]->stitched.clear();
-  return DDDMR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Depth camera sources: DepthCameraLayer::getObservation in local mode (depth_feed.hip.h)
-// ---------------------------------------------------------------------------
-// The aggregate = every source's current observation in source order, into a back buffer, published.
-// producer_mu held; *n_aggregate = sum of src_n[] (the caller has checked it against max_points).
-static int publish_sources(dddmr_rollout_ctx* ctx, uint32_t* n_aggregate) {
-  const int back = acquire_back(ctx);
-  size_t at = 0;
-  for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) {
-    if (!ctx->src_n[i]) continue;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->cloud_dev[back] + at, ctx->src_cloud[i], (size_t)ctx->src_n[i] * sizeof(float4), hipMemcpyDeviceToDevice, ctx->copy_stream));
-    at += ctx->src_n[i];
-  }
-  HIPCHK(ctx, hipEventRecord(ctx->cloud_ready[back], ctx->copy_stream));
-  publish_cloud(ctx, back, (uint32_t)at, 1);
-  *n_aggregate = (uint32_t)at;
-  return DDDMR_OK;
-}
-
-// icfg == nullptr: a source fed point clouds; otherwise one fed depth images
-static int set_depth_source_impl(dddmr_rollout_ctx* ctx, const char* what, int32_t source_id, const dddmr_depth_source_config* cfg,
-                                 const dddmr_depth_image_config* icfg) {
-  if (!ctx) return DDDMR_ERR_BAD_ARG;
-  if (!cfg || source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d (at most %d sensors) / null config", what, source_id, dddmr_rollout_ctx::kMaxSources);
-  if (!(cfg->min_obstacle_height <= cfg->max_obstacle_height) || cfg->observation_persistence_ns < 0 || cfg->max_frame_points == 0 ||
-      cfg->max_frames == 0)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: bad height band / persistence / capacities", what);
-  if (cfg->max_frame_points > (1u << 28)) return fail(ctx, DDDMR_ERR_CAPACITY, "%s: max_frame_points %u", what, cfg->max_frame_points);
-  DimgParams ip{};
-  if (icfg) {
-    if (icfg->width == 0 || icfg->height == 0 || icfg->width > 16384 || icfg->height > 16384 || icfg->sample_step == 0 ||
-        (icfg->flags & ~DDDMR_DEPTH_IMAGE_DROP_ZERO) != 0)
-      return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: image %u x %u, sample_step %u, flags %#x", what, icfg->width, icfg->height,
-                  icfg->sample_step, icfg->flags);
-    if (!std::isfinite(icfg->fx) || !std::isfinite(icfg->fy) || icfg->fx == 0.0 || icfg->fy == 0.0 || !std::isfinite(icfg->cx) ||
-        !std::isfinite(icfg->cy) || !(icfg->max_distance > 0.0) || !(icfg->leaf_size > 0.0) || !std::isfinite(icfg->leaf_size))
-      return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: bad intrinsics / max_distance / leaf_size", what);
-    // cbDepthImg:111-114: float cx = K[2], cy = K[5], fx = 1.0f / K[0], fy = 1.0f / K[4] (double division, float result)
-    ip.cx = (float)icfg->cx;
-    ip.cy = (float)icfg->cy;
-    ip.fx = (float)(1.0 / icfg->fx);
-    ip.fy = (float)(1.0 / icfg->fy);
-    ip.inv_leaf = 1.0f / (float)icfg->leaf_size;      // pcl::VoxelGrid::setLeafSize(float ...): inverse_leaf_size_ = 1 / leaf_size_
-    ip.drop_zero = (icfg->flags & DDDMR_DEPTH_IMAGE_DROP_ZERO) ? 1u : 0u;
-    ip.max_distance = icfg->max_distance;
-    ip.width = icfg->width;
-    ip.step = icfg->sample_step;
-    ip.cols = (icfg->width + icfg->sample_step - 1) / icfg->sample_step;
-    ip.rows = (icfg->height + icfg->sample_step - 1) / icfg->sample_step;
-    if (!std::isfinite(ip.inv_leaf) || !std::isfinite(ip.fx) || !std::isfinite(ip.fy) || !dimg_box_ok(ip, icfg->height))
-      return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: the frustum's voxel box (intrinsics, max_distance %g, leaf_size %g) could reach 2^31 cells",
-                  what, icfg->max_distance, icfg->leaf_size);
-    if ((uint64_t)ip.rows * ip.cols > cfg->max_frame_points)
-      return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: max_frame_points %u < the %u x %u sampled pixels", what, cfg->max_frame_points, ip.rows, ip.cols);
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  if (ctx->src_is_lidar[source_id] || ctx->src_feed[source_id] || (source_id == 0 && ctx->feed.stitcher_num > 0))
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d is a lidar source", what, source_id);
-  const bool had_points = ctx->src_n[source_id] != 0;
-  if (ctx->depth[source_id]) {                       // re-configuring empties the source
-    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-    depth_free(*ctx->depth[source_id]);
-    delete ctx->depth[source_id];
-    ctx->depth[source_id] = nullptr;
-    if (ctx->dimg[source_id]) {
-      dimg_free(*ctx->dimg[source_id]);
-      delete ctx->dimg[source_id];
-      ctx->dimg[source_id] = nullptr;
-    }
-    ctx->src_cloud[source_id] = nullptr;
-    ctx->src_n[source_id] = 0;
-    ctx->has_frustum[source_id] = false;               // the frustum belongs to the observations that just left
-    ++ctx->depth_epoch;
-  }
-  auto* ds = new DepthSource();
-  ds->zmin = cfg->min_obstacle_height;
-  ds->zmax = cfg->max_obstacle_height;
-  ds->persistence_ns = cfg->observation_persistence_ns;
-  ds->max_frame_points = cfg->max_frame_points;
-  ds->max_frames = cfg->max_frames;
-  DepthImage* di = nullptr;
-  if (icfg) {
-    di = new DepthImage();
-    di->p = ip;
-    di->height = icfg->height;
-  }
-  int rc = DDDMR_OK;
-  if (depth_alloc(*ds, ctx->cfg.max_points, icfg == nullptr) != 0 || (di && dimg_alloc(*di) != 0)) {
-    depth_free(*ds);
-    delete ds;
-    if (di) {
-      dimg_free(*di);
-      delete di;
-    }
-    rc = fail(ctx, DDDMR_ERR_HIP, "%s: scratch of source %d", what, source_id);
-  } else {
-    ctx->depth[source_id] = ds;
-    ctx->dimg[source_id] = di;
-    ctx->src_cloud[source_id] = ds->buf[ds->cur];
-    ctx->multi_source = true;
-  }
-  if (had_points) {                                  // the aggregate loses the emptied source's segment
-    uint32_t n_all;
-    const int prc = publish_sources(ctx, &n_all);
-    if (rc == DDDMR_OK) rc = prc;
-  }
-  return rc;
-}
-
-int dddmr_rollout_set_depth_source(dddmr_rollout_ctx* ctx, int32_t source_id, const dddmr_depth_source_config* cfg) {
-  return set_depth_source_impl(ctx, "set_depth_source", source_id, cfg, nullptr);
-}
-
-int dddmr_rollout_set_depth_image_source(dddmr_rollout_ctx* ctx, int32_t source_id, const dddmr_depth_source_config* cfg,
-                                         const dddmr_depth_image_config* image_cfg) {
-  if (!ctx) return DDDMR_ERR_BAD_ARG;
-  if (!image_cfg) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_image_source: null image config");
-  return set_depth_source_impl(ctx, "set_depth_image_source", source_id, cfg, image_cfg);
-}
-
-// One frame of either kind: xyz (a cloud source) or depth_mm (an image source) is set.  bufferCloud's bookkeeping around
-// the device work is the same for both.
-static int set_depth_impl(dddmr_rollout_ctx* ctx, const char* what, int32_t source_id, const float* xyz, size_t n_points,
-                          const uint16_t* depth_mm, size_t stride_bytes, const double T_base_sensor[7], const double T_gbl_base[7],
-                          int64_t stamp_ns, uint32_t* n_camera_points, uint32_t* n_frame_points, uint32_t* n_source_points,
-                          uint32_t* n_aggregate_points) {
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  DepthSource* ds = ctx->depth[source_id];
-  if (!ds) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d is not a configured depth source", what, source_id);
-  DepthImage* di = ctx->dimg[source_id];
-  if (depth_mm && !di) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d is configured for point clouds", what, source_id);
-  if (!depth_mm && di) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d is configured for depth images", what, source_id);
-  if (depth_mm && stride_bytes < 2 * (size_t)di->p.width)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: row stride %zu < 2 * width %u", what, stride_bytes, di->p.width);
-  if (n_points > ds->max_frame_points)
-    return fail(ctx, DDDMR_ERR_CAPACITY, "%s: %zu points > max_frame_points %u", what, n_points, ds->max_frame_points);
-  // purgeStaleObservations (depth_camera_observation_buffer.cpp:203-231) with last_updated_ = stamp_ns decides from
-  // the stamps alone, so which observations stay is known before the frame is processed
-  const int64_t stamp_us = stamp_ns / 1000;          // pcl_conversions::toPCL keeps whole microseconds
-  auto stays = [&](int64_t us, bool newest) {
-    if (ds->persistence_ns == 0) return newest;      // "keeping observations for no time": only the newest one
-    return !(stamp_ns - us * 1000 > ds->persistence_ns);
-  };
-  std::vector<DepthFrame> kept;
-  size_t kept_points = 0;
-  for (const DepthFrame& fr : ds->frames)
-    if (stays(fr.stamp_us, false)) { kept.push_back(fr); kept_points += fr.n; }
-  const bool none_leaves = kept.size() == ds->frames.size();
-  const bool new_alive = stays(stamp_us, true);
-  if (kept.size() + (new_alive ? 1 : 0) > ds->max_frames)
-    return fail(ctx, DDDMR_ERR_CAPACITY, "%s: %zu observations alive > max_frames %u", what, kept.size() + 1, ds->max_frames);
-  // Nothing leaves: the frame is appended behind the alive ones.  Otherwise the ones that stay are copied to the
-  // other buffer (device to device) and the frame is built behind them; the buffers swap on success only.
-  const int dst_buf = none_leaves ? ds->cur : ds->cur ^ 1;
-  if (!none_leaves) {
-    size_t src_at = 0, dst_at = 0;
-    for (const DepthFrame& fr : ds->frames) {        // the caller's stamps need not be monotonic: any frame may be the one to leave
-      if (stays(fr.stamp_us, false) && fr.n) {
-        HIPCHK(ctx, hipMemcpyAsync(ds->buf[dst_buf] + dst_at, ds->buf[ds->cur] + src_at, (size_t)fr.n * sizeof(float4), hipMemcpyDeviceToDevice, ctx->copy_stream));
-        dst_at += fr.n;
-      }
-      src_at += fr.n;
-    }
-  }
-  DepthParams dp;
-  quat_to_rot(T_base_sensor, dp.Rbs);
-  quat_to_rot(T_gbl_base, dp.Rgb);
-  for (int i = 0; i < 3; ++i) {
-    dp.tbs[i] = T_base_sensor[i];
-    dp.tgb[i] = T_gbl_base[i];
-  }
-  dp.zmin = ds->zmin;
-  dp.zmax = ds->zmax;
-  dp.n = (int)n_points;
-  uint32_t n_out = 0, n_camera = 0;
-  const int rc = di ? depth_image_feed(*ds, *di, dp, depth_mm, stride_bytes, ds->buf[dst_buf] + kept_points, ctx->copy_stream, &n_camera, &n_out)
-                    : depth_feed(*ds, dp, xyz, stride_bytes, ds->buf[dst_buf] + kept_points, ctx->copy_stream, &n_out);
-  if (rc != 0) return fail(ctx, DDDMR_ERR_HIP, "%s: depth feed failed (%d)", what, rc);
-  const size_t n_source = kept_points + (new_alive ? n_out : 0);
-  size_t total = n_source;
-  for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i)
-    if (i != source_id) total += ctx->src_n[i];
-  if (total > ctx->cfg.max_points)
-    return fail(ctx, DDDMR_ERR_CAPACITY, "%s: the sensors' observations together (%zu points) exceed max_points %u", what, total, ctx->cfg.max_points);
-  // commit: from here on nothing fails before the aggregate is rebuilt from the new state
-  const std::vector<DepthFrame> old_frames = ds->frames;
-  const int old_cur = ds->cur;
-  const uint32_t old_n = ctx->src_n[source_id];
-  if (new_alive) kept.push_back(DepthFrame{n_out, stamp_us});
-  ds->frames.swap(kept);
-  ds->cur = dst_buf;
-  ctx->src_cloud[source_id] = ds->buf[ds->cur];
-  ctx->src_n[source_id] = (uint32_t)n_source;
-  ++ctx->depth_epoch;                                // the clearing verdicts' grid is rebuilt by the next call that needs it
-  uint32_t n_all = 0;
-  const int prc = publish_sources(ctx, &n_all);
-  if (prc != DDDMR_OK) {                             // a failed copy: the source goes back to what the published aggregate holds
-    ds->frames = old_frames;
-    ds->cur = old_cur;
-    ctx->src_cloud[source_id] = ds->buf[ds->cur];
-    ctx->src_n[source_id] = old_n;
-    return prc;
-  }
-  if (di) {                                          // the stage-one cloud of an accepted image becomes the source's latest
-    di->cur ^= 1;
-    di->n_cloud = n_camera;
-  }
-  if (n_camera_points) *n_camera_points = n_camera;
-  if (n_frame_points) *n_frame_points = n_out;
-  if (n_source_points) *n_source_points = (uint32_t)n_source;
-  if (n_aggregate_points) *n_aggregate_points = n_all;
-  return DDDMR_OK;
-}
-
-int dddmr_rollout_set_depth_frame(dddmr_rollout_ctx* ctx, int32_t source_id, const float* xyz, size_t n_points,
-                                  size_t stride_bytes, const double T_base_sensor[7], const double T_gbl_base[7],
-                                  int64_t stamp_ns, uint32_t* n_frame_points, uint32_t* n_source_points,
-                                  uint32_t* n_aggregate_points) {
-  if (!ctx || !T_base_sensor || !T_gbl_base) return DDDMR_ERR_BAD_ARG;
-  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_frame: source %d (at most %d sensors)", source_id, dddmr_rollout_ctx::kMaxSources);
-  if (n_points > 0 && (!xyz || stride_bytes < 12 || stride_bytes % 4 != 0))
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_frame: bad pointer/stride");
-  return set_depth_impl(ctx, "set_depth_frame", source_id, xyz, n_points, nullptr, stride_bytes, T_base_sensor, T_gbl_base, stamp_ns,
-                        nullptr, n_frame_points, n_source_points, n_aggregate_points);
-}
-
-int dddmr_rollout_set_depth_image(dddmr_rollout_ctx* ctx, int32_t source_id, const uint16_t* depth_mm, size_t row_stride_bytes,
-                                  const double T_base_optical[7], const double T_gbl_base[7], int64_t stamp_ns,
-                                  uint32_t* n_camera_points, uint32_t* n_frame_points, uint32_t* n_source_points,
-                                  uint32_t* n_aggregate_points) {
-  if (!ctx || !T_base_optical || !T_gbl_base) return DDDMR_ERR_BAD_ARG;
-  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_image: source %d (at most %d sensors)", source_id, dddmr_rollout_ctx::kMaxSources);
-  if (!depth_mm) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_image: null image");
-  return set_depth_impl(ctx, "set_depth_image", source_id, nullptr, 0, depth_mm, row_stride_bytes, T_base_optical, T_gbl_base, stamp_ns,
-                        n_camera_points, n_frame_points, n_source_points, n_aggregate_points);
-}
-
-int dddmr_rollout_get_depth_image_cloud(dddmr_rollout_ctx* ctx, int32_t source_id, float* xyz_out, size_t capacity, size_t* n_points) {
-  if (!ctx || !n_points) return DDDMR_ERR_BAD_ARG;
-  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "get_depth_image_cloud: source %d (at most %d sensors)", source_id, dddmr_rollout_ctx::kMaxSources);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  const DepthImage* di = ctx->dimg[source_id];
-  if (!di) return fail(ctx, DDDMR_ERR_BAD_ARG, "get_depth_image_cloud: source %d is not a depth image source", source_id);
-  *n_points = di->n_cloud;
-  if (!xyz_out) return DDDMR_OK;
-  if (capacity < di->n_cloud) return fail(ctx, DDDMR_ERR_CAPACITY, "get_depth_image_cloud: capacity %zu < %u", capacity, di->n_cloud);
-  if (di->n_cloud) {
-    HIPCHK(ctx, hipMemcpyAsync(xyz_out, di->cloud[di->cur], (size_t)di->n_cloud * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->copy_stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-  }
-  return DDDMR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Lidar sweep sources: the front half of ImageProjection::cloudHandler, then cbSensor (lidar_sweep.hip.h)
-// ---------------------------------------------------------------------------
-int dddmr_rollout_set_lidar_sweep_source(dddmr_rollout_ctx* ctx, int32_t source_id, const dddmr_lidar_sweep_config* cfg) {
-  if (!ctx) return DDDMR_ERR_BAD_ARG;
-  const char* what = "set_lidar_sweep_source";
-  if (!cfg || source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d (at most %d sensors) / null config", what, source_id, dddmr_rollout_ctx::kMaxSources);
-  const uint32_t V = cfg->num_vertical_scans, H = cfg->num_horizontal_scans;
-  if (V < 2 || H < 4 || cfg->ground_scan_index >= V || !(cfg->vertical_angle_top > cfg->vertical_angle_bottom) ||
-      !(cfg->minimum_detection_range < cfg->maximum_detection_range) || cfg->flags != 0)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: image %u x %u, ground_scan_index %u, angles %g .. %g, range %g .. %g, flags %#x", what, V, H,
-                cfg->ground_scan_index, cfg->vertical_angle_bottom, cfg->vertical_angle_top, cfg->minimum_detection_range,
-                cfg->maximum_detection_range, cfg->flags);
-  if (!std::isfinite(cfg->vertical_angle_bottom) || !std::isfinite(cfg->vertical_angle_top) || !std::isfinite(cfg->segment_theta) ||
-      !std::isfinite(cfg->minimum_detection_range) || !std::isfinite(cfg->maximum_detection_range) || !std::isfinite(cfg->sensor_mount_angle))
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: non-finite parameter", what);
-  if (V > kSweepMaxRows || H > kSweepMaxCols || (uint64_t)V * H > kSweepMaxPixels || cfg->max_sweep_points > kSweepMaxPoints)
-    return fail(ctx, DDDMR_ERR_CAPACITY, "%s: image %u x %u (at most %u x %u, %u pixels), max_sweep_points %u (at most %u)", what, V, H,
-                kSweepMaxRows, kSweepMaxCols, kSweepMaxPixels, cfg->max_sweep_points, kSweepMaxPoints);
-  // the constructor's conversions (imageProjection.cpp:67-125 into the members of imageProjection.h:67-107)
-  const double kDegToRad = M_PI / 180.0;                         // utility.h:51
-  SweepParams k{};
-  const float bottom = (float)cfg->vertical_angle_bottom, top = (float)cfg->vertical_angle_top;
-  k.V = V;
-  k.H = H;
-  k.gsi = cfg->ground_scan_index;
-  k.res_x = (float)((M_PI * 2) / (int)H);
-  k.res_y = (float)(kDegToRad * (double)(top - bottom) / (double)(float)((int)V - 1));
-  k.ang_bottom = (float)(-((double)bottom - 0.1) * kDegToRad);
-  float theta = (float)cfg->segment_theta;
-  theta = (float)((double)theta * kDegToRad);
-  k.tan_theta = std::tan(theta);                                 // float overloads on float arguments
-  k.sin_x = std::sin(k.res_x);
-  k.cos_x = std::cos(k.res_x);
-  k.sin_y = std::sin(k.res_y);
-  k.cos_y = std::cos(k.res_y);
-  k.min_range = (float)cfg->minimum_detection_range;
-  k.max_range = (float)cfg->maximum_detection_range;
-  k.valid_points = cfg->segment_valid_point_num;
-  k.valid_lines = cfg->segment_valid_line_num;
-  k.mount = cfg->sensor_mount_angle;
-  k.ground_limit = 10 * kDegToRad;
-  {
-    // tf2::Quaternion::setRPY(0, mount, 0) = (0, sin(mount / 2), 0, cos(mount / 2)), through transformToEigen
-    const double q[7] = {0, 0, 0, 0, std::sin(cfg->sensor_mount_angle * 0.5), 0, std::cos(cfg->sensor_mount_angle * 0.5)};
-    quat_to_rot(q, k.Rp);
-  }
-  if (!(k.res_y > 0.f) || !std::isfinite(k.max_range))
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: the vertical resolution or the maximum range does not fit a float", what);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  if (ctx->depth[source_id]) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d is a depth camera source", what, source_id);
-  if (!ctx->sweep[source_id] && (ctx->src_is_lidar[source_id] || ctx->src_feed[source_id] || (source_id == 0 && ctx->feed.stitcher_num > 0)))
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d is a scan source", what, source_id);
-  const bool had_points = ctx->src_n[source_id] != 0;
-  if (ctx->sweep[source_id]) {                         // re-configuring empties the source
-    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-    sweep_features_off(*ctx->sweep[source_id]);          // re-configuring turns the features off
-    sweep_free(*ctx->sweep[source_id]);
-    delete ctx->sweep[source_id];
-    ctx->sweep[source_id] = nullptr;
-    ctx->src_cloud[source_id] = nullptr;
-    ctx->src_n[source_id] = 0;
-    ctx->src_is_lidar[source_id] = false;
-  }
-  auto* sw = new LidarSweep();
-  sw->p = k;
-  sw->max_points = cfg->max_sweep_points;
-  int rc = DDDMR_OK;
-  if (sweep_alloc(*sw) != 0) {
-    sweep_free(*sw);
-    delete sw;
-    rc = fail(ctx, DDDMR_ERR_HIP, "%s: scratch of source %d", what, source_id);
-  } else {
-    ctx->sweep[source_id] = sw;
-    ctx->src_cloud[source_id] = sw->obs[sw->cur];
-    ctx->src_is_lidar[source_id] = true;
-    ctx->multi_source = true;
-  }
-  if (had_points) {                                    // the aggregate loses the emptied source's segment
-    uint32_t n_all;
-    const int prc = publish_sources(ctx, &n_all);
-    if (rc == DDDMR_OK) rc = prc;
-  }
-  return rc;
-}
-
-int dddmr_rollout_set_lidar_sweep(dddmr_rollout_ctx* ctx, int32_t source_id, const float* xyz, size_t n_points, size_t stride_bytes,
-                                  const double T_base_sensor[7], const double T_gbl_base[7], double perception_window_size,
-                                  double marking_height, uint32_t* n_segmented, uint32_t* n_source_points, uint32_t* n_aggregate_points) {
-  if (!ctx || !T_base_sensor || !T_gbl_base) return DDDMR_ERR_BAD_ARG;
-  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_lidar_sweep: source %d (at most %d sensors)", source_id, dddmr_rollout_ctx::kMaxSources);
-  if (n_points > 0 && (!xyz || stride_bytes < 12 || stride_bytes % 4 != 0)) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_lidar_sweep: bad pointer/stride");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  LidarSweep* sw = ctx->sweep[source_id];
-  if (!sw) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_lidar_sweep: source %d is not a configured lidar sweep source", source_id);
-  if (n_points > sw->max_points) return fail(ctx, DDDMR_ERR_CAPACITY, "set_lidar_sweep: %zu points > max_sweep_points %u", n_points, sw->max_points);
-  FeedParams fp;
-  quat_to_rot(T_base_sensor, fp.Rbs);
-  quat_to_rot(T_gbl_base, fp.Rgb);
-  for (int i = 0; i < 3; ++i) {
-    fp.tbs[i] = T_base_sensor[i];
-    fp.tgb[i] = T_gbl_base[i];
-  }
-  fp.n = 0;                                            // the device knows the count
-  fp.window = (float)perception_window_size;
-  fp.height = (float)marking_height;
-  uint32_t n_seg = 0, n_out = 0;
-  const int rc = sweep_feed(*sw, fp, xyz, n_points, stride_bytes, ctx->copy_stream, &n_seg, &n_out);
-  if (rc != 0) return fail(ctx, DDDMR_ERR_HIP, "set_lidar_sweep: sweep feed failed (%d)", rc);
-  FeatResult feat_counts{};
-  if (sw->features) std::memcpy(&feat_counts, sw->features->res_host, sizeof(feat_counts));   // written before the feed's release
-  size_t total = n_out;
-  for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i)
-    if (i != source_id) total += ctx->src_n[i];
-  if (total > ctx->cfg.max_points)
-    return fail(ctx, DDDMR_ERR_CAPACITY, "set_lidar_sweep: the sensors' observations together (%zu points) exceed max_points %u", total, ctx->cfg.max_points);
-  // commit: the buffers the sweep was built in become the current ones
-  const uint32_t old_n = ctx->src_n[source_id];
-  sw->cur ^= 1;
-  ctx->src_cloud[source_id] = sw->obs[sw->cur];
-  ctx->src_n[source_id] = n_out;
-  uint32_t n_all = 0;
-  const int prc = publish_sources(ctx, &n_all);
-  if (prc != DDDMR_OK) {                               // a failed copy: back to what the published aggregate holds
-    sw->cur ^= 1;
-    ctx->src_cloud[source_id] = sw->obs[sw->cur];
-    ctx->src_n[source_id] = old_n;
-    return prc;
-  }
-  sw->n_cloud = n_seg;
-  sw->have_sweep = true;
-  if (LidarFeatures* lf = sw->features) {              // the features were built beside the sweep: they are current with it
-    lf->n_seg[sw->cur] = feat_counts.n_seg;
-    for (int w = 0; w < 3; ++w) lf->n_feat[sw->cur][w] = feat_counts.n_feat[w];
-    lf->have_sweep = true;
-  }
-  if (n_segmented) *n_segmented = n_seg;
-  if (n_source_points) *n_source_points = n_out;
-  if (n_aggregate_points) *n_aggregate_points = n_all;
-  return DDDMR_OK;
-}
-
-int dddmr_rollout_get_lidar_sweep_cloud(dddmr_rollout_ctx* ctx, int32_t source_id, float* xyzl_out, size_t capacity, size_t* n_points) {
-  if (!ctx || !n_points) return DDDMR_ERR_BAD_ARG;
-  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "get_lidar_sweep_cloud: source %d (at most %d sensors)", source_id, dddmr_rollout_ctx::kMaxSources);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  const LidarSweep* sw = ctx->sweep[source_id];
-  if (!sw) return fail(ctx, DDDMR_ERR_STATE, "get_lidar_sweep_cloud: source %d is not a lidar sweep source", source_id);
-  *n_points = sw->n_cloud;
-  if (!xyzl_out) return DDDMR_OK;
-  if (capacity < sw->n_cloud) return fail(ctx, DDDMR_ERR_CAPACITY, "get_lidar_sweep_cloud: capacity %zu < %u", capacity, sw->n_cloud);
-  if (sw->n_cloud) {
-    HIPCHK(ctx, hipMemcpyAsync(xyzl_out, sw->cloud[sw->cur], (size_t)sw->n_cloud * sizeof(float4), hipMemcpyDeviceToHost, ctx->copy_stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-  }
-  return DDDMR_OK;
-}
-
-int dddmr_rollout_get_lidar_sweep_image(dddmr_rollout_ctx* ctx, int32_t source_id, float* range_out, int32_t* label_out, int8_t* ground_out,
-                                        size_t capacity_pixels) {
-  if (!ctx) return DDDMR_ERR_BAD_ARG;
-  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "get_lidar_sweep_image: source %d (at most %d sensors)", source_id, dddmr_rollout_ctx::kMaxSources);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  const LidarSweep* sw = ctx->sweep[source_id];
-  if (!sw) return fail(ctx, DDDMR_ERR_STATE, "get_lidar_sweep_image: source %d is not a lidar sweep source", source_id);
-  const size_t px = (size_t)sw->p.V * sw->p.H;
-  if (capacity_pixels < px) return fail(ctx, DDDMR_ERR_CAPACITY, "get_lidar_sweep_image: capacity %zu < %zu pixels", capacity_pixels, px);
-  if (!sw->have_sweep) {                               // resetParameters' image: nothing projected yet
-    for (size_t i = 0; i < px; ++i) {
-      if (range_out) range_out[i] = FLT_MAX;
-      if (label_out) label_out[i] = -1;
-      if (ground_out) ground_out[i] = 0;
-    }
-    return DDDMR_OK;
-  }
-  if (range_out) HIPCHK(ctx, hipMemcpyAsync(range_out, sw->range_img[sw->cur], px * sizeof(float), hipMemcpyDeviceToHost, ctx->copy_stream));
-  if (label_out) HIPCHK(ctx, hipMemcpyAsync(label_out, sw->label_img[sw->cur], px * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->copy_stream));
-  if (ground_out) HIPCHK(ctx, hipMemcpyAsync(ground_out, sw->ground_img[sw->cur], px, hipMemcpyDeviceToHost, ctx->copy_stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-  return DDDMR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Lidar sweep features: the feature half of mcl_feature_node on a sweep source (lidar_features.hip.h)
-// ---------------------------------------------------------------------------
-static void sweep_features_off(LidarSweep& sw) {
-  if (!sw.features) return;
-  features_free(*sw.features);
-  delete sw.features;
-  sw.features = nullptr;
-}
-
-int dddmr_rollout_set_lidar_sweep_features(dddmr_rollout_ctx* ctx, int32_t source_id, const dddmr_lidar_features_config* cfg) {
-  if (!ctx) return DDDMR_ERR_BAD_ARG;
-  const char* what = "set_lidar_sweep_features";
-  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d (at most %d sensors)", what, source_id, dddmr_rollout_ctx::kMaxSources);
-  if (cfg) {
-    if (!std::isfinite(cfg->edge_threshold) || !std::isfinite(cfg->surf_threshold) || cfg->edge_threshold < 0.0 || cfg->surf_threshold < 0.0 ||
-        cfg->flags != 0)
-      return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: thresholds %g / %g, flags %#x", what, cfg->edge_threshold, cfg->surf_threshold, cfg->flags);
-    for (int i = 0; i < 12; ++i)
-      if (!std::isfinite(cfg->T_out[i])) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: T_out[%d] is not finite", what, i);
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  LidarSweep* sw = ctx->sweep[source_id];
-  if (!sw) return fail(ctx, DDDMR_ERR_STATE, "%s: source %d is not a lidar sweep source", what, source_id);
-  FeatParams k{};
-  if (cfg) {
-    k.edge_threshold = (float)cfg->edge_threshold;     // float members (featureAssociation.h:62-63)
-    k.surf_threshold = (float)cfg->surf_threshold;
-    for (int r = 0; r < 3; ++r) {
-      for (int c = 0; c < 3; ++c) k.R[3 * r + c] = cfg->T_out[4 * r + c];
-      k.t[r] = cfg->T_out[4 * r + 3];
-    }
-    k.V = sw->p.V;
-    k.H = sw->p.H;
-  }
-  HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-  if (!cfg) {
-    sweep_features_off(*sw);
-    return DDDMR_OK;
-  }
-  if (sw->features) {                                  // new parameters: they hold from the next sweep on; what the getters
-    sw->features->p = k;                               // return stays the latest accepted sweep's
-    return DDDMR_OK;
-  }
-  auto* lf = new LidarFeatures();
-  lf->p = k;
-  if (features_alloc(*lf) != 0) {
-    features_free(*lf);
-    delete lf;
-    return fail(ctx, DDDMR_ERR_HIP, "%s: scratch of source %d", what, source_id);
-  }
-  sw->features = lf;
-  return DDDMR_OK;
-}
-
-static int sweep_features_of(dddmr_rollout_ctx* ctx, int32_t source_id, const char* what, LidarSweep** out) {
-  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: source %d (at most %d sensors)", what, source_id, dddmr_rollout_ctx::kMaxSources);
-  LidarSweep* sw = ctx->sweep[source_id];
-  if (!sw) return fail(ctx, DDDMR_ERR_STATE, "%s: source %d is not a lidar sweep source", what, source_id);
-  if (!sw->features) return fail(ctx, DDDMR_ERR_STATE, "%s: the features of source %d are off", what, source_id);
-  *out = sw;
-  return DDDMR_OK;
-}
-
-int dddmr_rollout_get_lidar_sweep_segmented(dddmr_rollout_ctx* ctx, int32_t source_id, float* xyz, float* range, int32_t* col_ind,
-                                            uint8_t* ground_flag, int32_t* start_ring_index, int32_t* end_ring_index, size_t capacity,
-                                            size_t* n) {
-  if (!ctx || !n) return DDDMR_ERR_BAD_ARG;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  LidarSweep* sw = nullptr;
-  const int rc = sweep_features_of(ctx, source_id, "get_lidar_sweep_segmented", &sw);
-  if (rc != DDDMR_OK) return rc;
-  const LidarFeatures& lf = *sw->features;
-  const int b = sw->cur;
-  const size_t count = lf.n_seg[b], V = sw->p.V;
-  const bool points = xyz || range || col_ind || ground_flag;
-  if (points && capacity < count) return fail(ctx, DDDMR_ERR_CAPACITY, "get_lidar_sweep_segmented: capacity %zu < %zu", capacity, count);
-  *n = count;
-  std::vector<float4> pt;
-  std::vector<uint32_t> cr;
-  std::vector<int32_t> ring(2 * V);
-  if (points && count) {
-    pt.resize(count);
-    cr.resize(count);
-    HIPCHK(ctx, hipMemcpyAsync(pt.data(), lf.seg_pt[b], count * sizeof(float4), hipMemcpyDeviceToHost, ctx->copy_stream));
-    HIPCHK(ctx, hipMemcpyAsync(cr.data(), lf.seg_cr[b], count * 4, hipMemcpyDeviceToHost, ctx->copy_stream));
-  }
-  if (start_ring_index || end_ring_index)
-    HIPCHK(ctx, hipMemcpyAsync(ring.data(), lf.ring[b], 2 * V * 4, hipMemcpyDeviceToHost, ctx->copy_stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-  for (size_t i = 0; i < pt.size(); ++i) {
-    if (xyz) { xyz[3 * i] = pt[i].x; xyz[3 * i + 1] = pt[i].y; xyz[3 * i + 2] = pt[i].z; }
-    if (range) range[i] = pt[i].w;
-    if (col_ind) col_ind[i] = (int32_t)(cr[i] & 0xFFFFu);
-    if (ground_flag) ground_flag[i] = (uint8_t)(cr[i] >> 31);
-  }
-  for (size_t r = 0; r < V; ++r) {                     // before the first sweep: the indices of an empty cloud
-    const bool have = lf.have_sweep;
-    if (start_ring_index) start_ring_index[r] = have ? ring[r] : 4;
-    if (end_ring_index) end_ring_index[r] = have ? ring[V + r] : -6;
-  }
-  return DDDMR_OK;
-}
-
-int dddmr_rollout_get_lidar_sweep_features(dddmr_rollout_ctx* ctx, int32_t source_id, int which, float* xyzr_out, uint32_t* seg_index_out,
-                                           size_t capacity, size_t* n_points) {
-  if (!ctx || !n_points) return DDDMR_ERR_BAD_ARG;
-  if (which < 0 || which > 2) return fail(ctx, DDDMR_ERR_BAD_ARG, "get_lidar_sweep_features: which %d (0 sharp, 1 less sharp, 2 flat)", which);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  LidarSweep* sw = nullptr;
-  const int rc = sweep_features_of(ctx, source_id, "get_lidar_sweep_features", &sw);
-  if (rc != DDDMR_OK) return rc;
-  const LidarFeatures& lf = *sw->features;
-  const int b = sw->cur;
-  const size_t count = lf.n_feat[b][which], off = feat_offset(sw->p.V, which);
-  if ((xyzr_out || seg_index_out) && capacity < count)
-    return fail(ctx, DDDMR_ERR_CAPACITY, "get_lidar_sweep_features: capacity %zu < %zu", capacity, count);
-  *n_points = count;
-  if (count && xyzr_out) HIPCHK(ctx, hipMemcpyAsync(xyzr_out, lf.feat[b] + off, count * sizeof(float4), hipMemcpyDeviceToHost, ctx->copy_stream));
-  if (count && seg_index_out) HIPCHK(ctx, hipMemcpyAsync(seg_index_out, lf.feat_idx[b] + off, count * 4, hipMemcpyDeviceToHost, ctx->copy_stream));
-  if (count && (xyzr_out || seg_index_out)) HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-  return DDDMR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Depth camera frustums, point tests and selfClear's clearing verdicts (depth_clear.hip.h)
-// ---------------------------------------------------------------------------
-int dddmr_rollout_set_depth_frustum(dddmr_rollout_ctx* ctx, int32_t source_id, const dddmr_depth_frustum_config* cfg,
-                                    const double T_gbl_sensor[7]) {
-  if (!ctx) return DDDMR_ERR_BAD_ARG;
-  if (!cfg || !T_gbl_sensor || source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_frustum: source %d (at most %d sensors) / null argument", source_id, dddmr_rollout_ctx::kMaxSources);
-  const double kPi = 3.14159265358979323846;
-  if (!(cfg->FOV_W > 0.0 && cfg->FOV_W < kPi) || !(cfg->FOV_V > 0.0 && cfg->FOV_V < kPi) || !(cfg->obstacle_min_range > 0.0) ||
-      !(cfg->obstacle_max_range > cfg->obstacle_min_range) || !std::isfinite(cfg->obstacle_max_range))
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_frustum: FOV %g x %g rad, range %g .. %g m", cfg->FOV_W, cfg->FOV_V, cfg->obstacle_min_range,
-                cfg->obstacle_max_range);
-  for (int i = 0; i < 7; ++i)
-    if (!std::isfinite(T_gbl_sensor[i])) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_frustum: non-finite transform");
-  std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  if (!ctx->depth[source_id]) return fail(ctx, DDDMR_ERR_STATE, "set_depth_frustum: source %d is not a depth camera source", source_id);
-  double R[9];
-  quat_to_rot(T_gbl_sensor, R);
-  frustum_build(ctx->frustum[source_id], cfg->FOV_W, cfg->FOV_V, cfg->obstacle_min_range, cfg->obstacle_max_range, R, T_gbl_sensor);
-  ctx->has_frustum[source_id] = true;
-  return DDDMR_OK;
-}
-
-int dddmr_rollout_get_depth_frustum(dddmr_rollout_ctx* ctx, int32_t source_id, float vertices[8][3], float normals[6][3],
-                                    float planes[6][4], float origin[3]) {
-  if (!ctx) return DDDMR_ERR_BAD_ARG;
-  if (source_id < 0 || source_id >= dddmr_rollout_ctx::kMaxSources)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "get_depth_frustum: source %d (at most %d sensors)", source_id, dddmr_rollout_ctx::kMaxSources);
-  std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  if (!ctx->depth[source_id] || !ctx->has_frustum[source_id])
-    return fail(ctx, DDDMR_ERR_STATE, "get_depth_frustum: source %d has no frustum", source_id);
-  const DcFrustum& F = ctx->frustum[source_id];
-  if (vertices) std::memcpy(vertices, F.vtx, sizeof(F.vtx));
-  if (normals) std::memcpy(normals, F.nrm, sizeof(F.nrm));
-  if (planes) std::memcpy(planes, F.pl, sizeof(F.pl));
-  if (origin)
-    for (int a = 0; a < 3; ++a) origin[a] = (float)F.origin[a];
-  return DDDMR_OK;
-}
-
-// The frustums of all depth sources in source order; every depth source must have one.  producer_mu held.
-static int depth_frustums(dddmr_rollout_ctx* ctx, const char* what, DcFrustums* S) {
-  S->n = 0;
-  for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) {
-    if (!ctx->depth[i]) continue;
-    if (!ctx->has_frustum[i]) return fail(ctx, DDDMR_ERR_STATE, "%s: depth source %d has no frustum yet", what, i);
-    S->f[S->n++] = ctx->frustum[i];
-  }
-  if (S->n == 0) return fail(ctx, DDDMR_ERR_STATE, "%s: the context has no depth camera source", what);
-  return DDDMR_OK;
-}
-
-static int depth_clear_scratch(dddmr_rollout_ctx* ctx, const char* what) {
-  if (ctx->dclear) return DDDMR_OK;
-  auto* d = new DepthClear();
-  if (dc_alloc(*d, ctx->cfg.max_points) != 0) {
-    dc_free(*d);
-    delete d;
-    return fail(ctx, DDDMR_ERR_HIP, "%s: scratch allocation failed", what);
-  }
-  ctx->dclear = d;
-  return DDDMR_OK;
-}
-
-// The grid over the depth sources' observation (n_obs points in all), rebuilt only when a depth source has published
-// since it was last built: the clearing verdicts and selfMark's clusters share it.  producer_mu held.
-static int depth_observation_grid(dddmr_rollout_ctx* ctx, DepthClear& d, size_t n_obs, hipStream_t st, uint32_t* ops) {
-  if (d.built && d.built_epoch == ctx->depth_epoch) return DDDMR_OK;
-  size_t at = 0;
-  for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) {
-    if (!ctx->depth[i] || !ctx->src_n[i]) continue;
-    HIPCHK(ctx, hipMemcpyAsync(d.pts + at, ctx->src_cloud[i], (size_t)ctx->src_n[i] * sizeof(float4), hipMemcpyDeviceToDevice, st));
-    at += ctx->src_n[i];
-    ++*ops;
-  }
-  d.built = false;
-  const int b = dc_build_grid(d, (uint32_t)n_obs, st);
-  if (b < 0) return fail(ctx, DDDMR_ERR_HIP, "depth observation grid: build failed");
-  *ops += (uint32_t)b;
-  d.built = true;
-  d.built_epoch = ctx->depth_epoch;
-  return DDDMR_OK;
-}
-
-int dddmr_rollout_depth_frustum_test(dddmr_rollout_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes,
-                                     uint8_t* in_frustums_out, uint8_t* attach_out) {
-  if (!ctx) return DDDMR_ERR_BAD_ARG;
-  if (n > 0 && (!xyz || stride_bytes < 12 || stride_bytes % 4 != 0)) return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_frustum_test: bad pointer/stride");
-  if (n > (1u << 28)) return fail(ctx, DDDMR_ERR_CAPACITY, "depth_frustum_test: %zu points", n);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  DcFrustums S;
-  int rc = depth_frustums(ctx, "depth_frustum_test", &S);
-  if (rc != DDDMR_OK) return rc;
-  if (n == 0) return DDDMR_OK;
-  if ((rc = depth_clear_scratch(ctx, "depth_frustum_test")) != DDDMR_OK) return rc;
-  DepthClear& d = *ctx->dclear;
-  if (dc_reserve(&d.in_host, &d.in_dev, &d.in_cap, n * 12) != 0 || dc_reserve(&d.out_host, &d.out_dev, &d.out_cap, n) != 0)
-    return fail(ctx, DDDMR_ERR_HIP, "depth_frustum_test: staging for %zu points", n);
-  float* st = static_cast<float*>(d.in_host);
-  if (stride_bytes == 12) {
-    std::memcpy(st, xyz, n * 12);
-  } else {
-    const size_t sf = stride_bytes / 4;
-    for (size_t i = 0; i < n; ++i) {
-      st[3 * i + 0] = xyz[i * sf + 0];
-      st[3 * i + 1] = xyz[i * sf + 1];
-      st[3 * i + 2] = xyz[i * sf + 2];
-    }
-  }
-  hipLaunchKernelGGL(k_dc_frustum_test, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->copy_stream, S,
-                     static_cast<const float*>(d.in_dev), (uint32_t)n, static_cast<uint8_t*>(d.out_dev));
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-  const uint8_t* o = static_cast<const uint8_t*>(d.out_host);
-  for (size_t i = 0; i < n; ++i) {
-    if (in_frustums_out) in_frustums_out[i] = o[i] & 1u;
-    if (attach_out) attach_out[i] = (o[i] >> 1) & 1u;
-  }
-  return DDDMR_OK;
-}
-
-int dddmr_rollout_depth_clear_verdicts(dddmr_rollout_ctx* ctx, double xy_resolution, double height_resolution,
-                                       const int32_t* voxel_xyz, const uint32_t* offsets, const float* cluster_xyz, size_t m,
-                                       uint8_t* verdict_out, uint32_t* engaged_out) {
-  if (!ctx) return DDDMR_ERR_BAD_ARG;
-  if (!(xy_resolution > 0.0) || !(height_resolution > 0.0) || !std::isfinite(xy_resolution) || !std::isfinite(height_resolution))
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_clear_verdicts: resolutions %g / %g", xy_resolution, height_resolution);
-  if (m > 0 && (!voxel_xyz || !offsets || !verdict_out)) return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_clear_verdicts: null argument");
-  if (m > (1u << 24)) return fail(ctx, DDDMR_ERR_CAPACITY, "depth_clear_verdicts: %zu markings", m);
-  if (m > 0) {
-    if (offsets[0] != 0) return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_clear_verdicts: offsets[0] = %u", offsets[0]);
-    for (size_t i = 0; i < m; ++i)
-      if (offsets[i + 1] < offsets[i]) return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_clear_verdicts: offsets decrease at marking %zu", i);
-    if (offsets[m] > 0 && !cluster_xyz) return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_clear_verdicts: null cluster points");
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  DcFrustums S;
-  int rc = depth_frustums(ctx, "depth_clear_verdicts", &S);
-  if (rc != DDDMR_OK) return rc;
-  if (m == 0) return DDDMR_OK;
-  if ((rc = depth_clear_scratch(ctx, "depth_clear_verdicts")) != DDDMR_OK) return rc;
-  DepthClear& d = *ctx->dclear;
-  hipStream_t st = ctx->copy_stream;      // the stream the depth feeds ran on: their frames are complete before this work
-  uint32_t ops = 0;
-  // aggregatePointCloudFromObservations: the depth sources' alive frames, in source order (lidar sources stay out)
-  size_t n_obs = 0;
-  for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i)
-    if (ctx->depth[i]) n_obs += ctx->src_n[i];
-  const bool observation_clear = !(n_obs > 5);       // depth_camera_layer.cpp:258-264
-  if (!observation_clear && (rc = depth_observation_grid(ctx, d, n_obs, st, &ops)) != DDDMR_OK) return rc;
-  const size_t total = offsets[m];
-  const size_t vox_bytes = m * 3 * sizeof(int32_t), off_bytes = (m + 1) * sizeof(uint32_t);
-  if (dc_reserve(&d.in_host, &d.in_dev, &d.in_cap, vox_bytes + off_bytes + total * 12) != 0 ||
-      dc_reserve(&d.out_host, &d.out_dev, &d.out_cap, m * sizeof(uint2)) != 0)
-    return fail(ctx, DDDMR_ERR_HIP, "depth_clear_verdicts: staging for %zu markings, %zu cluster points", m, total);
-  char* in = static_cast<char*>(d.in_host);
-  std::memcpy(in, voxel_xyz, vox_bytes);
-  std::memcpy(in + vox_bytes, offsets, off_bytes);
-  if (total) std::memcpy(in + vox_bytes + off_bytes, cluster_xyz, total * 12);
-  const char* dev = static_cast<const char*>(d.in_dev);
-  DcVerdictParams k;
-  k.res = xy_resolution;
-  k.hres = height_resolution;
-  k.m = (uint32_t)m;
-  k.observation_clear = observation_clear ? 1u : 0u;
-  hipLaunchKernelGGL(k_dc_verdicts, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, k, S, d.hdr, reinterpret_cast<const int32_t*>(dev),
-                     reinterpret_cast<const uint32_t*>(dev + vox_bytes), reinterpret_cast<const float*>(dev + vox_bytes + off_bytes),
-                     static_cast<uint2*>(d.out_dev));
-  ++ops;
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipStreamSynchronize(st));           // the call's one host wait
-  d.launches_last = ops;
-  const uint2* o = static_cast<const uint2*>(d.out_host);
-  for (size_t i = 0; i < m; ++i)
-    if (o[i].x & kDcEmptyCluster)
-      return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_clear_verdicts: marking %zu reaches the engagement ratio with an empty cluster", i);
-  for (size_t i = 0; i < m; ++i) {
-    verdict_out[i] = (uint8_t)o[i].x;
-    if (engaged_out) engaged_out[i] = o[i].y;
-  }
-  return DDDMR_OK;
-}
-
-int dddmr_rollout_depth_clear_launches(dddmr_rollout_ctx* ctx, uint32_t* launches_last_call) {
-  if (!ctx || !launches_last_call) return DDDMR_ERR_BAD_ARG;
-  std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  *launches_last_call = ctx->dclear ? ctx->dclear->launches_last : 0u;
+  publish_cloud(ctx, back, (uint32_t)n_points, foreign_layout());
   return DDDMR_OK;
 }
 
@@ -2202,6 +1301,7 @@ int dddmr_rollout_get_best_cuboids(dddmr_rollout_ctx* ctx, float* vertices_out, 
 
 }  // extern "C"
 
+#include "sensor_sources.hip.h"
 #include "marking_host.hip.h"
 #include "depth_mark.hip.h"
 #include "depth_layer.hip.h"

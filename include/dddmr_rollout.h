@@ -245,7 +245,11 @@ int dddmr_rollout_set_stitcher(dddmr_rollout_ctx* ctx, int32_t stitcher_num);
    becomes the concatenation, in source order, of every source's LATEST observation (a source that has
    not reported yet contributes nothing).  *n_source_points / *n_aggregate_points (either may be NULL)
    receive the two sizes.  The first call with a source id switches the context to this mode; plain
-   dddmr_rollout_set_scan then means source 0.  The observations together must fit max_points. */
+   dddmr_rollout_set_scan then means source 0.  The observations together must fit max_points: a scan
+   whose observation does not fit beside the other sources' is refused with DDDMR_ERR_CAPACITY, and since
+   the source's one buffer is overwritten by then, that source is left EMPTY and the aggregate is
+   republished from the other sources.  They feed on as before, and the refused source works again as
+   soon as its observation fits. */
 #define DDDMR_MAX_SOURCES 4
 int dddmr_rollout_set_scan_source(dddmr_rollout_ctx* ctx, int32_t source_id, const float* xyz,
                                   size_t n_points, size_t stride_bytes, const double T_base_sensor[7],

@@ -238,5 +238,23 @@ def test_two_sensors_concatenate_on_the_device_like_aggregate_observations():
     if len(ref[0]) + len(ref[1]) > cap:
         with LocalPlanner([th], max_points=cap) as lp:
             lp.set_scan_source(0, scans[0], mounts[0], tgb, 8.0, 1.8)
-            with pytest.raises(Exception):
+            with pytest.raises(Exception) as e:
                 lp.set_scan_source(1, scans[1], mounts[1], tgb, 8.0, 1.8)
+            # The refused sensor's one buffer is overwritten, so it is left empty and the aggregate republished without it:
+            # the context is not wedged.  The other sensor feeds on, and the refused one works again once it fits.
+            assert e.value.code == K.ERR_CAPACITY
+            _match(lp.get_cloud()[:, :3], ref[0])
+            assert lp.set_scan_source(0, scans[2], mounts[0], tgb, 8.0, 1.8) == (len(ref[2]), len(ref[2]))
+            _match(lp.get_cloud()[:, :3], ref[2])
+            assert len(ref[2]) + 1 <= cap                                             # (from the oracle alone, like the guard above)
+            one = next(scans[1][i:i + 1] for i in range(len(scans[1])) if _survives_alone(scans[1][i:i + 1], mounts[1], tgb, ref[1]))
+            assert lp.set_scan_source(1, one, mounts[1], tgb, 8.0, 1.8) == (1, len(ref[2]) + 1)
+            got = lp.get_cloud()[:, :3]
+            _match(got[:-1], ref[2])
+            _match(got[-1:], oracle.feed(one, mounts[1], tgb, 8.0, 1.8))
+
+
+def _survives_alone(row, mount, tgb, ref_xyz):
+    """a one-point scan that the feed keeps, as the point of ref_xyz it was there (alone in its voxel)"""
+    one = oracle.feed(row, mount, tgb, 8.0, 1.8)
+    return len(one) == 1 and np.abs(ref_xyz[:, :3] - one[0, :3]).max(axis=1).min() <= 1e-5

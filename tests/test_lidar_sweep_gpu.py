@@ -275,6 +275,26 @@ def test_error_paths_leave_the_context_usable():
         assert_stage_one(sweep(lp, 0, c, raw), ref, "after re-configuring")
 
 
+def test_reconfiguring_a_sweep_source_releases_all_of_it():
+    """Configuring a configured sweep source tears the old one down as a whole: its segment leaves the aggregate, its
+    features are off and its range image reads as never projected."""
+    c, raw, ref = Cs.case("4x8-g1")
+    with planner() as lp:
+        configure(lp, 0, c)
+        lp.set_lidar_sweep_features(0, 0.1, 0.1)
+        n_seg, n_src, n_all = lp.set_lidar_sweep(0, raw, TBS, TGB, WINDOW, HEIGHT)
+        assert n_seg == len(ref["cloud"]) > 0 and n_src == n_all == len(lp.get_cloud()) > 0
+        assert lp.get_lidar_sweep_features(0, 1) is not None                                  # on, and answering
+        assert not (lp.get_lidar_sweep_image(0, c.V, c.H)[0] == R.FLT_MAX).all()
+        configure(lp, 0, c)
+        assert len(lp.get_cloud()) == 0 and len(lp.get_lidar_sweep_cloud(0)) == 0
+        with pytest.raises(RolloutError) as e:
+            lp.get_lidar_sweep_features(0, 1)
+        assert e.value.code == K.ERR_STATE and "features of source 0 are off" in str(e.value)
+        rng, lab, gnd = lp.get_lidar_sweep_image(0, c.V, c.H)
+        assert (rng == R.FLT_MAX).all() and (lab == -1).all() and (gnd == 0).all()
+
+
 def test_an_aggregate_above_max_points_refuses_the_sweep_and_changes_nothing():
     c, raw, ref = Cs.case("16x64-g7-m0.2")
     small = raw[: len(raw) // 4]
