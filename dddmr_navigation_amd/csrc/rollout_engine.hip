@@ -89,6 +89,7 @@ struct dddmr_rollout_ctx {
   float* axes_dev = nullptr;
   float4* samples_dev = nullptr;
   float4* plan_dev = nullptr;
+  float* plan_pairs_dev = nullptr;     // the same poses as pair records, padded: phase P's scalar walk (plan_pack_pairs)
   double* costs = nullptr;
   int32_t* steps = nullptr;
   float4* samples_out = nullptr;
@@ -331,7 +332,7 @@ void dddmr_rollout_destroy(dddmr_rollout_ctx* ctx) {
     if (ctx->cloud_ready[i]) (void)hipEventDestroy(ctx->cloud_ready[i]);
   }
   void* dev[] = {ctx->row_tab, ctx->pt_slot, ctx->sorted, ctx->cell_count, ctx->cell_start, ctx->axes_dev,
-                 ctx->samples_dev, ctx->plan_dev, ctx->costs, ctx->steps, ctx->samples_out,
+                 ctx->samples_dev, ctx->plan_dev, ctx->plan_pairs_dev, ctx->costs, ctx->steps, ctx->samples_out,
                  ctx->best_key, ctx->overflow, ctx->tickets, ctx->poses_dev, ctx->traj_load, ctx->assign, ctx->blocked_plan, ctx->blocked_flags};
   for (void* p : dev)
     if (p) (void)hipFree(p);
@@ -406,7 +407,7 @@ int dddmr_rollout_create(const dddmr_rollout_config* cfg, dddmr_rollout_ctx** ou
     HIPCHK(ctx, hipEventCreate(&ctx->evs0));
     HIPCHK(ctx, hipEventCreate(&ctx->evs1));
     const size_t P = cfg->max_points, N = cfg->max_trajectories;
-    // whole trips of phase P's scalar-load walk plus one chunk of slack for its last request ahead
+    // the pair records: whole trips of phase P's scalar-load walk plus one chunk of slack for its last request ahead
     const size_t plan_cap = plan_padded_poses(std::max<uint32_t>(cfg->max_plan_poses, 1));
     for (int i = 0; i < kCloudBufs; ++i) {
       HIPCHK(ctx, hipMalloc(&ctx->cloud_dev[i], P * sizeof(float4)));
@@ -421,7 +422,8 @@ int dddmr_rollout_create(const dddmr_rollout_config* cfg, dddmr_rollout_ctx** ou
     HIPCHK(ctx, hipMalloc(&ctx->row_tab, (size_t)kTabCap * sizeof(uint32_t)));
     HIPCHK(ctx, hipMalloc(&ctx->axes_dev, 3 * kMaxAxis * sizeof(float)));
     HIPCHK(ctx, hipMalloc(&ctx->samples_dev, N * sizeof(float4)));
-    HIPCHK(ctx, hipMalloc(&ctx->plan_dev, plan_cap * sizeof(float4)));
+    HIPCHK(ctx, hipMalloc(&ctx->plan_dev, std::max<size_t>(cfg->max_plan_poses, 1) * sizeof(float4)));
+    HIPCHK(ctx, hipMalloc(&ctx->plan_pairs_dev, plan_cap * kPlanPoseWords * sizeof(float)));
     HIPCHK(ctx, hipMalloc(&ctx->costs, N * sizeof(double)));
     HIPCHK(ctx, hipMalloc(&ctx->steps, N * sizeof(int32_t)));
     HIPCHK(ctx, hipMalloc(&ctx->samples_out, N * sizeof(float4)));
@@ -638,15 +640,17 @@ int dddmr_rollout_set_prune_plan(dddmr_rollout_ctx* ctx, const double* poses, si
   if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "set_prune_plan while a tick_begin is pending");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   // ModelSharedData::updateData: positions as float PointXYZI (model_shared_data.h:83-91)
-  // Behind the poses: copies of the last one up to plan_padded_poses() (k_score's phase P reads whole chunks, and a
-  // duplicate cannot change a minimum).  Written on every call, so a shorter plan after a longer one is padded too.
-  const size_t n_padded = plan_padded_poses(n_poses);
-  std::vector<float4> xyz(n_padded);
-  for (size_t i = 0; i < n_poses; ++i)
-    xyz[i] = make_float4((float)poses[7 * i + 0], (float)poses[7 * i + 1], (float)poses[7 * i + 2], 0.f);
-  for (size_t i = n_poses; i < n_padded; ++i) xyz[i] = n_poses ? xyz[n_poses - 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+  // For phase P's scalar walk the same positions go up a second time as pair records, padded with copies of the last
+  // pose to whole loop trips (plan_pack_pairs).  Packed and written on every call, never per tick, so a shorter plan
+  // after a longer one is padded afresh.
   if (n_poses) {
-    HIPCHK(ctx, hipMemcpy(ctx->plan_dev, xyz.data(), n_padded * sizeof(float4), hipMemcpyHostToDevice));
+    std::vector<float4> xyz(n_poses);
+    for (size_t i = 0; i < n_poses; ++i)
+      xyz[i] = make_float4((float)poses[7 * i + 0], (float)poses[7 * i + 1], (float)poses[7 * i + 2], 0.f);
+    std::vector<float> pairs(plan_padded_poses(n_poses) * kPlanPoseWords);
+    plan_pack_pairs(xyz.data(), n_poses, pairs.data());
+    HIPCHK(ctx, hipMemcpy(ctx->plan_dev, xyz.data(), xyz.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(ctx->plan_pairs_dev, pairs.data(), pairs.size() * sizeof(float), hipMemcpyHostToDevice));
     std::memcpy(ctx->plan_last, poses + 7 * (n_poses - 1), 7 * sizeof(double));
   }
   ctx->plan_m = (uint32_t)n_poses;
@@ -781,7 +785,7 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
   hipLaunchKernelGGL((k_score<T, L, P>), dim3(wgs), dim3(T), lds, ctx->stream, k, ctx->traj_info, ctx->st_sc,     \
                      ctx->st_xy, ctx->plan_dev, ctx->cell_start, ctx->sorted, ctx->costs, ctx->steps,             \
                      ctx->samples_out, ctx->best_key, ctx->overflow, ctx->tickets + 1, score_result, ctx->assign, \
-                     ctx->traj_load, score_words, ctx->row_tab)
+                     ctx->traj_load, score_words, ctx->row_tab, ctx->plan_pairs_dev)
     if (p.thr == 512) { if (p.lean) DDDMR_LAUNCH_SCORE(512, true); else DDDMR_LAUNCH_SCORE(512, false); }
     else              { if (p.lean) DDDMR_LAUNCH_SCORE(256, true); else DDDMR_LAUNCH_SCORE(256, false); }
 #undef DDDMR_LAUNCH_SCORE

@@ -952,36 +952,64 @@ __device__ __forceinline__ f2 l2_simple2(f2 ax, f2 ay, f2 az, float bx, float by
 // usable wait, so the one wait of a trip falls AFTER its arithmetic.  The compiler does not count loads issued from
 // asm statements, hence the loads and the waits (nothing else) are asm, and every wait names the registers it
 // retires as read-write operands, which keeps their consumers below it and the registers allocated until then.
-// kPlanChunk poses are one request; a trip of the loop is two chunks (two register sets, no copies), so the device
-// copy of the plan is padded with copies of its last pose up to a multiple of kPlanTrip (a duplicate cannot change a
-// minimum) and has kPlanChunk more poses of slack behind that for the last request ahead (plan_padded_poses()).
-constexpr int kPlanChunk = 4;      // (8 poses a chunk: 51 instead of 18 SGPR spills in k_score<512,true,false>)
+// The walk reads a copy of the plan of its own, stored as pair records: x0 x1 y0 y1 z0 z1 for poses (2i, 2i+1), three
+// words a pose.  v_pk_add_f32 takes (x0, x1) from an aligned SGPR pair, so every packed operand is a register pair
+// exactly as loaded (the float4 plan cost eight s_mov_b32 per four poses to pair them up, and a quarter of the
+// registers held its unused w).
+// kPlanChunk poses are one request; a trip of the loop is two chunks (two register sets, no copies), so the pair
+// records are padded with copies of the last pose up to a multiple of kPlanTrip (a duplicate cannot change a
+// minimum) and have kPlanChunk more poses of slack behind that for the last request ahead (plan_padded_poses()).
+constexpr int kPlanChunk = 4;      // 12 SGPRs a chunk, 24 for the two of a trip (6 and 8 poses fit too and measured no
+                                   // faster in the tick: DESIGN.md section 6, profiles/r18_score_plan_pairs.json)
 constexpr int kPlanTrip = 2 * kPlanChunk;
+constexpr int kPlanPoseWords = 3;  // floats per pose in the pair records
+static_assert(kPlanChunk == 4, "plan_request / plan_chunk_min are written for 8 + 4 words a chunk");
 __host__ __device__ constexpr size_t plan_padded_poses(size_t m) {
   return (m + kPlanTrip - 1) / kPlanTrip * kPlanTrip + kPlanChunk;
 }
-typedef float f16v __attribute__((ext_vector_type(16)));    // four float4 poses in 16 consecutive SGPRs
+// The pair records of an m-pose plan: plan_padded_poses(m) poses, kPlanPoseWords floats each, into out.  Poses past
+// the last are copies of the last one (zeros for an empty plan, which nobody reads).  Host arithmetic alone.
+inline void plan_pack_pairs(const float4* xyz, size_t m, float* out) {
+  const size_t n = plan_padded_poses(m);
+  for (size_t i = 0; i < n; ++i) {
+    const float4 p = m ? xyz[i < m ? i : m - 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float* r = out + 2 * kPlanPoseWords * (i / 2) + (i & 1);
+    r[0] = p.x;
+    r[2] = p.y;
+    r[4] = p.z;
+  }
+}
+typedef float f8v __attribute__((ext_vector_type(8)));
+typedef float f4v __attribute__((ext_vector_type(4)));
+struct PlanChunk {     // two pair records in 12 SGPRs: words 0..7 and 8..11
+  f8v a;
+  f4v b;
+};
 // issue only: the registers hold nothing until plan_wait() has passed them through
-__device__ __forceinline__ f16v plan_request(const float4* __restrict__ plan_xyz, uint32_t byte_ofs) {
-  f16v c;
-  asm volatile("s_load_dwordx16 %0, %1, %2" : "=s"(c) : "s"(plan_xyz), "s"(byte_ofs));
+__device__ __forceinline__ PlanChunk plan_request(const float* __restrict__ plan_pairs, uint32_t byte_ofs) {
+  PlanChunk c;
+  asm volatile("s_load_dwordx8 %0, %2, %3\n\ts_load_dwordx4 %1, %2, %3 offset:32"
+               : "=&s"(c.a), "=&s"(c.b) : "s"(plan_pairs), "s"(byte_ofs));
   return c;
 }
 // the one wait of a trip.  The empty statement in front of it keeps the arithmetic `best` depends on above the wait
 // (volatile statements keep their order); it is a statement of its own because a VGPR operand on the wait itself
 // makes the compiler treat all its results, the chunk included, as per-lane values.
-__device__ __forceinline__ void plan_wait(f16v& c, float& best) {
+__device__ __forceinline__ void plan_wait(PlanChunk& c, float& best) {
   asm volatile("" : "+v"(best));
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(c));
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(c.a), "+s"(c.b));
 }
 // no instruction, placed behind a request: the arithmetic on the current chunk reads it through this statement and
 // so stays below the request (left alone, the compiler issued the request after most of the trip's arithmetic), and
 // the chunk carried round the loop stays in scalar registers (it was moved to VGPRs at the loop's end otherwise).
-__device__ __forceinline__ void plan_current(f16v& c) { asm volatile("" : "+s"(c)); }
-// poses (2i, 2i+1) share the packed lanes; four poses per step exactly as the LDS route pairs them
-__device__ __forceinline__ float plan_chunk_min(float best, const f16v q, float px, float py, float pz) {
-  const f2 da = l2_simple2(f2{q[0], q[4]}, f2{q[1], q[5]}, f2{q[2], q[6]}, px, py, pz);
-  const f2 db = l2_simple2(f2{q[8], q[12]}, f2{q[9], q[13]}, f2{q[10], q[14]}, px, py, pz);
+__device__ __forceinline__ void plan_current(PlanChunk& c) { asm volatile("" : "+s"(c.a), "+s"(c.b)); }
+// poses (2i, 2i+1) share the packed lanes, four poses per step exactly as the LDS route pairs them; record i is words
+// 6i .. 6i+5, and record 1 lies across the two tuples (x in a, y and z in b): every pair starts at an even register
+__device__ __forceinline__ float plan_chunk_min(float best, const PlanChunk& q, float px, float py, float pz) {
+  const f8v a = q.a;
+  const f4v b = q.b;
+  const f2 da = l2_simple2(f2{a[0], a[1]}, f2{a[2], a[3]}, f2{a[4], a[5]}, px, py, pz);
+  const f2 db = l2_simple2(f2{a[6], a[7]}, f2{b[0], b[1]}, f2{b[2], b[3]}, px, py, pz);
   return fminf(fminf(best, fminf(da.x, da.y)), fminf(db.x, db.y));
 }
 
@@ -1193,7 +1221,8 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
     const Pt3* __restrict__ sorted, double* __restrict__ costs, int32_t* __restrict__ steps_out,
     float4* __restrict__ samples_out, int64_t* __restrict__ best_key, uint32_t* __restrict__ overflow,
     uint32_t* __restrict__ ticket, DevResult* __restrict__ result, const uint32_t* __restrict__ assign,
-    uint32_t* __restrict__ traj_load, int64_t* __restrict__ words_out, const uint32_t* __restrict__ row_tab) {
+    uint32_t* __restrict__ traj_load, int64_t* __restrict__ words_out, const uint32_t* __restrict__ row_tab,
+    const float* __restrict__ plan_pairs) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int tile = k.tile;
   const int S1 = k.max_steps + 1;
@@ -1434,6 +1463,8 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
       reinterpret_cast<int*>(r)[16] = (cy0 & 0xFFFF) | (cy1 << 16);
       // A point inside the (convex) box is no farther from the pose than the farthest
       // vertex, so with all vertices well inside the 1 m ball the radius test is moot.
+      // (a lean launch has rec_pose == 0, so the bit is set in all its records: the walk's use_radius is a compile-time
+      // false there and must stay in step with this line)
       reinterpret_cast<int*>(r)[17] = j | ((vmax2 < 0.99f || !rec_pose) ? 0x10000 : 0);
       if (rec_pose) { r[18] = px; r[19] = py; r[20] = pz; }
       if (need_mm) {
@@ -1582,7 +1613,7 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
       const float* rq = rec + (size_t)q * rec_words;
       const int jw = reinterpret_cast<const int*>(rq)[17];
       const int j = jw & 0xFFFF;
-      const bool use_radius = (jw & 0x10000) == 0;
+      const bool use_radius = !kLean && (jw & 0x10000) == 0;   // (lean: rec_pose is 0 and D1 set the bit in every record)
       const bool hb = !need_box || head[j].hit_box != 0;
       const bool hm = !need_mm || head[j].hit_mm != 0;
       if (hb && hm) return;                       // trajectory already decided
@@ -1721,20 +1752,20 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
         // through the scalar unit (uniform index into the kernel argument -> s_load, operands in SGPRs) instead of
         // 64 lanes reading one LDS address -- broadcast 16-byte LDS reads were what bound this phase.
         // The next chunk is requested before the arithmetic on the current one (plan_request / plan_wait above); the
-        // device plan is padded to whole trips with copies of its last pose, so there is no remainder and no mask.
+        // pair records are padded to whole trips with copies of the last pose, so there is no remainder and no mask.
         // The walk sits under wave-uniform conditions only (a wave with one valid lane walks with all its lanes, the
         // others' minima are never stored): under the per-lane `valid` the compiler carried the chunk in VGPRs.
         if (k.m > 0 && __ballot(valid) != 0ull) {
-          constexpr uint32_t kChunkBytes = 16u * kPlanChunk;
-          const uint32_t end = 16u * (uint32_t)k.m;
-          f16v ca = plan_request(plan_xyz, 0u);
+          constexpr uint32_t kPoseBytes = 4u * kPlanPoseWords, kChunkBytes = kPoseBytes * kPlanChunk;
+          const uint32_t end = kPoseBytes * (uint32_t)k.m;
+          PlanChunk ca = plan_request(plan_pairs, 0u);
           plan_wait(ca, best);
           for (uint32_t o = 0; o < end; o += 2u * kChunkBytes) {
-            f16v cb = plan_request(plan_xyz, o + kChunkBytes);
+            PlanChunk cb = plan_request(plan_pairs, o + kChunkBytes);
             plan_current(ca);
             best = plan_chunk_min(best, ca, px, py, pz);
             plan_wait(cb, best);
-            ca = plan_request(plan_xyz, o + 2u * kChunkBytes);     // (the last one reads the slack)
+            ca = plan_request(plan_pairs, o + 2u * kChunkBytes);   // (the last one reads the slack)
             plan_current(cb);
             best = plan_chunk_min(best, cb, px, py, pz);
             plan_wait(ca, best);

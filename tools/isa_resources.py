@@ -20,7 +20,7 @@ for blk in re.split(r"\n\s*- \.agpr_count:", text)[1:]:
     if short.startswith("rocprim") or short.startswith("(anonymous"):
         continue
     get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))
-    res[short] = {"vgpr": get("vgpr_count"), "sgpr": get("sgpr_count"), "vgpr_spills": get("vgpr_spill_count"),
+    res[short] = {"vgpr": get("vgpr_count"), "sgpr": get("sgpr_count"), "vgpr_spills": get("vgpr_spill_count"), "sgpr_spills": get("sgpr_spill_count"),
                   "scratch_bytes": get("private_segment_fixed_size"), "static_lds_bytes": get("group_segment_fixed_size"),
                   "max_flat_workgroup_size": get("max_flat_workgroup_size")}
 json.dump(res, sys.stdout, indent=1, sort_keys=True)
