@@ -91,6 +91,7 @@ struct dddmr_rollout_ctx {
   float4* plan_dev = nullptr;
   float* plan_pairs_dev = nullptr;     // the same poses as pair records, padded: phase P's scalar walk (plan_pack_pairs)
   double* costs = nullptr;
+  TrajPartial* partial = nullptr;      // per local trajectory: what k_score hands k_finalize on a multi-round shard
   int32_t* steps = nullptr;
   float4* samples_out = nullptr;
   int64_t* best_key = nullptr;
@@ -332,7 +333,7 @@ void dddmr_rollout_destroy(dddmr_rollout_ctx* ctx) {
     if (ctx->cloud_ready[i]) (void)hipEventDestroy(ctx->cloud_ready[i]);
   }
   void* dev[] = {ctx->row_tab, ctx->pt_slot, ctx->sorted, ctx->cell_count, ctx->cell_start, ctx->axes_dev,
-                 ctx->samples_dev, ctx->plan_dev, ctx->plan_pairs_dev, ctx->costs, ctx->steps, ctx->samples_out,
+                 ctx->samples_dev, ctx->plan_dev, ctx->plan_pairs_dev, ctx->costs, ctx->partial, ctx->steps, ctx->samples_out,
                  ctx->best_key, ctx->overflow, ctx->tickets, ctx->poses_dev, ctx->traj_load, ctx->assign, ctx->blocked_plan, ctx->blocked_flags};
   for (void* p : dev)
     if (p) (void)hipFree(p);
@@ -425,9 +426,11 @@ int dddmr_rollout_create(const dddmr_rollout_config* cfg, dddmr_rollout_ctx** ou
     HIPCHK(ctx, hipMalloc(&ctx->plan_dev, std::max<size_t>(cfg->max_plan_poses, 1) * sizeof(float4)));
     HIPCHK(ctx, hipMalloc(&ctx->plan_pairs_dev, plan_cap * kPlanPoseWords * sizeof(float)));
     HIPCHK(ctx, hipMalloc(&ctx->costs, N * sizeof(double)));
+    HIPCHK(ctx, hipMalloc(&ctx->partial, N * sizeof(TrajPartial)));
     HIPCHK(ctx, hipMalloc(&ctx->steps, N * sizeof(int32_t)));
     HIPCHK(ctx, hipMalloc(&ctx->samples_out, N * sizeof(float4)));
-    // words 0..2: reduced argmin words; from kSlotBase on: four words per k_score workgroup (single-round shards)
+    // words 0..2: unused (the binning launch still resets them); from kSlotBase on: four words per workgroup of the
+    // launch that ends the scoring (k_score on single-round shards, k_finalize on multi-round ones)
     HIPCHK(ctx, hipMalloc(&ctx->best_key, ((size_t)kSlotBase + (size_t)kSlotWords * ctx->cfg.max_trajectories) * sizeof(int64_t)));
     HIPCHK(ctx, hipMalloc(&ctx->overflow, sizeof(uint32_t)));
     HIPCHK(ctx, hipMalloc(&ctx->traj_load, N * sizeof(uint32_t)));
@@ -745,6 +748,7 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
     HIPCHK(ctx, hipMemsetAsync(ctx->costs, 0xFF, (size_t)k.n_local * sizeof(double), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->steps, 0xFF, (size_t)k.n_local * sizeof(int32_t), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->samples_out, 0xFF, (size_t)k.n_local * sizeof(float4), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->partial, 0xFF, (size_t)k.n_local * sizeof(TrajPartial), ctx->stream));
   }
   k.seq = ++ctx->seq;
   if (k.seq == 0) k.seq = ctx->seq = 1;
@@ -785,7 +789,7 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
   hipLaunchKernelGGL((k_score<T, L, P>), dim3(wgs), dim3(T), lds, ctx->stream, k, ctx->traj_info, ctx->st_sc,     \
                      ctx->st_xy, ctx->plan_dev, ctx->cell_start, ctx->sorted, ctx->costs, ctx->steps,             \
                      ctx->samples_out, ctx->best_key, ctx->overflow, ctx->tickets + 1, score_result, ctx->assign, \
-                     ctx->traj_load, score_words, ctx->row_tab, ctx->plan_pairs_dev)
+                     ctx->traj_load, score_words, ctx->row_tab, ctx->plan_pairs_dev, ctx->partial)
     if (p.thr == 512) { if (p.lean) DDDMR_LAUNCH_SCORE(512, true); else DDDMR_LAUNCH_SCORE(512, false); }
     else              { if (p.lean) DDDMR_LAUNCH_SCORE(256, true); else DDDMR_LAUNCH_SCORE(256, false); }
 #undef DDDMR_LAUNCH_SCORE
@@ -794,9 +798,12 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
     hipLaunchKernelGGL(k_empty_result, dim3(1), dim3(64), 0, ctx->stream, k, ctx->cell_start, score_result, score_words);
   }
   if (timed) HIPCHK(ctx, hipEventRecord(ctx->evs1, ctx->stream));
+  // multi-round shards: stacked scoring + exact argmin, one lane per trajectory (the HIP-event score_ms above then
+  // covers k_score without the stacked scoring)
   if (k.n_local > 0 && k.final_kernel)
-    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, ctx->stream, k, ctx->best_key, ctx->costs, ctx->samples_out,
-                       ctx->cell_start, ctx->overflow, score_result, score_words);
+    hipLaunchKernelGGL(k_finalize, dim3((k.n_local + kFinalThreads - 1) / kFinalThreads), dim3(kFinalThreads), 0, ctx->stream, k,
+                       ctx->traj_info, ctx->partial, ctx->costs, ctx->steps, ctx->samples_out, ctx->traj_load, ctx->best_key,
+                       ctx->cell_start, ctx->overflow, ctx->tickets + 1, score_result, score_words);
   if (exchange) {
     // ONE collective per tick, on the tick's stream: ordered after k_score / k_finalize (which wrote this rank's two
     // words of slots_dev) and before k_resolve by stream order alone; no host synchronisation in between.

@@ -7,9 +7,11 @@
 //                  mpc_critics/include/mpc_critics/model_shared_data.h:78-81)
 //   k_bin_scatter: counting-sort scatter -> cell-sorted float4 points
 //   k_score      : fused rollout (trajectory_generators theories) + all critics
-//                  (mpc_critics/models/*.cpp) + packed-key argmin; the last
+//                  (mpc_critics/models/*.cpp) + exact argmin; the last
 //                  workgroup decodes the winner (local_planner.cpp:447-480)
 //                  into host-mapped memory
+//   k_finalize   : shards of several rounds of k_score workgroups only: the
+//                  stacked scoring and the argmin, one lane per trajectory
 //
 // No MFMA anywhere: this is gather / compare work.
 //
@@ -71,9 +73,9 @@ constexpr int kMaxTile = 16;          // trajectories per workgroup (upper bound
 constexpr int kMaxPlan = 512;         // prune-plan poses kept in LDS
 constexpr int kInlineAxes = 192;      // sample-axis floats that travel inside the kernel arguments
 constexpr int64_t kKeyNone = INT64_MAX;
-// best_key[]: words 0..2 are the reduced argmin words of multi-round shards (packed key, cost bits, sampled
-// collision count); from word kSlotBase on, four words per k_score workgroup for single-round shards (see the
-// tail of k_score): cost bits | global index | vx, vy | w, generated << 40, collided << 32
+// best_key[]: words 0..2 are unused (the binning launch still resets them); from word kSlotBase on, four words per
+// workgroup of the launch that ends the scoring -- k_score on single-round shards (see its tail), k_finalize on
+// multi-round ones: cost bits | global index | vx, vy | w and the collision counts (pack_slot_word3)
 constexpr int kSlotBase = 8;
 constexpr int kSlotWords = 4;
 constexpr double kMaxAcceptedCost = 9999999.0;   // local_planner.cpp:452
@@ -135,7 +137,7 @@ struct DevTick {
   int roll_blocks;   // the rollout workgroups and (use_assign) one assignment workgroup
   int box_fast;      // the cuboid is a body-frame box in the reference's vertex order (host-checked)
   int rec_pose;      // OBB records carry the pose (some pair may need the 1 m radius test, or min-max critic)
-  int final_kernel;  // 1: the winner is decoded by k_finalize after k_score (multi-round shards), 0: by k_score's last workgroup
+  int final_kernel;  // 1: k_finalize scores the stack and decodes the winner after k_score (multi-round shards), 0: k_score and its last workgroup do
   int probe;         // 1: the collision walk starts with a probe round (pays when most trajectories collide)
   uint32_t seq;      // tick sequence number echoed into DevResult::seq
   float axes_inl[kInlineAxes];
@@ -172,8 +174,8 @@ __host__ __device__ inline int64_t pack_key(double cost, uint32_t gidx) {
   const uint64_t idx_mask = (1ull << kKeyIndexBits) - 1;
   return (int64_t)((c.u & ~idx_mask) | (idx_mask - (uint64_t)gidx));
 }
-// The full bit pattern of an acceptable cost (non-negative doubles order like their bits):
-// reduced beside the packed key so that the winner is exact, see k_score's decode.
+// The full bit pattern of an acceptable cost (non-negative doubles order like their bits): what the argmin
+// compares, as signed 64-bit words, so that the winner is exact (pack_key() is only the format of DevResult::key).
 __host__ __device__ inline int64_t cost_bits(double cost) {
   if (!(cost >= 0.0 && cost <= kMaxAcceptedCost)) return kKeyNone;
   union { double d; int64_t i; } c;
@@ -185,6 +187,17 @@ __host__ __device__ inline int32_t key_index(int64_t key) {
   const uint64_t idx_mask = (1ull << kKeyIndexBits) - 1;
   return (int32_t)(idx_mask - ((uint64_t)key & idx_mask));
 }
+
+// Slot word 3: the winner's w in the low half, then how many trajectories of the workgroup the collision critics
+// rejected and how many it generated, 16 bits each (a k_score tile has <= kMaxTile trajectories, a k_finalize
+// workgroup 256).  Both slot writers and reduce_slots go through these.
+__host__ __device__ inline unsigned long long pack_slot_word3(uint32_t w_bits, uint32_t collided, uint32_t generated) {
+  return (unsigned long long)w_bits | ((unsigned long long)(collided & 0xFFFFu) << 32) |
+         ((unsigned long long)(generated & 0xFFFFu) << 48);
+}
+__host__ __device__ inline uint32_t slot_w_bits(unsigned long long w3) { return (uint32_t)w3; }
+__host__ __device__ inline uint32_t slot_collided(unsigned long long w3) { return (uint32_t)(w3 >> 32) & 0xFFFFu; }
+__host__ __device__ inline uint32_t slot_generated(unsigned long long w3) { return (uint32_t)(w3 >> 48) & 0xFFFFu; }
 
 // ---------------------------------------------------------------------------
 // float helpers that must not be contracted into fma
@@ -876,7 +889,8 @@ __global__ __launch_bounds__(kBinThreads, 8) void k_bin_count(DevTick k, const f
 //      points; workgroup exclusive scan of the 8-point work items
 //   D3 load-balanced walk: every lane takes an equal share of the flattened
 //      item list; trajectory-level early exit through LDS flags
-//   E  stacked scoring + packed-key wave min-reduction + one atomicMin
+//   E  StickPath sums; then, single-round shards: stacked scoring + the tile's exact winner into the workgroup's
+//      slot + ticket; multi-round shards: one record per trajectory for k_finalize, nothing else
 // ---------------------------------------------------------------------------
 // Diagnostic build only (make diag): per-workgroup phase timestamps, written to a
 // buffer nothing else reads (cdna_hip_programming.md 7, In-kernel stamps).
@@ -1019,9 +1033,120 @@ typedef int i16v __attribute__((ext_vector_type(16)));
 struct StackArgs {
   i8v kind;
   i16v w, tw, ow;
-  static __device__ __forceinline__ double weight(const i16v& a, int m) { return __hiloint2double(a[2 * m + 1], a[2 * m]); }
+  static __host__ __device__ __forceinline__ double weight(const i16v& a, int m) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __hiloint2double(a[2 * m + 1], a[2 * m]);
+#else
+    const uint64_t u = ((uint64_t)(uint32_t)a[2 * m + 1] << 32) | (uint64_t)(uint32_t)a[2 * m];
+    double d;
+    __builtin_memcpy(&d, &u, sizeof(d));
+    return d;
+#endif
+  }
 };
 static_assert(DDDMR_MAX_CRITICS == 8, "StackArgs holds eight slots");
+// The kinds and the three weight arrays of the whole stack, read into register tuples as ONE group of loads.  A device
+// caller follows this with `asm volatile("" : "+s"(sa.kind), "+s"(sa.w), "+s"(sa.tw), "+s"(sa.ow))`: the empty statement
+// makes the kernel-argument loads opaque there, one wait for all of them, and none can sink into the slot chain
+// (left to itself the compiler loaded ckind[m], waited, branched, loaded the slot's weight and waited again: two
+// dependent round trips per slot, up to eight slots in series).
+__host__ __device__ __forceinline__ void stack_args_load(const DevTick& k, StackArgs& sa) {
+  __builtin_memcpy(&sa.kind, k.ckind, sizeof(sa.kind));
+  __builtin_memcpy(&sa.w, k.cw, sizeof(sa.w));
+  __builtin_memcpy(&sa.tw, k.ctw, sizeof(sa.tw));
+  __builtin_memcpy(&sa.ow, k.cow, sizeof(sa.ow));
+}
+
+// What k_score leaves per local trajectory for k_finalize on a multi-round shard (DevTick::final_kernel), beside
+// traj_info[li]: everything the critic stack reads that only k_score knows.
+struct TrajPartial {    // 32 bytes, indexed by the local trajectory
+  double stick_sum;     // StickPathModel: sum of the per-step 1-NN distances (0 for a collided trajectory)
+  double pp_dist;       // PurePursuitModel: |translation| of the pose difference
+  double pp_yaw;        // PurePursuitModel: folded yaw of the pose difference
+  float dist_last;      // TowardGlobalPlanModel: 1-NN distance of the last step (0 for a collided trajectory)
+  uint32_t flags;       // walked << 2 | hit_mm << 1 | hit_box
+};
+static_assert(sizeof(TrajPartial) == 32, "one 32-byte record per trajectory");
+__host__ __device__ inline uint32_t partial_flags(int walked, bool hit_box, bool hit_mm) {
+  return ((uint32_t)walked << 2) | (hit_mm ? 2u : 0u) | (hit_box ? 1u : 0u);
+}
+
+// The collision critics' verdict as the stack sees it: a collided ("dead") trajectory skipped phase P, and its cost
+// is -1 whatever else the stack holds.  (want_minmax is the kernel's need_mm: the lean k_score is only launched
+// without a min-max critic, and hit_mm is never set there.)
+__host__ __device__ __forceinline__ bool traj_dead(const DevTick& k, bool hit_box, bool hit_mm) {
+  return k.n_points >= 5 && ((k.want_collision != 0 && hit_box) || (k.want_minmax != 0 && hit_mm));
+}
+
+// Stacked scoring of ONE trajectory (stacked_scoring_model.cpp:75-93): cost = 0, every critic slot in stack order adds
+// its return, the first negative return IS the cost.  Called by k_score's single-round tail, by k_finalize and by the
+// host test, so the paths cannot drift.  *cbits is the cost's bit pattern when the planner may accept it
+// (local_planner.cpp:452-463), kKeyNone otherwise.  The chain is unrolled over the <= 8 slots, so every index into
+// the StackArgs tuples is a compile-time one.
+__host__ __device__ __forceinline__ double score_stack(const DevTick& k, const StackArgs& sa, const float w, const int steps,
+                                                       const bool hit_box, const bool hit_mm, const double stick_sum,
+                                                       const double pp_dist, const double pp_yaw, const float dist_last,
+                                                       int64_t* cbits) {
+  *cbits = kKeyNone;
+  if (steps <= 0) return DDDMR_COST_NOT_GENERATED;
+  const bool cloud_ok = k.n_points >= 5;   // collision_model.cpp:53-55
+  // A collided trajectory skipped phase P: its distances hold nothing.  The stack may list a path critic BEFORE the
+  // collision critic (any plugin order is legal, mpc_critics_ros.cpp:60-81); its non-negative return is then added
+  // and thrown away by the collision critic's -1 further down the stack, so 0 stands in for it here.
+  const bool dead = traj_dead(k, hit_box, hit_mm);
+  double cost = 0.0;
+  bool done = false;
+#pragma unroll
+  for (int m = 0; m < DDDMR_MAX_CRITICS; ++m) {
+    if (m >= k.n_critics || done) continue;
+    double r = 0.0;
+    const double cw_m = StackArgs::weight(sa.w, m);
+    switch (sa.kind[m]) {
+      case DDDMR_CRITIC_COLLISION:
+        r = (cloud_ok && hit_box) ? -1.0 : 0.0;
+        break;
+      case DDDMR_CRITIC_COLLISION_MIN_MAX:
+        r = (cloud_ok && hit_mm) ? -1.0 : 0.0;
+        break;
+      case DDDMR_CRITIC_STICK_PATH:
+        if (k.m < 3) r = 10.0;
+        else if (dead) r = 0.0;
+        else r = stick_sum / (double)k.m;
+        break;
+      case DDDMR_CRITIC_PURE_PURSUIT:
+        if (k.m == 0 || steps < 2) r = -4.0;
+        else r = StackArgs::weight(sa.tw, m) * pp_dist + StackArgs::weight(sa.ow, m) * pp_yaw;
+        break;
+      case DDDMR_CRITIC_TOWARD_GLOBAL_PLAN:
+        if (k.m < 3) r = 10.0;
+        else if (dead) r = 0.0;
+        else r = (double)dist_last * cw_m;
+        break;
+      case DDDMR_CRITIC_SHORTEST_ANGLE: {
+        const double thv = (double)w;
+        if (k.heading_dev >= 0) r = (thv >= 0) ? cw_m : cw_m * 2;
+        else r = (thv >= 0) ? cw_m * 2 : cw_m;
+      } break;
+      case DDDMR_CRITIC_TWIRLING:
+        r = fabs((double)w) * cw_m;
+        break;
+      default:
+        r = 0.0;
+    }
+    if (r < 0) { cost = r; done = true; }
+    else cost += r;
+  }
+  *cbits = cost_bits(cost);
+  return cost;
+}
+
+// Load feedback: what a trajectory cost k_score, in collision work items -- the walk, the path critics' 1-NN
+// searches when it got that far (`collided`: a wanted collision critic rejected it), and the per-pair phases.
+// (The verdict comes from the caller: k_score has it at hand, and re-deriving it from the DevTick there cost the
+// non-lean variants a stack frame.)
+__host__ __device__ inline uint32_t traj_load_of(int plan_m, int walked, int steps, bool collided) {
+  return (uint32_t)walked + (uint32_t)steps * (2u + (collided ? 0u : (uint32_t)((plan_m + 15) >> 4)));
+}
 
 __device__ __forceinline__ f2 dot3_2(f2 dx, f2 dy, f2 dz, float a, float b, float c) {
 #pragma clang fp contract(off)
@@ -1075,74 +1200,14 @@ __device__ __forceinline__ void obb_axes_in_place(float* r) {
   }
 }
 
-// Winner decode (local_planner.cpp:447-480), run by ONE wave once every k_score workgroup has filed its keys:
-// either wave 0 of the workgroup that drew the last ticket (small shards: no extra launch) or k_finalize.
-//
-// Exactness: the reference compares full doubles (`cost_ <= minimum_cost`, :460).  The key's winner i is the
-// highest index among the costs that share the minimum's top 40 bits; if cost[i] IS the minimum (its bits equal
-// the reduced cost word -- always, unless two costs differ by less than 3.7e-9 relative without being equal) then
-// i is also the highest index among the exactly minimal costs, i.e. the reference's answer.  Otherwise the wave
-// rescans the shard's costs for the exact minimum (rare; 64 lanes, device-scope loads).
-__device__ __forceinline__ void decode_winner(const DevTick& k, const int lane, const int64_t* __restrict__ best_key,
-                                              const double* __restrict__ costs, const float4* __restrict__ samples_out,
-                                              const uint32_t* __restrict__ cell_start, const uint32_t* __restrict__ overflow,
-                                              DevResult* __restrict__ result, int64_t* __restrict__ words_out) {
-  const int64_t kmin = __hip_atomic_load(best_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const int64_t cmin = __hip_atomic_load(best_key + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const unsigned long long* cost_words = reinterpret_cast<const unsigned long long*>(costs);
-  int li = -1;
-  if (kmin != kKeyNone) {
-    li = key_index(kmin) - k.begin;
-    const long long cb = (long long)__hip_atomic_load(cost_words + li, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cb != (long long)cmin) {
-      int found = -1;
-      for (int i = lane; i < k.n_local; i += 64)
-        if ((long long)__hip_atomic_load(cost_words + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (long long)cmin) found = i;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) found = max(found, __shfl_xor(found, o, 64));
-      li = found;
-    }
-  }
-  if (lane == 0) {
-    DevResult r;
-    r.index = li >= 0 ? k.begin + li : -1;
-    r.cost = -1.0;
-    r.vx = r.vy = r.wz = 0.f;
-    r.key = kKeyNone;
-    if (li >= 0) {
-      r.cost = __longlong_as_double((long long)cmin);
-      r.key = pack_key(r.cost, (uint32_t)r.index);
-      const float* so = reinterpret_cast<const float*>(samples_out + li);
-      r.vx = __hip_atomic_load(so + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      r.vy = __hip_atomic_load(so + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      r.wz = __hip_atomic_load(so + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    r.n_binned = cell_start[k.n_cells];
-    r.overflow = __hip_atomic_load(overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    r.seq = 0;
-    {
-      // sampled share of collided trajectories, scaled to the shard
-      const unsigned long long w2 = (unsigned long long)__hip_atomic_load(best_key + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned long long sampled = w2 >> 32, collided = w2 & 0xFFFFFFFFull;
-      r.n_collided = sampled ? (uint32_t)(collided * (unsigned long long)k.n_local / sampled) : 0u;
-    }
-    *result = r;
-    if (words_out) {
-      // multi-rank context: this shard's (cost bits, -index) slot of the all-reduce that follows on
-      // the stream; `result` then is a device-side staging record and k_resolve tells the host
-      words_out[0] = li >= 0 ? (int64_t)cmin : kKeyNone;
-      words_out[1] = li >= 0 ? -(int64_t)r.index : kKeyNone;
-    } else {
-      __threadfence_system();
-      __hip_atomic_store(&result->seq, k.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
-}
-
-// Single-round shards: wave 0 of the last workgroup reduces the workgroups' slots (see the tail of k_score) --
-// minimum cost as full doubles, equal costs -> highest index -- and publishes the result.  The loads of up to
+// Winner decode (local_planner.cpp:447-480), run by ONE wave once every workgroup of the launch has filed its slot:
+// wave 0 of the workgroup that drew the last ticket -- of k_score on a single-round shard (see its tail), of
+// k_finalize on a multi-round one.  It reduces the slots -- minimum cost as full doubles, equal costs -> highest
+// index, exactly the reference's `cost_ <= minimum_cost` scan (:456-463) -- and publishes the result.  The loads of up to
 // 8 slots per lane (a launch of <= 512 workgroups) are all issued before the first use, beside the two other words
 // the result needs: ONE memory round trip, then six shuffle steps.
+// (kStamps: the diagnostic build's stamps 16..18 belong to k_score's rows of the stamp buffer)
+template <bool kStamps>
 __device__ __forceinline__ void reduce_slots(const DevTick& k, const int lane, const int n_slots,
                                              const unsigned long long* __restrict__ slots,
                                              const uint32_t* __restrict__ cell_start, const uint32_t* __restrict__ overflow,
@@ -1168,12 +1233,12 @@ __device__ __forceinline__ void reduce_slots(const DevTick& k, const int lane, c
       const int i = base + u * 64 + lane;
       if (i < n_slots) {
         const long long c = (long long)w[u][0], gi = (long long)w[u][1];
-        n_coll += (uint32_t)((w[u][3] >> 32) & 0xFFu);
+        n_coll += slot_collided(w[u][3]);
         if (c < bc || (c == bc && gi > bi)) { bc = c; bi = gi; b2 = w[u][2]; b3 = w[u][3]; }
       }
     }
   }
-  DDDMR_STAMP_RAW(16);
+  if (kStamps) DDDMR_STAMP_RAW(16);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const long long oc = __shfl_xor(bc, o, 64), oi = __shfl_xor(bi, o, 64);
@@ -1193,8 +1258,8 @@ __device__ __forceinline__ void reduce_slots(const DevTick& k, const int lane, c
     r.n_binned = n_binned;
     r.overflow = over;
     r.seq = 0;
-    r.n_collided = n_coll;          // exact here (every workgroup reports), sampled on multi-round shards
-    DDDMR_STAMP_RAW(17);
+    r.n_collided = n_coll;          // exact on both paths: every workgroup reports its count
+    if (kStamps) DDDMR_STAMP_RAW(17);
     *result = r;
     if (words_out) {
       // multi-rank context: this shard's (cost bits, -index) slot of the all-reduce that follows on
@@ -1205,8 +1270,22 @@ __device__ __forceinline__ void reduce_slots(const DevTick& k, const int lane, c
       __threadfence_system();
       __hip_atomic_store(&result->seq, k.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    DDDMR_STAMP_RAW(18);
+    if (kStamps) DDDMR_STAMP_RAW(18);
   }
+}
+
+// StickPath's sum of one trajectory's per-step distances by one wave: lanes stride the steps, then a fixed
+// reduction tree in double -- inside the 16-lane rows towards their first lane (DPP), then the four row sums.  The
+// total is valid in lane 0.  One definition, so that both tails of k_score add in the same order.
+__device__ __forceinline__ double stick_sum_wave(const float* dr, const int ns, const int lane) {
+  double acc = 0.0;
+  for (int s2 = lane; s2 < ns; s2 += 64) acc += (double)dr[s2];
+  acc += dpp_row_shl<8>(acc);
+  acc += dpp_row_shl<4>(acc);
+  acc += dpp_row_shl<2>(acc);
+  acc += dpp_row_shl<1>(acc);
+  const double r1 = __shfl(acc, 16, 64), r2 = __shfl(acc, 32, 64), r3 = __shfl(acc, 48, 64);
+  return (acc + r1) + (r2 + r3);
 }
 
 // kLean: the common case -- no min-max critic, no pair that needs the 1 m radius test (the cuboid lies
@@ -1222,7 +1301,7 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
     float4* __restrict__ samples_out, int64_t* __restrict__ best_key, uint32_t* __restrict__ overflow,
     uint32_t* __restrict__ ticket, DevResult* __restrict__ result, const uint32_t* __restrict__ assign,
     uint32_t* __restrict__ traj_load, int64_t* __restrict__ words_out, const uint32_t* __restrict__ row_tab,
-    const float* __restrict__ plan_pairs) {
+    const float* __restrict__ plan_pairs, TrajPartial* __restrict__ partial) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int tile = k.tile;
   const int S1 = k.max_steps + 1;
@@ -1799,158 +1878,71 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
   // StickPath's sum of per-step distances (stick_path_model.cpp:62-73): one wave per
   // trajectory, lanes stride the steps, fixed reduction tree in double (the
   // reference adds in step order; the difference is <= 1e-15 relative).
+  //
+  // Multi-round shards (k.final_kernel) END here.  A workgroup's life is what bounds the launch there (workgroups
+  // queue for the slots their LDS allows), and everything after the sums -- the stacked scoring chain of <= 16 lanes,
+  // the tile's argmin, device-scope traffic -- kept a slot's LDS while one wave worked.  So lane 0 of the wave
+  // that summed trajectory j files its 32-byte record (plain stores: records are read after the launch boundary)
+  // and the wave ends: no barrier, no scoring, no per-trajectory output, no key, no atomic.  k_finalize scores the
+  // whole shard one lane per trajectory and takes the exact argmin.  Every trajectory of the tile gets a record,
+  // a not-generated and a collided one too (the outputs may be poisoned before the tick).
+  if (k.final_kernel) {
+    for (int j = wid; j < nt; j += kScoreThreads / 64) {
+      const int ns = head[j].steps;
+      const double sum = stick_sum_wave(dist + (size_t)j * S1, ns, lane);
+      if (lane == 0) {
+        const bool hb = head[j].hit_box != 0, hm = head[j].hit_mm != 0;
+        const bool dead = cloud_ok && ((need_box && hb) || (need_mm && hm));    // (skipped phase P: no distances)
+        TrajPartial* pr = partial + head[j].li;
+        pr->stick_sum = dead ? 0.0 : sum;
+        pr->pp_dist = head[j].pp_dist;
+        pr->pp_yaw = head[j].pp_yaw;
+        pr->dist_last = (ns > 0 && !dead) ? dist[(size_t)j * S1 + ns - 1] : 0.f;
+        pr->flags = partial_flags(head[j].walked, hb, hm);
+      }
+    }
+    DDDMR_STAMP(10);  // end of (wave 0's) StickPath sums and records
+    DDDMR_STAMP(11);
+    DDDMR_STAMP(7);
+    return;
+  }
   for (int j = wid; j < nt; j += kScoreThreads / 64) {
-    const int ns = head[j].steps;
-    const float* dr = dist + (size_t)j * S1;
-    double acc = 0.0;
-    for (int s2 = lane; s2 < ns; s2 += 64) acc += (double)dr[s2];
-    // fixed tree: inside the 16-lane rows towards their first lane (DPP), then the four row sums
-    acc += dpp_row_shl<8>(acc);
-    acc += dpp_row_shl<4>(acc);
-    acc += dpp_row_shl<2>(acc);
-    acc += dpp_row_shl<1>(acc);
-    const double r1 = __shfl(acc, 16, 64), r2 = __shfl(acc, 32, 64), r3 = __shfl(acc, 48, 64);
-    if (lane == 0) head[j].stick_sum = (acc + r1) + (r2 + r3);
+    const double sum = stick_sum_wave(dist + (size_t)j * S1, head[j].steps, lane);
+    if (lane == 0) head[j].stick_sum = sum;
   }
   __syncthreads();
   DDDMR_STAMP(10);  // end of the StickPath sums
 
-  // ---- phase E: stacked scoring (stacked_scoring_model.cpp:75-93) + argmin ----
-  int64_t key = kKeyNone, cbits = kKeyNone;
+  // ---- phase E (single-round shards): stacked scoring (stacked_scoring_model.cpp:75-93) + argmin ----
+  int64_t cbits = kKeyNone;
   int my_gi = -1;
   if (tid < nt) {
     const TrajHead h = head[tid];
     const int li = head[tid].li;
     const int gi = k.begin + li;
     my_gi = gi;
+    const bool hb = h.hit_box != 0, hm = h.hit_mm != 0;
+    const bool dead = cloud_ok && ((need_box && hb) || (need_mm && hm));
     double cost = DDDMR_COST_NOT_GENERATED;
     if (h.steps > 0) {
-      cost = 0.0;
-      const float* dr = dist + (size_t)tid * S1;
-      // A collided trajectory skipped phase P: its dist[] row and stick_sum hold nothing.  The
-      // stack may list a path critic BEFORE the collision critic (any plugin order is legal,
-      // mpc_critics_ros.cpp:60-81); its non-negative return is then added and thrown away by
-      // the collision critic's -1 further down the stack, so 0 stands in for it here.
-      const bool dead = cloud_ok && ((need_box && h.hit_box) || (need_mm && h.hit_mm));
-      // The kinds and the three weight arrays of the whole stack are read into locals as ONE group of kernel-argument
-      // loads with one wait (the empty statement makes them opaque there, so no load can sink into the slot chain);
-      // left to itself the compiler loaded ckind[m], waited, branched, loaded the slot's weight and waited again:
-      // two dependent round trips per slot, up to eight slots in series on the one wave the workgroup's end waits for.
-      // The chain below is unrolled over the <= 8 slots, so every index into the locals is a compile-time one.
+      const float dist_last = dead ? 0.f : dist[(size_t)tid * S1 + h.steps - 1];
+      // one group of kernel-argument loads with one wait, see stack_args_load(): this is the one wave the
+      // workgroup's end waits for
       StackArgs sa;
-      __builtin_memcpy(&sa.kind, k.ckind, sizeof(sa.kind));
-      __builtin_memcpy(&sa.w, k.cw, sizeof(sa.w));
-      __builtin_memcpy(&sa.tw, k.ctw, sizeof(sa.tw));
-      __builtin_memcpy(&sa.ow, k.cow, sizeof(sa.ow));
+      stack_args_load(k, sa);
       asm volatile("" : "+s"(sa.kind), "+s"(sa.w), "+s"(sa.tw), "+s"(sa.ow));
-      bool done = false;
-#pragma unroll
-      for (int m = 0; m < DDDMR_MAX_CRITICS; ++m) {
-        if (m >= k.n_critics || done) continue;
-        double r = 0.0;
-        const double cw_m = sa.weight(sa.w, m);
-        switch (sa.kind[m]) {
-          case DDDMR_CRITIC_COLLISION:
-            r = (cloud_ok && h.hit_box) ? -1.0 : 0.0;
-            break;
-          case DDDMR_CRITIC_COLLISION_MIN_MAX:
-            r = (cloud_ok && h.hit_mm) ? -1.0 : 0.0;
-            break;
-          case DDDMR_CRITIC_STICK_PATH:
-            if (k.m < 3) {
-              r = 10.0;
-            } else if (dead) {
-              r = 0.0;
-            } else {
-              const double acc = h.stick_sum;
-              r = acc / (double)k.m;
-            }
-            break;
-          case DDDMR_CRITIC_PURE_PURSUIT:
-            if (k.m == 0 || h.steps < 2) r = -4.0;
-            else r = sa.weight(sa.tw, m) * h.pp_dist + sa.weight(sa.ow, m) * h.pp_yaw;
-            break;
-          case DDDMR_CRITIC_TOWARD_GLOBAL_PLAN:
-            if (k.m < 3) r = 10.0;
-            else if (dead) r = 0.0;
-            else r = (double)dr[h.steps - 1] * cw_m;
-            break;
-          case DDDMR_CRITIC_SHORTEST_ANGLE: {
-            const double thv = (double)h.w;
-            if (k.heading_dev >= 0) r = (thv >= 0) ? cw_m : cw_m * 2;
-            else r = (thv >= 0) ? cw_m * 2 : cw_m;
-          } break;
-          case DDDMR_CRITIC_TWIRLING:
-            r = fabs((double)h.w) * cw_m;
-            break;
-          default:
-            r = 0.0;
-        }
-        if (r < 0) { cost = r; done = true; }
-        else cost += r;
-      }
-      if (k.final_kernel) key = pack_key(cost, (uint32_t)gi);
-      cbits = cost_bits(cost);
+      cost = score_stack(k, sa, h.w, h.steps, hb, hm, h.stick_sum, h.pp_dist, h.pp_yaw, dist_last, &cbits);
     }
-    // per-trajectory outputs: plain stores (nothing on the device reads them before the launch ends: k_finalize
-    // comes after the launch boundary, and a single-round shard's last workgroup works from the workgroup slots)
+    // per-trajectory outputs: plain stores (nothing on the device reads them before the launch ends: the last
+    // workgroup works from the workgroup slots)
     costs[li] = cost;
     samples_out[li] = make_float4(h.vx, h.vy, h.w, 0.f);
     steps_out[li] = h.steps;
-    // what this trajectory cost (in collision work items): the walk, the path critics'
-    // 1-NN searches when it got that far, and the per-pair phases
-    const bool collided = (need_box && h.hit_box) || (need_mm && h.hit_mm);
-    traj_load[li] = (uint32_t)h.walked + (uint32_t)h.steps * (2u + (collided ? 0u : (uint32_t)((k.m + 15) >> 4)));
+    traj_load[li] = traj_load_of(k.m, h.walked, h.steps, (need_box && hb) || (need_mm && hm));
   }
   DDDMR_STAMP(11);  // end of the stacked scoring + per-trajectory stores
   // ---- argmin hand-off ----
-  // Multi-round shards (k.final_kernel): wave-0 min-reduction of two words -- the packed key (top 40 bits of the
-  // cost | inverted index: one atomicMin yields minimum cost AND, among costs equal in those bits, the highest
-  // index) and the cost's full bit pattern, which makes k_finalize's decode exact -- and one pair of atomicMins.
-  if (k.final_kernel) {
-    if (tid < 64) {
-      static_assert(kMaxTile <= 16, "only lanes 0..kMaxTile-1 hold keys");
-      {
-        long long kk = (long long)key, cc = (long long)cbits, o;
-        o = dpp_row_shl<8>(kk); kk = o < kk ? o : kk;
-        o = dpp_row_shl<4>(kk); kk = o < kk ? o : kk;
-        o = dpp_row_shl<2>(kk); kk = o < kk ? o : kk;
-        o = dpp_row_shl<1>(kk); kk = o < kk ? o : kk;
-        o = dpp_row_shl<8>(cc); cc = o < cc ? o : cc;
-        o = dpp_row_shl<4>(cc); cc = o < cc ? o : cc;
-        o = dpp_row_shl<2>(cc); cc = o < cc ? o : cc;
-        o = dpp_row_shl<1>(cc); cc = o < cc ? o : cc;
-        key = (int64_t)kk;                                   // lane 0: minimum of lanes 0..15
-        cbits = (int64_t)cc;
-      }
-      // Same-address device-scope atomics serialise (~4 ns each): a workgroup first LOOKS at the running minima
-      // (plain device-scope loads, served in parallel) and only issues an atomicMin for a word it can still lower.
-      // The minima only ever decrease, so a stale (larger) value can cause a superfluous atomic, never a missing
-      // one (C3 k_score 126.5 -> 122 us).
-      if (tid == 0 && key != kKeyNone) {
-        const long long cur_k = (long long)__hip_atomic_load(best_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const long long cur_c = (long long)__hip_atomic_load(best_key + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((long long)key < cur_k) atomicMin((long long*)best_key, (long long)key);
-        if ((long long)cbits < cur_c) atomicMin((long long*)best_key + 1, (long long)cbits);
-      }
-      // How many trajectories the collision critics rejected -- a SAMPLE (every 16th workgroup; tiles are dealt as
-      // representative mixes): the next tick's walk starts with a probe round only when most do (the probe settles
-      // colliding trajectories early and is pure overhead otherwise).  Word 2 counts the sampled collided
-      // trajectories in its low half and the sampled trajectories in its high half.
-      if ((blockIdx.x & 15u) == 0u) {
-        const bool gen = tid < nt && head[tid].steps > 0;
-        const bool coll = gen && cloud_ok && ((need_box && head[tid].hit_box) || (need_mm && head[tid].hit_mm));
-        const unsigned long long cm = __ballot(coll), gm = __ballot(gen);
-        if (tid == 0 && gm)
-          atomicAdd((unsigned long long*)best_key + 2, ((unsigned long long)__popcll(gm) << 32) | (unsigned long long)__popcll(cm));
-      }
-    }
-    // nothing more to do here -- k_finalize decodes after the launch, so a workgroup neither waits for its stores
-    // nor pays a device-scope ticket round trip while it holds a slot that the next workgroup is waiting for.
-    DDDMR_STAMP(7);
-    return;
-  }
-  // Single-round shards: all workgroups of the launch finish within a few microseconds of each other, and what they
+  // All workgroups of the launch finish within a few microseconds of each other, and what they
   // used to do then -- two atomicMins and a ticket on the SAME addresses -- queued up behind one another (C2: 3.6 us
   // of a workgroup's 23 us on average, 8.6 us for the unluckiest, which is what the launch waits for).  Now every
   // workgroup leaves its exact local winner in its OWN slot (four 8-byte write-through stores: cost bits, global
@@ -1985,8 +1977,7 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
       __hip_atomic_store(sl + 1, (unsigned long long)(long long)win_gi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(sl + 2, (unsigned long long)__float_as_uint(vx) | ((unsigned long long)__float_as_uint(vy) << 32),
                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(sl + 3, (unsigned long long)__float_as_uint(w) | ((unsigned long long)__popcll(cm) << 32) |
-                                     ((unsigned long long)__popcll(gm) << 40),
+      __hip_atomic_store(sl + 3, pack_slot_word3(__float_as_uint(w), (uint32_t)__popcll(cm), (uint32_t)__popcll(gm)),
                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     // wave 0 alone goes on (the other waves are done: nothing they wrote is read on the device again): its slot
@@ -1998,18 +1989,98 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
     DDDMR_STAMP_RAW(15);
     if (t == gridDim.x - 1) {
       if (lane == 0) *ticket = 0;
-      reduce_slots(k, lane, (int)gridDim.x, slots, cell_start, overflow, result, words_out);
+      reduce_slots<true>(k, lane, (int)gridDim.x, slots, cell_start, overflow, result, words_out);
     }
   }
   DDDMR_STAMP(7);
 }
 
-// Winner decode as its own one-wave launch (multi-round shards, DevTick::final_kernel).
-__global__ __launch_bounds__(64) void k_finalize(DevTick k, const int64_t* __restrict__ best_key, const double* __restrict__ costs,
-                                                 const float4* __restrict__ samples_out, const uint32_t* __restrict__ cell_start,
-                                                 const uint32_t* __restrict__ overflow, DevResult* __restrict__ result,
-                                                 int64_t* __restrict__ words_out) {
-  decode_winner(k, (int)threadIdx.x, best_key, costs, samples_out, cell_start, overflow, result, words_out);
+// Stacked scoring + argmin of a multi-round shard as a launch of its own (DevTick::final_kernel), one lane per local
+// trajectory, ceil(n_local / 256) workgroups of kFinalThreads.  Lane li reads traj_info[li] and the record k_score
+// left for it (plain loads: both were written by earlier launches), runs the same score_stack() as the single-round
+// tail of k_score and writes the trajectory's four outputs.  The workgroup then reduces the exact pair -- cost bits
+// as signed 64-bit, highest global index among equals (local_planner.cpp:456-463) -- carrying the winner's sample
+// along, and counts its collided / generated trajectories.  Wave 0 files that as the workgroup's slot with the
+// hand-off of k_score's single-round tail (four device-scope stores, s_waitcnt vmcnt(0), one relaxed device-scope
+// ticket; DDDMR_HANDOFF_ORDER), and the wave that draws the last ticket runs reduce_slots().  No packed key, no
+// rescan: nothing is compared at less than a double's width.
+constexpr int kFinalThreads = 256;
+__global__ __launch_bounds__(kFinalThreads) void k_finalize(
+    DevTick k, const TrajInfo* __restrict__ info, const TrajPartial* __restrict__ partial, double* __restrict__ costs,
+    int32_t* __restrict__ steps_out, float4* __restrict__ samples_out, uint32_t* __restrict__ traj_load,
+    int64_t* __restrict__ best_key, const uint32_t* __restrict__ cell_start, const uint32_t* __restrict__ overflow,
+    uint32_t* __restrict__ ticket, DevResult* __restrict__ result, int64_t* __restrict__ words_out) {
+  constexpr int kWaves = kFinalThreads / 64;
+  __shared__ long long s_c[kWaves];
+  __shared__ int s_gi[kWaves];
+  __shared__ unsigned long long s_v[kWaves];     // vx | vy << 32
+  __shared__ uint32_t s_w[kWaves], s_coll[kWaves], s_gen[kWaves];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int li = (int)blockIdx.x * kFinalThreads + tid;
+  StackArgs sa;
+  stack_args_load(k, sa);
+  asm volatile("" : "+s"(sa.kind), "+s"(sa.w), "+s"(sa.tw), "+s"(sa.ow));
+  long long cc = (long long)kKeyNone;
+  int gi = -1;
+  unsigned long long v2 = 0;
+  uint32_t wb = 0;
+  bool gen = false, coll = false;
+  if (li < k.n_local) {
+    const TrajInfo ti = info[li];
+    const TrajPartial pr = partial[li];
+    const bool hb = (pr.flags & 1u) != 0, hm = (pr.flags & 2u) != 0;
+    int64_t cbits;
+    const double cost = score_stack(k, sa, ti.w, ti.steps, hb, hm, pr.stick_sum, pr.pp_dist, pr.pp_yaw, pr.dist_last, &cbits);
+    costs[li] = cost;
+    samples_out[li] = make_float4(ti.vx, ti.vy, ti.w, 0.f);
+    steps_out[li] = ti.steps;
+    traj_load[li] = traj_load_of(k.m, (int)(pr.flags >> 2), ti.steps, (k.want_collision != 0 && hb) || (k.want_minmax != 0 && hm));
+    cc = (long long)cbits;
+    gi = k.begin + li;
+    v2 = (unsigned long long)__float_as_uint(ti.vx) | ((unsigned long long)__float_as_uint(ti.vy) << 32);
+    wb = __float_as_uint(ti.w);
+    gen = ti.steps > 0;
+    coll = gen && traj_dead(k, hb, hm);
+  }
+  const uint32_t n_coll = (uint32_t)__popcll(__ballot(coll)), n_gen = (uint32_t)__popcll(__ballot(gen));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const long long oc = __shfl_xor(cc, o, 64);
+    const int oi = __shfl_xor(gi, o, 64);
+    const unsigned long long ov = __shfl_xor(v2, o, 64);
+    const uint32_t ow = __shfl_xor(wb, o, 64);
+    if (oc < cc || (oc == cc && oi > gi)) { cc = oc; gi = oi; v2 = ov; wb = ow; }
+  }
+  if (lane == 0) {
+    s_c[wid] = cc; s_gi[wid] = gi; s_v[wid] = v2; s_w[wid] = wb; s_coll[wid] = n_coll; s_gen[wid] = n_gen;
+  }
+  __syncthreads();
+  if (tid >= 64) return;
+  uint32_t tc = 0, tg = 0;
+  cc = s_c[0]; gi = s_gi[0]; v2 = s_v[0]; wb = s_w[0];
+#pragma unroll
+  for (int q = 0; q < kWaves; ++q) {
+    tc += s_coll[q];
+    tg += s_gen[q];
+    if (q > 0 && (s_c[q] < cc || (s_c[q] == cc && s_gi[q] > gi))) { cc = s_c[q]; gi = s_gi[q]; v2 = s_v[q]; wb = s_w[q]; }
+  }
+  unsigned long long* slots = reinterpret_cast<unsigned long long*>(best_key) + kSlotBase;
+  if (lane == 0) {
+    const bool any = cc != (long long)kKeyNone;       // (no acceptable cost: the slot carries no sample)
+    unsigned long long* sl = slots + (size_t)blockIdx.x * kSlotWords;
+    __hip_atomic_store(sl + 0, (unsigned long long)cc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(sl + 1, (unsigned long long)(long long)gi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(sl + 2, any ? v2 : 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(sl + 3, pack_slot_word3(any ? wb : 0u, tc, tg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  uint32_t t = 0;
+  if (lane == 0) t = __hip_atomic_fetch_add(ticket, 1u, DDDMR_HANDOFF_ORDER, __HIP_MEMORY_SCOPE_AGENT);
+  t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+  if (t == gridDim.x - 1) {
+    if (lane == 0) *ticket = 0;
+    reduce_slots<false>(k, lane, (int)gridDim.x, slots, cell_start, overflow, result, words_out);
+  }
 }
 
 // n_local == 0 (a rank without samples): result only.

@@ -501,7 +501,7 @@ int plan_tick(const TickKnobs& kn, const TickFeedback& fb, const dddmr_rollout_c
   p->lean = !k.want_minmax && !k.rec_pose && k.box_fast;
   // Who decodes the winner: shards that run as ONE round of workgroups let the last workgroup do it (a
   // finalize launch would cost the tick ~3 us); bigger shards run several rounds, where every workgroup's ticket
-  // round trip holds a slot that the next workgroup is waiting for -- there a one-wave k_finalize follows.
+  // round trip holds a slot that the next workgroup is waiting for -- there k_finalize follows and scores the stacks too.
   // The collision walk's probe round (every lane first walks ONE item, spread evenly over the tile's list) settles
   // colliding trajectories early; when few collide it is a barrier and a scan for nothing.  Measured: 86 %
   // colliding (C3, r01 scene) k_score 114 us with / 155 us without; 25 % colliding (r02 scenes) C3 126.5 / 124.0 us,
