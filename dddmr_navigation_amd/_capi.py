@@ -326,6 +326,7 @@ EXPORTED_SYMBOLS = (
     "dddmr_rollout_winner_words",
     "dddmr_rollout_resolve_words",
     "dddmr_rollout_get_debug",
+    "dddmr_rollout_heading_rows",
     "dddmr_rollout_get_best_poses",
     "dddmr_rollout_get_best_cuboids",
     "dddmr_rollout_get_pose_arrays",
@@ -448,6 +449,10 @@ def load_library() -> C.CDLL:
     lib.dddmr_rollout_resolve_words.restype = C.c_int
     lib.dddmr_rollout_get_debug.argtypes = [ctx_p, C.POINTER(RolloutDebug)]
     lib.dddmr_rollout_get_debug.restype = C.c_int
+    # (a library built from an older commit, loaded through DDDMR_LIB_NAME by the measurement jobs, has no such entry)
+    if hasattr(lib, "dddmr_rollout_heading_rows"):
+        lib.dddmr_rollout_heading_rows.argtypes = [ctx_p]
+        lib.dddmr_rollout_heading_rows.restype = C.c_int
     lib.dddmr_rollout_get_best_poses.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.dddmr_rollout_get_best_poses.restype = C.c_int
     lib.dddmr_rollout_get_best_cuboids.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]

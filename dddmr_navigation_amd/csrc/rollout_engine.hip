@@ -69,7 +69,8 @@ struct dddmr_rollout_ctx {
   std::vector<dddmr_theory_config> theories;
   int device = 0;
   hipStream_t stream = nullptr, copy_stream = nullptr;
-  // k_rollout state arrays, grown on demand: [n_local][max steps of the tick]
+  // k_rollout state arrays, grown on demand: [n_local][max steps of the tick] (of st_sc a tick with shared heading rows
+  // fills only the first nth rows, one per angular sample)
   TrajInfo* traj_info = nullptr;
   double2* st_sc = nullptr;
   float2* st_xy = nullptr;
@@ -167,6 +168,8 @@ struct dddmr_rollout_ctx {
   int timing = 1;   // DDDMR_TIMING: 0 no HIP events, 1 around k_score (score_ms), 2 also around the whole tick
   int timing_every = 1;   // DDDMR_TIMING_EVERY: record the events on every n-th tick only
   int spin = 1;     // DDDMR_SPIN: poll the host-mapped result instead of hipStreamSynchronize
+  bool heading_rows = true;   // DDDMR_HEADING_ROWS=0: a heading chain per trajectory on every tick (rollout_kernels.hip.h)
+  int last_heading_rows = -1; // what the last launched tick did (dddmr_rollout_heading_rows)
   uint32_t seq = 0;
   DevResult last_result{};   // host copy of the last COLLECTED tick's result
   float last_score_ms = 0.f, last_device_ms = 0.f;
@@ -391,6 +394,7 @@ int dddmr_rollout_create(const dddmr_rollout_config* cfg, dddmr_rollout_ctx** ou
   if (const char* e = std::getenv("DDDMR_TIMING")) ctx->timing = std::atoi(e);
   if (const char* e = std::getenv("DDDMR_TIMING_EVERY")) ctx->timing_every = std::max(1, std::atoi(e));
   if (const char* e = std::getenv("DDDMR_SPIN")) ctx->spin = std::atoi(e);
+  if (const char* e = std::getenv("DDDMR_HEADING_ROWS")) ctx->heading_rows = std::atoi(e) != 0;
   if (const char* e = std::getenv("DDDMR_FINAL")) ctx->knobs.final_mode = std::atoi(e) ? 1 : 0;
   if (const char* e = std::getenv("DDDMR_PROBE")) ctx->knobs.probe_mode = std::atoi(e) ? 1 : 0;
 
@@ -759,19 +763,34 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
   // traj_load will describe this tick's shard of this theory
   ctx->feedback.load_theory = theory_id;
   ctx->feedback.load_nlocal = k.n_local;
+  // Heading rows per angular sample (rollout_kernels.hip.h, heading_rows_shared()): decided here, outside the plan, and
+  // handed to the rollout as an argument of its own.  The rows' LDS comes on top of the plan's; a tick whose rollout
+  // workgroups would no longer sit two to a CU with it (72 KB of dynamic LDS beside k_bin_count's 8 KB of static) keeps
+  // a chain per trajectory.
+  size_t roll_lds = p.roll_lds;
+  int heading_rows = 0;
+  if (ctx->heading_rows && heading_rows_shared(k)) {
+    const size_t with_rows = p.roll_lds + heading_rows_lds_bytes(k.max_steps, k.kind == DDDMR_THEORY_OMNI_SIMPLE);
+    const size_t two_per_cu = (size_t)72 * 1024;
+    if (with_rows <= (size_t)kScoreLdsMax && (with_rows <= two_per_cu || p.roll_lds > two_per_cu)) {
+      roll_lds = with_rows;
+      heading_rows = 1;
+    }
+  }
+  ctx->last_heading_rows = heading_rows;
   if (k.n_points > 0) {
-    hipLaunchKernelGGL(k_bin_count, dim3(p.cnt_blocks + p.roll_blocks + (k.use_assign ? k.assign_groups : 0)), dim3(kBinThreads), p.roll_lds,
+    hipLaunchKernelGGL(k_bin_count, dim3(p.cnt_blocks + p.roll_blocks + (k.use_assign ? k.assign_groups : 0)), dim3(kBinThreads), roll_lds,
                        ctx->stream, k, ctx->cloud_dev[cidx], ctx->cell_count, ctx->cell_start, ctx->pt_slot, ctx->tickets,
                        ctx->best_key, ctx->overflow, ctx->axes_dev, ctx->samples_dev, ctx->traj_info, ctx->st_sc,
-                       ctx->st_xy, ctx->traj_load, ctx->assign);
+                       ctx->st_xy, ctx->traj_load, ctx->assign, heading_rows);
     hipLaunchKernelGGL(k_bin_scatter, dim3(p.bin_blocks), dim3(256), 0, ctx->stream, k, ctx->cloud_dev[cidx],
                        ctx->pt_slot, ctx->cell_start, ctx->sorted, ctx->row_tab);
   } else {
     hipLaunchKernelGGL(k_bin_reset, dim3(1), dim3(256), 0, ctx->stream, k, ctx->cell_count, ctx->cell_start,
                        ctx->best_key, ctx->overflow);
     if (p.roll_blocks > 0)
-      hipLaunchKernelGGL(k_rollout, dim3(p.roll_blocks), dim3(256), p.roll_lds, ctx->stream, k, ctx->axes_dev,
-                         ctx->samples_dev, ctx->traj_info, ctx->st_sc, ctx->st_xy);
+      hipLaunchKernelGGL(k_rollout, dim3(p.roll_blocks), dim3(256), roll_lds, ctx->stream, k, ctx->axes_dev,
+                         ctx->samples_dev, ctx->traj_info, ctx->st_sc, ctx->st_xy, heading_rows);
     if (k.use_assign)
       hipLaunchKernelGGL(k_assign, dim3(k.assign_groups), dim3(kBinThreads), 0, ctx->stream, k, ctx->traj_load, ctx->assign);
   }
@@ -1185,6 +1204,12 @@ int dddmr_rollout_samples(dddmr_rollout_ctx* ctx, const char* theory_name, const
   return DDDMR_OK;
 }
 
+int dddmr_rollout_heading_rows(dddmr_rollout_ctx* ctx) {
+  if (!ctx) return -1;
+  std::lock_guard<std::mutex> tk(ctx->tick_mu);
+  return ctx->last_heading_rows;
+}
+
 int dddmr_rollout_get_debug(dddmr_rollout_ctx* ctx, dddmr_rollout_debug* dbg) {
   if (!ctx || !dbg) return DDDMR_ERR_BAD_ARG;
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
@@ -1247,7 +1272,7 @@ int dddmr_rollout_get_pose_arrays(dddmr_rollout_ctx* ctx, int32_t which, double*
     rc = DDDMR_ERR_HIP;
   if (rc == DDDMR_OK) {
     hipLaunchKernelGGL(k_pose_arrays, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, ctx->stream, ctx->last, off_dev,
-                       ctx->steps, ctx->st_sc, ctx->st_xy, out_dev);
+                       ctx->steps, ctx->traj_info, ctx->st_sc, ctx->st_xy, out_dev);
     if (hipMemcpyAsync(poses_out, out_dev, total * 7 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess)
       rc = DDDMR_ERR_HIP;

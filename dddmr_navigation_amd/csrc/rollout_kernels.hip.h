@@ -143,6 +143,42 @@ struct DevTick {
   float axes_inl[kInlineAxes];
 };
 
+// Heading rows.  On a grid tick with a fixed step count the heading chain theta <- float(double(theta) + w * dt) and its
+// sin / cos depend on the angular sample alone (dt = sim_time / fixed_steps, and rotate-in-place's sim_time = 6.28 / |w|
+// is again a function of w): the shard's trajectories fall into nth classes, class = (begin + li) % nth, whose members
+// share one row of headings.  The rollout workgroups then take the shard in class-major order, so that each of them
+// evaluates at most two rows instead of one per trajectory.  True when that holds for the tick: every class has at
+// least rt members in the shard, hence rt consecutive positions span at most two classes.
+__host__ __device__ inline bool heading_rows_shared(const DevTick& k) {
+  return k.list_mode == 0 && k.fixed_steps > 0 && k.n_local > 0 && k.nth > 0 && k.rt > 0 && k.n_local / k.nth >= k.rt;
+}
+
+// Position `pos` of the class-major order of a shard [begin, begin + n_local): all members of class 0 in ascending li,
+// then class 1, ...  Class c's first member is li = (c - begin % nth + nth) % nth, the next ones follow at stride nth;
+// with q = n_local / nth and r = n_local % nth the r classes begin % nth, ... (cyclically) have q + 1 members, the
+// others q.  Along the classes those sizes form at most three runs (a, b, a), which gives the position's class in one
+// division.  Any begin >= 0, n_local > 0, nth > 0 and 0 <= pos < n_local; a permutation of [0, n_local).
+struct ClassPos { int cls, member, li; };
+__host__ __device__ inline ClassPos class_major_position(int begin, int n_local, int nth, int pos) {
+  const int b0 = begin % nth, q = n_local / nth, r = n_local % nth;
+  const bool wrap = b0 + r > nth;                     // the classes with q + 1 members run over the end of the axis
+  const int s1 = wrap ? b0 + r - nth : b0, s2 = wrap ? b0 : b0 + r;
+  const int a = wrap ? q + 1 : q, b = wrap ? q : q + 1;
+  const int p1 = s1 * a, p2 = p1 + (s2 - s1) * b;
+  ClassPos cp;
+  if (pos < p1) { cp.cls = pos / a; cp.member = pos - cp.cls * a; }
+  else if (pos < p2) { const int d = (pos - p1) / b; cp.cls = s1 + d; cp.member = pos - p1 - d * b; }
+  else { const int d = (pos - p2) / a; cp.cls = s2 + d; cp.member = pos - p2 - d * a; }
+  cp.li = (cp.cls - b0 + nth) % nth + cp.member * nth;
+  return cp;
+}
+
+// Dynamic LDS of the class rows, beyond rollout_lds_bytes(): two rows of (cos, sin) per step, and for omni two more of
+// cos / sin(pi/2 + theta).
+__host__ __device__ inline size_t heading_rows_lds_bytes(int max_steps, bool omni) {
+  return (size_t)2 * (size_t)(max_steps + 1) * (omni ? 32 : 16);
+}
+
 // Load feedback: every tick k_score files what each trajectory cost it (collision
 // work items actually walked, path-critic work, pairs); the next tick's assignment
 // block (rides along with k_bin_count, like the rollout) deals the trajectories to
@@ -443,6 +479,10 @@ __global__ __launch_bounds__(256) void k_bin_scatter(DevTick k, const float4* __
 //   C  one lane per trajectory: x,y running sum p <- float(double(p) + inc)
 // Output per (trajectory, step): body-frame x,y after the step (float2) and
 // cos/sin of the heading after the step (double2, the pose's AngleAxisd rotation).
+// With shared heading rows (heading_rows_shared(), the BASELINE shapes) the workgroups take the shard in class-major
+// order: A runs the theta chain and B the sin/cos once per (class, step), at most two classes a workgroup, every pair
+// forms its increment from its class's row, and st_sc holds one row per class instead of one per trajectory
+// (TrajInfo::hrow names a trajectory's row either way).
 // ---------------------------------------------------------------------------
 #ifdef DDDMR_PHASE_STAMPS
 constexpr int kStampSlots = 20;      // 0..11 s_memtime per phase, 12 / 13 s_memrealtime (100 MHz, chip-wide) at start / end, 14 XCC | CU id, 15..18 the last workgroup's hand-off
@@ -486,7 +526,7 @@ struct TrajInfo {      // per trajectory, 32 bytes
   int steps;           // 0 = not generated
   double dt;
   int over;            // step count exceeded the context's max_steps (capacity error)
-  int pad;
+  int hrow;            // row of st_sc with its headings: the trajectory's own, or with shared heading rows its angular sample's
 };
 
 __host__ __device__ inline size_t rollout_lds_bytes(int rt, int max_steps) {
@@ -497,7 +537,7 @@ template <int kThreads>
 __device__ __forceinline__ void rollout_block(const DevTick& k, const int block, const float* __restrict__ axes,
                                               const float4* __restrict__ samples, TrajInfo* __restrict__ info,
                                               double2* __restrict__ st_sc, float2* __restrict__ st_xy,
-                                              unsigned char* roll_lds) {
+                                              unsigned char* roll_lds, const bool shared) {
   const int S1 = k.max_steps + 1;
   const int rt = k.rt;
   // [rt][S1] slots of 16 bytes.  Phase A leaves theta_s in ONE float of the slot, phase B (the lane that read it)
@@ -508,15 +548,38 @@ __device__ __forceinline__ void rollout_block(const DevTick& k, const int block,
   __shared__ int steps_s[kRolloutMax];
   __shared__ float vel_s[kRolloutMax][3];
   __shared__ double dt_s[kRolloutMax];
+  __shared__ int li_s[kRolloutMax];                   // local trajectory of row j
+  __shared__ unsigned char lc_s[kRolloutMax];         // shared mode: which of the workgroup's class rows it reads
   const int tid = threadIdx.x;
-  const int l0 = block * rt;                          // first local trajectory of this workgroup
-  const int nt = min(rt, k.n_local - l0);
+  const int l0 = block * rt;                          // first local trajectory of this workgroup (shared mode: first
+  const int nt = min(rt, k.n_local - l0);             //   position of the class-major order, see class_major_position())
   const bool omni = (k.kind == DDDMR_THEORY_OMNI_SIMPLE);
+  // Shared mode (heading_rows_shared(k), decided by the launch stage): the workgroup's positions span the classes
+  // c0 .. c0 + ncls - 1, ncls <= 2; their heading rows live behind the [rt][S1] slots, (cos, sin) first, then omni's
+  // quarter-ahead pair.  Every generated trajectory of such a tick has fixed_steps steps.
+  double2* hrow = reinterpret_cast<double2*>(roll_lds + rollout_lds_bytes(rt, k.max_steps));
+  double2* qrow = hrow + 2 * S1;
+  const int ns_row = k.fixed_steps <= k.max_steps ? k.fixed_steps : 0;
+  int c0 = 0, ncls = 0;
+  bool owns_row0 = false;       // the workgroup that holds a class's first member writes its row of st_sc
+  if (shared) {
+    const ClassPos first = class_major_position(k.begin, k.n_local, k.nth, l0);
+    c0 = first.cls;
+    owns_row0 = first.member == 0;
+    ncls = class_major_position(k.begin, k.n_local, k.nth, l0 + nt - 1).cls - c0 + 1;
+  }
   DDDMR_RSTAMP(0);
 
   // ---- phase A ----
   if (tid < nt) {
-    const int li = l0 + tid;
+    int li = l0 + tid, lc = 0;
+    bool heads_row = false;                           // shared mode: this lane runs the theta chain of its class
+    if (shared) {
+      const ClassPos cp = class_major_position(k.begin, k.n_local, k.nth, l0 + tid);
+      li = cp.li;
+      lc = cp.cls - c0;
+      heads_row = tid == 0 || cp.member == 0;
+    }
     const int gi = k.begin + li;
     float vx, vy, w;
     if (k.list_mode) {
@@ -581,19 +644,34 @@ __device__ __forceinline__ void rollout_block(const DevTick& k, const int block,
     ti.steps = ns;
     ti.dt = dt;
     ti.over = over;
-    ti.pad = 0;
+    ti.hrow = shared ? c0 + lc : li;
     info[li] = ti;
     steps_s[tid] = ns;
     vel_s[tid][0] = vx; vel_s[tid][1] = vy; vel_s[tid][2] = w;
     dt_s[tid] = dt;
+    li_s[tid] = li;
+    lc_s[tid] = (unsigned char)lc;
     // theta_{k+1} = float(theta_k + w*dt)   (computeNewPositions, dd_simple...cpp:457-464)
-    float* row = reinterpret_cast<float*>(inc + (size_t)tid * S1) + ((tid >> 4) & 3);
-    float a = 0.f;
-    row[0] = 0.f;
-    const double wdt = (double)w * dt;
-    for (int s = 1; s <= ns; ++s) {
-      a = (float)((double)a + wdt);
-      row[4 * s] = a;
+    if (!shared) {
+      float* row = reinterpret_cast<float*>(inc + (size_t)tid * S1) + ((tid >> 4) & 3);
+      float a = 0.f;
+      row[0] = 0.f;
+      const double wdt = (double)w * dt;
+      for (int s = 1; s <= ns; ++s) {
+        a = (float)((double)a + wdt);
+        row[4 * s] = a;
+      }
+    } else if (heads_row) {
+      // the class's chain, from the dt every generated member computes above (this lane's own trajectory may be gated)
+      const double dt_row = ns_row > 0 ? sim_time / (double)ns_row : 0.0;
+      float* row = reinterpret_cast<float*>(hrow + (size_t)lc * S1);
+      float a = 0.f;
+      row[0] = 0.f;
+      const double wdt = (double)w * dt_row;
+      for (int s = 1; s <= ns_row; ++s) {
+        a = (float)((double)a + wdt);
+        row[4 * s] = a;
+      }
     }
   }
   __syncthreads();
@@ -603,7 +681,51 @@ __device__ __forceinline__ void rollout_block(const DevTick& k, const int block,
   // (j, s) of a lane's items advance by a fixed stride: one integer division per lane, not one per item
   const int stride_j = kThreads / S1, stride_s = kThreads - stride_j * S1;
   int bj = tid / S1, bs = tid - bj * S1;
-  for (int idx = tid; idx < nt * S1; idx += kThreads) {
+  if (shared) {
+    // the rows: one sincos per (class, step) ...
+    for (int idx = tid; idx < ncls * S1; idx += kThreads) {
+      const int s = idx >= S1 ? idx - S1 : idx;
+      if (s <= ns_row) {
+        const double ang = (double)*reinterpret_cast<const float*>(hrow + idx);
+        double sn, cs;
+        sincos_heading(ang, &sn, &cs);
+        hrow[idx] = make_double2(cs, sn);
+        // heading after step s-1 = theta_s: the pose's rotation (dd_simple...cpp:416), one row of st_sc per class
+        if (s >= 1 && (idx >= S1 || owns_row0)) st_sc[(size_t)(c0 + (idx >= S1 ? 1 : 0)) * k.max_steps + (s - 1)] = make_double2(cs, sn);
+        if (omni) {
+          double s2, c2;
+          sincos_quarter_ahead(ang, sn, cs, &s2, &c2);   // cos/sin(M_PI_2 + theta), omni_simple...cpp:501-502
+          qrow[idx] = make_double2(c2, s2);
+        }
+      }
+    }
+    __syncthreads();
+    // ... then every pair forms its increment from its class's row, by the operations of the loop below
+    for (int idx = tid; idx < nt * S1; idx += kThreads) {
+      const int j = bj, s = bs;
+      bj += stride_j;
+      bs += stride_s;
+      if (bs >= S1) { bs -= S1; ++bj; }
+      const int ns = steps_s[j];
+      if (s <= ns && ns > 0) {
+        const int r = (int)lc_s[j] * S1 + s;
+        const double2 h = hrow[r];
+        const double cs = h.x, sn = h.y;
+        if (s < ns) {
+          const float vx = vel_s[j][0], vy = vel_s[j][1];
+          const float cf = (float)cs, sf = (float)sn;
+          double ix = (double)fmul(vx, cf), iy = (double)fmul(vx, sf);
+          if (omni) {
+            const double2 q = qrow[r];
+            ix += (double)vy * q.x;
+            iy += (double)vy * q.y;
+          }
+          inc[idx] = make_double2(ix * dt_s[j], iy * dt_s[j]);
+        }
+      }
+    }
+  }
+  for (int idx = tid; !shared && idx < nt * S1; idx += kThreads) {      // a sincos per pair
     const int j = bj, s = bs;
     bj += stride_j;
     bs += stride_s;
@@ -668,7 +790,7 @@ __device__ __forceinline__ void rollout_block(const DevTick& k, const int block,
     if (bs >= S1) { bs -= S1; ++bj; }
     if (s < steps_s[j]) {
       const float* slot = reinterpret_cast<const float*>(inc + idx);
-      st_xy[(size_t)(l0 + j) * k.max_steps + s] = make_float2(slot[0], slot[2]);
+      st_xy[(size_t)li_s[j] * k.max_steps + s] = make_float2(slot[0], slot[2]);
     }
   }
   DDDMR_RSTAMP(3);
@@ -783,9 +905,9 @@ __global__ __launch_bounds__(kBinThreads) void k_assign(DevTick k, const uint32_
 __global__ __launch_bounds__(256) void k_rollout(DevTick k, const float* __restrict__ axes,
                                                  const float4* __restrict__ samples,
                                                  TrajInfo* __restrict__ info, double2* __restrict__ st_sc,
-                                                 float2* __restrict__ st_xy) {
+                                                 float2* __restrict__ st_xy, const int heading_rows) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
-  rollout_block<256>(k, (int)blockIdx.x, axes, samples, info, st_sc, st_xy, dyn_lds);
+  rollout_block<256>(k, (int)blockIdx.x, axes, samples, info, st_sc, st_xy, dyn_lds, heading_rows != 0);
 }
 
 // Crop the cloud to the local costmap tile and count points per cell; the LAST
@@ -803,7 +925,8 @@ __global__ __launch_bounds__(kBinThreads, 8) void k_bin_count(DevTick k, const f
                                                    uint32_t* __restrict__ overflow, const float* __restrict__ axes,
                                                    const float4* __restrict__ samples, TrajInfo* __restrict__ info,
                                                    double2* __restrict__ st_sc, float2* __restrict__ st_xy,
-                                                   const uint32_t* __restrict__ load, uint32_t* __restrict__ assign) {
+                                                   const uint32_t* __restrict__ load, uint32_t* __restrict__ assign,
+                                                   const int heading_rows) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
   // Longest first: the assignment workgroups (only launched with use_assign), the rollout, then the binning
   // workgroups -- when the launch does not fit the chip in one round, the short ones fill the tail.
@@ -813,7 +936,7 @@ __global__ __launch_bounds__(kBinThreads, 8) void k_bin_count(DevTick k, const f
     return;
   }
   if ((int)blockIdx.x < n_assign + k.roll_blocks) {
-    rollout_block<kBinThreads>(k, (int)blockIdx.x - n_assign, axes, samples, info, st_sc, st_xy, dyn_lds);
+    rollout_block<kBinThreads>(k, (int)blockIdx.x - n_assign, axes, samples, info, st_sc, st_xy, dyn_lds, heading_rows != 0);
     return;
   }
   const int bin_block = (int)blockIdx.x - n_assign - k.roll_blocks;
@@ -902,7 +1025,7 @@ struct TrajHead {     // per-trajectory header in LDS
   int pair_base;      // first flattened (traj,step) pair of this trajectory
   int hit_box;        // CollisionModel verdict
   int hit_mm;         // CollisionMinMaxModel verdict
-  int pad;
+  int aux;            // TrajInfo::hrow (row of st_sc) through phase D1 and pure pursuit; from phase P on the first surviving pair
   double pp_dist;     // PurePursuitModel: |translation| of the pose difference
   double pp_yaw;      // PurePursuitModel: folded yaw of the pose difference
   double stick_sum;   // StickPathModel: sum of the per-step 1-NN distances
@@ -1363,7 +1486,7 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
     h.steps = ti.steps;
     h.dt = ti.dt;
     h.pair_base = 0;
-    h.hit_box = 0; h.hit_mm = 0; h.pad = 0;
+    h.hit_box = 0; h.hit_mm = 0; h.aux = ti.hrow;
     h.pp_dist = 0.0; h.pp_yaw = 0.0; h.stick_sum = 0.0;
     h.li = li;
     h.walked = 0;
@@ -1396,7 +1519,7 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
     while (j + 1 < nt && head[j + 1].pair_base <= q) ++j;
     const int s = q - head[j].pair_base;
     const size_t so = (size_t)head[j].li * k.max_steps + s;
-    const double2 cs = st_sc[so];                    // heading after the step
+    const double2 cs = st_sc[(size_t)head[j].aux * k.max_steps + s];   // heading after the step
     const float2 bxy = st_xy[so];                    // body-frame position after the step
     const double c = cs.x, sn = cs.y;
     // trans_gbl2traj = pos_af3 * [Rz(theta), (x, y, 0)]
@@ -1558,7 +1681,7 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
   if (tid < nt && head[tid].steps > 0) {
     const int j = tid;
     const size_t so = (size_t)head[j].li * k.max_steps + (head[j].steps - 1);
-    const double2 cs = st_sc[so];
+    const double2 cs = st_sc[(size_t)head[j].aux * k.max_steps + (head[j].steps - 1)];
     const float2 bxy = st_xy[so];
     const double c = cs.x, sn = cs.y;
     double L[9], T[3];
@@ -1800,7 +1923,7 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
       st = dead ? 0u : (uint32_t)head[tid].steps;
     }
     const uint32_t incl = wave_incl_scan_u32(st);
-    if (tid < nt) head[tid].pad = (int)(incl - st);         // first surviving pair of trajectory tid
+    if (tid < nt) head[tid].aux = (int)(incl - st);         // first surviving pair of trajectory tid
     if (tid == max(nt, 1) - 1) alive_pairs_s = nt > 0 ? (int)incl : 0;
   }
   __syncthreads();
@@ -1819,8 +1942,8 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
       int j = 0, s = 0;
       float px = 0.f, py = 0.f, pz = 0.f;
       if (valid) {
-        while (j + 1 < nt && head[j + 1].pad <= q2) ++j;    // (dead trajectories have empty ranges)
-        s = q2 - head[j].pad;
+        while (j + 1 < nt && head[j + 1].aux <= q2) ++j;    // (dead trajectories have empty ranges)
+        s = q2 - head[j].aux;
         const float4 pp = ppos[head[j].pair_base + s];    // the pose D1 composed for this pair
         px = pp.x; py = pp.y; pz = pp.z;
       }
@@ -2242,12 +2365,13 @@ __global__ void k_trajectory_poses(DevTick k, int li, const float4* __restrict__
 // the first output pose of trajectory li, or -1 when it is not wanted.
 __global__ __launch_bounds__(256) void k_pose_arrays(DevTick k, const int32_t* __restrict__ off,
                                                      const int32_t* __restrict__ steps,
+                                                     const TrajInfo* __restrict__ info,
                                                      const double2* __restrict__ st_sc, const float2* __restrict__ st_xy,
                                                      double* __restrict__ poses) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int li = (int)(idx / (size_t)k.max_steps), s = (int)(idx % (size_t)k.max_steps);
   if (li >= k.n_local || s >= steps[li] || off[li] < 0) return;
-  const double2 cs = st_sc[idx];
+  const double2 cs = st_sc[(size_t)info[li].hrow * k.max_steps + s];
   const float2 bxy = st_xy[idx];
   double L[9], T[3];
   for (int i = 0; i < 3; ++i) {

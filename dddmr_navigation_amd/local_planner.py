@@ -599,6 +599,11 @@ class LocalPlanner:
                                                             C.byref(n)))
         return out[: n.value]
 
+    def heading_rows(self) -> int:
+        """1 if the last launched tick shared one row of headings per angular sample, 0 if every trajectory ran its
+        own chain, -1 before any tick (dddmr_rollout_heading_rows)."""
+        return int(self._lib.dddmr_rollout_heading_rows(self._ctx))
+
     def best_poses(self) -> np.ndarray:
         n = C.c_size_t(0)
         self._check(self._lib.dddmr_rollout_get_best_poses(self._ctx, None, 0, C.byref(n)))

@@ -834,6 +834,12 @@ int dddmr_rollout_comm_loopback_set_peer(dddmr_rollout_ctx* ctx, int32_t peer_ra
 /* Per-trajectory outputs of the last tick (any pointer may be NULL). */
 int dddmr_rollout_get_debug(dddmr_rollout_ctx* ctx, dddmr_rollout_debug* dbg);
 
+/* How the last launched tick rolled its headings out: 1 one row of headings per angular sample, shared by the
+   sample's trajectories (grid ticks with a fixed step count whose shard holds enough members of every angular
+   sample; DDDMR_HEADING_ROWS=0 at create switches it off), 0 a heading chain per trajectory, -1 before any tick.
+   Both give the same bits; tests use this to know which path they compared. */
+int dddmr_rollout_heading_rows(dddmr_rollout_ctx* ctx);
+
 /* Debug pose arrays of the last tick, poses_out[n][7] x y z qx qy qz qw, trajectory by
    trajectory in sample order, poses in step order: which = 0 the `trajectory` topic
    (every generated trajectory, local_planner.cpp:549-569), which = 1 the
