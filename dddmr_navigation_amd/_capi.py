@@ -296,6 +296,25 @@ class MclStats(C.Structure):
     ]
 
 
+class MclObservationConfig(C.Structure):
+    """dddmr_mcl_observation_config: cbLeGoFeatureCloud's two parameters (mcl_3dl.yaml) and the input capacities."""
+    _fields_ = [
+        ("euc_cluster_distance", C.c_double), ("euc_cluster_min_size", C.c_int32),
+        ("max_flat_points", C.c_uint32), ("max_less_sharp_points", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+    ]
+
+
+class MclObservationStats(C.Structure):
+    _fields_ = [
+        ("n_flat_in", C.c_uint32), ("n_flat_out", C.c_uint32), ("n_less_sharp_in", C.c_uint32), ("n_less_sharp_out", C.c_uint32),
+        ("branch", C.c_uint32), ("n_clusters", C.c_uint32), ("n_small_clusters", C.c_uint32), ("n_nan_normals", C.c_uint32),
+        ("sum_normal_x", C.c_double), ("sum_normal_y", C.c_double), ("launches", C.c_uint32), ("host_waits", C.c_uint32),
+    ]
+
+
+MCL_BRANCH_CLUSTERS, MCL_BRANCH_X_DOMINANT, MCL_BRANCH_Y_DOMINANT = 0, 1, 2
+
+
 # dddmr_rollout_depth_clear_verdicts: bit 0 of a verdict = kept, bits 1-2 = the branch that decided
 DEPTH_CLEAR_KEPT = 1
 DEPTH_CLEAR_OUTSIDE, DEPTH_CLEAR_ATTACHED, DEPTH_CLEAR_INSIDE = 1, 2, 3
@@ -388,6 +407,11 @@ EXPORTED_SYMBOLS = (
     "dddmr_rollout_mcl_set_map",
     "dddmr_rollout_mcl_measure",
     "dddmr_rollout_mcl_get_terms",
+    "dddmr_rollout_mcl_set_observation_config",
+    "dddmr_rollout_mcl_prepare",
+    "dddmr_rollout_mcl_prepare_from_sweep",
+    "dddmr_rollout_mcl_get_observation",
+    "dddmr_rollout_mcl_measure_prepared",
     "dddmr_rollout_stream_ceiling",
     "dddmr_rollout_selftest_sincos",
     "dddmr_rollout_last_error",
@@ -600,6 +624,19 @@ def load_library() -> C.CDLL:
         lib.dddmr_rollout_mcl_measure.restype = C.c_int
         lib.dddmr_rollout_mcl_get_terms.argtypes = [ctx_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         lib.dddmr_rollout_mcl_get_terms.restype = C.c_int
+    if hasattr(lib, "dddmr_rollout_mcl_prepare"):
+        lib.dddmr_rollout_mcl_set_observation_config.argtypes = [ctx_p, C.POINTER(MclObservationConfig)]
+        lib.dddmr_rollout_mcl_set_observation_config.restype = C.c_int
+        lib.dddmr_rollout_mcl_prepare.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                  C.POINTER(C.c_double), C.POINTER(MclObservationStats)]
+        lib.dddmr_rollout_mcl_prepare.restype = C.c_int
+        lib.dddmr_rollout_mcl_prepare_from_sweep.argtypes = [ctx_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(MclObservationStats)]
+        lib.dddmr_rollout_mcl_prepare_from_sweep.restype = C.c_int
+        lib.dddmr_rollout_mcl_get_observation.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t,
+                                                          C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t]
+        lib.dddmr_rollout_mcl_get_observation.restype = C.c_int
+        lib.dddmr_rollout_mcl_measure_prepared.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(MclStats)]
+        lib.dddmr_rollout_mcl_measure_prepared.restype = C.c_int
     lib.dddmr_rollout_stream_ceiling.argtypes = [ctx_p, C.c_size_t, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.dddmr_rollout_stream_ceiling.restype = C.c_int
     lib.dddmr_rollout_selftest_sincos.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]

@@ -326,6 +326,9 @@ __global__ __launch_bounds__(256) void k_mcl_finish(MclParams k, MclTerms t, con
 // ---- host (included by rollout_engine.hip after marking_host.hip.h, whose grid builder this uses) -------------------
 namespace {
 
+struct MclObs;                             // the prepared observation, mcl_observation.hip.h
+void mclobs_free(MclObs* o);
+
 struct MclMap {                            // one swapKdTree generation
   GridBuf map, ground;
   float4 *map_pts = nullptr, *ground_pts = nullptr, *normals = nullptr;
@@ -349,10 +352,12 @@ struct MclState {
   MclResult *res_host = nullptr, *res_dev = nullptr;
   uint32_t seq = 0;
   uint32_t last_n = 0;                     // particles of the last successful measure (get_terms)
+  MclObs* obs = nullptr;                   // dddmr_rollout_mcl_set_observation_config
 };
 
 void mcl_free(MclState* s) {
   if (!s) return;
+  mclobs_free(s->obs);
   dev_free(s->mem);
   if (s->obs_host) (void)hipHostFree(s->obs_host);
   if (s->states_host) (void)hipHostFree(s->states_host);
@@ -433,6 +438,56 @@ bool mcl_cloud_ok(const float* xyz, size_t n, size_t stride_bytes) {
   for (int a = 0; a < 3; ++a)
     if (!(hi[a] - lo[a] <= kMclMaxExtent)) return false;
   return true;
+}
+
+// One measure over an observation the device can read (k_mcl_match's layout): the host-mapped staging of
+// dddmr_rollout_mcl_measure, or the prepared observation of mcl_observation.hip.h.  tick_mu held.
+int mcl_run(dddmr_rollout_ctx* ctx, const char* what, MclState* s, const float4* obs_dev, size_t n_flat, size_t n_less_sharp, const float* states,
+            size_t n_states, float* likelihood_out, float* quality_out, dddmr_mcl_stats* stats) {
+  if (s->cur < 0) return fail(ctx, DDDMR_ERR_STATE, "%s before mcl_set_map", what);
+  if (n_states > s->cfg.max_particles)
+    return fail(ctx, DDDMR_ERR_CAPACITY, "%s: %zu particles, capacity %u", what, n_states, s->cfg.max_particles);
+  if (n_states == 0) {
+    if (stats) { stats->quality_min = 1.0f; stats->quality_max = 0.0f; }
+    s->last_n = 0;
+    return DDDMR_OK;
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::memcpy(s->states_host, states, n_states * 7 * sizeof(float));
+  MclParams k = s->k;
+  k.n_flat = (uint32_t)n_flat;
+  k.n_ls = (uint32_t)n_less_sharp;
+  k.n_states = (uint32_t)n_states;
+  const MclMap& m = s->maps[s->cur];
+  const uint32_t n_obs = k.n_flat + k.n_ls, N = k.n_states;
+  const uint32_t seq = ++s->seq ? s->seq : ++s->seq;
+  hipStream_t st = ctx->stream;
+  hipLaunchKernelGGL(k_mcl_ground, dim3(N), dim3(64), 0, st, k, m.ground.g, m.map.g, m.normals, s->states_dev, s->t);
+  const uint32_t blocks = std::min<uint32_t>((N + 3) / 4, 2048u);
+  hipLaunchKernelGGL(k_mcl_match, dim3(blocks), dim3(256), (size_t)n_obs * 32, st, k, m.ground.g, m.map.g, obs_dev, s->states_dev, s->t,
+                     s->qual_dev, s->out_dev, s->out_dev + s->cfg.max_particles);
+  hipLaunchKernelGGL(k_mcl_finish, dim3(1), dim3(256), 0, st, k, s->t, s->qual_dev, s->res_dev, seq);
+  HIPCHK(ctx, hipGetLastError());
+  uint32_t waits = 1;                                  // the spin on the result word
+  if (!wait_seq(&s->res_host->seq, seq)) {             // not seen within the spin's bound: wait for the stream instead
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    ++waits;
+  }
+  const MclResult r = *s->res_host;
+  if (stats) {
+    stats->quality_min = r.q_min; stats->quality_max = r.q_max;
+    stats->n_bad_states = r.n_bad; stats->n_over_capacity = r.n_over; stats->max_ground_neighbours_seen = r.max_ground;
+    stats->launches = 3; stats->host_waits = waits;
+  }
+  if (r.n_over) {
+    s->last_n = 0;
+    return fail(ctx, DDDMR_ERR_CAPACITY, "%s: %u particles with more than max_ground_neighbours %u ground points inside the radius (up to %u)",
+                what, r.n_over, s->cfg.max_ground_neighbours, r.max_ground);
+  }
+  std::memcpy(likelihood_out, s->out_host, n_states * sizeof(float));
+  std::memcpy(quality_out, s->out_host + s->cfg.max_particles, n_states * sizeof(float));
+  s->last_n = N;
+  return DDDMR_OK;
 }
 
 }  // namespace
@@ -518,53 +573,15 @@ int dddmr_rollout_mcl_measure(dddmr_rollout_ctx* ctx, const float* flat_xyz, siz
   MclState* s = ctx->mcl;
   if (!s) return fail(ctx, DDDMR_ERR_STATE, "mcl_measure before mcl_create");
   if (s->cur < 0) return fail(ctx, DDDMR_ERR_STATE, "mcl_measure before mcl_set_map");
-  if (n_states > s->cfg.max_particles || n_flat > s->cfg.max_observation_points || n_less_sharp > s->cfg.max_observation_points ||
-      n_flat + n_less_sharp > s->cfg.max_observation_points)
+  if (n_flat > s->cfg.max_observation_points || n_less_sharp > s->cfg.max_observation_points ||
+      n_flat + n_less_sharp > s->cfg.max_observation_points || n_states > s->cfg.max_particles)
     return fail(ctx, DDDMR_ERR_CAPACITY, "mcl_measure: %zu particles, %zu + %zu observation points, capacity %u / %u", n_states, n_flat,
                 n_less_sharp, s->cfg.max_particles, s->cfg.max_observation_points);
-  if (n_states == 0) {
-    if (stats) { stats->quality_min = 1.0f; stats->quality_max = 0.0f; }
-    s->last_n = 0;
-    return DDDMR_OK;
+  if (n_states) {                                      // (without a particle nothing is read)
+    for (size_t i = 0; i < n_flat; ++i) s->obs_host[i] = make_float4(flat_xyz[3 * i], flat_xyz[3 * i + 1], flat_xyz[3 * i + 2], 1.0f);
+    if (n_less_sharp) std::memcpy(s->obs_host + n_flat, less_sharp_xyzi, n_less_sharp * sizeof(float4));
   }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  for (size_t i = 0; i < n_flat; ++i) s->obs_host[i] = make_float4(flat_xyz[3 * i], flat_xyz[3 * i + 1], flat_xyz[3 * i + 2], 1.0f);
-  if (n_less_sharp) std::memcpy(s->obs_host + n_flat, less_sharp_xyzi, n_less_sharp * sizeof(float4));
-  std::memcpy(s->states_host, states, n_states * 7 * sizeof(float));
-  MclParams k = s->k;
-  k.n_flat = (uint32_t)n_flat;
-  k.n_ls = (uint32_t)n_less_sharp;
-  k.n_states = (uint32_t)n_states;
-  const MclMap& m = s->maps[s->cur];
-  const uint32_t n_obs = k.n_flat + k.n_ls, N = k.n_states;
-  const uint32_t seq = ++s->seq ? s->seq : ++s->seq;
-  hipStream_t st = ctx->stream;
-  hipLaunchKernelGGL(k_mcl_ground, dim3(N), dim3(64), 0, st, k, m.ground.g, m.map.g, m.normals, s->states_dev, s->t);
-  const uint32_t blocks = std::min<uint32_t>((N + 3) / 4, 2048u);
-  hipLaunchKernelGGL(k_mcl_match, dim3(blocks), dim3(256), (size_t)n_obs * 32, st, k, m.ground.g, m.map.g, s->obs_dev, s->states_dev, s->t,
-                     s->qual_dev, s->out_dev, s->out_dev + s->cfg.max_particles);
-  hipLaunchKernelGGL(k_mcl_finish, dim3(1), dim3(256), 0, st, k, s->t, s->qual_dev, s->res_dev, seq);
-  HIPCHK(ctx, hipGetLastError());
-  uint32_t waits = 1;                                  // the spin on the result word
-  if (!wait_seq(&s->res_host->seq, seq)) {             // not seen within the spin's bound: wait for the stream instead
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    ++waits;
-  }
-  const MclResult r = *s->res_host;
-  if (stats) {
-    stats->quality_min = r.q_min; stats->quality_max = r.q_max;
-    stats->n_bad_states = r.n_bad; stats->n_over_capacity = r.n_over; stats->max_ground_neighbours_seen = r.max_ground;
-    stats->launches = 3; stats->host_waits = waits;
-  }
-  if (r.n_over) {
-    s->last_n = 0;
-    return fail(ctx, DDDMR_ERR_CAPACITY, "mcl_measure: %u particles with more than max_ground_neighbours %u ground points inside the radius (up to %u)",
-                r.n_over, s->cfg.max_ground_neighbours, r.max_ground);
-  }
-  std::memcpy(likelihood_out, s->out_host, n_states * sizeof(float));
-  std::memcpy(quality_out, s->out_host + s->cfg.max_particles, n_states * sizeof(float));
-  s->last_n = N;
-  return DDDMR_OK;
+  return mcl_run(ctx, "mcl_measure", s, s->obs_dev, n_flat, n_less_sharp, states, n_states, likelihood_out, quality_out, stats);
 }
 
 int dddmr_rollout_mcl_get_terms(dddmr_rollout_ctx* ctx, float* score_like_out, float* pos_weight_out, uint32_t* n_match_out,

@@ -295,6 +295,8 @@ size_t dddmr_rollout_sizeof(int which) {
     case 18: return sizeof(dddmr_mcl_config);
     case 19: return sizeof(dddmr_mcl_stats);
     case 20: return sizeof(dddmr_lidar_features_config);
+    case 21: return sizeof(dddmr_mcl_observation_config);
+    case 22: return sizeof(dddmr_mcl_observation_stats);
     default: return 0;
   }
 }
@@ -1343,3 +1345,4 @@ int dddmr_rollout_get_best_cuboids(dddmr_rollout_ctx* ctx, float* vertices_out, 
 #include "depth_layer.hip.h"
 #include "perception_stack.hip.h"
 #include "mcl_measure.hip.h"
+#include "mcl_observation.hip.h"

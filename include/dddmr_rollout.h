@@ -470,7 +470,8 @@ int dddmr_rollout_get_lidar_sweep_image(dddmr_rollout_ctx* ctx, int32_t source_i
    point at segment index 0 is ring 0's first flat pick unless it is occlusion-marked.  Equal curvatures sort by
    ascending index (std::sort leaves their order undefined).  The relTime part of the intensity and findStartEndAngle
    are left out (mcl_3dl overwrites or ignores the intensity).  Sharp, less sharp and flat are produced; less flat is
-   not.  What cbLeGoFeatureCloud does with the lists (VoxelGrid, normals, clusters) stays with the host.
+   not.  What cbLeGoFeatureCloud does with the lists (VoxelGrid, normals, clusters) is dddmr_rollout_mcl_prepare_from_sweep,
+   which reads them where they lie.
 
    The features are part of the sweep's double-buffered result: built beside the current one and swapped in only when
    the aggregate accepted the sweep, so after a refused sweep the getters return the previous sweep's.  cfg == NULL
@@ -1043,7 +1044,8 @@ int dddmr_rollout_stack_reset(dddmr_rollout_ctx* ctx);
 /* ---- Particle filter lidar likelihood: mcl_3dl's LidarMeasurementModelLikelihood::measure for a batch of particles ----
    (dddmr_mcl_3dl/src/lidar_measurement_model_likelihood.cpp:86-252, called once per particle by pf_->measure,
    src/mcl_3dl.cpp:466-503).  The one function of the localiser that is a batch kernel; motion prediction, bias,
-   resampling, weight normalisation, sub-map loading and the segmentation of the observation stay on the host.
+   resampling, weight normalisation and sub-map loading stay on the host; the preparation of the observation
+   (cbLeGoFeatureCloud) is the block after this one.
 
    dddmr_rollout_mcl_create takes the model's parameters (likelihood.match_dist_min / match_dist_flat /
    radius_of_ground_search / threshold_for_trusted_ground) and the capacities.  DDDMR_ERR_BAD_ARG: a distance that is
@@ -1104,6 +1106,82 @@ int dddmr_rollout_mcl_measure(dddmr_rollout_ctx* ctx, const float* flat_xyz, siz
                               float* quality_out, dddmr_mcl_stats* stats);
 int dddmr_rollout_mcl_get_terms(dddmr_rollout_ctx* ctx, float* score_like_out, float* pos_weight_out, uint32_t* n_match_out,
                                 uint32_t* n_ground_out, uint8_t* healthy_out, size_t capacity);
+
+/* ---- The localiser's observation: mcl_3dl's MCL3dlNode::cbLeGoFeatureCloud on the device (additions to ABI version 2;
+   no existing struct or entry changes; a context that never configures the observation runs exactly the launches it
+   ran before).  src/dddmr_mcl_3dl/src/mcl_3dl.cpp:263-464 turns a sweep's flat and less-sharp lists into the two clouds
+   measure() takes; line numbers below are that file's.  T_b2s is trans_b2s_af3 (base_link <- sensor), row-major 3 x 4,
+   computed by the caller.  Float where the reference is float, double where it is double, nothing fused:
+     transform (:295-296)       pcl::transformPointCloud(Affine3d) on both lists: double multiply-add, float result.
+     flat (:306-309)            VoxelGrid with leaf (1.0f, 1.0f, 0.1f): voxel = floor(p * inverse_leaf) - min_b with the
+                                inverse per axis in float, output in voxel-index order (x fastest), centroid = float
+                                running sum in input order / count.  Only x y z go on.
+     normals (:320-329)         NormalEstimation, setKSearch(5), on the transformed less-sharp cloud itself: the 5 nearest
+                                by FLANN's float L2_Simple, the point included, ties by (d2, index); all of them when
+                                there are fewer than 5; fewer than 3 give a NaN normal; float mean and covariance about
+                                the first neighbour; PCL's closed-form eigen33; flipped toward (0, 0, 0).  Restated from
+                                memory of PCL 1.15: DESIGN.md 4e numbers the assumptions.
+     dominance (:340-360)       two double sums of fabs(normal_y) and fabs(normal_x) in index order, each component
+                                skipped on its own when NaN; x dominant when sx / sy >= 1.6, else y dominant when
+                                sy / sx >= 1.6 (0 / 0 selects neither: an empty list takes the cluster branch).
+     dominant branch (:362-403) every point in input order; intensity 1.0f when normal_x is NaN, else float(0.05 * sy /
+                                sx) (x dominant; y dominant mirrored) when the float ratio normal_y / normal_x >= 0.5,
+                                else 1.0f.
+     cluster branch (:404-443)  EuclideanClusterExtraction(euc_cluster_distance, euc_cluster_min_size, N): strict float
+                                d2 < float(tol * tol), clusters in order of their lowest index, indices ascending, a
+                                cluster below the minimum is dropped WITH its points, the kept ones ordered by
+                                libstdc++'s std::sort(rbegin, rend) on the size (replayed on the host: the prepare's one
+                                wait); intensity float(double(size) / double(N)), halved when size < min_size + 1.
+   The result is measure()'s two arrays: flat x y z and less sharp x y z intensity.  It is double-buffered and stays in
+   device memory; a refused prepare leaves the previous one in place for the getter and the measure.
+
+   dddmr_rollout_mcl_set_observation_config: the two parameters (mcl_3dl.yaml: euc_cluster_distance 0.8,
+   euc_cluster_min_size 3) and the input capacities; NULL switches the observation off.  A new configuration forgets the
+   prepared observation, and so does a second dddmr_rollout_mcl_create.  Deliberate differences from the reference:
+   a NEGATIVE euc_cluster_min_size and a non-positive or non-finite euc_cluster_distance are refused
+   (DDDMR_ERR_BAD_ARG), and dddmr_rollout_mcl_prepare refuses a non-finite input coordinate (DDDMR_ERR_BAD_ARG; the
+   reference's answer there is whatever PCL does with is_dense).  DDDMR_ERR_CAPACITY: max_flat_points +
+   max_less_sharp_points above mcl_create's max_observation_points (the outputs are never more than the inputs).
+   dddmr_rollout_mcl_prepare: xyz records, strides in bytes.  dddmr_rollout_mcl_prepare_from_sweep: the accepted
+   sweep's flat (which 2) and less-sharp (which 1) features of a sweep source, x y z only, read in device memory.
+   DDDMR_ERR_STATE: no mcl_create, no configuration, a dddmr_rollout_tick_begin pending, or (from_sweep) not a sweep
+   source or its features off.  DDDMR_ERR_CAPACITY: more input points than configured.  DDDMR_ERR_BAD_ARG: a
+   non-finite T_b2s entry, a bad stride, unknown flags.  stats (may be NULL): the counts, the branch, the two sums;
+   n_clusters counts the kept clusters, n_small_clusters those of them with size < min_size + 1, n_nan_normals the
+   points whose normal_x is NaN; launches (1, or 2 in the cluster branch) and host_waits (1).
+
+   dddmr_rollout_mcl_get_observation follows dddmr_rollout_get_lidar_sweep_features: NULL outputs only report the counts,
+   DDDMR_ERR_CAPACITY when an output is wanted and its capacity is below the count; normals_out is [n_less_sharp_in][3]
+   in INPUT order.  Before the first prepare: zero points.
+   dddmr_rollout_mcl_measure_prepared is dddmr_rollout_mcl_measure on the prepared observation where it lies: the same
+   three kernels, the same answers, dddmr_rollout_mcl_get_terms answers for it too.  Like mcl_measure it refuses an
+   observation without any point (DDDMR_ERR_BAD_ARG). */
+typedef struct {
+  double euc_cluster_distance;                        /* mcl_3dl.yaml: 0.8 */
+  int32_t euc_cluster_min_size;                       /* 3 */
+  uint32_t max_flat_points, max_less_sharp_points;    /* inputs; sum <= mcl max_observation_points */
+  uint32_t flags, reserved;                           /* 0 */
+} dddmr_mcl_observation_config;
+
+typedef struct {
+  uint32_t n_flat_in, n_flat_out, n_less_sharp_in, n_less_sharp_out;
+  uint32_t branch;                                    /* 0 clusters, 1 x dominant, 2 y dominant */
+  uint32_t n_clusters, n_small_clusters, n_nan_normals;
+  double sum_normal_x, sum_normal_y;
+  uint32_t launches, host_waits;
+} dddmr_mcl_observation_stats;
+
+int dddmr_rollout_mcl_set_observation_config(dddmr_rollout_ctx* ctx, const dddmr_mcl_observation_config* cfg);
+int dddmr_rollout_mcl_prepare(dddmr_rollout_ctx* ctx, const float* flat_xyz, size_t n_flat, size_t flat_stride_bytes,
+                              const float* less_sharp_xyz, size_t n_less_sharp, size_t less_sharp_stride_bytes,
+                              const double T_b2s[12], dddmr_mcl_observation_stats* stats);
+int dddmr_rollout_mcl_prepare_from_sweep(dddmr_rollout_ctx* ctx, int32_t source_id, const double T_b2s[12],
+                                         dddmr_mcl_observation_stats* stats);
+int dddmr_rollout_mcl_get_observation(dddmr_rollout_ctx* ctx, float* flat_xyz_out, size_t flat_capacity, size_t* n_flat,
+                                      float* less_sharp_xyzi_out, size_t less_sharp_capacity, size_t* n_less_sharp,
+                                      float* normals_out /* [n_less_sharp_in][3], input order */, size_t normals_capacity);
+int dddmr_rollout_mcl_measure_prepared(dddmr_rollout_ctx* ctx, const float* states /* [n_states][7] */, size_t n_states,
+                                       float* likelihood_out, float* quality_out, dddmr_mcl_stats* stats);
 
 /* Measurement aid ("a measured stream-copy ceiling on the same GPU"): streams
    `bytes` (>= 1 GiB recommended: beyond the 256 MB of MALL) `reps` times through a float4 copy

@@ -260,6 +260,25 @@ class LocalPlanner {
     quality.swap(qual);
     return DDDMR_OK;
   }
+  // the localiser's observation (mcl_3dl's cbLeGoFeatureCloud) prepared on the device, and the measure on it where it lies
+  int mclSetObservationConfig(const dddmr_mcl_observation_config* cfg) { return dddmr_rollout_mcl_set_observation_config(ctx_, cfg); }
+  int mclPrepare(const float* flat_xyz, size_t n_flat, size_t flat_stride_bytes, const float* less_sharp_xyz, size_t n_less_sharp,
+                 size_t less_sharp_stride_bytes, const double T_b2s[12], dddmr_mcl_observation_stats* stats = nullptr) {
+    return dddmr_rollout_mcl_prepare(ctx_, flat_xyz, n_flat, flat_stride_bytes, less_sharp_xyz, n_less_sharp, less_sharp_stride_bytes, T_b2s, stats);
+  }
+  int mclPrepareFromSweep(int32_t source_id, const double T_b2s[12], dddmr_mcl_observation_stats* stats = nullptr) {
+    return dddmr_rollout_mcl_prepare_from_sweep(ctx_, source_id, T_b2s, stats);
+  }
+  int mclMeasurePrepared(const std::vector<float>& states, std::vector<float>& likelihood, std::vector<float>& quality, dddmr_mcl_stats& stats) {
+    const size_t n = states.size() / 7;
+    std::vector<float> like(n), qual(n);
+    stats = dddmr_mcl_stats{};
+    const int rc = dddmr_rollout_mcl_measure_prepared(ctx_, states.data(), n, like.data(), qual.data(), &stats);
+    if (rc != DDDMR_OK) return rc;
+    likelihood.swap(like);
+    quality.swap(qual);
+    return DDDMR_OK;
+  }
   // prune plan poses, x y z qx qy qz qw each (output of Local_Planner::prunePlan)
   void setPlan(const double* poses_xyz_qxyzw, size_t n_poses) {
     check(dddmr_rollout_set_prune_plan(ctx_, poses_xyz_qxyzw, n_poses));
