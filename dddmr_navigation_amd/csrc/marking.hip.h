@@ -255,9 +255,6 @@ __global__ __launch_bounds__(256) void k_mk_fov(MarkParams k, MarkStore s, MarkC
   s.fov_flag[w] = flag;
 }
 
-#ifdef DDDMR_PHASE_STAMPS
-__device__ int g_mk_exp_noprobe;                    // diagnostic build: 1 = the ray probes look nothing up (wrong results: timing only)
-#endif
 // -DDDDMR_CLEAR_CYCLES (on top of the diagnostic build): per-ray cycle sums -- their same-address atomics make the launch
 // itself ~20x slower, so they are only good for shares, never next to kernel times
 #ifdef DDDMR_CLEAR_CYCLES
@@ -320,9 +317,6 @@ __device__ __forceinline__ bool mk_clear_wave(const MarkParams& k, const MarkSto
         }
         if (!stop) {
           const float r2 = static_cast<float>(sd * sd);
-#ifdef DDDMR_PHASE_STAMPS
-          if (!g_mk_exp_noprobe)
-#endif
           hit = grid_radius_count(prev, ax, ay, az, (float)sd + k.pad, r2, 1) > 0;
         }
       }

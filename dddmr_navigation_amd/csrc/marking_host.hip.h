@@ -5,6 +5,7 @@
 
 #include "marking.hip.h"
 #include "marking_fused.hip.h"
+#include "marking_plan.hip.h"
 #include "marking_store.hip.h"
 
 namespace {
@@ -110,12 +111,7 @@ struct MarkingState {
   hipStream_t own_stream = nullptr;        // the update's stream while a tick_begin is pending (else the context's)
   hipStream_t cur = nullptr;               // stream of the update in progress
   uint32_t updates_overlapped = 0;
-  uint32_t grid_parts = 4;                 // DDDMR_MKF_GRIDPARTS: workgroups that build the observation grid (1, 2, 4, 8)
-  bool unmark_with_groups = true;          // DDDMR_MKF_UNMARK=roots: removePCPtr blocks in the seeds' launch instead of the partitions'
-  bool grid_in_lds = true;                 // DDDMR_MKF_GRID=global: counts by a count launch's global atomics instead
-  uint32_t splat_parts = 0;                // DDDMR_MKF_PARTS: blocks that share a row segment's bands in the commit launch (0: estimated)
-  uint32_t unmark_parts = 8;               // DDDMR_MKF_UNPARTS (tuning)
-  uint32_t fuse_cells = kFuseMaxCells;     // DDDMR_MKF_CELLS: cells of the fused route's observation grid (tuning)
+  MarkKnobs knobs;                         // the DDDMR_MKF_* variables (marking_plan.hip.h)
 };
 
 void marking_free(MarkingState* m) {
@@ -131,26 +127,6 @@ void marking_free(MarkingState* m) {
   if (m->e2) (void)hipEventDestroy(m->e2);
   delete m;
 }
-
-// Grid geometry over [lo, hi] with the wanted cell sizes, coarsened until it fits `cap_cells`.
-void grid_shape(PointGrid& g, const float lo[3], const float hi[3], float cell_xy, float cell_z, uint32_t cap_cells) {
-  for (;;) {
-    g.nx = std::max(1, (int)std::ceil((hi[0] - lo[0]) / cell_xy) + 1);
-    g.ny = std::max(1, (int)std::ceil((hi[1] - lo[1]) / cell_xy) + 1);
-    g.nz = std::max(1, (int)std::ceil((hi[2] - lo[2]) / cell_z) + 1);
-    if ((uint64_t)g.nx * g.ny * g.nz <= cap_cells) break;
-    cell_xy *= 1.3f;
-    cell_z *= 1.3f;
-  }
-  g.ox = lo[0]; g.oy = lo[1]; g.oz = lo[2];
-  g.inv_xy = 1.0f / cell_xy;
-  g.inv_z = 1.0f / cell_z;
-}
-
-// grid_cx / grid_cy / grid_cz of marking.hip.h on the host (same float operations)
-int host_cx(const PointGrid& g, float x) { return std::min(std::max((int)std::floor((x - g.ox) * g.inv_xy), 0), g.nx - 1); }
-int host_cy(const PointGrid& g, float y) { return std::min(std::max((int)std::floor((y - g.oy) * g.inv_xy), 0), g.ny - 1); }
-int host_cz(const PointGrid& g, float z) { return std::min(std::max((int)std::floor((z - g.oz) * g.inv_z), 0), g.nz - 1); }
 
 int grid_alloc(dddmr_rollout_ctx* ctx, DevAllocs& mem, GridBuf& b, uint32_t cap_cells, uint32_t cap_points) {
   b.cap_cells = cap_cells;
@@ -172,74 +148,6 @@ int grid_build(dddmr_rollout_ctx* ctx, void* temp, size_t temp_bytes, GridBuf& b
   HIPCHK(ctx, rocprim::exclusive_scan(temp, temp_bytes, g.cell_start, g.cell_start, 0u, cells + 1, rocprim::plus<uint32_t>(), stream));
   hipLaunchKernelGGL(k_grid_scatter, dim3((n + 255) / 256), dim3(256), 0, stream, g, pts, slot);
   return DDDMR_OK;
-}
-
-void quat_rotate_z(const double q[4], double out[3]) {   // tf2::quatRotate(q, (0, 0, 1)); q = x y z w
-  // q * v
-  const double ax = q[1] * 1.0, ay = -q[0] * 1.0, az = q[3] * 1.0, aw = -q[2] * 1.0;   // (w*0 + y*1 - z*0, w*0 + z*0 - x*1, w*1 + x*0 - y*0, -x*0 - y*0 - z*1)
-  // (q * v) * q^-1, q^-1 = (-x, -y, -z, w)
-  const double bx = -q[0], by = -q[1], bz = -q[2], bw = q[3];
-  out[0] = aw * bx + ax * bw + ay * bz - az * by;
-  out[1] = aw * by + ay * bw + az * bx - ax * bz;
-  out[2] = aw * bz + az * bw + ax * by - ay * bx;
-}
-
-// ModelCoefficients of the plane through base_link with base z as its normal (:401-409; depth camera :568-578):
-// tf2::quatRotate(q, (0, 0, 1)) and d in double, each rounded to float
-void base_plane(const double T_gbl_base[7], float mc[4]) {
-  const double qb[4] = {T_gbl_base[3], T_gbl_base[4], T_gbl_base[5], T_gbl_base[6]};
-  double nb[3];
-  quat_rotate_z(qb, nb);
-  mc[0] = (float)nb[0]; mc[1] = (float)nb[1]; mc[2] = (float)nb[2];
-  const double d = -T_gbl_base[0] * nb[0] - T_gbl_base[1] * nb[1] - T_gbl_base[2] * nb[2];
-  mc[3] = (float)d;
-}
-// what an update's MarkParams take from the robot's pose: the base plane and selfClear's window in voxel keys
-// (lidar :489-496, depth camera :280-287), from k's own res / hres / window / marking_height
-void mark_params_pose(MarkParams& k, const double T_gbl_base[7]) {
-  base_plane(T_gbl_base, k.mc);
-  k.wx0 = (int)((T_gbl_base[0] - k.window) / k.res);
-  k.wx1 = (int)((T_gbl_base[0] + k.window) / k.res);
-  k.wy0 = (int)((T_gbl_base[1] - k.window) / k.res);
-  k.wy1 = (int)((T_gbl_base[1] + k.window) / k.res);
-  k.wz0 = (int)((T_gbl_base[2] - k.marking_height) / k.hres);
-  k.wz1 = (int)((T_gbl_base[2] + k.marking_height) / k.hres);
-}
-
-// Eigen quaternion of a rotation matrix (row-major R), as tf2::eigenToTransform forms trans_gbl2s_'s rotation
-void rot_to_quat(const double R[9], double q[4]) {
-  double t = R[0] + R[4] + R[8];
-  if (t > 0.0) {
-    t = std::sqrt(t + 1.0);
-    q[3] = 0.5 * t;
-    t = 0.5 / t;
-    q[0] = (R[7] - R[5]) * t;
-    q[1] = (R[2] - R[6]) * t;
-    q[2] = (R[3] - R[1]) * t;
-  } else {
-    int i = 0;
-    if (R[4] > R[0]) i = 1;
-    if (R[8] > R[4 * i]) i = 2;
-    const int j = (i + 1) % 3, k = (j + 1) % 3;
-    t = std::sqrt(R[4 * i] - R[4 * j] - R[4 * k] + 1.0);
-    q[i] = 0.5 * t;
-    t = 0.5 / t;
-    q[3] = (R[3 * k + j] - R[3 * j + k]) * t;
-    q[j] = (R[3 * j + i] + R[3 * i + j]) * t;
-    q[k] = (R[3 * k + i] + R[3 * i + k]) * t;
-  }
-}
-// tf2 Matrix3x3::setRotation(q), row-major
-void tf2_set_rotation(const double q[4], double R[9]) {
-  const double d = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
-  const double s = 2.0 / d;
-  const double xs = q[0] * s, ys = q[1] * s, zs = q[2] * s;
-  const double wx = q[3] * xs, wy = q[3] * ys, wz = q[3] * zs;
-  const double xx = q[0] * xs, xy = q[0] * ys, xz = q[0] * zs;
-  const double yy = q[1] * ys, yz = q[1] * zs, zz = q[2] * zs;
-  R[0] = 1.0 - (yy + zz); R[1] = xy - wz; R[2] = xz + wy;
-  R[3] = xy + wz; R[4] = 1.0 - (xx + zz); R[5] = yz - wx;
-  R[6] = xz - wy; R[7] = yz + wx; R[8] = 1.0 - (xx + yy);
 }
 
 int upload_static(dddmr_rollout_ctx* ctx, DevAllocs& mem, void* temp, size_t temp_bytes, GridBuf& b, float4** dev, const float* xyz, size_t n,
@@ -375,12 +283,13 @@ int dddmr_rollout_marking_create(dddmr_rollout_ctx* ctx, const dddmr_marking_con
     HIPCHK(ctx, hipMemset(m->ticket, 0, 34 * sizeof(uint32_t)));
     HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&m->host_out), sizeof(MarkCounters), hipHostMallocMapped));
     HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&m->host_out_dev), m->host_out, 0));
-    if (const char* e = std::getenv("DDDMR_MKF_UNMARK")) m->unmark_with_groups = std::strcmp(e, "roots") != 0;
-    if (const char* e = std::getenv("DDDMR_MKF_GRIDPARTS")) { const int v = std::atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8) m->grid_parts = (uint32_t)v; }
-    if (const char* e = std::getenv("DDDMR_MKF_GRID")) m->grid_in_lds = std::strcmp(e, "global") != 0;
-    if (const char* e = std::getenv("DDDMR_MKF_PARTS")) m->splat_parts = (uint32_t)std::min(128, std::max(0, std::atoi(e)));
-    if (const char* e = std::getenv("DDDMR_MKF_UNPARTS")) m->unmark_parts = (uint32_t)std::min(64, std::max(1, std::atoi(e)));
-    if (const char* e = std::getenv("DDDMR_MKF_CELLS")) m->fuse_cells = std::min<uint32_t>(kFuseMaxCells, std::max(4096, std::atoi(e)));
+    MarkKnobs& kn = m->knobs;
+    if (const char* e = std::getenv("DDDMR_MKF_UNMARK")) kn.unmark_with_groups = std::strcmp(e, "roots") != 0;
+    if (const char* e = std::getenv("DDDMR_MKF_GRIDPARTS")) { const int v = std::atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8) kn.grid_parts = (uint32_t)v; }
+    if (const char* e = std::getenv("DDDMR_MKF_GRID")) kn.grid_in_lds = std::strcmp(e, "global") != 0;
+    if (const char* e = std::getenv("DDDMR_MKF_PARTS")) kn.splat_parts = (uint32_t)std::min(128, std::max(0, std::atoi(e)));
+    if (const char* e = std::getenv("DDDMR_MKF_UNPARTS")) kn.unmark_parts = (uint32_t)std::min(64, std::max(1, std::atoi(e)));
+    if (const char* e = std::getenv("DDDMR_MKF_CELLS")) kn.fuse_cells = std::min<uint32_t>(kFuseMaxCells, std::max(4096, std::atoi(e)));
     if (const char* e = std::getenv("DDDMR_MARKING_ROUTE")) m->route = std::strcmp(e, "general") == 0 ? 0 : (std::strcmp(e, "fused") == 0 ? 1 : -1);
     HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_mkf_groups), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPartLdsBytes));
     HIPCHK(ctx, hipEventCreate(&m->e0));
@@ -416,12 +325,6 @@ int marking_reset_locked(dddmr_rollout_ctx* ctx) {
   return DDDMR_OK;
 }
 
-struct UpdateFrame {          // host-side inputs of one update besides the kernel parameters
-  MarkParams k;
-  double Rb[9];               // rotation of T_gbl_base
-  double t_gb[3];
-};
-
 #define MK_LAUNCH(m, ...) do { hipLaunchKernelGGL(__VA_ARGS__); ++(m)->launches_last; } while (0)
 
 // the store's housekeeping (rare); its kernels count as launches of the update
@@ -432,28 +335,6 @@ int marking_maintenance(dddmr_rollout_ctx* ctx, MarkingState* m, hipStream_t st)
   return runs < 0 ? runs : DDDMR_OK;
 }
 
-// the crop box of the feed (base frame |x|,|y| <= window, z in [0, marking_height]) in the global frame, + 0.3 m
-void crop_box(const MarkingState* m, const UpdateFrame& f, float lo[3], float hi[3]) {
-  const dddmr_marking_config& c = m->cfg;
-  for (int a = 0; a < 3; ++a) { lo[a] = 3.4e38f; hi[a] = -3.4e38f; }
-  for (int corner = 0; corner < 8; ++corner) {
-    const double bx = (corner & 1) ? c.perception_window_size : -c.perception_window_size;
-    const double by = (corner & 2) ? c.perception_window_size : -c.perception_window_size;
-    const double bz = (corner & 4) ? c.marking_height : 0.0;
-    for (int a = 0; a < 3; ++a) {
-      const float v = (float)(f.Rb[3 * a] * bx + f.Rb[3 * a + 1] * by + f.Rb[3 * a + 2] * bz + f.t_gb[a]);
-      lo[a] = std::min(lo[a], v - 0.3f);
-      hi[a] = std::max(hi[a], v + 0.3f);
-    }
-  }
-}
-// grid over it
-void obs_grid_shape(const MarkingState* m, const UpdateFrame& f, uint32_t cap_cells, PointGrid& g, float lo[3], float hi[3]) {
-  crop_box(m, f, lo, hi);
-  const float cell = std::max(0.1f, f.k.tol);
-  grid_shape(g, lo, hi, cell, cell, cap_cells);
-}
-
 // selfMark of this observation, general route: rocPRIM sorts, any observation size (marking.hip.h)
 int mark_general(dddmr_rollout_ctx* ctx, MarkingState* m, const UpdateFrame& f, const float4* obs, uint32_t n_obs, hipStream_t st) {
   const MarkParams& k = f.k;
@@ -461,7 +342,7 @@ int mark_general(dddmr_rollout_ctx* ctx, MarkingState* m, const UpdateFrame& f, 
   const int cur = m->prev >= 0 ? 1 - m->prev : 0;
   GridBuf& gb = m->obs[cur];
   float lo[3], hi[3];
-  obs_grid_shape(m, f, gb.cap_cells, gb.g, lo, hi);
+  obs_grid_shape(m->cfg, f, gb.cap_cells, gb.g, lo, hi);
   const float4* pts = obs;                   // (the cloud buffer stays pinned until the update returns)
   int rc = grid_build(ctx, m->sc.temp, m->sc.temp_bytes, gb, pts, n_obs, m->gslot, st);
   m->launches_last += 5;                     // memset, count, rocPRIM scan (2 kernels), scatter
@@ -513,6 +394,17 @@ int mark_general(dddmr_rollout_ctx* ctx, MarkingState* m, const UpdateFrame& f, 
   return DDDMR_OK;
 }
 
+// The tail of an update whose counters live on the device: the alive list, the end event, the counters' copy and the wait.
+int finish_on_device(dddmr_rollout_ctx* ctx, MarkingState* m, const MarkParams& k, bool timed, MarkCounters& out) {
+  hipStream_t st = m->cur;
+  MK_LAUNCH(m, k_mk_finish, dim3((m->store.table + 255) / 256), dim3(256), 0, st, k, m->store.s, m->store.counters);
+  if (timed) HIPCHK(ctx, hipEventRecord(m->e2, st));
+  HIPCHK(ctx, hipMemcpyAsync(&out, m->store.counters, sizeof(out), hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  HIPCHK(ctx, hipGetLastError());
+  return DDDMR_OK;
+}
+
 // one update on the general route (~55 launches for a 6 k-point observation)
 int update_general(dddmr_rollout_ctx* ctx, MarkingState* m, const UpdateFrame& f, const float4* obs, uint32_t n_obs, bool timed,
                    MarkCounters& out) {
@@ -544,16 +436,39 @@ int update_general(dddmr_rollout_ctx* ctx, MarkingState* m, const UpdateFrame& f
     rc = mark_general(ctx, m, f, obs, n_obs, st);
     if (rc != DDDMR_OK) return rc;
   }
-  MK_LAUNCH(m, k_mk_finish, dim3((m->store.table + 255) / 256), dim3(256), 0, st, k, s, m->store.counters);
-  if (timed) HIPCHK(ctx, hipEventRecord(m->e2, st));
-  HIPCHK(ctx, hipMemcpyAsync(&out, m->store.counters, sizeof(out), hipMemcpyDeviceToHost, st));
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  HIPCHK(ctx, hipGetLastError());
+  if ((rc = finish_on_device(ctx, m, k, timed, out)) != DDDMR_OK) return rc;
   ++m->updates_general;
   return DDDMR_OK;
 }
 
-// one update on the fused route: six launches, no copies (marking_fused.hip.h)
+// A fused update that flagged `fallback`: a cluster beyond one partition workgroup, or voxel ranges beyond the 28-bit
+// sort keys (points hundreds of metres apart: only a cloud handed over with set_cloud can do that).  The clear phase
+// stands, nothing of the mark phase has reached the store but keys and claims, and the mark phase is redone on the
+// general route.  out: the fused update's counters, replaced by the finished update's.
+int fused_fallback(dddmr_rollout_ctx* ctx, MarkingState* m, const UpdateFrame& f, const float4* obs, uint32_t n_obs, bool timed,
+                   MarkCounters& out) {
+  hipStream_t st = m->cur;
+  --m->updates_fused;
+  m->counters_clean = false;
+  HIPCHK(ctx, hipMemsetAsync(m->store.s.owner, 0, (size_t)m->store.table * sizeof(unsigned long long), st));
+  MarkCounters zero{};
+  zero.pool_used = out.pool_used;
+  HIPCHK(ctx, hipMemcpyAsync(m->store.counters, &zero, sizeof(zero), hipMemcpyHostToDevice, st));
+  int rc = mark_general(ctx, m, f, obs, n_obs, st);
+  if (rc != DDDMR_OK) return rc;
+  MarkCounters g{};
+  if ((rc = finish_on_device(ctx, m, f.k, timed, g)) != DDDMR_OK) return rc;
+  g.n_in_window = out.n_in_window; g.n_cleared = out.n_cleared; g.n_removed = out.n_removed; g.n_rehashed = out.n_rehashed;
+  g.n_new_keys += out.n_new_keys;
+  g.fallback = 1u;
+  out = g;
+  m->alive_list_stale = false;
+  ++m->updates_general;
+  return DDDMR_OK;
+}
+
+// one update on the fused route: five launches (a sixth with DDDMR_MKF_GRID=global), no copies (marking_fused.hip.h);
+// what each launch gets is planned by plan_fused_update (marking_plan.hip.h)
 int update_fused(dddmr_rollout_ctx* ctx, MarkingState* m, const UpdateFrame& f, const float4* obs, uint32_t n_obs, bool timed,
                  MarkCounters& out) {
   hipStream_t st = m->cur;
@@ -569,98 +484,41 @@ int update_fused(dddmr_rollout_ctx* ctx, MarkingState* m, const UpdateFrame& f, 
   if (timed) HIPCHK(ctx, hipEventRecord(m->e0, st));
   int rc = marking_maintenance(ctx, m, st);
   if (rc != DDDMR_OK) return rc;
-  const bool mark = n_obs > 5;                                                   // :320-321
   const int cur = m->prev >= 0 ? 1 - m->prev : 0;
   GridBuf& gb = m->obs[cur];
   const PointGrid empty_grid = m->obs[0].g;
   const PointGrid prev_grid = m->prev >= 0 ? m->obs[m->prev].g : empty_grid;
-  if (mark) {
-    float lo[3], hi[3];
-    const uint32_t cap = std::min(gb.cap_cells, m->fuse_cells);
-    obs_grid_shape(m, f, cap, gb.g, lo, hi);
-    gb.g.n = n_obs;
-  }
+  const PointGrid& ground = m->grids.ground.g;
   const uint32_t n_alive = m->store.n_alive;
-  // ground cells of the window + inflation radius: the nodes the node-by-node dGraph updates look at
-  SplatRange rg{};
-  {
-    float lo[3], hi[3];
-    crop_box(m, f, lo, hi);
-    const PointGrid& gg = m->grids.ground.g;
-    const float pad = (float)m->cfg.inflation_radius + 0.05f;
-    rg.cx0 = host_cx(gg, lo[0] - pad); rg.cx1 = host_cx(gg, hi[0] + pad);
-    rg.cy0 = host_cy(gg, lo[1] - pad); rg.cy1 = host_cy(gg, hi[1] + pad);
-    rg.rows = (uint32_t)(rg.cy1 - rg.cy0 + 1) * (uint32_t)gg.nz;
-    rg.segs = std::max(1u, (m->grids.ground.max_row + 63u) / 64u);
-    rg.delta = (int)std::floor(((float)m->cfg.inflation_radius + 1e-3f) * gg.inv_xy) + 1;
-    rg.bands = (m->grids.n_ground && (uint32_t)(rg.cy1 - rg.cy0 + 1) <= kBandMax) ? (uint32_t)(rg.cy1 - rg.cy0 + 1) : 0u;
+  const FusedPlan p = plan_fused_update(m->knobs, m->cfg, f, ground, m->grids.ground.max_row, m->grids.n_ground, gb.cap_cells, n_obs,
+                                        n_alive, m->store.table);
+  if (p.mark) {                              // the planned geometry over this grid's storage
+    PointGrid g = p.obs;
+    g.cell_start = gb.g.cell_start;
+    g.sorted = gb.g.sorted;
+    gb.g = g;
   }
   FuseBufs fb{obs, m->sc.parent, m->sc.ds, m->gen, m->store.clear_list, m->unmark_pts,
-              BandList{m->band_pts, m->band_cnt}, BandList{m->band_pts + (size_t)kBandMax * kBandCap, m->band_cnt + kBandMax}, rg,
-              m->ticket, m->cell_count, m->sc.keys_a, m->host_out_dev, m->grid_in_lds ? 1u : 0u, m->hi_rank};
-  // Blocks that share one row segment's bands in the commit launch: a block takes every n_part-th 256-point chunk of the
-  // 2 delta + 1 bands in reach, so more blocks than chunks only add blocks that read the band counts and leave (measured at
-  // C5M, ~110 points per band, 9 bands in reach: n_part 48 / 24 / 16 / 12 / 8 -> mark phase 80 / 68 / 68 / 66 / 67 us).
-  // Estimated from the observation size (at most one generator point per observation point, about half in practice).
-  uint32_t n_part = m->splat_parts;
-  if (n_part == 0) {
-    const uint32_t per_band = std::max(1u, n_obs / 2u / std::max(1u, rg.bands));
-    const uint32_t chunks = (2u * (uint32_t)rg.delta + 1u) * ((per_band + 255u) / 256u);
-    n_part = std::min(48u, std::max(8u, chunks + chunks / 3u));
-  }
-  const uint32_t seg_groups = (rg.segs + 3u) / 4u;
+              BandList{m->band_pts, m->band_cnt}, BandList{m->band_pts + (size_t)kBandMax * kBandCap, m->band_cnt + kBandMax}, p.rg,
+              m->ticket, m->cell_count, m->sc.keys_a, m->host_out_dev, m->knobs.grid_in_lds ? 1u : 0u, m->hi_rank};
   if (m->seq == 3 && std::getenv("DDDMR_DEBUG_GRID"))
     std::fprintf(stderr, "[dddmr] marking update: %u points, %u alive; window rows %u x %u segments, %u bands, delta %d -> %u blocks per row segment\n",
-                 n_obs, m->store.n_alive, rg.rows, rg.segs, rg.bands, rg.delta, n_part);
-  const uint32_t nb_band = rg.bands ? rg.rows * seg_groups * n_part : 0u;
-  // (DDDMR_MKF_GRID=global only) cell counts of the observation grid
-  const bool big = n_obs > kFuseRegObs;          // (the count launch's form of the grid only takes kFuseRegObs points)
-  if (mark && !m->grid_in_lds && !big) MK_LAUNCH(m, k_mkf_count, dim3((n_obs + 255) / 256), dim3(256), 0, st, gb.g, fb);
-  // grid launch: the observation grid (built in LDS by the first grid_parts workgroups) | every store slot: window + FOV test -> ray-test list
-  {
-    const uint32_t nb_grid = mark ? ((m->grid_in_lds || big) ? m->grid_parts : 1u) : 0u;
-    if (big) MK_LAUNCH(m, k_mkf_grid_fov<true>, dim3(nb_grid + (m->store.table + 1023) / 1024), dim3(1024), 0, st, k, s, gb.g, fb, m->store.counters, nb_grid);
-    else MK_LAUNCH(m, k_mkf_grid_fov<false>, dim3(nb_grid + (m->store.table + 1023) / 1024), dim3(1024), 0, st, k, s, gb.g, fb, m->store.counters, nb_grid);
-  }
-#ifdef DDDMR_PHASE_STAMPS
-  if (const char* e = std::getenv("DDDMR_MKF_EXP")) { const int v = (std::atoi(e) & 128) ? 1 : 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(dddmr::g_mk_exp_noprobe), &v, sizeof(v)); }
-#endif
-  // clear launch: ray tests | union-find
-  uint32_t nb_clear = (n_alive + 3) / 4, nb_cc = mark ? (n_obs * 4 + 255) / 256 : 0;
-#ifdef DDDMR_PHASE_STAMPS
-  // diagnostic build only (results are wrong with either): time the two halves of the launch apart
-  if (const char* e = std::getenv("DDDMR_MKF_EXP")) { if (std::atoi(e) & 1) nb_cc = 0; if (std::atoi(e) & 2) nb_clear = 0; }
-#endif
-  if (nb_clear + nb_cc)
-    MK_LAUNCH(m, k_mkf_clear_cc, dim3(nb_clear + nb_cc), dim3(256), 0, st, k, s, prev_grid, gb.g, m->grids.ground.g, fb, m->store.counters, nb_clear);
+                 n_obs, n_alive, p.rg.rows, p.rg.segs, p.rg.bands, p.rg.delta, p.n_part);
+  if (p.count_blocks) MK_LAUNCH(m, k_mkf_count, dim3(p.count_blocks), dim3(256), 0, st, gb.g, fb);
+  if (p.big) MK_LAUNCH(m, k_mkf_grid_fov<true>, dim3(p.grid_launch()), dim3(1024), 0, st, k, s, gb.g, fb, m->store.counters, p.nb_grid);
+  else MK_LAUNCH(m, k_mkf_grid_fov<false>, dim3(p.grid_launch()), dim3(1024), 0, st, k, s, gb.g, fb, m->store.counters, p.nb_grid);
+  if (p.clear_launch())
+    MK_LAUNCH(m, k_mkf_clear_cc, dim3(p.clear_launch()), dim3(256), 0, st, k, s, prev_grid, gb.g, ground, fb, m->store.counters, p.nb_clear);
   if (timed) HIPCHK(ctx, hipEventRecord(m->e1, st));
-  uint32_t nb_un_groups = 0, nb_band_groups = 0;
-  // seed launch: seeds (| removePCPtr of the cleared markings when it does not ride in the partition launch)
-  {
-    // (the removed markings of one update are a tenth of the new generator points: fewer, longer blocks per row)
-    const uint32_t n_part_un = m->unmark_parts;
-    uint32_t nb_roots = mark ? (n_obs + 255) / 256 : 0, nb_un = (n_alive && rg.bands) ? rg.rows * seg_groups * n_part_un : 0u, nb_walk = n_alive ? 64u : 0u;
-#ifdef DDDMR_PHASE_STAMPS
-    if (const char* e = std::getenv("DDDMR_MKF_EXP")) { if (std::atoi(e) & 32) nb_un = 0; if (std::atoi(e) & 64) nb_walk = 0; }
-#endif
-    if (mark && m->unmark_with_groups) { nb_un_groups = nb_un + nb_walk; nb_band_groups = nb_un; nb_un = 0; nb_walk = 0; }
-    if (nb_roots + nb_un + nb_walk)
-      MK_LAUNCH(m, k_mkf_roots_unmark, dim3(nb_roots + nb_un + nb_walk), dim3(256), 0, st, k, fb, m->sc.cl, s, m->grids.ground.g, m->store.counters, nb_roots,
-                nb_un, seg_groups, n_part_un);
-  }
-  // partition launch: 64 partitions of the clusters | removePCPtr: ground node by ground node, point by point for the points that found no band
-  if (mark)
-    MK_LAUNCH(m, k_mkf_groups, dim3(kFuseParts + nb_un_groups), dim3(kPartThreads), kPartLdsBytes, st, k, fb, m->sc.cl, s, m->grids.ground.g, m->grids.map.g, m->grids.n_map,
-              m->store.counters, nb_band_groups, seg_groups, m->unmark_parts);
-  // commit launch: keepers -> pool | dGraph of the new generator points (node by node); the last block publishes the counters
-  {
-    uint32_t nb_commit = mark ? (n_obs + 255) / 256 : 0, nb_b = mark ? nb_band : 0u, nb_walk = mark ? 256u : 1u;
-#ifdef DDDMR_PHASE_STAMPS
-    if (const char* e = std::getenv("DDDMR_MKF_EXP")) { if (std::atoi(e) & 4) nb_commit = 0; if (std::atoi(e) & 8) nb_b = 0; if (std::atoi(e) & 16) nb_walk = 1; }
-#endif
-    MK_LAUNCH(m, k_mkf_commit_dgraph, dim3(nb_commit + nb_b + nb_walk), dim3(256), 0, st, k, fb, m->sc.cl, s, m->grids.ground.g, m->store.counters, nb_commit,
-              nb_b, seg_groups, n_part);
-  }
+  if (p.seed_launch())
+    MK_LAUNCH(m, k_mkf_roots_unmark, dim3(p.seed_launch()), dim3(256), 0, st, k, fb, m->sc.cl, s, ground, m->store.counters, p.nb_roots, p.nb_un,
+              p.seg_groups, p.n_part_un);
+  if (p.part_launch())
+    MK_LAUNCH(m, k_mkf_groups, dim3(p.part_launch()), dim3(kPartThreads), kPartLdsBytes, st, k, fb, m->sc.cl, s, ground, m->grids.map.g, m->grids.n_map,
+              m->store.counters, p.nb_band_groups, p.seg_groups, p.n_part_un);
+  // (the commit launch's last block publishes the counters to host-mapped memory)
+  MK_LAUNCH(m, k_mkf_commit_dgraph, dim3(p.commit_launch()), dim3(256), 0, st, k, fb, m->sc.cl, s, ground, m->store.counters, p.nb_commit, p.nb_b,
+            p.seg_groups, p.n_part);
   if (timed) HIPCHK(ctx, hipEventRecord(m->e2, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
   HIPCHK(ctx, hipGetLastError());
@@ -671,35 +529,11 @@ int update_fused(dddmr_rollout_ctx* ctx, MarkingState* m, const UpdateFrame& f, 
   for (uint32_t v : out.n_cleared_shard) out.n_cleared += v;
   out.n_alive = n_alive - out.n_cleared + out.n_revived;
   out.n_clusters = n_obs;                                                        // extent of the per-cluster records (named by seed index)
-  if (mark && !out.fallback) {
+  if (p.mark && !out.fallback) {
     m->prev = cur;                                                               // pcl_msg_gbl_ of this selfMark
     m->n_prev = n_obs;
   }
-  if (!out.fallback) return DDDMR_OK;
-  // A cluster beyond one partition workgroup, or voxel ranges beyond the 28-bit sort keys (points hundreds of metres
-  // apart: only a cloud handed over with set_cloud can do that): the clear phase stands, nothing of the mark phase
-  // has reached the store but keys and claims, and the mark phase is redone on the general route.
-  --m->updates_fused;
-  m->counters_clean = false;
-  HIPCHK(ctx, hipMemsetAsync(s.owner, 0, (size_t)m->store.table * sizeof(unsigned long long), st));
-  MarkCounters zero{};
-  zero.pool_used = out.pool_used;
-  HIPCHK(ctx, hipMemcpyAsync(m->store.counters, &zero, sizeof(zero), hipMemcpyHostToDevice, st));
-  rc = mark_general(ctx, m, f, obs, n_obs, st);
-  if (rc != DDDMR_OK) return rc;
-  MK_LAUNCH(m, k_mk_finish, dim3((m->store.table + 255) / 256), dim3(256), 0, st, k, s, m->store.counters);
-  if (timed) HIPCHK(ctx, hipEventRecord(m->e2, st));
-  MarkCounters g{};
-  HIPCHK(ctx, hipMemcpyAsync(&g, m->store.counters, sizeof(g), hipMemcpyDeviceToHost, st));
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  HIPCHK(ctx, hipGetLastError());
-  g.n_in_window = out.n_in_window; g.n_cleared = out.n_cleared; g.n_removed = out.n_removed; g.n_rehashed = out.n_rehashed;
-  g.n_new_keys += out.n_new_keys;
-  g.fallback = 1u;
-  out = g;
-  m->alive_list_stale = false;
-  ++m->updates_general;
-  return DDDMR_OK;
+  return out.fallback ? fused_fallback(ctx, m, f, obs, n_obs, timed, out) : DDDMR_OK;
 }
 }  // namespace
 
@@ -718,30 +552,19 @@ int dddmr_rollout_marking_update(dddmr_rollout_ctx* ctx, const double T_base_sen
   // state), provided it reads the SAME observation the pending tick has pinned: a third pinned buffer would leave a
   // producer none to write into.
   const bool overlapped = ctx->pend.active;
-  int cidx;
-  struct Release { dddmr_rollout_ctx* c; ~Release() { if (c) release_cloud(c); } } release{nullptr};
+  CloudPin pin(ctx, overlapped ? CloudPin::kOfPendingTick : CloudPin::kFront);
   if (overlapped) {
-    {
-      std::lock_guard<std::mutex> lk(ctx->cloud_mu);
-      if (ctx->busy < 0 || ctx->busy != ctx->front)
-        return fail(ctx, DDDMR_ERR_STATE, "marking_update while a tick_begin is pending: a newer observation was published after tick_begin");
-      cidx = ctx->busy;
-    }
+    if (!pin.is_front())
+      return fail(ctx, DDDMR_ERR_STATE, "marking_update while a tick_begin is pending: a newer observation was published after tick_begin");
     if (!m->own_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking));
     m->cur = m->own_stream;
-    HIPCHK(ctx, hipStreamWaitEvent(m->cur, ctx->cloud_ready[cidx], 0));      // (the tick's stream has its own wait enqueued)
+    HIPCHK(ctx, pin.wait_on(m->cur));      // (the tick's stream has its own wait enqueued)
     ++m->updates_overlapped;
   } else {
-    bool pending;
-    cidx = pin_front(ctx, &pending);
-    release.c = ctx;
     m->cur = ctx->stream;
-    if (pending) {
-      HIPCHK(ctx, hipStreamWaitEvent(m->cur, ctx->cloud_ready[cidx], 0));
-      cloud_wait_done(ctx, cidx);
-    }
+    HIPCHK(ctx, pin.wait_on(m->cur));
   }
-  return marking_update_on(ctx, m, ctx->cloud_dev[cidx], ctx->cloud_n[cidx], T_base_sensor, T_gbl_base, stats);
+  return marking_update_on(ctx, m, pin.dev(), pin.n_points(), T_base_sensor, T_gbl_base, stats);
 }
 
 }  // extern "C"
@@ -751,45 +574,13 @@ namespace {
 // tick_mu held; the caller keeps `obs` from being recycled until this returns (the update waits for its stream).
 int marking_update_on(dddmr_rollout_ctx* ctx, MarkingState* m, const float4* obs, uint32_t n_obs, const double T_base_sensor[7],
                       const double T_gbl_base[7], dddmr_marking_stats* stats) {
-  const dddmr_marking_config& c = m->cfg;
   if (n_obs > m->max_obs) return fail(ctx, DDDMR_ERR_CAPACITY, "marking_update: observation of %u points, layer sized for %u", n_obs, m->max_obs);
-
-  // ---- transforms (host, double): trans_gbl2s_af3_ = gbl2b * b2s (:236-237), its tf2 form (:238) ----
-  UpdateFrame f{};
-  MarkParams& k = f.k;
-  double Rbs[9], Rs_e[9], ts[3];
-  quat_to_rot(T_gbl_base, f.Rb);
-  quat_to_rot(T_base_sensor, Rbs);
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) Rs_e[3 * i + j] = f.Rb[3 * i + 0] * Rbs[0 + j] + f.Rb[3 * i + 1] * Rbs[3 + j] + f.Rb[3 * i + 2] * Rbs[6 + j];
-    ts[i] = f.Rb[3 * i + 0] * T_base_sensor[0] + f.Rb[3 * i + 1] * T_base_sensor[1] + f.Rb[3 * i + 2] * T_base_sensor[2] + T_gbl_base[i];
-    f.t_gb[i] = T_gbl_base[i];
-  }
-  double qs[4];
-  rot_to_quat(Rs_e, qs);
-  tf2_set_rotation(qs, k.Rs);
-  quat_rotate_z(qs, k.sn);
-  for (int i = 0; i < 3; ++i) k.st[i] = ts[i];
-  k.sd = -ts[0] * k.sn[0] - ts[1] * k.sn[1] - ts[2] * k.sn[2];
-  k.res = c.xy_resolution; k.hres = c.height_resolution; k.marking_height = c.marking_height; k.window = c.perception_window_size;
-  k.fov_top = c.vertical_FOV_top; k.fov_bottom = c.vertical_FOV_bottom;
-  k.ps = c.scan_effective_positive_start; k.pe = c.scan_effective_positive_end;
-  k.ns = c.scan_effective_negative_start; k.ne = c.scan_effective_negative_end;
-  k.ignore_ratio = c.segmentation_ignore_ratio; k.inscribed = c.inscribed_radius; k.inflation = c.inflation_radius;
-  k.tol = (float)c.euclidean_cluster_extraction_tolerance;
-  k.tol2 = static_cast<float>(c.euclidean_cluster_extraction_tolerance * c.euclidean_cluster_extraction_tolerance);
-  k.min_cluster = c.euclidean_cluster_extraction_min_cluster_size;
-  mark_params_pose(k, T_gbl_base);
-  k.n_obs = n_obs;
-  k.n_prev = m->prev >= 0 ? m->n_prev : 0;
-  k.pad = 1e-4f;
-  if (const char* e = std::getenv("DDDMR_MK_PAD")) k.pad = (float)std::atof(e);      // (diagnosis)
-  k.table_mask = m->store.table - 1;
-  k.pool_cap = m->store.pool_cap;
-  k.n_ground = m->grids.n_ground;
-  k.n_alive_prev = m->store.n_alive;
-  k.seq = ++m->seq;
-  if (k.seq == 0) k.seq = m->seq = 1;
+  float pad = 1e-4f;
+  if (const char* e = std::getenv("DDDMR_MK_PAD")) pad = (float)std::atof(e);      // (diagnosis)
+  if (++m->seq == 0) m->seq = 1;
+  const UpdateFrame f = make_update_frame(m->cfg, T_base_sensor, T_gbl_base, n_obs, m->prev >= 0 ? m->n_prev : 0, m->store.table,
+                                          m->store.pool_cap, m->grids.n_ground, m->store.n_alive, m->seq, pad);
+  const MarkParams& k = f.k;
 
   // HIP events serialise the queue around them: the update is timed like the tick (DDDMR_TIMING / _EVERY)
   const bool timed = stats && ctx->timing >= 1 && (m->seq % (uint32_t)ctx->timing_every) == 0;
@@ -798,6 +589,14 @@ int marking_update_on(dddmr_rollout_ctx* ctx, MarkingState* m, const float4* obs
   const bool fused = m->route != 0 && n_obs <= kFuseMaxObs;
   if (m->route == 1 && !fused)
     return fail(ctx, DDDMR_ERR_CAPACITY, "marking_update: DDDMR_MARKING_ROUTE=fused, observation of %u points > %u", n_obs, kFuseMaxObs);
+  // An error return below may leave work enqueued on m->cur that reads `obs` and the layer's buffers: wait for it, so
+  // that the caller may release the observation and the next call finds the stream idle (the status of that wait does
+  // not matter: the error being returned is the one to report).  The returns past the update's own wait are disarmed.
+  struct Drain {
+    hipStream_t st;
+    bool armed = true;
+    ~Drain() { if (armed) (void)hipStreamSynchronize(st); }
+  } drain{m->cur};
   const int rc = fused ? update_fused(ctx, m, f, obs, n_obs, timed, out) : update_general(ctx, m, f, obs, n_obs, timed, out);
   if (rc != DDDMR_OK) return rc;
   m->store.pool_used = out.pool_used;
@@ -807,6 +606,7 @@ int marking_update_on(dddmr_rollout_ctx* ctx, MarkingState* m, const float4* obs
     const int rt = marking_fix_ties(ctx, m, k, out);
     if (rt != DDDMR_OK) return rt;
   }
+  drain.armed = false;                       // (the update and the tie fixes have waited for the stream)
   if (timed) {
     HIPCHK(ctx, hipEventElapsedTime(&m->last_clear_ms, m->e0, m->e1));
     HIPCHK(ctx, hipEventElapsedTime(&m->last_mark_ms, m->e1, m->e2));

@@ -238,14 +238,10 @@ int dddmr_rollout_stack_update(dddmr_rollout_ctx* ctx, const double T_base_senso
   if (lidar) {
     MarkingState* m = ctx->marking;
     auto pass = [&]() -> int {
-      bool pending;
-      const int cidx = pin_front(ctx, &pending);
-      struct Release { dddmr_rollout_ctx* c; ~Release() { release_cloud(c); } } release{ctx};
+      CloudPin pin(ctx);
+      const int cidx = pin.idx();
       m->cur = ctx->stream;
-      if (pending) {
-        HIPCHK(ctx, hipStreamWaitEvent(m->cur, ctx->cloud_ready[cidx], 0));
-        cloud_wait_done(ctx, cidx);
-      }
+      HIPCHK(ctx, pin.wait_on(m->cur));
       SourceLayout L;
       {
         std::lock_guard<std::mutex> lk(ctx->cloud_mu);

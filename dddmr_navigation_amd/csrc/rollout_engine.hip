@@ -184,7 +184,66 @@ struct dddmr_rollout_ctx {
 
 namespace {
 
-void release_cloud(dddmr_rollout_ctx* c);
+// A consumer's pin on a cloud buffer (tick_mu held): while `busy` names the buffer no producer recycles it.
+//  - kFront pins the published front buffer and releases it when the pin goes out of scope, on any return.  `busy` is
+//    -1 whenever one is taken: every pinner holds tick_mu and releases before it returns, and every entry point but the
+//    marking update refuses while a tick is pending.
+//  - keep() hands the pin to the pending tick (tick_enqueue succeeded); kAdopted in tick_collect takes it back and
+//    releases it.
+//  - kOfPendingTick looks at the buffer a pending tick pins without ever releasing it (the overlapped marking update,
+//    on a stream of its own: it always has to wait for the upload there).
+// The "upload still pending" flag of the buffer is only cleared once the stream wait is enqueued (wait_on): an early
+// error return between the pin and the wait must not lose the ordering against copy_stream.
+class CloudPin {
+ public:
+  enum Mode { kFront, kOfPendingTick, kAdopted };
+  explicit CloudPin(dddmr_rollout_ctx* c, Mode mode = kFront) : c_(c), owns_(mode != kOfPendingTick) {
+    if (mode == kAdopted) {   // (only holders of tick_mu write `busy`: reading it takes no lock, and tick_collect took none)
+      idx_ = c_->busy;
+      return;
+    }
+    std::lock_guard<std::mutex> lk(c_->cloud_mu);
+    if (mode == kFront) {
+      idx_ = c_->busy = c_->front;
+      need_wait_ = c_->wait_pending[idx_];
+    } else {
+      idx_ = c_->busy;
+      need_wait_ = true;
+    }
+    is_front_ = idx_ >= 0 && idx_ == c_->front;
+  }
+  CloudPin(const CloudPin&) = delete;
+  CloudPin& operator=(const CloudPin&) = delete;
+  ~CloudPin() {
+    if (!owns_) return;
+    std::lock_guard<std::mutex> lk(c_->cloud_mu);
+    c_->busy = -1;
+  }
+  int idx() const { return idx_; }
+  bool is_front() const { return is_front_; }    // no newer observation had been published when the pin was taken (not kAdopted)
+  uint32_t n_points() const { return c_->cloud_n[idx_]; }
+  const float4* dev() const { return c_->cloud_dev[idx_]; }
+  // `stream` waits for the buffer's upload, if it still has to
+  hipError_t wait_on(hipStream_t stream) {
+    if (!need_wait_) return hipSuccess;
+    const hipError_t e = hipStreamWaitEvent(stream, c_->cloud_ready[idx_], 0);
+    if (e != hipSuccess) return e;
+    need_wait_ = false;
+    if (owns_) {
+      std::lock_guard<std::mutex> lk(c_->cloud_mu);
+      c_->wait_pending[idx_] = false;   // (idx is pinned, so it cannot have been republished meanwhile)
+    }
+    return hipSuccess;
+  }
+  void keep() { owns_ = false; }
+
+ private:
+  dddmr_rollout_ctx* c_;
+  bool owns_;
+  int idx_ = -1;
+  bool need_wait_ = false, is_front_ = false;
+};
+
 void release_source(dddmr_rollout_ctx* c, int id);   // sensor_sources.hip.h
 
 // RCCL entry points, resolved at run time: the engine has no link-time dependency on librccl (hosts
@@ -502,20 +561,6 @@ static int acquire_back(dddmr_rollout_ctx* ctx) {
   return -1;   // unreachable: three buffers, two exclusions
 }
 
-// Pin the front buffer for a consumer on ctx->stream (tick_mu held).  *need_wait says whether the
-// stream still has to wait for the buffer's upload; call cloud_wait_done() once that wait is enqueued.
-static int pin_front(dddmr_rollout_ctx* ctx, bool* need_wait) {
-  std::lock_guard<std::mutex> lk(ctx->cloud_mu);
-  const int idx = ctx->front;
-  ctx->busy = idx;
-  *need_wait = ctx->wait_pending[idx];
-  return idx;
-}
-static void cloud_wait_done(dddmr_rollout_ctx* ctx, int idx) {
-  std::lock_guard<std::mutex> lk(ctx->cloud_mu);
-  ctx->wait_pending[idx] = false;   // (idx is pinned, so it cannot have been republished meanwhile)
-}
-
 int dddmr_rollout_set_cloud(dddmr_rollout_ctx* ctx, const float* xyzi, size_t n_points,
                             size_t stride_bytes) {
   if (!ctx) return DDDMR_ERR_BAD_ARG;
@@ -559,10 +604,9 @@ int dddmr_rollout_get_cloud(dddmr_rollout_ctx* ctx, float* xyzi_out, size_t capa
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "get_cloud while a tick_begin is pending");
-  bool pending;
-  const int idx = pin_front(ctx, &pending);     // a producer must not recycle the buffer while it is copied
-  struct Release { dddmr_rollout_ctx* c; ~Release() { release_cloud(c); } } release{ctx};
-  const uint32_t n = ctx->cloud_n[idx];
+  CloudPin pin(ctx);                            // a producer must not recycle the buffer while it is copied
+  const int idx = pin.idx();
+  const uint32_t n = pin.n_points();
   *n_points = n;
   if (!xyzi_out) return DDDMR_OK;
   if (capacity < n) return fail(ctx, DDDMR_ERR_CAPACITY, "get_cloud: capacity %zu < %u", capacity, n);
@@ -584,10 +628,8 @@ int dddmr_rollout_path_blocked(dddmr_rollout_ctx* ctx, const float* plan_xyzi, s
   *opinion = DDDMR_OPINION_PASS;
   if (blocked_flags) std::memset(blocked_flags, 0, n_plan);
   // pin the front cloud like a tick does
-  bool pending;
-  const int cidx = pin_front(ctx, &pending);
-  struct Release { dddmr_rollout_ctx* c; ~Release() { release_cloud(c); } } release{ctx};
-  const uint32_t n_points = ctx->cloud_n[cidx];
+  CloudPin pin(ctx);
+  const uint32_t n_points = pin.n_points();
   if (n_points <= 5 || n_plan == 0) return DDDMR_OK;                  // path_blocked_strategy.cpp:62-64
   BlockedParams b;
   b.n_points = (int)n_points;
@@ -614,14 +656,11 @@ int dddmr_rollout_path_blocked(dddmr_rollout_ctx* ctx, const float* plan_xyzi, s
       HIPCHK(ctx, hipMalloc(&ctx->blocked_plan, kBlockedMaxPlan * sizeof(float4)));
       HIPCHK(ctx, hipMalloc(&ctx->blocked_flags, (kBlockedMaxPlan / 32) * sizeof(uint32_t)));
     }
-    if (pending) {
-      HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->cloud_ready[cidx], 0));
-      cloud_wait_done(ctx, cidx);
-    }
+    HIPCHK(ctx, pin.wait_on(ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(ctx->blocked_plan, plan_xyzi, n_plan * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->blocked_flags, 0, (kBlockedMaxPlan / 32) * sizeof(uint32_t), ctx->stream));
     const int blocks = (int)std::min<uint32_t>(1024, (n_points + 255) / 256);
-    hipLaunchKernelGGL(k_path_blocked, dim3(blocks), dim3(256), 0, ctx->stream, b, ctx->cloud_dev[cidx],
+    hipLaunchKernelGGL(k_path_blocked, dim3(blocks), dim3(256), 0, ctx->stream, b, pin.dev(),
                        ctx->blocked_plan, ctx->blocked_flags);
     uint32_t words[kBlockedMaxPlan / 32];
     HIPCHK(ctx, hipMemcpyAsync(words, ctx->blocked_flags, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
@@ -670,11 +709,6 @@ int dddmr_rollout_set_prune_plan(dddmr_rollout_ctx* ctx, const double* poses, si
 
 namespace {
 
-void release_cloud(dddmr_rollout_ctx* c) {
-  std::lock_guard<std::mutex> lk(c->cloud_mu);
-  c->busy = -1;
-}
-
 void no_winner(dddmr_rollout_result* out) {
   std::memset(out, 0, sizeof(*out));
   out->planner_state = DDDMR_ALL_TRAJECTORIES_FAIL;
@@ -694,24 +728,15 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
   make_window(*th, *in, w);   // initialise(): velocity samples of this tick
 
   // The cloud's front buffer is pinned before the plan's capacity checks, because the plan needs its size.  No caller
-  // can tell: `busy` is -1 whenever a tick is enqueued (every other pinner holds tick_mu and releases before it
-  // returns, and every entry point refuses while a tick is pending), and the guard releases on any error return.
-  // (The "upload still pending" flag is only cleared once the stream wait below is enqueued: an early error return in
-  // between must not lose the ordering against copy_stream.)
-  bool pending;
-  const int cidx = pin_front(ctx, &pending);
-  struct Unbusy {          // releases the cloud buffer again if enqueueing fails half-way
-    dddmr_rollout_ctx* c;
-    bool armed = true;
-    ~Unbusy() { if (armed) release_cloud(c); }
-  } unbusy{ctx};
+  // can tell: the pin releases the buffer again on any error return (CloudPin).
+  CloudPin pin(ctx);
 
   TickPlan& p = ctx->pend.plan;
   DevTick& k = p.k;
   const int theory_id = (int)(th - ctx->theories.data());
   const bool exchange = ctx->comm || ctx->comm_loopback;
   std::string err;
-  const int rc = plan_tick(ctx->knobs, ctx->feedback, ctx->cfg, *th, theory_id, *in, w, ctx->cloud_n[cidx], ctx->plan_m,
+  const int rc = plan_tick(ctx->knobs, ctx->feedback, ctx->cfg, *th, theory_id, *in, w, pin.n_points(), ctx->plan_m,
                            ctx->plan_last, exchange, &p, &err);
   if (rc != DDDMR_OK) return fail(ctx, rc, "%s", err.c_str());
   if (ctx->seq == 3 && std::getenv("DDDMR_DEBUG_GRID"))
@@ -744,10 +769,7 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
       if (!ctx->traj_info) HIPCHK(ctx, hipMalloc(&ctx->traj_info, (size_t)ctx->cfg.max_trajectories * sizeof(TrajInfo)));
     }
   }
-  if (pending) {
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->cloud_ready[cidx], 0));
-    cloud_wait_done(ctx, cidx);
-  }
+  HIPCHK(ctx, pin.wait_on(ctx->stream));
 
   const auto prof_t1 = std::chrono::steady_clock::now();
   if (ctx->poison && k.n_local > 0) {
@@ -782,10 +804,10 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
   ctx->last_heading_rows = heading_rows;
   if (k.n_points > 0) {
     hipLaunchKernelGGL(k_bin_count, dim3(p.cnt_blocks + p.roll_blocks + (k.use_assign ? k.assign_groups : 0)), dim3(kBinThreads), roll_lds,
-                       ctx->stream, k, ctx->cloud_dev[cidx], ctx->cell_count, ctx->cell_start, ctx->pt_slot, ctx->tickets,
+                       ctx->stream, k, pin.dev(), ctx->cell_count, ctx->cell_start, ctx->pt_slot, ctx->tickets,
                        ctx->best_key, ctx->overflow, ctx->axes_dev, ctx->samples_dev, ctx->traj_info, ctx->st_sc,
                        ctx->st_xy, ctx->traj_load, ctx->assign, heading_rows);
-    hipLaunchKernelGGL(k_bin_scatter, dim3(p.bin_blocks), dim3(256), 0, ctx->stream, k, ctx->cloud_dev[cidx],
+    hipLaunchKernelGGL(k_bin_scatter, dim3(p.bin_blocks), dim3(256), 0, ctx->stream, k, pin.dev(),
                        ctx->pt_slot, ctx->cell_start, ctx->sorted, ctx->row_tab);
   } else {
     hipLaunchKernelGGL(k_bin_reset, dim3(1), dim3(256), 0, ctx->stream, k, ctx->cell_count, ctx->cell_start,
@@ -847,7 +869,7 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
     ctx->prof_ns[1] += std::chrono::duration<double, std::nano>(prof_t2 - prof_t1).count();
     ++ctx->prof_n;
   }
-  unbusy.armed = false;   // the cloud buffer stays pinned until tick_collect
+  pin.keep();             // the cloud buffer stays pinned until tick_collect
   ctx->pend.active = true;
   ctx->pend.timed = timed;
   ctx->pend.timed_all = timed_all;
@@ -858,7 +880,7 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
 int tick_collect(dddmr_rollout_ctx* ctx, dddmr_rollout_result* out) {
   if (!ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "tick_end without tick_begin");
   ctx->pend.active = false;
-  struct Release { dddmr_rollout_ctx* c; ~Release() { release_cloud(c); } } release{ctx};
+  CloudPin pin(ctx, CloudPin::kAdopted);   // releases the tick's cloud buffer on any return
   const TickPlan& p = ctx->pend.plan;
   const DevTick& k = p.k;
   no_winner(out);

@@ -63,7 +63,7 @@ class MarkingLayer:
         self._lp._check(self._lp._lib.dddmr_rollout_marking_reset(self._lp._ctx))
 
     def route_counts(self) -> dict:
-        """Updates that ran fused (four launches) / on the general route, launches of the last update."""
+        """Updates that ran fused (five launches, observations of up to 32768 points) / on the general route, launches of the last update."""
         a, b, n = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
         self._lp._check(self._lp._lib.dddmr_rollout_marking_route_counts(self._lp._ctx, C.byref(a), C.byref(b), C.byref(n)))
         return {"fused": int(a.value), "general": int(b.value), "launches_last_update": int(n.value)}

@@ -940,7 +940,7 @@ int dddmr_rollout_marking_get_voxels(dddmr_rollout_ctx* ctx, int32_t* xyz_out, s
    lethal set (lethal_map_ keys) as one byte per ground node. */
 int dddmr_rollout_marking_get_dgraph(dddmr_rollout_ctx* ctx, double* values_out, size_t capacity);
 int dddmr_rollout_marking_get_lethal(dddmr_rollout_ctx* ctx, uint8_t* flags_out, size_t capacity);
-/* Which route the updates took (observations of up to 16384 points run fused: six launches, no
+/* Which route the updates took (observations of up to 32768 points run fused: five launches, no
    copies; larger ones take the general route with library sorts; DDDMR_MARKING_ROUTE=general|fused
    forces one) and how many kernels / memsets the last update launched.  Diagnostics, any pointer
    may be NULL. */

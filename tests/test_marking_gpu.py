@@ -36,7 +36,7 @@ def _vset(v):
 @pytest.fixture(autouse=True, params=["fused", "general"])
 def route(request, monkeypatch):
     """Every test runs on both routes of dddmr_rollout_marking_update: `fused` (five launches, observations of up to
-    16384 points: csrc/marking_fused.hip.h) and `general` (library sorts, any size: csrc/marking.hip.h).  The layer
+    32768 points: csrc/marking_fused.hip.h) and `general` (library sorts, any size: csrc/marking.hip.h).  The layer
     reads DDDMR_MARKING_ROUTE when it is created."""
     monkeypatch.setenv("DDDMR_MARKING_ROUTE", request.param)
     return request.param
@@ -434,6 +434,40 @@ def test_update_next_to_a_pending_tick_gives_the_serial_results():
         assert e.value.code == K.ERR_STATE
         assert fields(b.tick_end())[:2] == fields(rb)[:2]
         np.testing.assert_array_equal(la.dgraph(), lb.dgraph())
+
+
+def test_fused_update_launch_counts(monkeypatch):
+    """What a fused update launches, by the kind of update (csrc/marking_plan.hip.h plans it, update_fused issues it):
+    a marked update takes the five launches (grid, clear, seed, partition, commit); one of <= 5 points with nothing
+    alive only the grid launch's slot blocks and the commit launch's lone walk block; one of <= 5 points with markings
+    alive also the ray tests and their removePCPtr in the seed launch.  A scene this small never triggers the store's
+    housekeeping, whose kernels would count too.  The numbers were read from update_fused and confirmed on the commit
+    before the launch plan was split off, which reported 2, 5, 5, 4 for these four updates on an MI355X."""
+    monkeypatch.setenv("DDDMR_MARKING_ROUTE", "fused")
+    sc = scenes.bench_scene("C2")
+    cfg = marking.shipped_config()
+    ground = marking.ground_lattice(half=4.0)
+    mo = oracle.MarkingOracle(cfg, ground, np.zeros((0, 3), np.float32))
+    t_gb = (0.0, 0.0, 0.0, 0, 0, 0, 1)
+    tiny = np.array([[-2.0, 0.1 * i, 0.5, 0] for i in range(4)], dtype=np.float32)
+    # an obstacle of ~200 points: a 1 m x 1 m wall patch 2 m to the robot's left (the scan's effective azimuth leaves out
+    # +-30 degrees dead ahead), 0.07 m between neighbours (one cluster at tolerance 0.1)
+    xx, zz = np.meshgrid(np.arange(14) * 0.07 - 0.45, np.arange(14) * 0.07 + 0.1)
+    wall = np.stack([xx.ravel(), np.full(xx.size, 2.0), zz.ravel(), np.zeros(xx.size)], axis=1).astype(np.float32)
+    got, alive = [], []
+    with LocalPlanner([sc.theory], max_points=1 << 12) as lp:
+        layer = marking.MarkingLayer(lp, cfg, ground, np.zeros((0, 3), np.float32))
+        for obs in (tiny, wall, wall, tiny):
+            lp.set_cloud(obs)
+            st = layer.update(T_BS, t_gb)
+            so = mo.update(obs[:, :3], T_BS, t_gb)
+            assert (st.n_observation, st.n_clusters, st.n_marked, st.n_cleared, st.n_alive) == \
+                   (so.n_observation, so.n_clusters, so.n_marked, so.n_cleared, so.n_alive)
+            got.append(layer.route_counts()["launches_last_update"])
+            alive.append(st.n_alive)
+        assert layer.route_counts()["fused"] == 4
+    assert alive[0] == 0 and alive[1] > 0 and alive[2] > 0, alive     # (the fourth update meets markings alive)
+    assert got == [2, 5, 5, 4], got
 
 
 @pytest.mark.parametrize("offset", [(1500.0, -800.0, 30.0), (-4200.5, 3100.25, -12.0)])
