@@ -14,9 +14,19 @@
 #include <vector>
 #include "ref_eigen.hpp"
 
+// Point-type declaration macros: only enough for mcl_3dl's utilities.h to declare its pose point type, which the
+// particle-measure unit never instantiates (no ASSUMPTIONS.md row: no arithmetic behind them).
+#define PCL_ADD_POINT4D float x; float y; float z; float ref_shim_pad_;
+#define PCL_ADD_INTENSITY float intensity
+#define EIGEN_MAKE_ALIGNED_OPERATOR_NEW
+#define EIGEN_ALIGN16 __attribute__((aligned(16)))
+#define POINT_CLOUD_REGISTER_POINT_STRUCT(name, fields)
+
 namespace pcl {
 struct PointXYZ { float x = 0.f, y = 0.f, z = 0.f; };
 struct PointXYZI { float x = 0.f, y = 0.f, z = 0.f, intensity = 0.f; };
+// pcl::Normal: three floats read by name (no ASSUMPTIONS.md row: plain storage)
+struct Normal { float normal_x = 0.f, normal_y = 0.f, normal_z = 0.f, curvature = 0.f; };
 
 template <class PointT> class PointCloud {
  public:
@@ -62,14 +72,17 @@ template <class PointT> void getMinMax3D(const PointCloud<PointT>& c, PointT& mn
 //  row 2: squared distance = L2_Simple<float>, diff*diff accumulated in x, y, z order in float;
 //  row 1: radiusSearch(p, double r) hands static_cast<float>(r * r) to FLANN, which keeps a point iff dist < r2;
 //         results sorted by distance (PCL's default), equal distances by index;
-//  row 3: nearestKSearch is exact (eps = 0); on equal distances the lowest index.
+//  row 3: nearestKSearch is exact (eps = 0); on equal distances the lowest index;
+//  row 19: radiusSearch(..., max_nn) with 0 < max_nn < cloud size keeps the max_nn closest of the points inside the
+//         radius (FLANN's KNNRadiusResultSet), max_nn = 0 or >= the cloud size keeps all; both output vectors are
+//         resized to the count kept (to 0 when nothing is inside the radius).
 template <class PointT> class KdTreeFLANN {
  public:
   using Ptr = std::shared_ptr<KdTreeFLANN<PointT>>;
   using PointCloudConstPtr = std::shared_ptr<const PointCloud<PointT>>;
   void setInputCloud(const PointCloudConstPtr& cloud) { cloud_ = cloud; cell_ = 0.0; grid_.clear(); }
   int radiusSearch(const PointT& p, double radius, std::vector<int>& k_indices, std::vector<float>& k_sqr_distances,
-                   unsigned int = 0) const {
+                   unsigned int max_nn = 0) const {
     const float r2 = static_cast<float>(radius * radius);
     k_indices.clear();
     k_sqr_distances.clear();
@@ -92,6 +105,7 @@ template <class PointT> class KdTreeFLANN {
           }
         }
     std::sort(hits.begin(), hits.end());
+    if (max_nn != 0 && max_nn < cloud_->points.size() && hits.size() > max_nn) hits.resize(max_nn);
     for (auto& h : hits) { k_indices.push_back(h.second); k_sqr_distances.push_back(h.first); }
     return (int)hits.size();
   }

@@ -12,6 +12,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace rclcpp {
@@ -59,6 +60,7 @@ class Parameter {
   Parameter(std::string n, ParameterValue v) : name_(std::move(n)), v_(std::move(v)) {}
   const std::vector<double>& as_double_array() const { return v_.as_double_array(); }
   double as_double() const { return v_.as<double>(); }
+  long as_int() const { return v_.as<long>(); }
   bool as_bool() const { return v_.as<bool>(); }
   const std::string& as_string() const { return v_.as_string(); }
   const std::string& get_name() const { return name_; }
@@ -122,12 +124,53 @@ class NodeLoggingInterface {
   using SharedPtr = std::shared_ptr<NodeLoggingInterface>;
   Logger get_logger() const { return Logger(); }
 };
+// NodeParametersInterface over a Node's parameter map (the launch file's role is Node::set_override, as above)
+class NodeParametersInterface {
+ public:
+  using SharedPtr = std::shared_ptr<NodeParametersInterface>;
+  explicit NodeParametersInterface(Node::SharedPtr node) : node_(std::move(node)) {}
+  const ParameterValue& declare_parameter(const std::string& n, const ParameterValue& dflt) {
+    return node_->declare_parameter(n, dflt);
+  }
+  Parameter get_parameter(const std::string& n) const { return node_->get_parameter(n); }
+
+ private:
+  Node::SharedPtr node_;
+};
 }  // namespace node_interfaces
 struct Time { double s = 0.0; };
 }  // namespace rclcpp
 
 // Logging does nothing: the arguments are not evaluated (the reference's log arguments have no side effects).
+// Except RCLCPP_DEBUG in a library built with -DREF_SHIM_TRACE_DEBUG: each call appends one record to a per-thread
+// buffer, the number of its numeric arguments and then those arguments widened to double (the logger, the format and
+// any non-numeric argument are dropped), so a driver reads a function's intermediate values where the reference logs
+// them, without a change to the reference's text.  No ASSUMPTIONS.md row: nothing of rclcpp's arithmetic is involved.
+namespace ref_shim_trace {
+inline std::vector<double>& buffer() {
+  static thread_local std::vector<double> b;
+  return b;
+}
+template <class T> inline void put(std::vector<double>& b, std::size_t& n, const T& v) {
+  if constexpr (std::is_arithmetic_v<T>) {
+    b.push_back(static_cast<double>(v));
+    ++n;
+  }
+}
+template <class... A> inline void record(const char*, const A&... a) {
+  std::vector<double>& b = buffer();
+  const std::size_t at = b.size();
+  std::size_t n = 0;
+  b.push_back(0.0);
+  (put(b, n, a), ...);
+  b[at] = static_cast<double>(n);
+}
+}  // namespace ref_shim_trace
+#ifdef REF_SHIM_TRACE_DEBUG
+#define RCLCPP_DEBUG(logger, ...) ::ref_shim_trace::record(__VA_ARGS__)
+#else
 #define RCLCPP_DEBUG(...) do {} while (0)
+#endif
 #define RCLCPP_INFO(...) do {} while (0)
 #define RCLCPP_WARN(...) do {} while (0)
 #define RCLCPP_ERROR(...) do {} while (0)

@@ -18,10 +18,50 @@ inline tf2Scalar tf2Asin(tf2Scalar x) {
   return std::asin(x);
 }
 
+// tf2::Vector3 (row 14): three doubles; dot sums x, y, z left to right, cross is the closed form, length = sqrt(dot),
+// normalized() returns *this / length() and leaves *this alone
+class Vector3 {
+ public:
+  Vector3() = default;
+  Vector3(const tf2Scalar& x, const tf2Scalar& y, const tf2Scalar& z) : v_{x, y, z} {}
+  const tf2Scalar& x() const { return v_[0]; }
+  const tf2Scalar& y() const { return v_[1]; }
+  const tf2Scalar& z() const { return v_[2]; }
+  tf2Scalar dot(const Vector3& o) const { return v_[0] * o.v_[0] + v_[1] * o.v_[1] + v_[2] * o.v_[2]; }
+  tf2Scalar length2() const { return dot(*this); }
+  tf2Scalar length() const { return std::sqrt(length2()); }
+  Vector3 cross(const Vector3& o) const {
+    return Vector3(v_[1] * o.v_[2] - v_[2] * o.v_[1], v_[2] * o.v_[0] - v_[0] * o.v_[2], v_[0] * o.v_[1] - v_[1] * o.v_[0]);
+  }
+  Vector3 normalized() const {
+    const tf2Scalar s = tf2Scalar(1.0) / length();
+    return Vector3(v_[0] * s, v_[1] * s, v_[2] * s);
+  }
+
+ private:
+  tf2Scalar v_[3] = {0, 0, 0};
+};
+
 class Quaternion {
  public:
   Quaternion() = default;
   Quaternion(tf2Scalar x, tf2Scalar y, tf2Scalar z, tf2Scalar w) : q_{x, y, z, w} {}
+  // Quaternion(axis, angle) -> setRotation (row 14): s = sin(angle / 2) / |axis|, a zero axis gives NaN or inf
+  Quaternion(const Vector3& axis, const tf2Scalar& angle) {
+    const tf2Scalar d = axis.length();
+    const tf2Scalar s = std::sin(angle * tf2Scalar(0.5)) / d;
+    q_[0] = axis.x() * s;
+    q_[1] = axis.y() * s;
+    q_[2] = axis.z() * s;
+    q_[3] = std::cos(angle * tf2Scalar(0.5));
+  }
+  tf2Scalar length() const { return std::sqrt(length2()); }
+  // normalize = operator/=(length()) = operator*=(1 / length()) (row 14)
+  Quaternion& normalize() {
+    const tf2Scalar s = tf2Scalar(1.0) / length();
+    q_[0] *= s; q_[1] *= s; q_[2] *= s; q_[3] *= s;
+    return *this;
+  }
   tf2Scalar x() const { return q_[0]; }
   tf2Scalar y() const { return q_[1]; }
   tf2Scalar z() const { return q_[2]; }
@@ -33,8 +73,20 @@ class Quaternion {
   tf2Scalar q_[4] = {0, 0, 0, 1};
 };
 
+// the Hamilton product, every component's four terms summed left to right (row 14)
+inline Quaternion operator*(const Quaternion& a, const Quaternion& b) {
+  return Quaternion(a.w() * b.x() + a.x() * b.w() + a.y() * b.z() - a.z() * b.y(),
+                    a.w() * b.y() + a.y() * b.w() + a.z() * b.x() - a.x() * b.z(),
+                    a.w() * b.z() + a.z() * b.w() + a.x() * b.y() - a.y() * b.x(),
+                    a.w() * b.w() - a.x() * b.x() - a.y() * b.y() - a.z() * b.z());
+}
+
 class Matrix3x3 {
  public:
+  // getRPY = getEulerYPR with the arguments in the other order (row 13)
+  void getRPY(tf2Scalar& roll, tf2Scalar& pitch, tf2Scalar& yaw, unsigned int solution_number = 1) const {
+    getEulerYPR(yaw, pitch, roll, solution_number);
+  }
   // Matrix3x3(q) -> setRotation(q): s = 2 / |q|^2 (row 13)
   explicit Matrix3x3(const Quaternion& q) {
     const tf2Scalar d = q.length2();
@@ -49,17 +101,18 @@ class Matrix3x3 {
     for (int i = 0; i < 9; ++i) m_[i / 3][i % 3] = v[i];
   }
   // getEulerYPR, solution 1: pitch = -asin(m20), yaw = atan2(m10 / cos pitch, m00 / cos pitch); gimbal lock
-  // (|m20| >= 1): yaw = 0, pitch = +-pi/2, roll from atan2(m21, m22) (row 13)
+  // (|m20| >= 1): yaw = 0, pitch = +-pi/2, roll = atan2(m21, m22) (row 13: tf2 takes the bare difference angle
+  // where Bullet's btMatrix3x3 adds the pitch to it)
   void getEulerYPR(tf2Scalar& yaw, tf2Scalar& pitch, tf2Scalar& roll, unsigned int = 1) const {
     if (std::fabs(m_[2][0]) >= 1) {
       yaw = 0;
       const tf2Scalar delta = std::atan2(m_[2][1], m_[2][2]);
       if (m_[2][0] < 0) {
         pitch = M_PI / tf2Scalar(2.0);
-        roll = pitch + delta;
+        roll = delta;
       } else {
         pitch = -M_PI / tf2Scalar(2.0);
-        roll = -pitch + delta;
+        roll = delta;
       }
     } else {
       pitch = -tf2Asin(m_[2][0]);

@@ -1,0 +1,1 @@
+// Stand-in at the include path the reference uses: empty, the particle-measure unit transforms no sensor message.

@@ -2,13 +2,21 @@
 (dddmr_mcl_3dl/src/lidar_measurement_model_likelihood.cpp:86-252) for a batch of particles, with the lambda around it
 (src/mcl_3dl.cpp:476-498): float32 where the reference is float, float64 where it is double.
 
-UNPINNED: the function needs PCL, FLANN and tf2, none of which can be built beside this repository, so nothing
-compiled from the reference checks this file.  What it assumes about them:
-  * pcl::KdTreeFLANN::radiusSearch: FLANN's float L2_Simple distance ((dx*dx + dy*dy) + dz*dz), neighbours with
-    d2 < static_cast<float>(radius * radius), sorted by ascending d2; the order of equal distances is not defined
-    (ranked by ground index here: `n_tied` counts where that could show).
-  * tf2::Quaternion(axis, angle) divides by the axis' length; Quaternion::normalize multiplies by 1 / length;
-    Matrix3x3(q).getRPY is setRotation + getEulerYPR "solution 1", whose gimbal branch takes roll = atan2(m21, m22).
+PINNED to the reference's own code: lidar_measurement_model_likelihood.cpp, with state_6dof.h, quat.h, vec3.h and pf.h,
+compiled unmodified against the stand-ins of oracle/ref/shim/ (oracle/ref/ref_mcl_driver.cpp, `make -C oracle ref`).
+tests/test_mcl_measure_pin_cpu.py holds this file to it on bits -- quality, counts, branch, the float averages of the
+normals, roll and roll_diff as doubles, likelihood, and State6DOF::transform through the reference's Quat and Vec3 -- and
+tests/golden/REF_MCL_*.npz carry its answers to machines without the reference.  So the function's logic,
+its float / double promotions and the transform are pinned.  Not pinned:
+  * what the stand-ins encode of FLANN and tf2 (oracle/ASSUMPTIONS.md rows 1-3, 13, 14, 19):
+    pcl::KdTreeFLANN::radiusSearch is FLANN's float L2_Simple distance ((dx*dx + dy*dy) + dz*dz), neighbours with
+    d2 < static_cast<float>(radius * radius), sorted by ascending d2, with max_nn = 1 the nearest of them and the
+    output vectors sized to the count found; tf2::Quaternion(axis, angle) divides by the axis' length;
+    Quaternion::normalize multiplies by 1 / length; Matrix3x3(q).getRPY is setRotation + getEulerYPR "solution 1",
+    whose gimbal branch takes roll = atan2(m21, m22) (no case reaches that branch);
+  * the order of equal ground distances (ranked by ground index here and in the stand-in: `n_tied` counts where that
+    could show, and the cases are drawn until it is 0);
+  * the deliberate differences below, which the pin's cases leave out.
 State6DOF::transform follows include/mcl_3dl/quat.h:87-93,131-143,175-178 and state_6dof.h:188-198 operation by
 operation.
 
@@ -111,8 +119,9 @@ class Cloud:
         return out
 
 
-def weight_healthy(avg, rot, d2_nn):
-    """:133-177 -> (pos_weight float32, n_fragile)"""
+def weight_healthy(avg, rot, d2_nn, report=None):
+    """:133-177 -> (pos_weight float32, n_fragile); report, when given, receives roll and roll_diff (doubles) where
+    the 3x test lets the chain run"""
     avg_nx, avg_ny, avg_nz = (float(v) for v in avg)
     fragile = 0
     for a in (avg_nx, avg_ny):
@@ -165,6 +174,8 @@ def weight_healthy(avg, rot, d2_nn):
         roll_diff = ar
     else:
         roll_diff = 0.55
+    if report is not None:
+        report["roll"], report["roll_diff"] = roll, roll_diff
     wd = (1.0 - float(np.sqrt(F(d2_nn)))) * (1 - roll_diff)
     if wd != 0.0 and abs(wd) < MARGIN:
         fragile += 1
@@ -176,7 +187,9 @@ def weight_healthy(avg, rot, d2_nn):
 
 def measure(cfg: Config, map_xyz, ground_xyz, ground_normals, flat_xyz, less_sharp_xyzi, states) -> dict:
     """-> dict of per-particle arrays: likelihood, quality, score, pos_weight (float32), n_match, n_ground (uint32),
-    healthy, bad (bool), n_fragile, n_tied (int); and quality_min / quality_max, n_bad"""
+    healthy, bad (bool), n_fragile, n_tied (int); the intermediate values the reference logs, NaN where a particle's
+    branch has none: avg [N,3] (float32, the averaged normal), roll, roll_diff (float64); and quality_min /
+    quality_max, n_bad"""
     mdm, mdf = F(cfg.match_dist_min), F(cfg.match_dist_flat)
     r2_match = F(float(mdm) * float(mdm))
     rg = float(cfg.radius_of_ground_search)
@@ -190,7 +203,8 @@ def measure(cfg: Config, map_xyz, ground_xyz, ground_normals, flat_xyz, less_sha
     assert n_obs > 0
     out = dict(likelihood=np.zeros(N, F), quality=np.zeros(N, F), score=np.zeros(N, F), pos_weight=np.zeros(N, F),
                n_match=np.zeros(N, np.uint32), n_ground=np.zeros(N, np.uint32), healthy=np.zeros(N, bool), bad=np.zeros(N, bool),
-               n_fragile=np.zeros(N, np.int64), n_tied=np.zeros(N, np.int64))
+               n_fragile=np.zeros(N, np.int64), n_tied=np.zeros(N, np.int64), avg=np.full((N, 3), np.nan, F),
+               roll=np.full(N, np.nan), roll_diff=np.full(N, np.nan))
     good = np.isfinite(states).all(axis=1)
     out["bad"] = ~good
     moved_flat = transform(states[:, :3], states[:, 3:], flat) if len(flat) else np.zeros((N, 0, 3), F)
@@ -218,7 +232,11 @@ def measure(cfg: Config, map_xyz, ground_xyz, ground_normals, flat_xyz, less_sha
             else:
                 near = cground.nearest_many(pose[None, :], float(np.sqrt(NN_D2)), NN_D2)[0]
                 d2_nn = near if np.isfinite(near) else F(4.0)
-            pw, fragile = weight_healthy(avg, states[p, 3:], d2_nn)
+            report = {}
+            pw, fragile = weight_healthy(avg, states[p, 3:], d2_nn, report)
+            out["avg"][p] = avg
+            if report:
+                out["roll"][p], out["roll_diff"][p] = report["roll"], report["roll_diff"]
         else:
             near = cmap.nearest_many(pose[None, :], float(np.sqrt(NN_D2)), NN_D2)[0]
             pw = F(0.01)

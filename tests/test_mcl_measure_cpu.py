@@ -1,5 +1,5 @@
-"""CPU tests of the particle-measure restatement (tests/helpers/mcl_measure_ref.py, UNPINNED: it follows mcl_3dl's
-measure() by reading, nothing compiled from the reference checks it), of the generated cases' input conditions, of the
+"""CPU tests of the particle-measure restatement (tests/helpers/mcl_measure_ref.py; what pins it to mcl_3dl's own
+measure() compiled from the reference is tests/test_mcl_measure_pin_cpu.py), of the generated cases' input conditions, of the
 library's exports and of the ROS-side bridge."""
 import ctypes as C
 import os

@@ -1,6 +1,7 @@
 """GPU parity of the particle filter's lidar likelihood (dddmr_rollout_mcl_*, dddmr_navigation_amd.localization) against
-the NumPy restatement of mcl_3dl's measure() (tests/helpers/mcl_measure_ref.py, UNPINNED: PCL, FLANN and tf2 cannot be
-built here).
+the NumPy restatement of mcl_3dl's measure() (tests/helpers/mcl_measure_ref.py, pinned on bits to the reference's own
+code compiled against library stand-ins: tests/test_mcl_measure_pin_cpu.py; the device against that build's recorded
+answers: tests/test_mcl_measure_pin_gpu.py).
 
 For EVERY particle of every case: score_like, the match count, the ground count, the branch and the quality are
 compared on bits (the same IEEE float operations in the same order on both sides); pos_weight within 1 float ulp (its
