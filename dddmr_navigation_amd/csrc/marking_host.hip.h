@@ -592,11 +592,7 @@ int marking_update_on(dddmr_rollout_ctx* ctx, MarkingState* m, const float4* obs
   // An error return below may leave work enqueued on m->cur that reads `obs` and the layer's buffers: wait for it, so
   // that the caller may release the observation and the next call finds the stream idle (the status of that wait does
   // not matter: the error being returned is the one to report).  The returns past the update's own wait are disarmed.
-  struct Drain {
-    hipStream_t st;
-    bool armed = true;
-    ~Drain() { if (armed) (void)hipStreamSynchronize(st); }
-  } drain{m->cur};
+  Drain drain{m->cur};
   const int rc = fused ? update_fused(ctx, m, f, obs, n_obs, timed, out) : update_general(ctx, m, f, obs, n_obs, timed, out);
   if (rc != DDDMR_OK) return rc;
   m->store.pool_used = out.pool_used;

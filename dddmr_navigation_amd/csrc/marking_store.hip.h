@@ -16,20 +16,6 @@ namespace {
 
 using namespace dddmr;
 
-// Device allocations are recorded where they are made: the owner's *_free walks the vector.  (Swapping a main array with
-// its _alt array leaves the set of pointers as it is.)
-using DevAllocs = std::vector<void*>;
-template <class T>
-hipError_t dev_alloc(DevAllocs& owner, T** p, size_t count) {
-  const hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
-  if (e == hipSuccess) owner.push_back(*p);
-  return e;
-}
-void dev_free(DevAllocs& owner) {
-  for (void* q : owner) (void)hipFree(q);
-  owner.clear();
-}
-
 struct StoreBuf {
   MarkStore s{};
   MarkHead head{};                         // null pointers: a store without heads

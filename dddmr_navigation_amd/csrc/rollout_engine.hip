@@ -4,6 +4,9 @@
 // Host responsibilities (cheap, per tick): planning the tick (tick_plan.hip.h: the theory's initialise(), the local
 // costmap tile, the launch shapes) and launching the five kernels of rollout_kernels.hip.h.
 // Everything proportional to N_traj x N_steps or to the cloud runs on the GPU.
+// Here: the context, create / destroy, the cloud triple buffer, the tick and its read-backs.  The multi-rank exchange is
+// in rollout_comm.hip.h, the diagnostics in rollout_diag.hip.h, the sensor sources and the modules in the headers
+// included at the end.
 //
 // Citations are relative to /root/reference/src/dddmr_local_planner/.
 #include <hip/hip_runtime.h>
@@ -69,6 +72,7 @@ struct dddmr_rollout_ctx {
   std::vector<dddmr_theory_config> theories;
   int device = 0;
   hipStream_t stream = nullptr, copy_stream = nullptr;
+  DevAllocs mem;           // every device allocation of the context itself (the modules and sources own theirs)
   // k_rollout state arrays, grown on demand: [n_local][max steps of the tick] (of st_sc a tick with shared heading rows
   // fills only the first nth rows, one per angular sample)
   TrajInfo* traj_info = nullptr;
@@ -100,7 +104,7 @@ struct dddmr_rollout_ctx {
   DevResult* result_dev = nullptr;   // device alias of result_host (host-mapped)
   uint32_t* tickets = nullptr;       // [0] binning ticket, [1] scoring ticket
   // load feedback (device): per-trajectory load of the last tick, tile assignment of this one
-  float4* blocked_plan = nullptr;      // PathBlockedStrategy scratch (lazily allocated)
+  float4* blocked_plan = nullptr;      // PathBlockedStrategy scratch: kBlockedMaxPlan points, a flag bit each
   uint32_t* blocked_flags = nullptr;
   uint32_t* traj_load = nullptr;
   uint32_t* assign = nullptr;
@@ -111,6 +115,8 @@ struct dddmr_rollout_ctx {
   bool poison = false;
   // DDDMR_HOST_PROF=1: host-side time of the tick's stages, printed at destroy
   bool host_prof = false;
+  bool debug_grid = false;   // DDDMR_DEBUG_GRID: the third tick prints its k_score shape
+  int ceil_blocks = 0;       // DDDMR_CEIL_BLOCKS: workgroups of the stream-ceiling kernels (0: sized by the buffers)
   double prof_ns[4] = {0, 0, 0, 0};
   uint64_t prof_n = 0;
   double* poses_dev = nullptr;
@@ -168,7 +174,6 @@ struct dddmr_rollout_ctx {
   int timing = 1;   // DDDMR_TIMING: 0 no HIP events, 1 around k_score (score_ms), 2 also around the whole tick
   int timing_every = 1;   // DDDMR_TIMING_EVERY: record the events on every n-th tick only
   int spin = 1;     // DDDMR_SPIN: poll the host-mapped result instead of hipStreamSynchronize
-  bool heading_rows = true;   // DDDMR_HEADING_ROWS=0: a heading chain per trajectory on every tick (rollout_kernels.hip.h)
   int last_heading_rows = -1; // what the last launched tick did (dddmr_rollout_heading_rows)
   uint32_t seq = 0;
   DevResult last_result{};   // host copy of the last COLLECTED tick's result
@@ -244,48 +249,16 @@ class CloudPin {
   bool need_wait_ = false, is_front_ = false;
 };
 
-void release_source(dddmr_rollout_ctx* c, int id);   // sensor_sources.hip.h
-
-// RCCL entry points, resolved at run time: the engine has no link-time dependency on librccl (hosts
-// that never call dddmr_rollout_comm_init do not need it), and a process that already holds a copy --
-// PyTorch ships its own librccl.so -- shares it instead of loading a second one.
-struct Rccl {
-  void* handle = nullptr;
-  ncclResult_t (*get_unique_id)(ncclUniqueId*) = nullptr;
-  ncclResult_t (*comm_init_rank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-  ncclResult_t (*comm_destroy)(ncclComm_t) = nullptr;
-  ncclResult_t (*comm_count)(const ncclComm_t, int*) = nullptr;
-  ncclResult_t (*all_reduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-  const char* (*error_string)(ncclResult_t) = nullptr;
-  std::string why;
-  bool ok() const { return handle != nullptr; }
+// An error return may leave work enqueued that reads a pinned cloud buffer: while armed, the guard waits for the stream
+// when it goes out of scope, so that a CloudPin declared BEFORE it releases a buffer nothing reads any more and the next
+// call finds the stream idle.  Disarmed where the function has waited itself or handed the pin to the pending tick.
+struct Drain {
+  hipStream_t st;
+  bool armed = true;
+  ~Drain() { if (armed) (void)hipStreamSynchronize(st); }
 };
-Rccl& rccl() {
-  static Rccl r;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    const char* names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1", "/opt/rocm/lib/librccl.so"};
-    void* h = nullptr;
-    if (const char* e = std::getenv("DDDMR_RCCL_LIB")) h = dlopen(e, RTLD_NOW | RTLD_GLOBAL);
-    for (const char* n : names) {
-      if (h) break;
-      h = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
-    }
-    if (!h) { r.why = std::string("librccl not found: ") + (dlerror() ? dlerror() : "?"); return; }
-    r.get_unique_id = reinterpret_cast<decltype(r.get_unique_id)>(dlsym(h, "ncclGetUniqueId"));
-    r.comm_init_rank = reinterpret_cast<decltype(r.comm_init_rank)>(dlsym(h, "ncclCommInitRank"));
-    r.comm_destroy = reinterpret_cast<decltype(r.comm_destroy)>(dlsym(h, "ncclCommDestroy"));
-    r.comm_count = reinterpret_cast<decltype(r.comm_count)>(dlsym(h, "ncclCommCount"));
-    r.all_reduce = reinterpret_cast<decltype(r.all_reduce)>(dlsym(h, "ncclAllReduce"));
-    r.error_string = reinterpret_cast<decltype(r.error_string)>(dlsym(h, "ncclGetErrorString"));
-    if (!r.get_unique_id || !r.comm_init_rank || !r.comm_destroy || !r.comm_count || !r.all_reduce || !r.error_string) {
-      r.why = "librccl lacks an expected symbol";
-      return;
-    }
-    r.handle = h;
-  });
-  return r;
-}
+
+void release_source(dddmr_rollout_ctx* c, int id);   // sensor_sources.hip.h
 
 int fail(dddmr_rollout_ctx* ctx, int code, const char* fmt, ...) {
   char buf[512];
@@ -308,26 +281,51 @@ int fail(dddmr_rollout_ctx* ctx, int code, const char* fmt, ...) {
                   __FILE__, __LINE__);                                                      \
   } while (0)
 
+int refuse_pending(dddmr_rollout_ctx* ctx, const char* what) {
+  return fail(ctx, DDDMR_ERR_STATE, "%s while a tick_begin is pending", what);
+}
+// An entry point that must not run beside a pending tick: holds tick_mu from here on, refuses under its name.
+#define TICK_IDLE(ctx, what)                        \
+  std::lock_guard<std::mutex> tk((ctx)->tick_mu);   \
+  if ((ctx)->pend.active) return refuse_pending(ctx, what)
+
 const dddmr_theory_config* find_theory(const dddmr_rollout_ctx* ctx, const char* name) {
   for (const auto& t : ctx->theories)
     if (std::strncmp(t.name, name, DDDMR_NAME_LEN) == 0) return &t;
   return nullptr;
 }
 
+// Every DDDMR_* variable this file listens to, read once per context, before its first HIP call.  (DDDMR_RCCL_LIB stays
+// with rccl(), which runs without a context; the modules read their own.)
+void read_env(dddmr_rollout_ctx* ctx) {
+  TickKnobs& kn = ctx->knobs;
+  if (const char* e = std::getenv("DDDMR_CELL")) {
+    const float v = (float)std::atof(e);
+    if (v > 0.01f && v < 10.f) { kn.cell_size = v; kn.cell_forced = true; }
+  }
+  if (const char* e = std::getenv("DDDMR_TILE")) kn.tile_override = std::atoi(e);
+  if (const char* e = std::getenv("DDDMR_RT")) kn.rt_override = std::atoi(e);
+  if (const char* e = std::getenv("DDDMR_THREADS")) kn.threads_override = std::atoi(e) == 512 ? 512 : 256;
+  if (const char* e = std::getenv("DDDMR_TAIL_ROUND")) kn.tail_round = std::atoi(e) != 0;
+  if (const char* e = std::getenv("DDDMR_HEADING_ROWS")) kn.heading_rows = std::atoi(e) != 0;
+  if (const char* e = std::getenv("DDDMR_FINAL")) kn.final_mode = std::atoi(e) ? 1 : 0;
+  if (const char* e = std::getenv("DDDMR_PROBE")) kn.probe_mode = std::atoi(e) ? 1 : 0;
+  if (const char* e = std::getenv("DDDMR_TIMING")) ctx->timing = std::atoi(e);
+  if (const char* e = std::getenv("DDDMR_TIMING_EVERY")) ctx->timing_every = std::max(1, std::atoi(e));
+  if (const char* e = std::getenv("DDDMR_SPIN")) ctx->spin = std::atoi(e);
+  const struct { const char* name; bool* on; } given[] = {   // switched on by being set, to whatever
+      {"DDDMR_NO_ASSIGN", &kn.no_assign}, {"DDDMR_NO_BOXFAST", &kn.no_boxfast}, {"DDDMR_NO_TAB", &kn.no_tab},
+      {"DDDMR_GNZ_ONE", &kn.gnz_one},     {"DDDMR_POISON", &ctx->poison},       {"DDDMR_HOST_PROF", &ctx->host_prof},
+      {"DDDMR_DEBUG_GRID", &ctx->debug_grid}};
+  for (const auto& g : given) *g.on = std::getenv(g.name) != nullptr;
+  if (const char* e = std::getenv("DDDMR_CEIL_BLOCKS")) ctx->ceil_blocks = std::max(1, std::atoi(e));
+}
+
 }  // namespace
 
-extern "C" {
+#include "rollout_comm.hip.h"
 
-#ifdef DDDMR_PHASE_STAMPS
-// diagnostic build only: copy the per-workgroup phase stamps of the last k_score launch
-int dddmr_rollout_diag_stamps(unsigned long long* out, size_t n_words) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), n_words * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
-}
-// ... and of the last k_bin_count launch (binning, assignment and rollout workgroups)
-int dddmr_rollout_diag_rstamps(unsigned long long* out, size_t n_words) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rstamps), n_words * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
-}
-#endif
+extern "C" {
 
 const char* dddmr_rollout_version(void) { return "dddmr-rollout-mi355x 0.1 (gfx950)"; }
 
@@ -389,34 +387,17 @@ void dddmr_rollout_destroy(dddmr_rollout_ctx* ctx) {
   if (ctx->dlayer) { depth_layer_free(ctx->dlayer); ctx->dlayer = nullptr; }
   if (ctx->mcl) { mcl_free(ctx->mcl); ctx->mcl = nullptr; }
   if (ctx->comm) (void)rccl().comm_destroy(ctx->comm);
-  if (ctx->slots_dev) (void)hipFree(ctx->slots_dev);
-  if (ctx->slots_red) (void)hipFree(ctx->slots_red);
-  if (ctx->local_result_dev) (void)hipFree(ctx->local_result_dev);
-  for (int i = 0; i < kCloudBufs; ++i) {
-    if (ctx->cloud_dev[i]) (void)hipFree(ctx->cloud_dev[i]);
-    if (ctx->cloud_ready[i]) (void)hipEventDestroy(ctx->cloud_ready[i]);
-  }
-  void* dev[] = {ctx->row_tab, ctx->pt_slot, ctx->sorted, ctx->cell_count, ctx->cell_start, ctx->axes_dev,
-                 ctx->samples_dev, ctx->plan_dev, ctx->plan_pairs_dev, ctx->costs, ctx->partial, ctx->steps, ctx->samples_out,
-                 ctx->best_key, ctx->overflow, ctx->tickets, ctx->poses_dev, ctx->traj_load, ctx->assign, ctx->blocked_plan, ctx->blocked_flags};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
+  dev_free(ctx->mem);
   perception_free(ctx->feed);
   if (ctx->dclear) { dc_free(*ctx->dclear); delete ctx->dclear; }
   for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) release_source(ctx, i);
-  for (int i = 0; i < kCloudBufs; ++i)
-    if (ctx->cloud_stage[i]) (void)hipHostFree(ctx->cloud_stage[i]);
-  if (ctx->small_stage) (void)hipHostFree(ctx->small_stage);
-  if (ctx->result_host) (void)hipHostFree(ctx->result_host);
-  if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-  if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-  if (ctx->evs0) (void)hipEventDestroy(ctx->evs0);
-  if (ctx->evs1) (void)hipEventDestroy(ctx->evs1);
-  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-  if (ctx->traj_info) (void)hipFree(ctx->traj_info);
-  if (ctx->st_sc) (void)hipFree(ctx->st_sc);
-  if (ctx->st_xy) (void)hipFree(ctx->st_xy);
+  for (void* p : {(void*)ctx->cloud_stage[0], (void*)ctx->cloud_stage[1], (void*)ctx->cloud_stage[2], (void*)ctx->small_stage,
+                  (void*)ctx->result_host})
+    if (p) (void)hipHostFree(p);
+  for (hipEvent_t e : {ctx->cloud_ready[0], ctx->cloud_ready[1], ctx->cloud_ready[2], ctx->ev0, ctx->ev1, ctx->evs0, ctx->evs1})
+    if (e) (void)hipEventDestroy(e);
+  for (hipStream_t s : {ctx->stream, ctx->copy_stream})
+    if (s) (void)hipStreamDestroy(s);
   delete ctx;
 }
 
@@ -444,20 +425,7 @@ int dddmr_rollout_create(const dddmr_rollout_config* cfg, dddmr_rollout_ctx** ou
   ctx->theories.assign(cfg->theories, cfg->theories + cfg->n_theories);
   ctx->cfg.theories = ctx->theories.data();
   ctx->device = cfg->device;
-  if (const char* e = std::getenv("DDDMR_CELL")) {
-    const float v = (float)std::atof(e);
-    if (v > 0.01f && v < 10.f) { ctx->knobs.cell_size = v; ctx->knobs.cell_forced = true; }
-  }
-  if (const char* e = std::getenv("DDDMR_TILE")) ctx->knobs.tile_override = std::atoi(e);
-  if (const char* e = std::getenv("DDDMR_RT")) ctx->knobs.rt_override = std::atoi(e);
-  if (const char* e = std::getenv("DDDMR_THREADS")) ctx->knobs.threads_override = std::atoi(e) == 512 ? 512 : 256;
-  if (const char* e = std::getenv("DDDMR_TAIL_ROUND")) ctx->knobs.tail_round = std::atoi(e) != 0;
-  if (const char* e = std::getenv("DDDMR_TIMING")) ctx->timing = std::atoi(e);
-  if (const char* e = std::getenv("DDDMR_TIMING_EVERY")) ctx->timing_every = std::max(1, std::atoi(e));
-  if (const char* e = std::getenv("DDDMR_SPIN")) ctx->spin = std::atoi(e);
-  if (const char* e = std::getenv("DDDMR_HEADING_ROWS")) ctx->heading_rows = std::atoi(e) != 0;
-  if (const char* e = std::getenv("DDDMR_FINAL")) ctx->knobs.final_mode = std::atoi(e) ? 1 : 0;
-  if (const char* e = std::getenv("DDDMR_PROBE")) ctx->knobs.probe_mode = std::atoi(e) ? 1 : 0;
+  read_env(ctx);
 
   auto init = [&]() -> int {
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -468,65 +436,58 @@ int dddmr_rollout_create(const dddmr_rollout_config* cfg, dddmr_rollout_ctx** ou
     }
     HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
     HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    HIPCHK(ctx, hipEventCreate(&ctx->ev0));
-    HIPCHK(ctx, hipEventCreate(&ctx->ev1));
-    HIPCHK(ctx, hipEventCreate(&ctx->evs0));
-    HIPCHK(ctx, hipEventCreate(&ctx->evs1));
+    for (hipEvent_t* e : {&ctx->ev0, &ctx->ev1, &ctx->evs0, &ctx->evs1}) HIPCHK(ctx, hipEventCreate(e));
     const size_t P = cfg->max_points, N = cfg->max_trajectories;
     // the pair records: whole trips of phase P's scalar-load walk plus one chunk of slack for its last request ahead
     const size_t plan_cap = plan_padded_poses(std::max<uint32_t>(cfg->max_plan_poses, 1));
+    DevAllocs& mem = ctx->mem;
     for (int i = 0; i < kCloudBufs; ++i) {
-      HIPCHK(ctx, hipMalloc(&ctx->cloud_dev[i], P * sizeof(float4)));
+      HIPCHK(ctx, dev_alloc(mem, &ctx->cloud_dev[i], P));
       HIPCHK(ctx, hipEventCreateWithFlags(&ctx->cloud_ready[i], hipEventDisableTiming));
     }
-    HIPCHK(ctx, hipMalloc(&ctx->pt_slot, P * sizeof(uint2)));
-    HIPCHK(ctx, hipMalloc(&ctx->sorted, (P + kItem) * sizeof(Pt3)));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->pt_slot, P));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->sorted, P + kItem));
     HIPCHK(ctx, hipMemset(ctx->sorted, 0, (P + kItem) * sizeof(Pt3)));
-    HIPCHK(ctx, hipMalloc(&ctx->cell_count, (kCapCells + 1) * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&ctx->cell_start, (kCapCells + 1) * sizeof(uint32_t)));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->cell_count, (size_t)kCapCells + 1));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->cell_start, (size_t)kCapCells + 1));
     HIPCHK(ctx, hipMemset(ctx->cell_count, 0, (kCapCells + 1) * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&ctx->row_tab, (size_t)kTabCap * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&ctx->axes_dev, 3 * kMaxAxis * sizeof(float)));
-    HIPCHK(ctx, hipMalloc(&ctx->samples_dev, N * sizeof(float4)));
-    HIPCHK(ctx, hipMalloc(&ctx->plan_dev, std::max<size_t>(cfg->max_plan_poses, 1) * sizeof(float4)));
-    HIPCHK(ctx, hipMalloc(&ctx->plan_pairs_dev, plan_cap * kPlanPoseWords * sizeof(float)));
-    HIPCHK(ctx, hipMalloc(&ctx->costs, N * sizeof(double)));
-    HIPCHK(ctx, hipMalloc(&ctx->partial, N * sizeof(TrajPartial)));
-    HIPCHK(ctx, hipMalloc(&ctx->steps, N * sizeof(int32_t)));
-    HIPCHK(ctx, hipMalloc(&ctx->samples_out, N * sizeof(float4)));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->row_tab, (size_t)kTabCap));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->axes_dev, (size_t)3 * kMaxAxis));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->samples_dev, N));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->plan_dev, std::max<size_t>(cfg->max_plan_poses, 1)));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->plan_pairs_dev, plan_cap * kPlanPoseWords));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->costs, N));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->partial, N));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->steps, N));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->samples_out, N));
     // words 0..2: unused (the binning launch still resets them); from kSlotBase on: four words per workgroup of the
     // launch that ends the scoring (k_score on single-round shards, k_finalize on multi-round ones)
-    HIPCHK(ctx, hipMalloc(&ctx->best_key, ((size_t)kSlotBase + (size_t)kSlotWords * ctx->cfg.max_trajectories) * sizeof(int64_t)));
-    HIPCHK(ctx, hipMalloc(&ctx->overflow, sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&ctx->traj_load, N * sizeof(uint32_t)));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->best_key, (size_t)kSlotBase + (size_t)kSlotWords * N));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->overflow, 1));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->traj_load, N));
     HIPCHK(ctx, hipMemset(ctx->traj_load, 0, N * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&ctx->assign, N * sizeof(uint32_t)));
-    ctx->knobs.no_assign = std::getenv("DDDMR_NO_ASSIGN") != nullptr;
-    ctx->knobs.no_boxfast = std::getenv("DDDMR_NO_BOXFAST") != nullptr;
-    ctx->knobs.no_tab = std::getenv("DDDMR_NO_TAB") != nullptr;
-    ctx->poison = std::getenv("DDDMR_POISON") != nullptr;
-    ctx->host_prof = std::getenv("DDDMR_HOST_PROF") != nullptr;
-    ctx->knobs.gnz_one = std::getenv("DDDMR_GNZ_ONE") != nullptr;
-    HIPCHK(ctx, hipMalloc(&ctx->tickets, 2 * sizeof(uint32_t)));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->assign, N));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->tickets, 2));
     HIPCHK(ctx, hipMemset(ctx->tickets, 0, 2 * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMalloc(&ctx->poses_dev, (size_t)cfg->max_steps * 7 * sizeof(double)));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->poses_dev, (size_t)cfg->max_steps * 7));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->blocked_plan, (size_t)kBlockedMaxPlan));
+    HIPCHK(ctx, dev_alloc(mem, &ctx->blocked_flags, (size_t)kBlockedMaxPlan / 32));
     for (int i = 0; i < kCloudBufs; ++i) HIPCHK(ctx, hipHostMalloc(&ctx->cloud_stage[i], P * sizeof(float4), hipHostMallocDefault));
     const size_t small = std::max<size_t>({3 * kMaxAxis * sizeof(float), N * sizeof(float4),
                                            plan_cap * sizeof(float4)});
     HIPCHK(ctx, hipHostMalloc(&ctx->small_stage, small, hipHostMallocDefault));
-    HIPCHK(ctx, hipHostMalloc(&ctx->result_host, sizeof(DevResult), hipHostMallocMapped));
-    HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->result_dev), ctx->result_host, 0));
+    if (host_mapped_alloc(&ctx->result_host, &ctx->result_dev, sizeof(DevResult)) != 0)
+      return fail(ctx, DDDMR_ERR_HIP, "result record allocation failed");
     const int rc = perception_alloc(ctx->feed, P);
     if (rc != 0) return fail(ctx, DDDMR_ERR_HIP, "perception scratch allocation failed");
-    HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_rollout), hipFuncAttributeMaxDynamicSharedMemorySize, kScoreLdsMax));
-    HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_bin_count), hipFuncAttributeMaxDynamicSharedMemorySize, kScoreLdsMax));
     {
-      const void* score_kernels[] = {
+      const void* big_lds_kernels[] = {
+          reinterpret_cast<const void*>(k_rollout), reinterpret_cast<const void*>(k_bin_count),
           reinterpret_cast<const void*>(k_score<256, false, false>), reinterpret_cast<const void*>(k_score<256, false, true>),
           reinterpret_cast<const void*>(k_score<256, true, false>),  reinterpret_cast<const void*>(k_score<256, true, true>),
           reinterpret_cast<const void*>(k_score<512, false, false>), reinterpret_cast<const void*>(k_score<512, false, true>),
           reinterpret_cast<const void*>(k_score<512, true, false>),  reinterpret_cast<const void*>(k_score<512, true, true>)};
-      for (const void* f : score_kernels) HIPCHK(ctx, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kScoreLdsMax));
+      for (const void* f : big_lds_kernels) HIPCHK(ctx, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kScoreLdsMax));
     }
     HIPCHK(ctx, hipDeviceSynchronize());
     return DDDMR_OK;
@@ -602,8 +563,7 @@ int dddmr_rollout_set_cloud(dddmr_rollout_ctx* ctx, const float* xyzi, size_t n_
 int dddmr_rollout_get_cloud(dddmr_rollout_ctx* ctx, float* xyzi_out, size_t capacity, size_t* n_points) {
   if (!ctx || !n_points) return DDDMR_ERR_BAD_ARG;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "get_cloud while a tick_begin is pending");
+  TICK_IDLE(ctx, "get_cloud");
   CloudPin pin(ctx);                            // a producer must not recycle the buffer while it is copied
   const int idx = pin.idx();
   const uint32_t n = pin.n_points();
@@ -621,14 +581,14 @@ int dddmr_rollout_path_blocked(dddmr_rollout_ctx* ctx, const float* plan_xyzi, s
   if (n_plan > 0 && !plan_xyzi) return fail(ctx, DDDMR_ERR_BAD_ARG, "path_blocked: null plan");
   if (n_plan > (size_t)kBlockedMaxPlan)
     return fail(ctx, DDDMR_ERR_CAPACITY, "path_blocked: %zu plan points > %d", n_plan, kBlockedMaxPlan);
-  std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "path_blocked while a tick_begin is pending");
+  TICK_IDLE(ctx, "path_blocked");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   *ratio = 0.0;
   *opinion = DDDMR_OPINION_PASS;
   if (blocked_flags) std::memset(blocked_flags, 0, n_plan);
-  // pin the front cloud like a tick does
+  // pin the front cloud like a tick does; an error return past the launch waits for the stream before the pin lets go
   CloudPin pin(ctx);
+  Drain drain{ctx->stream, false};
   const uint32_t n_points = pin.n_points();
   if (n_points <= 5 || n_plan == 0) return DDDMR_OK;                  // path_blocked_strategy.cpp:62-64
   BlockedParams b;
@@ -652,19 +612,17 @@ int dddmr_rollout_path_blocked(dddmr_rollout_ctx* ctx, const float* plan_xyzi, s
       b.lo[a] = std::nextafter(b.lo[a] - grow, -3.402823466e+38f);
       b.hi[a] = std::nextafter(b.hi[a] + grow, 3.402823466e+38f);
     }
-    if (!ctx->blocked_plan) {
-      HIPCHK(ctx, hipMalloc(&ctx->blocked_plan, kBlockedMaxPlan * sizeof(float4)));
-      HIPCHK(ctx, hipMalloc(&ctx->blocked_flags, (kBlockedMaxPlan / 32) * sizeof(uint32_t)));
-    }
     HIPCHK(ctx, pin.wait_on(ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(ctx->blocked_plan, plan_xyzi, n_plan * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->blocked_flags, 0, (kBlockedMaxPlan / 32) * sizeof(uint32_t), ctx->stream));
     const int blocks = (int)std::min<uint32_t>(1024, (n_points + 255) / 256);
+    uint32_t words[kBlockedMaxPlan / 32];
+    drain.armed = true;                        // from here on the stream reads the pinned cloud (and writes `words`)
     hipLaunchKernelGGL(k_path_blocked, dim3(blocks), dim3(256), 0, ctx->stream, b, pin.dev(),
                        ctx->blocked_plan, ctx->blocked_flags);
-    uint32_t words[kBlockedMaxPlan / 32];
     HIPCHK(ctx, hipMemcpyAsync(words, ctx->blocked_flags, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    drain.armed = false;
     size_t blocked = 0;
     for (size_t i = 0; i < n_plan; ++i) {
       const bool hit = (words[i >> 5] >> (i & 31)) & 1u;
@@ -684,8 +642,7 @@ int dddmr_rollout_set_prune_plan(dddmr_rollout_ctx* ctx, const double* poses, si
   if (n_poses > ctx->cfg.max_plan_poses)
     return fail(ctx, DDDMR_ERR_CAPACITY, "set_prune_plan: %zu poses > max_plan_poses %u", n_poses,
                 ctx->cfg.max_plan_poses);
-  std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "set_prune_plan while a tick_begin is pending");
+  TICK_IDLE(ctx, "set_prune_plan");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   // ModelSharedData::updateData: positions as float PointXYZI (model_shared_data.h:83-91)
   // For phase P's scalar walk the same positions go up a second time as pair records, padded with copies of the last
@@ -709,11 +666,17 @@ int dddmr_rollout_set_prune_plan(dddmr_rollout_ctx* ctx, const double* poses, si
 
 namespace {
 
-void no_winner(dddmr_rollout_result* out) {
-  std::memset(out, 0, sizeof(*out));
+// "no trajectory": what every such result shares; the key is the caller's (resolve keeps the one it was given)
+void set_no_winner(dddmr_rollout_result* out) {
   out->planner_state = DDDMR_ALL_TRAJECTORIES_FAIL;
   out->best_index = -1;
   out->best_cost = -1.0;
+  out->vx = out->vy = out->wz = 0.0;
+}
+
+void no_winner(dddmr_rollout_result* out) {
+  std::memset(out, 0, sizeof(*out));
+  set_no_winner(out);
   out->key = kKeyNone;
 }
 
@@ -728,8 +691,9 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
   make_window(*th, *in, w);   // initialise(): velocity samples of this tick
 
   // The cloud's front buffer is pinned before the plan's capacity checks, because the plan needs its size.  No caller
-  // can tell: the pin releases the buffer again on any error return (CloudPin).
+  // can tell: the pin releases the buffer again on any error return (CloudPin), once nothing reads it any more (Drain).
   CloudPin pin(ctx);
+  Drain drain{ctx->stream, false};
 
   TickPlan& p = ctx->pend.plan;
   DevTick& k = p.k;
@@ -739,7 +703,7 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
   const int rc = plan_tick(ctx->knobs, ctx->feedback, ctx->cfg, *th, theory_id, *in, w, pin.n_points(), ctx->plan_m,
                            ctx->plan_last, exchange, &p, &err);
   if (rc != DDDMR_OK) return fail(ctx, rc, "%s", err.c_str());
-  if (ctx->seq == 3 && std::getenv("DDDMR_DEBUG_GRID"))
+  if (ctx->seq == 3 && ctx->debug_grid)
     std::fprintf(stderr, "[dddmr] k_score shape: %d lanes, tile %d, %d-step rows, %zu bytes of dynamic LDS (tile+1 would need %zu)\n", p.thr, k.tile,
                  p.s_tick, p.score_lds, plan_score_lds(k, k.tile + 1));
 
@@ -759,14 +723,12 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
     const size_t need = (size_t)k.n_local * (size_t)p.s_tick;
     if (need > ctx->st_cap || !ctx->traj_info) {
       HIPCHK(ctx, hipDeviceSynchronize());
-      if (ctx->st_sc) (void)hipFree(ctx->st_sc);
-      if (ctx->st_xy) (void)hipFree(ctx->st_xy);
-      ctx->st_sc = nullptr; ctx->st_xy = nullptr; ctx->st_cap = 0;
+      ctx->st_cap = 0;
       const size_t cap = need + need / 4 + 1024;
-      HIPCHK(ctx, hipMalloc(&ctx->st_sc, cap * sizeof(double2)));
-      HIPCHK(ctx, hipMalloc(&ctx->st_xy, cap * sizeof(float2)));
+      HIPCHK(ctx, dev_realloc(ctx->mem, &ctx->st_sc, cap));
+      HIPCHK(ctx, dev_realloc(ctx->mem, &ctx->st_xy, cap));
       ctx->st_cap = cap;
-      if (!ctx->traj_info) HIPCHK(ctx, hipMalloc(&ctx->traj_info, (size_t)ctx->cfg.max_trajectories * sizeof(TrajInfo)));
+      if (!ctx->traj_info) HIPCHK(ctx, dev_alloc(ctx->mem, &ctx->traj_info, (size_t)ctx->cfg.max_trajectories));
     }
   }
   HIPCHK(ctx, pin.wait_on(ctx->stream));
@@ -787,34 +749,21 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
   // traj_load will describe this tick's shard of this theory
   ctx->feedback.load_theory = theory_id;
   ctx->feedback.load_nlocal = k.n_local;
-  // Heading rows per angular sample (rollout_kernels.hip.h, heading_rows_shared()): decided here, outside the plan, and
-  // handed to the rollout as an argument of its own.  The rows' LDS comes on top of the plan's; a tick whose rollout
-  // workgroups would no longer sit two to a CU with it (72 KB of dynamic LDS beside k_bin_count's 8 KB of static) keeps
-  // a chain per trajectory.
-  size_t roll_lds = p.roll_lds;
-  int heading_rows = 0;
-  if (ctx->heading_rows && heading_rows_shared(k)) {
-    const size_t with_rows = p.roll_lds + heading_rows_lds_bytes(k.max_steps, k.kind == DDDMR_THEORY_OMNI_SIMPLE);
-    const size_t two_per_cu = (size_t)72 * 1024;
-    if (with_rows <= (size_t)kScoreLdsMax && (with_rows <= two_per_cu || p.roll_lds > two_per_cu)) {
-      roll_lds = with_rows;
-      heading_rows = 1;
-    }
-  }
-  ctx->last_heading_rows = heading_rows;
+  ctx->last_heading_rows = p.heading_rows;
+  drain.armed = true;       // from here on the stream reads the pinned cloud
   if (k.n_points > 0) {
-    hipLaunchKernelGGL(k_bin_count, dim3(p.cnt_blocks + p.roll_blocks + (k.use_assign ? k.assign_groups : 0)), dim3(kBinThreads), roll_lds,
-                       ctx->stream, k, pin.dev(), ctx->cell_count, ctx->cell_start, ctx->pt_slot, ctx->tickets,
+    hipLaunchKernelGGL(k_bin_count, dim3(p.cnt_blocks + p.roll_blocks + (k.use_assign ? k.assign_groups : 0)), dim3(kBinThreads),
+                       p.roll_launch_lds, ctx->stream, k, pin.dev(), ctx->cell_count, ctx->cell_start, ctx->pt_slot, ctx->tickets,
                        ctx->best_key, ctx->overflow, ctx->axes_dev, ctx->samples_dev, ctx->traj_info, ctx->st_sc,
-                       ctx->st_xy, ctx->traj_load, ctx->assign, heading_rows);
+                       ctx->st_xy, ctx->traj_load, ctx->assign, p.heading_rows);
     hipLaunchKernelGGL(k_bin_scatter, dim3(p.bin_blocks), dim3(256), 0, ctx->stream, k, pin.dev(),
                        ctx->pt_slot, ctx->cell_start, ctx->sorted, ctx->row_tab);
   } else {
     hipLaunchKernelGGL(k_bin_reset, dim3(1), dim3(256), 0, ctx->stream, k, ctx->cell_count, ctx->cell_start,
                        ctx->best_key, ctx->overflow);
     if (p.roll_blocks > 0)
-      hipLaunchKernelGGL(k_rollout, dim3(p.roll_blocks), dim3(256), roll_lds, ctx->stream, k, ctx->axes_dev,
-                         ctx->samples_dev, ctx->traj_info, ctx->st_sc, ctx->st_xy, heading_rows);
+      hipLaunchKernelGGL(k_rollout, dim3(p.roll_blocks), dim3(256), p.roll_launch_lds, ctx->stream, k, ctx->axes_dev,
+                         ctx->samples_dev, ctx->traj_info, ctx->st_sc, ctx->st_xy, p.heading_rows);
     if (k.use_assign)
       hipLaunchKernelGGL(k_assign, dim3(k.assign_groups), dim3(kBinThreads), 0, ctx->stream, k, ctx->traj_load, ctx->assign);
   }
@@ -870,6 +819,7 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
     ++ctx->prof_n;
   }
   pin.keep();             // the cloud buffer stays pinned until tick_collect
+  drain.armed = false;    // ... which waits for the tick
   ctx->pend.active = true;
   ctx->pend.timed = timed;
   ctx->pend.timed_all = timed_all;
@@ -930,8 +880,7 @@ extern "C" {
 int dddmr_rollout_tick(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_tick_input* in,
                        dddmr_rollout_result* out) {
   if (!ctx || !theory_name || !in || !out) return DDDMR_ERR_BAD_ARG;
-  std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "tick while a tick_begin is pending");
+  TICK_IDLE(ctx, "tick");
   no_winner(out);
   const int rc = tick_enqueue(ctx, theory_name, in);
   if (rc != DDDMR_OK) return rc;
@@ -958,10 +907,7 @@ int dddmr_rollout_resolve(dddmr_rollout_ctx* ctx, int64_t reduced_key, dddmr_rol
   inout->key = reduced_key;
   const int32_t idx = key_index(reduced_key);
   if (idx < 0) {
-    inout->planner_state = DDDMR_ALL_TRAJECTORIES_FAIL;
-    inout->best_index = -1;
-    inout->best_cost = -1.0;
-    inout->vx = inout->vy = inout->wz = 0.0;
+    set_no_winner(inout);
     return DDDMR_OK;
   }
   if (idx >= ctx->last.n_global) return fail(ctx, DDDMR_ERR_BAD_ARG, "resolve: index %d out of range", idx);
@@ -1001,10 +947,7 @@ int dddmr_rollout_resolve_words(dddmr_rollout_ctx* ctx, const int64_t* words, in
     if (cr < c || (cr == c && ir < ni)) { c = cr; ni = ir; }
   }
   if (c == INT64_MAX) {
-    inout->planner_state = DDDMR_ALL_TRAJECTORIES_FAIL;
-    inout->best_index = -1;
-    inout->best_cost = -1.0;
-    inout->vx = inout->vy = inout->wz = 0.0;
+    set_no_winner(inout);
     inout->key = kKeyNone;
     return DDDMR_OK;
   }
@@ -1022,69 +965,6 @@ int dddmr_rollout_resolve_words(dddmr_rollout_ctx* ctx, const int64_t* words, in
   return DDDMR_OK;
 }
 
-int dddmr_rollout_comm_unique_id(uint8_t id_out[DDDMR_COMM_ID_BYTES]) {
-  static_assert(DDDMR_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "unique id size");
-  if (!id_out) return DDDMR_ERR_BAD_ARG;
-  if (!rccl().ok()) return DDDMR_ERR_NO_DEVICE;
-  ncclUniqueId id;
-  if (rccl().get_unique_id(&id) != ncclSuccess) return DDDMR_ERR_HIP;
-  std::memcpy(id_out, id.internal, DDDMR_COMM_ID_BYTES);
-  return DDDMR_OK;
-}
-
-// slot vectors of the per-tick exchange: [2 * n_ranks] words to send (own pair written by k_score / k_finalize,
-// INT64_MAX elsewhere: the other ranks' slots never change) and to receive
-static int alloc_exchange_buffers(dddmr_rollout_ctx* ctx, int n_ranks) {
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (ctx->slots_dev) { (void)hipFree(ctx->slots_dev); ctx->slots_dev = nullptr; }      // (re-initialisation after comm_destroy)
-  if (ctx->slots_red) { (void)hipFree(ctx->slots_red); ctx->slots_red = nullptr; }
-  if (ctx->local_result_dev) { (void)hipFree(ctx->local_result_dev); ctx->local_result_dev = nullptr; }
-  HIPCHK(ctx, hipMalloc(&ctx->slots_dev, (size_t)2 * n_ranks * sizeof(int64_t)));
-  HIPCHK(ctx, hipMalloc(&ctx->slots_red, (size_t)2 * n_ranks * sizeof(int64_t)));
-  HIPCHK(ctx, hipMalloc(&ctx->local_result_dev, sizeof(DevResult)));
-  std::vector<int64_t> none((size_t)2 * n_ranks, INT64_MAX);
-  HIPCHK(ctx, hipMemcpy(ctx->slots_dev, none.data(), none.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-  HIPCHK(ctx, hipMemcpy(ctx->slots_red, none.data(), none.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-  return DDDMR_OK;
-}
-
-int dddmr_rollout_comm_init(dddmr_rollout_ctx* ctx, const uint8_t id[DDDMR_COMM_ID_BYTES], int32_t rank, int32_t n_ranks) {
-  if (!ctx || !id) return DDDMR_ERR_BAD_ARG;
-  std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "comm_init while a tick_begin is pending");
-  if (ctx->comm) return fail(ctx, DDDMR_ERR_STATE, "comm_init: the context already has a communicator");
-  const int world = std::max(1, ctx->cfg.world_size);
-  if (n_ranks != world || rank != std::min(std::max(0, ctx->cfg.rank), world - 1))
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "comm_init: rank %d of %d does not match the context's shard (rank %d of %d)", rank,
-                n_ranks, ctx->cfg.rank, world);
-  if (ctx->comm_loopback) return fail(ctx, DDDMR_ERR_STATE, "comm_init: the context is in loopback mode");
-  if (!rccl().ok()) return fail(ctx, DDDMR_ERR_NO_DEVICE, "comm_init: %s", rccl().why.c_str());
-  const int ab = alloc_exchange_buffers(ctx, n_ranks);
-  if (ab != DDDMR_OK) return ab;
-  ncclUniqueId uid;
-  std::memcpy(uid.internal, id, DDDMR_COMM_ID_BYTES);
-  ncclComm_t comm = nullptr;
-  const ncclResult_t rc = rccl().comm_init_rank(&comm, n_ranks, uid, rank);     // collective: every rank calls it
-  if (rc != ncclSuccess) return fail(ctx, DDDMR_ERR_HIP, "ncclCommInitRank failed: %s", rccl().error_string(rc));
-  ctx->comm = comm;
-  ctx->comm_ranks = n_ranks;
-  return DDDMR_OK;
-}
-
-int dddmr_rollout_comm_destroy(dddmr_rollout_ctx* ctx) {
-  if (!ctx) return DDDMR_ERR_BAD_ARG;
-  std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "comm_destroy while a tick_begin is pending");
-  if (!ctx->comm && !ctx->comm_loopback) return DDDMR_OK;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->comm) (void)rccl().comm_destroy(ctx->comm);
-  ctx->comm = nullptr;
-  ctx->comm_loopback = false;
-  ctx->comm_ranks = 0;
-  return DDDMR_OK;
-}
-
 int dddmr_rollout_device_count(int32_t* n_out) {
   if (!n_out) return DDDMR_ERR_BAD_ARG;
   int n = 0;
@@ -1092,123 +972,6 @@ int dddmr_rollout_device_count(int32_t* n_out) {
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return DDDMR_ERR_NO_DEVICE; }
   *n_out = n;
   return DDDMR_OK;
-}
-
-int dddmr_rollout_comm_ranks(dddmr_rollout_ctx* ctx, int32_t* n_ranks_out) {
-  if (!ctx || !n_ranks_out) return DDDMR_ERR_BAD_ARG;
-  std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  *n_ranks_out = 0;
-  if (ctx->comm_loopback) { *n_ranks_out = ctx->comm_ranks; return DDDMR_OK; }
-  if (!ctx->comm) return DDDMR_OK;
-  int n = 0;
-  const ncclResult_t rc = rccl().comm_count(ctx->comm, &n);      // what RCCL itself says, not what we asked for
-  if (rc != ncclSuccess) return fail(ctx, DDDMR_ERR_HIP, "ncclCommCount failed: %s", rccl().error_string(rc));
-  *n_ranks_out = n;
-  return DDDMR_OK;
-}
-
-int dddmr_rollout_comm_loopback(dddmr_rollout_ctx* ctx) {
-  if (!ctx) return DDDMR_ERR_BAD_ARG;
-  std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "comm_loopback while a tick_begin is pending");
-  if (ctx->comm || ctx->comm_loopback) return fail(ctx, DDDMR_ERR_STATE, "comm_loopback: the context already has an exchange");
-  const int world = std::max(1, ctx->cfg.world_size);
-  const int ab = alloc_exchange_buffers(ctx, world);
-  if (ab != DDDMR_OK) return ab;
-  ctx->comm_loopback = true;
-  ctx->comm_ranks = world;
-  return DDDMR_OK;
-}
-
-int dddmr_rollout_comm_loopback_set_peer(dddmr_rollout_ctx* ctx, int32_t peer_rank, const int64_t words[2]) {
-  if (!ctx || !words) return DDDMR_ERR_BAD_ARG;
-  std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  if (!ctx->comm_loopback) return fail(ctx, DDDMR_ERR_STATE, "comm_loopback_set_peer: the context is not in loopback mode");
-  if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "comm_loopback_set_peer while a tick_begin is pending");
-  const int world = ctx->comm_ranks, rank = std::min(std::max(0, ctx->cfg.rank), world - 1);
-  if (peer_rank < 0 || peer_rank >= world || peer_rank == rank)
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "comm_loopback_set_peer: peer %d of %d (own rank %d)", peer_rank, world, rank);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  HIPCHK(ctx, hipMemcpy(ctx->slots_dev + 2 * peer_rank, words, 2 * sizeof(int64_t), hipMemcpyHostToDevice));
-  return DDDMR_OK;
-}
-
-// Stream ceiling of this GPU ("a measured stream-copy ceiling on the same GPU ... both
-// denominators"): `bytes` per buffer (>= 1 GiB defeats the 256 MB of MALL), `reps` launches each.
-int dddmr_rollout_selftest_sincos(dddmr_rollout_ctx* ctx, const double* angles, size_t n, double* sin_out,
-                                  double* cos_out) {
-  if (!ctx || !angles || !sin_out || !cos_out || n == 0 || n > ((size_t)1 << 24)) return DDDMR_ERR_BAD_ARG;
-  std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "selftest_sincos while a tick_begin is pending");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  double* buf = nullptr;
-  HIPCHK(ctx, hipMalloc(&buf, 3 * n * sizeof(double)));
-  int rc = DDDMR_OK;
-  auto run = [&]() -> int {
-    HIPCHK(ctx, hipMemcpyAsync(buf, angles, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_selftest_sincos, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, buf, (int)n,
-                       buf + n, buf + 2 * n);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(sin_out, buf + n, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(cos_out, buf + 2 * n, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return DDDMR_OK;
-  };
-  rc = run();
-  (void)hipFree(buf);
-  return rc;
-}
-
-int dddmr_rollout_stream_ceiling(dddmr_rollout_ctx* ctx, size_t bytes, int32_t reps, double* copy_gbps,
-                                 double* read_gbps) {
-  if (!ctx || !copy_gbps || !read_gbps || reps <= 0 || bytes < (1u << 20)) return DDDMR_ERR_BAD_ARG;
-  std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "stream_ceiling while a tick_begin is pending");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  const size_t n = bytes / sizeof(float4);
-  // one pass of the four-loads-in-flight loop per lane measured best (grid sweep 1k ... 64k workgroups:
-  // copy 4.5 -> 5.2 TB/s, read 5.7 -> 6.0 TB/s; tools/exp_ceiling.py)
-  int blocks = (int)std::min<size_t>(65536, std::max<size_t>(1, n / (256 * 4)));
-  if (const char* e = std::getenv("DDDMR_CEIL_BLOCKS")) blocks = std::max(1, std::atoi(e));
-  float4 *src = nullptr, *dst = nullptr;
-  float* sink = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = DDDMR_OK;
-  auto run = [&]() -> int {
-    HIPCHK(ctx, hipMalloc(&src, n * sizeof(float4)));
-    HIPCHK(ctx, hipMalloc(&dst, n * sizeof(float4)));
-    HIPCHK(ctx, hipMalloc(&sink, (size_t)blocks * 256 * sizeof(float)));
-    HIPCHK(ctx, hipMemsetAsync(src, 0x11, n * sizeof(float4), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(dst, 0, n * sizeof(float4), ctx->stream));
-    HIPCHK(ctx, hipEventCreate(&e0));
-    HIPCHK(ctx, hipEventCreate(&e1));
-    float ms = 0.f;
-    hipLaunchKernelGGL(k_stream_copy, dim3(blocks), dim3(256), 0, ctx->stream, src, dst, n);   // warm-up
-    HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
-    for (int r = 0; r < reps; ++r) hipLaunchKernelGGL(k_stream_copy, dim3(blocks), dim3(256), 0, ctx->stream, src, dst, n);
-    HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
-    HIPCHK(ctx, hipEventSynchronize(e1));
-    HIPCHK(ctx, hipEventElapsedTime(&ms, e0, e1));
-    *copy_gbps = 2.0 * (double)(n * sizeof(float4)) * reps / ((double)ms * 1e-3) / 1e9;
-    hipLaunchKernelGGL(k_stream_read, dim3(blocks), dim3(256), 0, ctx->stream, src, sink, n);
-    HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
-    for (int r = 0; r < reps; ++r) hipLaunchKernelGGL(k_stream_read, dim3(blocks), dim3(256), 0, ctx->stream, src, sink, n);
-    HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
-    HIPCHK(ctx, hipEventSynchronize(e1));
-    HIPCHK(ctx, hipEventElapsedTime(&ms, e0, e1));
-    *read_gbps = (double)(n * sizeof(float4)) * reps / ((double)ms * 1e-3) / 1e9;
-    HIPCHK(ctx, hipGetLastError());
-    return DDDMR_OK;
-  };
-  rc = run();
-  (void)hipStreamSynchronize(ctx->stream);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (src) (void)hipFree(src);
-  if (dst) (void)hipFree(dst);
-  if (sink) (void)hipFree(sink);
-  return rc;
 }
 
 // The theory's initialise() alone: the velocity samples a tick with these inputs would roll out, in the
@@ -1238,7 +1001,7 @@ int dddmr_rollout_get_debug(dddmr_rollout_ctx* ctx, dddmr_rollout_debug* dbg) {
   if (!ctx || !dbg) return DDDMR_ERR_BAD_ARG;
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   if (!ctx->have_last) return fail(ctx, DDDMR_ERR_STATE, "get_debug before any tick");
-  if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "get_debug while a tick_begin is pending");
+  if (ctx->pend.active) return refuse_pending(ctx, "get_debug");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the tick may have returned on the polled sequence number
   const size_t n = (size_t)ctx->last.n_local;
@@ -1262,7 +1025,7 @@ int dddmr_rollout_get_pose_arrays(dddmr_rollout_ctx* ctx, int32_t which, double*
   if (!ctx || !n_poses || (which != 0 && which != 1)) return DDDMR_ERR_BAD_ARG;
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   if (!ctx->have_last) return fail(ctx, DDDMR_ERR_STATE, "get_pose_arrays before any tick");
-  if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "get_pose_arrays while a tick_begin is pending");
+  if (ctx->pend.active) return refuse_pending(ctx, "get_pose_arrays");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   const int n = ctx->last.n_local;
@@ -1283,46 +1046,48 @@ int dddmr_rollout_get_pose_arrays(dddmr_rollout_ctx* ctx, int32_t which, double*
   if (!poses_out || total == 0) return DDDMR_OK;
   if (capacity < total) return fail(ctx, DDDMR_ERR_CAPACITY, "get_pose_arrays: capacity %zu < %zu", capacity, total);
   if (total > (size_t)INT32_MAX) return fail(ctx, DDDMR_ERR_CAPACITY, "get_pose_arrays: %zu poses", total);
+  DevScope tmp;
   int32_t* off_dev = nullptr;
   double* out_dev = nullptr;
-  HIPCHK(ctx, hipMalloc(&off_dev, (size_t)n * sizeof(int32_t)));
-  if (hipMalloc(&out_dev, total * 7 * sizeof(double)) != hipSuccess) {
-    (void)hipFree(off_dev);
+  HIPCHK(ctx, dev_alloc(tmp.mem, &off_dev, (size_t)n));
+  if (dev_alloc(tmp.mem, &out_dev, total * 7) != hipSuccess)
     return fail(ctx, DDDMR_ERR_HIP, "get_pose_arrays: out of device memory for %zu poses", total);
-  }
-  int rc = DDDMR_OK;
   const size_t pairs = (size_t)n * (size_t)ctx->last.max_steps;
-  if (hipMemcpyAsync(off_dev, off.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-    rc = DDDMR_ERR_HIP;
-  if (rc == DDDMR_OK) {
-    hipLaunchKernelGGL(k_pose_arrays, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, ctx->stream, ctx->last, off_dev,
-                       ctx->steps, ctx->traj_info, ctx->st_sc, ctx->st_xy, out_dev);
-    if (hipMemcpyAsync(poses_out, out_dev, total * 7 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess)
-      rc = DDDMR_ERR_HIP;
-  }
-  (void)hipFree(off_dev);
-  (void)hipFree(out_dev);
-  if (rc != DDDMR_OK) return fail(ctx, rc, "get_pose_arrays: %s", hipGetErrorString(hipGetLastError()));
+  HIPCHK(ctx, hipMemcpyAsync(off_dev, off.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_pose_arrays, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, ctx->stream, ctx->last, off_dev,
+                     ctx->steps, ctx->traj_info, ctx->st_sc, ctx->st_xy, out_dev);
+  HIPCHK(ctx, hipMemcpyAsync(poses_out, out_dev, total * 7 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return DDDMR_OK;
+}
+
+// The last collected tick's winner on this rank, for get_best_poses / get_best_cuboids (tick_mu held): its local index
+// and step count, with the stream idle.  *li < 0, *ns == 0: no winner, or it lives on another rank.
+static int best_local(dddmr_rollout_ctx* ctx, const char* what, int* li, int32_t* ns) {
+  *li = -1;
+  *ns = 0;
+  if (!ctx->have_last) return fail(ctx, DDDMR_ERR_STATE, "%s before any tick", what);
+  if (ctx->pend.active) return refuse_pending(ctx, what);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  const int32_t idx = ctx->last_result.index;
+  if (idx < 0) return DDDMR_OK;
+  const int l = idx - ctx->last.begin;
+  if (l < 0 || l >= ctx->last.n_local) return DDDMR_OK;  // winner is on another rank
+  HIPCHK(ctx, hipMemcpy(ns, ctx->steps + l, sizeof(int32_t), hipMemcpyDeviceToHost));
+  *li = l;
   return DDDMR_OK;
 }
 
 int dddmr_rollout_get_best_poses(dddmr_rollout_ctx* ctx, double* poses_out, size_t capacity, size_t* n_poses) {
   if (!ctx || !n_poses) return DDDMR_ERR_BAD_ARG;
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  if (!ctx->have_last) return fail(ctx, DDDMR_ERR_STATE, "get_best_poses before any tick");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "get_best_poses while a tick_begin is pending");
-  const int32_t idx = ctx->last_result.index;
-  *n_poses = 0;
-  if (idx < 0) return DDDMR_OK;
-  const int li = idx - ctx->last.begin;
-  if (li < 0 || li >= ctx->last.n_local) return DDDMR_OK;  // winner is on another rank
-  int32_t ns = 0;
-  HIPCHK(ctx, hipMemcpy(&ns, ctx->steps + li, sizeof(int32_t), hipMemcpyDeviceToHost));
+  int li;
+  int32_t ns;
+  const int rc = best_local(ctx, "get_best_poses", &li, &ns);
+  if (rc != DDDMR_OK) return rc;
   *n_poses = (size_t)ns;
-  if (!poses_out) return DDDMR_OK;
+  if (li < 0 || !poses_out) return DDDMR_OK;
   if (capacity < (size_t)ns) return fail(ctx, DDDMR_ERR_CAPACITY, "get_best_poses: capacity %zu < %d", capacity, ns);
   hipLaunchKernelGGL(k_trajectory_poses, dim3(1), dim3(64), 0, ctx->stream, ctx->last, li, ctx->samples_out,
                      ctx->steps, ctx->poses_dev, (float*)nullptr);
@@ -1334,33 +1099,26 @@ int dddmr_rollout_get_best_poses(dddmr_rollout_ctx* ctx, double* poses_out, size
 int dddmr_rollout_get_best_cuboids(dddmr_rollout_ctx* ctx, float* vertices_out, size_t capacity_poses, size_t* n_poses) {
   if (!ctx || !n_poses) return DDDMR_ERR_BAD_ARG;
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  if (!ctx->have_last) return fail(ctx, DDDMR_ERR_STATE, "get_best_cuboids before any tick");
-  if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "get_best_cuboids while a tick_begin is pending");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  const int32_t idx = ctx->last_result.index;
-  *n_poses = 0;
-  if (idx < 0) return DDDMR_OK;
-  const int li = idx - ctx->last.begin;
-  if (li < 0 || li >= ctx->last.n_local) return DDDMR_OK;  // winner is on another rank
-  int32_t ns = 0;
-  HIPCHK(ctx, hipMemcpy(&ns, ctx->steps + li, sizeof(int32_t), hipMemcpyDeviceToHost));
+  int li;
+  int32_t ns;
+  const int rc = best_local(ctx, "get_best_cuboids", &li, &ns);
+  if (rc != DDDMR_OK) return rc;
   *n_poses = (size_t)ns;
-  if (!vertices_out || ns == 0) return DDDMR_OK;
+  if (li < 0 || !vertices_out || ns == 0) return DDDMR_OK;
   if (capacity_poses < (size_t)ns) return fail(ctx, DDDMR_ERR_CAPACITY, "get_best_cuboids: capacity %zu < %d", capacity_poses, ns);
+  DevScope tmp;
   float* cub_dev = nullptr;
-  HIPCHK(ctx, hipMalloc(&cub_dev, (size_t)ns * 24 * sizeof(float)));
+  HIPCHK(ctx, dev_alloc(tmp.mem, &cub_dev, (size_t)ns * 24));
   hipLaunchKernelGGL(k_trajectory_poses, dim3(1), dim3(64), 0, ctx->stream, ctx->last, li, ctx->samples_out,
                      ctx->steps, ctx->poses_dev, cub_dev);
-  const hipError_t e = hipMemcpyAsync(vertices_out, cub_dev, (size_t)ns * 24 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(cub_dev);
-  if (e != hipSuccess || e2 != hipSuccess) return fail(ctx, DDDMR_ERR_HIP, "get_best_cuboids: copy failed");
+  HIPCHK(ctx, hipMemcpyAsync(vertices_out, cub_dev, (size_t)ns * 24 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return DDDMR_OK;
 }
 
 }  // extern "C"
 
+#include "rollout_diag.hip.h"
 #include "sensor_sources.hip.h"
 #include "marking_host.hip.h"
 #include "depth_mark.hip.h"

@@ -242,6 +242,7 @@ struct TickKnobs {
   bool no_assign = false;     // DDDMR_NO_ASSIGN: always deal the trajectories strided
   bool no_boxfast = false;    // DDDMR_NO_BOXFAST: always take the general vertex transform
   bool no_tab = false;        // DDDMR_NO_TAB: k_score reads the row-run index from L2 instead of staging it in LDS
+  bool heading_rows = true;   // DDDMR_HEADING_ROWS=0: a heading chain per trajectory on every tick (rollout_kernels.hip.h)
   int n_cu = 256;             // compute units of the device
 };
 
@@ -269,7 +270,9 @@ struct TickPlan {
   int cnt_blocks = 0;       // binning workgroups of the k_bin_count launch
   int bin_blocks = 0;       // k_bin_scatter workgroups
   int roll_blocks = 0;      // rollout workgroups, riding along with k_bin_count
-  size_t roll_lds = 0;
+  size_t roll_lds = 0;      // the rollout's own dynamic LDS: its [rt][steps + 1] slots
+  int heading_rows = 0;     // 1: the rollout shares heading rows per angular sample (heading_rows_shared())
+  size_t roll_launch_lds = 0;   // dynamic LDS of the launch that rolls out: roll_lds, plus the rows when they are shared
   SampleUpload upload = kUploadNone;
   uint32_t n_samples = 0, local_begin = 0, n_local = 0;   // the result's head
 };
@@ -566,6 +569,19 @@ int plan_tick(const TickKnobs& kn, const TickFeedback& fb, const dddmr_rollout_c
   p->cnt_blocks = std::max(1, std::min(512, (k.n_points + per_wg - 1) / per_wg));
   p->roll_blocks = k.n_local > 0 ? (k.n_local + k.rt - 1) / k.rt : 0;
   p->roll_lds = k.n_local > 0 ? rollout_lds_bytes(k.rt, s_tick) : 0;
+  // Heading rows per angular sample (rollout_kernels.hip.h, heading_rows_shared()): handed to the rollout as an argument
+  // of its own.  The rows' LDS comes on top of the rollout's; a tick whose rollout workgroups would no longer sit two to
+  // a CU with it (72 KB of dynamic LDS beside k_bin_count's 8 KB of static) keeps a chain per trajectory.
+  p->heading_rows = 0;
+  p->roll_launch_lds = p->roll_lds;
+  if (kn.heading_rows && heading_rows_shared(k)) {
+    const size_t with_rows = p->roll_lds + heading_rows_lds_bytes(k.max_steps, k.kind == DDDMR_THEORY_OMNI_SIMPLE);
+    const size_t two_per_cu = (size_t)72 * 1024;
+    if (with_rows <= (size_t)kScoreLdsMax && (with_rows <= two_per_cu || p->roll_lds > two_per_cu)) {
+      p->roll_launch_lds = with_rows;
+      p->heading_rows = 1;
+    }
+  }
   k.bin_blocks = p->cnt_blocks;
   k.roll_blocks = p->roll_blocks;
   // Load feedback: valid when the previous tick scored the same shard of the same theory

@@ -14,8 +14,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <vector>
 
 // The reference is an x86-64 build without FMA contraction: every multiply and add below
 // rounds separately, in float and in double (hipcc's default would fuse them).
@@ -191,6 +193,35 @@ inline int host_mapped_alloc(T** host, T** dev, size_t bytes) {
   if (hipHostMalloc(reinterpret_cast<void**>(host), bytes, hipHostMallocMapped) != hipSuccess) return -1;
   return hipHostGetDevicePointer(reinterpret_cast<void**>(dev), *host, 0) == hipSuccess ? 0 : -1;
 }
+
+// Who owns device memory: the context (rollout_engine.hip), the marking store and every module state record what they
+// allocate in a DevAllocs of their own, where it is made; the owner's *_free walks the vector.  (Swapping a main array
+// with its _alt array leaves the set of pointers as it is.)
+using DevAllocs = std::vector<void*>;
+template <class T>
+inline hipError_t dev_alloc(DevAllocs& owner, T** p, size_t count) {
+  const hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
+  if (e == hipSuccess) owner.push_back(*p);
+  return e;
+}
+inline void dev_free(DevAllocs& owner) {
+  for (void* q : owner) (void)hipFree(q);
+  owner.clear();
+}
+// A buffer that grows, or comes back after its user was torn down: the owner drops and frees what *p names (nothing when
+// it is null), then allocates `count` elements afresh.  On failure *p is null.
+template <class T>
+inline hipError_t dev_realloc(DevAllocs& owner, T** p, size_t count) {
+  owner.erase(std::remove(owner.begin(), owner.end(), static_cast<void*>(*p)), owner.end());
+  (void)hipFree(*p);
+  *p = nullptr;
+  return dev_alloc(owner, p, count);
+}
+// The temporaries of one call: freed on any return.  (Lives on the stack, never copied.)
+struct DevScope {
+  DevAllocs mem;
+  ~DevScope() { dev_free(mem); }
+};
 
 // Bounded spin on a host-mapped word that a kernel stores last with a system-scope release.  True when the word was
 // seen: what the kernel wrote before it may then be read.  False: the caller falls back to its stream synchronise.
