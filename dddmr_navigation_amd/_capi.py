@@ -346,6 +346,7 @@ EXPORTED_SYMBOLS = (
     "dddmr_rollout_resolve_words",
     "dddmr_rollout_get_debug",
     "dddmr_rollout_heading_rows",
+    "dddmr_rollout_fused_walk",
     "dddmr_rollout_get_best_poses",
     "dddmr_rollout_get_best_cuboids",
     "dddmr_rollout_get_pose_arrays",
@@ -477,6 +478,9 @@ def load_library() -> C.CDLL:
     if hasattr(lib, "dddmr_rollout_heading_rows"):
         lib.dddmr_rollout_heading_rows.argtypes = [ctx_p]
         lib.dddmr_rollout_heading_rows.restype = C.c_int
+    if hasattr(lib, "dddmr_rollout_fused_walk"):
+        lib.dddmr_rollout_fused_walk.argtypes = [ctx_p]
+        lib.dddmr_rollout_fused_walk.restype = C.c_int
     lib.dddmr_rollout_get_best_poses.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.dddmr_rollout_get_best_poses.restype = C.c_int
     lib.dddmr_rollout_get_best_cuboids.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]

@@ -175,6 +175,7 @@ struct dddmr_rollout_ctx {
   int timing_every = 1;   // DDDMR_TIMING_EVERY: record the events on every n-th tick only
   int spin = 1;     // DDDMR_SPIN: poll the host-mapped result instead of hipStreamSynchronize
   int last_heading_rows = -1; // what the last launched tick did (dddmr_rollout_heading_rows)
+  int last_fused_walk = -1;   // ... and which way its k_score walked the prune plan (dddmr_rollout_fused_walk)
   uint32_t seq = 0;
   DevResult last_result{};   // host copy of the last COLLECTED tick's result
   float last_score_ms = 0.f, last_device_ms = 0.f;
@@ -308,6 +309,7 @@ void read_env(dddmr_rollout_ctx* ctx) {
   if (const char* e = std::getenv("DDDMR_THREADS")) kn.threads_override = std::atoi(e) == 512 ? 512 : 256;
   if (const char* e = std::getenv("DDDMR_TAIL_ROUND")) kn.tail_round = std::atoi(e) != 0;
   if (const char* e = std::getenv("DDDMR_HEADING_ROWS")) kn.heading_rows = std::atoi(e) != 0;
+  if (const char* e = std::getenv("DDDMR_FUSE_WALK")) kn.fuse_walk = std::atoi(e) != 0;
   if (const char* e = std::getenv("DDDMR_FINAL")) kn.final_mode = std::atoi(e) ? 1 : 0;
   if (const char* e = std::getenv("DDDMR_PROBE")) kn.probe_mode = std::atoi(e) ? 1 : 0;
   if (const char* e = std::getenv("DDDMR_TIMING")) ctx->timing = std::atoi(e);
@@ -750,6 +752,7 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
   ctx->feedback.load_theory = theory_id;
   ctx->feedback.load_nlocal = k.n_local;
   ctx->last_heading_rows = p.heading_rows;
+  ctx->last_fused_walk = k.n_local > 0 ? p.fused_walk : 0;
   drain.armed = true;       // from here on the stream reads the pinned cloud
   if (k.n_points > 0) {
     hipLaunchKernelGGL(k_bin_count, dim3(p.cnt_blocks + p.roll_blocks + (k.use_assign ? k.assign_groups : 0)), dim3(kBinThreads),
@@ -781,7 +784,7 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
   hipLaunchKernelGGL((k_score<T, L, P>), dim3(wgs), dim3(T), lds, ctx->stream, k, ctx->traj_info, ctx->st_sc,     \
                      ctx->st_xy, ctx->plan_dev, ctx->cell_start, ctx->sorted, ctx->costs, ctx->steps,             \
                      ctx->samples_out, ctx->best_key, ctx->overflow, ctx->tickets + 1, score_result, ctx->assign, \
-                     ctx->traj_load, score_words, ctx->row_tab, ctx->plan_pairs_dev, ctx->partial)
+                     ctx->traj_load, score_words, ctx->row_tab, ctx->plan_pairs_dev, ctx->partial, p.fused_walk)
     if (p.thr == 512) { if (p.lean) DDDMR_LAUNCH_SCORE(512, true); else DDDMR_LAUNCH_SCORE(512, false); }
     else              { if (p.lean) DDDMR_LAUNCH_SCORE(256, true); else DDDMR_LAUNCH_SCORE(256, false); }
 #undef DDDMR_LAUNCH_SCORE
@@ -995,6 +998,12 @@ int dddmr_rollout_heading_rows(dddmr_rollout_ctx* ctx) {
   if (!ctx) return -1;
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   return ctx->last_heading_rows;
+}
+
+int dddmr_rollout_fused_walk(dddmr_rollout_ctx* ctx) {
+  if (!ctx) return -1;
+  std::lock_guard<std::mutex> tk(ctx->tick_mu);
+  return ctx->last_fused_walk;
 }
 
 int dddmr_rollout_get_debug(dddmr_rollout_ctx* ctx, dddmr_rollout_debug* dbg) {

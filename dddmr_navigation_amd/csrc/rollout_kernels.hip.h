@@ -1424,11 +1424,16 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
     float4* __restrict__ samples_out, int64_t* __restrict__ best_key, uint32_t* __restrict__ overflow,
     uint32_t* __restrict__ ticket, DevResult* __restrict__ result, const uint32_t* __restrict__ assign,
     uint32_t* __restrict__ traj_load, int64_t* __restrict__ words_out, const uint32_t* __restrict__ row_tab,
-    const float* __restrict__ plan_pairs, TrajPartial* __restrict__ partial) {
+    const float* __restrict__ plan_pairs, TrajPartial* __restrict__ partial, const int fused_walk) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int tile = k.tile;
   const int S1 = k.max_steps + 1;
   const int Qcap = tile * k.max_steps;
+  // The fused walk (TickPlan::fused_walk, decided by plan_tick): the lean 512-lane kernel alone; every other
+  // instantiation carries the argument and ignores it.  (The host's conditions that memory safety rests on are checked
+  // again: every pair has a lane of its own, there is a plan.)
+  constexpr bool kCanFuse = kLean && kScoreThreads == 512;
+  const bool fused = kCanFuse && fused_walk != 0 && Qcap <= kScoreThreads && k.m > 0 && k.want_collision != 0 && k.n_points >= 5;
   const bool need_box = k.want_collision != 0, need_mm = !kLean && k.want_minmax != 0;
   const bool rec_pose = !kLean && k.rec_pose != 0;
   const bool box_fast = kLean || k.box_fast != 0;      // (the lean variant is only launched for body-frame boxes)
@@ -1533,7 +1538,8 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
     }
     pose_translation(k, bxy, T);
     const float px = (float)T[0], py = (float)T[1], pz = (float)T[2];   // trajectory.cpp:69-75
-    ppos[q] = make_float4(px, py, pz, 0.f);
+    // (w: where the pair's distance goes, for the fused walk -- nobody else reads it)
+    ppos[q] = make_float4(px, py, pz, kCanFuse ? __int_as_float(j * S1 + s) : 0.f);
 
     // ---- cuboid -> OBB record (collision_model.cpp:85-115) ----
     if (do_coll) {
@@ -1903,7 +1909,44 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
           }
         }
       }
-      __syncthreads();
+      // (a fused tick's last round ends at the barrier behind the plan walk below)
+      if (!(fused && round + 1 == n_rounds)) __syncthreads();
+    }
+    // ---- fused walk: the path critics' plan walk as the tail of the collision walk, for EVERY pair ----
+    // Phase P waits for the walk only to learn which trajectories collided, and with more than 256 surviving pairs
+    // that knowledge saves it nothing: every lane walks the whole plan either way.  On a fused tick (plan_tick keeps
+    // them to tiles whose pairs fit one pass of lanes, q == tid, and to few collisions) a wave goes from its last item
+    // straight into the plan walk for its own pairs: no survivor scan, no barrier before it, and the waves that were
+    // dealt no items walk the plan while the others still walk theirs.  The same chunks in the same order with the
+    // same arithmetic as phase P below, so the distances are the same bits; collided trajectories get distances too,
+    // which nobody reads.  (Spreading the plan's chunks over the items of the walk -- point loads issued, 2 / 4 / 8
+    // chunks, points tested -- was built and measured: it lost most of what this gains)
+    if (fused) {
+      const bool mine = tid < total_pairs;
+      float px = 0.f, py = 0.f, pz = 0.f, best = 3.402823466e+38f;
+      int dst = 0;
+      if (mine) {
+        const float4 pp = ppos[tid];              // the pose D1 composed for this pair
+        px = pp.x; py = pp.y; pz = pp.z;
+        dst = __float_as_int(pp.w);
+      }
+      if (__ballot(mine) != 0ull) {                 // wave-uniform, as in phase P: a wave walks with all its lanes
+        constexpr uint32_t kPoseBytes = 4u * kPlanPoseWords, kChunkBytes = kPoseBytes * kPlanChunk;
+        const uint32_t end = kPoseBytes * (uint32_t)k.m;
+        PlanChunk ca = plan_request(plan_pairs, 0u);
+        plan_wait(ca, best);
+        for (uint32_t o = 0; o < end; o += 2u * kChunkBytes) {
+          PlanChunk cb = plan_request(plan_pairs, o + kChunkBytes);
+          plan_current(ca);
+          best = plan_chunk_min(best, ca, px, py, pz);
+          plan_wait(cb, best);
+          ca = plan_request(plan_pairs, o + 2u * kChunkBytes);   // (the last one reads the slack)
+          plan_current(cb);
+          best = plan_chunk_min(best, cb, px, py, pz);
+          plan_wait(ca, best);
+        }
+      }
+      if (mine) dist[dst] = sqrtf(best);
     }
   }
   __syncthreads();
@@ -1916,6 +1959,8 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
   // reference never reaches them after CollisionModel returned -1
   // (stacked_scoring_model.cpp:83-86).  With most samples colliding in cluttered
   // scenes this skips most of the 1-NN searches.
+  // (a fused tick has every pair's distance already)
+  if (!fused) {
   if (tid < 64) {
     uint32_t st = 0;
     if (tid < nt) {
@@ -1996,7 +2041,8 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
     }
   }
   __syncthreads();
-  DDDMR_STAMP(8);   // end of phase P
+  }
+  DDDMR_STAMP(8);   // end of phase P (a fused tick: right behind stamp 6, its plan walk is the end of D3)
 
   // StickPath's sum of per-step distances (stick_path_model.cpp:62-73): one wave per
   // trajectory, lanes stride the steps, fixed reduction tree in double (the

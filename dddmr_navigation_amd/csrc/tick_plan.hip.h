@@ -243,6 +243,7 @@ struct TickKnobs {
   bool no_boxfast = false;    // DDDMR_NO_BOXFAST: always take the general vertex transform
   bool no_tab = false;        // DDDMR_NO_TAB: k_score reads the row-run index from L2 instead of staging it in LDS
   bool heading_rows = true;   // DDDMR_HEADING_ROWS=0: a heading chain per trajectory on every tick (rollout_kernels.hip.h)
+  bool fuse_walk = true;      // DDDMR_FUSE_WALK=0: phase P always stays a phase of its own behind the collision walk
   int n_cu = 256;             // compute units of the device
 };
 
@@ -273,9 +274,17 @@ struct TickPlan {
   size_t roll_lds = 0;      // the rollout's own dynamic LDS: its [rt][steps + 1] slots
   int heading_rows = 0;     // 1: the rollout shares heading rows per angular sample (heading_rows_shared())
   size_t roll_launch_lds = 0;   // dynamic LDS of the launch that rolls out: roll_lds, plus the rows when they are shared
+  int fused_walk = 0;       // 1: k_score walks the prune plan as the tail of the collision walk, for every pair (fused_walk_share_max())
   SampleUpload upload = kUploadNone;
   uint32_t n_samples = 0, local_begin = 0, n_local = 0;   // the result's head
 };
+
+// The fused walk (k_score, rollout_kernels.hip.h) spends phase P's arithmetic on every pair of a tile, colliding or not.
+// The separate phase walks the plan with one lane per SURVIVING pair and halves its work (two lanes a pair) once a tile
+// has at most 256 of them.  With `pairs` = tile x max_steps pairs a tile and a share c of the trajectories colliding, a
+// typical tile keeps pairs x (1 - c): more than 256, i.e. nothing saved by waiting for the verdicts, while
+// c <= 1 - 256 / pairs.  Derived, not tuned.  (C3: 6 x 80 pairs, bound 0.467; C2: 8 x 50, bound 0.36.)
+inline float fused_walk_share_max(int pairs) { return 1.0f - 256.0f / (float)pairs; }
 
 // dynamic LDS of a k_score workgroup of `tile` trajectories in the tick k describes
 size_t plan_score_lds(const DevTick& k, int tile) {
@@ -512,6 +521,15 @@ int plan_tick(const TickKnobs& kn, const TickFeedback& fb, const dddmr_rollout_c
   // gives identical results.
   const bool same_as_last = fb.load_theory == theory_id && fb.load_nlocal == k.n_local;
   k.probe = kn.probe_mode >= 0 ? kn.probe_mode : ((!same_as_last || fb.collided_share > 0.5f) ? 1 : 0);
+  // The prune-plan walk as the tail of the collision walk: lean launches whose pairs fit one pass of lanes, phase P on its
+  // one-lane-per-pose route (more than 256 pairs), and few enough collisions that waiting for the verdicts would save
+  // it nothing (fused_walk_share_max()).  A context's first tick (share 1.0) keeps the separate phase.  Either way
+  // gives identical results.
+  {
+    const int pairs = tile * s_tick;
+    p->fused_walk = (kn.fuse_walk && k.n_local > 0 && p->lean && k.want_collision && k.n_points >= 5 && k.m >= 1 && pairs <= thr &&
+                     pairs > 256 && fb.collided_share <= fused_walk_share_max(pairs)) ? 1 : 0;
+  }
   const bool one_round = k.n_local <= 0 || (k.n_local + tile - 1) / tile <= kn.n_cu * (thr == 512 ? 2 : 4);
   k.final_kernel = kn.final_mode >= 0 ? kn.final_mode : (one_round ? 0 : 1);
 

@@ -604,6 +604,11 @@ class LocalPlanner:
         own chain, -1 before any tick (dddmr_rollout_heading_rows)."""
         return int(self._lib.dddmr_rollout_heading_rows(self._ctx))
 
+    def fused_walk(self) -> int:
+        """1 if the last launched tick walked the prune plan as the tail of the collision walk, 0 if the path critics' search
+        ran as a phase of its own, -1 before any tick (dddmr_rollout_fused_walk)."""
+        return int(self._lib.dddmr_rollout_fused_walk(self._ctx))
+
     def best_poses(self) -> np.ndarray:
         n = C.c_size_t(0)
         self._check(self._lib.dddmr_rollout_get_best_poses(self._ctx, None, 0, C.byref(n)))

@@ -841,6 +841,13 @@ int dddmr_rollout_get_debug(dddmr_rollout_ctx* ctx, dddmr_rollout_debug* dbg);
    Both give the same bits; tests use this to know which path they compared. */
 int dddmr_rollout_heading_rows(dddmr_rollout_ctx* ctx);
 
+/* How the last launched tick searched the prune plan for the path critics: 1 as the tail of the collision walk, wave
+   by wave with no barrier in between, for every (trajectory, step) pair (lean 512-lane launches with more than 256 and at most 512 pairs a workgroup, a cloud of
+   at least 5 points, a plan, and a previous tick of which at most 1 - 256 / pairs of the trajectories collided;
+   DDDMR_FUSE_WALK=0 at create switches it off), 0 as a phase of its own for the surviving trajectories, -1 before any
+   tick.  Both give the same bits; tests use this to know which path they compared. */
+int dddmr_rollout_fused_walk(dddmr_rollout_ctx* ctx);
+
 /* Debug pose arrays of the last tick, poses_out[n][7] x y z qx qy qz qw, trajectory by
    trajectory in sample order, poses in step order: which = 0 the `trajectory` topic
    (every generated trajectory, local_planner.cpp:549-569), which = 1 the

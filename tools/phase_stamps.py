@@ -17,6 +17,8 @@ with LocalPlanner([sc.theory], max_points=max(len(sc.cloud), 16)) as lp:
     name = sc.theory.name.decode()
     for _ in range(5):
         r = lp.tick(name, sc.tick)
+    # which way the last tick's k_score walked the prune plan (a library built from an older commit has no such entry)
+    fused = lp.fused_walk() if hasattr(lib, "dddmr_rollout_fused_walk") else 0
     SL = 20
     n_wg = 16384
     buf = np.zeros(n_wg * SL, dtype=np.uint64)
@@ -71,6 +73,9 @@ with LocalPlanner([sc.theory], max_points=max(len(sc.cloud), 16)) as lp:
     order = np.argsort(-lifew)[:6]
     cols = [("A", 0, 1), ("D1", 3, 4), ("D2", 4, 5), ("D3", 5, 6), ("P", 6, 8), ("E", 8, 7)]
     med = {nm: np.median((st[:, b] - st[:, a]) / 1000.0) for nm, a, b in cols}
+    if fused == 1:
+        print("  fused walk: every wave walked the prune plan as the tail of D3, for every pair; there is no phase P (stamp 8 "
+              "is taken right behind stamp 6) -- P reads 0 and D3 holds its arithmetic")
     print("  median phases (kc):", " ".join(f"{nm} {med[nm]:.1f}" for nm, _, _ in cols), f"| life {np.median(lifew):.1f} us, items {np.median(tot):.0f}")
     for i in order:
         print(f"  slow wg: life {lifew[i]:.1f} us start {ws[i]:.2f} items {tot[i]:5d} |", " ".join(f"{nm} {(st[i, b] - st[i, a]) / 1000.0:.1f}" for nm, a, b in cols))
