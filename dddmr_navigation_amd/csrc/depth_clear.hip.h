@@ -338,7 +338,7 @@ struct DepthClear {
   uint2* slot = nullptr;
   uint32_t* cell_start = nullptr;
   float4* sorted = nullptr;
-  void* temp = nullptr;
+  char* temp = nullptr;              // rocPRIM storage of the scan
   size_t temp_bytes = 0;
   uint32_t n_obs = 0;
   uint64_t built_epoch = 0;
@@ -351,49 +351,26 @@ struct DepthClear {
   void* out_dev = nullptr;
   size_t out_cap = 0;
   uint32_t launches_last = 0;        // kernels, memsets and copies the last verdict call enqueued
+  Owned mem;
 };
 
-inline void dc_free(DepthClear& d) {
-  void* dev[] = {d.hdr, d.bounds, d.pts, d.slot, d.cell_start, d.sorted, d.temp};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
-  if (d.in_host) (void)hipHostFree(d.in_host);
-  if (d.out_host) (void)hipHostFree(d.out_host);
-  d = DepthClear();
-}
+inline void dc_free(DepthClear& d) { d = DepthClear(); }
 
-inline int dc_alloc(DepthClear& d, size_t max_points) {
+// temp_bytes: what rocPRIM's exclusive scan over kDcCapCells + 1 cells asks for (the caller's query: it needs the device)
+inline int dc_alloc(DepthClear& d, size_t max_points, size_t temp_bytes) {
   const size_t np = std::max<size_t>(max_points, 1);
-  if (hipMalloc(&d.hdr, sizeof(PointGrid)) != hipSuccess) return -1;
-  if (hipMalloc(&d.bounds, 6 * sizeof(uint32_t)) != hipSuccess) return -1;
-  if (hipMalloc(&d.pts, np * sizeof(float4)) != hipSuccess) return -1;
-  if (hipMalloc(&d.slot, np * sizeof(uint2)) != hipSuccess) return -1;
-  if (hipMalloc(&d.cell_start, ((size_t)kDcCapCells + 1) * sizeof(uint32_t)) != hipSuccess) return -1;
-  if (hipMalloc(&d.sorted, np * sizeof(float4)) != hipSuccess) return -1;
-  if (rocprim::exclusive_scan(nullptr, d.temp_bytes, d.cell_start, d.cell_start, 0u, (size_t)kDcCapCells + 1,
-                              rocprim::plus<uint32_t>(), nullptr) != hipSuccess)
+  DevAllocs& dev = d.mem.dev;
+  d.temp_bytes = temp_bytes;
+  if (dev_alloc(dev, &d.hdr, 1) != hipSuccess || dev_alloc(dev, &d.bounds, 6) != hipSuccess || dev_alloc(dev, &d.pts, np) != hipSuccess ||
+      dev_alloc(dev, &d.slot, np) != hipSuccess || dev_alloc(dev, &d.cell_start, (size_t)kDcCapCells + 1) != hipSuccess ||
+      dev_alloc(dev, &d.sorted, np) != hipSuccess || dev_alloc(dev, &d.temp, std::max<size_t>(temp_bytes, 16)) != hipSuccess)
     return -1;
-  if (hipMalloc(&d.temp, std::max<size_t>(d.temp_bytes, 16)) != hipSuccess) return -1;
   PointGrid g;
   g.cell_start = d.cell_start;
   g.sorted = d.sorted;
   const uint32_t b0[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
   if (hipMemcpy(d.hdr, &g, sizeof(g), hipMemcpyHostToDevice) != hipSuccess) return -1;
   if (hipMemcpy(d.bounds, b0, sizeof(b0), hipMemcpyHostToDevice) != hipSuccess) return -1;
-  return 0;
-}
-
-// make a pinned, device-mapped buffer hold at least `bytes` (the stream is idle: every call ends with a wait)
-inline int dc_reserve(void** host, void** dev, size_t* cap, size_t bytes) {
-  if (bytes <= *cap) return 0;
-  size_t want = std::max<size_t>(*cap, 1u << 16);
-  while (want < bytes) want <<= 1;
-  if (*host) (void)hipHostFree(*host);
-  *host = nullptr;
-  *dev = nullptr;
-  *cap = 0;
-  if (host_mapped_alloc(host, dev, want) != 0) return -1;
-  *cap = want;
   return 0;
 }
 

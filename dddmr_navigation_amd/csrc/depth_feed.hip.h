@@ -79,6 +79,7 @@ struct DepthSource {
   DepthResult* res_host = nullptr;
   DepthResult* res_dev = nullptr;
   uint32_t seq = 0;
+  Owned mem;
 };
 
 // One raw record per lane (valid = the lane has one), every lane of the wave calls it: bufferCloud's transform and
@@ -159,30 +160,20 @@ __global__ __launch_bounds__(256) void k_depth_emit(DepthParams f, const float4*
   }
 }
 
-inline void depth_free(DepthSource& s) {
-  for (float4* b : s.buf)
-    if (b) (void)hipFree(b);
-  if (s.surv) (void)hipFree(s.surv);
-  s.table.free();
-  if (s.counters) (void)hipFree(s.counters);
-  if (s.res_host) (void)hipHostFree(s.res_host);
-  if (s.stage) (void)hipHostFree(s.stage);
-  s = DepthSource();
-}
+inline void depth_free(DepthSource& s) { s = DepthSource(); }
 
 // max_points bounds what the source may publish; a frame under construction sits behind it.  raw_stage = false: a
 // source fed depth images, which stages those itself (depth_image.hip.h)
 inline int depth_alloc(DepthSource& s, size_t max_points, bool raw_stage = true) {
   const size_t F = s.max_frame_points;
   for (float4*& b : s.buf)
-    if (hipMalloc(&b, (max_points + F) * sizeof(float4)) != hipSuccess) return -1;
-  if (hipMalloc(&s.surv, F * sizeof(float4)) != hipSuccess) return -1;
-  if (s.table.alloc(F) != 0) return -1;
-  if (hipMalloc(&s.counters, 4 * sizeof(uint32_t)) != hipSuccess) return -1;
-  if (hipMemset(s.counters, 0, 4 * sizeof(uint32_t)) != hipSuccess) return -1;
-  if (host_mapped_alloc(&s.res_host, &s.res_dev, sizeof(DepthResult)) != 0) return -1;
+    if (dev_alloc(s.mem.dev, &b, max_points + F) != hipSuccess) return -1;
+  if (dev_alloc(s.mem.dev, &s.surv, F) != hipSuccess) return -1;
+  if (s.table.alloc(s.mem.dev, F) != 0) return -1;
+  if (dev_alloc_zeroed(s.mem.dev, &s.counters, 4) != hipSuccess) return -1;
+  if (host_mapped_alloc(s.mem.host, &s.res_host, &s.res_dev, sizeof(DepthResult)) != 0) return -1;
   // k_depth_insert reads the raw frame straight from this pinned, device-mapped buffer
-  if (raw_stage && host_mapped_alloc(&s.stage, &s.stage_dev, F * 4 * sizeof(float)) != 0) return -1;
+  if (raw_stage && host_mapped_alloc(s.mem.host, &s.stage, &s.stage_dev, F * 4 * sizeof(float)) != 0) return -1;
   std::memset(s.res_host, 0, sizeof(DepthResult));
   return 0;
 }
@@ -193,7 +184,7 @@ inline int depth_feed(DepthSource& s, DepthParams f, const float* raw, size_t st
   *n_out = 0;
   if (f.n == 0) return 0;
   const int stride_floats = stage_xyz_records(s.stage, raw, (size_t)f.n, stride_bytes);
-  const uint32_t seq = ++s.seq ? s.seq : ++s.seq;
+  const uint32_t seq = next_seq(s.seq);
   // table of this frame: the first `slots` entries, load <= 0.5 even if every record survives in a voxel of its own
   const size_t slots = voxel_slots_for((size_t)f.n);
   if (slots > s.table.slots) return -2;
@@ -203,9 +194,8 @@ inline int depth_feed(DepthSource& s, DepthParams f, const float* raw, size_t st
   // survivors and voxels are a fraction of the raw records: a fixed grid walks them
   const dim3 emit_grid(std::min<unsigned>(grid.x, kDepthEmitBlocks));
   hipLaunchKernelGGL(k_depth_emit, emit_grid, block, 0, stream, f, s.surv, table, out_dev, s.counters, s.res_dev, seq);
-  if (hipGetLastError() != hipSuccess) return -5;
   // the device chose the branch from its own count; the host waits once, for the last kernel's word
-  if (!wait_seq(&s.res_host->seq, seq) && hipStreamSynchronize(stream) != hipSuccess) return -4;
+  if (const int rc = feed_wait(stream, &s.res_host->seq, seq)) return rc;
   *n_out = s.res_host->n_out;
   return 0;
 }

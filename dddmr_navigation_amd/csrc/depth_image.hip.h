@@ -71,6 +71,7 @@ struct DepthImage {
   uint32_t n_cloud = 0;
   DimgResult* res_host = nullptr;
   DimgResult* res_dev = nullptr;
+  Owned mem;
 };
 
 __device__ __forceinline__ double dimg_shfl_up(double v, int delta) {
@@ -170,26 +171,17 @@ __global__ __launch_bounds__(256) void k_dimg_centroid(DepthParams f, VoxelView 
   }
 }
 
-inline void dimg_free(DepthImage& d) {
-  if (d.stage) (void)hipHostFree(d.stage);
-  d.table.free();
-  if (d.counters) (void)hipFree(d.counters);
-  for (float* c : d.cloud)
-    if (c) (void)hipFree(c);
-  if (d.res_host) (void)hipHostFree(d.res_host);
-  d = DepthImage();
-}
+inline void dimg_free(DepthImage& d) { d = DepthImage(); }
 
 // d.p and d.height are set; the tables hold every sampled pixel in a voxel of its own at load <= 0.5
 inline int dimg_alloc(DepthImage& d) {
   const size_t n = (size_t)d.p.rows * d.p.cols;
-  if (host_mapped_alloc(&d.stage, &d.stage_dev, (size_t)d.p.rows * d.p.width * sizeof(uint16_t) + 8) != 0) return -1;
-  if (d.table.alloc(n) != 0) return -1;
-  if (hipMalloc(&d.counters, 4 * sizeof(uint32_t)) != hipSuccess) return -1;
+  if (host_mapped_alloc(d.mem.host, &d.stage, &d.stage_dev, (size_t)d.p.rows * d.p.width * sizeof(uint16_t) + 8) != 0) return -1;
+  if (d.table.alloc(d.mem.dev, n) != 0) return -1;
+  if (dev_alloc_zeroed(d.mem.dev, &d.counters, 4) != hipSuccess) return -1;
   for (float*& c : d.cloud)
-    if (hipMalloc(&c, n * 3 * sizeof(float)) != hipSuccess) return -1;
-  if (hipMemset(d.counters, 0, 4 * sizeof(uint32_t)) != hipSuccess) return -1;
-  if (host_mapped_alloc(&d.res_host, &d.res_dev, sizeof(DimgResult)) != 0) return -1;
+    if (dev_alloc(d.mem.dev, &c, n * 3) != hipSuccess) return -1;
+  if (host_mapped_alloc(d.mem.host, &d.res_host, &d.res_dev, sizeof(DimgResult)) != 0) return -1;
   std::memset(d.res_host, 0, sizeof(DimgResult));
   return 0;
 }
@@ -231,7 +223,7 @@ inline int depth_image_feed(DepthSource& s, DepthImage& d, DepthParams f, const 
   // both tables in full: neither stage knows its voxel count before its kernel has run
   const VoxelView cam = d.table.view(d.table.slots, d.counters + 0);
   const VoxelView table = s.table.view(s.table.slots, s.counters + 2);
-  const uint32_t seq = ++s.seq ? s.seq : ++s.seq;
+  const uint32_t seq = next_seq(s.seq);
   const uint32_t n = p.rows * p.cols;
   const dim3 block(256);
   if (DDDMR_DIMG_PX == 4 && p.step == 1 && p.width % 4 == 0)
@@ -242,8 +234,7 @@ inline int depth_image_feed(DepthSource& s, DepthImage& d, DepthParams f, const 
   hipLaunchKernelGGL(k_dimg_centroid, walk, block, 0, stream, f, cam, d.counters, d.cloud[d.cur ^ 1], d.res_dev, s.surv, table,
                      s.counters);
   hipLaunchKernelGGL(k_depth_emit, walk, block, 0, stream, f, s.surv, table, out_dev, s.counters, s.res_dev, seq);
-  if (hipGetLastError() != hipSuccess) return -5;
-  if (!wait_seq(&s.res_host->seq, seq) && hipStreamSynchronize(stream) != hipSuccess) return -4;
+  if (const int rc = feed_wait(stream, &s.res_host->seq, seq)) return rc;
   *n_out = s.res_host->n_out;
   *n_camera = *reinterpret_cast<volatile uint32_t*>(&d.res_host->n_camera);
   return 0;

@@ -189,6 +189,7 @@ struct DepthLayerState {
   uint32_t* n_gen = nullptr;
   DlCounters* extra = nullptr;
   DevAllocs mem;                           // (of the above)
+  HostAllocs host;                         // (of out_host)
   void* out_host = nullptr;                // DlOut, tie arrays [3 * max_obs], fix list [max_obs / 2] uint2
   void* out_dev = nullptr;
   uint32_t seq = 0;
@@ -198,7 +199,7 @@ void depth_layer_free(DepthLayerState* s) {
   if (!s) return;
   dev_free(s->mem);
   store_free(s->store);
-  if (s->out_host) (void)hipHostFree(s->out_host);
+  host_free(s->host);
   depth_mark_free(s->dm);
   delete s;
 }
@@ -228,7 +229,7 @@ int depth_layer_init(dddmr_rollout_ctx* ctx, DepthLayerState* s, const float* gr
   HIPCHK(ctx, dev_alloc(s->mem, &s->n_gen, 1));
   HIPCHK(ctx, dev_alloc(s->mem, &s->extra, 1));
   const size_t bytes = sizeof(DlOut) + 3 * N * sizeof(uint32_t) + (N / 2 + 1) * sizeof(uint2);
-  if (host_mapped_alloc(&s->out_host, &s->out_dev, bytes) != 0) return fail(ctx, DDDMR_ERR_HIP, "depth_layer_create: staging of %zu bytes", bytes);
+  if (host_mapped_alloc(s->host, &s->out_host, &s->out_dev, bytes) != 0) return fail(ctx, DDDMR_ERR_HIP, "depth_layer_create: staging of %zu bytes", bytes);
   return store_reset(ctx, s->store, ctx->copy_stream, s->cfg.max_obstacle_distance);      // resetdGraph.  producer_mu held.
 }
 

@@ -177,6 +177,7 @@ struct DepthMarkState {
   uint32_t* fate = nullptr;
   MarkCounters* counters = nullptr;
   DevAllocs mem;                           // (of the two above)
+  HostAllocs host;                         // (of the staging below)
   // pinned + mapped results, grown on demand
   void* out_host = nullptr;
   void* out_dev = nullptr;
@@ -188,7 +189,7 @@ void depth_mark_free(DepthMarkState* s) {
   dev_free(s->mem);
   dev_free(s->sc.mem);
   dev_free(s->grids.mem);
-  if (s->out_host) (void)hipHostFree(s->out_host);
+  host_free(s->host);
   delete s;
 }
 
@@ -331,7 +332,7 @@ int dddmr_rollout_depth_mark_clusters(dddmr_rollout_ctx* ctx, const double T_gbl
   if ((rc = depth_observation_grid(ctx, d, n_obs, st, &ops)) != DDDMR_OK) return rc;
   const uint32_t n = (uint32_t)n_obs;
   const size_t rec_at = sizeof(DmHeader), pts_at = rec_at + (size_t)n * sizeof(DmRecord);
-  if (dc_reserve(&s->out_host, &s->out_dev, &s->out_cap, pts_at + (size_t)n * 12) != 0)
+  if (host_mapped_reserve(s->host, &s->out_host, &s->out_dev, &s->out_cap, pts_at + (size_t)n * 12) != 0)
     return fail(ctx, DDDMR_ERR_HIP, "depth_mark_clusters: staging for %u observation points", n);
 
   if ((rc = depth_mark_enqueue(ctx, s, T_gbl_base, d, n, S, st, &ops)) != DDDMR_OK) return rc;

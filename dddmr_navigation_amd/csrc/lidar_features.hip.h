@@ -74,7 +74,9 @@ struct LidarFeatures {
   bool have_sweep = false;             // a sweep has been accepted since the features were switched on
   FeatResult* res_host = nullptr;
   FeatResult* res_dev = nullptr;
+  Owned mem;
 };
+inline void FeaturesDelete::operator()(LidarFeatures* f) const { delete f; }
 
 __host__ __device__ __forceinline__ uint32_t feat_offset(uint32_t V, int which) {
   return which == 0 ? 0u : which == 1 ? kFeatSharp * V : (kFeatSharp + kFeatLess) * V;
@@ -358,28 +360,19 @@ __global__ __launch_bounds__(256) void k_feat_emit(FeatParams k, const uint32_t*
   feat_idx[o] = idx;
 }
 
-inline void features_free(LidarFeatures& f) {
-  void* dev[] = {f.block_cnt, f.n_dev, f.curv, f.meta, f.smooth, f.slots, f.slot_cnt, f.seg_pt[0], f.seg_pt[1], f.seg_cr[0], f.seg_cr[1],
-                 f.ring[0], f.ring[1], f.feat[0], f.feat[1], f.feat_idx[0], f.feat_idx[1]};
-  for (void* d : dev)
-    if (d) (void)hipFree(d);
-  if (f.res_host) (void)hipHostFree(f.res_host);
-  f = LidarFeatures();
-}
+inline void features_free(LidarFeatures& f) { f = LidarFeatures(); }
 
 // f.p is set
 inline int features_alloc(LidarFeatures& f) {
   const size_t V = f.p.V, px = V * f.p.H, blocks = (px + 255) / 256;
-  auto dev = [](auto** ptr, size_t bytes) {
-    return hipMalloc(reinterpret_cast<void**>(ptr), bytes) == hipSuccess && hipMemset(*ptr, 0, bytes) == hipSuccess;
-  };
-  bool ok = dev(&f.block_cnt, blocks * 4) && dev(&f.n_dev, 4) && dev(&f.curv, px * 4) && dev(&f.meta, px * 4) && dev(&f.smooth, px * 8) &&
-            dev(&f.slots, V * kFeatPerRing * 4) && dev(&f.slot_cnt, V * 3 * 4);
+  auto dev = [&f](auto** ptr, size_t count) { return dev_alloc_zeroed(f.mem.dev, ptr, count) == hipSuccess; };
+  bool ok = dev(&f.block_cnt, blocks) && dev(&f.n_dev, 1) && dev(&f.curv, px) && dev(&f.meta, px) && dev(&f.smooth, px) &&
+            dev(&f.slots, V * kFeatPerRing) && dev(&f.slot_cnt, V * 3);
   for (int b = 0; b < 2 && ok; ++b)
-    ok = dev(&f.seg_pt[b], px * sizeof(float4)) && dev(&f.seg_cr[b], px * 4) && dev(&f.ring[b], 2 * V * 4) &&
-         dev(&f.feat[b], V * kFeatPerRing * sizeof(float4)) && dev(&f.feat_idx[b], V * kFeatPerRing * 4);
+    ok = dev(&f.seg_pt[b], px) && dev(&f.seg_cr[b], px) && dev(&f.ring[b], 2 * V) && dev(&f.feat[b], V * kFeatPerRing) &&
+         dev(&f.feat_idx[b], V * kFeatPerRing);
   if (!ok) return -1;
-  if (host_mapped_alloc(&f.res_host, &f.res_dev, sizeof(FeatResult)) != 0) return -1;
+  if (host_mapped_alloc(f.mem.host, &f.res_host, &f.res_dev, sizeof(FeatResult)) != 0) return -1;
   std::memset(f.res_host, 0, sizeof(FeatResult));
   return 0;
 }

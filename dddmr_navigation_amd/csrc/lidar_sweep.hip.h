@@ -44,6 +44,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
+#include <memory>
 
 #include "perception_kernels.hip.h"
 
@@ -76,10 +77,13 @@ struct SweepResult {           // host-mapped, written by the last k_sweep_outpu
 struct LidarFeatures;           // lidar_features.hip.h
 inline void features_launch(LidarFeatures& f, int b, const int32_t* label_img, const uint8_t* ground_img, const float* range_img,
                             const float4* pts, hipStream_t stream);
+struct FeaturesDelete {         // (the type is complete only there)
+  void operator()(LidarFeatures* f) const;
+};
 
 struct LidarSweep {
   SweepParams p;
-  LidarFeatures* features = nullptr;   // not null: the source's features are on; owned by the engine
+  std::unique_ptr<LidarFeatures, FeaturesDelete> features;   // not null: the source's features are on
   uint32_t max_points = 0;             // raw points per sweep
   PerceptionScratch feed;              // stage two's table; its pinned staging holds the raw sweep
   float4* moved = nullptr;             // [max_points] pitch-removed point, range in w
@@ -102,6 +106,7 @@ struct LidarSweep {
   bool have_sweep = false;
   SweepResult* res_host = nullptr;
   SweepResult* res_dev = nullptr;
+  Owned mem;                           // (the nested scratch owns its own)
 };
 
 // :331-362 for one pitch-removed point: its pixel, or -1 when one of the three tests drops it
@@ -377,34 +382,21 @@ __global__ __launch_bounds__(256) void k_feed_insert_device(FeedParams f, const 
   feed_insert_record(f, s.x, s.y, s.z, table);
 }
 
-inline void sweep_free(LidarSweep& s) {
-  perception_free(s.feed);
-  void* dev[] = {s.moved, s.pix_idx, s.pts, s.parent, s.size, s.rows, s.num, s.block_cnt, s.n_dev,
-                 s.range_img[0], s.range_img[1], s.label_img[0], s.label_img[1], s.ground_img[0], s.ground_img[1],
-                 s.cloud[0], s.cloud[1], s.obs[0], s.obs[1]};
-  for (void* d : dev)
-    if (d) (void)hipFree(d);
-  if (s.res_host) (void)hipHostFree(s.res_host);
-  s = LidarSweep();
-}
+inline void sweep_free(LidarSweep& s) { s = LidarSweep(); }   // (with its features, if they are on)
 
 // s.p (V, H) and s.max_points are set
 inline int sweep_alloc(LidarSweep& s) {
   const size_t px = (size_t)s.p.V * s.p.H, blocks = (px + 255) / 256;
   if (perception_alloc(s.feed, std::max<size_t>(px, s.max_points)) != 0) return -1;
-  auto dev = [](auto** ptr, size_t bytes, bool zero) {
-    if (hipMalloc(reinterpret_cast<void**>(ptr), bytes) != hipSuccess) return false;
-    return !zero || hipMemset(*ptr, 0, bytes) == hipSuccess;
+  auto dev = [&s](auto** ptr, size_t count, bool zero = false) {
+    return (zero ? dev_alloc_zeroed(s.mem.dev, ptr, count) : dev_alloc(s.mem.dev, ptr, count)) == hipSuccess;
   };
-  bool ok = dev(&s.moved, std::max<size_t>(s.max_points, 1) * sizeof(float4), false) && dev(&s.pix_idx, px * 4, true) &&
-            dev(&s.pts, px * sizeof(float4), false) && dev(&s.parent, px * 4, false) && dev(&s.size, px * 4, true) &&
-            dev(&s.rows, px * 16, true) && dev(&s.num, px * 4, false) && dev(&s.block_cnt, blocks * sizeof(uint2), false) &&
-            dev(&s.n_dev, 4, true);
+  bool ok = dev(&s.moved, std::max<size_t>(s.max_points, 1)) && dev(&s.pix_idx, px, true) && dev(&s.pts, px) && dev(&s.parent, px) &&
+            dev(&s.size, px, true) && dev(&s.rows, 4 * px, true) && dev(&s.num, px) && dev(&s.block_cnt, blocks) && dev(&s.n_dev, 1, true);
   for (int b = 0; b < 2 && ok; ++b)
-    ok = dev(&s.range_img[b], px * 4, false) && dev(&s.label_img[b], px * 4, false) && dev(&s.ground_img[b], px, false) &&
-         dev(&s.cloud[b], px * sizeof(float4), false) && dev(&s.obs[b], px * sizeof(float4), false);
+    ok = dev(&s.range_img[b], px) && dev(&s.label_img[b], px) && dev(&s.ground_img[b], px) && dev(&s.cloud[b], px) && dev(&s.obs[b], px);
   if (!ok) return -1;
-  if (host_mapped_alloc(&s.res_host, &s.res_dev, sizeof(SweepResult)) != 0) return -1;
+  if (host_mapped_alloc(s.mem.host, &s.res_host, &s.res_dev, sizeof(SweepResult)) != 0) return -1;
   std::memset(s.res_host, 0, sizeof(SweepResult));
   return 0;
 }
@@ -434,11 +426,10 @@ inline int sweep_feed(LidarSweep& s, FeedParams f, const float* raw, size_t n, s
   // stage two: cbSensor on the device cloud; at most one point per pixel reaches it
   PerceptionScratch& ps = s.feed;
   const VoxelView table = ps.table.view(voxel_slots_for(px), ps.counters + 2);
-  const uint32_t seq = ++ps.seq ? ps.seq : ++ps.seq;
+  const uint32_t seq = next_seq(ps.seq);
   hipLaunchKernelGGL(k_feed_insert_device, per_pixel, block, 0, stream, f, s.cloud[b], s.n_dev, table);
   hipLaunchKernelGGL(k_feed_emit, per_pixel, block, 0, stream, f, table, s.obs[b], ps.counters, ps.res_dev, seq);
-  if (hipGetLastError() != hipSuccess) return -5;
-  if (!wait_seq(&ps.res_host->seq, seq) && hipStreamSynchronize(stream) != hipSuccess) return -4;
+  if (const int rc = feed_wait(stream, &ps.res_host->seq, seq)) return rc;
   *n_out = ps.res_host->n_out;
   *n_segmented = *reinterpret_cast<volatile uint32_t*>(&s.res_host->n_segmented);
   return 0;

@@ -92,6 +92,7 @@ struct MarkingState {
   float4 *proj = nullptr, *gen = nullptr;
   uint32_t* pool_ofs = nullptr;
   DevAllocs mem;              // the device allocations of this struct itself
+  HostAllocs host;            // ... and host_out
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
   uint32_t seq = 0;
   // fused route (marking_fused.hip.h)
@@ -102,7 +103,7 @@ struct MarkingState {
   uint32_t* cell_count = nullptr;          // [kFuseMaxCells], all zero between updates
   bool alive_list_stale = false;           // the fused route keeps no alive list: the general route rebuilds it first
   uint32_t* ticket = nullptr;              // [2]
-  MarkCounters* host_out = nullptr;        // host-mapped (hipHostMalloc), host_out_dev = its device address
+  MarkCounters* host_out = nullptr;        // host-mapped, host_out_dev = its device address
   MarkCounters* host_out_dev = nullptr;
   bool counters_clean = false;             // device counters zeroed (pool fill kept) by the last fused update
   int route = -1;                          // DDDMR_MARKING_ROUTE: -1 by size, 0 general (rocPRIM), 1 fused only
@@ -120,7 +121,7 @@ void marking_free(MarkingState* m) {
   dev_free(m->sc.mem);
   dev_free(m->grids.mem);
   store_free(m->store);
-  if (m->host_out) (void)hipHostFree(m->host_out);
+  host_free(m->host);
   if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
   if (m->e0) (void)hipEventDestroy(m->e0);
   if (m->e1) (void)hipEventDestroy(m->e1);
@@ -174,11 +175,11 @@ int upload_static(dddmr_rollout_ctx* ctx, DevAllocs& mem, void* temp, size_t tem
     b.max_row = 0;
     for (uint32_t r : rows) b.max_row = std::max(b.max_row, r);
   }
+  DevScope scope;
   uint2* slot = nullptr;
-  HIPCHK(ctx, hipMalloc(&slot, std::max<size_t>(n, 1) * sizeof(uint2)));
+  HIPCHK(ctx, dev_alloc(scope.mem, &slot, std::max<size_t>(n, 1)));
   const int rb = grid_build(ctx, temp, temp_bytes, b, *dev, (uint32_t)n, slot, ctx->stream);
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  (void)hipFree(slot);
   return rb;
 }
 
@@ -281,8 +282,8 @@ int dddmr_rollout_marking_create(dddmr_rollout_ctx* ctx, const dddmr_marking_con
     HIPCHK(ctx, hipMemset(m->cell_count, 0, (size_t)kFuseMaxCells * sizeof(uint32_t)));
     HIPCHK(ctx, dev_alloc(m->mem, &m->ticket, 34));
     HIPCHK(ctx, hipMemset(m->ticket, 0, 34 * sizeof(uint32_t)));
-    HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&m->host_out), sizeof(MarkCounters), hipHostMallocMapped));
-    HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&m->host_out_dev), m->host_out, 0));
+    if (host_mapped_alloc(m->host, &m->host_out, &m->host_out_dev, sizeof(MarkCounters)) != 0)
+      return fail(ctx, DDDMR_ERR_HIP, "marking_create: host-mapped counters");
     MarkKnobs& kn = m->knobs;
     if (const char* e = std::getenv("DDDMR_MKF_UNMARK")) kn.unmark_with_groups = std::strcmp(e, "roots") != 0;
     if (const char* e = std::getenv("DDDMR_MKF_GRIDPARTS")) { const int v = std::atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8) kn.grid_parts = (uint32_t)v; }

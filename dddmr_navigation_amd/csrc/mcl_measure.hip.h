@@ -345,6 +345,7 @@ struct MclState {
   MclTerms t{};
   float* qual_dev = nullptr;
   DevAllocs mem;
+  HostAllocs host;
   // host-mapped: the call's inputs (read in place by the kernels) and results
   float4 *obs_host = nullptr, *obs_dev = nullptr;
   float *states_host = nullptr, *states_dev = nullptr;
@@ -359,10 +360,7 @@ void mcl_free(MclState* s) {
   if (!s) return;
   mclobs_free(s->obs);
   dev_free(s->mem);
-  if (s->obs_host) (void)hipHostFree(s->obs_host);
-  if (s->states_host) (void)hipHostFree(s->states_host);
-  if (s->out_host) (void)hipHostFree(s->out_host);
-  if (s->res_host) (void)hipHostFree(s->res_host);
+  host_free(s->host);
   delete s;
 }
 
@@ -393,10 +391,10 @@ int mcl_alloc(dddmr_rollout_ctx* ctx, MclState* s) {
   HIPCHK(ctx, dev_alloc(s->mem, &s->t.n_ground, N));
   HIPCHK(ctx, dev_alloc(s->mem, &s->t.flags, N));
   HIPCHK(ctx, dev_alloc(s->mem, &s->qual_dev, N));
-  if (host_mapped_alloc(&s->obs_host, &s->obs_dev, (size_t)c.max_observation_points * sizeof(float4)) != 0 ||
-      host_mapped_alloc(&s->states_host, &s->states_dev, N * 7 * sizeof(float)) != 0 ||
-      host_mapped_alloc(&s->out_host, &s->out_dev, N * 2 * sizeof(float)) != 0 ||
-      host_mapped_alloc(&s->res_host, &s->res_dev, sizeof(MclResult)) != 0)
+  if (host_mapped_alloc(s->host, &s->obs_host, &s->obs_dev, (size_t)c.max_observation_points * sizeof(float4)) != 0 ||
+      host_mapped_alloc(s->host, &s->states_host, &s->states_dev, N * 7 * sizeof(float)) != 0 ||
+      host_mapped_alloc(s->host, &s->out_host, &s->out_dev, N * 2 * sizeof(float)) != 0 ||
+      host_mapped_alloc(s->host, &s->res_host, &s->res_dev, sizeof(MclResult)) != 0)
     return fail(ctx, DDDMR_ERR_HIP, "mcl_create: host-mapped staging");
   std::memset(s->res_host, 0, sizeof(MclResult));
   return DDDMR_OK;
@@ -460,7 +458,7 @@ int mcl_run(dddmr_rollout_ctx* ctx, const char* what, MclState* s, const float4*
   k.n_states = (uint32_t)n_states;
   const MclMap& m = s->maps[s->cur];
   const uint32_t n_obs = k.n_flat + k.n_ls, N = k.n_states;
-  const uint32_t seq = ++s->seq ? s->seq : ++s->seq;
+  const uint32_t seq = next_seq(s->seq);
   hipStream_t st = ctx->stream;
   hipLaunchKernelGGL(k_mcl_ground, dim3(N), dim3(64), 0, st, k, m.ground.g, m.map.g, m.normals, s->states_dev, s->t);
   const uint32_t blocks = std::min<uint32_t>((N + 3) / 4, 2048u);

@@ -420,6 +420,7 @@ struct MclObs {
   float4* pts = nullptr;
   uint2* slot_rank = nullptr;
   DevAllocs mem;
+  HostAllocs host;
   // host-mapped: the host entry's input, the kept clusters' sizes, their plan, the result
   float4 *in_host = nullptr, *in_dev = nullptr;
   uint32_t *kept_host = nullptr, *kept_dev = nullptr;
@@ -431,10 +432,7 @@ struct MclObs {
 void mclobs_free(MclObs* o) {
   if (!o) return;
   dev_free(o->mem);
-  if (o->in_host) (void)hipHostFree(o->in_host);
-  if (o->kept_host) (void)hipHostFree(o->kept_host);
-  if (o->plan_host) (void)hipHostFree(o->plan_host);
-  if (o->res_host) (void)hipHostFree(o->res_host);
+  host_free(o->host);
   delete o;
 }
 
@@ -446,10 +444,10 @@ int mclobs_alloc(dddmr_rollout_ctx* ctx, MclObs* o) {
   }
   HIPCHK(ctx, dev_alloc(o->mem, &o->pts, nl));
   HIPCHK(ctx, dev_alloc(o->mem, &o->slot_rank, nl));
-  if (host_mapped_alloc(&o->in_host, &o->in_dev, cap * sizeof(float4)) != 0 ||
-      host_mapped_alloc(&o->kept_host, &o->kept_dev, nl * sizeof(uint32_t)) != 0 ||
-      host_mapped_alloc(&o->plan_host, &o->plan_dev, nl * sizeof(uint2)) != 0 ||
-      host_mapped_alloc(&o->res_host, &o->res_dev, sizeof(MclObsResult)) != 0)
+  if (host_mapped_alloc(o->host, &o->in_host, &o->in_dev, cap * sizeof(float4)) != 0 ||
+      host_mapped_alloc(o->host, &o->kept_host, &o->kept_dev, nl * sizeof(uint32_t)) != 0 ||
+      host_mapped_alloc(o->host, &o->plan_host, &o->plan_dev, nl * sizeof(uint2)) != 0 ||
+      host_mapped_alloc(o->host, &o->res_host, &o->res_dev, sizeof(MclObsResult)) != 0)
     return fail(ctx, DDDMR_ERR_HIP, "mcl_set_observation_config: host-mapped staging");
   std::memset(o->res_host, 0, sizeof(MclObsResult));
   return DDDMR_OK;
@@ -468,7 +466,7 @@ int mclobs_run(dddmr_rollout_ctx* ctx, const char* what, MclObs* o, const float4
   k.min_size = o->cfg.euc_cluster_min_size;
   k.n_flat = n_flat;
   k.n_ls = n_ls;
-  k.seq = ++o->seq ? o->seq : ++o->seq;
+  k.seq = next_seq(o->seq);
   const int b = o->cur ^ 1;
   hipStream_t st = ctx->stream;
   hipLaunchKernelGGL(k_mclobs_prepare, dim3(1), dim3(kMclObsThreads), 0, st, k, flat_dev, ls_dev, o->obs[b], o->normals[b], o->pts, o->slot_rank,

@@ -52,6 +52,7 @@ struct PerceptionScratch {
   // stitcher (cbSensor :185-200): the last stitcher_num raw scans, oldest first, packed xyz in `stage`
   int stitcher_num = 0;
   std::deque<uint32_t> stitched;       // point counts of the queued scans
+  Owned mem;
 };
 
 // one raw record through cbSensor's transform, crop and voxel insert
@@ -97,25 +98,18 @@ __global__ __launch_bounds__(256) void k_feed_emit(FeedParams f, VoxelView table
 
 inline int perception_alloc(PerceptionScratch& s, size_t max_points) {
   s.cap_points = max_points;
-  if (s.table.alloc(max_points) != 0) return -1;
-  if (hipMalloc(&s.counters, 4 * sizeof(uint32_t)) != hipSuccess) return -1;
-  if (hipMemset(s.counters, 0, 4 * sizeof(uint32_t)) != hipSuccess) return -1;
-  if (host_mapped_alloc(&s.res_host, &s.res_dev, sizeof(FeedResult)) != 0) return -1;
+  if (s.table.alloc(s.mem.dev, max_points) != 0) return -1;
+  if (dev_alloc_zeroed(s.mem.dev, &s.counters, 4) != hipSuccess) return -1;
+  if (host_mapped_alloc(s.mem.host, &s.res_host, &s.res_dev, sizeof(FeedResult)) != 0) return -1;
   // the raw scan is read by k_feed_insert straight from this pinned, device-mapped buffer
   // (no separate H2D copy: the kernel's coalesced reads stream it over PCIe)
-  if (host_mapped_alloc(&s.stage, &s.stage_dev, max_points * 4 * sizeof(float)) != 0) return -1;
+  if (host_mapped_alloc(s.mem.host, &s.stage, &s.stage_dev, max_points * 4 * sizeof(float)) != 0) return -1;
   s.res_host->n_out = 0;
   s.res_host->seq = 0;
   return 0;
 }
 
-inline void perception_free(PerceptionScratch& s) {
-  s.table.free();
-  if (s.counters) (void)hipFree(s.counters);
-  if (s.res_host) (void)hipHostFree(s.res_host);
-  if (s.stage) (void)hipHostFree(s.stage);
-  s = PerceptionScratch();
-}
+inline void perception_free(PerceptionScratch& s) { s = PerceptionScratch(); }
 
 // scan: caller's records (stride_bytes apart, x y z first).  Output: out_dev (global frame).
 // With a stitcher depth N > 0 the scan joins the queue of the last N raw scans (the oldest one leaves when
@@ -147,13 +141,11 @@ inline int perception_feed(PerceptionScratch& s, FeedParams f, const float* scan
   // the raw records go to pinned memory (the stitcher's queue is there already, packed)
   const int stride_floats = stitch ? 3 : stage_xyz_records(s.stage, scan, (size_t)f.n, stride_bytes);
   const VoxelView table = s.table.view(slots, s.counters + 2);
-  const uint32_t seq = ++s.seq ? s.seq : ++s.seq;
+  const uint32_t seq = next_seq(s.seq);
   hipLaunchKernelGGL(k_feed_insert, dim3((f.n + 255) / 256), dim3(256), 0, stream, f, s.stage_dev, stride_floats, table);
   hipLaunchKernelGGL(k_feed_emit, dim3((unsigned)((f.n + 255) / 256)), dim3(256), 0, stream, f, table, out_dev, s.counters,
                      s.res_dev, seq);
-  if (hipGetLastError() != hipSuccess) return -5;
-  // poll the host-mapped sequence number (bounded), then make sure the stream is idle
-  if (!wait_seq(&s.res_host->seq, seq) && hipStreamSynchronize(stream) != hipSuccess) return -4;
+  if (const int rc = feed_wait(stream, &s.res_host->seq, seq)) return rc;
   *n_out = s.res_host->n_out;
   return 0;
 }

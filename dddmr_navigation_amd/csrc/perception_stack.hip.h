@@ -96,6 +96,7 @@ struct StackState {
   uint32_t* n_changed_dev = nullptr;
   float4* lidar_obs = nullptr;               // gather buffer for lidar sources that are not neighbours in the aggregate (lazy)
   DevAllocs mem;
+  HostAllocs host;
   // host-mapped: uint32 count | pad | double value[cap] | uint32 node[cap] | uint8 mask[cap]
   char *list_host = nullptr, *list_dev = nullptr;
   uint32_t n_changed = 0;                    // of the last update (true count)
@@ -104,7 +105,7 @@ struct StackState {
 void stack_free(StackState* s) {
   if (!s) return;
   dev_free(s->mem);
-  if (s->list_host) (void)hipHostFree(s->list_host);
+  host_free(s->host);
   delete s;
 }
 
@@ -193,7 +194,7 @@ int dddmr_rollout_stack_create(dddmr_rollout_ctx* ctx, const dddmr_stack_config*
     HIPCHK(ctx, dev_alloc(s->mem, &s->n_changed_dev, 1));
     for (int i = 0; i < cfg->n_host_layers; ++i) HIPCHK(ctx, dev_alloc(s->mem, &s->host_layer[i], s->n_nodes));
     const size_t bytes = 8 + 13 * stack_cap(s);
-    if (host_mapped_alloc(&s->list_host, &s->list_dev, bytes) != 0) return fail(ctx, DDDMR_ERR_HIP, "stack_create: change list of %zu bytes", bytes);
+    if (host_mapped_alloc(s->host, &s->list_host, &s->list_dev, bytes) != 0) return fail(ctx, DDDMR_ERR_HIP, "stack_create: change list of %zu bytes", bytes);
     // (the published arrays start as a pattern no result has, so the first pass writes every node)
     HIPCHK(ctx, hipMemsetAsync(s->min_pub, 0xFF, (size_t)s->n_nodes * sizeof(double), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(s->mask_pub, 0xFF, s->n_nodes, ctx->stream));

@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -54,13 +55,15 @@ struct MclState;                           // the particle filter's lidar likeli
 void mcl_free(MclState* s);
 
 // What a sensor source owns, beside its record in the context's SourceTable (sensor_sources.hip.h keeps the two in step).
+// Each state frees its memory when it dies: assigning an empty SourceOwned tears the source down (release_source).
 struct SourceOwned {
-  PerceptionScratch* feed = nullptr;       // scan sources above 0: stitcher state and staging (source 0 feeds through ctx->feed)
-  DepthSource* depth = nullptr;            // depth sources
-  DepthImage* dimg = nullptr;              // ... that are fed images
-  LidarSweep* sweep = nullptr;             // sweep sources
-  // the latest observation on the device: a scan source's own allocation (made by its first feed), otherwise an alias of
-  // the depth source's current frame buffer or of the sweep's current observation buffer
+  std::unique_ptr<PerceptionScratch> feed; // scan sources above 0: stitcher state and staging (source 0 feeds through ctx->feed)
+  std::unique_ptr<DepthSource> depth;      // depth sources
+  std::unique_ptr<DepthImage> dimg;        // ... that are fed images
+  std::unique_ptr<LidarSweep> sweep;       // sweep sources
+  Owned scan_obs;                          // a scan source's observation buffer, made by its first feed
+  // the latest observation on the device, an alias: of the buffer in scan_obs, of the depth source's current frame buffer
+  // or of the sweep's current observation buffer
   float4* obs = nullptr;
   DcFrustum frustum{};                     // depth sources: valid while the record says has_frustum
 };
@@ -73,6 +76,7 @@ struct dddmr_rollout_ctx {
   int device = 0;
   hipStream_t stream = nullptr, copy_stream = nullptr;
   DevAllocs mem;           // every device allocation of the context itself (the modules and sources own theirs)
+  HostAllocs host;         // ... and its pinned host memory
   // k_rollout state arrays, grown on demand: [n_local][max steps of the tick] (of st_sc a tick with shared heading rows
   // fills only the first nth rows, one per angular sample)
   TrajInfo* traj_info = nullptr;
@@ -127,7 +131,7 @@ struct dddmr_rollout_ctx {
   static constexpr int kMaxSources = DDDMR_MAX_SOURCES;
   SourceTable sources;
   SourceOwned src[kMaxSources];
-  DepthClear* dclear = nullptr;     // the clearing verdicts' scratch (depth_clear.hip.h), allocated by the first verdict / point-test call
+  std::unique_ptr<DepthClear> dclear;   // the clearing verdicts' scratch (depth_clear.hip.h), allocated by the first verdict / point-test call
 
   // pinned host memory
   float4* cloud_stage[kCloudBufs] = {nullptr, nullptr, nullptr};   // pinned staging, one per device cloud buffer
@@ -248,15 +252,6 @@ class CloudPin {
   bool owns_;
   int idx_ = -1;
   bool need_wait_ = false, is_front_ = false;
-};
-
-// An error return may leave work enqueued that reads a pinned cloud buffer: while armed, the guard waits for the stream
-// when it goes out of scope, so that a CloudPin declared BEFORE it releases a buffer nothing reads any more and the next
-// call finds the stream idle.  Disarmed where the function has waited itself or handed the pin to the pending tick.
-struct Drain {
-  hipStream_t st;
-  bool armed = true;
-  ~Drain() { if (armed) (void)hipStreamSynchronize(st); }
 };
 
 void release_source(dddmr_rollout_ctx* c, int id);   // sensor_sources.hip.h
@@ -391,11 +386,9 @@ void dddmr_rollout_destroy(dddmr_rollout_ctx* ctx) {
   if (ctx->comm) (void)rccl().comm_destroy(ctx->comm);
   dev_free(ctx->mem);
   perception_free(ctx->feed);
-  if (ctx->dclear) { dc_free(*ctx->dclear); delete ctx->dclear; }
+  ctx->dclear.reset();
   for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) release_source(ctx, i);
-  for (void* p : {(void*)ctx->cloud_stage[0], (void*)ctx->cloud_stage[1], (void*)ctx->cloud_stage[2], (void*)ctx->small_stage,
-                  (void*)ctx->result_host})
-    if (p) (void)hipHostFree(p);
+  host_free(ctx->host);
   for (hipEvent_t e : {ctx->cloud_ready[0], ctx->cloud_ready[1], ctx->cloud_ready[2], ctx->ev0, ctx->ev1, ctx->evs0, ctx->evs1})
     if (e) (void)hipEventDestroy(e);
   for (hipStream_t s : {ctx->stream, ctx->copy_stream})
@@ -474,11 +467,11 @@ int dddmr_rollout_create(const dddmr_rollout_config* cfg, dddmr_rollout_ctx** ou
     HIPCHK(ctx, dev_alloc(mem, &ctx->poses_dev, (size_t)cfg->max_steps * 7));
     HIPCHK(ctx, dev_alloc(mem, &ctx->blocked_plan, (size_t)kBlockedMaxPlan));
     HIPCHK(ctx, dev_alloc(mem, &ctx->blocked_flags, (size_t)kBlockedMaxPlan / 32));
-    for (int i = 0; i < kCloudBufs; ++i) HIPCHK(ctx, hipHostMalloc(&ctx->cloud_stage[i], P * sizeof(float4), hipHostMallocDefault));
+    for (int i = 0; i < kCloudBufs; ++i) HIPCHK(ctx, host_alloc(ctx->host, &ctx->cloud_stage[i], P * sizeof(float4)));
     const size_t small = std::max<size_t>({3 * kMaxAxis * sizeof(float), N * sizeof(float4),
                                            plan_cap * sizeof(float4)});
-    HIPCHK(ctx, hipHostMalloc(&ctx->small_stage, small, hipHostMallocDefault));
-    if (host_mapped_alloc(&ctx->result_host, &ctx->result_dev, sizeof(DevResult)) != 0)
+    HIPCHK(ctx, host_alloc(ctx->host, &ctx->small_stage, small));
+    if (host_mapped_alloc(ctx->host, &ctx->result_host, &ctx->result_dev, sizeof(DevResult)) != 0)
       return fail(ctx, DDDMR_ERR_HIP, "result record allocation failed");
     const int rc = perception_alloc(ctx->feed, P);
     if (rc != 0) return fail(ctx, DDDMR_ERR_HIP, "perception scratch allocation failed");

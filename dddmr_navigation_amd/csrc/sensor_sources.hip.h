@@ -40,47 +40,33 @@ int read_back(dddmr_rollout_ctx* ctx, const char* what, void* out, const void* d
   *n_out = count;
   if (!out) return DDDMR_OK;
   if (capacity < count) return fail(ctx, DDDMR_ERR_CAPACITY, "%s: capacity %zu < %u", what, capacity, count);
-  if (count) {
+  if (count) {                                         // (one enqueue and its wait: no exit lies between them)
     HIPCHK(ctx, hipMemcpyAsync(out, dev, (size_t)count * elem_bytes, hipMemcpyDeviceToHost, ctx->copy_stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
   }
   return DDDMR_OK;
 }
 
+// How every module state below is made: in a unique_ptr of its own, which moves into its slot once the state is complete.
+// One that could not be allocated in full frees what it got as the pointer goes out of scope (Owned, voxel_table.hip.h);
+// resetting the slot is the whole teardown.
+
 // the feed scratch (stitcher state, staging) of a scan source above 0, allocated on first use
 int scan_scratch(dddmr_rollout_ctx* ctx, const char* what, int id, PerceptionScratch** out) {
   SourceOwned& own = ctx->src[id];
   if (!own.feed) {
-    auto* ps = new PerceptionScratch();
-    if (perception_alloc(*ps, ctx->cfg.max_points) != 0) {
-      perception_free(*ps);
-      delete ps;
-      return fail(ctx, DDDMR_ERR_HIP, "%s: scratch of source %d", what, id);
-    }
-    own.feed = ps;
+    auto ps = std::make_unique<PerceptionScratch>();
+    if (perception_alloc(*ps, ctx->cfg.max_points) != 0) return fail(ctx, DDDMR_ERR_HIP, "%s: scratch of source %d", what, id);
+    own.feed = std::move(ps);
   }
-  *out = own.feed;
+  *out = own.feed.get();
   return DDDMR_OK;
 }
 
-void sweep_features_off(LidarSweep& sw) {
-  if (!sw.features) return;
-  features_free(*sw.features);
-  delete sw.features;
-  sw.features = nullptr;
-}
-
-// Tear a source of any kind down: what it owns is freed, its record is cleared (its points leave the next aggregate).
-// The caller has made sure that no device work still reads its buffers.
+// Tear a source of any kind down: its record is cleared (its points leave the next aggregate) and what it owns is freed,
+// here and nowhere else.  The caller has synchronised copy_stream: no device work still reads the source's buffers.
 void release_source(dddmr_rollout_ctx* ctx, int id) {
-  SourceOwned& own = ctx->src[id];
-  const bool aliased = own.depth || own.sweep;         // obs is one of their buffers
-  if (own.depth) { depth_free(*own.depth); delete own.depth; }
-  if (own.dimg) { dimg_free(*own.dimg); delete own.dimg; }
-  if (own.sweep) { sweep_features_off(*own.sweep); sweep_free(*own.sweep); delete own.sweep; }
-  if (own.feed) { perception_free(*own.feed); delete own.feed; }
-  if (own.obs && !aliased) (void)hipFree(own.obs);
-  own = SourceOwned{};
+  ctx->src[id] = SourceOwned{};
   ctx->sources.release(id);
 }
 
@@ -89,12 +75,14 @@ void release_source(dddmr_rollout_ctx* ctx, int id) {
 int publish_sources(dddmr_rollout_ctx* ctx, uint32_t* n_aggregate) {
   const int back = acquire_back(ctx);
   const SourceLayout L = ctx->sources.layout();
+  Drain drain{ctx->copy_stream};                       // an error exit leaves no copy behind that reads a source's buffer
   for (int i = 0; i < SourceTable::kMax; ++i) {
     if (!L.n[i]) continue;
     HIPCHK(ctx, hipMemcpyAsync(ctx->cloud_dev[back] + L.at[i], ctx->src[i].obs, (size_t)L.n[i] * sizeof(float4), hipMemcpyDeviceToDevice, ctx->copy_stream));
   }
   // the tick's stream waits on this event, so the work that built the observations need not have retired yet
   HIPCHK(ctx, hipEventRecord(ctx->cloud_ready[back], ctx->copy_stream));
+  drain.armed = false;                                 // (success never waits here)
   publish_cloud(ctx, back, L.total, L);
   *n_aggregate = L.total;
   return DDDMR_OK;
@@ -164,7 +152,7 @@ static int set_scan_impl(dddmr_rollout_ctx* ctx, int source, const float* xyz, s
   SourceOwned* own = source >= 0 ? &ctx->src[source] : nullptr;
   if (own) {
     table.note_scan(source);
-    if (!own->obs) HIPCHK(ctx, hipMalloc(&own->obs, (size_t)std::max<uint32_t>(ctx->cfg.max_points, 1) * sizeof(float4)));
+    if (!own->obs) HIPCHK(ctx, dev_alloc(own->scan_obs.dev, &own->obs, std::max<uint32_t>(ctx->cfg.max_points, 1)));
   }
   const int back = own ? -1 : acquire_back(ctx);       // the single-producer form feeds straight into the back buffer
   FeedParams fp;
@@ -277,31 +265,25 @@ static int set_depth_source_impl(dddmr_rollout_ctx* ctx, const char* what, int32
   if ((rc = source_refused(ctx, what, SourceOp::kConfigureDepth, source_id)) != DDDMR_OK) return rc;
   bool had_points;
   if ((rc = configure_begin(ctx, source_id, &had_points)) != DDDMR_OK) return rc;   // (the frustum leaves with the observations)
-  auto* ds = new DepthSource();
+  auto ds = std::make_unique<DepthSource>();
   ds->zmin = cfg->min_obstacle_height;
   ds->zmax = cfg->max_obstacle_height;
   ds->persistence_ns = cfg->observation_persistence_ns;
   ds->max_frame_points = cfg->max_frame_points;
   ds->max_frames = cfg->max_frames;
-  DepthImage* di = nullptr;
+  std::unique_ptr<DepthImage> di;
   if (icfg) {
-    di = new DepthImage();
+    di = std::make_unique<DepthImage>();
     di->p = ip;
     di->height = icfg->height;
   }
   if (depth_alloc(*ds, ctx->cfg.max_points, icfg == nullptr) != 0 || (di && dimg_alloc(*di) != 0)) {
-    depth_free(*ds);
-    delete ds;
-    if (di) {
-      dimg_free(*di);
-      delete di;
-    }
     rc = fail(ctx, DDDMR_ERR_HIP, "%s: scratch of source %d", what, source_id);
   } else {
-    ctx->src[source_id].depth = ds;
-    ctx->src[source_id].dimg = di;
     ctx->src[source_id].obs = ds->buf[ds->cur];
     ctx->sources.configure(source_id, di ? SourceKind::kDepthImage : SourceKind::kDepthCloud);
+    ctx->src[source_id].depth = std::move(ds);
+    ctx->src[source_id].dimg = std::move(di);
   }
   return configure_end(ctx, what, source_id, had_points, rc);
 }
@@ -327,8 +309,8 @@ static int set_depth_impl(dddmr_rollout_ctx* ctx, const char* what, int32_t sour
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
   int rc = source_refused(ctx, what, depth_mm ? SourceOp::kFeedImage : SourceOp::kFeedFrame, source_id);
   if (rc != DDDMR_OK) return rc;
-  DepthSource* ds = ctx->src[source_id].depth;
-  DepthImage* di = ctx->src[source_id].dimg;
+  DepthSource* ds = ctx->src[source_id].depth.get();
+  DepthImage* di = ctx->src[source_id].dimg.get();
   if (depth_mm && stride_bytes < 2 * (size_t)di->p.width)
     return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: row stride %zu < 2 * width %u", what, stride_bytes, di->p.width);
   if (n_points > ds->max_frame_points)
@@ -351,7 +333,11 @@ static int set_depth_impl(dddmr_rollout_ctx* ctx, const char* what, int32_t sour
   // Nothing leaves: the frame is appended behind the alive ones.  Otherwise the ones that stay are copied to the
   // other buffer (device to device) and the frame is built behind them; the buffers swap on success only.
   const int dst_buf = none_leaves ? ds->cur : ds->cur ^ 1;
+  // From the first copy on, an error exit waits for what is enqueued (the feed's -2 and a refused commit leave the copies
+  // behind).  Disarmed once the source is committed: the feed has waited, and the aggregate's copies are ordered by event.
+  Drain drain{ctx->copy_stream, false};
   if (!none_leaves) {
+    drain.armed = true;
     size_t src_at = 0, dst_at = 0;
     for (const DepthFrame& fr : ds->frames) {        // the caller's stamps need not be monotonic: any frame may be the one to leave
       if (stays(fr.stamp_us, false) && fr.n) {
@@ -373,6 +359,7 @@ static int set_depth_impl(dddmr_rollout_ctx* ctx, const char* what, int32_t sour
   const size_t n_source = kept_points + (new_alive ? n_out : 0);
   uint32_t n_all = 0;
   if ((rc = commit_source(ctx, what, source_id, ds->buf[dst_buf], n_source, &n_all)) != DDDMR_OK) return rc;
+  drain.armed = false;
   // committed (the clearing verdicts' grid is rebuilt by the next call that needs it): the source's frames follow
   if (new_alive) kept.push_back(DepthFrame{n_out, stamp_us});
   ds->frames.swap(kept);
@@ -417,7 +404,7 @@ int dddmr_rollout_get_depth_image_cloud(dddmr_rollout_ctx* ctx, int32_t source_i
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
   if (const int rc = source_refused(ctx, "get_depth_image_cloud", SourceOp::kImageCloudGetter, source_id)) return rc;
-  const DepthImage* di = ctx->src[source_id].dimg;
+  const DepthImage* di = ctx->src[source_id].dimg.get();
   return read_back(ctx, "get_depth_image_cloud", xyz_out, di->cloud[di->cur], di->n_cloud, 3 * sizeof(float), capacity, n_points);
 }
 
@@ -476,17 +463,15 @@ int dddmr_rollout_set_lidar_sweep_source(dddmr_rollout_ctx* ctx, int32_t source_
   if ((rc = source_refused(ctx, what, SourceOp::kConfigureSweep, source_id)) != DDDMR_OK) return rc;
   bool had_points;
   if ((rc = configure_begin(ctx, source_id, &had_points)) != DDDMR_OK) return rc;   // (which turns the features off)
-  auto* sw = new LidarSweep();
+  auto sw = std::make_unique<LidarSweep>();
   sw->p = k;
   sw->max_points = cfg->max_sweep_points;
   if (sweep_alloc(*sw) != 0) {
-    sweep_free(*sw);
-    delete sw;
     rc = fail(ctx, DDDMR_ERR_HIP, "%s: scratch of source %d", what, source_id);
   } else {
-    ctx->src[source_id].sweep = sw;
     ctx->src[source_id].obs = sw->obs[sw->cur];
     ctx->sources.configure(source_id, SourceKind::kSweep);
+    ctx->src[source_id].sweep = std::move(sw);
   }
   return configure_end(ctx, what, source_id, had_points, rc);
 }
@@ -501,7 +486,7 @@ int dddmr_rollout_set_lidar_sweep(dddmr_rollout_ctx* ctx, int32_t source_id, con
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
   int rc = source_refused(ctx, "set_lidar_sweep", SourceOp::kFeedSweep, source_id);
   if (rc != DDDMR_OK) return rc;
-  LidarSweep* sw = ctx->src[source_id].sweep;
+  LidarSweep* sw = ctx->src[source_id].sweep.get();
   if (n_points > sw->max_points) return fail(ctx, DDDMR_ERR_CAPACITY, "set_lidar_sweep: %zu points > max_sweep_points %u", n_points, sw->max_points);
   FeedParams fp;
   set_mounts(fp, T_base_sensor, T_gbl_base);
@@ -518,7 +503,7 @@ int dddmr_rollout_set_lidar_sweep(dddmr_rollout_ctx* ctx, int32_t source_id, con
   sw->cur ^= 1;                                        // committed: the buffers the sweep was built in become the current ones
   sw->n_cloud = n_seg;
   sw->have_sweep = true;
-  if (LidarFeatures* lf = sw->features) {              // the features were built beside the sweep: they are current with it
+  if (LidarFeatures* lf = sw->features.get()) {        // the features were built beside the sweep: they are current with it
     lf->n_seg[sw->cur] = feat_counts.n_seg;
     for (int w = 0; w < 3; ++w) lf->n_feat[sw->cur][w] = feat_counts.n_feat[w];
     lf->have_sweep = true;
@@ -535,7 +520,7 @@ int dddmr_rollout_get_lidar_sweep_cloud(dddmr_rollout_ctx* ctx, int32_t source_i
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
   if (const int rc = source_refused(ctx, "get_lidar_sweep_cloud", SourceOp::kSweepGetter, source_id)) return rc;
-  const LidarSweep* sw = ctx->src[source_id].sweep;
+  const LidarSweep* sw = ctx->src[source_id].sweep.get();
   return read_back(ctx, "get_lidar_sweep_cloud", xyzl_out, sw->cloud[sw->cur], sw->n_cloud, sizeof(float4), capacity, n_points);
 }
 
@@ -546,7 +531,7 @@ int dddmr_rollout_get_lidar_sweep_image(dddmr_rollout_ctx* ctx, int32_t source_i
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
   if (const int rc = source_refused(ctx, "get_lidar_sweep_image", SourceOp::kSweepGetter, source_id)) return rc;
-  const LidarSweep* sw = ctx->src[source_id].sweep;
+  const LidarSweep* sw = ctx->src[source_id].sweep.get();
   const size_t px = (size_t)sw->p.V * sw->p.H;
   if (capacity_pixels < px) return fail(ctx, DDDMR_ERR_CAPACITY, "get_lidar_sweep_image: capacity %zu < %zu pixels", capacity_pixels, px);
   if (!sw->have_sweep) {                               // resetParameters' image: nothing projected yet
@@ -557,10 +542,12 @@ int dddmr_rollout_get_lidar_sweep_image(dddmr_rollout_ctx* ctx, int32_t source_i
     }
     return DDDMR_OK;
   }
+  Drain drain{ctx->copy_stream};                       // an error exit leaves no copy behind that writes the caller's memory
   if (range_out) HIPCHK(ctx, hipMemcpyAsync(range_out, sw->range_img[sw->cur], px * sizeof(float), hipMemcpyDeviceToHost, ctx->copy_stream));
   if (label_out) HIPCHK(ctx, hipMemcpyAsync(label_out, sw->label_img[sw->cur], px * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->copy_stream));
   if (ground_out) HIPCHK(ctx, hipMemcpyAsync(ground_out, sw->ground_img[sw->cur], px, hipMemcpyDeviceToHost, ctx->copy_stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+  drain.armed = false;
   return DDDMR_OK;
 }
 
@@ -581,7 +568,7 @@ int dddmr_rollout_set_lidar_sweep_features(dddmr_rollout_ctx* ctx, int32_t sourc
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
   if (const int rc = source_refused(ctx, what, SourceOp::kSweepGetter, source_id)) return rc;
-  LidarSweep* sw = ctx->src[source_id].sweep;
+  LidarSweep* sw = ctx->src[source_id].sweep.get();
   FeatParams k{};
   if (cfg) {
     k.edge_threshold = (float)cfg->edge_threshold;     // float members (featureAssociation.h:62-63)
@@ -595,28 +582,24 @@ int dddmr_rollout_set_lidar_sweep_features(dddmr_rollout_ctx* ctx, int32_t sourc
   }
   HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
   if (!cfg) {
-    sweep_features_off(*sw);
+    sw->features.reset();
     return DDDMR_OK;
   }
   if (sw->features) {                                  // new parameters: they hold from the next sweep on; what the getters
     sw->features->p = k;                               // return stays the latest accepted sweep's
     return DDDMR_OK;
   }
-  auto* lf = new LidarFeatures();
+  auto lf = std::make_unique<LidarFeatures>();
   lf->p = k;
-  if (features_alloc(*lf) != 0) {
-    features_free(*lf);
-    delete lf;
-    return fail(ctx, DDDMR_ERR_HIP, "%s: scratch of source %d", what, source_id);
-  }
-  sw->features = lf;
+  if (features_alloc(*lf) != 0) return fail(ctx, DDDMR_ERR_HIP, "%s: scratch of source %d", what, source_id);
+  sw->features.reset(lf.release());
   return DDDMR_OK;
 }
 
 static int sweep_features_of(dddmr_rollout_ctx* ctx, int32_t source_id, const char* what, LidarSweep** out) {
   if (const int arc = source_arg(ctx, what, source_id)) return arc;
   if (const int rc = source_refused(ctx, what, SourceOp::kSweepGetter, source_id)) return rc;
-  LidarSweep* sw = ctx->src[source_id].sweep;
+  LidarSweep* sw = ctx->src[source_id].sweep.get();
   if (!sw->features) return fail(ctx, DDDMR_ERR_STATE, "%s: the features of source %d are off", what, source_id);
   *out = sw;
   return DDDMR_OK;
@@ -640,6 +623,7 @@ int dddmr_rollout_get_lidar_sweep_segmented(dddmr_rollout_ctx* ctx, int32_t sour
   std::vector<float4> pt;
   std::vector<uint32_t> cr;
   std::vector<int32_t> ring(2 * V);
+  Drain drain{ctx->copy_stream};                       // declared behind the vectors: an error exit waits before they die
   if (points && count) {
     pt.resize(count);
     cr.resize(count);
@@ -649,6 +633,7 @@ int dddmr_rollout_get_lidar_sweep_segmented(dddmr_rollout_ctx* ctx, int32_t sour
   if (start_ring_index || end_ring_index)
     HIPCHK(ctx, hipMemcpyAsync(ring.data(), lf.ring[b], 2 * V * 4, hipMemcpyDeviceToHost, ctx->copy_stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+  drain.armed = false;
   for (size_t i = 0; i < pt.size(); ++i) {
     if (xyz) { xyz[3 * i] = pt[i].x; xyz[3 * i + 1] = pt[i].y; xyz[3 * i + 2] = pt[i].z; }
     if (range) range[i] = pt[i].w;
@@ -678,9 +663,11 @@ int dddmr_rollout_get_lidar_sweep_features(dddmr_rollout_ctx* ctx, int32_t sourc
   if ((xyzr_out || seg_index_out) && capacity < count)
     return fail(ctx, DDDMR_ERR_CAPACITY, "get_lidar_sweep_features: capacity %zu < %zu", capacity, count);
   *n_points = count;
+  Drain drain{ctx->copy_stream};
   if (count && xyzr_out) HIPCHK(ctx, hipMemcpyAsync(xyzr_out, lf.feat[b] + off, count * sizeof(float4), hipMemcpyDeviceToHost, ctx->copy_stream));
   if (count && seg_index_out) HIPCHK(ctx, hipMemcpyAsync(seg_index_out, lf.feat_idx[b] + off, count * 4, hipMemcpyDeviceToHost, ctx->copy_stream));
   if (count && (xyzr_out || seg_index_out)) HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+  drain.armed = false;
   return DDDMR_OK;
 }
 
@@ -736,13 +723,13 @@ static int depth_frustums(dddmr_rollout_ctx* ctx, const char* what, DcFrustums* 
 
 static int depth_clear_scratch(dddmr_rollout_ctx* ctx, const char* what) {
   if (ctx->dclear) return DDDMR_OK;
-  auto* d = new DepthClear();
-  if (dc_alloc(*d, ctx->cfg.max_points) != 0) {
-    dc_free(*d);
-    delete d;
+  size_t temp_bytes = 0;                               // of the grid builder's scan: rocPRIM asks the device
+  uint32_t* cells = nullptr;
+  auto d = std::make_unique<DepthClear>();
+  if (rocprim::exclusive_scan(nullptr, temp_bytes, cells, cells, 0u, (size_t)kDcCapCells + 1, rocprim::plus<uint32_t>(), nullptr) != hipSuccess ||
+      dc_alloc(*d, ctx->cfg.max_points, temp_bytes) != 0)
     return fail(ctx, DDDMR_ERR_HIP, "%s: scratch allocation failed", what);
-  }
-  ctx->dclear = d;
+  ctx->dclear = std::move(d);
   return DDDMR_OK;
 }
 
@@ -751,6 +738,7 @@ static int depth_clear_scratch(dddmr_rollout_ctx* ctx, const char* what) {
 static int depth_observation_grid(dddmr_rollout_ctx* ctx, DepthClear& d, size_t n_obs, hipStream_t st, uint32_t* ops) {
   if (d.built && d.built_epoch == ctx->sources.depth_epoch) return DDDMR_OK;
   size_t at = 0;
+  Drain drain{st};                                     // an error exit leaves no half-built grid running
   for (int i = 0; i < dddmr_rollout_ctx::kMaxSources; ++i) {
     const SourceRecord& r = ctx->sources.rec[i];
     if (!is_depth(r.kind) || !r.n) continue;
@@ -762,6 +750,7 @@ static int depth_observation_grid(dddmr_rollout_ctx* ctx, DepthClear& d, size_t 
   const int b = dc_build_grid(d, (uint32_t)n_obs, st);
   if (b < 0) return fail(ctx, DDDMR_ERR_HIP, "depth observation grid: build failed");
   *ops += (uint32_t)b;
+  drain.armed = false;                                 // (the caller's one wait follows its own launches)
   d.built = true;
   d.built_epoch = ctx->sources.depth_epoch;
   return DDDMR_OK;
@@ -780,7 +769,8 @@ int dddmr_rollout_depth_frustum_test(dddmr_rollout_ctx* ctx, const float* xyz, s
   if (n == 0) return DDDMR_OK;
   if ((rc = depth_clear_scratch(ctx, "depth_frustum_test")) != DDDMR_OK) return rc;
   DepthClear& d = *ctx->dclear;
-  if (dc_reserve(&d.in_host, &d.in_dev, &d.in_cap, n * 12) != 0 || dc_reserve(&d.out_host, &d.out_dev, &d.out_cap, n) != 0)
+  if (host_mapped_reserve(d.mem.host, &d.in_host, &d.in_dev, &d.in_cap, n * 12) != 0 ||
+      host_mapped_reserve(d.mem.host, &d.out_host, &d.out_dev, &d.out_cap, n) != 0)
     return fail(ctx, DDDMR_ERR_HIP, "depth_frustum_test: staging for %zu points", n);
   float* st = static_cast<float*>(d.in_host);
   if (stride_bytes == 12) {
@@ -795,8 +785,10 @@ int dddmr_rollout_depth_frustum_test(dddmr_rollout_ctx* ctx, const float* xyz, s
   }
   hipLaunchKernelGGL(k_dc_frustum_test, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->copy_stream, S,
                      static_cast<const float*>(d.in_dev), (uint32_t)n, static_cast<uint8_t*>(d.out_dev));
+  Drain drain{ctx->copy_stream};
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+  drain.armed = false;
   const uint8_t* o = static_cast<const uint8_t*>(d.out_host);
   for (size_t i = 0; i < n; ++i) {
     if (in_frustums_out) in_frustums_out[i] = o[i] & 1u;
@@ -832,11 +824,12 @@ int dddmr_rollout_depth_clear_verdicts(dddmr_rollout_ctx* ctx, double xy_resolut
   // aggregatePointCloudFromObservations: the depth sources' alive frames, in source order (lidar sources stay out)
   const size_t n_obs = ctx->sources.depth_points();
   const bool observation_clear = !(n_obs > 5);       // depth_camera_layer.cpp:258-264
+  Drain drain{st};                                   // from the grid's launches on: an error exit below waits for them
   if (!observation_clear && (rc = depth_observation_grid(ctx, d, n_obs, st, &ops)) != DDDMR_OK) return rc;
   const size_t total = offsets[m];
   const size_t vox_bytes = m * 3 * sizeof(int32_t), off_bytes = (m + 1) * sizeof(uint32_t);
-  if (dc_reserve(&d.in_host, &d.in_dev, &d.in_cap, vox_bytes + off_bytes + total * 12) != 0 ||
-      dc_reserve(&d.out_host, &d.out_dev, &d.out_cap, m * sizeof(uint2)) != 0)
+  if (host_mapped_reserve(d.mem.host, &d.in_host, &d.in_dev, &d.in_cap, vox_bytes + off_bytes + total * 12) != 0 ||
+      host_mapped_reserve(d.mem.host, &d.out_host, &d.out_dev, &d.out_cap, m * sizeof(uint2)) != 0)
     return fail(ctx, DDDMR_ERR_HIP, "depth_clear_verdicts: staging for %zu markings, %zu cluster points", m, total);
   char* in = static_cast<char*>(d.in_host);
   std::memcpy(in, voxel_xyz, vox_bytes);
@@ -854,6 +847,7 @@ int dddmr_rollout_depth_clear_verdicts(dddmr_rollout_ctx* ctx, double xy_resolut
   ++ops;
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(st));           // the call's one host wait
+  drain.armed = false;
   d.launches_last = ops;
   const uint2* o = static_cast<const uint2*>(d.out_host);
   for (size_t i = 0; i < m; ++i)
