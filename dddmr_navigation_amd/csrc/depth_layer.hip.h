@@ -181,34 +181,26 @@ namespace {
 struct DepthLayerState {
   dddmr_depth_layer_config cfg{};
   uint32_t max_obs = 0;
-  DepthMarkState* dm = nullptr;            // the cluster pipeline's scratch (rocPRIM storage included) and the ground / map grids
+  std::unique_ptr<DepthMarkState> dm;      // the cluster pipeline's scratch (rocPRIM storage included) and the ground / map grids
   StoreBuf store;                          // with heads; its pool_used persists on the device between updates
   // scratch of one update beside dm's (sized for max_obs)
   float4 *proj = nullptr, *gen = nullptr;
   uint32_t *gen_first = nullptr, *gen_count = nullptr, *slot = nullptr, *pc_dst = nullptr, *gen_dst = nullptr;
   uint32_t* n_gen = nullptr;
   DlCounters* extra = nullptr;
-  DevAllocs mem;                           // (of the above)
-  HostAllocs host;                         // (of out_host)
+  Owned mem;                               // (of the above and out_host)
   void* out_host = nullptr;                // DlOut, tie arrays [3 * max_obs], fix list [max_obs / 2] uint2
   void* out_dev = nullptr;
   uint32_t seq = 0;
 };
 
-void depth_layer_free(DepthLayerState* s) {
-  if (!s) return;
-  dev_free(s->mem);
-  store_free(s->store);
-  host_free(s->host);
-  depth_mark_free(s->dm);
-  delete s;
-}
+static_assert(!std::is_copy_constructible_v<DepthLayerState>);
 
 int depth_layer_init(dddmr_rollout_ctx* ctx, DepthLayerState* s, const float* ground_xyz, size_t n_ground, size_t ground_stride_bytes,
                      const float* map_xyz, size_t n_map, size_t map_stride_bytes) {
-  int rc = store_alloc(ctx, s->store, 8, s->cfg.max_markings, s->cfg.max_cluster_points, (uint32_t)n_ground, false, true);
-  if (rc != DDDMR_OK) return rc;
-  s->dm = new DepthMarkState();
+  if (store_alloc(s->store, 8, s->cfg.max_markings, s->cfg.max_cluster_points, (uint32_t)n_ground, false, true) != 0)
+    return fail(ctx, DDDMR_ERR_HIP, "depth_layer_create: the marking store's allocation failed");
+  s->dm = std::make_unique<DepthMarkState>();
   s->dm->cfg.xy_resolution = s->cfg.xy_resolution;
   s->dm->cfg.height_resolution = s->cfg.height_resolution;
   s->dm->cfg.euclidean_cluster_extraction_tolerance = s->cfg.euclidean_cluster_extraction_tolerance;
@@ -216,20 +208,20 @@ int depth_layer_init(dddmr_rollout_ctx* ctx, DepthLayerState* s, const float* gr
   s->dm->cfg.segmentation_ignore_ratio = s->cfg.segmentation_ignore_ratio;
   s->dm->cfg.max_observation_points = s->cfg.max_observation_points;
   s->dm->max_obs = s->max_obs;
-  rc = depth_mark_init(ctx, s->dm, s->store.table, ground_xyz, n_ground, ground_stride_bytes, map_xyz, n_map, map_stride_bytes);
+  const int rc = depth_mark_init(ctx, s->dm.get(), s->store.table, ground_xyz, n_ground, ground_stride_bytes, map_xyz, n_map, map_stride_bytes);
   if (rc != DDDMR_OK) return rc;
   const size_t N = s->max_obs;
-  HIPCHK(ctx, dev_alloc(s->mem, &s->proj, N));
-  HIPCHK(ctx, dev_alloc(s->mem, &s->gen, N));
-  HIPCHK(ctx, dev_alloc(s->mem, &s->gen_first, N));
-  HIPCHK(ctx, dev_alloc(s->mem, &s->gen_count, N));
-  HIPCHK(ctx, dev_alloc(s->mem, &s->slot, N));
-  HIPCHK(ctx, dev_alloc(s->mem, &s->pc_dst, N));
-  HIPCHK(ctx, dev_alloc(s->mem, &s->gen_dst, N));
-  HIPCHK(ctx, dev_alloc(s->mem, &s->n_gen, 1));
-  HIPCHK(ctx, dev_alloc(s->mem, &s->extra, 1));
+  HIPCHK(ctx, dev_alloc(s->mem.dev, &s->proj, N));
+  HIPCHK(ctx, dev_alloc(s->mem.dev, &s->gen, N));
+  HIPCHK(ctx, dev_alloc(s->mem.dev, &s->gen_first, N));
+  HIPCHK(ctx, dev_alloc(s->mem.dev, &s->gen_count, N));
+  HIPCHK(ctx, dev_alloc(s->mem.dev, &s->slot, N));
+  HIPCHK(ctx, dev_alloc(s->mem.dev, &s->pc_dst, N));
+  HIPCHK(ctx, dev_alloc(s->mem.dev, &s->gen_dst, N));
+  HIPCHK(ctx, dev_alloc(s->mem.dev, &s->n_gen, 1));
+  HIPCHK(ctx, dev_alloc(s->mem.dev, &s->extra, 1));
   const size_t bytes = sizeof(DlOut) + 3 * N * sizeof(uint32_t) + (N / 2 + 1) * sizeof(uint2);
-  if (host_mapped_alloc(s->host, &s->out_host, &s->out_dev, bytes) != 0) return fail(ctx, DDDMR_ERR_HIP, "depth_layer_create: staging of %zu bytes", bytes);
+  if (host_mapped_alloc(s->mem.host, &s->out_host, &s->out_dev, bytes) != 0) return fail(ctx, DDDMR_ERR_HIP, "depth_layer_create: staging of %zu bytes", bytes);
   return store_reset(ctx, s->store, ctx->copy_stream, s->cfg.max_obstacle_distance);      // resetdGraph.  producer_mu held.
 }
 
@@ -237,7 +229,7 @@ int depth_layer_init(dddmr_rollout_ctx* ctx, DepthLayerState* s, const float* gr
 
 DepthLayerState* depth_layer_of(dddmr_rollout_ctx* ctx, const char* what) {
   if (!ctx->dlayer) (void)fail(ctx, DDDMR_ERR_STATE, "%s before depth_layer_create", what);
-  return ctx->dlayer;
+  return ctx->dlayer.get();
 }
 
 int depth_layer_update_locked(dddmr_rollout_ctx* ctx, const double T_gbl_base[7], dddmr_depth_layer_stats* stats);
@@ -250,8 +242,7 @@ int dddmr_rollout_depth_layer_create(dddmr_rollout_ctx* ctx, const dddmr_depth_l
                                      size_t n_ground, size_t ground_stride_bytes, const float* map_xyz, size_t n_map,
                                      size_t map_stride_bytes) {
   if (!ctx || !cfg) return DDDMR_ERR_BAD_ARG;
-  if ((n_ground && (!ground_xyz || ground_stride_bytes < 12 || ground_stride_bytes % 4)) ||
-      (n_map && (!map_xyz || map_stride_bytes < 12 || map_stride_bytes % 4)))
+  if (!cloud_arg_ok(ground_xyz, n_ground, ground_stride_bytes) || !cloud_arg_ok(map_xyz, n_map, map_stride_bytes))
     return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_layer_create: bad cloud pointer / stride");
   const double positive[] = {cfg->xy_resolution, cfg->height_resolution, cfg->euclidean_cluster_extraction_tolerance,
                              cfg->inflation_radius, cfg->perception_window_size, cfg->marking_height};
@@ -271,14 +262,13 @@ int dddmr_rollout_depth_layer_create(dddmr_rollout_ctx* ctx, const dddmr_depth_l
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-  auto* s = new DepthLayerState();
+  auto s = std::make_unique<DepthLayerState>();
   s->cfg = *cfg;
   s->max_obs = cfg->max_observation_points;
-  const int rc = depth_layer_init(ctx, s, ground_xyz, n_ground, ground_stride_bytes, map_xyz, n_map, map_stride_bytes);
-  if (rc != DDDMR_OK) { depth_layer_free(s); return rc; }
-  if (ctx->stack) { stack_free(ctx->stack); ctx->stack = nullptr; }      // (a stack holds the layer it was created over)
-  if (ctx->dlayer) depth_layer_free(ctx->dlayer);
-  ctx->dlayer = s;                                       // only a complete state is ever visible
+  const int rc = depth_layer_init(ctx, s.get(), ground_xyz, n_ground, ground_stride_bytes, map_xyz, n_map, map_stride_bytes);
+  if (rc != DDDMR_OK) return rc;                         // (the old layer and its stack survive a failed create)
+  ctx->stack.reset();                                    // (a stack holds the layer it was created over)
+  ctx->dlayer.reset(s.release());                        // only a complete state is ever visible
   return DDDMR_OK;
 }
 
@@ -319,10 +309,11 @@ int depth_layer_update_locked(dddmr_rollout_ctx* ctx, const double T_gbl_base[7]
   hipStream_t st = ctx->copy_stream;      // the stream the depth feeds ran on: their frames are complete before this work
   uint32_t ops = 0;
   const bool observation_clear = !(n_obs > 5);           // :258-264, :491-492
+  Drain drain{st};                        // from the first enqueue to either wait: an error exit in between waits for the stream
   if (!observation_clear && (rc = depth_observation_grid(ctx, d, n_obs, st, &ops)) != DDDMR_OK) return rc;
   const uint32_t n = (uint32_t)n_obs;
   const dddmr_depth_layer_config& c = s->cfg;
-  DepthMarkState* dm = s->dm;
+  DepthMarkState* dm = s->dm.get();
   StoreBuf& sb = s->store;
   MarkStore& m = sb.s;
 
@@ -335,8 +326,7 @@ int depth_layer_update_locked(dddmr_rollout_ctx* ctx, const double T_gbl_base[7]
   k.table_mask = sb.table - 1;
   k.pool_cap = sb.pool_cap;
   k.n_ground = sb.n_ground;
-  k.seq = ++s->seq;
-  if (k.seq == 0) k.seq = s->seq = 1;
+  k.seq = next_seq(s->seq);
 
   dddmr_depth_layer_stats out{};
   out.n_observation = n;
@@ -389,6 +379,7 @@ int depth_layer_update_locked(dddmr_rollout_ctx* ctx, const double T_gbl_base[7]
             s->extra, dm->counters, cl, reinterpret_cast<DlOut*>(dev), reinterpret_cast<uint32_t*>(dev + tie_at));
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(st));                 // the update's one host wait
+  drain.armed = false;
   out.host_waits = 1;
   DlOut o = *reinterpret_cast<const DlOut*>(host);
   if (o.c.n_dup > 0 && !o.c.overflow && !o.mark_overflow) {
@@ -400,12 +391,14 @@ int depth_layer_update_locked(dddmr_rollout_ctx* ctx, const double T_gbl_base[7]
     if (!fix.empty()) {
       const uint32_t n_fix = (uint32_t)fix.size();
       std::memcpy(host + fix_at, fix.data(), fix.size() * sizeof(uint2));
+      drain.armed = true;
       DL_LAUNCH(k_mk_fix_owner, dim3((n_fix + 3) / 4), dim3(256), 0, st, k, n_fix, reinterpret_cast<const uint2*>(dev + fix_at), dm->sc.ds,
                 dm->sc.ds_first, s->gen, cl, m, sb.head, sb.counters);
       DL_LAUNCH(k_dl_out, dim3(1), dim3(256), 0, st, 0u, s->max_obs, sb.counters, s->extra, dm->counters, cl, reinterpret_cast<DlOut*>(dev),
                 reinterpret_cast<uint32_t*>(dev + tie_at));
       HIPCHK(ctx, hipGetLastError());
       HIPCHK(ctx, hipStreamSynchronize(st));             // the second wait of an update with a contested voxel
+      drain.armed = false;
       out.host_waits = 2;
       const DlOut o2 = *reinterpret_cast<const DlOut*>(host);
       o.c.pool_used = o2.c.pool_used;

@@ -176,32 +176,26 @@ struct DepthMarkState {
   ClusterScratch sc;                       // scratch of one call (sized for max_obs), with fate and the counters below
   uint32_t* fate = nullptr;
   MarkCounters* counters = nullptr;
-  DevAllocs mem;                           // (of the two above)
-  HostAllocs host;                         // (of the staging below)
+  Owned mem;                               // (of the two above and the staging below)
   // pinned + mapped results, grown on demand
   void* out_host = nullptr;
   void* out_dev = nullptr;
   size_t out_cap = 0;
 };
 
-void depth_mark_free(DepthMarkState* s) {
-  if (!s) return;
-  dev_free(s->mem);
-  dev_free(s->sc.mem);
-  dev_free(s->grids.mem);
-  host_free(s->host);
-  delete s;
-}
+static_assert(!std::is_copy_constructible_v<DepthMarkState>);
 
 // `table`: slots of the marking store that does its housekeeping with this state's rocPRIM storage (depth_layer.hip.h), 0: none
 int depth_mark_init(dddmr_rollout_ctx* ctx, DepthMarkState* s, size_t table, const float* ground_xyz, size_t n_ground, size_t ground_stride_bytes,
                     const float* map_xyz, size_t n_map, size_t map_stride_bytes) {
-  int rc = cluster_scratch_alloc(ctx, s->sc, s->max_obs, table);
+  size_t temp_bytes = 0;
+  int rc = cluster_temp_bytes(ctx, s->max_obs, table, &temp_bytes);
   if (rc != DDDMR_OK) return rc;
+  if (cluster_scratch_alloc(s->sc, s->max_obs, temp_bytes) != 0) return fail(ctx, DDDMR_ERR_HIP, "depth mark: the cluster scratch's allocation failed");
   rc = static_grids_upload(ctx, s->grids, s->sc.temp, s->sc.temp_bytes, ground_xyz, n_ground, ground_stride_bytes, map_xyz, n_map, map_stride_bytes);
   if (rc != DDDMR_OK) return rc;
-  HIPCHK(ctx, dev_alloc(s->mem, &s->fate, s->max_obs));
-  HIPCHK(ctx, dev_alloc(s->mem, &s->counters, 1));
+  HIPCHK(ctx, dev_alloc(s->mem.dev, &s->fate, s->max_obs));
+  HIPCHK(ctx, dev_alloc(s->mem.dev, &s->counters, 1));
   return DDDMR_OK;
 }
 
@@ -263,8 +257,7 @@ int dddmr_rollout_depth_mark_create(dddmr_rollout_ctx* ctx, const dddmr_depth_ma
                                     size_t n_ground, size_t ground_stride_bytes, const float* map_xyz, size_t n_map,
                                     size_t map_stride_bytes) {
   if (!ctx || !cfg) return DDDMR_ERR_BAD_ARG;
-  if ((n_ground && (!ground_xyz || ground_stride_bytes < 12 || ground_stride_bytes % 4)) ||
-      (n_map && (!map_xyz || map_stride_bytes < 12 || map_stride_bytes % 4)))
+  if (!cloud_arg_ok(ground_xyz, n_ground, ground_stride_bytes) || !cloud_arg_ok(map_xyz, n_map, map_stride_bytes))
     return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_mark_create: bad cloud pointer / stride");
   if (!(cfg->xy_resolution > 0) || !(cfg->height_resolution > 0) || !(cfg->euclidean_cluster_extraction_tolerance > 0) ||
       !std::isfinite(cfg->xy_resolution) || !std::isfinite(cfg->height_resolution) ||
@@ -279,14 +272,13 @@ int dddmr_rollout_depth_mark_create(dddmr_rollout_ctx* ctx, const dddmr_depth_ma
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-  if (ctx->dmark) { depth_mark_free(ctx->dmark); ctx->dmark = nullptr; }
-  auto* s = new DepthMarkState();
+  ctx->dmark.reset();                                    // (the old state goes first: after a failed create there is none)
+  auto s = std::make_unique<DepthMarkState>();
   s->cfg = *cfg;
   s->max_obs = cfg->max_observation_points;
-  const int rc = depth_mark_init(ctx, s, 0, ground_xyz, n_ground, ground_stride_bytes, map_xyz, n_map, map_stride_bytes);
-  if (rc != DDDMR_OK) { depth_mark_free(s); return rc; }
-  ctx->dmark = s;                                        // only a complete state is ever visible
-  return DDDMR_OK;
+  const int rc = depth_mark_init(ctx, s.get(), 0, ground_xyz, n_ground, ground_stride_bytes, map_xyz, n_map, map_stride_bytes);
+  if (rc == DDDMR_OK) ctx->dmark.reset(s.release());     // only a complete state is ever visible
+  return rc;
 }
 
 int dddmr_rollout_depth_mark_clusters(dddmr_rollout_ctx* ctx, const double T_gbl_base[7], size_t capacity_clusters,
@@ -304,7 +296,7 @@ int dddmr_rollout_depth_mark_clusters(dddmr_rollout_ctx* ctx, const double T_gbl
   const bool count_only = n_out == 0;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
-  DepthMarkState* s = ctx->dmark;
+  DepthMarkState* s = ctx->dmark.get();
   if (!s) return fail(ctx, DDDMR_ERR_STATE, "depth_mark_clusters before depth_mark_create");
   DcFrustums S;
   int rc = depth_frustums(ctx, "depth_mark_clusters", &S);
@@ -329,10 +321,11 @@ int dddmr_rollout_depth_mark_clusters(dddmr_rollout_ctx* ctx, const double T_gbl
   DepthClear& d = *ctx->dclear;
   hipStream_t st = ctx->copy_stream;      // the stream the depth feeds ran on: their frames are complete before this work
   uint32_t ops = 0;
+  Drain drain{st};                        // from the grid's launches on: an error exit below waits for them
   if ((rc = depth_observation_grid(ctx, d, n_obs, st, &ops)) != DDDMR_OK) return rc;
   const uint32_t n = (uint32_t)n_obs;
   const size_t rec_at = sizeof(DmHeader), pts_at = rec_at + (size_t)n * sizeof(DmRecord);
-  if (host_mapped_reserve(s->host, &s->out_host, &s->out_dev, &s->out_cap, pts_at + (size_t)n * 12) != 0)
+  if (host_mapped_reserve(s->mem.host, &s->out_host, &s->out_dev, &s->out_cap, pts_at + (size_t)n * 12) != 0)
     return fail(ctx, DDDMR_ERR_HIP, "depth_mark_clusters: staging for %u observation points", n);
 
   if ((rc = depth_mark_enqueue(ctx, s, T_gbl_base, d, n, S, st, &ops)) != DDDMR_OK) return rc;
@@ -345,6 +338,7 @@ int dddmr_rollout_depth_mark_clusters(dddmr_rollout_ctx* ctx, const double T_gbl
   ops += 2 * 10 + 2 * 3 + 2;              // rocPRIM: two sorts (block sort + ~8 merge passes + id wrapper), two scans; two memsets
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(st));                 // the call's one host wait
+  drain.armed = false;
   out.launches = ops;
 
   const char* host = static_cast<const char*>(s->out_host);

@@ -76,7 +76,6 @@ struct LidarFeatures {
   FeatResult* res_dev = nullptr;
   Owned mem;
 };
-inline void FeaturesDelete::operator()(LidarFeatures* f) const { delete f; }
 
 __host__ __device__ __forceinline__ uint32_t feat_offset(uint32_t V, int which) {
   return which == 0 ? 0u : which == 1 ? kFeatSharp * V : (kFeatSharp + kFeatLess) * V;

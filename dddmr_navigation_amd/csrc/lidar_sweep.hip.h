@@ -77,13 +77,10 @@ struct SweepResult {           // host-mapped, written by the last k_sweep_outpu
 struct LidarFeatures;           // lidar_features.hip.h
 inline void features_launch(LidarFeatures& f, int b, const int32_t* label_img, const uint8_t* ground_img, const float* range_img,
                             const float4* pts, hipStream_t stream);
-struct FeaturesDelete {         // (the type is complete only there)
-  void operator()(LidarFeatures* f) const;
-};
 
 struct LidarSweep {
   SweepParams p;
-  std::unique_ptr<LidarFeatures, FeaturesDelete> features;   // not null: the source's features are on
+  std::unique_ptr<LidarFeatures, LateDelete<LidarFeatures>> features;   // not null: the source's features are on
   uint32_t max_points = 0;             // raw points per sweep
   PerceptionScratch feed;              // stage two's table; its pinned staging holds the raw sweep
   float4* moved = nullptr;             // [max_points] pitch-removed point, range in w

@@ -14,68 +14,18 @@ using namespace dddmr;
 
 constexpr uint32_t kMarkMaxObs = 1u << 20;   // points of one observation (20-bit point index inside the sort keys)
 
-struct GridBuf {              // a PointGrid with its storage
-  PointGrid g;
-  uint32_t cap_cells = 0, cap_points = 0;
-  uint32_t max_row = 0;       // static grids: points of the fullest (y, z) row of cells
-};
-
-// The ground and the static map: the points and a grid over each, uploaded once (static_grids_upload).
-struct StaticGrids {
-  uint32_t n_ground = 0, n_map = 0;
-  float4 *ground_pts = nullptr, *map_pts = nullptr;
-  GridBuf ground, map;
-  DevAllocs mem;
-};
-
-// Scratch of the cluster pipeline for one observation of up to N points (the general route's kernels of marking.hip.h,
-// the depth camera's selfMark of depth_mark.hip.h).
-struct ClusterScratch {
-  uint32_t* parent = nullptr;
-  unsigned long long *keys_a = nullptr, *keys_b = nullptr, *keys1 = nullptr;
-  uint32_t *vals_a = nullptr, *vals_b = nullptr, *flags = nullptr, *incl = nullptr, *cid_incl = nullptr;
-  float4* ds = nullptr;
-  uint32_t* ds_first = nullptr;
-  ClusterArrays cl{};                      // start, size, centroid, state, ds_count, vkey (the rest is the marking layers' own)
-  uint32_t* n_groups = nullptr;            // [2]: groups of the 0.2 m and of the 0.1 m VoxelGrid
-  char* temp = nullptr;                    // rocPRIM temporary storage
-  size_t temp_bytes = 0;
-  DevAllocs mem;
-};
-
-// `table`: slots of the marking store whose housekeeping scans with this scratch's rocPRIM storage (0: none)
-int cluster_scratch_alloc(dddmr_rollout_ctx* ctx, ClusterScratch& c, size_t N, size_t table) {
-  // rocPRIM temporary storage: the largest request among the sorts and scans of the cluster pipeline, the static grids'
-  // builder (up to 2^22 cells) and the store's housekeeping
-  {
-    size_t a = 0, b = 0, e = 0, d = 0;
-    unsigned long long* k = nullptr;
-    uint32_t* v = nullptr;
-    HIPCHK(ctx, rocprim::radix_sort_keys(nullptr, a, k, k, N, 0, 40, ctx->stream));
-    HIPCHK(ctx, rocprim::radix_sort_pairs(nullptr, b, k, k, v, v, N, 0, 62, ctx->stream));
-    HIPCHK(ctx, rocprim::exclusive_scan(nullptr, e, v, v, 0u, std::max((size_t)(1u << 22) + 1, table), rocprim::plus<uint32_t>(), ctx->stream));
-    HIPCHK(ctx, rocprim::inclusive_scan(nullptr, d, v, v, std::max(N, table), rocprim::plus<uint32_t>(), ctx->stream));
-    c.temp_bytes = std::max({a, b, e, d, (size_t)4096}) + 256;
-    HIPCHK(ctx, dev_alloc(c.mem, &c.temp, c.temp_bytes));
-  }
-  HIPCHK(ctx, dev_alloc(c.mem, &c.parent, N));
-  HIPCHK(ctx, dev_alloc(c.mem, &c.keys_a, N));
-  HIPCHK(ctx, dev_alloc(c.mem, &c.keys_b, N));
-  HIPCHK(ctx, dev_alloc(c.mem, &c.keys1, N));
-  HIPCHK(ctx, dev_alloc(c.mem, &c.vals_a, N));
-  HIPCHK(ctx, dev_alloc(c.mem, &c.vals_b, N));
-  HIPCHK(ctx, dev_alloc(c.mem, &c.flags, N));
-  HIPCHK(ctx, dev_alloc(c.mem, &c.incl, N));
-  HIPCHK(ctx, dev_alloc(c.mem, &c.cid_incl, N));
-  HIPCHK(ctx, dev_alloc(c.mem, &c.ds, N));
-  HIPCHK(ctx, dev_alloc(c.mem, &c.ds_first, N));
-  HIPCHK(ctx, dev_alloc(c.mem, &c.cl.start, N + 1));
-  HIPCHK(ctx, dev_alloc(c.mem, &c.cl.size, N));
-  HIPCHK(ctx, dev_alloc(c.mem, &c.cl.centroid, N));
-  HIPCHK(ctx, dev_alloc(c.mem, &c.cl.state, N));
-  HIPCHK(ctx, dev_alloc(c.mem, &c.cl.ds_count, N));
-  HIPCHK(ctx, dev_alloc(c.mem, &c.cl.vkey, 3 * N));
-  HIPCHK(ctx, dev_alloc(c.mem, &c.n_groups, 2));
+// The rocPRIM temporary storage a ClusterScratch for observations of up to N points needs: the largest request among the
+// sorts and scans of the cluster pipeline, the static grids' builder (up to 2^22 cells) and the housekeeping of a marking
+// store of `table` slots that scans with it (0: none).  rocPRIM asks the device, hence the stream.
+int cluster_temp_bytes(dddmr_rollout_ctx* ctx, size_t N, size_t table, size_t* bytes) {
+  size_t a = 0, b = 0, e = 0, d = 0;
+  unsigned long long* k = nullptr;
+  uint32_t* v = nullptr;
+  HIPCHK(ctx, rocprim::radix_sort_keys(nullptr, a, k, k, N, 0, 40, ctx->stream));
+  HIPCHK(ctx, rocprim::radix_sort_pairs(nullptr, b, k, k, v, v, N, 0, 62, ctx->stream));
+  HIPCHK(ctx, rocprim::exclusive_scan(nullptr, e, v, v, 0u, std::max((size_t)(1u << 22) + 1, table), rocprim::plus<uint32_t>(), ctx->stream));
+  HIPCHK(ctx, rocprim::inclusive_scan(nullptr, d, v, v, std::max(N, table), rocprim::plus<uint32_t>(), ctx->stream));
+  *bytes = std::max({a, b, e, d, (size_t)4096}) + 256;
   return DDDMR_OK;
 }
 
@@ -91,8 +41,7 @@ struct MarkingState {
   uint2* gslot = nullptr;
   float4 *proj = nullptr, *gen = nullptr;
   uint32_t* pool_ofs = nullptr;
-  DevAllocs mem;              // the device allocations of this struct itself
-  HostAllocs host;            // ... and host_out
+  Owned mem;                  // the device allocations of this struct itself, and host_out
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
   uint32_t seq = 0;
   // fused route (marking_fused.hip.h)
@@ -113,29 +62,13 @@ struct MarkingState {
   hipStream_t cur = nullptr;               // stream of the update in progress
   uint32_t updates_overlapped = 0;
   MarkKnobs knobs;                         // the DDDMR_MKF_* variables (marking_plan.hip.h)
+  ~MarkingState() {
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+    for (hipEvent_t e : {e0, e1, e2})
+      if (e) (void)hipEventDestroy(e);
+  }
 };
-
-void marking_free(MarkingState* m) {
-  if (!m) return;
-  dev_free(m->mem);
-  dev_free(m->sc.mem);
-  dev_free(m->grids.mem);
-  store_free(m->store);
-  host_free(m->host);
-  if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
-  if (m->e0) (void)hipEventDestroy(m->e0);
-  if (m->e1) (void)hipEventDestroy(m->e1);
-  if (m->e2) (void)hipEventDestroy(m->e2);
-  delete m;
-}
-
-int grid_alloc(dddmr_rollout_ctx* ctx, DevAllocs& mem, GridBuf& b, uint32_t cap_cells, uint32_t cap_points) {
-  b.cap_cells = cap_cells;
-  b.cap_points = cap_points;
-  HIPCHK(ctx, dev_alloc(mem, &b.g.cell_start, (size_t)cap_cells + 1));
-  HIPCHK(ctx, dev_alloc(mem, &b.g.sorted, std::max<uint32_t>(cap_points, 1)));
-  return DDDMR_OK;
-}
+static_assert(!std::is_copy_constructible_v<MarkingState>);
 
 // count -> exclusive scan (rocPRIM storage `temp`) -> scatter on `stream`; `counts` doubles as cell_start
 int grid_build(dddmr_rollout_ctx* ctx, void* temp, size_t temp_bytes, GridBuf& b, const float4* pts, uint32_t n, uint2* slot,
@@ -153,33 +86,25 @@ int grid_build(dddmr_rollout_ctx* ctx, void* temp, size_t temp_bytes, GridBuf& b
 
 int upload_static(dddmr_rollout_ctx* ctx, DevAllocs& mem, void* temp, size_t temp_bytes, GridBuf& b, float4** dev, const float* xyz, size_t n,
                   size_t stride_bytes, float cell_xy, float cell_z) {
-  std::vector<float4> h(std::max<size_t>(n, 1));
-  float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-  const size_t sf = stride_bytes / sizeof(float);
-  for (size_t i = 0; i < n; ++i) {
-    const float* p = xyz + i * sf;
-    h[i] = make_float4(p[0], p[1], p[2], 0.f);
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = i ? std::min(lo[a], p[a]) : p[a];
-      hi[a] = i ? std::max(hi[a], p[a]) : p[a];
-    }
-  }
-  HIPCHK(ctx, dev_alloc(mem, dev, h.size()));
-  HIPCHK(ctx, hipMemcpy(*dev, h.data(), h.size() * sizeof(float4), hipMemcpyHostToDevice));
-  grid_shape(b.g, lo, hi, cell_xy, cell_z, 1u << 22);
-  const int rc = grid_alloc(ctx, mem, b, (uint32_t)((size_t)b.g.nx * b.g.ny * b.g.nz), (uint32_t)n);
-  if (rc != DDDMR_OK) return rc;
+  const HostCloud h(xyz, n, stride_bytes);
+  HIPCHK(ctx, dev_alloc(mem, dev, h.pts.size()));
+  HIPCHK(ctx, hipMemcpy(*dev, h.pts.data(), h.pts.size() * sizeof(float4), hipMemcpyHostToDevice));
+  grid_shape(b.g, h.lo, h.hi, cell_xy, cell_z, 1u << 22);
+  if (grid_alloc(mem, b, (uint32_t)((size_t)b.g.nx * b.g.ny * b.g.nz), (uint32_t)n) != 0)
+    return fail(ctx, DDDMR_ERR_HIP, "static grid of %zu points: allocation failed", n);
   {
     std::vector<uint32_t> rows((size_t)b.g.ny * b.g.nz, 0u);
-    for (size_t i = 0; i < n; ++i) ++rows[(size_t)host_cz(b.g, h[i].z) * b.g.ny + host_cy(b.g, h[i].y)];
+    for (size_t i = 0; i < n; ++i) ++rows[(size_t)host_cz(b.g, h.pts[i].z) * b.g.ny + host_cy(b.g, h.pts[i].y)];
     b.max_row = 0;
     for (uint32_t r : rows) b.max_row = std::max(b.max_row, r);
   }
   DevScope scope;
   uint2* slot = nullptr;
   HIPCHK(ctx, dev_alloc(scope.mem, &slot, std::max<size_t>(n, 1)));
+  Drain drain{ctx->stream};                  // behind `scope`: an error exit waits before the builder's scratch is freed
   const int rb = grid_build(ctx, temp, temp_bytes, b, *dev, (uint32_t)n, slot, ctx->stream);
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  drain.armed = false;
   return rb;
 }
 
@@ -188,9 +113,9 @@ int static_grids_upload(dddmr_rollout_ctx* ctx, StaticGrids& g, void* temp, size
                         size_t ground_stride_bytes, const float* map_xyz, size_t n_map, size_t map_stride_bytes) {
   g.n_ground = (uint32_t)n_ground;
   g.n_map = (uint32_t)n_map;
-  const int rc = upload_static(ctx, g.mem, temp, temp_bytes, g.ground, &g.ground_pts, ground_xyz, n_ground, ground_stride_bytes, 0.5f, 1e6f);
+  const int rc = upload_static(ctx, g.mem.dev, temp, temp_bytes, g.ground, &g.ground_pts, ground_xyz, n_ground, ground_stride_bytes, 0.5f, 1e6f);
   if (rc != DDDMR_OK) return rc;
-  return upload_static(ctx, g.mem, temp, temp_bytes, g.map, &g.map_pts, map_xyz, n_map, map_stride_bytes, 0.25f, 0.25f);
+  return upload_static(ctx, g.mem.dev, temp, temp_bytes, g.map, &g.map_pts, map_xyz, n_map, map_stride_bytes, 0.25f, 0.25f);
 }
 
 // Contested voxels (store_tie_fixes): the clusters' sizes, states and slots come to the host with three copies, and the
@@ -200,22 +125,26 @@ int marking_fix_ties(dddmr_rollout_ctx* ctx, MarkingState* m, const MarkParams& 
   if (nc == 0) return DDDMR_OK;
   hipStream_t st = m->cur;
   std::vector<uint32_t> size(nc), state(nc), slot(nc);
+  std::vector<uint2> fix;
+  MarkCounters after{};                                // (on the fused route the device copy holds only what k_mk_fix_owner touches)
+  Drain drain{st};                                     // behind what the copies read and write: an error exit waits before they die
   HIPCHK(ctx, hipMemcpyAsync(size.data(), m->sc.cl.size, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipMemcpyAsync(state.data(), m->sc.cl.state, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipMemcpyAsync(slot.data(), m->sc.cl.slot, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  std::vector<uint2> fix;
+  drain.armed = false;
   const int rc = store_tie_fixes(ctx, "marking_update", m->max_obs, m->cfg.euclidean_cluster_extraction_min_cluster_size, nc, size.data(),
                                  state.data(), slot.data(), fix);
   if (rc != DDDMR_OK || fix.empty()) return rc;
   // (vals_b is scratch of the update that just finished: >= max_obs words)
   uint2* fix_dev = reinterpret_cast<uint2*>(m->sc.vals_b);
+  drain.armed = true;
   HIPCHK(ctx, hipMemcpyAsync(fix_dev, fix.data(), fix.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_mk_fix_owner, dim3((unsigned)((fix.size() + 3) / 4)), dim3(256), 0, st, k, (uint32_t)fix.size(), fix_dev,
                      (const float4*)nullptr, (const uint32_t*)nullptr, m->gen, m->sc.cl, m->store.s, m->store.head, m->store.counters);
-  MarkCounters after{};                                // (on the fused route the device copy holds only what k_mk_fix_owner touches)
   HIPCHK(ctx, hipMemcpyAsync(&after, m->store.counters, sizeof(after), hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));               // (also keeps `fix` alive until the copy has run)
+  drain.armed = false;
   HIPCHK(ctx, hipGetLastError());
   out.pool_used = after.pool_used;
   out.overflow |= after.overflow;
@@ -224,7 +153,7 @@ int marking_fix_ties(dddmr_rollout_ctx* ctx, MarkingState* m, const MarkParams& 
   return DDDMR_OK;
 }
 
-int marking_reset_locked(dddmr_rollout_ctx* ctx);
+int marking_reset_locked(dddmr_rollout_ctx* ctx, struct MarkingState* m);
 int marking_update_on(dddmr_rollout_ctx* ctx, struct MarkingState* m, const float4* obs, uint32_t n_obs, const double T_base_sensor[7],
                       const double T_gbl_base[7], dddmr_marking_stats* stats);
 
@@ -236,8 +165,7 @@ int dddmr_rollout_marking_create(dddmr_rollout_ctx* ctx, const dddmr_marking_con
                                  size_t n_ground, size_t ground_stride_bytes, const float* map_xyz, size_t n_map,
                                  size_t map_stride_bytes) {
   if (!ctx || !cfg) return DDDMR_ERR_BAD_ARG;
-  if ((n_ground && (!ground_xyz || ground_stride_bytes < 12 || ground_stride_bytes % 4)) ||
-      (n_map && (!map_xyz || map_stride_bytes < 12 || map_stride_bytes % 4)))
+  if (!cloud_arg_ok(ground_xyz, n_ground, ground_stride_bytes) || !cloud_arg_ok(map_xyz, n_map, map_stride_bytes))
     return fail(ctx, DDDMR_ERR_BAD_ARG, "marking_create: bad cloud pointer / stride");
   if (!(cfg->xy_resolution > 0) || !(cfg->height_resolution > 0) || !(cfg->euclidean_cluster_extraction_tolerance > 0) ||
       !(cfg->inflation_radius > 0) || cfg->max_markings == 0 || cfg->max_cluster_points == 0)
@@ -250,39 +178,42 @@ int dddmr_rollout_marking_create(dddmr_rollout_ctx* ctx, const dddmr_marking_con
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "marking_create while a tick_begin is pending");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (ctx->stack) { stack_free(ctx->stack); ctx->stack = nullptr; }      // (a stack holds the layer it was created over)
-  if (ctx->marking) { marking_free(ctx->marking); ctx->marking = nullptr; }
-  auto* m = new MarkingState();
-  ctx->marking = m;
+  ctx->stack.reset();                                    // (a stack holds the layer it was created over)
+  ctx->marking.reset();                                  // (the old layer goes first: after a failed create there is none)
+  auto m = std::make_unique<MarkingState>();
   m->cfg = *cfg;
   m->max_obs = ctx->cfg.max_points;
   auto init = [&]() -> int {
     const size_t N = m->max_obs;
-    int rc = store_alloc(ctx, m->store, 1024, cfg->max_markings, cfg->max_cluster_points, (uint32_t)n_ground, true, false);
+    size_t temp_bytes = 0;
+    if (store_alloc(m->store, 1024, cfg->max_markings, cfg->max_cluster_points, (uint32_t)n_ground, true, false) != 0)
+      return fail(ctx, DDDMR_ERR_HIP, "marking_create: the marking store's allocation failed");
+    int rc = cluster_temp_bytes(ctx, N, m->store.table, &temp_bytes);
     if (rc != DDDMR_OK) return rc;
-    if ((rc = cluster_scratch_alloc(ctx, m->sc, N, m->store.table)) != DDDMR_OK) return rc;
+    if (cluster_scratch_alloc(m->sc, N, temp_bytes) != 0) return fail(ctx, DDDMR_ERR_HIP, "marking_create: the cluster scratch's allocation failed");
     rc = static_grids_upload(ctx, m->grids, m->sc.temp, m->sc.temp_bytes, ground_xyz, n_ground, ground_stride_bytes, map_xyz, n_map,
                              map_stride_bytes);
     if (rc != DDDMR_OK) return rc;
+    DevAllocs& mem = m->mem.dev;
     for (int i = 0; i < 2; ++i)
-      if ((rc = grid_alloc(ctx, m->mem, m->obs[i], 1u << 21, (uint32_t)N)) != DDDMR_OK) return rc;
-    HIPCHK(ctx, dev_alloc(m->mem, &m->sc.cl.gen_first, N));
-    HIPCHK(ctx, dev_alloc(m->mem, &m->sc.cl.gen_count, N));
-    HIPCHK(ctx, dev_alloc(m->mem, &m->sc.cl.slot, N));
-    HIPCHK(ctx, dev_alloc(m->mem, &m->gslot, N));
-    HIPCHK(ctx, dev_alloc(m->mem, &m->proj, N));
-    HIPCHK(ctx, dev_alloc(m->mem, &m->gen, N));
-    HIPCHK(ctx, dev_alloc(m->mem, &m->pool_ofs, N));
-    HIPCHK(ctx, dev_alloc(m->mem, &m->unmark_pts, m->store.pool_cap));
-    HIPCHK(ctx, dev_alloc(m->mem, &m->band_pts, (size_t)2 * kBandMax * kBandCap));
-    HIPCHK(ctx, dev_alloc(m->mem, &m->band_cnt, (size_t)2 * kBandMax));
-    HIPCHK(ctx, dev_alloc(m->mem, &m->hi_rank, (size_t)8 * (kFuseMaxObs - kFuseRegObs)));
+      if (grid_alloc(mem, m->obs[i], 1u << 21, (uint32_t)N) != 0) return fail(ctx, DDDMR_ERR_HIP, "marking_create: the observation grids' allocation failed");
+    HIPCHK(ctx, dev_alloc(mem, &m->sc.cl.gen_first, N));
+    HIPCHK(ctx, dev_alloc(mem, &m->sc.cl.gen_count, N));
+    HIPCHK(ctx, dev_alloc(mem, &m->sc.cl.slot, N));
+    HIPCHK(ctx, dev_alloc(mem, &m->gslot, N));
+    HIPCHK(ctx, dev_alloc(mem, &m->proj, N));
+    HIPCHK(ctx, dev_alloc(mem, &m->gen, N));
+    HIPCHK(ctx, dev_alloc(mem, &m->pool_ofs, N));
+    HIPCHK(ctx, dev_alloc(mem, &m->unmark_pts, m->store.pool_cap));
+    HIPCHK(ctx, dev_alloc(mem, &m->band_pts, (size_t)2 * kBandMax * kBandCap));
+    HIPCHK(ctx, dev_alloc(mem, &m->band_cnt, (size_t)2 * kBandMax));
+    HIPCHK(ctx, dev_alloc(mem, &m->hi_rank, (size_t)8 * (kFuseMaxObs - kFuseRegObs)));
     HIPCHK(ctx, hipMemset(m->band_cnt, 0, (size_t)2 * kBandMax * sizeof(uint32_t)));
-    HIPCHK(ctx, dev_alloc(m->mem, &m->cell_count, kFuseMaxCells));
+    HIPCHK(ctx, dev_alloc(mem, &m->cell_count, kFuseMaxCells));
     HIPCHK(ctx, hipMemset(m->cell_count, 0, (size_t)kFuseMaxCells * sizeof(uint32_t)));
-    HIPCHK(ctx, dev_alloc(m->mem, &m->ticket, 34));
+    HIPCHK(ctx, dev_alloc(mem, &m->ticket, 34));
     HIPCHK(ctx, hipMemset(m->ticket, 0, 34 * sizeof(uint32_t)));
-    if (host_mapped_alloc(m->host, &m->host_out, &m->host_out_dev, sizeof(MarkCounters)) != 0)
+    if (host_mapped_alloc(m->mem.host, &m->host_out, &m->host_out_dev, sizeof(MarkCounters)) != 0)
       return fail(ctx, DDDMR_ERR_HIP, "marking_create: host-mapped counters");
     MarkKnobs& kn = m->knobs;
     if (const char* e = std::getenv("DDDMR_MKF_UNMARK")) kn.unmark_with_groups = std::strcmp(e, "roots") != 0;
@@ -299,23 +230,22 @@ int dddmr_rollout_marking_create(dddmr_rollout_ctx* ctx, const dddmr_marking_con
     return DDDMR_OK;
   };
   int rc = init();
-  if (rc == DDDMR_OK) rc = marking_reset_locked(ctx);
-  if (rc != DDDMR_OK) { marking_free(m); ctx->marking = nullptr; }
+  if (rc == DDDMR_OK) rc = marking_reset_locked(ctx, m.get());
+  if (rc == DDDMR_OK) ctx->marking.reset(m.release());   // only a complete state is ever visible
   return rc;
 }
 
 int dddmr_rollout_marking_reset(dddmr_rollout_ctx* ctx) {
   if (!ctx) return DDDMR_ERR_BAD_ARG;
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  return marking_reset_locked(ctx);
+  return marking_reset_locked(ctx, ctx->marking.get());
 }
 
 }  // extern "C"
 
 namespace {
 // MultiLayerSpinningLidar::resetdGraph (:831-839)
-int marking_reset_locked(dddmr_rollout_ctx* ctx) {
-  MarkingState* m = ctx->marking;
+int marking_reset_locked(dddmr_rollout_ctx* ctx, MarkingState* m) {
   if (!m) return fail(ctx, DDDMR_ERR_STATE, "marking_reset before marking_create");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const int rc = store_reset(ctx, m->store, ctx->stream, m->cfg.max_obstacle_distance);
@@ -544,7 +474,7 @@ int dddmr_rollout_marking_update(dddmr_rollout_ctx* ctx, const double T_base_sen
                                  dddmr_marking_stats* stats) {
   if (!ctx || !T_base_sensor || !T_gbl_base) return DDDMR_ERR_BAD_ARG;
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  MarkingState* m = ctx->marking;
+  MarkingState* m = ctx->marking.get();
   if (!m) return fail(ctx, DDDMR_ERR_STATE, "marking_update before marking_create");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   // The observation = the context's published aggregate cloud (global frame), pinned like a tick pins it.
@@ -630,7 +560,7 @@ int dddmr_rollout_marking_route_counts(dddmr_rollout_ctx* ctx, uint32_t* updates
                                        uint32_t* launches_last_update) {
   if (!ctx) return DDDMR_ERR_BAD_ARG;
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  MarkingState* m = ctx->marking;
+  MarkingState* m = ctx->marking.get();
   if (!m) return fail(ctx, DDDMR_ERR_STATE, "marking_route_counts before marking_create");
   if (updates_fused) *updates_fused = m->updates_fused;
   if (updates_general) *updates_general = m->updates_general;
@@ -656,7 +586,7 @@ int dddmr_rollout_diag_mkclear(unsigned long long* out) {
 int dddmr_rollout_marking_get_voxels(dddmr_rollout_ctx* ctx, int32_t* xyz_out, size_t capacity, size_t* n) {
   if (!ctx || !n) return DDDMR_ERR_BAD_ARG;
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  MarkingState* m = ctx->marking;
+  MarkingState* m = ctx->marking.get();
   if (!m) return fail(ctx, DDDMR_ERR_STATE, "marking_get_voxels before marking_create");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   return store_read_voxels(ctx, m->store, "marking_get_voxels", xyz_out, capacity, n);
@@ -668,7 +598,7 @@ int dddmr_rollout_marking_get_voxels(dddmr_rollout_ctx* ctx, int32_t* xyz_out, s
 int dddmr_rollout_marking_get_points(dddmr_rollout_ctx* ctx, float* xyz_out, int32_t* voxel_out, size_t capacity, size_t* n) {
   if (!ctx || !n) return DDDMR_ERR_BAD_ARG;
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  MarkingState* m = ctx->marking;
+  MarkingState* m = ctx->marking.get();
   if (!m) return fail(ctx, DDDMR_ERR_STATE, "marking_get_points before marking_create");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::vector<StoreSlot> slots;
@@ -696,7 +626,7 @@ int dddmr_rollout_marking_get_points(dddmr_rollout_ctx* ctx, float* xyz_out, int
 int dddmr_rollout_marking_get_dgraph(dddmr_rollout_ctx* ctx, double* values_out, size_t capacity) {
   if (!ctx || !values_out) return DDDMR_ERR_BAD_ARG;
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  MarkingState* m = ctx->marking;
+  MarkingState* m = ctx->marking.get();
   if (!m) return fail(ctx, DDDMR_ERR_STATE, "marking_get_dgraph before marking_create");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   return store_read_dgraph(ctx, m->store, "marking_get_dgraph", values_out, capacity);
@@ -705,7 +635,7 @@ int dddmr_rollout_marking_get_dgraph(dddmr_rollout_ctx* ctx, double* values_out,
 int dddmr_rollout_marking_get_lethal(dddmr_rollout_ctx* ctx, uint8_t* flags_out, size_t capacity) {
   if (!ctx || !flags_out) return DDDMR_ERR_BAD_ARG;
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
-  MarkingState* m = ctx->marking;
+  MarkingState* m = ctx->marking.get();
   if (!m) return fail(ctx, DDDMR_ERR_STATE, "marking_get_lethal before marking_create");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   return store_read_lethal(ctx, m->store, "marking_get_lethal", flags_out, capacity);

@@ -10,74 +10,18 @@
 
 #include <unordered_map>
 
-#include "marking.hip.h"
+#include "marking_buffers.hip.h"   // StoreBuf and its allocation
 
 namespace {
 
 using namespace dddmr;
-
-struct StoreBuf {
-  MarkStore s{};
-  MarkHead head{};                         // null pointers: a store without heads
-  uint32_t* clear_list = nullptr;          // [table] alive slots selfClear has to test, this update
-  // second set of the arrays a slot moves with, for the garbage collection (k_mk_rehash) and the pool compaction
-  unsigned long long* keys_alt = nullptr;
-  uint32_t *alive_alt = nullptr, *pts_ofs_alt = nullptr, *pts_n_alt = nullptr;
-  MarkHead head_alt{};
-  float4* pool_alt = nullptr;
-  uint32_t *compact_sizes = nullptr, *compact_ofs = nullptr;
-  MarkCounters* counters = nullptr;        // device
-  uint32_t table = 0, pool_cap = 0, n_ground = 0;
-  uint32_t pool_used = 0, n_alive = 0, keys_used = 0;   // host mirrors
-  DevAllocs mem;
-};
-
-// table: the power of two >= max(min_table, 2 * max_markings)
-int store_alloc(dddmr_rollout_ctx* ctx, StoreBuf& b, uint32_t min_table, uint32_t max_markings, uint32_t pool_cap, uint32_t n_ground,
-                bool with_fov_flag, bool with_head) {
-  uint32_t t = min_table;
-  while (t < 2 * max_markings) t <<= 1;
-  b.table = t;
-  b.pool_cap = pool_cap;
-  b.n_ground = n_ground;
-  MarkStore& s = b.s;
-  HIPCHK(ctx, dev_alloc(b.mem, &s.keys, t));
-  HIPCHK(ctx, dev_alloc(b.mem, &s.alive, t));
-  HIPCHK(ctx, dev_alloc(b.mem, &s.pts_ofs, t));
-  HIPCHK(ctx, dev_alloc(b.mem, &s.pts_n, t));
-  HIPCHK(ctx, dev_alloc(b.mem, &s.removed_seq, t));
-  HIPCHK(ctx, dev_alloc(b.mem, &s.owner, t));
-  HIPCHK(ctx, dev_alloc(b.mem, &s.alive_list, t));
-  HIPCHK(ctx, dev_alloc(b.mem, &s.removed_list, t));
-  if (with_fov_flag) HIPCHK(ctx, dev_alloc(b.mem, &s.fov_flag, t));
-  HIPCHK(ctx, dev_alloc(b.mem, &s.pool, pool_cap));
-  HIPCHK(ctx, dev_alloc(b.mem, &s.dgraph, (size_t)n_ground + 1));
-  HIPCHK(ctx, dev_alloc(b.mem, &s.lethal, (size_t)n_ground + 1));
-  HIPCHK(ctx, dev_alloc(b.mem, &b.clear_list, t));
-  HIPCHK(ctx, dev_alloc(b.mem, &b.keys_alt, t));
-  HIPCHK(ctx, dev_alloc(b.mem, &b.alive_alt, t));
-  HIPCHK(ctx, dev_alloc(b.mem, &b.pts_ofs_alt, t));
-  HIPCHK(ctx, dev_alloc(b.mem, &b.pts_n_alt, t));
-  HIPCHK(ctx, dev_alloc(b.mem, &b.pool_alt, pool_cap));
-  if (with_head) {
-    HIPCHK(ctx, dev_alloc(b.mem, &b.head.pc_ofs, t));
-    HIPCHK(ctx, dev_alloc(b.mem, &b.head.pc_n, t));
-    HIPCHK(ctx, dev_alloc(b.mem, &b.head_alt.pc_ofs, t));
-    HIPCHK(ctx, dev_alloc(b.mem, &b.head_alt.pc_n, t));
-  }
-  HIPCHK(ctx, dev_alloc(b.mem, &b.compact_sizes, t));
-  HIPCHK(ctx, dev_alloc(b.mem, &b.compact_ofs, t));
-  HIPCHK(ctx, dev_alloc(b.mem, &b.counters, 1));
-  return DDDMR_OK;
-}
-
-void store_free(StoreBuf& b) { dev_free(b.mem); }
 
 // resetdGraph (MultiLayerSpinningLidar :831-839, the depth camera layer's alike): empty store, zeroed counters,
 // dGraph = max_obstacle_distance on keys 0 .. n_ground.  Waits for `st`.
 int store_reset(dddmr_rollout_ctx* ctx, StoreBuf& b, hipStream_t st, double max_obstacle_distance) {
   MarkStore& s = b.s;
   const size_t t = b.table;
+  Drain drain{st};                         // an error exit leaves no memset running over a store that may then be freed
   HIPCHK(ctx, hipMemsetAsync(s.keys, 0, t * sizeof(unsigned long long), st));
   HIPCHK(ctx, hipMemsetAsync(s.alive, 0, t * sizeof(uint32_t), st));
   HIPCHK(ctx, hipMemsetAsync(s.pts_ofs, 0, t * sizeof(uint32_t), st));
@@ -93,6 +37,7 @@ int store_reset(dddmr_rollout_ctx* ctx, StoreBuf& b, hipStream_t st, double max_
   hipLaunchKernelGGL(k_mk_fill_dgraph, dim3((b.n_ground + 1 + 255) / 256), dim3(256), 0, st, b.n_ground + 1, s.dgraph, max_obstacle_distance);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(st));
+  drain.armed = false;
   b.pool_used = 0;
   b.n_alive = 0;
   b.keys_used = 0;

@@ -327,7 +327,6 @@ __global__ __launch_bounds__(256) void k_mcl_finish(MclParams k, MclTerms t, con
 namespace {
 
 struct MclObs;                             // the prepared observation, mcl_observation.hip.h
-void mclobs_free(MclObs* o);
 
 struct MclMap {                            // one swapKdTree generation
   GridBuf map, ground;
@@ -344,8 +343,7 @@ struct MclState {
   size_t temp_bytes = 0;
   MclTerms t{};
   float* qual_dev = nullptr;
-  DevAllocs mem;
-  HostAllocs host;
+  Owned mem;
   // host-mapped: the call's inputs (read in place by the kernels) and results
   float4 *obs_host = nullptr, *obs_dev = nullptr;
   float *states_host = nullptr, *states_dev = nullptr;
@@ -353,88 +351,66 @@ struct MclState {
   MclResult *res_host = nullptr, *res_dev = nullptr;
   uint32_t seq = 0;
   uint32_t last_n = 0;                     // particles of the last successful measure (get_terms)
-  MclObs* obs = nullptr;                   // dddmr_rollout_mcl_set_observation_config
+  std::unique_ptr<MclObs, LateDelete<MclObs>> obs;   // dddmr_rollout_mcl_set_observation_config
 };
-
-void mcl_free(MclState* s) {
-  if (!s) return;
-  mclobs_free(s->obs);
-  dev_free(s->mem);
-  host_free(s->host);
-  delete s;
-}
+static_assert(!std::is_copy_constructible_v<MclState>);
 
 constexpr uint32_t kMclCells = 1u << 21;   // cells of each grid (grid_shape coarsens the cell until the cloud's box fits)
 
 int mcl_alloc(dddmr_rollout_ctx* ctx, MclState* s) {
   const dddmr_mcl_config& c = s->cfg;
+  DevAllocs& mem = s->mem.dev;
   {
     size_t e = 0;
     uint32_t* v = nullptr;
     HIPCHK(ctx, rocprim::exclusive_scan(nullptr, e, v, v, 0u, (size_t)kMclCells + 1, rocprim::plus<uint32_t>(), ctx->stream));
     s->temp_bytes = std::max(e, (size_t)4096) + 256;
-    HIPCHK(ctx, dev_alloc(s->mem, &s->temp, s->temp_bytes));
+    HIPCHK(ctx, dev_alloc(mem, &s->temp, s->temp_bytes));
   }
-  HIPCHK(ctx, dev_alloc(s->mem, &s->slot, std::max<size_t>(std::max(c.max_map_points, c.max_ground_points), 1)));
+  HIPCHK(ctx, dev_alloc(mem, &s->slot, std::max<size_t>(std::max(c.max_map_points, c.max_ground_points), 1)));
   for (MclMap& m : s->maps) {
-    int rc = grid_alloc(ctx, s->mem, m.map, kMclCells, c.max_map_points);
-    if (rc == DDDMR_OK) rc = grid_alloc(ctx, s->mem, m.ground, kMclCells, c.max_ground_points);
-    if (rc != DDDMR_OK) return rc;
-    HIPCHK(ctx, dev_alloc(s->mem, &m.map_pts, std::max<size_t>(c.max_map_points, 1)));
-    HIPCHK(ctx, dev_alloc(s->mem, &m.ground_pts, std::max<size_t>(c.max_ground_points, 1)));
-    HIPCHK(ctx, dev_alloc(s->mem, &m.normals, std::max<size_t>(c.max_ground_points, 1)));
+    if (grid_alloc(mem, m.map, kMclCells, c.max_map_points) != 0 || grid_alloc(mem, m.ground, kMclCells, c.max_ground_points) != 0)
+      return fail(ctx, DDDMR_ERR_HIP, "mcl_create: the grids' allocation failed");
+    HIPCHK(ctx, dev_alloc(mem, &m.map_pts, std::max<size_t>(c.max_map_points, 1)));
+    HIPCHK(ctx, dev_alloc(mem, &m.ground_pts, std::max<size_t>(c.max_ground_points, 1)));
+    HIPCHK(ctx, dev_alloc(mem, &m.normals, std::max<size_t>(c.max_ground_points, 1)));
   }
   const size_t N = c.max_particles;
-  HIPCHK(ctx, dev_alloc(s->mem, &s->t.score, N));
-  HIPCHK(ctx, dev_alloc(s->mem, &s->t.pos_weight, N));
-  HIPCHK(ctx, dev_alloc(s->mem, &s->t.n_match, N));
-  HIPCHK(ctx, dev_alloc(s->mem, &s->t.n_ground, N));
-  HIPCHK(ctx, dev_alloc(s->mem, &s->t.flags, N));
-  HIPCHK(ctx, dev_alloc(s->mem, &s->qual_dev, N));
-  if (host_mapped_alloc(s->host, &s->obs_host, &s->obs_dev, (size_t)c.max_observation_points * sizeof(float4)) != 0 ||
-      host_mapped_alloc(s->host, &s->states_host, &s->states_dev, N * 7 * sizeof(float)) != 0 ||
-      host_mapped_alloc(s->host, &s->out_host, &s->out_dev, N * 2 * sizeof(float)) != 0 ||
-      host_mapped_alloc(s->host, &s->res_host, &s->res_dev, sizeof(MclResult)) != 0)
+  HIPCHK(ctx, dev_alloc(mem, &s->t.score, N));
+  HIPCHK(ctx, dev_alloc(mem, &s->t.pos_weight, N));
+  HIPCHK(ctx, dev_alloc(mem, &s->t.n_match, N));
+  HIPCHK(ctx, dev_alloc(mem, &s->t.n_ground, N));
+  HIPCHK(ctx, dev_alloc(mem, &s->t.flags, N));
+  HIPCHK(ctx, dev_alloc(mem, &s->qual_dev, N));
+  if (host_mapped_alloc(s->mem.host, &s->obs_host, &s->obs_dev, (size_t)c.max_observation_points * sizeof(float4)) != 0 ||
+      host_mapped_alloc(s->mem.host, &s->states_host, &s->states_dev, N * 7 * sizeof(float)) != 0 ||
+      host_mapped_alloc(s->mem.host, &s->out_host, &s->out_dev, N * 2 * sizeof(float)) != 0 ||
+      host_mapped_alloc(s->mem.host, &s->res_host, &s->res_dev, sizeof(MclResult)) != 0)
     return fail(ctx, DDDMR_ERR_HIP, "mcl_create: host-mapped staging");
   std::memset(s->res_host, 0, sizeof(MclResult));
   return DDDMR_OK;
 }
 
 // One cloud into a generation's buffers: the points, their box, the grid.  Cells at least twice the match radius wide,
-// so that a point's query touches at most 2 x 2 rows of cells (grid_for_each's fast path).
-int mcl_upload(dddmr_rollout_ctx* ctx, MclState* s, GridBuf& b, float4* dev, const float* xyz, size_t n, size_t stride_bytes) {
-  std::vector<float4> h(std::max<size_t>(n, 1), make_float4(0.f, 0.f, 0.f, 0.f));
-  float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-  const size_t sf = stride_bytes / sizeof(float);
-  for (size_t i = 0; i < n; ++i) {
-    const float* p = xyz + i * sf;
-    h[i] = make_float4(p[0], p[1], p[2], 0.f);
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = i ? std::min(lo[a], p[a]) : p[a];
-      hi[a] = i ? std::max(hi[a], p[a]) : p[a];
-    }
-  }
-  if (n) HIPCHK(ctx, hipMemcpyAsync(dev, h.data(), n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+// so that a point's query touches at most 2 x 2 rows of cells (grid_for_each's fast path).  Waits for the stream: the
+// caller's `h` is pageable.
+int mcl_upload(dddmr_rollout_ctx* ctx, MclState* s, GridBuf& b, float4* dev, const HostCloud& h, size_t n) {
+  Drain drain{ctx->stream};
+  if (n) HIPCHK(ctx, hipMemcpyAsync(dev, h.pts.data(), n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
   const float cell = 2.02f * (s->k.mdm + kMclPad);
-  grid_shape(b.g, lo, hi, cell, cell, b.cap_cells);
+  grid_shape(b.g, h.lo, h.hi, cell, cell, b.cap_cells);
   const int rc = grid_build(ctx, s->temp, s->temp_bytes, b, dev, (uint32_t)n, s->slot, ctx->stream);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // (h is pageable and leaves scope)
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  drain.armed = false;
   return rc;
 }
 
 // finite coordinates within 1e6 m, and a box the search pad covers (kMclMaxExtent)
-bool mcl_cloud_ok(const float* xyz, size_t n, size_t stride_bytes) {
-  const size_t sf = stride_bytes / sizeof(float);
-  float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+bool mcl_cloud_ok(const HostCloud& h, size_t n) {
   for (size_t i = 0; i < n; ++i)
-    for (int a = 0; a < 3; ++a) {
-      const float v = xyz[i * sf + a];
-      if (!(std::fabs(v) <= 1e6f)) return false;
-      lo[a] = i ? std::min(lo[a], v) : v;
-      hi[a] = i ? std::max(hi[a], v) : v;
-    }
+    if (!(std::fabs(h.pts[i].x) <= 1e6f) || !(std::fabs(h.pts[i].y) <= 1e6f) || !(std::fabs(h.pts[i].z) <= 1e6f)) return false;
   for (int a = 0; a < 3; ++a)
-    if (!(hi[a] - lo[a] <= kMclMaxExtent)) return false;
+    if (!(h.hi[a] - h.lo[a] <= kMclMaxExtent)) return false;
   return true;
 }
 
@@ -465,12 +441,8 @@ int mcl_run(dddmr_rollout_ctx* ctx, const char* what, MclState* s, const float4*
   hipLaunchKernelGGL(k_mcl_match, dim3(blocks), dim3(256), (size_t)n_obs * 32, st, k, m.ground.g, m.map.g, obs_dev, s->states_dev, s->t,
                      s->qual_dev, s->out_dev, s->out_dev + s->cfg.max_particles);
   hipLaunchKernelGGL(k_mcl_finish, dim3(1), dim3(256), 0, st, k, s->t, s->qual_dev, s->res_dev, seq);
-  HIPCHK(ctx, hipGetLastError());
-  uint32_t waits = 1;                                  // the spin on the result word
-  if (!wait_seq(&s->res_host->seq, seq)) {             // not seen within the spin's bound: wait for the stream instead
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    ++waits;
-  }
+  uint32_t waits = 0;                                  // the spin on the result word, and the stream's when the spin ran out
+  if (const int rc = feed_wait(st, &s->res_host->seq, seq, &waits)) return fail(ctx, DDDMR_ERR_HIP, "%s: launch or wait failed (%d)", what, rc);
   const MclResult r = *s->res_host;
   if (stats) {
     stats->quality_min = r.q_min; stats->quality_max = r.q_max;
@@ -509,7 +481,7 @@ int dddmr_rollout_mcl_create(dddmr_rollout_ctx* ctx, const dddmr_mcl_config* cfg
   if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "mcl_create while a tick_begin is pending");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  auto* s = new MclState();
+  auto s = std::make_unique<MclState>();
   s->cfg = *cfg;
   MclParams& k = s->k;
   k.mdm = (float)cfg->match_dist_min;
@@ -519,41 +491,35 @@ int dddmr_rollout_mcl_create(dddmr_rollout_ctx* ctx, const dddmr_mcl_config* cfg
   k.r2_ground = static_cast<float>(cfg->radius_of_ground_search * cfg->radius_of_ground_search);
   k.threshold = (uint32_t)cfg->threshold_for_trusted_ground;
   k.cap_nb = cfg->max_ground_neighbours;
-  const int rc = mcl_alloc(ctx, s);
-  if (rc != DDDMR_OK) { mcl_free(s); return rc; }
-  if (ctx->mcl) mcl_free(ctx->mcl);
-  ctx->mcl = s;                                          // only a complete state is ever visible
-  return DDDMR_OK;
+  const int rc = mcl_alloc(ctx, s.get());
+  if (rc == DDDMR_OK) ctx->mcl.reset(s.release());       // only a complete state is ever visible; the old one survives a failed create
+  return rc;
 }
 
 int dddmr_rollout_mcl_set_map(dddmr_rollout_ctx* ctx, const float* map_xyz, size_t n_map, size_t map_stride_bytes,
                               const float* ground_xyz, const float* ground_normals, size_t n_ground, size_t ground_stride_bytes,
                               size_t normal_stride_bytes) {
   if (!ctx) return DDDMR_ERR_BAD_ARG;
-  if ((n_map && (!map_xyz || map_stride_bytes < 12 || map_stride_bytes % 4)) ||
-      (n_ground && (!ground_xyz || !ground_normals || ground_stride_bytes < 12 || ground_stride_bytes % 4 || normal_stride_bytes < 12 ||
-                    normal_stride_bytes % 4)))
+  if (!cloud_arg_ok(map_xyz, n_map, map_stride_bytes) || !cloud_arg_ok(ground_xyz, n_ground, ground_stride_bytes) ||
+      !cloud_arg_ok(ground_normals, n_ground, normal_stride_bytes))
     return fail(ctx, DDDMR_ERR_BAD_ARG, "mcl_set_map: bad cloud pointer / stride");
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "mcl_set_map while a tick_begin is pending");
-  MclState* s = ctx->mcl;
+  MclState* s = ctx->mcl.get();
   if (!s) return fail(ctx, DDDMR_ERR_STATE, "mcl_set_map before mcl_create");
   if (n_map > s->cfg.max_map_points || n_ground > s->cfg.max_ground_points)
     return fail(ctx, DDDMR_ERR_CAPACITY, "mcl_set_map: %zu map / %zu ground points, capacity %u / %u", n_map, n_ground, s->cfg.max_map_points,
                 s->cfg.max_ground_points);
-  if (!mcl_cloud_ok(map_xyz, n_map, map_stride_bytes) || !mcl_cloud_ok(ground_xyz, n_ground, ground_stride_bytes))
+  const HostCloud map_h(map_xyz, n_map, map_stride_bytes), ground_h(ground_xyz, n_ground, ground_stride_bytes);
+  if (!mcl_cloud_ok(map_h, n_map) || !mcl_cloud_ok(ground_h, n_ground))
     return fail(ctx, DDDMR_ERR_BAD_ARG, "mcl_set_map: a map or ground coordinate is not finite or beyond 1e6 m, or a cloud is wider than %g m on an axis", (double)kMclMaxExtent);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   MclMap& m = s->maps[s->cur == 0 ? 1 : 0];              // beside the current one
-  int rc = mcl_upload(ctx, s, m.map, m.map_pts, map_xyz, n_map, map_stride_bytes);
-  if (rc == DDDMR_OK) rc = mcl_upload(ctx, s, m.ground, m.ground_pts, ground_xyz, n_ground, ground_stride_bytes);
+  int rc = mcl_upload(ctx, s, m.map, m.map_pts, map_h, n_map);
+  if (rc == DDDMR_OK) rc = mcl_upload(ctx, s, m.ground, m.ground_pts, ground_h, n_ground);
   if (rc != DDDMR_OK) return rc;
-  if (n_ground) {
-    std::vector<float4> h(n_ground);
-    const size_t sf = normal_stride_bytes / sizeof(float);
-    for (size_t i = 0; i < n_ground; ++i) h[i] = make_float4(ground_normals[i * sf], ground_normals[i * sf + 1], ground_normals[i * sf + 2], 0.f);
-    HIPCHK(ctx, hipMemcpy(m.normals, h.data(), n_ground * sizeof(float4), hipMemcpyHostToDevice));
-  }
+  if (n_ground)
+    HIPCHK(ctx, hipMemcpy(m.normals, HostCloud(ground_normals, n_ground, normal_stride_bytes).pts.data(), n_ground * sizeof(float4), hipMemcpyHostToDevice));
   s->cur = s->cur == 0 ? 1 : 0;
   return DDDMR_OK;
 }
@@ -568,7 +534,7 @@ int dddmr_rollout_mcl_measure(dddmr_rollout_ctx* ctx, const float* flat_xyz, siz
   if (n_flat + n_less_sharp == 0) return fail(ctx, DDDMR_ERR_BAD_ARG, "mcl_measure: no observation point (the reference divides 0 by 0)");
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "mcl_measure while a tick_begin is pending");
-  MclState* s = ctx->mcl;
+  MclState* s = ctx->mcl.get();
   if (!s) return fail(ctx, DDDMR_ERR_STATE, "mcl_measure before mcl_create");
   if (s->cur < 0) return fail(ctx, DDDMR_ERR_STATE, "mcl_measure before mcl_set_map");
   if (n_flat > s->cfg.max_observation_points || n_less_sharp > s->cfg.max_observation_points ||
@@ -587,7 +553,7 @@ int dddmr_rollout_mcl_get_terms(dddmr_rollout_ctx* ctx, float* score_like_out, f
   if (!ctx) return DDDMR_ERR_BAD_ARG;
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "mcl_get_terms while a tick_begin is pending");
-  MclState* s = ctx->mcl;
+  MclState* s = ctx->mcl.get();
   if (!s) return fail(ctx, DDDMR_ERR_STATE, "mcl_get_terms before mcl_create");
   const size_t n = s->last_n;
   if (capacity < n) return fail(ctx, DDDMR_ERR_CAPACITY, "mcl_get_terms: capacity %zu < %zu particles", capacity, n);

@@ -419,8 +419,7 @@ struct MclObs {
   int cur = 0;                              // obs[cur] answers the getter and the measure
   float4* pts = nullptr;
   uint2* slot_rank = nullptr;
-  DevAllocs mem;
-  HostAllocs host;
+  Owned mem;
   // host-mapped: the host entry's input, the kept clusters' sizes, their plan, the result
   float4 *in_host = nullptr, *in_dev = nullptr;
   uint32_t *kept_host = nullptr, *kept_dev = nullptr;
@@ -429,25 +428,20 @@ struct MclObs {
   uint32_t seq = 0;
 };
 
-void mclobs_free(MclObs* o) {
-  if (!o) return;
-  dev_free(o->mem);
-  host_free(o->host);
-  delete o;
-}
+static_assert(!std::is_copy_constructible_v<MclObs>);
 
 int mclobs_alloc(dddmr_rollout_ctx* ctx, MclObs* o) {
   const size_t cap = std::max<uint32_t>(o->cap, 1), nl = std::max<uint32_t>(o->cfg.max_less_sharp_points, 1);
   for (int b = 0; b < 2; ++b) {
-    HIPCHK(ctx, dev_alloc(o->mem, &o->obs[b], cap));
-    HIPCHK(ctx, dev_alloc(o->mem, &o->normals[b], nl));
+    HIPCHK(ctx, dev_alloc(o->mem.dev, &o->obs[b], cap));
+    HIPCHK(ctx, dev_alloc(o->mem.dev, &o->normals[b], nl));
   }
-  HIPCHK(ctx, dev_alloc(o->mem, &o->pts, nl));
-  HIPCHK(ctx, dev_alloc(o->mem, &o->slot_rank, nl));
-  if (host_mapped_alloc(o->host, &o->in_host, &o->in_dev, cap * sizeof(float4)) != 0 ||
-      host_mapped_alloc(o->host, &o->kept_host, &o->kept_dev, nl * sizeof(uint32_t)) != 0 ||
-      host_mapped_alloc(o->host, &o->plan_host, &o->plan_dev, nl * sizeof(uint2)) != 0 ||
-      host_mapped_alloc(o->host, &o->res_host, &o->res_dev, sizeof(MclObsResult)) != 0)
+  HIPCHK(ctx, dev_alloc(o->mem.dev, &o->pts, nl));
+  HIPCHK(ctx, dev_alloc(o->mem.dev, &o->slot_rank, nl));
+  if (host_mapped_alloc(o->mem.host, &o->in_host, &o->in_dev, cap * sizeof(float4)) != 0 ||
+      host_mapped_alloc(o->mem.host, &o->kept_host, &o->kept_dev, nl * sizeof(uint32_t)) != 0 ||
+      host_mapped_alloc(o->mem.host, &o->plan_host, &o->plan_dev, nl * sizeof(uint2)) != 0 ||
+      host_mapped_alloc(o->mem.host, &o->res_host, &o->res_dev, sizeof(MclObsResult)) != 0)
     return fail(ctx, DDDMR_ERR_HIP, "mcl_set_observation_config: host-mapped staging");
   std::memset(o->res_host, 0, sizeof(MclObsResult));
   return DDDMR_OK;
@@ -471,12 +465,8 @@ int mclobs_run(dddmr_rollout_ctx* ctx, const char* what, MclObs* o, const float4
   hipStream_t st = ctx->stream;
   hipLaunchKernelGGL(k_mclobs_prepare, dim3(1), dim3(kMclObsThreads), 0, st, k, flat_dev, ls_dev, o->obs[b], o->normals[b], o->pts, o->slot_rank,
                      o->kept_dev, o->res_dev);
-  HIPCHK(ctx, hipGetLastError());
-  uint32_t launches = 1, waits = 1;
-  if (!wait_seq(&o->res_host->seq, k.seq)) {
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    ++waits;
-  }
+  uint32_t launches = 1, waits = 0;
+  if (const int rc = feed_wait(st, &o->res_host->seq, k.seq, &waits)) return fail(ctx, DDDMR_ERR_HIP, "%s: launch or wait failed (%d)", what, rc);
   const MclObsResult r = *o->res_host;
   if (r.n_flat_out > n_flat || r.n_ls_out > n_ls || r.n_kept > n_ls) return fail(ctx, DDDMR_ERR_HIP, "%s: inconsistent counts from the device", what);
   if (r.branch == kMclObsClusters && r.n_kept) {
@@ -492,9 +482,11 @@ int mclobs_run(dddmr_rollout_ctx* ctx, const char* what, MclObs* o, const float4
       at += size;
     }
     if (at != r.n_ls_out) return fail(ctx, DDDMR_ERR_HIP, "%s: the kept clusters hold %u points, the device counted %u", what, at, r.n_ls_out);
+    Drain drain{st};                                     // (the prepare does not wait for this launch; an error exit does)
     hipLaunchKernelGGL(k_mclobs_pack, dim3((n_ls + 255) / 256), dim3(256), 0, st, n_ls, r.n_ls_out, o->pts, o->slot_rank, o->plan_dev,
                        o->obs[b] + r.n_flat_out);
     HIPCHK(ctx, hipGetLastError());
+    drain.armed = false;
     ++launches;
   }
   o->n_flat[b] = r.n_flat_out;
@@ -515,7 +507,7 @@ int mclobs_run(dddmr_rollout_ctx* ctx, const char* what, MclObs* o, const float4
 // the checks every observation entry starts with; tick_mu held
 int mclobs_state(dddmr_rollout_ctx* ctx, const char* what, bool need_config, MclState** out) {
   if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "%s while a tick_begin is pending", what);
-  MclState* s = ctx->mcl;
+  MclState* s = ctx->mcl.get();
   if (!s) return fail(ctx, DDDMR_ERR_STATE, "%s before mcl_create", what);
   if (need_config && !s->obs) return fail(ctx, DDDMR_ERR_STATE, "%s before mcl_set_observation_config", what);
   *out = s;
@@ -544,18 +536,15 @@ int dddmr_rollout_mcl_set_observation_config(dddmr_rollout_ctx* ctx, const dddmr
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   if (!cfg) {
-    mclobs_free(s->obs);
-    s->obs = nullptr;
+    s->obs.reset();
     return DDDMR_OK;
   }
-  auto* o = new MclObs();
+  auto o = std::make_unique<MclObs>();
   o->cfg = *cfg;
   o->cap = cfg->max_flat_points + cfg->max_less_sharp_points;
-  const int rc = mclobs_alloc(ctx, o);
-  if (rc != DDDMR_OK) { mclobs_free(o); return rc; }
-  mclobs_free(s->obs);                                   // (a new configuration forgets the prepared observation)
-  s->obs = o;
-  return DDDMR_OK;
+  const int rc = mclobs_alloc(ctx, o.get());
+  if (rc == DDDMR_OK) s->obs.reset(o.release());         // (a new configuration forgets the prepared observation; the old one survives a failed create)
+  return rc;
 }
 
 int dddmr_rollout_mcl_prepare(dddmr_rollout_ctx* ctx, const float* flat_xyz, size_t n_flat, size_t flat_stride_bytes,
@@ -564,15 +553,14 @@ int dddmr_rollout_mcl_prepare(dddmr_rollout_ctx* ctx, const float* flat_xyz, siz
   if (!ctx) return DDDMR_ERR_BAD_ARG;
   const char* what = "mcl_prepare";
   if (stats) *stats = dddmr_mcl_observation_stats{};
-  if (!T_b2s || (n_flat && (!flat_xyz || flat_stride_bytes < 12 || flat_stride_bytes % 4)) ||
-      (n_less_sharp && (!less_sharp_xyz || less_sharp_stride_bytes < 12 || less_sharp_stride_bytes % 4)))
+  if (!T_b2s || !cloud_arg_ok(flat_xyz, n_flat, flat_stride_bytes) || !cloud_arg_ok(less_sharp_xyz, n_less_sharp, less_sharp_stride_bytes))
     return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: null argument or bad stride", what);
   for (int i = 0; i < 12; ++i)
     if (!std::isfinite(T_b2s[i])) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: T_b2s[%d] is not finite", what, i);
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   MclState* s = nullptr;
   if (const int rc = mclobs_state(ctx, what, true, &s)) return rc;
-  MclObs* o = s->obs;
+  MclObs* o = s->obs.get();
   if (n_flat > o->cfg.max_flat_points || n_less_sharp > o->cfg.max_less_sharp_points)
     return fail(ctx, DDDMR_ERR_CAPACITY, "%s: %zu flat / %zu less-sharp points, configured for %u / %u", what, n_flat, n_less_sharp,
                 o->cfg.max_flat_points, o->cfg.max_less_sharp_points);
@@ -600,7 +588,7 @@ int dddmr_rollout_mcl_prepare_from_sweep(dddmr_rollout_ctx* ctx, int32_t source_
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   MclState* s = nullptr;
   if (const int rc = mclobs_state(ctx, what, true, &s)) return rc;
-  MclObs* o = s->obs;
+  MclObs* o = s->obs.get();
   HIPCHK(ctx, hipSetDevice(ctx->device));
   // the source's current buffers are complete (set_lidar_sweep waits for its result before it commits) and stay as they
   // are while producer_mu is held: the next sweep builds beside them
@@ -624,7 +612,7 @@ int dddmr_rollout_mcl_get_observation(dddmr_rollout_ctx* ctx, float* flat_xyz_ou
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   MclState* s = nullptr;
   if (const int rc = mclobs_state(ctx, what, true, &s)) return rc;
-  const MclObs* o = s->obs;
+  const MclObs* o = s->obs.get();
   const int b = o->cur;
   const size_t nf = o->n_flat[b], nl = o->n_ls[b], nn = o->n_ls_in[b];
   if ((flat_xyz_out && flat_capacity < nf) || (less_sharp_xyzi_out && less_sharp_capacity < nl) || (normals_out && normals_capacity < nn))
@@ -656,7 +644,7 @@ int dddmr_rollout_mcl_measure_prepared(dddmr_rollout_ctx* ctx, const float* stat
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   MclState* s = nullptr;
   if (const int rc = mclobs_state(ctx, what, true, &s)) return rc;
-  const MclObs* o = s->obs;
+  const MclObs* o = s->obs.get();
   const int b = o->cur;
   if (o->n_flat[b] + o->n_ls[b] == 0) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: no observation point (the reference divides 0 by 0)", what);
   return mcl_run(ctx, what, s, o->obs[b], o->n_flat[b], o->n_ls[b], states, n_states, likelihood_out, quality_out, stats);

@@ -95,23 +95,17 @@ struct StackState {
   bool host_set[DDDMR_STACK_MAX_HOST] = {};
   uint32_t* n_changed_dev = nullptr;
   float4* lidar_obs = nullptr;               // gather buffer for lidar sources that are not neighbours in the aggregate (lazy)
-  DevAllocs mem;
-  HostAllocs host;
+  Owned mem;
   // host-mapped: uint32 count | pad | double value[cap] | uint32 node[cap] | uint8 mask[cap]
   char *list_host = nullptr, *list_dev = nullptr;
   uint32_t n_changed = 0;                    // of the last update (true count)
 };
 
-void stack_free(StackState* s) {
-  if (!s) return;
-  dev_free(s->mem);
-  host_free(s->host);
-  delete s;
-}
+static_assert(!std::is_copy_constructible_v<StackState>);
 
 StackState* stack_of(dddmr_rollout_ctx* ctx, const char* what) {
   if (!ctx->stack) (void)fail(ctx, DDDMR_ERR_STATE, "%s before stack_create (or after a later marking_create / depth_layer_create)", what);
-  return ctx->stack;
+  return ctx->stack.get();
 }
 
 size_t stack_cap(const StackState* s) { return std::max<size_t>(s->cfg.max_changes, 1); }
@@ -139,12 +133,14 @@ int stack_recompute(dddmr_rollout_ctx* ctx, StackState* s, bool publish_only, ui
   a.chg_mask = stack_list_mask(s, s->list_dev);
   a.n_changed = s->n_changed_dev;
   hipStream_t st = ctx->stream;
+  Drain drain{st};                           // an error exit leaves nothing running that writes the state's arrays
   HIPCHK(ctx, hipMemsetAsync(s->n_changed_dev, 0, sizeof(uint32_t), st));
   const uint32_t blocks = std::min<uint32_t>((s->n_nodes + 255u) / 256u, 2048u);
   hipLaunchKernelGGL(k_stack_min, dim3(blocks), dim3(256), 0, st, a);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipMemcpyAsync(s->list_host, s->n_changed_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
+  drain.armed = false;
   if (ops) *ops += 3;
   s->n_changed = publish_only ? 0u : *reinterpret_cast<const uint32_t*>(s->list_host);
   return DDDMR_OK;
@@ -185,26 +181,24 @@ int dddmr_rollout_stack_create(dddmr_rollout_ctx* ctx, const dddmr_stack_config*
       return fail(ctx, DDDMR_ERR_BAD_ARG, "stack_create: n_ground %u, the depth layer has %u", cfg->n_ground, ctx->dlayer->store.n_ground);
   }
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  auto* s = new StackState();
+  auto s = std::make_unique<StackState>();
   s->cfg = *cfg;
   s->n_nodes = cfg->n_ground + 1;
-  auto init = [&]() -> int {
-    HIPCHK(ctx, dev_alloc(s->mem, &s->min_pub, s->n_nodes));
-    HIPCHK(ctx, dev_alloc(s->mem, &s->mask_pub, s->n_nodes));
-    HIPCHK(ctx, dev_alloc(s->mem, &s->n_changed_dev, 1));
-    for (int i = 0; i < cfg->n_host_layers; ++i) HIPCHK(ctx, dev_alloc(s->mem, &s->host_layer[i], s->n_nodes));
-    const size_t bytes = 8 + 13 * stack_cap(s);
-    if (host_mapped_alloc(s->host, &s->list_host, &s->list_dev, bytes) != 0) return fail(ctx, DDDMR_ERR_HIP, "stack_create: change list of %zu bytes", bytes);
-    // (the published arrays start as a pattern no result has, so the first pass writes every node)
-    HIPCHK(ctx, hipMemsetAsync(s->min_pub, 0xFF, (size_t)s->n_nodes * sizeof(double), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(s->mask_pub, 0xFF, s->n_nodes, ctx->stream));
-    return stack_recompute(ctx, s, true, nullptr);
-  };
-  const int rc = init();
-  if (rc != DDDMR_OK) { stack_free(s); return rc; }
-  if (ctx->stack) stack_free(ctx->stack);
-  ctx->stack = s;                                        // only a complete state is ever visible
-  return DDDMR_OK;
+  DevAllocs& mem = s->mem.dev;
+  HIPCHK(ctx, dev_alloc(mem, &s->min_pub, s->n_nodes));
+  HIPCHK(ctx, dev_alloc(mem, &s->mask_pub, s->n_nodes));
+  HIPCHK(ctx, dev_alloc(mem, &s->n_changed_dev, 1));
+  for (int i = 0; i < cfg->n_host_layers; ++i) HIPCHK(ctx, dev_alloc(mem, &s->host_layer[i], s->n_nodes));
+  const size_t bytes = 8 + 13 * stack_cap(s.get());
+  if (host_mapped_alloc(s->mem.host, &s->list_host, &s->list_dev, bytes) != 0) return fail(ctx, DDDMR_ERR_HIP, "stack_create: change list of %zu bytes", bytes);
+  // (the published arrays start as a pattern no result has, so the first pass writes every node)
+  Drain drain{ctx->stream};                              // behind `s`: an error exit waits for the memsets before the state dies
+  HIPCHK(ctx, hipMemsetAsync(s->min_pub, 0xFF, (size_t)s->n_nodes * sizeof(double), ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(s->mask_pub, 0xFF, s->n_nodes, ctx->stream));
+  const int rc = stack_recompute(ctx, s.get(), true, nullptr);
+  drain.armed = false;                                   // (stack_recompute has waited, or drained)
+  if (rc == DDDMR_OK) ctx->stack.reset(s.release());     // only a complete state is ever visible; the old one survives a failed create
+  return rc;
 }
 
 int dddmr_rollout_stack_set_host_layer(dddmr_rollout_ctx* ctx, int32_t slot, const double* values) {
@@ -237,9 +231,10 @@ int dddmr_rollout_stack_update(dddmr_rollout_ctx* ctx, const double T_base_senso
   uint32_t ops = 0;
   // ---- lidar layer, on the lidar sources' segments of the pinned aggregate ----
   if (lidar) {
-    MarkingState* m = ctx->marking;
+    MarkingState* m = ctx->marking.get();
     auto pass = [&]() -> int {
       CloudPin pin(ctx);
+      Drain drain{ctx->stream, false};                   // behind the pin: armed by the gather copies, which read the pinned aggregate
       const int cidx = pin.idx();
       m->cur = ctx->stream;
       HIPCHK(ctx, pin.wait_on(m->cur));
@@ -263,8 +258,9 @@ int dddmr_rollout_stack_update(dddmr_rollout_ctx* ctx, const double T_base_senso
       if (L.total > ctx->cloud_n[cidx]) return fail(ctx, DDDMR_ERR_STATE, "stack_update: source counts %u beyond the aggregate's %u points", L.total, ctx->cloud_n[cidx]);
       const float4* obs = ctx->cloud_dev[cidx] + (n_runs ? runs[0].at : 0u);
       if (n_runs > 1) {
-        if (!s->lidar_obs) HIPCHK(ctx, dev_alloc(s->mem, &s->lidar_obs, (size_t)std::max<uint32_t>(ctx->cfg.max_points, 1)));
+        if (!s->lidar_obs) HIPCHK(ctx, dev_alloc(s->mem.dev, &s->lidar_obs, (size_t)std::max<uint32_t>(ctx->cfg.max_points, 1)));
         uint32_t to = 0;
+        drain.armed = true;
         for (int r = 0; r < n_runs; ++r) {
           HIPCHK(ctx, hipMemcpyAsync(s->lidar_obs + to, ctx->cloud_dev[cidx] + runs[r].at, (size_t)runs[r].n * sizeof(float4), hipMemcpyDeviceToDevice, m->cur));
           to += runs[r].n;
@@ -272,7 +268,9 @@ int dddmr_rollout_stack_update(dddmr_rollout_ctx* ctx, const double T_base_senso
         }
         obs = s->lidar_obs;
       }
-      return marking_update_on(ctx, m, obs, total, T_base_sensor, T_gbl_base, &out.lidar);
+      const int rc = marking_update_on(ctx, m, obs, total, T_base_sensor, T_gbl_base, &out.lidar);
+      drain.armed = drain.armed && rc != DDDMR_OK;       // (a successful update has waited for the stream)
+      return rc;
     };
     out.lidar_rc = pass();
     ops += m->launches_last;
@@ -370,7 +368,7 @@ int dddmr_rollout_stack_reset(dddmr_rollout_ctx* ctx) {
   if (ctx->pend.active) return fail(ctx, DDDMR_ERR_STATE, "stack_reset while a tick_begin is pending");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int rc = DDDMR_OK;
-  if (s->cfg.use_lidar_layer) rc = marking_reset_locked(ctx);
+  if (s->cfg.use_lidar_layer) rc = marking_reset_locked(ctx, ctx->marking.get());
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
   if (s->cfg.use_depth_layer) {
     const int rd = store_reset(ctx, ctx->dlayer->store, ctx->copy_stream, ctx->dlayer->cfg.max_obstacle_distance);

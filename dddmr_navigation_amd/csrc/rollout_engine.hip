@@ -43,16 +43,15 @@ namespace {
 
 constexpr int kCloudBufs = 3;              // front / busy / free, see dddmr_rollout_ctx
 
+// The module states, defined in the headers included at the end.  Each frees what it owns when it dies, and dies only
+// while the context's device is current: in its module's create (after hipSetDevice) and in dddmr_rollout_destroy.
 struct MarkingState;                       // global-mode marking / clearing layer, marking_host.hip.h
-void marking_free(MarkingState* m);
 struct DepthMarkState;                     // the depth camera's selfMark, depth_mark.hip.h
-void depth_mark_free(DepthMarkState* s);
 struct DepthLayerState;                    // the depth camera layer's store, dGraph and lethal set, depth_layer.hip.h
-void depth_layer_free(DepthLayerState* s);
 struct StackState;                         // the perception stack over the two layers, perception_stack.hip.h
-void stack_free(StackState* s);
 struct MclState;                           // the particle filter's lidar likelihood, mcl_measure.hip.h
-void mcl_free(MclState* s);
+template <class T>
+using ModuleSlot = std::unique_ptr<T, LateDelete<T>>;   // enters its slot once complete (each module's create)
 
 // What a sensor source owns, beside its record in the context's SourceTable (sensor_sources.hip.h keeps the two in step).
 // Each state frees its memory when it dies: assigning an empty SourceOwned tears the source down (release_source).
@@ -161,11 +160,11 @@ struct dddmr_rollout_ctx {
   int64_t* slots_red = nullptr;      // [2 * comm_ranks] receive
   DevResult* local_result_dev = nullptr;
 
-  MarkingState* marking = nullptr;   // dddmr_rollout_marking_create
-  DepthMarkState* dmark = nullptr;   // dddmr_rollout_depth_mark_create
-  DepthLayerState* dlayer = nullptr; // dddmr_rollout_depth_layer_create
-  StackState* stack = nullptr;       // dddmr_rollout_stack_create (tick_mu)
-  MclState* mcl = nullptr;           // dddmr_rollout_mcl_create (tick_mu)
+  ModuleSlot<MarkingState> marking;  // dddmr_rollout_marking_create
+  ModuleSlot<DepthMarkState> dmark;  // dddmr_rollout_depth_mark_create
+  ModuleSlot<DepthLayerState> dlayer; // dddmr_rollout_depth_layer_create
+  ModuleSlot<StackState> stack;      // dddmr_rollout_stack_create (tick_mu)
+  ModuleSlot<MclState> mcl;          // dddmr_rollout_mcl_create (tick_mu)
 
   std::mutex tick_mu;
   std::mutex err_mu;        // last_error is written by tick and sensor threads alike
@@ -378,11 +377,11 @@ void dddmr_rollout_destroy(dddmr_rollout_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
-  if (ctx->marking) { marking_free(ctx->marking); ctx->marking = nullptr; }
-  if (ctx->dmark) { depth_mark_free(ctx->dmark); ctx->dmark = nullptr; }
-  if (ctx->stack) { stack_free(ctx->stack); ctx->stack = nullptr; }
-  if (ctx->dlayer) { depth_layer_free(ctx->dlayer); ctx->dlayer = nullptr; }
-  if (ctx->mcl) { mcl_free(ctx->mcl); ctx->mcl = nullptr; }
+  ctx->marking.reset();                  // (the modules go between the waits above and the streams' end below)
+  ctx->dmark.reset();
+  ctx->stack.reset();
+  ctx->dlayer.reset();
+  ctx->mcl.reset();
   if (ctx->comm) (void)rccl().comm_destroy(ctx->comm);
   dev_free(ctx->mem);
   perception_free(ctx->feed);
@@ -520,7 +519,7 @@ static int acquire_back(dddmr_rollout_ctx* ctx) {
 int dddmr_rollout_set_cloud(dddmr_rollout_ctx* ctx, const float* xyzi, size_t n_points,
                             size_t stride_bytes) {
   if (!ctx) return DDDMR_ERR_BAD_ARG;
-  if (n_points > 0 && (!xyzi || stride_bytes < 12 || stride_bytes % 4 != 0))
+  if (!cloud_arg_ok(xyzi, n_points, stride_bytes))
     return fail(ctx, DDDMR_ERR_BAD_ARG, "set_cloud: bad pointer/stride");
   if (n_points > ctx->cfg.max_points)
     return fail(ctx, DDDMR_ERR_CAPACITY, "set_cloud: %zu points > max_points %u", n_points, ctx->cfg.max_points);

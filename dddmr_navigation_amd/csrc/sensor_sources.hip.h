@@ -136,7 +136,7 @@ static int set_scan_impl(dddmr_rollout_ctx* ctx, int source, const float* xyz, s
   if (!ctx || !T_base_sensor || !T_gbl_base) return DDDMR_ERR_BAD_ARG;
   int rc;
   if (source >= 0 && (rc = source_arg(ctx, "set_scan", source)) != DDDMR_OK) return rc;
-  if (n_points > 0 && (!xyz || stride_bytes < 12 || stride_bytes % 4 != 0))
+  if (!cloud_arg_ok(xyz, n_points, stride_bytes))
     return fail(ctx, DDDMR_ERR_BAD_ARG, "set_scan: bad pointer/stride");
   if (n_points > ctx->cfg.max_points)
     return fail(ctx, DDDMR_ERR_CAPACITY, "set_scan: %zu points > max_points %u", n_points, ctx->cfg.max_points);
@@ -381,7 +381,7 @@ int dddmr_rollout_set_depth_frame(dddmr_rollout_ctx* ctx, int32_t source_id, con
                                   uint32_t* n_aggregate_points) {
   if (!ctx || !T_base_sensor || !T_gbl_base) return DDDMR_ERR_BAD_ARG;
   if (const int arc = source_arg(ctx, "set_depth_frame", source_id)) return arc;
-  if (n_points > 0 && (!xyz || stride_bytes < 12 || stride_bytes % 4 != 0))
+  if (!cloud_arg_ok(xyz, n_points, stride_bytes))
     return fail(ctx, DDDMR_ERR_BAD_ARG, "set_depth_frame: bad pointer/stride");
   return set_depth_impl(ctx, "set_depth_frame", source_id, xyz, n_points, nullptr, stride_bytes, T_base_sensor, T_gbl_base, stamp_ns,
                         nullptr, n_frame_points, n_source_points, n_aggregate_points);
@@ -481,7 +481,7 @@ int dddmr_rollout_set_lidar_sweep(dddmr_rollout_ctx* ctx, int32_t source_id, con
                                   double marking_height, uint32_t* n_segmented, uint32_t* n_source_points, uint32_t* n_aggregate_points) {
   if (!ctx || !T_base_sensor || !T_gbl_base) return DDDMR_ERR_BAD_ARG;
   if (const int arc = source_arg(ctx, "set_lidar_sweep", source_id)) return arc;
-  if (n_points > 0 && (!xyz || stride_bytes < 12 || stride_bytes % 4 != 0)) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_lidar_sweep: bad pointer/stride");
+  if (!cloud_arg_ok(xyz, n_points, stride_bytes)) return fail(ctx, DDDMR_ERR_BAD_ARG, "set_lidar_sweep: bad pointer/stride");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> prod(ctx->producer_mu);
   int rc = source_refused(ctx, "set_lidar_sweep", SourceOp::kFeedSweep, source_id);
@@ -759,7 +759,7 @@ static int depth_observation_grid(dddmr_rollout_ctx* ctx, DepthClear& d, size_t 
 int dddmr_rollout_depth_frustum_test(dddmr_rollout_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes,
                                      uint8_t* in_frustums_out, uint8_t* attach_out) {
   if (!ctx) return DDDMR_ERR_BAD_ARG;
-  if (n > 0 && (!xyz || stride_bytes < 12 || stride_bytes % 4 != 0)) return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_frustum_test: bad pointer/stride");
+  if (!cloud_arg_ok(xyz, n, stride_bytes)) return fail(ctx, DDDMR_ERR_BAD_ARG, "depth_frustum_test: bad pointer/stride");
   if (n > (1u << 28)) return fail(ctx, DDDMR_ERR_CAPACITY, "depth_frustum_test: %zu points", n);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> prod(ctx->producer_mu);

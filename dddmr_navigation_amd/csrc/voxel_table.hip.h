@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 // The reference is an x86-64 build without FMA contraction: every multiply and add below
@@ -143,9 +144,9 @@ inline size_t voxel_slots_for(size_t n) {
 }
 
 // Who owns device memory: the context (rollout_engine.hip), the marking store and every module state record what they
-// allocate in a DevAllocs of their own, where it is made; the owner's *_free walks the vector.  (Swapping a main array
-// with its _alt array leaves the set of pointers as it is.)  hipMalloc / hipFree and their pinned-host kin are called
-// here and nowhere else in the library.
+// allocate in a DevAllocs of their own, where it is made; the context's teardown walks its vector, a state's Owned (below)
+// walks its own when the state dies.  (Swapping a main array with its _alt array leaves the set of pointers as it is.)
+// hipMalloc / hipFree and their pinned-host kin are called here and nowhere else in the library.
 using DevAllocs = std::vector<void*>;
 template <class T>
 inline hipError_t dev_alloc(DevAllocs& owner, T** p, size_t count) {
@@ -232,6 +233,17 @@ struct Owned {
   void release() { dev_free(dev); host_free(host); }
 };
 
+// The deleter of a unique_ptr that is declared where the state's type is still incomplete (the context's module slots, a
+// sweep's features, the localiser's observation): instantiated at the end of the translation unit, which must have
+// included the state's header by then.
+template <class T>
+struct LateDelete {
+  void operator()(T* p) const {
+    static_assert(sizeof(T) > 0, "the state's header has to be included before the end of the translation unit");
+    delete p;
+  }
+};
+
 struct VoxelTable {
   unsigned char* mem = nullptr;   // the layout above over `slots` entries; a call may use only the first of them
   uint32_t* claimed = nullptr;    // [max_keys]
@@ -257,6 +269,27 @@ inline void pack_xyz_records(float* dst, const float* src, size_t n, size_t stri
     dst[3 * i + 1] = src[i * sf + 1];
     dst[3 * i + 2] = src[i * sf + 2];
   }
+}
+
+// n records narrowed to float4 (w = 0; one zero element without a point) with their box (zeros without a point)
+struct HostCloud {
+  std::vector<float4> pts;
+  float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+  HostCloud(const float* xyz, size_t n, size_t stride_bytes) : pts(std::max<size_t>(n, 1), make_float4(0.f, 0.f, 0.f, 0.f)) {
+    const size_t sf = stride_bytes / sizeof(float);
+    for (size_t i = 0; i < n; ++i) {
+      const float* p = xyz + i * sf;
+      pts[i] = make_float4(p[0], p[1], p[2], 0.f);
+      for (int a = 0; a < 3; ++a) {
+        lo[a] = i ? std::min(lo[a], p[a]) : p[a];
+        hi[a] = i ? std::max(hi[a], p[a]) : p[a];
+      }
+    }
+  }
+};
+// a caller's cloud argument: n records of at least x y z, float-aligned
+inline bool cloud_arg_ok(const float* xyz, size_t n, size_t stride_bytes) {
+  return !n || (xyz && stride_bytes >= 12 && stride_bytes % 4 == 0);
 }
 
 // Stages the caller's records for a kernel: 12- and 16-byte records go as they are, wider ones (PCL: 32 bytes) are
@@ -296,12 +329,16 @@ inline bool wait_seq(volatile uint32_t* word, uint32_t seq) {
 inline uint32_t next_seq(uint32_t& seq) { return ++seq ? seq : ++seq; }
 // The tail of a feed, behind its last launch: -5 when a launch failed, once what was enqueued before it has drained;
 // otherwise the call's one host wait, the bounded spin on the result's word and then the stream: -4 when that fails.
-inline int feed_wait(hipStream_t stream, volatile uint32_t* word, uint32_t seq) {
+// *waits, when given, grows by the waits made: one, two when the spin ran out.
+inline int feed_wait(hipStream_t stream, volatile uint32_t* word, uint32_t seq, uint32_t* waits = nullptr) {
   if (hipGetLastError() != hipSuccess) {
     (void)hipStreamSynchronize(stream);
     return -5;
   }
-  return !wait_seq(word, seq) && hipStreamSynchronize(stream) != hipSuccess ? -4 : 0;
+  if (waits) ++*waits;
+  if (wait_seq(word, seq)) return 0;
+  if (waits) ++*waits;
+  return hipStreamSynchronize(stream) != hipSuccess ? -4 : 0;
 }
 
 }  // namespace dddmr

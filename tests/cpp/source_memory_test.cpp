@@ -1,5 +1,5 @@
 // Who frees what in the sensor half of the library (csrc/voxel_table.hip.h's owners and the module states built on
-// them), on the CPU.  The HIP allocation calls are replaced by counting stand-ins on malloc, each of which can be told to
+// them) and in the marking layers' building blocks (csrc/marking_buffers.hip.h), on the CPU.  The HIP allocation calls are replaced by counting stand-ins on malloc, each of which can be told to
 // fail at the k-th call of a pass.  For every state: a clean alloc + free leaves nothing live; with the failure placed
 // at every call of the clean pass in turn, alloc reports failure and nothing stays live afterwards; and no pointer is
 // ever freed twice, nothing unknown is freed, no memset or copy leaves its allocation.  Then the two growing helpers
@@ -111,6 +111,7 @@ hipError_t fake_hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKin
 #include "depth_clear.hip.h"
 #include "depth_image.hip.h"
 #include "lidar_features.hip.h"
+#include "marking_buffers.hip.h"
 
 using namespace dddmr;
 
@@ -221,6 +222,22 @@ void check_states() {
         return features_alloc(*s.features);
       },
       sweep_free, sweep_reset);
+  // the marking layers' building blocks, at table 8, pool 4, n_ground 1, N = 2; freed by assigning an empty state
+  for (const bool depth : {false, true})               // the lidar layer's store has the fov flag, the depth layer's has heads
+    check_state<StoreBuf>(
+        depth ? "StoreBuf (depth layer)" : "StoreBuf (lidar layer)", [&](StoreBuf& b) { return store_alloc(b, 8, 4, 4, 1, !depth, depth); },
+        [](StoreBuf& b) { b = StoreBuf(); },
+        [](const StoreBuf& b) { return !b.s.keys && !b.s.fov_flag && !b.head.pc_n && !b.head_alt.pc_ofs && !b.pool_alt && !b.counters && b.table == 0; });
+  check_state<ClusterScratch>(
+      "ClusterScratch", [](ClusterScratch& c) { return cluster_scratch_alloc(c, 2, 4096); }, [](ClusterScratch& c) { c = ClusterScratch(); },
+      [](const ClusterScratch& c) { return !c.temp && !c.parent && !c.cl.vkey && !c.n_groups && c.temp_bytes == 0; });
+  struct OwnedGrid {                                   // a GridBuf allocates into its user's owner
+    GridBuf b;
+    Owned mem;
+  };
+  check_state<OwnedGrid>(
+      "GridBuf", [](OwnedGrid& g) { return grid_alloc(g.mem.dev, g.b, 8, 2); }, [](OwnedGrid& g) { g = OwnedGrid(); },
+      [](const OwnedGrid& g) { return !g.b.g.cell_start && !g.b.g.sorted && g.b.cap_cells == 0; });
 }
 
 // dev_realloc: grow, grow with every call of the grow failing in turn, free
