@@ -1,8 +1,12 @@
 """ctypes view of include/dddmr_rollout.h (the C-ABI of the rollout engine).
 
-The struct layouts here mirror the header field by field; `tests/test_capi_cpu.py`
-checks sizeof() of every struct against the compiled library
-(`dddmr_rollout_sizeof`) so the two cannot drift apart silently.
+The struct layouts here mirror the header field by field, and `SIGNATURES` is the one table of every function's
+return and argument types; `load_library()` binds it and `EXPORTED_SYMBOLS` is derived from it.  What keeps the two
+sides from drifting apart silently, all in `tests/test_capi_cpu.py`: sizeof() of every struct in `SIZEOF_STRUCTS`
+against the compiled library (`dddmr_rollout_sizeof`; absolute sizes are pinned in the features' own test files);
+every prototype of the header against `SIGNATURES` (name, parameter count, the kind of each parameter and of the return
+type -- field order and pointee types are not checked); the library's exports against the header.  What the classes
+on top hand to the library is pinned call by call in `tests/test_binding_trace_cpu.py`.
 
 There is deliberately no CPU fallback: if the HIP library is missing or no HIP
 device is usable, loading / `dddmr_rollout_create` fails loudly.
@@ -328,96 +332,119 @@ class RolloutDebug(C.Structure):
     ]
 
 
-# every symbol include/dddmr_rollout.h declares
-EXPORTED_SYMBOLS = (
-    "dddmr_rollout_create",
-    "dddmr_rollout_destroy",
-    "dddmr_rollout_set_cloud",
-    "dddmr_rollout_set_scan",
-    "dddmr_rollout_set_stitcher",
-    "dddmr_rollout_get_cloud",
-    "dddmr_rollout_set_prune_plan",
-    "dddmr_rollout_samples",
-    "dddmr_rollout_tick",
-    "dddmr_rollout_tick_begin",
-    "dddmr_rollout_tick_end",
-    "dddmr_rollout_resolve",
-    "dddmr_rollout_winner_words",
-    "dddmr_rollout_resolve_words",
-    "dddmr_rollout_get_debug",
-    "dddmr_rollout_heading_rows",
-    "dddmr_rollout_fused_walk",
-    "dddmr_rollout_get_best_poses",
-    "dddmr_rollout_get_best_cuboids",
-    "dddmr_rollout_get_pose_arrays",
-    "dddmr_rollout_path_blocked",
-    "dddmr_rollout_pack_key",
-    "dddmr_rollout_key_index",
-    "dddmr_rollout_comm_unique_id",
-    "dddmr_rollout_comm_init",
-    "dddmr_rollout_comm_destroy",
-    "dddmr_rollout_comm_ranks",
-    "dddmr_rollout_device_count",
-    "dddmr_rollout_comm_loopback",
-    "dddmr_rollout_comm_loopback_set_peer",
-    "dddmr_rollout_marking_create",
-    "dddmr_rollout_marking_update",
-    "dddmr_rollout_marking_reset",
-    "dddmr_rollout_marking_get_voxels",
-    "dddmr_rollout_marking_get_points",
-    "dddmr_rollout_marking_get_dgraph",
-    "dddmr_rollout_marking_get_lethal",
-    "dddmr_rollout_marking_route_counts",
-    "dddmr_rollout_set_scan_source",
-    "dddmr_rollout_set_stitcher_source",
-    "dddmr_rollout_set_depth_source",
-    "dddmr_rollout_set_depth_frame",
-    "dddmr_rollout_set_depth_image_source",
-    "dddmr_rollout_set_depth_image",
-    "dddmr_rollout_get_depth_image_cloud",
-    "dddmr_rollout_set_lidar_sweep_source",
-    "dddmr_rollout_set_lidar_sweep",
-    "dddmr_rollout_get_lidar_sweep_cloud",
-    "dddmr_rollout_get_lidar_sweep_image",
-    "dddmr_rollout_set_lidar_sweep_features",
-    "dddmr_rollout_get_lidar_sweep_segmented",
-    "dddmr_rollout_get_lidar_sweep_features",
-    "dddmr_rollout_set_depth_frustum",
-    "dddmr_rollout_get_depth_frustum",
-    "dddmr_rollout_depth_frustum_test",
-    "dddmr_rollout_depth_clear_verdicts",
-    "dddmr_rollout_depth_clear_launches",
-    "dddmr_rollout_depth_mark_create",
-    "dddmr_rollout_depth_mark_clusters",
-    "dddmr_rollout_depth_layer_create",
-    "dddmr_rollout_depth_layer_update",
-    "dddmr_rollout_depth_layer_reset",
-    "dddmr_rollout_depth_layer_get_voxels",
-    "dddmr_rollout_depth_layer_get_clusters",
-    "dddmr_rollout_depth_layer_get_dgraph",
-    "dddmr_rollout_depth_layer_get_lethal",
-    "dddmr_rollout_stack_create",
-    "dddmr_rollout_stack_set_host_layer",
-    "dddmr_rollout_stack_update",
-    "dddmr_rollout_stack_get_changes",
-    "dddmr_rollout_stack_get_min_dgraph",
-    "dddmr_rollout_stack_get_lethal_mask",
-    "dddmr_rollout_stack_get_lethal_nodes",
-    "dddmr_rollout_stack_reset",
-    "dddmr_rollout_mcl_create",
-    "dddmr_rollout_mcl_set_map",
-    "dddmr_rollout_mcl_measure",
-    "dddmr_rollout_mcl_get_terms",
-    "dddmr_rollout_mcl_set_observation_config",
-    "dddmr_rollout_mcl_prepare",
-    "dddmr_rollout_mcl_prepare_from_sweep",
-    "dddmr_rollout_mcl_get_observation",
-    "dddmr_rollout_mcl_measure_prepared",
-    "dddmr_rollout_stream_ceiling",
-    "dddmr_rollout_selftest_sincos",
-    "dddmr_rollout_last_error",
-    "dddmr_rollout_version",
+# the structs dddmr_rollout_sizeof knows, in its order (rollout_engine.hip: case 0 .. 22)
+SIZEOF_STRUCTS = (
+    CriticConfig, TheoryConfig, RolloutConfig, TickInput, RolloutResult, RolloutDebug, MarkingConfig, MarkingStats,
+    DepthSourceConfig, DepthImageConfig, DepthFrustumConfig, DepthMarkConfig, DepthMarkStats, DepthLayerConfig,
+    DepthLayerStats, StackConfig, StackStats, LidarSweepConfig, MclConfig, MclStats, LidarFeaturesConfig,
+    MclObservationConfig, MclObservationStats,
 )
+
+_P = C.POINTER
+_int, _i32, _u32, _i64, _sz, _dbl, _str = C.c_int, C.c_int32, C.c_uint32, C.c_int64, C.c_size_t, C.c_double, C.c_char_p
+_ctx = _vp = C.c_void_p
+_pd, _pu, _pn, _pi64 = _P(_dbl), _P(_u32), _P(_sz), _P(_i64)
+_cloud = [_vp, _sz, _sz]                      # records, count, stride in bytes
+_get = (_int, [_ctx, _vp, _sz, _pn])          # the two-call getter: buffer, capacity, count
+_get_of = (_int, [_ctx, _i32, _vp, _sz, _pn])     # ... of a source
+_fixed = (_int, [_ctx, _vp, _sz])             # n values into a buffer (also set_prune_plan)
+_plain = (_int, [_ctx])
+
+# name without the dddmr_rollout_ prefix -> (restype, argtypes), in the header's order
+_TABLE = {
+    "create": (_int, [_P(RolloutConfig), _P(_ctx)]),
+    "destroy": (None, [_ctx]),
+    "set_cloud": (_int, [_ctx] + _cloud),
+    "set_scan": (_int, [_ctx] + _cloud + [_pd, _pd, _dbl, _dbl, _pu]),
+    "set_stitcher": (_int, [_ctx, _i32]),
+    "get_cloud": _get,
+    "set_prune_plan": _fixed,
+    "samples": (_int, [_ctx, _str, _P(TickInput), _vp, _sz, _pn]),
+    "tick": (_int, [_ctx, _str, _P(TickInput), _P(RolloutResult)]),
+    "tick_begin": (_int, [_ctx, _str, _P(TickInput)]),
+    "tick_end": (_int, [_ctx, _P(RolloutResult)]),
+    "resolve": (_int, [_ctx, _i64, _P(RolloutResult)]),
+    "winner_words": (None, [_P(RolloutResult), _pi64]),
+    "resolve_words": (_int, [_ctx, _pi64, _i32, _P(RolloutResult)]),
+    "get_debug": (_int, [_ctx, _P(RolloutDebug)]),
+    "heading_rows": _plain,
+    "fused_walk": _plain,
+    "get_best_poses": _get,
+    "get_best_cuboids": _get,
+    "get_pose_arrays": _get_of,
+    "path_blocked": (_int, [_ctx, _vp, _sz, _dbl, _pd, _P(_i32), _vp]),
+    "pack_key": (_i64, [_dbl, _u32]),
+    "key_index": (_i32, [_i64]),
+    "comm_unique_id": (_int, [_vp]),
+    "comm_init": (_int, [_ctx, _vp, _i32, _i32]),
+    "comm_destroy": _plain,
+    "comm_ranks": (_int, [_ctx, _P(_i32)]),
+    "device_count": (_int, [_P(_i32)]),
+    "comm_loopback": _plain,
+    "comm_loopback_set_peer": (_int, [_ctx, _i32, _pi64]),
+    "marking_create": (_int, [_ctx, _P(MarkingConfig)] + _cloud + _cloud),
+    "marking_update": (_int, [_ctx, _pd, _pd, _P(MarkingStats)]),
+    "marking_reset": _plain,
+    "marking_get_voxels": _get,
+    "marking_get_points": (_int, [_ctx, _vp, _vp, _sz, _pn]),
+    "marking_get_dgraph": _fixed,
+    "marking_get_lethal": _fixed,
+    "marking_route_counts": (_int, [_ctx, _pu, _pu, _pu]),
+    "set_scan_source": (_int, [_ctx, _i32] + _cloud + [_pd, _pd, _dbl, _dbl, _pu, _pu]),
+    "set_stitcher_source": (_int, [_ctx, _i32, _i32]),
+    "set_depth_source": (_int, [_ctx, _i32, _P(DepthSourceConfig)]),
+    "set_depth_frame": (_int, [_ctx, _i32] + _cloud + [_pd, _pd, _i64, _pu, _pu, _pu]),
+    "set_depth_image_source": (_int, [_ctx, _i32, _P(DepthSourceConfig), _P(DepthImageConfig)]),
+    "set_depth_image": (_int, [_ctx, _i32, _vp, _sz, _pd, _pd, _i64, _pu, _pu, _pu, _pu]),
+    "get_depth_image_cloud": _get_of,
+    "set_lidar_sweep_source": (_int, [_ctx, _i32, _P(LidarSweepConfig)]),
+    "set_lidar_sweep": (_int, [_ctx, _i32] + _cloud + [_pd, _pd, _dbl, _dbl, _pu, _pu, _pu]),
+    "get_lidar_sweep_cloud": _get_of,
+    "get_lidar_sweep_image": (_int, [_ctx, _i32, _vp, _vp, _vp, _sz]),
+    "set_lidar_sweep_features": (_int, [_ctx, _i32, _P(LidarFeaturesConfig)]),
+    "get_lidar_sweep_segmented": (_int, [_ctx, _i32] + [_vp] * 6 + [_sz, _pn]),
+    "get_lidar_sweep_features": (_int, [_ctx, _i32, _int, _vp, _vp, _sz, _pn]),
+    "set_depth_frustum": (_int, [_ctx, _i32, _P(DepthFrustumConfig), _pd]),
+    "get_depth_frustum": (_int, [_ctx, _i32, _vp, _vp, _vp, _vp]),
+    "depth_frustum_test": (_int, [_ctx] + _cloud + [_vp, _vp]),
+    "depth_clear_verdicts": (_int, [_ctx, _dbl, _dbl, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "depth_clear_launches": (_int, [_ctx, _pu]),
+    "depth_mark_create": (_int, [_ctx, _P(DepthMarkConfig)] + _cloud + _cloud),
+    "depth_mark_clusters": (_int, [_ctx, _pd, _sz, _sz] + [_vp] * 6 + [_P(DepthMarkStats)]),
+    "depth_layer_create": (_int, [_ctx, _P(DepthLayerConfig)] + _cloud + _cloud),
+    "depth_layer_update": (_int, [_ctx, _pd, _P(DepthLayerStats)]),
+    "depth_layer_reset": _plain,
+    "depth_layer_get_voxels": _get,
+    "depth_layer_get_clusters": (_int, [_ctx, _vp, _vp, _vp, _sz, _sz, _pn, _pn]),
+    "depth_layer_get_dgraph": _fixed,
+    "depth_layer_get_lethal": _fixed,
+    "stack_create": (_int, [_ctx, _P(StackConfig)]),
+    "stack_set_host_layer": (_int, [_ctx, _i32, _vp]),
+    "stack_update": (_int, [_ctx, _pd, _pd, _P(StackStats)]),
+    "stack_get_changes": (_int, [_ctx, _vp, _vp, _vp, _sz, _pn]),
+    "stack_get_min_dgraph": _fixed,
+    "stack_get_lethal_mask": _fixed,
+    "stack_get_lethal_nodes": _get,
+    "stack_reset": _plain,
+    "mcl_create": (_int, [_ctx, _P(MclConfig)]),
+    "mcl_set_map": (_int, [_ctx] + _cloud + [_vp, _vp, _sz, _sz, _sz]),
+    "mcl_measure": (_int, [_ctx, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _P(MclStats)]),
+    "mcl_get_terms": (_int, [_ctx] + [_vp] * 5 + [_sz]),
+    "mcl_set_observation_config": (_int, [_ctx, _P(MclObservationConfig)]),
+    "mcl_prepare": (_int, [_ctx] + _cloud + _cloud + [_pd, _P(MclObservationStats)]),
+    "mcl_prepare_from_sweep": (_int, [_ctx, _i32, _pd, _P(MclObservationStats)]),
+    "mcl_get_observation": (_int, [_ctx, _vp, _sz, _pn, _vp, _sz, _pn, _vp, _sz]),
+    "mcl_measure_prepared": (_int, [_ctx, _vp, _sz, _vp, _vp, _P(MclStats)]),
+    "stream_ceiling": (_int, [_ctx, _sz, _i32, _pd, _pd]),
+    "selftest_sincos": (_int, [_ctx, _vp, _sz, _vp, _vp]),
+    "last_error": (_str, [_ctx]),
+    "version": (_str, []),
+    "sizeof": (_sz, [_int]),                  # the layout self-check of the CPU tests
+}
+SIGNATURES = {"dddmr_rollout_" + name: sig for name, sig in _TABLE.items()}
+NOT_IN_HEADER = ("dddmr_rollout_sizeof",)
+# every symbol include/dddmr_rollout.h declares
+EXPORTED_SYMBOLS = tuple(name for name in SIGNATURES if name not in NOT_IN_HEADER)
 
 _LIB_NAME = "libdddmr_rollout.so"
 _lib = None
@@ -430,7 +457,9 @@ def library_path() -> str:
 
 
 def load_library() -> C.CDLL:
-    """Load the HIP engine.  Raises (never falls back) if it is not built."""
+    """Load the HIP engine and bind SIGNATURES.  Raises (never falls back) if it is not built.  The shipped library
+    must export every entry; one that DDDMR_LIB_NAME selects (a diagnostic build, a measurement tool's build of an older
+    commit) may lack some, and calling one of those raises AttributeError."""
     global _lib
     if _lib is not None:
         return _lib
@@ -441,216 +470,15 @@ def load_library() -> C.CDLL:
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the rollout engine."
         )
     lib = C.CDLL(path)
-    ctx_p = C.c_void_p
-    lib.dddmr_rollout_create.argtypes = [C.POINTER(RolloutConfig), C.POINTER(ctx_p)]
-    lib.dddmr_rollout_create.restype = C.c_int
-    lib.dddmr_rollout_destroy.argtypes = [ctx_p]
-    lib.dddmr_rollout_destroy.restype = None
-    lib.dddmr_rollout_set_cloud.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_size_t]
-    lib.dddmr_rollout_set_cloud.restype = C.c_int
-    lib.dddmr_rollout_set_scan.argtypes = [
-        ctx_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double),
-        C.c_double, C.c_double, C.POINTER(C.c_uint32)]
-    lib.dddmr_rollout_set_scan.restype = C.c_int
-    lib.dddmr_rollout_set_stitcher.argtypes = [ctx_p, C.c_int32]
-    lib.dddmr_rollout_set_stitcher.restype = C.c_int
-    lib.dddmr_rollout_get_cloud.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    lib.dddmr_rollout_get_cloud.restype = C.c_int
-    lib.dddmr_rollout_set_prune_plan.argtypes = [ctx_p, C.c_void_p, C.c_size_t]
-    lib.dddmr_rollout_set_prune_plan.restype = C.c_int
-    lib.dddmr_rollout_samples.argtypes = [ctx_p, C.c_char_p, C.POINTER(TickInput), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    lib.dddmr_rollout_samples.restype = C.c_int
-    lib.dddmr_rollout_tick.argtypes = [ctx_p, C.c_char_p, C.POINTER(TickInput), C.POINTER(RolloutResult)]
-    lib.dddmr_rollout_tick.restype = C.c_int
-    lib.dddmr_rollout_tick_begin.argtypes = [ctx_p, C.c_char_p, C.POINTER(TickInput)]
-    lib.dddmr_rollout_tick_begin.restype = C.c_int
-    lib.dddmr_rollout_tick_end.argtypes = [ctx_p, C.POINTER(RolloutResult)]
-    lib.dddmr_rollout_tick_end.restype = C.c_int
-    lib.dddmr_rollout_resolve.argtypes = [ctx_p, C.c_int64, C.POINTER(RolloutResult)]
-    lib.dddmr_rollout_resolve.restype = C.c_int
-    lib.dddmr_rollout_winner_words.argtypes = [C.POINTER(RolloutResult), C.POINTER(C.c_int64)]
-    lib.dddmr_rollout_winner_words.restype = None
-    lib.dddmr_rollout_resolve_words.argtypes = [ctx_p, C.POINTER(C.c_int64), C.c_int32, C.POINTER(RolloutResult)]
-    lib.dddmr_rollout_resolve_words.restype = C.c_int
-    lib.dddmr_rollout_get_debug.argtypes = [ctx_p, C.POINTER(RolloutDebug)]
-    lib.dddmr_rollout_get_debug.restype = C.c_int
-    # (a library built from an older commit, loaded through DDDMR_LIB_NAME by the measurement jobs, has no such entry)
-    if hasattr(lib, "dddmr_rollout_heading_rows"):
-        lib.dddmr_rollout_heading_rows.argtypes = [ctx_p]
-        lib.dddmr_rollout_heading_rows.restype = C.c_int
-    if hasattr(lib, "dddmr_rollout_fused_walk"):
-        lib.dddmr_rollout_fused_walk.argtypes = [ctx_p]
-        lib.dddmr_rollout_fused_walk.restype = C.c_int
-    lib.dddmr_rollout_get_best_poses.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    lib.dddmr_rollout_get_best_poses.restype = C.c_int
-    lib.dddmr_rollout_get_best_cuboids.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    lib.dddmr_rollout_get_best_cuboids.restype = C.c_int
-    lib.dddmr_rollout_get_pose_arrays.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    lib.dddmr_rollout_get_pose_arrays.restype = C.c_int
-    lib.dddmr_rollout_path_blocked.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_double, C.POINTER(C.c_double),
-                                               C.POINTER(C.c_int32), C.c_void_p]
-    lib.dddmr_rollout_path_blocked.restype = C.c_int
-    lib.dddmr_rollout_pack_key.argtypes = [C.c_double, C.c_uint32]
-    lib.dddmr_rollout_pack_key.restype = C.c_int64
-    lib.dddmr_rollout_key_index.argtypes = [C.c_int64]
-    lib.dddmr_rollout_key_index.restype = C.c_int32
-    lib.dddmr_rollout_comm_unique_id.argtypes = [C.c_void_p]
-    lib.dddmr_rollout_comm_unique_id.restype = C.c_int
-    lib.dddmr_rollout_comm_init.argtypes = [ctx_p, C.c_void_p, C.c_int32, C.c_int32]
-    lib.dddmr_rollout_comm_init.restype = C.c_int
-    lib.dddmr_rollout_comm_destroy.argtypes = [ctx_p]
-    lib.dddmr_rollout_comm_destroy.restype = C.c_int
-    lib.dddmr_rollout_device_count.argtypes = [C.POINTER(C.c_int32)]
-    lib.dddmr_rollout_device_count.restype = C.c_int
-    lib.dddmr_rollout_comm_ranks.argtypes = [ctx_p, C.POINTER(C.c_int32)]
-    lib.dddmr_rollout_comm_ranks.restype = C.c_int
-    lib.dddmr_rollout_comm_loopback.argtypes = [ctx_p]
-    lib.dddmr_rollout_comm_loopback.restype = C.c_int
-    lib.dddmr_rollout_comm_loopback_set_peer.argtypes = [ctx_p, C.c_int32, C.POINTER(C.c_int64)]
-    lib.dddmr_rollout_comm_loopback_set_peer.restype = C.c_int
-    lib.dddmr_rollout_marking_create.argtypes = [ctx_p, C.POINTER(MarkingConfig), C.c_void_p, C.c_size_t, C.c_size_t,
-                                                 C.c_void_p, C.c_size_t, C.c_size_t]
-    lib.dddmr_rollout_marking_create.restype = C.c_int
-    lib.dddmr_rollout_marking_update.argtypes = [ctx_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(MarkingStats)]
-    lib.dddmr_rollout_marking_update.restype = C.c_int
-    lib.dddmr_rollout_marking_reset.argtypes = [ctx_p]
-    lib.dddmr_rollout_marking_reset.restype = C.c_int
-    lib.dddmr_rollout_marking_get_voxels.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    lib.dddmr_rollout_marking_get_voxels.restype = C.c_int
-    lib.dddmr_rollout_marking_get_points.argtypes = [ctx_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    lib.dddmr_rollout_marking_get_points.restype = C.c_int
-    lib.dddmr_rollout_marking_get_dgraph.argtypes = [ctx_p, C.c_void_p, C.c_size_t]
-    lib.dddmr_rollout_marking_get_dgraph.restype = C.c_int
-    lib.dddmr_rollout_marking_get_lethal.argtypes = [ctx_p, C.c_void_p, C.c_size_t]
-    lib.dddmr_rollout_marking_get_lethal.restype = C.c_int
-    lib.dddmr_rollout_marking_route_counts.argtypes = [ctx_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    lib.dddmr_rollout_marking_route_counts.restype = C.c_int
-    lib.dddmr_rollout_set_scan_source.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_double),
-                                                  C.POINTER(C.c_double), C.c_double, C.c_double, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    lib.dddmr_rollout_set_scan_source.restype = C.c_int
-    lib.dddmr_rollout_set_stitcher_source.argtypes = [ctx_p, C.c_int32, C.c_int32]
-    lib.dddmr_rollout_set_stitcher_source.restype = C.c_int
-    lib.dddmr_rollout_set_depth_source.argtypes = [ctx_p, C.c_int32, C.POINTER(DepthSourceConfig)]
-    lib.dddmr_rollout_set_depth_source.restype = C.c_int
-    lib.dddmr_rollout_set_depth_frame.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_double),
-                                                  C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
-                                                  C.POINTER(C.c_uint32)]
-    lib.dddmr_rollout_set_depth_frame.restype = C.c_int
-    lib.dddmr_rollout_set_depth_image_source.argtypes = [ctx_p, C.c_int32, C.POINTER(DepthSourceConfig), C.POINTER(DepthImageConfig)]
-    lib.dddmr_rollout_set_depth_image_source.restype = C.c_int
-    lib.dddmr_rollout_set_depth_image.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                                  C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
-                                                  C.POINTER(C.c_uint32)]
-    lib.dddmr_rollout_set_depth_image.restype = C.c_int
-    lib.dddmr_rollout_get_depth_image_cloud.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    lib.dddmr_rollout_get_depth_image_cloud.restype = C.c_int
-    # (a library built from an older commit, loaded through DDDMR_LIB_NAME by tools/lidar_sweep_bench.py, has no sweep entries)
-    if hasattr(lib, "dddmr_rollout_set_lidar_sweep_source"):
-        lib.dddmr_rollout_set_lidar_sweep_source.argtypes = [ctx_p, C.c_int32, C.POINTER(LidarSweepConfig)]
-        lib.dddmr_rollout_set_lidar_sweep_source.restype = C.c_int
-        lib.dddmr_rollout_set_lidar_sweep.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_double),
-                                                      C.POINTER(C.c_double), C.c_double, C.c_double, C.POINTER(C.c_uint32),
-                                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        lib.dddmr_rollout_set_lidar_sweep.restype = C.c_int
-        lib.dddmr_rollout_get_lidar_sweep_cloud.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-        lib.dddmr_rollout_get_lidar_sweep_cloud.restype = C.c_int
-        lib.dddmr_rollout_get_lidar_sweep_image.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-        lib.dddmr_rollout_get_lidar_sweep_image.restype = C.c_int
-    if hasattr(lib, "dddmr_rollout_set_lidar_sweep_features"):         # (absent from a library built from an older commit)
-        lib.dddmr_rollout_set_lidar_sweep_features.argtypes = [ctx_p, C.c_int32, C.POINTER(LidarFeaturesConfig)]
-        lib.dddmr_rollout_set_lidar_sweep_features.restype = C.c_int
-        lib.dddmr_rollout_get_lidar_sweep_segmented.argtypes = [ctx_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_size_t, C.POINTER(C.c_size_t)]
-        lib.dddmr_rollout_get_lidar_sweep_segmented.restype = C.c_int
-        lib.dddmr_rollout_get_lidar_sweep_features.argtypes = [ctx_p, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
-                                                               C.POINTER(C.c_size_t)]
-        lib.dddmr_rollout_get_lidar_sweep_features.restype = C.c_int
-    lib.dddmr_rollout_set_depth_frustum.argtypes = [ctx_p, C.c_int32, C.POINTER(DepthFrustumConfig), C.POINTER(C.c_double)]
-    lib.dddmr_rollout_set_depth_frustum.restype = C.c_int
-    lib.dddmr_rollout_get_depth_frustum.argtypes = [ctx_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.dddmr_rollout_get_depth_frustum.restype = C.c_int
-    lib.dddmr_rollout_depth_frustum_test.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.dddmr_rollout_depth_frustum_test.restype = C.c_int
-    lib.dddmr_rollout_depth_clear_verdicts.argtypes = [ctx_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                                       C.c_void_p, C.c_void_p]
-    lib.dddmr_rollout_depth_clear_verdicts.restype = C.c_int
-    lib.dddmr_rollout_depth_clear_launches.argtypes = [ctx_p, C.POINTER(C.c_uint32)]
-    lib.dddmr_rollout_depth_clear_launches.restype = C.c_int
-    lib.dddmr_rollout_depth_mark_create.argtypes = [ctx_p, C.POINTER(DepthMarkConfig), C.c_void_p, C.c_size_t, C.c_size_t,
-                                                    C.c_void_p, C.c_size_t, C.c_size_t]
-    lib.dddmr_rollout_depth_mark_create.restype = C.c_int
-    lib.dddmr_rollout_depth_mark_clusters.argtypes = [ctx_p, C.POINTER(C.c_double), C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
-                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DepthMarkStats)]
-    lib.dddmr_rollout_depth_mark_clusters.restype = C.c_int
-    lib.dddmr_rollout_depth_layer_create.argtypes = [ctx_p, C.POINTER(DepthLayerConfig), C.c_void_p, C.c_size_t, C.c_size_t,
-                                                     C.c_void_p, C.c_size_t, C.c_size_t]
-    lib.dddmr_rollout_depth_layer_create.restype = C.c_int
-    lib.dddmr_rollout_depth_layer_update.argtypes = [ctx_p, C.POINTER(C.c_double), C.POINTER(DepthLayerStats)]
-    lib.dddmr_rollout_depth_layer_update.restype = C.c_int
-    lib.dddmr_rollout_depth_layer_reset.argtypes = [ctx_p]
-    lib.dddmr_rollout_depth_layer_reset.restype = C.c_int
-    lib.dddmr_rollout_depth_layer_get_voxels.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    lib.dddmr_rollout_depth_layer_get_voxels.restype = C.c_int
-    lib.dddmr_rollout_depth_layer_get_clusters.argtypes = [ctx_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
-                                                           C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-    lib.dddmr_rollout_depth_layer_get_clusters.restype = C.c_int
-    lib.dddmr_rollout_depth_layer_get_dgraph.argtypes = [ctx_p, C.c_void_p, C.c_size_t]
-    lib.dddmr_rollout_depth_layer_get_dgraph.restype = C.c_int
-    lib.dddmr_rollout_depth_layer_get_lethal.argtypes = [ctx_p, C.c_void_p, C.c_size_t]
-    lib.dddmr_rollout_depth_layer_get_lethal.restype = C.c_int
-    # (a library built from an older commit, which the measurement tools load through DDDMR_LIB_NAME, has no stack entries;
-    # build() and tests/test_capi_cpu.py check that the shipped library exports every symbol, and calling a missing one raises)
-    if hasattr(lib, "dddmr_rollout_stack_create"):
-        lib.dddmr_rollout_stack_create.argtypes = [ctx_p, C.POINTER(StackConfig)]
-        lib.dddmr_rollout_stack_create.restype = C.c_int
-        lib.dddmr_rollout_stack_set_host_layer.argtypes = [ctx_p, C.c_int32, C.c_void_p]
-        lib.dddmr_rollout_stack_set_host_layer.restype = C.c_int
-        lib.dddmr_rollout_stack_update.argtypes = [ctx_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(StackStats)]
-        lib.dddmr_rollout_stack_update.restype = C.c_int
-        lib.dddmr_rollout_stack_get_changes.argtypes = [ctx_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-        lib.dddmr_rollout_stack_get_changes.restype = C.c_int
-        lib.dddmr_rollout_stack_get_min_dgraph.argtypes = [ctx_p, C.c_void_p, C.c_size_t]
-        lib.dddmr_rollout_stack_get_min_dgraph.restype = C.c_int
-        lib.dddmr_rollout_stack_get_lethal_mask.argtypes = [ctx_p, C.c_void_p, C.c_size_t]
-        lib.dddmr_rollout_stack_get_lethal_mask.restype = C.c_int
-        lib.dddmr_rollout_stack_get_lethal_nodes.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-        lib.dddmr_rollout_stack_get_lethal_nodes.restype = C.c_int
-        lib.dddmr_rollout_stack_reset.argtypes = [ctx_p]
-        lib.dddmr_rollout_stack_reset.restype = C.c_int
-    # (a library built from an older commit, loaded through DDDMR_LIB_NAME by the measurement tools, has no mcl entries)
-    if hasattr(lib, "dddmr_rollout_mcl_create"):
-        lib.dddmr_rollout_mcl_create.argtypes = [ctx_p, C.POINTER(MclConfig)]
-        lib.dddmr_rollout_mcl_create.restype = C.c_int
-        lib.dddmr_rollout_mcl_set_map.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
-                                                  C.c_size_t, C.c_size_t]
-        lib.dddmr_rollout_mcl_set_map.restype = C.c_int
-        lib.dddmr_rollout_mcl_measure.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                                  C.c_void_p, C.c_void_p, C.POINTER(MclStats)]
-        lib.dddmr_rollout_mcl_measure.restype = C.c_int
-        lib.dddmr_rollout_mcl_get_terms.argtypes = [ctx_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-        lib.dddmr_rollout_mcl_get_terms.restype = C.c_int
-    if hasattr(lib, "dddmr_rollout_mcl_prepare"):
-        lib.dddmr_rollout_mcl_set_observation_config.argtypes = [ctx_p, C.POINTER(MclObservationConfig)]
-        lib.dddmr_rollout_mcl_set_observation_config.restype = C.c_int
-        lib.dddmr_rollout_mcl_prepare.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
-                                                  C.POINTER(C.c_double), C.POINTER(MclObservationStats)]
-        lib.dddmr_rollout_mcl_prepare.restype = C.c_int
-        lib.dddmr_rollout_mcl_prepare_from_sweep.argtypes = [ctx_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(MclObservationStats)]
-        lib.dddmr_rollout_mcl_prepare_from_sweep.restype = C.c_int
-        lib.dddmr_rollout_mcl_get_observation.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t,
-                                                          C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t]
-        lib.dddmr_rollout_mcl_get_observation.restype = C.c_int
-        lib.dddmr_rollout_mcl_measure_prepared.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(MclStats)]
-        lib.dddmr_rollout_mcl_measure_prepared.restype = C.c_int
-    lib.dddmr_rollout_stream_ceiling.argtypes = [ctx_p, C.c_size_t, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    lib.dddmr_rollout_stream_ceiling.restype = C.c_int
-    lib.dddmr_rollout_selftest_sincos.argtypes = [ctx_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.dddmr_rollout_selftest_sincos.restype = C.c_int
-    lib.dddmr_rollout_last_error.argtypes = [ctx_p]
-    lib.dddmr_rollout_last_error.restype = C.c_char_p
-    lib.dddmr_rollout_version.argtypes = []
-    lib.dddmr_rollout_version.restype = C.c_char_p
-    # not part of the public header: layout self-check used by the CPU tests
-    lib.dddmr_rollout_sizeof.argtypes = [C.c_int]
-    lib.dddmr_rollout_sizeof.restype = C.c_size_t
+    shipped = "DDDMR_LIB_NAME" not in os.environ
+    for name, (restype, argtypes) in SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            if shipped:
+                raise RuntimeError(f"{path} does not export {name}: rebuild it from this tree") from None
+            continue
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
+

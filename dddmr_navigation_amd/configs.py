@@ -9,6 +9,7 @@ import ctypes as C
 from typing import Iterable, Sequence
 
 from . import _capi as K
+from . import _marshal as M
 
 # Shipped robot cuboid (dddmr_local_planner/local_planner/config/local_planner_play_ground.yaml:13-21)
 _CUBOID = {
@@ -42,10 +43,7 @@ def theory(name: str, kind: int, critics: Sequence[K.CriticConfig], cuboid=None,
     """Build a TheoryConfig; unspecified fields take the plugin's
     declare_parameter defaults (dd_simple...cpp:47-134, omni_simple...cpp:47-158,
     dd_rotate_inplace_theory.cpp:47-129)."""
-    t = K.TheoryConfig()
-    t.name = name.encode()
-    t.kind = kind
-    defaults = dict(
+    t = M.struct_from(K.TheoryConfig, dict(
         use_motor_constraint=0,
         min_vel_x=0.01, max_vel_x=0.1,
         min_vel_y=-0.1, max_vel_y=0.1,
@@ -59,12 +57,9 @@ def theory(name: str, kind: int, critics: Sequence[K.CriticConfig], cuboid=None,
         sim_granularity=0.1, angular_sim_granularity=0.05,
         rotation_speed=0.4,
         bench_fixed_steps=0, bench_no_zero_insert=0,
-    )
-    defaults.update(kw)
-    for k, v in defaults.items():
-        if not hasattr(t, k):
-            raise KeyError(k)
-        setattr(t, k, v)
+    ), kw)
+    t.name = name.encode()
+    t.kind = kind
     verts = cuboid if cuboid is not None else cuboid_vertices()
     assert len(verts) == 8
     for i, v in enumerate(verts):

@@ -7,21 +7,16 @@ from __future__ import annotations
 import numpy as np
 
 from . import _capi as K
+from . import _marshal as M
 
 
 def shipped_config(**kw) -> K.DepthLayerConfig:
     """The depth camera block of the shipped perception_3d_global configuration, the plugin's defaults elsewhere."""
-    c = K.DepthLayerConfig()
-    d = dict(xy_resolution=0.05, height_resolution=0.05, marking_height=2.0, perception_window_size=5.0,
-             euclidean_cluster_extraction_tolerance=0.1, euclidean_cluster_extraction_min_cluster_size=1,
-             segmentation_ignore_ratio=0.2, inscribed_radius=0.5, inflation_radius=1.5, max_obstacle_distance=9999.0,
-             max_observation_points=1 << 16, max_markings=1 << 15, max_cluster_points=1 << 20)
-    d.update(kw)
-    for k, v in d.items():
-        if not hasattr(c, k) or k.startswith("reserved"):
-            raise KeyError(k)
-        setattr(c, k, v)
-    return c
+    return M.struct_from(K.DepthLayerConfig, dict(
+        xy_resolution=0.05, height_resolution=0.05, marking_height=2.0, perception_window_size=5.0,
+        euclidean_cluster_extraction_tolerance=0.1, euclidean_cluster_extraction_min_cluster_size=1,
+        segmentation_ignore_ratio=0.2, inscribed_radius=0.5, inflation_radius=1.5, max_obstacle_distance=9999.0,
+        max_observation_points=1 << 16, max_markings=1 << 15, max_cluster_points=1 << 20), kw)
 
 
 class DepthLayer:

@@ -17,6 +17,7 @@ from typing import Iterable, Optional
 import numpy as np
 
 from . import _capi as K
+from . import _marshal as M
 from . import configs
 
 
@@ -105,71 +106,67 @@ class LocalPlanner:
             msg = self._lib.dddmr_rollout_last_error(self._ctx)
             raise RolloutError(rc, msg.decode() if msg else "")
 
+    # -- how everything off the timed paths reaches the library (this class and the layer classes on top of it);
+    # -- tick, tick_begin / tick_end, set_cloud, set_scan, setPlan and the word exchange name their function themselves
+    def _rc(self, name: str, *args) -> int:
+        """dddmr_rollout_<name>(ctx, *args) -> its status, for the callers that store stats before they raise."""
+        return getattr(self._lib, "dddmr_rollout_" + name)(self._ctx, *args)
+
+    def _call(self, name: str, *args):
+        self._check(getattr(self._lib, "dddmr_rollout_" + name)(self._ctx, *args))
+
+    def _get(self, name: str, lead, *outs):
+        """A two-call getter dddmr_rollout_<name>(ctx, *lead, buffers..., capacity, count*): see _marshal.two_call."""
+        fn = getattr(self._lib, "dddmr_rollout_" + name)
+        return M.two_call(lambda *a: fn(self._ctx, *lead, *a), self._check, *outs)
+
+    def _fixed(self, name: str, n: int, dtype, as_bool: bool = False):
+        fn = getattr(self._lib, "dddmr_rollout_" + name)
+        return M.fixed(lambda *a: fn(self._ctx, *a), self._check, n, dtype, as_bool)
+
     # -- inputs ------------------------------------------------------------
     def set_cloud(self, cloud: np.ndarray):
         """Aggregate observation, [P, >=3] float32 rows (x y z [intensity ...])."""
-        cloud = np.ascontiguousarray(cloud, dtype=np.float32)
-        if cloud.ndim != 2 or (cloud.shape[0] and cloud.shape[1] < 3):
-            raise ValueError("cloud must be [P, >=3] float32")
-        stride = cloud.strides[0] if cloud.shape[0] else 16
-        self._check(self._lib.dddmr_rollout_set_cloud(self._ctx, cloud.ctypes.data_as(C.c_void_p),
-                                                      cloud.shape[0], stride))
+        _, p, n, stride = M.cloud(cloud, "cloud")
+        self._check(self._lib.dddmr_rollout_set_cloud(self._ctx, p, n, stride))
 
     def set_scan(self, scan_xyz: np.ndarray, T_base_sensor, T_gbl_base, perception_window_size: float,
                  marking_height: float) -> int:
         """Fused local-mode perception feed (cbSensor); returns the number of
         downsampled points now forming the aggregate observation."""
-        scan = np.ascontiguousarray(scan_xyz, dtype=np.float32)
-        if scan.ndim != 2 or (scan.shape[0] and scan.shape[1] < 3):
-            raise ValueError("scan must be [P, >=3] float32")
-        tbs = (C.c_double * 7)(*[float(v) for v in T_base_sensor])
-        tgb = (C.c_double * 7)(*[float(v) for v in T_gbl_base])
+        _, p, n, stride = M.cloud(scan_xyz, "scan")
         n_out = C.c_uint32(0)
-        stride = scan.strides[0] if scan.shape[0] else 12
-        self._check(self._lib.dddmr_rollout_set_scan(self._ctx, scan.ctypes.data_as(C.c_void_p), scan.shape[0],
-                                                     stride, tbs, tgb, perception_window_size, marking_height,
-                                                     C.byref(n_out)))
+        self._check(self._lib.dddmr_rollout_set_scan(self._ctx, p, n, stride, M.pose(T_base_sensor), M.pose(T_gbl_base),
+                                                     perception_window_size, marking_height, C.byref(n_out)))
         return int(n_out.value)
 
     def set_scan_source(self, source_id: int, scan_xyz: np.ndarray, T_base_sensor, T_gbl_base, perception_window_size: float,
                         marking_height: float):
         """One of several sensors (StackedPerception::aggregateObservations, stacked_perception.cpp:128-140): returns
         (points of this sensor's observation, points of the aggregate = all sensors' latest observations in source order)."""
-        scan = np.ascontiguousarray(scan_xyz, dtype=np.float32)
-        if scan.ndim != 2 or (scan.shape[0] and scan.shape[1] < 3):
-            raise ValueError("scan must be [P, >=3] float32")
-        tbs = (C.c_double * 7)(*[float(v) for v in T_base_sensor])
-        tgb = (C.c_double * 7)(*[float(v) for v in T_gbl_base])
+        _, p, n, stride = M.cloud(scan_xyz, "scan")
         n_src, n_all = C.c_uint32(0), C.c_uint32(0)
-        stride = scan.strides[0] if scan.shape[0] else 12
-        self._check(self._lib.dddmr_rollout_set_scan_source(self._ctx, int(source_id), scan.ctypes.data_as(C.c_void_p), scan.shape[0],
-                                                            stride, tbs, tgb, perception_window_size, marking_height,
-                                                            C.byref(n_src), C.byref(n_all)))
+        self._call("set_scan_source", int(source_id), p, n, stride, M.pose(T_base_sensor), M.pose(T_gbl_base),
+                   perception_window_size, marking_height, C.byref(n_src), C.byref(n_all))
         return int(n_src.value), int(n_all.value)
 
     def set_stitcher_source(self, source_id: int, stitcher_num: int):
-        self._check(self._lib.dddmr_rollout_set_stitcher_source(self._ctx, int(source_id), int(stitcher_num)))
+        self._call("set_stitcher_source", int(source_id), int(stitcher_num))
 
     def set_depth_source(self, source_id: int, min_obstacle_height: float, max_obstacle_height: float,
                          observation_persistence_ns: int = 0, max_frame_points: int = 848 * 480, max_frames: int = 1):
         """Make `source_id` a depth camera source (DepthCameraObservationBuffer's parameters); empties a configured one."""
         cfg = K.DepthSourceConfig(float(min_obstacle_height), float(max_obstacle_height), int(observation_persistence_ns),
                                   int(max_frame_points), int(max_frames))
-        self._check(self._lib.dddmr_rollout_set_depth_source(self._ctx, int(source_id), C.byref(cfg)))
+        self._call("set_depth_source", int(source_id), C.byref(cfg))
 
     def set_depth_frame(self, source_id: int, frame_xyz: np.ndarray, T_base_sensor, T_gbl_base, stamp_ns: int):
         """One depth frame through bufferCloud's local-mode steps (depth_camera_observation_buffer.cpp:78-187): returns
         (points of this frame's observation, points of the source's alive frames, points of the aggregate)."""
-        frame = np.ascontiguousarray(frame_xyz, dtype=np.float32)
-        if frame.ndim != 2 or (frame.shape[0] and frame.shape[1] < 3):
-            raise ValueError("frame must be [P, >=3] float32")
-        tbs = (C.c_double * 7)(*[float(v) for v in T_base_sensor])
-        tgb = (C.c_double * 7)(*[float(v) for v in T_gbl_base])
+        _, p, n, stride = M.cloud(frame_xyz, "frame")
         n_frame, n_src, n_all = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
-        stride = frame.strides[0] if frame.shape[0] else 12
-        self._check(self._lib.dddmr_rollout_set_depth_frame(self._ctx, int(source_id), frame.ctypes.data_as(C.c_void_p), frame.shape[0],
-                                                            stride, tbs, tgb, int(stamp_ns), C.byref(n_frame), C.byref(n_src),
-                                                            C.byref(n_all)))
+        self._call("set_depth_frame", int(source_id), p, n, stride, M.pose(T_base_sensor), M.pose(T_gbl_base), int(stamp_ns),
+                   C.byref(n_frame), C.byref(n_src), C.byref(n_all))
         return int(n_frame.value), int(n_src.value), int(n_all.value)
 
     def set_depth_image_source(self, source_id: int, min_obstacle_height: float, max_obstacle_height: float, width: int, height: int,
@@ -185,7 +182,7 @@ class LocalPlanner:
                                   int(max_frame_points), int(max_frames))
         icfg = K.DepthImageConfig(int(width), int(height), float(fx), float(fy), float(cx), float(cy), float(max_distance),
                                   float(leaf_size), int(sample_step), K.DEPTH_IMAGE_DROP_ZERO if drop_zero else 0)
-        self._check(self._lib.dddmr_rollout_set_depth_image_source(self._ctx, int(source_id), C.byref(cfg), C.byref(icfg)))
+        self._call("set_depth_image_source", int(source_id), C.byref(cfg), C.byref(icfg))
 
     def set_depth_image(self, source_id: int, depth_mm: np.ndarray, T_base_optical, T_gbl_base, stamp_ns: int):
         """One [height, width] uint16 millimetre image (rows may be padded: any array whose pixels of a row are adjacent is
@@ -196,23 +193,15 @@ class LocalPlanner:
             raise ValueError("depth image must be [height, width] uint16")
         if img.shape[1] > 1 and img.strides[1] != 2 or img.strides[0] < 2 * img.shape[1]:
             img = np.ascontiguousarray(img)
-        tbo = (C.c_double * 7)(*[float(v) for v in T_base_optical])
-        tgb = (C.c_double * 7)(*[float(v) for v in T_gbl_base])
         n_cam, n_frame, n_src, n_all = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
-        self._check(self._lib.dddmr_rollout_set_depth_image(self._ctx, int(source_id), img.ctypes.data_as(C.c_void_p), img.strides[0],
-                                                            tbo, tgb, int(stamp_ns), C.byref(n_cam), C.byref(n_frame),
-                                                            C.byref(n_src), C.byref(n_all)))
+        self._call("set_depth_image", int(source_id), M.ptr(img), img.strides[0], M.pose(T_base_optical), M.pose(T_gbl_base),
+                   int(stamp_ns), C.byref(n_cam), C.byref(n_frame), C.byref(n_src), C.byref(n_all))
         return int(n_cam.value), int(n_frame.value), int(n_src.value), int(n_all.value)
 
     def get_depth_image_cloud(self, source_id: int) -> np.ndarray:
         """The stage-one cloud of the source's latest image, [K,3] float32 in the optical frame (the node's
         point_cloud_from_depth topic)."""
-        n = C.c_size_t(0)
-        self._check(self._lib.dddmr_rollout_get_depth_image_cloud(self._ctx, int(source_id), None, 0, C.byref(n)))
-        out = np.zeros((max(n.value, 1), 3), dtype=np.float32)
-        self._check(self._lib.dddmr_rollout_get_depth_image_cloud(self._ctx, int(source_id), out.ctypes.data_as(C.c_void_p),
-                                                                  out.shape[0], C.byref(n)))
-        return out[: n.value]
+        return self._get("get_depth_image_cloud", (int(source_id),), ((3,), np.float32))[0]
 
     def set_lidar_sweep_source(self, source_id: int, num_vertical_scans: int, num_horizontal_scans: int,
                                vertical_angle_bottom: float, vertical_angle_top: float, ground_scan_index: int,
@@ -227,41 +216,28 @@ class LocalPlanner:
                                  float(vertical_angle_top), int(ground_scan_index), float(segment_theta),
                                  int(segment_valid_point_num), int(segment_valid_line_num), float(minimum_detection_range),
                                  float(maximum_detection_range), float(sensor_mount_angle), int(max_sweep_points), int(flags))
-        self._check(self._lib.dddmr_rollout_set_lidar_sweep_source(self._ctx, int(source_id), C.byref(cfg)))
+        self._call("set_lidar_sweep_source", int(source_id), C.byref(cfg))
 
     def set_lidar_sweep(self, source_id: int, sweep_xyz: np.ndarray, T_base_sensor, T_gbl_base, perception_window_size: float,
                         marking_height: float):
         """One raw sweep through ImageProjection::cloudHandler's front half and cbSensor: returns (stage-one points = what
         the node would publish on segmented_cloud_pure, points of this source's observation, points of the aggregate)."""
-        scan = np.ascontiguousarray(sweep_xyz, dtype=np.float32)
-        if scan.ndim != 2 or (scan.shape[0] and scan.shape[1] < 3):
-            raise ValueError("sweep must be [P, >=3] float32")
-        tbs = (C.c_double * 7)(*[float(v) for v in T_base_sensor])
-        tgb = (C.c_double * 7)(*[float(v) for v in T_gbl_base])
+        _, p, n, stride = M.cloud(sweep_xyz, "sweep")
         n_seg, n_src, n_all = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
-        stride = scan.strides[0] if scan.shape[0] else 12
-        self._check(self._lib.dddmr_rollout_set_lidar_sweep(self._ctx, int(source_id), scan.ctypes.data_as(C.c_void_p), scan.shape[0],
-                                                            stride, tbs, tgb, perception_window_size, marking_height,
-                                                            C.byref(n_seg), C.byref(n_src), C.byref(n_all)))
+        self._call("set_lidar_sweep", int(source_id), p, n, stride, M.pose(T_base_sensor), M.pose(T_gbl_base),
+                   perception_window_size, marking_height, C.byref(n_seg), C.byref(n_src), C.byref(n_all))
         return int(n_seg.value), int(n_src.value), int(n_all.value)
 
     def get_lidar_sweep_cloud(self, source_id: int) -> np.ndarray:
         """Stage one's cloud of the source's latest sweep, [K,4] float32: x y z in the pitch-removed frame and the segment
         label, in raster order (the topic segmented_cloud_pure)."""
-        n = C.c_size_t(0)
-        self._check(self._lib.dddmr_rollout_get_lidar_sweep_cloud(self._ctx, int(source_id), None, 0, C.byref(n)))
-        out = np.zeros((max(n.value, 1), 4), dtype=np.float32)
-        self._check(self._lib.dddmr_rollout_get_lidar_sweep_cloud(self._ctx, int(source_id), out.ctypes.data_as(C.c_void_p),
-                                                                  out.shape[0], C.byref(n)))
-        return out[: n.value]
+        return self._get("get_lidar_sweep_cloud", (int(source_id),), ((4,), np.float32))[0]
 
     def get_lidar_sweep_image(self, source_id: int, num_vertical_scans: int, num_horizontal_scans: int):
         """(range [V,H] float32 with FLT_MAX where empty, label [V,H] int32, ground [V,H] int8) of the latest sweep."""
         V, H = int(num_vertical_scans), int(num_horizontal_scans)
         rng, lab, gnd = np.zeros((V, H), np.float32), np.zeros((V, H), np.int32), np.zeros((V, H), np.int8)
-        self._check(self._lib.dddmr_rollout_get_lidar_sweep_image(self._ctx, int(source_id), rng.ctypes.data_as(C.c_void_p),
-                                                                  lab.ctypes.data_as(C.c_void_p), gnd.ctypes.data_as(C.c_void_p),
-                                                                  V * H))
+        self._call("get_lidar_sweep_image", int(source_id), M.ptr(rng), M.ptr(lab), M.ptr(gnd), V * H)
         return rng, lab, gnd
 
     def set_lidar_sweep_features(self, source_id: int, edge_threshold: float = 0.1, surf_threshold: float = 0.1, T_out=None,
@@ -270,68 +246,48 @@ class LocalPlanner:
         also yields the segmented cloud and LeGO-LOAM's sharp / less sharp / flat points.  T_out: publishCloud's
         trans_c2s.inverse() as a [3,4] (or [4,4]) float64 matrix applied to the camera-frame point; identity if None."""
         if not enable:
-            self._check(self._lib.dddmr_rollout_set_lidar_sweep_features(self._ctx, int(source_id), None))
+            self._call("set_lidar_sweep_features", int(source_id), None)
             return
         T = np.hstack([np.eye(3), np.zeros((3, 1))]) if T_out is None else np.asarray(T_out, dtype=np.float64)
         if T.shape not in ((3, 4), (4, 4)):
             raise ValueError("T_out must be [3,4] or [4,4]")
         cfg = K.LidarFeaturesConfig(float(edge_threshold), float(surf_threshold), (C.c_double * 12)(*T[:3].reshape(-1).tolist()), int(flags))
-        self._check(self._lib.dddmr_rollout_set_lidar_sweep_features(self._ctx, int(source_id), C.byref(cfg)))
+        self._call("set_lidar_sweep_features", int(source_id), C.byref(cfg))
 
     def get_lidar_sweep_segmented(self, source_id: int, num_vertical_scans: int):
         """ImageProjection's segmented_cloud and seg_msg of the latest sweep: dict of xyz [n,3] float32, range [n] float32,
         col [n] int32, ground [n] uint8, start / end [V] int32 (start_ring_index / end_ring_index)."""
-        V, n = int(num_vertical_scans), C.c_size_t(0)
-        none = C.c_void_p(None)
-        self._check(self._lib.dddmr_rollout_get_lidar_sweep_segmented(self._ctx, int(source_id), none, none, none, none, none, none, 0, C.byref(n)))
-        cap = max(n.value, 1)
-        xyz, rng, col, gnd = np.zeros((cap, 3), np.float32), np.zeros(cap, np.float32), np.zeros(cap, np.int32), np.zeros(cap, np.uint8)
-        start, end = np.zeros(V, np.int32), np.zeros(V, np.int32)
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
-        self._check(self._lib.dddmr_rollout_get_lidar_sweep_segmented(self._ctx, int(source_id), ptr(xyz), ptr(rng), ptr(col), ptr(gnd),
-                                                                      ptr(start), ptr(end), cap, C.byref(n)))
-        k = n.value
-        return dict(xyz=xyz[:k], range=rng[:k], col=col[:k], ground=gnd[:k], start=start, end=end)
+        V = int(num_vertical_scans)
+        out = self._get("get_lidar_sweep_segmented", (int(source_id),), ((3,), np.float32), ((), np.float32), ((), np.int32),
+                        ((), np.uint8), np.zeros(V, np.int32), np.zeros(V, np.int32))
+        return dict(zip(("xyz", "range", "col", "ground", "start", "end"), out))
 
     def get_lidar_sweep_features(self, source_id: int, which: int):
         """One feature list of the latest sweep (which: 0 sharp, 1 less sharp, 2 flat): ([K,4] float32 x y z ring after T_out,
         [K] uint32 indices into the segmented cloud), in the reference's push order."""
-        n = C.c_size_t(0)
-        self._check(self._lib.dddmr_rollout_get_lidar_sweep_features(self._ctx, int(source_id), int(which), None, None, 0, C.byref(n)))
-        cap = max(n.value, 1)
-        out, idx = np.zeros((cap, 4), np.float32), np.zeros(cap, np.uint32)
-        self._check(self._lib.dddmr_rollout_get_lidar_sweep_features(self._ctx, int(source_id), int(which), out.ctypes.data_as(C.c_void_p),
-                                                                     idx.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
-        return out[: n.value], idx[: n.value]
+        return tuple(self._get("get_lidar_sweep_features", (int(source_id), int(which)), ((4,), np.float32), ((), np.uint32)))
 
     def set_depth_frustum(self, source_id: int, fov_w: float, fov_v: float, obstacle_min_range: float, obstacle_max_range: float,
                           T_gbl_sensor):
         """The frustum half of bufferCloud (depth_camera_observation_buffer.cpp:134-174) for this frame of the source:
         FOV in radians, T_gbl_sensor = m2s (x y z qx qy qz qw).  Replaces the source's frustum."""
         cfg = K.DepthFrustumConfig(float(fov_w), float(fov_v), float(obstacle_min_range), float(obstacle_max_range))
-        m2s = (C.c_double * 7)(*[float(v) for v in T_gbl_sensor])
-        self._check(self._lib.dddmr_rollout_set_depth_frustum(self._ctx, int(source_id), C.byref(cfg), m2s))
+        self._call("set_depth_frustum", int(source_id), C.byref(cfg), M.pose(T_gbl_sensor))
 
     def get_depth_frustum(self, source_id: int):
         """-> (vertices [8,3] TLNear TRNear BLNear BRNear TLFar TRFar BLFar BRFar, normals [6,3] near right bottom left
         far top, planes [6,4], origin [3]), float32, global frame."""
         vtx, nrm = np.zeros((8, 3), np.float32), np.zeros((6, 3), np.float32)
         pl, org = np.zeros((6, 4), np.float32), np.zeros(3, np.float32)
-        self._check(self._lib.dddmr_rollout_get_depth_frustum(self._ctx, int(source_id), vtx.ctypes.data, nrm.ctypes.data,
-                                                              pl.ctypes.data, org.ctypes.data))
+        self._call("get_depth_frustum", int(source_id), M.ptr(vtx), M.ptr(nrm), M.ptr(pl), M.ptr(org))
         return vtx, nrm, pl, org
 
     def depth_frustum_test(self, points_xyz: np.ndarray):
         """FrustumUtils::isinFrustumsObservations / isAttachFRUSTUMs (frustum_utils.cpp:124-290) for [N, >=3] float32
         points over all depth sources' frustums -> (in_frustums [N] bool, attach [N] bool)."""
-        pts = np.ascontiguousarray(points_xyz, dtype=np.float32)
-        if pts.ndim != 2 or (pts.shape[0] and pts.shape[1] < 3):
-            raise ValueError("points must be [N, >=3] float32")
-        n = pts.shape[0]
+        _, p, n, stride = M.cloud(points_xyz, "points")
         inside, attach = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
-        stride = pts.strides[0] if n else 12
-        self._check(self._lib.dddmr_rollout_depth_frustum_test(self._ctx, pts.ctypes.data, n, stride, inside.ctypes.data,
-                                                               attach.ctypes.data))
+        self._call("depth_frustum_test", p, n, stride, M.ptr(inside), M.ptr(attach))
         return inside[:n].astype(bool), attach[:n].astype(bool)
 
     def depth_clear_verdicts(self, xy_resolution: float, height_resolution: float, voxels: np.ndarray, offsets: np.ndarray,
@@ -346,111 +302,86 @@ class LocalPlanner:
         if off.shape[0] != m + 1 or (m and int(off[-1]) != pts.shape[0]):
             raise ValueError("offsets must be [M + 1] and end at the number of cluster points")
         verdict, engaged = np.zeros(max(m, 1), np.uint8), np.zeros(max(m, 1), np.uint32)
-        self._check(self._lib.dddmr_rollout_depth_clear_verdicts(self._ctx, float(xy_resolution), float(height_resolution),
-                                                                 vox.ctypes.data, off.ctypes.data, pts.ctypes.data, m,
-                                                                 verdict.ctypes.data, engaged.ctypes.data))
+        self._call("depth_clear_verdicts", float(xy_resolution), float(height_resolution), M.ptr(vox), M.ptr(off), M.ptr(pts), m,
+                   M.ptr(verdict), M.ptr(engaged))
         return verdict[:m], engaged[:m]
 
     def depth_clear_launches(self) -> int:
         """Device operations (kernels, memsets, copies) the last depth_clear_verdicts call enqueued."""
         n = C.c_uint32(0)
-        self._check(self._lib.dddmr_rollout_depth_clear_launches(self._ctx, C.byref(n)))
+        self._call("depth_clear_launches", C.byref(n))
         return int(n.value)
+
+    def _create_on_maps(self, name: str, cfg, ground_xyz, map_xyz):
+        """The layers' create calls: the configuration, then pcl_ground_ and pcl_map_ as clouds -> the ground array."""
+        g, gp, gn, gs = M.cloud(ground_xyz, "ground")
+        _, mp, mn, ms = M.cloud(map_xyz, "map")
+        self._call(name, C.byref(cfg), gp, gn, gs, mp, mn, ms)
+        return g
 
     def depth_mark_create(self, xy_resolution: float, height_resolution: float, ground_xyz: np.ndarray, map_xyz: np.ndarray,
                           tolerance: float = 0.1, min_cluster_size: int = 1, segmentation_ignore_ratio: float = 0.2,
                           max_observation_points: int = 1 << 16):
         """The depth camera layer's selfMark state: pcl_ground_ / pcl_map_ ([N, >=3] float32, the map may be empty) go to
         the device once.  Independent of the lidar marking layer; calling it again replaces the state."""
-        ground = np.ascontiguousarray(ground_xyz, dtype=np.float32)
-        smap = np.ascontiguousarray(map_xyz, dtype=np.float32)
-        for a in (ground, smap):
-            if a.ndim != 2 or (a.shape[0] and a.shape[1] < 3):
-                raise ValueError("ground / map must be [N, >=3] float32")
         cfg = K.DepthMarkConfig(float(xy_resolution), float(height_resolution), float(tolerance), int(min_cluster_size), 0,
                                 float(segmentation_ignore_ratio), int(max_observation_points), 0)
-        self._check(self._lib.dddmr_rollout_depth_mark_create(
-            self._ctx, C.byref(cfg), ground.ctypes.data if ground.shape[0] else None, ground.shape[0],
-            ground.strides[0] if ground.shape[0] else 12, smap.ctypes.data if smap.shape[0] else None, smap.shape[0],
-            smap.strides[0] if smap.shape[0] else 12))
+        self._create_on_maps("depth_mark_create", cfg, ground_xyz, map_xyz)
 
     def depth_mark_clusters(self, T_gbl_base):
         """One DepthCameraLayer::selfMark (depth_camera_layer.cpp:487-601) on the depth sources' current observation ->
         (centroids [C,3] float32, voxels [C,3] int32, sizes [C] uint32, offsets [C+1] uint32, points [P,3] float32,
         plane [4] float32, stats): what addPCPtr is to be called with, in the reference's order.  The buffers are sized
         by a count-only call first."""
-        tgb = (C.c_double * 7)(*[float(v) for v in T_gbl_base])
+        tgb = M.pose(T_gbl_base)
         st = K.DepthMarkStats()
-        self._check(self._lib.dddmr_rollout_depth_mark_clusters(self._ctx, tgb, 0, 0, None, None, None, None, None, None, C.byref(st)))
+        self._call("depth_mark_clusters", tgb, 0, 0, None, None, None, None, None, None, C.byref(st))
         c, p = int(st.n_accepted), int(st.n_points)
         cen, vox = np.zeros((max(c, 1), 3), np.float32), np.zeros((max(c, 1), 3), np.int32)
         size, off = np.zeros(max(c, 1), np.uint32), np.zeros(c + 1, np.uint32)
         pts, plane = np.zeros((max(p, 1), 3), np.float32), np.zeros(4, np.float32)
-        self._check(self._lib.dddmr_rollout_depth_mark_clusters(self._ctx, tgb, c, p, cen.ctypes.data, vox.ctypes.data, size.ctypes.data,
-                                                                off.ctypes.data, pts.ctypes.data, plane.ctypes.data, C.byref(st)))
+        self._call("depth_mark_clusters", tgb, c, p, M.ptr(cen), M.ptr(vox), M.ptr(size), M.ptr(off), M.ptr(pts), M.ptr(plane),
+                   C.byref(st))
         return cen[:c], vox[:c], size[:c], off, pts[:p], plane, st
 
     def depth_layer_create(self, cfg: "K.DepthLayerConfig", ground_xyz: np.ndarray, map_xyz: np.ndarray):
         """The depth camera layer's device state (store, dGraph, lethal set): pcl_ground_ / pcl_map_ ([N, >=3] float32, the
         map may be empty) go to the device once.  See dddmr_navigation_amd.depth_layer.DepthLayer."""
-        ground = np.ascontiguousarray(ground_xyz, dtype=np.float32)
-        smap = np.ascontiguousarray(map_xyz, dtype=np.float32)
-        for a in (ground, smap):
-            if a.ndim != 2 or (a.shape[0] and a.shape[1] < 3):
-                raise ValueError("ground / map must be [N, >=3] float32")
-        self._check(self._lib.dddmr_rollout_depth_layer_create(
-            self._ctx, C.byref(cfg), ground.ctypes.data if ground.shape[0] else None, ground.shape[0],
-            ground.strides[0] if ground.shape[0] else 12, smap.ctypes.data if smap.shape[0] else None, smap.shape[0],
-            smap.strides[0] if smap.shape[0] else 12))
+        self._create_on_maps("depth_layer_create", cfg, ground_xyz, map_xyz)
 
     def depth_layer_update(self, T_gbl_base) -> "K.DepthLayerStats":
         """One selfClear + selfMark pass of the depth camera layer on the depth sources' current observation."""
-        tgb = (C.c_double * 7)(*[float(v) for v in T_gbl_base])
         st = K.DepthLayerStats()
-        self._check(self._lib.dddmr_rollout_depth_layer_update(self._ctx, tgb, C.byref(st)))
+        self._call("depth_layer_update", M.pose(T_gbl_base), C.byref(st))
         return st
 
     def depth_layer_reset(self):
-        self._check(self._lib.dddmr_rollout_depth_layer_reset(self._ctx))
+        self._call("depth_layer_reset")
 
     def depth_layer_voxels(self) -> np.ndarray:
-        n = C.c_size_t(0)
-        self._check(self._lib.dddmr_rollout_depth_layer_get_voxels(self._ctx, None, 0, C.byref(n)))
-        out = np.zeros((max(n.value, 1), 3), dtype=np.int32)
-        self._check(self._lib.dddmr_rollout_depth_layer_get_voxels(self._ctx, out.ctypes.data, out.shape[0], C.byref(n)))
-        return out[: n.value]
+        return self._get("depth_layer_get_voxels", (), ((3,), np.int32))[0]
 
     def depth_layer_clusters(self):
         """The alive markings with their stored pc_ -> (voxels [M,3] int32, offsets [M+1] uint32, points [P,3] float32)."""
         m, p = C.c_size_t(0), C.c_size_t(0)
-        self._check(self._lib.dddmr_rollout_depth_layer_get_clusters(self._ctx, None, None, None, 0, 0, C.byref(m), C.byref(p)))
+        self._call("depth_layer_get_clusters", None, None, None, 0, 0, C.byref(m), C.byref(p))
         vox, off = np.zeros((max(m.value, 1), 3), np.int32), np.zeros(m.value + 1, np.uint32)
         pts = np.zeros((max(p.value, 1), 3), np.float32)
-        self._check(self._lib.dddmr_rollout_depth_layer_get_clusters(self._ctx, vox.ctypes.data, off.ctypes.data, pts.ctypes.data,
-                                                                     m.value, p.value, C.byref(m), C.byref(p)))
+        self._call("depth_layer_get_clusters", M.ptr(vox), M.ptr(off), M.ptr(pts), m.value, p.value, C.byref(m), C.byref(p))
         return vox[: m.value], off, pts[: p.value]
 
     def depth_layer_dgraph(self, n_ground: int) -> np.ndarray:
-        out = np.zeros(int(n_ground) + 1, dtype=np.float64)
-        self._check(self._lib.dddmr_rollout_depth_layer_get_dgraph(self._ctx, out.ctypes.data, out.size))
-        return out
+        return self._fixed("depth_layer_get_dgraph", int(n_ground) + 1, np.float64)
 
     def depth_layer_lethal(self, n_ground: int) -> np.ndarray:
-        out = np.zeros(int(n_ground) + 1, dtype=np.uint8)
-        self._check(self._lib.dddmr_rollout_depth_layer_get_lethal(self._ctx, out.ctypes.data, out.size))
-        return out.astype(bool)
+        return self._fixed("depth_layer_get_lethal", int(n_ground) + 1, np.uint8, as_bool=True)
 
     def set_stitcher(self, stitcher_num: int):
         """cbSensor's `stitcher_num` (multilayer_spinning_lidar.cpp:185-200): feed the last N raw scans together."""
-        self._check(self._lib.dddmr_rollout_set_stitcher(self._ctx, int(stitcher_num)))
+        self._call("set_stitcher", int(stitcher_num))
 
     def get_cloud(self) -> np.ndarray:
-        n = C.c_size_t(0)
-        self._check(self._lib.dddmr_rollout_get_cloud(self._ctx, None, 0, C.byref(n)))
-        out = np.zeros((max(n.value, 1), 4), dtype=np.float32)
-        self._check(self._lib.dddmr_rollout_get_cloud(self._ctx, out.ctypes.data_as(C.c_void_p), out.shape[0],
-                                                      C.byref(n)))
-        return out[: n.value]
+        return self._get("get_cloud", (), ((4,), np.float32))[0]
 
     def setPlan(self, prune_plan: np.ndarray):
         """Prune plan poses [M,7] (x y z qx qy qz qw), the output of
@@ -467,19 +398,12 @@ class LocalPlanner:
         plan = np.ascontiguousarray(pcl_prune_plan, dtype=np.float32).reshape(-1, 4)
         flags = np.zeros(max(len(plan), 1), dtype=np.uint8)
         ratio, op = C.c_double(0.0), C.c_int32(0)
-        self._check(self._lib.dddmr_rollout_path_blocked(self._ctx, plan.ctypes.data_as(C.c_void_p), len(plan),
-                                                         float(check_radius), C.byref(ratio), C.byref(op),
-                                                         flags.ctypes.data_as(C.c_void_p)))
+        self._call("path_blocked", M.ptr(plan), len(plan), float(check_radius), C.byref(ratio), C.byref(op), M.ptr(flags))
         return ratio.value, op.value, flags[: len(plan)].astype(bool)
 
     def samples(self, traj_gen_name: str, tick_in: K.TickInput) -> np.ndarray:
         """The theory's initialise(): the sample list a tick would roll out, [N,3] vx vy wz (host-only)."""
-        n = C.c_size_t(0)
-        self._check(self._lib.dddmr_rollout_samples(self._ctx, traj_gen_name.encode(), C.byref(tick_in), None, 0, C.byref(n)))
-        out = np.zeros((max(n.value, 1), 3), dtype=np.float32)
-        self._check(self._lib.dddmr_rollout_samples(self._ctx, traj_gen_name.encode(), C.byref(tick_in),
-                                                    out.ctypes.data_as(C.c_void_p), out.shape[0], C.byref(n)))
-        return out[: n.value]
+        return self._get("samples", (traj_gen_name.encode(), C.byref(tick_in)), ((3,), np.float32))[0]
 
     # -- the tick ----------------------------------------------------------
     def tick(self, traj_gen_name: str, tick_in: K.TickInput) -> K.RolloutResult:
@@ -511,7 +435,7 @@ class LocalPlanner:
         res = K.RolloutResult()
         if self.last_result is not None:
             C.memmove(C.byref(res), C.byref(self.last_result), C.sizeof(res))
-        self._check(self._lib.dddmr_rollout_resolve(self._ctx, C.c_int64(reduced_key), C.byref(res)))
+        self._call("resolve", C.c_int64(reduced_key), C.byref(res))
         return res
 
     def winner_words(self, res: Optional[K.RolloutResult] = None):
@@ -542,37 +466,35 @@ class LocalPlanner:
     def comm_init(self, unique_id: bytes, rank: int, n_ranks: int):
         if len(unique_id) != K.COMM_ID_BYTES:
             raise ValueError("unique id must be 128 bytes")
-        buf = (C.c_uint8 * K.COMM_ID_BYTES)(*unique_id)
-        self._check(self._lib.dddmr_rollout_comm_init(self._ctx, buf, rank, n_ranks))
+        self._call("comm_init", (C.c_uint8 * K.COMM_ID_BYTES)(*unique_id), rank, n_ranks)
 
     def comm_destroy(self):
-        self._check(self._lib.dddmr_rollout_comm_destroy(self._ctx))
+        self._call("comm_destroy")
 
     def comm_ranks(self) -> int:
         """Ranks the context's communicator reports (ncclCommCount); 0 without one."""
         n = C.c_int32(0)
-        self._check(self._lib.dddmr_rollout_comm_ranks(self._ctx, C.byref(n)))
+        self._call("comm_ranks", C.byref(n))
         return int(n.value)
 
     def comm_loopback(self):
         """Single-device rehearsal of the exchange: see dddmr_rollout_comm_loopback."""
-        self._check(self._lib.dddmr_rollout_comm_loopback(self._ctx))
+        self._call("comm_loopback")
 
     def comm_loopback_set_peer(self, peer_rank: int, words):
-        w = (C.c_int64 * 2)(int(words[0]), int(words[1]))
-        self._check(self._lib.dddmr_rollout_comm_loopback_set_peer(self._ctx, int(peer_rank), w))
+        self._call("comm_loopback_set_peer", int(peer_rank), (C.c_int64 * 2)(int(words[0]), int(words[1])))
 
     def stream_ceiling(self, nbytes: int = 1 << 30, reps: int = 10):
         """Measured stream ceilings of this GPU -> (copy GB/s counting read + write, read-only GB/s)."""
         cp, rd = C.c_double(0.0), C.c_double(0.0)
-        self._check(self._lib.dddmr_rollout_stream_ceiling(self._ctx, nbytes, reps, C.byref(cp), C.byref(rd)))
+        self._call("stream_ceiling", nbytes, reps, C.byref(cp), C.byref(rd))
         return cp.value, rd.value
 
     def selftest_sincos(self, angles):
         """sin / cos of heading angles from the rollout's own double routine -> (sin[n], cos[n]) f64"""
         a = np.ascontiguousarray(angles, dtype=np.float64)
         sn, cs = np.empty_like(a), np.empty_like(a)
-        self._check(self._lib.dddmr_rollout_selftest_sincos(self._ctx, a.ctypes.data, a.size, sn.ctypes.data, cs.ctypes.data))
+        self._call("selftest_sincos", M.ptr(a), a.size, M.ptr(sn), M.ptr(cs))
         return sn, cs
 
     # -- per-trajectory outputs of the last tick -----------------------------
@@ -586,42 +508,26 @@ class LocalPlanner:
         dbg.costs = costs.ctypes.data_as(C.POINTER(C.c_double))
         dbg.steps = steps.ctypes.data_as(C.POINTER(C.c_int32))
         dbg.samples = smp.ctypes.data_as(C.POINTER(C.c_float))
-        self._check(self._lib.dddmr_rollout_get_debug(self._ctx, C.byref(dbg)))
+        self._call("get_debug", C.byref(dbg))
         return costs[:n], steps[:n], smp[:n]
 
     def pose_arrays(self, accepted_only: bool = False) -> np.ndarray:
         """The `trajectory` / `accepted_trajectory` debug pose arrays of the last tick, [n,7]."""
-        which = 1 if accepted_only else 0
-        n = C.c_size_t(0)
-        self._check(self._lib.dddmr_rollout_get_pose_arrays(self._ctx, which, None, 0, C.byref(n)))
-        out = np.zeros((max(n.value, 1), 7), dtype=np.float64)
-        self._check(self._lib.dddmr_rollout_get_pose_arrays(self._ctx, which, out.ctypes.data_as(C.c_void_p), out.shape[0],
-                                                            C.byref(n)))
-        return out[: n.value]
+        return self._get("get_pose_arrays", (1 if accepted_only else 0,), ((7,), np.float64))[0]
 
     def heading_rows(self) -> int:
         """1 if the last launched tick shared one row of headings per angular sample, 0 if every trajectory ran its
         own chain, -1 before any tick (dddmr_rollout_heading_rows)."""
-        return int(self._lib.dddmr_rollout_heading_rows(self._ctx))
+        return int(self._rc("heading_rows"))
 
     def fused_walk(self) -> int:
         """1 if the last launched tick walked the prune plan as the tail of the collision walk, 0 if the path critics' search
         ran as a phase of its own, -1 before any tick (dddmr_rollout_fused_walk)."""
-        return int(self._lib.dddmr_rollout_fused_walk(self._ctx))
+        return int(self._rc("fused_walk"))
 
     def best_poses(self) -> np.ndarray:
-        n = C.c_size_t(0)
-        self._check(self._lib.dddmr_rollout_get_best_poses(self._ctx, None, 0, C.byref(n)))
-        out = np.zeros((max(n.value, 1), 7), dtype=np.float64)
-        self._check(self._lib.dddmr_rollout_get_best_poses(self._ctx, out.ctypes.data_as(C.c_void_p), out.shape[0],
-                                                           C.byref(n)))
-        return out[: n.value]
+        return self._get("get_best_poses", (), ((7,), np.float64))[0]
 
     def best_cuboids(self) -> np.ndarray:
         """Cuboid vertices carried along the best trajectory, [n_poses, 8, 3] float32."""
-        n = C.c_size_t(0)
-        self._check(self._lib.dddmr_rollout_get_best_cuboids(self._ctx, None, 0, C.byref(n)))
-        out = np.zeros((max(n.value, 1), 8, 3), dtype=np.float32)
-        self._check(self._lib.dddmr_rollout_get_best_cuboids(self._ctx, out.ctypes.data_as(C.c_void_p), out.shape[0],
-                                                             C.byref(n)))
-        return out[: n.value]
+        return self._get("get_best_cuboids", (), ((8, 3), np.float32))[0]

@@ -10,25 +10,20 @@ import ctypes as C
 import numpy as np
 
 from . import _capi as K
+from . import _marshal as M
 
 
 def shipped_config(**kw) -> K.MarkingConfig:
     """perception_3d_global / lidar block of
     dddmr_p2p_move_base/config/p2p_move_base_localization.yaml:286-334."""
-    c = K.MarkingConfig()
-    d = dict(xy_resolution=0.05, height_resolution=0.05, marking_height=2.0, perception_window_size=5.0,
-             vertical_FOV_top=15.0, vertical_FOV_bottom=-15.0,
-             scan_effective_positive_start=30.0, scan_effective_positive_end=180.0,
-             scan_effective_negative_start=-30.0, scan_effective_negative_end=-180.0,
-             euclidean_cluster_extraction_tolerance=0.1, euclidean_cluster_extraction_min_cluster_size=1,
-             segmentation_ignore_ratio=1.1, inscribed_radius=0.5, inflation_radius=1.5,
-             max_obstacle_distance=9999.0, max_markings=1 << 15, max_cluster_points=1 << 20)
-    d.update(kw)
-    for k, v in d.items():
-        if not hasattr(c, k):
-            raise KeyError(k)
-        setattr(c, k, v)
-    return c
+    return M.struct_from(K.MarkingConfig, dict(
+        xy_resolution=0.05, height_resolution=0.05, marking_height=2.0, perception_window_size=5.0,
+        vertical_FOV_top=15.0, vertical_FOV_bottom=-15.0,
+        scan_effective_positive_start=30.0, scan_effective_positive_end=180.0,
+        scan_effective_negative_start=-30.0, scan_effective_negative_end=-180.0,
+        euclidean_cluster_extraction_tolerance=0.1, euclidean_cluster_extraction_min_cluster_size=1,
+        segmentation_ignore_ratio=1.1, inscribed_radius=0.5, inflation_radius=1.5,
+        max_obstacle_distance=9999.0, max_markings=1 << 15, max_cluster_points=1 << 20), kw)
 
 
 class MarkingLayer:
@@ -38,21 +33,15 @@ class MarkingLayer:
     def __init__(self, lp, cfg: K.MarkingConfig, ground: np.ndarray, static_map: np.ndarray):
         self._lp = lp
         self.cfg = cfg
-        g = np.ascontiguousarray(ground, dtype=np.float32)
-        m = np.ascontiguousarray(static_map, dtype=np.float32).reshape(-1, max(3, static_map.shape[1] if static_map.ndim == 2 else 3))
-        self.n_ground = len(g)
-        lp._check(lp._lib.dddmr_rollout_marking_create(
-            lp._ctx, C.byref(cfg), g.ctypes.data_as(C.c_void_p), len(g), g.strides[0] if len(g) else 12,
-            m.ctypes.data_as(C.c_void_p), len(m), m.strides[0] if len(m) else 12))
+        self.n_ground = len(lp._create_on_maps("marking_create", cfg, ground, static_map))
+        self._update = lp._lib.dddmr_rollout_marking_update       # (update is on bench.py's clock: no lookup by name)
         self.last = None
         self.totals = dict(updates=0, clusters=0, marked=0, cleared=0, clear_ms=0.0, mark_ms=0.0)
 
     def update(self, T_base_sensor, T_gbl_base) -> K.MarkingStats:
         """One doClear_then_Mark pass on the context's current aggregate observation."""
-        tbs = (C.c_double * 7)(*[float(v) for v in T_base_sensor])
-        tgb = (C.c_double * 7)(*[float(v) for v in T_gbl_base])
         st = K.MarkingStats()
-        self._lp._check(self._lp._lib.dddmr_rollout_marking_update(self._lp._ctx, tbs, tgb, C.byref(st)))
+        self._lp._check(self._update(self._lp._ctx, M.pose(T_base_sensor), M.pose(T_gbl_base), C.byref(st)))
         self.last = st
         t = self.totals
         t["updates"] += 1; t["clusters"] += st.n_clusters; t["marked"] += st.n_marked; t["cleared"] += st.n_cleared
@@ -60,41 +49,28 @@ class MarkingLayer:
         return st
 
     def reset(self):
-        self._lp._check(self._lp._lib.dddmr_rollout_marking_reset(self._lp._ctx))
+        self._lp._call("marking_reset")
 
     def route_counts(self) -> dict:
         """Updates that ran fused (five launches, observations of up to 32768 points) / on the general route, launches of the last update."""
         a, b, n = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
-        self._lp._check(self._lp._lib.dddmr_rollout_marking_route_counts(self._lp._ctx, C.byref(a), C.byref(b), C.byref(n)))
+        self._lp._call("marking_route_counts", C.byref(a), C.byref(b), C.byref(n))
         return {"fused": int(a.value), "general": int(b.value), "launches_last_update": int(n.value)}
 
     def points(self, with_voxels: bool = False):
         """Generator points of the alive markings (projected on the ground plane, 0.1 m VoxelGrid), [n, 3] float32;
         with_voxels: also the voxel key of the marking each point belongs to, [n, 3] int32."""
-        n = C.c_size_t(0)
-        self._lp._check(self._lp._lib.dddmr_rollout_marking_get_points(self._lp._ctx, None, None, 0, C.byref(n)))
-        out = np.zeros((max(n.value, 1), 3), dtype=np.float32)
-        vox = np.zeros((max(n.value, 1), 3), dtype=np.int32)
-        self._lp._check(self._lp._lib.dddmr_rollout_marking_get_points(self._lp._ctx, out.ctypes.data_as(C.c_void_p), vox.ctypes.data_as(C.c_void_p),
-                                                                       out.shape[0], C.byref(n)))
-        return (out[: n.value], vox[: n.value]) if with_voxels else out[: n.value]
+        out, vox = self._lp._get("marking_get_points", (), ((3,), np.float32), ((3,), np.int32))
+        return (out, vox) if with_voxels else out
 
     def voxels(self) -> np.ndarray:
-        n = C.c_size_t(0)
-        self._lp._check(self._lp._lib.dddmr_rollout_marking_get_voxels(self._lp._ctx, None, 0, C.byref(n)))
-        out = np.zeros((max(n.value, 1), 3), dtype=np.int32)
-        self._lp._check(self._lp._lib.dddmr_rollout_marking_get_voxels(self._lp._ctx, out.ctypes.data_as(C.c_void_p), out.shape[0], C.byref(n)))
-        return out[: n.value]
+        return self._lp._get("marking_get_voxels", (), ((3,), np.int32))[0]
 
     def dgraph(self) -> np.ndarray:
-        out = np.zeros(self.n_ground + 1, dtype=np.float64)
-        self._lp._check(self._lp._lib.dddmr_rollout_marking_get_dgraph(self._lp._ctx, out.ctypes.data_as(C.c_void_p), out.size))
-        return out
+        return self._lp._fixed("marking_get_dgraph", self.n_ground + 1, np.float64)
 
     def lethal(self) -> np.ndarray:
-        out = np.zeros(self.n_ground + 1, dtype=np.uint8)
-        self._lp._check(self._lp._lib.dddmr_rollout_marking_get_lethal(self._lp._ctx, out.ctypes.data_as(C.c_void_p), out.size))
-        return out.astype(bool)
+        return self._lp._fixed("marking_get_lethal", self.n_ground + 1, np.uint8, as_bool=True)
 
     def summary(self) -> dict:
         t = self.totals

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi as K
+from . import _marshal as M
 
 
 class PerceptionStack:
@@ -39,7 +40,7 @@ class PerceptionStack:
             cfg.layer_order[i] = o
         cfg.max_changes = max_changes
         self.cfg = cfg
-        lp._check(lp._lib.dddmr_rollout_stack_create(lp._ctx, C.byref(cfg)))
+        lp._call("stack_create", C.byref(cfg))
         for slot, values in enumerate(host_layers):
             if values is not None:
                 self.set_host_layer(slot, values)
@@ -49,19 +50,19 @@ class PerceptionStack:
     def set_host_layer(self, slot: int, values):
         """A layer whose dGraph the host computes (static layer, zone layers): n_ground + 1 float64, None unsets the slot."""
         if values is None:
-            self._lp._check(self._lp._lib.dddmr_rollout_stack_set_host_layer(self._lp._ctx, slot, None))
+            self._lp._call("stack_set_host_layer", slot, None)
             return
         v = np.ascontiguousarray(values, dtype=np.float64)
         if v.shape != (self.n_ground + 1,):
             raise ValueError("a host layer is n_ground + 1 float64 values")
-        self._lp._check(self._lp._lib.dddmr_rollout_stack_set_host_layer(self._lp._ctx, slot, v.ctypes.data_as(C.c_void_p)))
+        self._lp._call("stack_set_host_layer", slot, M.ptr(v))
 
     def update(self, T_base_sensor=None, T_gbl_base=None) -> K.StackStats:
         """One pass; raises RolloutError with the first failing layer's code, self.last holds the stats either way."""
-        tbs = (C.c_double * 7)(*[float(v) for v in T_base_sensor]) if T_base_sensor is not None else None
-        tgb = (C.c_double * 7)(*[float(v) for v in T_gbl_base]) if T_gbl_base is not None else None
+        tbs = M.pose(T_base_sensor) if T_base_sensor is not None else None
+        tgb = M.pose(T_gbl_base) if T_gbl_base is not None else None
         st = K.StackStats()
-        rc = self._lp._lib.dddmr_rollout_stack_update(self._lp._ctx, tbs, tgb, C.byref(st))
+        rc = self._lp._rc("stack_update", tbs, tgb, C.byref(st))
         self.last = st
         t = self.totals
         t["updates"] += 1; t["changed"] += st.n_changed; t["launches"] += st.launches; t["host_waits"] += st.host_waits
@@ -72,7 +73,7 @@ class PerceptionStack:
     def n_changes(self) -> int:
         """The true count of the last update, also when it exceeds max_changes."""
         n = C.c_size_t(0)
-        rc = self._lp._lib.dddmr_rollout_stack_get_changes(self._lp._ctx, None, None, None, 0, C.byref(n))
+        rc = self._lp._rc("stack_get_changes", None, None, None, 0, C.byref(n))
         if rc != K.ERR_CAPACITY:
             self._lp._check(rc)
         return int(n.value)
@@ -83,32 +84,23 @@ class PerceptionStack:
         cap = max(int(self.cfg.max_changes), 1)
         node, value, mask = np.zeros(cap, np.uint32), np.zeros(cap, np.float64), np.zeros(cap, np.uint8)
         n = C.c_size_t(0)
-        self._lp._check(self._lp._lib.dddmr_rollout_stack_get_changes(
-            self._lp._ctx, node.ctypes.data_as(C.c_void_p), value.ctypes.data_as(C.c_void_p), mask.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
+        self._lp._call("stack_get_changes", M.ptr(node), M.ptr(value), M.ptr(mask), cap, C.byref(n))
         return node[: n.value], value[: n.value], mask[: n.value]
 
     def min_dgraph(self) -> np.ndarray:
-        out = np.zeros(self.n_ground + 1, dtype=np.float64)
-        self._lp._check(self._lp._lib.dddmr_rollout_stack_get_min_dgraph(self._lp._ctx, out.ctypes.data_as(C.c_void_p), out.size))
-        return out
+        return self._lp._fixed("stack_get_min_dgraph", self.n_ground + 1, np.float64)
 
     def lethal_mask(self) -> np.ndarray:
         """one byte per node; bit i = the layer at position i of `order`"""
-        out = np.zeros(self.n_ground + 1, dtype=np.uint8)
-        self._lp._check(self._lp._lib.dddmr_rollout_stack_get_lethal_mask(self._lp._ctx, out.ctypes.data_as(C.c_void_p), out.size))
-        return out
+        return self._lp._fixed("stack_get_lethal_mask", self.n_ground + 1, np.uint8)
 
     def lethal_nodes(self) -> np.ndarray:
         """aggregateLethal as node indices: per device layer in plugin order, its lethal nodes ascending"""
-        n = C.c_size_t(0)
-        self._lp._check(self._lp._lib.dddmr_rollout_stack_get_lethal_nodes(self._lp._ctx, None, 0, C.byref(n)))
-        out = np.zeros(max(n.value, 1), dtype=np.uint32)
-        self._lp._check(self._lp._lib.dddmr_rollout_stack_get_lethal_nodes(self._lp._ctx, out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)))
-        return out[: n.value]
+        return self._lp._get("stack_get_lethal_nodes", (), ((), np.uint32))[0]
 
     def reset(self):
         """StackedPerception::resetdGraph: both layers, then the stacked arrays; the change list is empty afterwards"""
-        self._lp._check(self._lp._lib.dddmr_rollout_stack_reset(self._lp._ctx))
+        self._lp._call("stack_reset")
 
     def summary(self) -> dict:
         t = self.totals

@@ -1,15 +1,20 @@
 """CPU tests of the C-ABI boundary: the library loads, exports every symbol the
-header declares, struct layouts agree, the argmin key orders like the
+header declares, the signature table agrees with the header's prototypes, struct layouts agree, the argmin key orders like the
 reference's scan, and the product fails loudly without a GPU (no fallback)."""
 import ctypes as C
 import os
 import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 
 from dddmr_navigation_amd import _capi as K, configs, sharding
 from conftest import ROOT, has_gpu
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+import capi_header  # noqa: E402
 
 
 def header_symbols():
@@ -30,9 +35,53 @@ def test_library_exports_every_header_symbol():
 
 def test_struct_layouts_match_compiled_library():
     lib = K.load_library()
-    for i, t in enumerate([K.CriticConfig, K.TheoryConfig, K.RolloutConfig, K.TickInput,
-                           K.RolloutResult, K.RolloutDebug, K.MarkingConfig, K.MarkingStats]):
+    assert len(K.SIZEOF_STRUCTS) == 23 and lib.dddmr_rollout_sizeof(len(K.SIZEOF_STRUCTS)) == 0
+    for i, t in enumerate(K.SIZEOF_STRUCTS):
         assert C.sizeof(t) == lib.dddmr_rollout_sizeof(i), t.__name__
+
+
+def test_signature_table_matches_header():
+    """every prototype of the header against _capi.SIGNATURES: the name, the number of parameters, the kind of each
+    (pointer / array, size_t, int / int32_t, uint32_t, int64_t, double) and of the return type.  Needs no library."""
+    protos = capi_header.prototypes()
+    assert len(protos) >= 87 and sorted(protos) == header_symbols()
+    assert sorted(set(K.SIGNATURES) - set(protos)) == list(K.NOT_IN_HEADER) == ["dddmr_rollout_sizeof"]
+    for name, (ret, params) in protos.items():
+        assert name in K.SIGNATURES, name
+        restype, argtypes = K.SIGNATURES[name]
+        assert capi_header.ctypes_kind(restype, is_return=True) == ret, name
+        assert len(argtypes) == len(params), name
+        for i, (t, kind) in enumerate(zip(argtypes, params)):
+            assert capi_header.ctypes_kind(t) == ("ptr" if kind in ("in", "out") else kind), f"{name}: parameter {i}"
+    assert not isinstance(K.EXPORTED_SYMBOLS, list) and len(K.EXPORTED_SYMBOLS) == len(protos)
+
+
+def test_missing_symbol_rule(tmp_path, monkeypatch):
+    """the shipped library must export every table entry (the load fails and names the first missing one); a library that
+    DDDMR_LIB_NAME selects may lack some, and calling one of those raises AttributeError"""
+    src, so = tmp_path / "partial.c", tmp_path / "libpartial.so"
+    src.write_text('const char* dddmr_rollout_version(void) { return "partial"; }\n')
+    subprocess.check_call(["cc", "-shared", "-fPIC", "-o", str(so), str(src)])
+    monkeypatch.setattr(K, "_lib", None)
+    monkeypatch.setattr(K, "library_path", lambda: str(so))
+    monkeypatch.delenv("DDDMR_LIB_NAME", raising=False)
+    with pytest.raises(RuntimeError, match="does not export dddmr_rollout_create"):
+        K.load_library()
+    assert K._lib is None
+    monkeypatch.setenv("DDDMR_LIB_NAME", "libpartial.so")
+    lib = K.load_library()
+    assert lib.dddmr_rollout_version() == b"partial"
+    with pytest.raises(AttributeError):
+        lib.dddmr_rollout_tick
+
+
+def test_header_parser_reads_each_kind():
+    p = capi_header.prototypes()
+    assert p["dddmr_rollout_version"] == ("str", []) and p["dddmr_rollout_destroy"] == ("void", ["out"])
+    assert p["dddmr_rollout_pack_key"] == ("int64", ["double", "uint32"]) and p["dddmr_rollout_key_index"] == ("int", ["int64"])
+    assert p["dddmr_rollout_set_cloud"] == ("int", ["out", "in", "size_t", "size_t"])
+    assert p["dddmr_rollout_winner_words"] == ("void", ["in", "out"])          # (int64_t words[2]: an array parameter)
+    assert p["dddmr_rollout_depth_mark_clusters"][1] == ["out", "in", "size_t", "size_t"] + ["out"] * 7
 
 
 def test_planner_state_values_match_reference_enum():
