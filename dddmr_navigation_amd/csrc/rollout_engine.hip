@@ -81,6 +81,7 @@ struct dddmr_rollout_ctx {
   TrajInfo* traj_info = nullptr;
   double2* st_sc = nullptr;
   float2* st_xy = nullptr;
+  double2* st_pp = nullptr;   // per trajectory: pure pursuit (distance, folded yaw) on its last pose, from the rollout
   size_t st_cap = 0;       // (trajectory, step) pairs the state arrays hold
   hipEvent_t ev0 = nullptr, ev1 = nullptr, evs0 = nullptr, evs1 = nullptr, cloud_ready[kCloudBufs] = {nullptr, nullptr, nullptr};
 
@@ -697,6 +698,8 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
   const int rc = plan_tick(ctx->knobs, ctx->feedback, ctx->cfg, *th, theory_id, *in, w, pin.n_points(), ctx->plan_m,
                            ctx->plan_last, exchange, &p, &err);
   if (rc != DDDMR_OK) return fail(ctx, rc, "%s", err.c_str());
+  if (ctx->seq == 0 && ctx->debug_grid)     // (the first tick: tests read the size of the row-run index k_score stages here)
+    std::fprintf(stderr, "[dddmr] grid: %d x %d x %d cells, row-run index of %d entries in LDS\n", k.gnx, k.gny, k.gnz, k.tab_entries);
   if (ctx->seq == 3 && ctx->debug_grid)
     std::fprintf(stderr, "[dddmr] k_score shape: %d lanes, tile %d, %d-step rows, %zu bytes of dynamic LDS (tile+1 would need %zu)\n", p.thr, k.tile,
                  p.s_tick, p.score_lds, plan_score_lds(k, k.tile + 1));
@@ -721,6 +724,7 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
       const size_t cap = need + need / 4 + 1024;
       HIPCHK(ctx, dev_realloc(ctx->mem, &ctx->st_sc, cap));
       HIPCHK(ctx, dev_realloc(ctx->mem, &ctx->st_xy, cap));
+      HIPCHK(ctx, dev_realloc(ctx->mem, &ctx->st_pp, (size_t)ctx->cfg.max_trajectories));
       ctx->st_cap = cap;
       if (!ctx->traj_info) HIPCHK(ctx, dev_alloc(ctx->mem, &ctx->traj_info, (size_t)ctx->cfg.max_trajectories));
     }
@@ -733,6 +737,7 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
     HIPCHK(ctx, hipMemsetAsync(ctx->steps, 0xFF, (size_t)k.n_local * sizeof(int32_t), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->samples_out, 0xFF, (size_t)k.n_local * sizeof(float4), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->partial, 0xFF, (size_t)k.n_local * sizeof(TrajPartial), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->st_pp, 0xFF, (size_t)k.n_local * sizeof(double2), ctx->stream));
   }
   k.seq = ++ctx->seq;
   if (k.seq == 0) k.seq = ctx->seq = 1;
@@ -750,7 +755,7 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
     hipLaunchKernelGGL(k_bin_count, dim3(p.cnt_blocks + p.roll_blocks + (k.use_assign ? k.assign_groups : 0)), dim3(kBinThreads),
                        p.roll_launch_lds, ctx->stream, k, pin.dev(), ctx->cell_count, ctx->cell_start, ctx->pt_slot, ctx->tickets,
                        ctx->best_key, ctx->overflow, ctx->axes_dev, ctx->samples_dev, ctx->traj_info, ctx->st_sc,
-                       ctx->st_xy, ctx->traj_load, ctx->assign, p.heading_rows);
+                       ctx->st_xy, ctx->st_pp, ctx->traj_load, ctx->assign, p.heading_rows);
     hipLaunchKernelGGL(k_bin_scatter, dim3(p.bin_blocks), dim3(256), 0, ctx->stream, k, pin.dev(),
                        ctx->pt_slot, ctx->cell_start, ctx->sorted, ctx->row_tab);
   } else {
@@ -758,7 +763,7 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
                        ctx->best_key, ctx->overflow);
     if (p.roll_blocks > 0)
       hipLaunchKernelGGL(k_rollout, dim3(p.roll_blocks), dim3(256), p.roll_launch_lds, ctx->stream, k, ctx->axes_dev,
-                         ctx->samples_dev, ctx->traj_info, ctx->st_sc, ctx->st_xy, p.heading_rows);
+                         ctx->samples_dev, ctx->traj_info, ctx->st_sc, ctx->st_xy, ctx->st_pp, p.heading_rows);
     if (k.use_assign)
       hipLaunchKernelGGL(k_assign, dim3(k.assign_groups), dim3(kBinThreads), 0, ctx->stream, k, ctx->traj_load, ctx->assign);
   }
@@ -776,7 +781,8 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
   hipLaunchKernelGGL((k_score<T, L, P>), dim3(wgs), dim3(T), lds, ctx->stream, k, ctx->traj_info, ctx->st_sc,     \
                      ctx->st_xy, ctx->plan_dev, ctx->cell_start, ctx->sorted, ctx->costs, ctx->steps,             \
                      ctx->samples_out, ctx->best_key, ctx->overflow, ctx->tickets + 1, score_result, ctx->assign, \
-                     ctx->traj_load, score_words, ctx->row_tab, ctx->plan_pairs_dev, ctx->partial, p.fused_walk)
+                     ctx->traj_load, score_words, ctx->row_tab, ctx->plan_pairs_dev, ctx->partial, p.fused_walk,  \
+                     ctx->st_pp)
     if (p.thr == 512) { if (p.lean) DDDMR_LAUNCH_SCORE(512, true); else DDDMR_LAUNCH_SCORE(512, false); }
     else              { if (p.lean) DDDMR_LAUNCH_SCORE(256, true); else DDDMR_LAUNCH_SCORE(256, false); }
 #undef DDDMR_LAUNCH_SCORE

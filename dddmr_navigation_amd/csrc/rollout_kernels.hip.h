@@ -485,7 +485,7 @@ __global__ __launch_bounds__(256) void k_bin_scatter(DevTick k, const float4* __
 // (TrajInfo::hrow names a trajectory's row either way).
 // ---------------------------------------------------------------------------
 #ifdef DDDMR_PHASE_STAMPS
-constexpr int kStampSlots = 20;      // 0..11 s_memtime per phase, 12 / 13 s_memrealtime (100 MHz, chip-wide) at start / end, 14 XCC | CU id, 15..18 the last workgroup's hand-off
+constexpr int kStampSlots = 20;      // 0..11 s_memtime per phase, 12 / 13 s_memrealtime (100 MHz, chip-wide) at start / end, 14 XCC | CU id, 15..18 the last workgroup's hand-off, 19 wave 0 leaves D1's pair loop
 __device__ unsigned long long g_stamps[16384 * kStampSlots];
 #define DDDMR_STAMP(i)                                                                         \
   do {                                                                                         \
@@ -533,11 +533,47 @@ __host__ __device__ inline size_t rollout_lds_bytes(int rt, int max_steps) {
   return (size_t)rt * (size_t)(max_steps + 1) * 16 + 16;   // one 16-byte slot per (trajectory, step): theta, then the increment
 }
 
+// translation of trans_gbl2traj = pos_af3 * [Rz(theta), (x, y, 0)] (one definition so
+// that every phase rounds it identically)
+__host__ __device__ __forceinline__ void pose_translation(const DevTick& k, float2 bxy, double T[3]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) T[i] = k.R[3 * i + 0] * (double)bxy.x + k.R[3 * i + 1] * (double)bxy.y + k.t[i];
+}
+
+// PurePursuitModel on a trajectory's last pose (pure_pursuit_model.cpp:86-113): (|translation|, folded yaw) of
+// D = inverse(T_traj) * T_plan against the LAST plan pose.  `bxy` and `cs` are the last step's entries of st_xy and
+// st_sc exactly as stored.  It depends on nothing but that pose, so the rollout computes it, one lane per trajectory,
+// and k_score only loads the pair (the weights are applied by the stacked scoring: they are per critic).
+__host__ __device__ inline double2 pure_pursuit_last_pose(const DevTick& k, const float2 bxy, const double2 cs) {
+  const double c = cs.x, sn = cs.y;
+  // trans_gbl2traj = pos_af3 * [Rz(theta), (x, y, 0)]
+  double L[9], T[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double r0 = k.R[3 * i + 0], r1 = k.R[3 * i + 1], r2 = k.R[3 * i + 2];
+    L[3 * i + 0] = r0 * c + r1 * sn;
+    L[3 * i + 1] = r1 * c - r0 * sn;
+    L[3 * i + 2] = r2;
+  }
+  pose_translation(k, bxy, T);
+  // rotation part L^T * planR, translation L^T (planT - T)
+  const double d0 = k.planT[0] - T[0], d1 = k.planT[1] - T[1], d2 = k.planT[2] - T[2];
+  const double tx = L[0] * d0 + L[3] * d1 + L[6] * d2;
+  const double ty = L[1] * d0 + L[4] * d1 + L[7] * d2;
+  const double tz = L[2] * d0 + L[5] * d1 + L[8] * d2;
+  const double D00 = L[0] * k.planR[0] + L[3] * k.planR[3] + L[6] * k.planR[6];
+  const double D10 = L[1] * k.planR[0] + L[4] * k.planR[3] + L[7] * k.planR[6];
+  const double D20 = L[2] * k.planR[0] + L[5] * k.planR[3] + L[8] * k.planR[6];
+  double yaw = 0.0;
+  if (fabs(D20) < 1.0) yaw = atan2(D10, D00);   // getEulerYPR, solution 1
+  return make_double2(sqrt(tx * tx + ty * ty + tz * tz), fmod(yaw + 3.1416, 3.1416));
+}
+
 template <int kThreads>
 __device__ __forceinline__ void rollout_block(const DevTick& k, const int block, const float* __restrict__ axes,
                                               const float4* __restrict__ samples, TrajInfo* __restrict__ info,
                                               double2* __restrict__ st_sc, float2* __restrict__ st_xy,
-                                              unsigned char* roll_lds, const bool shared) {
+                                              double2* __restrict__ st_pp, unsigned char* roll_lds, const bool shared) {
   const int S1 = k.max_steps + 1;
   const int rt = k.rt;
   // [rt][S1] slots of 16 bytes.  Phase A leaves theta_s in ONE float of the slot, phase B (the lane that read it)
@@ -748,6 +784,8 @@ __device__ __forceinline__ void rollout_block(const DevTick& k, const int block,
           iy += (double)vy * s2;
         }
         inc[idx] = make_double2(ix * dt_s[j], iy * dt_s[j]);
+      } else if (s >= 1) {
+        inc[idx] = make_double2(cs, sn);    // slot ns holds no increment: the last heading stays for pure pursuit below
       }
     }
   }
@@ -792,6 +830,19 @@ __device__ __forceinline__ void rollout_block(const DevTick& k, const int block,
       const float* slot = reinterpret_cast<const float*>(inc + idx);
       st_xy[(size_t)li_s[j] * k.max_steps + s] = make_float2(slot[0], slot[2]);
     }
+  }
+  // ---- pure pursuit on the last pose: one lane per trajectory, from the values st_xy and st_sc hold for step ns - 1
+  // (the position in its slot, the heading in slot ns or, with shared rows, in the class's row).  A trajectory that was
+  // not generated gets zeros, which nobody reads.
+  if (tid < nt) {
+    const int ns = steps_s[tid];
+    double2 pp = make_double2(0.0, 0.0);
+    if (ns > 0) {
+      const float* slot = reinterpret_cast<const float*>(inc + (size_t)tid * S1 + (ns - 1));
+      const double2 cs = shared ? hrow[(int)lc_s[tid] * S1 + ns] : inc[(size_t)tid * S1 + ns];
+      pp = pure_pursuit_last_pose(k, make_float2(slot[0], slot[2]), cs);
+    }
+    st_pp[li_s[tid]] = pp;
   }
   DDDMR_RSTAMP(3);
 }
@@ -905,9 +956,10 @@ __global__ __launch_bounds__(kBinThreads) void k_assign(DevTick k, const uint32_
 __global__ __launch_bounds__(256) void k_rollout(DevTick k, const float* __restrict__ axes,
                                                  const float4* __restrict__ samples,
                                                  TrajInfo* __restrict__ info, double2* __restrict__ st_sc,
-                                                 float2* __restrict__ st_xy, const int heading_rows) {
+                                                 float2* __restrict__ st_xy, double2* __restrict__ st_pp,
+                                                 const int heading_rows) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
-  rollout_block<256>(k, (int)blockIdx.x, axes, samples, info, st_sc, st_xy, dyn_lds, heading_rows != 0);
+  rollout_block<256>(k, (int)blockIdx.x, axes, samples, info, st_sc, st_xy, st_pp, dyn_lds, heading_rows != 0);
 }
 
 // Crop the cloud to the local costmap tile and count points per cell; the LAST
@@ -925,8 +977,8 @@ __global__ __launch_bounds__(kBinThreads, 8) void k_bin_count(DevTick k, const f
                                                    uint32_t* __restrict__ overflow, const float* __restrict__ axes,
                                                    const float4* __restrict__ samples, TrajInfo* __restrict__ info,
                                                    double2* __restrict__ st_sc, float2* __restrict__ st_xy,
-                                                   const uint32_t* __restrict__ load, uint32_t* __restrict__ assign,
-                                                   const int heading_rows) {
+                                                   double2* __restrict__ st_pp, const uint32_t* __restrict__ load,
+                                                   uint32_t* __restrict__ assign, const int heading_rows) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
   // Longest first: the assignment workgroups (only launched with use_assign), the rollout, then the binning
   // workgroups -- when the launch does not fit the chip in one round, the short ones fill the tail.
@@ -936,7 +988,7 @@ __global__ __launch_bounds__(kBinThreads, 8) void k_bin_count(DevTick k, const f
     return;
   }
   if ((int)blockIdx.x < n_assign + k.roll_blocks) {
-    rollout_block<kBinThreads>(k, (int)blockIdx.x - n_assign, axes, samples, info, st_sc, st_xy, dyn_lds, heading_rows != 0);
+    rollout_block<kBinThreads>(k, (int)blockIdx.x - n_assign, axes, samples, info, st_sc, st_xy, st_pp, dyn_lds, heading_rows != 0);
     return;
   }
   const int bin_block = (int)blockIdx.x - n_assign - k.roll_blocks;
@@ -1025,8 +1077,8 @@ struct TrajHead {     // per-trajectory header in LDS
   int pair_base;      // first flattened (traj,step) pair of this trajectory
   int hit_box;        // CollisionModel verdict
   int hit_mm;         // CollisionMinMaxModel verdict
-  int aux;            // TrajInfo::hrow (row of st_sc) through phase D1 and pure pursuit; from phase P on the first surviving pair
-  double pp_dist;     // PurePursuitModel: |translation| of the pose difference
+  int aux;            // TrajInfo::hrow (row of st_sc) through phase D1; from phase P on the first surviving pair
+  double pp_dist;     // PurePursuitModel: |translation| of the pose difference (from the rollout's st_pp, phase A)
   double pp_yaw;      // PurePursuitModel: folded yaw of the pose difference
   double stick_sum;   // StickPathModel: sum of the per-step 1-NN distances
   int li;             // local trajectory index (row of the k_rollout state arrays)
@@ -1294,13 +1346,6 @@ __device__ __forceinline__ int box_test2(const float* r, const Pt3 a, const Pt3 
   return (h0 ? 1 : 0) | (h1 ? 2 : 0);
 }
 
-// translation of trans_gbl2traj = pos_af3 * [Rz(theta), (x, y, 0)] (one definition so
-// that every phase rounds it identically)
-__device__ __forceinline__ void pose_translation(const DevTick& k, float2 bxy, double T[3]) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) T[i] = k.R[3 * i + 0] * (double)bxy.x + k.R[3 * i + 1] * (double)bxy.y + k.t[i];
-}
-
 // OBB record words [3..14]: the cuboid's vertices blb, brb, blt, flb as phase D1 left them -> axes (x: blb->flb,
 // y: blb->brb, z: blb->blt, collision_model.cpp:97-110) and half extents (:112-115), in place.
 __device__ __forceinline__ void obb_axes_in_place(float* r) {
@@ -1424,7 +1469,8 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
     float4* __restrict__ samples_out, int64_t* __restrict__ best_key, uint32_t* __restrict__ overflow,
     uint32_t* __restrict__ ticket, DevResult* __restrict__ result, const uint32_t* __restrict__ assign,
     uint32_t* __restrict__ traj_load, int64_t* __restrict__ words_out, const uint32_t* __restrict__ row_tab,
-    const float* __restrict__ plan_pairs, TrajPartial* __restrict__ partial, const int fused_walk) {
+    const float* __restrict__ plan_pairs, TrajPartial* __restrict__ partial, const int fused_walk,
+    const double2* __restrict__ st_pp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int tile = k.tile;
   const int S1 = k.max_steps + 1;
@@ -1477,14 +1523,44 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
   for (int j = 0; j < tile; ++j) nt += ((tb < k.nb_tiles || j + k.r0 < tile) && tile_slot(k, tb, j) < k.n_local) ? 1 : 0;
 
   DDDMR_STAMP(0);
-  // ---- stage the prune plan (float xyz, model_shared_data.h:83-91) ----
-  for (int i = tid; i < k.m; i += kScoreThreads) plan[i] = plan_xyz[i];
-
-  // ---- phase A: trajectory headers from k_rollout ----
-  if (tid < nt) {
+  // ---- phase A: trajectory headers from the rollout, the costmap's row-run index and the prune plan into LDS ----
+  // Every load is issued before the first one is waited for: the slot's trajectory (the header loads depend on it),
+  // the index, the plan, then the header; the LDS writes follow.  (A copy loop of unknown trip count waits for each
+  // load before it issues the next: that was 4 to 8 serial round trips per wave.)
+  const bool has_traj = tid < nt;
+  int li = 0;
+  if (has_traj) {
     const int slot = tile_slot(k, tb, tid);
-    const int li = k.use_assign ? (int)assign[slot] : slot;
+    li = k.use_assign ? (int)assign[slot] : slot;
+  }
+  // the index (built by k_bin_scatter): at most kTabCap entries, so a lane copies kTabCap / kScoreThreads of them, four
+  // to a load; the (< 4) entries behind the last whole quad go one to a lane
+  const int tab_n = k.tab_entries;          // (gnx+1)*gny, or 0 when the index does not fit
+  const bool tab_staged = tab_n > 0;
+  const bool copy_tab = tab_staged && k.n_points >= 5 && (need_box || need_mm);
+  constexpr int kTabQuads = kTabCap / (4 * kScoreThreads);
+  static_assert(kTabQuads * 4 * kScoreThreads == kTabCap, "the index copy covers kTabCap exactly");
+  const int tab_q = tab_n >> 2, tab_r = tab_n & 3;
+  uint4 tq[kTabQuads];
+  uint32_t tq_tail = 0u;
+  if (copy_tab) {
+    // (a lane beyond the last quad loads the last quad again and stores nothing: straight-line code, in bounds)
+    const int last_q = tab_q > 0 ? tab_q - 1 : 0;
+#pragma unroll
+    for (int e = 0; e < kTabQuads; ++e) {
+      tq[e] = make_uint4(0u, 0u, 0u, 0u);
+      if (tab_q > 0) tq[e] = reinterpret_cast<const uint4*>(row_tab)[min(tid + e * kScoreThreads, last_q)];
+    }
+    if (tid < tab_r) tq_tail = row_tab[4 * tab_q + tid];
+  }
+  // the plan's LDS copy (float xyz, model_shared_data.h:83-91) has one reader, the split search of phase P: a fused
+  // tick walks plan_pairs through the scalar unit and skips it
+  const bool copy_plan = !fused;
+  float4 plan_mine = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (copy_plan && tid < k.m) plan_mine = plan_xyz[tid];
+  if (has_traj) {
     const TrajInfo ti = info[li];
+    const double2 pp = st_pp[li];          // pure pursuit on the last pose, from the rollout
     if (ti.over) atomicOr(overflow, 1u);
     TrajHead h;
     h.vx = ti.vx; h.vy = ti.vy; h.w = ti.w;
@@ -1492,16 +1568,24 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
     h.dt = ti.dt;
     h.pair_base = 0;
     h.hit_box = 0; h.hit_mm = 0; h.aux = ti.hrow;
-    h.pp_dist = 0.0; h.pp_yaw = 0.0; h.stick_sum = 0.0;
+    h.pp_dist = pp.x; h.pp_yaw = pp.y; h.stick_sum = 0.0;   // (zeros for a trajectory that was not generated)
     h.li = li;
     h.walked = 0;
     head[tid] = h;
   }
-  // the costmap's row-run index is staged meanwhile (independent loads)
-  const int tab_n = k.tab_entries;          // (gnx+1)*gny, or 0 when the index does not fit
-  const bool tab_staged = tab_n > 0;
-  if (tab_staged && k.n_points >= 5 && (need_box || need_mm)) {
-    for (int i = tid; i < tab_n; i += kScoreThreads) tab[i] = row_tab[i];       // (built by k_bin_scatter)
+  if (copy_tab) {
+#pragma unroll
+    for (int e = 0; e < kTabQuads; ++e) {
+      const int i4 = tid + e * kScoreThreads;
+      if (i4 < tab_q) {        // (tab is only 4-byte aligned in the carve: word stores)
+        tab[4 * i4 + 0] = tq[e].x; tab[4 * i4 + 1] = tq[e].y; tab[4 * i4 + 2] = tq[e].z; tab[4 * i4 + 3] = tq[e].w;
+      }
+    }
+    if (tid < tab_r) tab[4 * tab_q + tid] = tq_tail;
+  }
+  if (copy_plan) {
+    if (tid < k.m) plan[tid] = plan_mine;
+    for (int i = tid + kScoreThreads; i < k.m; i += kScoreThreads) plan[i] = plan_xyz[i];   // (kMaxPlan poses, 256 lanes)
   }
   __syncthreads();
   DDDMR_STAMP(1);   // end of phase A
@@ -1525,8 +1609,11 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
     const int s = q - head[j].pair_base;
     const size_t so = (size_t)head[j].li * k.max_steps + s;
     const double2 cs = st_sc[(size_t)head[j].aux * k.max_steps + s];   // heading after the step
-    const float2 bxy = st_xy[so];                    // body-frame position after the step
-    const double c = cs.x, sn = cs.y;
+    float2 bxy = st_xy[so];                          // body-frame position after the step
+    double c = cs.x, sn = cs.y;
+    // Both state loads in flight before either is waited for: one round trip, not two (left alone, the heading's load
+    // sinks into the collision branch behind the pose's store).  The empty statement below uses all four values.
+    asm volatile("" : "+v"(c), "+v"(sn), "+v"(bxy.x), "+v"(bxy.y));
     // trans_gbl2traj = pos_af3 * [Rz(theta), (x, y, 0)]
     double L[9], T[3];
 #pragma unroll
@@ -1682,37 +1769,7 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
       if (cy1 - cy0 + 1 > k.rows_cap) atomicOr(overflow, 2u);   // host sizes the cells so this cannot happen
     }
   }
-  // ---- pure pursuit on the last pose (pure_pursuit_model.cpp:86-113): one lane per
-  // trajectory, after the pair loop so that only one wave pays for the atan2 ----
-  if (tid < nt && head[tid].steps > 0) {
-    const int j = tid;
-    const size_t so = (size_t)head[j].li * k.max_steps + (head[j].steps - 1);
-    const double2 cs = st_sc[(size_t)head[j].aux * k.max_steps + (head[j].steps - 1)];
-    const float2 bxy = st_xy[so];
-    const double c = cs.x, sn = cs.y;
-    double L[9], T[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const double r0 = k.R[3 * i + 0], r1 = k.R[3 * i + 1], r2 = k.R[3 * i + 2];
-      L[3 * i + 0] = r0 * c + r1 * sn;
-      L[3 * i + 1] = r1 * c - r0 * sn;
-      L[3 * i + 2] = r2;
-    }
-    pose_translation(k, bxy, T);
-    // D = inverse(T_traj) * T_plan ; rotation part L^T * planR, translation L^T (planT - T)
-    const double d0 = k.planT[0] - T[0], d1 = k.planT[1] - T[1], d2 = k.planT[2] - T[2];
-    const double tx = L[0] * d0 + L[3] * d1 + L[6] * d2;
-    const double ty = L[1] * d0 + L[4] * d1 + L[7] * d2;
-    const double tz = L[2] * d0 + L[5] * d1 + L[8] * d2;
-    const double D00 = L[0] * k.planR[0] + L[3] * k.planR[3] + L[6] * k.planR[6];
-    const double D10 = L[1] * k.planR[0] + L[4] * k.planR[3] + L[7] * k.planR[6];
-    const double D20 = L[2] * k.planR[0] + L[5] * k.planR[3] + L[8] * k.planR[6];
-    double yaw = 0.0;
-    if (fabs(D20) < 1.0) yaw = atan2(D10, D00);   // getEulerYPR, solution 1
-    // weights are applied in phase E (they are per-critic)
-    head[j].pp_dist = sqrt(tx * tx + ty * ty + tz * tz);
-    head[j].pp_yaw = fmod(yaw + 3.1416, 3.1416);
-  }
+  DDDMR_STAMP(19);  // wave 0 leaves the pair loop (the rest of D1 is its wait for the other waves)
   __syncthreads();
 
   DDDMR_STAMP(4);   // end of phase D1
@@ -1875,7 +1932,11 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
       return lo;
     };
     const int n_rounds = (kProbe && total > (uint32_t)kScoreThreads) ? 2 : 1;
+    // A walk of one round decides nothing before it: its prefix of the undecided trajectories' items is t_item0 itself,
+    // element for element, which lies behind D2's last barrier -- no scan, no barrier.
+    const uint32_t* const t_ubase_r = n_rounds == 1 ? t_item0 : t_ubase;
     for (int round = 0; round < n_rounds; ++round) {
+      if (n_rounds > 1) {
       if (tid < 64) {                               // exclusive prefix of the undecided trajectories' item counts
         uint32_t cnt = 0;
         if (tid < nt) {
@@ -1887,21 +1948,22 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
         if (tid == nt - 1) t_ubase[nt] = incl;
       }
       __syncthreads();
-      const uint32_t tot_r = t_ubase[nt];
+      }
+      const uint32_t tot_r = t_ubase_r[nt];
       const uint32_t chunk = (tot_r + kScoreThreads - 1) / kScoreThreads;
       uint32_t p = (uint32_t)tid * chunk;
       const uint32_t p1 = min(tot_r, p + ((round == 0 && n_rounds == 2) ? 1u : chunk));
       if (p < p1) {
         int j = 0;
-        while (t_ubase[j + 1] <= p) ++j;
-        uint32_t it = t_item0[j] + (p - t_ubase[j]);
+        while (t_ubase_r[j + 1] <= p) ++j;
+        uint32_t it = t_item0[j] + (p - t_ubase_r[j]);
         int sg = find_seg(it, 0);
         for (;;) {
           walk_item(it, sg);
           if (++p >= p1) break;
-          if (p >= t_ubase[j + 1]) {                  // next undecided trajectory
-            do { ++j; } while (t_ubase[j + 1] <= p);
-            it = t_item0[j] + (p - t_ubase[j]);
+          if (p >= t_ubase_r[j + 1]) {                // next undecided trajectory
+            do { ++j; } while (t_ubase_r[j + 1] <= p);
+            it = t_item0[j] + (p - t_ubase_r[j]);
             sg = find_seg(it, sg);
           } else {
             ++it;

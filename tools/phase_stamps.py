@@ -36,6 +36,10 @@ with LocalPlanner([sc.theory], max_points=max(len(sc.cloud), 16)) as lp:
     for i, nm in enumerate(names):
         d = (st[:, i + 1] - st[:, i]) / 1000.0   # kilo-cycles (s_memtime counts shader clocks)
         print(f"  {nm:18s} mean {d.mean():8.2f} kc  p50 {np.percentile(d,50):8.2f}  p99 {np.percentile(d,99):8.2f}  max {d.max():8.2f}")
+    if (st[:, 19] > 0).all():    # (a library built from an older commit has no such stamp)
+        loop = (st[:, 19] - st[:, 3]) / 1000.0; rest = (st[:, 4] - st[:, 19]) / 1000.0
+        print(f"    D1 split: wave 0's pair loop mean {loop.mean():6.2f} kc p50 {np.percentile(loop,50):6.2f} | from there to the end of "
+              f"D1 (wave 0 waits for the other waves) mean {rest.mean():6.2f} p50 {np.percentile(rest,50):6.2f}")
     dP = (st[:, 8] - st[:, 6]) / 1000.0; dE = (st[:, 7] - st[:, 8]) / 1000.0
     print(f"    of which P path 1-NN mean {dP.mean():8.2f} kc max {dP.max():8.2f};  E stick+score+argmin mean {dE.mean():8.2f} max {dE.max():8.2f}")
     e1 = (st[:, 10] - st[:, 8]) / 1000.0; e2 = (st[:, 11] - st[:, 10]) / 1000.0; e3 = (st[:, 7] - st[:, 11]) / 1000.0
