@@ -180,6 +180,8 @@ struct dddmr_rollout_ctx {
   int spin = 1;     // DDDMR_SPIN: poll the host-mapped result instead of hipStreamSynchronize
   int last_heading_rows = -1; // what the last launched tick did (dddmr_rollout_heading_rows)
   int last_fused_walk = -1;   // ... and which way its k_score walked the prune plan (dddmr_rollout_fused_walk)
+  int last_deal = -1;         // ... and how its assignment dealt the trajectories (dddmr_rollout_deal)
+  int last_assigned = 0;      // ... and whether it had an assignment at all (dddmr_rollout_get_deal)
   uint32_t seq = 0;
   DevResult last_result{};   // host copy of the last COLLECTED tick's result
   float last_score_ms = 0.f, last_device_ms = 0.f;
@@ -305,6 +307,7 @@ void read_env(dddmr_rollout_ctx* ctx) {
   if (const char* e = std::getenv("DDDMR_TAIL_ROUND")) kn.tail_round = std::atoi(e) != 0;
   if (const char* e = std::getenv("DDDMR_HEADING_ROWS")) kn.heading_rows = std::atoi(e) != 0;
   if (const char* e = std::getenv("DDDMR_FUSE_WALK")) kn.fuse_walk = std::atoi(e) != 0;
+  if (const char* e = std::getenv("DDDMR_DEAL")) kn.deal_mode = std::min(std::max(std::atoi(e), -1), 2);
   if (const char* e = std::getenv("DDDMR_FINAL")) kn.final_mode = std::atoi(e) ? 1 : 0;
   if (const char* e = std::getenv("DDDMR_PROBE")) kn.probe_mode = std::atoi(e) ? 1 : 0;
   if (const char* e = std::getenv("DDDMR_TIMING")) ctx->timing = std::atoi(e);
@@ -478,10 +481,11 @@ int dddmr_rollout_create(const dddmr_rollout_config* cfg, dddmr_rollout_ctx** ou
     {
       const void* big_lds_kernels[] = {
           reinterpret_cast<const void*>(k_rollout), reinterpret_cast<const void*>(k_bin_count),
-          reinterpret_cast<const void*>(k_score<256, false, false>), reinterpret_cast<const void*>(k_score<256, false, true>),
-          reinterpret_cast<const void*>(k_score<256, true, false>),  reinterpret_cast<const void*>(k_score<256, true, true>),
-          reinterpret_cast<const void*>(k_score<512, false, false>), reinterpret_cast<const void*>(k_score<512, false, true>),
-          reinterpret_cast<const void*>(k_score<512, true, false>),  reinterpret_cast<const void*>(k_score<512, true, true>)};
+#define DDDMR_SCORE_KERNELS(T, L) \
+  reinterpret_cast<const void*>(k_score<T, L, false, false>), reinterpret_cast<const void*>(k_score<T, L, true, false>), \
+  reinterpret_cast<const void*>(k_score<T, L, false, true>), reinterpret_cast<const void*>(k_score<T, L, true, true>)
+          DDDMR_SCORE_KERNELS(256, false), DDDMR_SCORE_KERNELS(256, true), DDDMR_SCORE_KERNELS(512, false), DDDMR_SCORE_KERNELS(512, true)};
+#undef DDDMR_SCORE_KERNELS
       for (const void* f : big_lds_kernels) HIPCHK(ctx, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kScoreLdsMax));
     }
     HIPCHK(ctx, hipDeviceSynchronize());
@@ -750,12 +754,14 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
   ctx->feedback.load_nlocal = k.n_local;
   ctx->last_heading_rows = p.heading_rows;
   ctx->last_fused_walk = k.n_local > 0 ? p.fused_walk : 0;
+  ctx->last_deal = p.deal;
+  ctx->last_assigned = k.use_assign;
   drain.armed = true;       // from here on the stream reads the pinned cloud
   if (k.n_points > 0) {
     hipLaunchKernelGGL(k_bin_count, dim3(p.cnt_blocks + p.roll_blocks + (k.use_assign ? k.assign_groups : 0)), dim3(kBinThreads),
                        p.roll_launch_lds, ctx->stream, k, pin.dev(), ctx->cell_count, ctx->cell_start, ctx->pt_slot, ctx->tickets,
                        ctx->best_key, ctx->overflow, ctx->axes_dev, ctx->samples_dev, ctx->traj_info, ctx->st_sc,
-                       ctx->st_xy, ctx->st_pp, ctx->traj_load, ctx->assign, p.heading_rows);
+                       ctx->st_xy, ctx->st_pp, ctx->traj_load, ctx->assign, p.heading_rows, p.deal, p.deal_head);
     hipLaunchKernelGGL(k_bin_scatter, dim3(p.bin_blocks), dim3(256), 0, ctx->stream, k, pin.dev(),
                        ctx->pt_slot, ctx->cell_start, ctx->sorted, ctx->row_tab);
   } else {
@@ -765,7 +771,8 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
       hipLaunchKernelGGL(k_rollout, dim3(p.roll_blocks), dim3(256), p.roll_launch_lds, ctx->stream, k, ctx->axes_dev,
                          ctx->samples_dev, ctx->traj_info, ctx->st_sc, ctx->st_xy, ctx->st_pp, p.heading_rows);
     if (k.use_assign)
-      hipLaunchKernelGGL(k_assign, dim3(k.assign_groups), dim3(kBinThreads), 0, ctx->stream, k, ctx->traj_load, ctx->assign);
+      hipLaunchKernelGGL(k_assign, dim3(k.assign_groups), dim3(kBinThreads), 0, ctx->stream, k, ctx->traj_load, ctx->assign, p.deal,
+                         p.deal_head);
   }
   if (timed) HIPCHK(ctx, hipEventRecord(ctx->evs0, ctx->stream));
   // multi-rank context: k_score leaves the shard's winner on the device (staging record + its slot of
@@ -778,15 +785,18 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
 #define DDDMR_LAUNCH_SCORE(T, L)                                                                                   \
   do { if (k.probe) DDDMR_LAUNCH_SCORE_P(T, L, true); else DDDMR_LAUNCH_SCORE_P(T, L, false); } while (0)
 #define DDDMR_LAUNCH_SCORE_P(T, L, P)                                                                              \
-  hipLaunchKernelGGL((k_score<T, L, P>), dim3(wgs), dim3(T), lds, ctx->stream, k, ctx->traj_info, ctx->st_sc,     \
+  do { if (p.deal != kDealSnake) DDDMR_LAUNCH_SCORE_K(T, L, P, true); else DDDMR_LAUNCH_SCORE_K(T, L, P, false); } while (0)
+#define DDDMR_LAUNCH_SCORE_K(T, L, P, I)                                                                           \
+  hipLaunchKernelGGL((k_score<T, L, P, I>), dim3(wgs), dim3(T), lds, ctx->stream, k, ctx->traj_info, ctx->st_sc,     \
                      ctx->st_xy, ctx->plan_dev, ctx->cell_start, ctx->sorted, ctx->costs, ctx->steps,             \
                      ctx->samples_out, ctx->best_key, ctx->overflow, ctx->tickets + 1, score_result, ctx->assign, \
                      ctx->traj_load, score_words, ctx->row_tab, ctx->plan_pairs_dev, ctx->partial, p.fused_walk,  \
-                     ctx->st_pp)
+                     ctx->st_pp, p.deal)
     if (p.thr == 512) { if (p.lean) DDDMR_LAUNCH_SCORE(512, true); else DDDMR_LAUNCH_SCORE(512, false); }
     else              { if (p.lean) DDDMR_LAUNCH_SCORE(256, true); else DDDMR_LAUNCH_SCORE(256, false); }
 #undef DDDMR_LAUNCH_SCORE
 #undef DDDMR_LAUNCH_SCORE_P
+#undef DDDMR_LAUNCH_SCORE_K
   } else {
     hipLaunchKernelGGL(k_empty_result, dim3(1), dim3(64), 0, ctx->stream, k, ctx->cell_start, score_result, score_words);
   }
@@ -1002,6 +1012,36 @@ int dddmr_rollout_fused_walk(dddmr_rollout_ctx* ctx) {
   if (!ctx) return -1;
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   return ctx->last_fused_walk;
+}
+
+int dddmr_rollout_deal(dddmr_rollout_ctx* ctx) {
+  if (!ctx) return -1;
+  std::lock_guard<std::mutex> tk(ctx->tick_mu);
+  return ctx->last_deal;
+}
+
+int dddmr_rollout_get_deal(dddmr_rollout_ctx* ctx, uint32_t* assign_out, uint32_t* load_out, size_t capacity, size_t* n_local,
+                           int32_t* assigned) {
+  if (!ctx || !n_local) return DDDMR_ERR_BAD_ARG;
+  std::lock_guard<std::mutex> tk(ctx->tick_mu);
+  if (!ctx->have_last) return fail(ctx, DDDMR_ERR_STATE, "get_deal before any tick");
+  if (ctx->pend.active) return refuse_pending(ctx, "get_deal");
+  const size_t n = (size_t)ctx->last.n_local;
+  *n_local = n;
+  if (assigned) *assigned = ctx->last_assigned;
+  if ((!assign_out && !load_out) || n == 0) return DDDMR_OK;
+  if (capacity < n) return fail(ctx, DDDMR_ERR_CAPACITY, "get_deal: capacity %zu < %zu", capacity, n);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (assign_out) {
+    if (ctx->last_assigned) {
+      HIPCHK(ctx, hipMemcpy(assign_out, ctx->assign, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    } else {
+      for (size_t i = 0; i < n; ++i) assign_out[i] = (uint32_t)i;     // strided: slot s holds trajectory s
+    }
+  }
+  if (load_out) HIPCHK(ctx, hipMemcpy(load_out, ctx->traj_load, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return DDDMR_OK;
 }
 
 int dddmr_rollout_get_debug(dddmr_rollout_ctx* ctx, dddmr_rollout_debug* dbg) {

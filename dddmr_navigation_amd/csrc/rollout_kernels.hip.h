@@ -180,10 +180,12 @@ __host__ __device__ inline size_t heading_rows_lds_bytes(int max_steps, bool omn
 }
 
 // Load feedback: every tick k_score files what each trajectory cost it (collision
-// work items actually walked, path-critic work, pairs); the next tick's assignment
+// work items actually walked -- on a sorted deal its candidate items, a key that does not depend on the deal --,
+// path-critic work, pairs); the next tick's assignment
 // block (rides along with k_bin_count, like the rollout) deals the trajectories to
-// the tiles heaviest-first in snake order, so that all workgroups carry the same
-// load and the launch has no long tail.  Any assignment gives identical results.
+// the tiles heaviest-first: in snake order where the shard runs as one round of workgroups, so that all of them carry
+// the same load and the launch has no long tail, sorted where it runs as several, so that the launch ends on its
+// cheapest workgroups (deal_slot()).  Any assignment gives identical results.
 constexpr int kLoadClasses = 1024;
 constexpr int kAssignMax = 1 << 18;    // larger shards keep the strided assignment (64 groups of 4096)
 
@@ -848,8 +850,9 @@ __device__ __forceinline__ void rollout_block(const DevTick& k, const int block,
 }
 
 // Assignment blocks: counting sort of the shard's trajectories by last tick's load,
-// heaviest first, then dealt to the tiles in snake order (rank r -> round r / tiles,
-// tile r % tiles, reversed in odd rounds).  Slot [round * n_tiles + tile] of assign[]
+// heaviest first, then dealt to the tiles by deal_slot() below: in snake order (rank r -> round r / tiles,
+// tile r % tiles, reversed in odd rounds) on shards of one round of resident workgroups, sorted (tile r / tile size)
+// on shards of several (TickPlan::deal).  Slot [round * n_tiles + tile] of assign[]
 // is what k_score reads.  Big shards are cut into k.assign_groups independent
 // groups, one workgroup each: group g owns the trajectories AND the tiles congruent
 // to g (n_tiles is a multiple of the group count), so every group deals a
@@ -862,27 +865,34 @@ __device__ __forceinline__ void rollout_block(const DevTick& k, const int block,
 // rest (measured: no gain, rollout_engine.hip; the default keeps nb_tiles = n_tiles, r0 = 0).  Slots are
 // numbered round by round, so slot s of round r belongs to workgroup s - base(r), and base(r) is a multiple of the
 // assignment groups: group g owns exactly the slots = g (mod groups), as before.
-__device__ __forceinline__ int tile_round_base(const DevTick& k, int r) {
+__host__ __device__ __forceinline__ int tile_round_base(const DevTick& k, int r) {
   return r < k.r0 ? r * k.nb_tiles : k.r0 * k.nb_tiles + (r - k.r0) * k.n_tiles;
 }
-__device__ __forceinline__ int tile_slot(const DevTick& k, int b, int j) {     // j-th slot of workgroup b
+__host__ __device__ __forceinline__ int tile_slot(const DevTick& k, int b, int j) {     // j-th slot of workgroup b
   return tile_round_base(k, b < k.nb_tiles ? j : j + k.r0) + b;
 }
-constexpr int kAssignPer = 4;          // trajectories per lane of an assignment block (held in registers)
-template <int kThreads>
-__device__ __forceinline__ void assign_block(const DevTick& k, const int grp, const uint32_t* __restrict__ load,
-                                             uint32_t* __restrict__ assign) {
-  __shared__ uint32_t hist[kLoadClasses];
-  __shared__ uint32_t wsum[kThreads / 64];
-  __shared__ uint32_t mx_s, mn_s;
-  static_assert(kLoadClasses == kThreads, "one class per lane in the scan");
-  const int tid = threadIdx.x;
+// The deal: which slot of assign[] the trajectory of rank r (heaviest first) of assignment group `grp` takes.  The
+// group's slots are the indices = grp (mod G) below n_local; slot grp + G * (round * tl + bl) is member `round` of the
+// group's workgroup bl (the launch's workgroup grp + G * bl), tl = n_tiles / G.  Every mode is a bijection from
+// [0, ng) onto those slots, so whatever the loads hold the assignment is a permutation and the results are the same bits.
+//  kDealSnake (0): round r / tl, workgroup r % tl, backwards in odd rounds while the round is complete: every
+//    workgroup gets the same load.  Right for a shard that runs as ONE round of resident workgroups, where the launch
+//    is as long as its heaviest workgroup.  (The only mode that knows the tail-round layout, r0 > 0.)
+//  kDealSorted (1): workgroup r / members, member r % members -- workgroup b holds the b-th `tile` heaviest, and since
+//    workgroups are dispatched in index order the launch runs heaviest first.  Right for a shard of several rounds:
+//    there equal lives leave the last, partial round as one full life on a mostly empty chip, while a sorted deal ends
+//    on the cheapest workgroups, and the trajectories that collide sit together, where the walk's early exit cuts work.
+//    The group's last round of slots is partial: with q = ng / tl and rem = ng % tl its first rem workgroups hold q + 1
+//    members and the others q (q + 1 = tile on every shard of more than one workgroup a group).
+//  kDealLightTail (2): `head` workgroups of the group (those of the launch's whole rounds of resident workgroups) get
+//    the snake over the heaviest trajectories, the workgroups behind them the snake over the lightest.  Kept behind
+//    DDDMR_DEAL=2 for measurement.
+enum { kDealSnake = 0, kDealSorted = 1, kDealLightTail = 2 };
+__host__ __device__ inline int deal_slot(const DevTick& k, const int grp, const int r, const int deal, const int head) {
   const int G = k.assign_groups;
-  const int n = k.n_local, tl = k.n_tiles / G, tlb = k.nb_tiles / G;     // slots of this group per late / early round
-  const int ng = (n - grp + G - 1) / G;              // trajectories (and slots) of this group
-  // r-th slot of the group in deal order (its slots are the indices = grp (mod G), see tile_slot()): round, position
-  // in the round, and the snake: odd rounds run backwards while the round is complete
-  auto group_slot = [&](int r) {
+  const int tl = k.n_tiles / G, tlb = k.nb_tiles / G;      // slots of this group per late / early round
+  const int ng = (k.n_local - grp + G - 1) / G;            // trajectories (and slots) of this group
+  if (deal == kDealSnake || k.r0 > 0) {
     const int early = k.r0 * tlb;
     int start, width, round;
     if (r < early) { round = r / tlb; start = round * tlb; width = tlb; }
@@ -890,7 +900,38 @@ __device__ __forceinline__ void assign_block(const DevTick& k, const int grp, co
     const int pos = r - start;
     const int bl = ((round & 1) && start + width <= ng) ? width - 1 - pos : pos;
     return grp + G * (start + bl);
-  };
+  }
+  const int q = ng / tl, rem = ng - q * tl;                // workgroup bl holds q + 1 members if bl < rem, else q
+  if (deal == kDealSorted) {
+    const int big = rem * (q + 1);
+    int bl, j;
+    if (r < big) { bl = r / (q + 1); j = r - bl * (q + 1); }
+    else { const int d = (r - big) / q; bl = rem + d; j = r - big - d * q; }     // (q > 0 here: r < ng = big + (tl - rem) * q)
+    return grp + G * (j * tl + bl);
+  }
+  // light tail: the snake over the workgroups [0, hd), then over [hd, tl); a range [lo, hi) has q complete rounds and
+  // the members q of its workgroups below rem
+  const int hd = head < 0 ? 0 : (head > tl ? tl : head);
+  const int n_head = q * hd + (rem < hd ? rem : hd);
+  const int lo = r < n_head ? 0 : hd, width = r < n_head ? hd : tl - hd;
+  const int rr = r < n_head ? r : r - n_head;
+  int round, pos;
+  if (rr < q * width) { round = rr / width; pos = rr - round * width; if (round & 1) pos = width - 1 - pos; }
+  else { round = q; pos = rr - q * width; }
+  return grp + G * (round * tl + lo + pos);
+}
+
+constexpr int kAssignPer = 4;          // trajectories per lane of an assignment block (held in registers)
+template <int kThreads>
+__device__ __forceinline__ void assign_block(const DevTick& k, const int grp, const uint32_t* __restrict__ load,
+                                             uint32_t* __restrict__ assign, const int deal, const int deal_head) {
+  __shared__ uint32_t hist[kLoadClasses];
+  __shared__ uint32_t wsum[kThreads / 64];
+  __shared__ uint32_t mx_s, mn_s;
+  static_assert(kLoadClasses == kThreads, "one class per lane in the scan");
+  const int tid = threadIdx.x;
+  const int G = k.assign_groups;
+  const int ng = (k.n_local - grp + G - 1) / G;      // trajectories (and slots) of this group
   DDDMR_RSTAMP(0);
   hist[tid] = 0;
   if (tid == 0) { mx_s = 1; mn_s = 0xFFFFFFFFu; }
@@ -941,15 +982,15 @@ __device__ __forceinline__ void assign_block(const DevTick& k, const int grp, co
     if (m < ng) {
       const int c = kLoadClasses - 1 - min(kLoadClasses - 1, (int)((float)v[e] * scale));
       const int r = (int)atomicAdd(&hist[c], 1u);
-      assign[group_slot(r)] = (uint32_t)(grp + G * m);
+      assign[deal_slot(k, grp, r, deal, deal_head)] = (uint32_t)(grp + G * m);
     }
   }
   DDDMR_RSTAMP(3);
 }
 
 __global__ __launch_bounds__(kBinThreads) void k_assign(DevTick k, const uint32_t* __restrict__ load,
-                                                        uint32_t* __restrict__ assign) {
-  assign_block<kBinThreads>(k, (int)blockIdx.x, load, assign);
+                                                        uint32_t* __restrict__ assign, const int deal, const int deal_head) {
+  assign_block<kBinThreads>(k, (int)blockIdx.x, load, assign, deal, deal_head);
 }
 
 // Stand-alone launch (empty cloud: there is no k_bin_count to ride along with).
@@ -978,13 +1019,14 @@ __global__ __launch_bounds__(kBinThreads, 8) void k_bin_count(DevTick k, const f
                                                    const float4* __restrict__ samples, TrajInfo* __restrict__ info,
                                                    double2* __restrict__ st_sc, float2* __restrict__ st_xy,
                                                    double2* __restrict__ st_pp, const uint32_t* __restrict__ load,
-                                                   uint32_t* __restrict__ assign, const int heading_rows) {
+                                                   uint32_t* __restrict__ assign, const int heading_rows,
+                                                   const int deal, const int deal_head) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
   // Longest first: the assignment workgroups (only launched with use_assign), the rollout, then the binning
   // workgroups -- when the launch does not fit the chip in one round, the short ones fill the tail.
   const int n_assign = k.use_assign ? k.assign_groups : 0;
   if ((int)blockIdx.x < n_assign) {
-    assign_block<kBinThreads>(k, (int)blockIdx.x, load, assign);
+    assign_block<kBinThreads>(k, (int)blockIdx.x, load, assign, deal, deal_head);
     return;
   }
   if ((int)blockIdx.x < n_assign + k.roll_blocks) {
@@ -1239,7 +1281,7 @@ struct TrajPartial {    // 32 bytes, indexed by the local trajectory
   double pp_dist;       // PurePursuitModel: |translation| of the pose difference
   double pp_yaw;        // PurePursuitModel: folded yaw of the pose difference
   float dist_last;      // TowardGlobalPlanModel: 1-NN distance of the last step (0 for a collided trajectory)
-  uint32_t flags;       // walked << 2 | hit_mm << 1 | hit_box
+  uint32_t flags;       // work << 2 | hit_mm << 1 | hit_box; work = items walked, or candidate items on a sorted deal (k_score)
 };
 static_assert(sizeof(TrajPartial) == 32, "one 32-byte record per trajectory");
 __host__ __device__ inline uint32_t partial_flags(int walked, bool hit_box, bool hit_mm) {
@@ -1461,7 +1503,10 @@ __device__ __forceinline__ double stick_sum_wave(const float* dr, const int ns, 
 // radius / min-max code, the records their optional words, phase D1 its general-vertex-list path.
 // kProbe: the collision walk starts with a probe round (compile-time: as a run-time flag it cost the walk its
 // schedule -- 121 -> 107 VGPRs and +10 % time).
-template <int kScoreThreads, bool kLean, bool kProbe>
+// kItemsKey: the tick runs on a sorted deal and files candidate item counts as its feedback (see work_of below).  A
+// compile-time fact, so that the ticks on the snake deal run the code they always ran: as a run-time flag alone the
+// second use of the item counts cost every instantiation about 50 scalar register spills (C3 on the snake +0.9 %, C2 +3 %).
+template <int kScoreThreads, bool kLean, bool kProbe, bool kItemsKey>
 __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_WPE : DDDMR_SCORE_WPE_256) void k_score(
     DevTick k, const TrajInfo* __restrict__ info, const double2* __restrict__ st_sc, const float2* __restrict__ st_xy,
     const float4* __restrict__ plan_xyz, const uint32_t* __restrict__ cell_start,
@@ -1470,7 +1515,7 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
     uint32_t* __restrict__ ticket, DevResult* __restrict__ result, const uint32_t* __restrict__ assign,
     uint32_t* __restrict__ traj_load, int64_t* __restrict__ words_out, const uint32_t* __restrict__ row_tab,
     const float* __restrict__ plan_pairs, TrajPartial* __restrict__ partial, const int fused_walk,
-    const double2* __restrict__ st_pp) {
+    const double2* __restrict__ st_pp, const int deal) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int tile = k.tile;
   const int S1 = k.max_steps + 1;
@@ -1517,7 +1562,10 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
   // assignment (load feedback, see assign_block) or, without one, the local
   // trajectories of those indices: neighbours in sample order head the same way and
   // would make whole tiles cheap (open space) or expensive (along a wall); striding
-  // mixes them.
+  // mixes them.  With an assignment the deal decides the mix (deal_slot()): equal tiles on a shard of one round of
+  // workgroups; on a shard of several, tile b holds the b-th heaviest trajectories, so that the workgroups dispatched
+  // last are the cheapest and the launch's ragged end is short.  `deal` here only selects what the tile files as its
+  // trajectories' work for the next tick's deal (see work_of below).
   const int tb = (int)blockIdx.x;
   int nt = 0;                                                  // <= tile (see tile_slot())
   for (int j = 0; j < tile; ++j) nt += ((tb < k.nb_tiles || j + k.r0 < tile) && tile_slot(k, tb, j) < k.n_local) ? 1 : 0;
@@ -2117,6 +2165,17 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
   // and the wave ends: no barrier, no scoring, no per-trajectory output, no key, no atomic.  k_finalize scores the
   // whole shard one lane per trajectory and takes the exact argmin.  Every trajectory of the tile gets a record,
   // a not-generated and a collided one too (the outputs may be poisoned before the tick).
+  // The feedback word's work term.  A tick on the snake deal files `walked`, the items the walk really touched; that
+  // depends on who shared the tile (a trajectory that collided early skipped the rest of its items).  A tick on a sorted
+  // deal (deal != kDealSnake) files the trajectory's CANDIDATE item count instead, t_item0[j + 1] - t_item0[j] of phase
+  // D2: exact, a function of cloud, pose and trajectory alone, so the order it gives does not flip from tick to tick
+  // with the company a trajectory kept.  (Clamped to the 30 bits TrajPartial::flags has for it.)
+  const bool key_items = kItemsKey && deal != kDealSnake;
+  const bool have_items = do_coll && total_pairs > 0;         // phase D2 ran: t_item0 is the tile's prefix
+  auto work_of = [&](const int j) {
+    if (!key_items) return head[j].walked;
+    return have_items ? (int)min(t_item0[j + 1] - t_item0[j], 0x3FFFFFFFu) : 0;
+  };
   if (k.final_kernel) {
     for (int j = wid; j < nt; j += kScoreThreads / 64) {
       const int ns = head[j].steps;
@@ -2129,7 +2188,7 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
         pr->pp_dist = head[j].pp_dist;
         pr->pp_yaw = head[j].pp_yaw;
         pr->dist_last = (ns > 0 && !dead) ? dist[(size_t)j * S1 + ns - 1] : 0.f;
-        pr->flags = partial_flags(head[j].walked, hb, hm);
+        pr->flags = partial_flags(work_of(j), hb, hm);
       }
     }
     DDDMR_STAMP(10);  // end of (wave 0's) StickPath sums and records
@@ -2169,7 +2228,7 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
     costs[li] = cost;
     samples_out[li] = make_float4(h.vx, h.vy, h.w, 0.f);
     steps_out[li] = h.steps;
-    traj_load[li] = traj_load_of(k.m, h.walked, h.steps, (need_box && hb) || (need_mm && hm));
+    traj_load[li] = traj_load_of(k.m, work_of(tid), h.steps, (need_box && hb) || (need_mm && hm));
   }
   DDDMR_STAMP(11);  // end of the stacked scoring + per-trajectory stores
   // ---- argmin hand-off ----

@@ -244,6 +244,7 @@ struct TickKnobs {
   bool no_tab = false;        // DDDMR_NO_TAB: k_score reads the row-run index from L2 instead of staging it in LDS
   bool heading_rows = true;   // DDDMR_HEADING_ROWS=0: a heading chain per trajectory on every tick (rollout_kernels.hip.h)
   bool fuse_walk = true;      // DDDMR_FUSE_WALK=0: phase P always stays a phase of its own behind the collision walk
+  int deal_mode = -1;         // DDDMR_DEAL: -1 by shard size (TickPlan::deal), 0 always the snake, 1 / 2 sorted / light tail wherever there is an assignment
   int n_cu = 256;             // compute units of the device
 };
 
@@ -275,6 +276,8 @@ struct TickPlan {
   int heading_rows = 0;     // 1: the rollout shares heading rows per angular sample (heading_rows_shared())
   size_t roll_launch_lds = 0;   // dynamic LDS of the launch that rolls out: roll_lds, plus the rows when they are shared
   int fused_walk = 0;       // 1: k_score walks the prune plan as the tail of the collision walk, for every pair (fused_walk_share_max())
+  int deal = 0;             // how the load-feedback assignment deals the trajectories to k_score's workgroups (deal_slot(): kDealSnake, kDealSorted, kDealLightTail)
+  int deal_head = 0;        // kDealLightTail: workgroups per assignment group that belong to the launch's whole rounds of resident workgroups
   SampleUpload upload = kUploadNone;
   uint32_t n_samples = 0, local_begin = 0, n_local = 0;   // the result's head
 };
@@ -629,6 +632,19 @@ int plan_tick(const TickKnobs& kn, const TickFeedback& fb, const dddmr_rollout_c
         k.r0 = tile - t2;
       }
     }
+  }
+  // The deal (rollout_kernels.hip.h, deal_slot()).  The snake makes all workgroups equally heavy, which is what bounds a
+  // launch of ONE round of resident workgroups.  On a shard of several rounds equal lives mean the last, partial round
+  // runs a full life on a mostly empty chip (C3: 2731 workgroups on 512 slots, 171 in the sixth round); there the sorted
+  // deal dispatches the heaviest tiles first and ends on the cheapest.  The tail-round layout keeps the snake.
+  // DDDMR_DEAL=1 / 2 force the sorted / light-tail deal wherever there is an assignment (tests, measurements).
+  {
+    const bool layout_ok = k.use_assign && k.r0 == 0;
+    const long slots = (long)kn.n_cu * (thr == 512 ? 2 : 4);
+    p->deal = kDealSnake;
+    if (kn.deal_mode < 0) { if (layout_ok && !one_round && tile > 1) p->deal = kDealSorted; }
+    else if (kn.deal_mode > 0 && layout_ok) p->deal = kn.deal_mode == kDealLightTail ? kDealLightTail : kDealSorted;
+    p->deal_head = (p->deal == kDealLightTail) ? (int)(((long)k.n_tiles / slots) * slots / k.assign_groups) : 0;
   }
   return DDDMR_OK;
 }

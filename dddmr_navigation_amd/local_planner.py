@@ -56,6 +56,26 @@ def device_count() -> int:
     return int(n.value) if rc == K.OK else 0
 
 
+# Diagnostics of the load-feedback deal.  Functions of a planner, not methods: the methods of LocalPlanner are the set
+# whose calls tests/golden/binding_trace.json records.
+def deal(lp: "LocalPlanner") -> int:
+    """How the last launched tick dealt the trajectories to k_score's workgroups: 0 snake, 1 sorted, 2 light tail,
+    -1 before any tick (dddmr_rollout_deal)."""
+    return int(lp._rc("deal"))
+
+
+def deal_arrays(lp: "LocalPlanner"):
+    """-> (assign[n_local] u32, load[n_local] u32, assigned) of the last tick (dddmr_rollout_get_deal): assign[slot] is
+    the local trajectory in that slot (slot = member * workgroups + workgroup), load[i] what trajectory i filed for the
+    next tick's deal, assigned whether the tick dealt by load feedback at all (else assign is the identity)."""
+    n, used = C.c_size_t(0), C.c_int32(0)
+    lp._call("get_deal", None, None, 0, C.byref(n), C.byref(used))
+    assign = np.zeros(max(n.value, 1), dtype=np.uint32)
+    load = np.zeros(max(n.value, 1), dtype=np.uint32)
+    lp._call("get_deal", M.ptr(assign), M.ptr(load), assign.size, C.byref(n), C.byref(used))
+    return assign[:n.value], load[:n.value], bool(used.value)
+
+
 class LocalPlanner:
     """One rollout context = the trajectory generators + critics of one robot."""
 

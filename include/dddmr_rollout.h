@@ -848,6 +848,20 @@ int dddmr_rollout_heading_rows(dddmr_rollout_ctx* ctx);
    tick.  Both give the same bits; tests use this to know which path they compared. */
 int dddmr_rollout_fused_walk(dddmr_rollout_ctx* ctx);
 
+/* How the last launched tick's load-feedback assignment dealt the trajectories to k_score's workgroups: 0 in snake
+   order, every workgroup equally heavy (shards that run as one round of resident workgroups, ticks without an
+   assignment, DDDMR_DEAL=0 at create), 1 sorted, workgroup b holds the b-th heaviest trajectories (shards of several
+   rounds, DDDMR_DEAL=1 wherever there is an assignment), 2 the light-tail variant (DDDMR_DEAL=2 only), -1 before any
+   tick.  Every deal gives the same bits; tests use this to know which one they compared. */
+int dddmr_rollout_deal(dddmr_rollout_ctx* ctx);
+
+/* The assignment of the last tick and the loads it filed, [n_local] each (either pointer may be NULL; call with both
+   NULL for the count): assign_out[slot] = local trajectory, slot = member * workgroups + workgroup; load_out[i] = the
+   load word trajectory i filed for the NEXT tick's deal.  *assigned (may be NULL) = 1 if the tick dealt by load
+   feedback, 0 if it took the trajectories strided (assign_out is then the identity). */
+int dddmr_rollout_get_deal(dddmr_rollout_ctx* ctx, uint32_t* assign_out, uint32_t* load_out, size_t capacity,
+                           size_t* n_local, int32_t* assigned);
+
 /* Debug pose arrays of the last tick, poses_out[n][7] x y z qx qy qz qw, trajectory by
    trajectory in sample order, poses in step order: which = 0 the `trajectory` topic
    (every generated trajectory, local_planner.cpp:549-569), which = 1 the
