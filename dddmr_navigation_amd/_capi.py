@@ -369,6 +369,7 @@ _TABLE = {
     "get_debug": (_int, [_ctx, _P(RolloutDebug)]),
     "heading_rows": _plain,
     "fused_walk": _plain,
+    "score_paths": _plain,
     "deal": _plain,
     "get_deal": (_int, [_ctx, _vp, _vp, _sz, _pn, _P(_i32)]),
     "get_best_poses": _get,

@@ -181,6 +181,7 @@ struct dddmr_rollout_ctx {
   int last_heading_rows = -1; // what the last launched tick did (dddmr_rollout_heading_rows)
   int last_fused_walk = -1;   // ... and which way its k_score walked the prune plan (dddmr_rollout_fused_walk)
   int last_deal = -1;         // ... and how its assignment dealt the trajectories (dddmr_rollout_deal)
+  int last_score_paths = -1;  // ... and which optional paths its k_score took (dddmr_rollout_score_paths)
   int last_assigned = 0;      // ... and whether it had an assignment at all (dddmr_rollout_get_deal)
   uint32_t seq = 0;
   DevResult last_result{};   // host copy of the last COLLECTED tick's result
@@ -307,6 +308,7 @@ void read_env(dddmr_rollout_ctx* ctx) {
   if (const char* e = std::getenv("DDDMR_TAIL_ROUND")) kn.tail_round = std::atoi(e) != 0;
   if (const char* e = std::getenv("DDDMR_HEADING_ROWS")) kn.heading_rows = std::atoi(e) != 0;
   if (const char* e = std::getenv("DDDMR_FUSE_WALK")) kn.fuse_walk = std::atoi(e) != 0;
+  if (const char* e = std::getenv("DDDMR_SKIP_DEAD")) kn.skip_dead = std::atoi(e) != 0;
   if (const char* e = std::getenv("DDDMR_DEAL")) kn.deal_mode = std::min(std::max(std::atoi(e), -1), 2);
   if (const char* e = std::getenv("DDDMR_FINAL")) kn.final_mode = std::atoi(e) ? 1 : 0;
   if (const char* e = std::getenv("DDDMR_PROBE")) kn.probe_mode = std::atoi(e) ? 1 : 0;
@@ -754,6 +756,7 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
   ctx->feedback.load_nlocal = k.n_local;
   ctx->last_heading_rows = p.heading_rows;
   ctx->last_fused_walk = k.n_local > 0 ? p.fused_walk : 0;
+  ctx->last_score_paths = k.n_local > 0 ? (p.skip_dead ? 1 : 0) : 0;
   ctx->last_deal = p.deal;
   ctx->last_assigned = k.use_assign;
   drain.armed = true;       // from here on the stream reads the pinned cloud
@@ -791,7 +794,7 @@ int tick_enqueue(dddmr_rollout_ctx* ctx, const char* theory_name, const dddmr_ti
                      ctx->st_xy, ctx->plan_dev, ctx->cell_start, ctx->sorted, ctx->costs, ctx->steps,             \
                      ctx->samples_out, ctx->best_key, ctx->overflow, ctx->tickets + 1, score_result, ctx->assign, \
                      ctx->traj_load, score_words, ctx->row_tab, ctx->plan_pairs_dev, ctx->partial, p.fused_walk,  \
-                     ctx->st_pp, p.deal)
+                     ctx->st_pp, p.deal, p.skip_dead)
     if (p.thr == 512) { if (p.lean) DDDMR_LAUNCH_SCORE(512, true); else DDDMR_LAUNCH_SCORE(512, false); }
     else              { if (p.lean) DDDMR_LAUNCH_SCORE(256, true); else DDDMR_LAUNCH_SCORE(256, false); }
 #undef DDDMR_LAUNCH_SCORE
@@ -1012,6 +1015,12 @@ int dddmr_rollout_fused_walk(dddmr_rollout_ctx* ctx) {
   if (!ctx) return -1;
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   return ctx->last_fused_walk;
+}
+
+int dddmr_rollout_score_paths(dddmr_rollout_ctx* ctx) {
+  if (!ctx) return -1;
+  std::lock_guard<std::mutex> tk(ctx->tick_mu);
+  return ctx->last_score_paths;
 }
 
 int dddmr_rollout_deal(dddmr_rollout_ctx* ctx) {

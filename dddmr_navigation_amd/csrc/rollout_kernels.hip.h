@@ -1515,7 +1515,7 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
     uint32_t* __restrict__ ticket, DevResult* __restrict__ result, const uint32_t* __restrict__ assign,
     uint32_t* __restrict__ traj_load, int64_t* __restrict__ words_out, const uint32_t* __restrict__ row_tab,
     const float* __restrict__ plan_pairs, TrajPartial* __restrict__ partial, const int fused_walk,
-    const double2* __restrict__ st_pp, const int deal) {
+    const double2* __restrict__ st_pp, const int deal, const int skip_dead) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int tile = k.tile;
   const int S1 = k.max_steps + 1;
@@ -1525,6 +1525,9 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
   // again: every pair has a lane of its own, there is a plan.)
   constexpr bool kCanFuse = kLean && kScoreThreads == 512;
   const bool fused = kCanFuse && fused_walk != 0 && Qcap <= kScoreThreads && k.m > 0 && k.want_collision != 0 && k.n_points >= 5;
+  // TickPlan::skip_dead: a fused tick leaves the trajectories its collision walk has rejected out of the plan walk and
+  // out of the StickPath sums (see the fused walk below); every other tick ignores the argument.
+  const bool skip = fused && skip_dead != 0;
   const bool need_box = k.want_collision != 0, need_mm = !kLean && k.want_minmax != 0;
   const bool rec_pose = !kLean && k.rec_pose != 0;
   const bool box_fast = kLean || k.box_fast != 0;      // (the lean variant is only launched for body-frame boxes)
@@ -1673,8 +1676,8 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
     }
     pose_translation(k, bxy, T);
     const float px = (float)T[0], py = (float)T[1], pz = (float)T[2];   // trajectory.cpp:69-75
-    // (w: where the pair's distance goes, for the fused walk -- nobody else reads it)
-    ppos[q] = make_float4(px, py, pz, kCanFuse ? __int_as_float(j * S1 + s) : 0.f);
+    // (w: the pair's trajectory and step, for the fused walk -- nobody else reads it; a fused tile has at most 512 pairs)
+    ppos[q] = make_float4(px, py, pz, kCanFuse ? __int_as_float((j << 16) | s) : 0.f);
 
     // ---- cuboid -> OBB record (collision_model.cpp:85-115) ----
     if (do_coll) {
@@ -2028,19 +2031,29 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
     // them to tiles whose pairs fit one pass of lanes, q == tid, and to few collisions) a wave goes from its last item
     // straight into the plan walk for its own pairs: no survivor scan, no barrier before it, and the waves that were
     // dealt no items walk the plan while the others still walk theirs.  The same chunks in the same order with the
-    // same arithmetic as phase P below, so the distances are the same bits; collided trajectories get distances too,
-    // which nobody reads.  (Spreading the plan's chunks over the items of the walk -- point loads issued, 2 / 4 / 8
+    // same arithmetic as phase P below, so the distances are the same bits.
+    // A trajectory the collision walk has rejected by then needs no distances: nothing reads them (the tails below file
+    // 0 for its sum and its last distance, as they do behind the separate phase P, which never wrote them either).  The
+    // verdict is in LDS and only ever goes from 0 to 1, so a lane that reads it set leaves its pair out, and a wave
+    // whose pairs are all out skips the walk (`skip`; a sorted deal puts the colliding trajectories of a shard into
+    // the same tiles, so whole workgroups skip it).  A verdict that falls later costs that pair's walk as before; how
+    // many waves skip depends on timing, the outputs do not.  The condition on the walk stays wave-uniform (see phase
+    // P): a wave with one live lane walks with all its lanes.
+    // (Spreading the plan's chunks over the items of the walk -- point loads issued, 2 / 4 / 8
     // chunks, points tested -- was built and measured: it lost most of what this gains)
     if (fused) {
       const bool mine = tid < total_pairs;
       float px = 0.f, py = 0.f, pz = 0.f, best = 3.402823466e+38f;
-      int dst = 0;
+      int dst = 0, j = 0;
       if (mine) {
         const float4 pp = ppos[tid];              // the pose D1 composed for this pair
         px = pp.x; py = pp.y; pz = pp.z;
-        dst = __float_as_int(pp.w);
+        const int js = __float_as_int(pp.w);
+        j = js >> 16;
+        dst = j * S1 + (js & 0xFFFF);
       }
-      if (__ballot(mine) != 0ull) {                 // wave-uniform, as in phase P: a wave walks with all its lanes
+      const bool live = mine && !(skip && __hip_atomic_load(&head[j].hit_box, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0);
+      if (__ballot(live) != 0ull) {                 // wave-uniform, as in phase P: a wave walks with all its lanes
         constexpr uint32_t kPoseBytes = 4u * kPlanPoseWords, kChunkBytes = kPoseBytes * kPlanChunk;
         const uint32_t end = kPoseBytes * (uint32_t)k.m;
         PlanChunk ca = plan_request(plan_pairs, 0u);
@@ -2056,7 +2069,7 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
           plan_wait(ca, best);
         }
       }
-      if (mine) dist[dst] = sqrtf(best);
+      if (live) dist[dst] = sqrtf(best);
     }
   }
   __syncthreads();
@@ -2179,7 +2192,8 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
   if (k.final_kernel) {
     for (int j = wid; j < nt; j += kScoreThreads / 64) {
       const int ns = head[j].steps;
-      const double sum = stick_sum_wave(dist + (size_t)j * S1, ns, lane);
+      // (skip: a rejected trajectory has no distances; the flags are final behind the barrier and j is the wave's)
+      const double sum = (skip && head[j].hit_box != 0) ? 0.0 : stick_sum_wave(dist + (size_t)j * S1, ns, lane);
       if (lane == 0) {
         const bool hb = head[j].hit_box != 0, hm = head[j].hit_mm != 0;
         const bool dead = cloud_ok && ((need_box && hb) || (need_mm && hm));    // (skipped phase P: no distances)
@@ -2197,7 +2211,7 @@ __global__ __launch_bounds__(kScoreThreads, kScoreThreads >= 512 ? DDDMR_SCORE_W
     return;
   }
   for (int j = wid; j < nt; j += kScoreThreads / 64) {
-    const double sum = stick_sum_wave(dist + (size_t)j * S1, head[j].steps, lane);
+    const double sum = (skip && head[j].hit_box != 0) ? 0.0 : stick_sum_wave(dist + (size_t)j * S1, head[j].steps, lane);
     if (lane == 0) head[j].stick_sum = sum;
   }
   __syncthreads();

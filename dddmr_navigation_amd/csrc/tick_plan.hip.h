@@ -244,6 +244,7 @@ struct TickKnobs {
   bool no_tab = false;        // DDDMR_NO_TAB: k_score reads the row-run index from L2 instead of staging it in LDS
   bool heading_rows = true;   // DDDMR_HEADING_ROWS=0: a heading chain per trajectory on every tick (rollout_kernels.hip.h)
   bool fuse_walk = true;      // DDDMR_FUSE_WALK=0: phase P always stays a phase of its own behind the collision walk
+  bool skip_dead = true;      // DDDMR_SKIP_DEAD=0: a fused tick walks the plan and sums the distances of rejected trajectories too
   int deal_mode = -1;         // DDDMR_DEAL: -1 by shard size (TickPlan::deal), 0 always the snake, 1 / 2 sorted / light tail wherever there is an assignment
   int n_cu = 256;             // compute units of the device
 };
@@ -276,6 +277,7 @@ struct TickPlan {
   int heading_rows = 0;     // 1: the rollout shares heading rows per angular sample (heading_rows_shared())
   size_t roll_launch_lds = 0;   // dynamic LDS of the launch that rolls out: roll_lds, plus the rows when they are shared
   int fused_walk = 0;       // 1: k_score walks the prune plan as the tail of the collision walk, for every pair (fused_walk_share_max())
+  int skip_dead = 0;        // 1: the fused walk and the StickPath sums leave out the trajectories the collision walk rejected (fused ticks only)
   int deal = 0;             // how the load-feedback assignment deals the trajectories to k_score's workgroups (deal_slot(): kDealSnake, kDealSorted, kDealLightTail)
   int deal_head = 0;        // kDealLightTail: workgroups per assignment group that belong to the launch's whole rounds of resident workgroups
   SampleUpload upload = kUploadNone;
@@ -532,6 +534,7 @@ int plan_tick(const TickKnobs& kn, const TickFeedback& fb, const dddmr_rollout_c
     const int pairs = tile * s_tick;
     p->fused_walk = (kn.fuse_walk && k.n_local > 0 && p->lean && k.want_collision && k.n_points >= 5 && k.m >= 1 && pairs <= thr &&
                      pairs > 256 && fb.collided_share <= fused_walk_share_max(pairs)) ? 1 : 0;
+    p->skip_dead = (kn.skip_dead && p->fused_walk) ? 1 : 0;
   }
   const bool one_round = k.n_local <= 0 || (k.n_local + tile - 1) / tile <= kn.n_cu * (thr == 512 ? 2 : 4);
   k.final_kernel = kn.final_mode >= 0 ? kn.final_mode : (one_round ? 0 : 1);

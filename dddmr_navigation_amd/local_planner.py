@@ -64,6 +64,12 @@ def deal(lp: "LocalPlanner") -> int:
     return int(lp._rc("deal"))
 
 
+def score_paths(lp: "LocalPlanner") -> int:
+    """Which optional paths the last launched tick's k_score took, as bits: bit 0 = the fused plan walk and the
+    StickPath sums left out the rejected trajectories; -1 before any tick (dddmr_rollout_score_paths)."""
+    return int(lp._rc("score_paths"))
+
+
 def deal_arrays(lp: "LocalPlanner"):
     """-> (assign[n_local] u32, load[n_local] u32, assigned) of the last tick (dddmr_rollout_get_deal): assign[slot] is
     the local trajectory in that slot (slot = member * workgroups + workgroup), load[i] what trajectory i filed for the

@@ -848,6 +848,12 @@ int dddmr_rollout_heading_rows(dddmr_rollout_ctx* ctx);
    tick.  Both give the same bits; tests use this to know which path they compared. */
 int dddmr_rollout_fused_walk(dddmr_rollout_ctx* ctx);
 
+/* Which optional paths the last launched tick's k_score took, as bits: bit 0 = the fused plan walk and the StickPath
+   sums left out the trajectories the collision walk had rejected (fused ticks only; DDDMR_SKIP_DEAD=0 at create
+   switches it off).  0 on a tick that is not fused or has an empty shard, -1 before any tick.  Either way gives the
+   same bits; tests use this to know which path they compared. */
+int dddmr_rollout_score_paths(dddmr_rollout_ctx* ctx);
+
 /* How the last launched tick's load-feedback assignment dealt the trajectories to k_score's workgroups: 0 in snake
    order, every workgroup equally heavy (shards that run as one round of resident workgroups, ticks without an
    assignment, DDDMR_DEAL=0 at create), 1 sorted, workgroup b holds the b-th heaviest trajectories (shards of several
