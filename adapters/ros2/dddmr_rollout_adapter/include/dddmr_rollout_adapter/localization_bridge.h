@@ -78,6 +78,9 @@ public:
     have_map_ = rc == DDDMR_OK;
     return rc;
   }
+  // ... or the map came from the device's own sub-maps (submap_bridge.h): call this after a SubmapBridge::swapIfReady
+  // that reported a swap, in place of setMap
+  void mapSwappedIn() {have_map_ = ctx_ != nullptr;}
 
   // One observation against every particle: likelihood[i] and quality[i] belong to particles[i] (what measure_func
   // returns for it, and the result's quality).  quality_min / quality_max: match_ratio_min / match_ratio_max of

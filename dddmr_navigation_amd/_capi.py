@@ -316,6 +316,21 @@ class MclObservationStats(C.Structure):
     ]
 
 
+class SubmapConfig(C.Structure):
+    """dddmr_submap_config: the keyframe store's capacities and NormalEstimation's setKSearch."""
+    _fields_ = [
+        ("max_keyframes", C.c_uint32), ("max_store_map_points", C.c_uint32), ("max_store_ground_points", C.c_uint32),
+        ("normal_k", C.c_uint32), ("reserved", C.c_uint32 * 2),
+    ]
+
+
+class SubmapStats(C.Structure):
+    _fields_ = [
+        ("n_keyframes", C.c_uint32), ("n_map", C.c_uint32), ("n_ground", C.c_uint32), ("n_nan_normals", C.c_uint32),
+        ("max_rings_searched", C.c_uint32), ("launches", C.c_uint32), ("host_waits", C.c_uint32), ("n_brute_force", C.c_uint32),
+    ]
+
+
 MCL_BRANCH_CLUSTERS, MCL_BRANCH_X_DOMINANT, MCL_BRANCH_Y_DOMINANT = 0, 1, 2
 
 
@@ -332,7 +347,8 @@ class RolloutDebug(C.Structure):
     ]
 
 
-# the structs dddmr_rollout_sizeof knows, in its order (rollout_engine.hip: case 0 .. 22)
+# the structs dddmr_rollout_sizeof knows, in its order (rollout_engine.hip: case 0 .. 22; the sub-map structs
+# are pinned by static_asserts in mcl_submap.hip.h and by tests/test_submap_cpu.py instead)
 SIZEOF_STRUCTS = (
     CriticConfig, TheoryConfig, RolloutConfig, TickInput, RolloutResult, RolloutDebug, MarkingConfig, MarkingStats,
     DepthSourceConfig, DepthImageConfig, DepthFrustumConfig, DepthMarkConfig, DepthMarkStats, DepthLayerConfig,
@@ -438,6 +454,12 @@ _TABLE = {
     "mcl_prepare_from_sweep": (_int, [_ctx, _i32, _pd, _P(MclObservationStats)]),
     "mcl_get_observation": (_int, [_ctx, _vp, _sz, _pn, _vp, _sz, _pn, _vp, _sz]),
     "mcl_measure_prepared": (_int, [_ctx, _vp, _sz, _vp, _vp, _P(MclStats)]),
+    "submap_create": (_int, [_ctx, _P(SubmapConfig)]),
+    "submap_add_keyframe": (_int, [_ctx] + _cloud + _cloud + [_pd, _pd, _vp]),
+    "submap_select": (_int, [_ctx, _pd, _dbl, _vp, _sz, _pn]),
+    "submap_warm_up": (_int, [_ctx, _vp, _sz, _P(SubmapStats)]),
+    "submap_swap": _plain,
+    "submap_get": (_int, [_ctx, _i32, _vp, _sz, _pn, _vp, _vp, _vp, _sz, _pn]),
     "stream_ceiling": (_int, [_ctx, _sz, _i32, _pd, _pd]),
     "selftest_sincos": (_int, [_ctx, _vp, _sz, _vp, _vp]),
     "last_error": (_str, [_ctx]),

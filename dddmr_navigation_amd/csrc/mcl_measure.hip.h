@@ -327,6 +327,7 @@ __global__ __launch_bounds__(256) void k_mcl_finish(MclParams k, MclTerms t, con
 namespace {
 
 struct MclObs;                             // the prepared observation, mcl_observation.hip.h
+struct SubMapState;                        // the keyframe store and the warm-up generation, mcl_submap.hip.h
 
 struct MclMap {                            // one swapKdTree generation
   GridBuf map, ground;
@@ -337,7 +338,10 @@ struct MclState {
   dddmr_mcl_config cfg{};
   MclParams k{};
   MclMap maps[2];
+  MclMap warm;                             // a third generation for the sub-maps' warm-up, allocated by the first submap_create
+  bool has_warm = false;                   // (owned by `mem` like the other two: submap_swap exchanges it with maps[cur])
   int cur = -1;                            // maps[cur] answers; -1 before the first set_map
+  uint64_t serial = 0;                     // grows with every new current generation (set_map, submap_swap)
   uint2* slot = nullptr;                   // grid builder scratch
   char* temp = nullptr;                    // rocPRIM storage of the grid builder's scan
   size_t temp_bytes = 0;
@@ -352,10 +356,22 @@ struct MclState {
   uint32_t seq = 0;
   uint32_t last_n = 0;                     // particles of the last successful measure (get_terms)
   std::unique_ptr<MclObs, LateDelete<MclObs>> obs;   // dddmr_rollout_mcl_set_observation_config
+  std::unique_ptr<SubMapState, LateDelete<SubMapState>> submap;   // dddmr_rollout_submap_create
 };
 static_assert(!std::is_copy_constructible_v<MclState>);
 
 constexpr uint32_t kMclCells = 1u << 21;   // cells of each grid (grid_shape coarsens the cell until the cloud's box fits)
+
+int mcl_alloc_generation(dddmr_rollout_ctx* ctx, MclState* s, MclMap& m) {
+  const dddmr_mcl_config& c = s->cfg;
+  DevAllocs& mem = s->mem.dev;
+  if (grid_alloc(mem, m.map, kMclCells, c.max_map_points) != 0 || grid_alloc(mem, m.ground, kMclCells, c.max_ground_points) != 0)
+    return fail(ctx, DDDMR_ERR_HIP, "mcl_create: the grids' allocation failed");
+  HIPCHK(ctx, dev_alloc(mem, &m.map_pts, std::max<size_t>(c.max_map_points, 1)));
+  HIPCHK(ctx, dev_alloc(mem, &m.ground_pts, std::max<size_t>(c.max_ground_points, 1)));
+  HIPCHK(ctx, dev_alloc(mem, &m.normals, std::max<size_t>(c.max_ground_points, 1)));
+  return DDDMR_OK;
+}
 
 int mcl_alloc(dddmr_rollout_ctx* ctx, MclState* s) {
   const dddmr_mcl_config& c = s->cfg;
@@ -368,13 +384,8 @@ int mcl_alloc(dddmr_rollout_ctx* ctx, MclState* s) {
     HIPCHK(ctx, dev_alloc(mem, &s->temp, s->temp_bytes));
   }
   HIPCHK(ctx, dev_alloc(mem, &s->slot, std::max<size_t>(std::max(c.max_map_points, c.max_ground_points), 1)));
-  for (MclMap& m : s->maps) {
-    if (grid_alloc(mem, m.map, kMclCells, c.max_map_points) != 0 || grid_alloc(mem, m.ground, kMclCells, c.max_ground_points) != 0)
-      return fail(ctx, DDDMR_ERR_HIP, "mcl_create: the grids' allocation failed");
-    HIPCHK(ctx, dev_alloc(mem, &m.map_pts, std::max<size_t>(c.max_map_points, 1)));
-    HIPCHK(ctx, dev_alloc(mem, &m.ground_pts, std::max<size_t>(c.max_ground_points, 1)));
-    HIPCHK(ctx, dev_alloc(mem, &m.normals, std::max<size_t>(c.max_ground_points, 1)));
-  }
+  for (MclMap& m : s->maps)
+    if (const int rc = mcl_alloc_generation(ctx, s, m)) return rc;
   const size_t N = c.max_particles;
   HIPCHK(ctx, dev_alloc(mem, &s->t.score, N));
   HIPCHK(ctx, dev_alloc(mem, &s->t.pos_weight, N));
@@ -391,27 +402,36 @@ int mcl_alloc(dddmr_rollout_ctx* ctx, MclState* s) {
   return DDDMR_OK;
 }
 
+// The grid of a generation's cloud, which lies in `dev` with its box known: enqueued on the context's stream, no wait.
+// set_map's upload and the sub-maps' warm-up (mcl_submap.hip.h) both build their grids here.
+int mcl_grid(dddmr_rollout_ctx* ctx, MclState* s, GridBuf& b, const float4* dev, const float lo[3], const float hi[3], size_t n) {
+  const float cell = 2.02f * (s->k.mdm + kMclPad);
+  grid_shape(b.g, lo, hi, cell, cell, b.cap_cells);
+  return grid_build(ctx, s->temp, s->temp_bytes, b, dev, (uint32_t)n, s->slot, ctx->stream);
+}
+
 // One cloud into a generation's buffers: the points, their box, the grid.  Cells at least twice the match radius wide,
 // so that a point's query touches at most 2 x 2 rows of cells (grid_for_each's fast path).  Waits for the stream: the
 // caller's `h` is pageable.
 int mcl_upload(dddmr_rollout_ctx* ctx, MclState* s, GridBuf& b, float4* dev, const HostCloud& h, size_t n) {
   Drain drain{ctx->stream};
   if (n) HIPCHK(ctx, hipMemcpyAsync(dev, h.pts.data(), n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-  const float cell = 2.02f * (s->k.mdm + kMclPad);
-  grid_shape(b.g, h.lo, h.hi, cell, cell, b.cap_cells);
-  const int rc = grid_build(ctx, s->temp, s->temp_bytes, b, dev, (uint32_t)n, s->slot, ctx->stream);
+  const int rc = mcl_grid(ctx, s, b, dev, h.lo, h.hi, n);
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   drain.armed = false;
   return rc;
 }
 
 // finite coordinates within 1e6 m, and a box the search pad covers (kMclMaxExtent)
+bool mcl_box_ok(const float lo[3], const float hi[3]) {
+  for (int a = 0; a < 3; ++a)
+    if (!(std::fabs(lo[a]) <= 1e6f) || !(std::fabs(hi[a]) <= 1e6f) || !(hi[a] - lo[a] <= kMclMaxExtent)) return false;
+  return true;
+}
 bool mcl_cloud_ok(const HostCloud& h, size_t n) {
   for (size_t i = 0; i < n; ++i)
     if (!(std::fabs(h.pts[i].x) <= 1e6f) || !(std::fabs(h.pts[i].y) <= 1e6f) || !(std::fabs(h.pts[i].z) <= 1e6f)) return false;
-  for (int a = 0; a < 3; ++a)
-    if (!(h.hi[a] - h.lo[a] <= kMclMaxExtent)) return false;
-  return true;
+  return mcl_box_ok(h.lo, h.hi);
 }
 
 // One measure over an observation the device can read (k_mcl_match's layout): the host-mapped staging of
@@ -521,6 +541,7 @@ int dddmr_rollout_mcl_set_map(dddmr_rollout_ctx* ctx, const float* map_xyz, size
   if (n_ground)
     HIPCHK(ctx, hipMemcpy(m.normals, HostCloud(ground_normals, n_ground, normal_stride_bytes).pts.data(), n_ground * sizeof(float4), hipMemcpyHostToDevice));
   s->cur = s->cur == 0 ? 1 : 0;
+  ++s->serial;
   return DDDMR_OK;
 }
 

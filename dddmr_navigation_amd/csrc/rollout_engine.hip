@@ -1182,3 +1182,4 @@ int dddmr_rollout_get_best_cuboids(dddmr_rollout_ctx* ctx, float* vertices_out, 
 #include "perception_stack.hip.h"
 #include "mcl_measure.hip.h"
 #include "mcl_observation.hip.h"
+#include "mcl_submap.hip.h"

@@ -1210,6 +1210,79 @@ int dddmr_rollout_mcl_get_observation(dddmr_rollout_ctx* ctx, float* flat_xyz_ou
 int dddmr_rollout_mcl_measure_prepared(dddmr_rollout_ctx* ctx, const float* states /* [n_states][7] */, size_t n_states,
                                        float* likelihood_out, float* quality_out, dddmr_mcl_stats* stats);
 
+/* ---- The localiser's sub-maps: mcl_3dl's SubMaps on the device (additions to ABI version 2; no existing struct or entry
+   changes).  src/dddmr_mcl_3dl/src/sub_maps.cpp keeps the pose graph's keyframes, and every
+   sub_map_warmup_trigger_distance (20 m) collects the keyframes within sub_map_search_radius (50 m) of the robot,
+   concatenates their corner and ground clouds, builds two kd-trees and estimates one normal per ground point
+   (pcl::NormalEstimation, setKSearch(20)), then swaps the result in.  Here the keyframes live in device memory once; a
+   warm-up is a list of keyframe ids, and nothing but that list crosses the bus.  Line numbers are sub_maps.cpp's.
+
+   dddmr_rollout_submap_create needs a dddmr_rollout_mcl_create first (DDDMR_ERR_STATE) and allocates the keyframe
+   store, a warm-up generation beside mcl_set_map's two and the neighbour scratch.  normal_k is 3 .. 32 (the reference:
+   20).  A later dddmr_rollout_mcl_create drops the store: every sub-map call then answers DDDMR_ERR_STATE until the
+   next submap_create.  A second submap_create starts an empty store and forgets a warm-up; the current map stays.
+
+   dddmr_rollout_submap_add_keyframe is one iteration of readPoseGraph's loop (:126-156) from pcl::transformPointCloud
+   on: each output coordinate is the double expression t0 * x + t1 * y + t2 * z + t3 rounded to float once.
+   T_map_base is 3 x 4 row-major, NULL = the clouds are in the map frame already; the quaternion from roll / pitch / yaw
+   stays with the caller.  position is the keyframe's pose (what the reference puts into its pose kd-tree).  The store is
+   append-only; ids are 0, 1, 2, ... in call order.  DDDMR_ERR_CAPACITY beyond max_keyframes or either point capacity;
+   DDDMR_ERR_BAD_ARG for a non-finite transform, position or coordinate, or a bad stride.  A refused call stores nothing.
+
+   dddmr_rollout_submap_select is the keyframe radius search (:225-235), host arithmetic: the position and the keyframe
+   positions rounded to float, FLANN's L2_Simple in float (x y z order), kept where d2 <= float(radius * radius).  Ids
+   come back ASCENDING (the reference asks FLANN for an unsorted result, whose order is the tree's traversal order;
+   DESIGN.md 5).  ids_out NULL: count only; a capacity below the count is DDDMR_ERR_CAPACITY with *n the count.
+
+   dddmr_rollout_submap_warm_up is the second half of warmUpThread (:283-298): the listed keyframes' corner clouds, then
+   their ground clouds, gathered device to device in the order given; the two grids as mcl_set_map builds them; the
+   normal_k nearest ground points of every ground point (the point included, ordered by (d2, index) with FLANN's float
+   d2; all of them when there are fewer); NormalEstimation's normal over them as for the observation (mean and
+   covariance about the first neighbour, PCL's closed-form eigen33, flipped toward (0, 0, 0), NaN below 3 neighbours).
+   The result is the warm-up generation; the current one and every mcl_measure answer are untouched until the swap.
+   DDDMR_ERR_BAD_ARG: an unknown or repeated id, or the extent mcl_set_map refuses (4096 m on an axis, 1e6 m from the
+   origin); DDDMR_ERR_CAPACITY above mcl_create's max_map_points / max_ground_points; DDDMR_ERR_STATE while a
+   dddmr_rollout_tick_begin is pending.  A refused call leaves an earlier warm-up in place.  stats (may be NULL):
+   launches does not depend on the clouds' sizes (an empty cloud skips its own), host_waits is 1; max_rings_searched is
+   the widest shell of grid cells a point's search reached, n_brute_force the points that finished by a pass over
+   the whole cloud instead.
+
+   dddmr_rollout_submap_swap is swapKdTree (:319-342): the warm-up generation becomes current, the warm-up slot empty.
+   DDDMR_ERR_STATE without a ready warm-up.  The first sub-map of a run (:224-268) is a warm-up followed by a swap.
+   dddmr_rollout_mcl_set_map keeps working and replaces the current generation only.
+
+   dddmr_rollout_submap_get: what the reference publishes as sub_map / sub_ground, and what tests need.  which: 0 the
+   current generation, 1 the warm-up (zero points when there is none).  Any output may be NULL; DDDMR_ERR_CAPACITY when
+   one is wanted and its capacity is below the count.  neighbours_out is [n_ground][normal_k], -1 padded; it answers for
+   a generation made by warm_up and gives -1 rows for one made by mcl_set_map. */
+typedef struct {
+  uint32_t max_keyframes;
+  uint32_t max_store_map_points, max_store_ground_points;   /* all keyframes' corner / ground points together */
+  uint32_t normal_k;                                  /* 3 .. 32; the reference: 20 */
+  uint32_t reserved[2];
+} dddmr_submap_config;
+
+typedef struct {
+  uint32_t n_keyframes, n_map, n_ground;
+  uint32_t n_nan_normals;
+  uint32_t max_rings_searched;
+  uint32_t launches, host_waits;
+  uint32_t n_brute_force;
+} dddmr_submap_stats;
+
+int dddmr_rollout_submap_create(dddmr_rollout_ctx* ctx, const dddmr_submap_config* cfg);
+int dddmr_rollout_submap_add_keyframe(dddmr_rollout_ctx* ctx, const float* corner_xyz, size_t n_corner, size_t corner_stride_bytes,
+                                      const float* ground_xyz, size_t n_ground, size_t ground_stride_bytes,
+                                      const double T_map_base[12] /* 3x4 row-major, NULL = already in the map frame */,
+                                      const double position[3], int32_t* id_out);
+int dddmr_rollout_submap_select(dddmr_rollout_ctx* ctx, const double position[3], double radius, int32_t* ids_out, size_t capacity,
+                                size_t* n);
+int dddmr_rollout_submap_warm_up(dddmr_rollout_ctx* ctx, const int32_t* ids, size_t n_ids, dddmr_submap_stats* stats);
+int dddmr_rollout_submap_swap(dddmr_rollout_ctx* ctx);
+int dddmr_rollout_submap_get(dddmr_rollout_ctx* ctx, int32_t which /* 0 current, 1 warm-up */, float* map_xyz_out, size_t map_capacity,
+                             size_t* n_map, float* ground_xyz_out, float* normals_out,
+                             int32_t* neighbours_out /* [n_ground][normal_k], -1 padded */, size_t ground_capacity, size_t* n_ground);
+
 /* Measurement aid ("a measured stream-copy ceiling on the same GPU"): streams
    `bytes` (>= 1 GiB recommended: beyond the 256 MB of MALL) `reps` times through a float4 copy
    kernel and a read-only kernel on the context's device; *copy_gbps counts read + write bytes.

@@ -279,6 +279,29 @@ class LocalPlanner {
     quality.swap(qual);
     return DDDMR_OK;
   }
+  // the localiser's sub-maps (mcl_3dl's SubMaps): the keyframes in device memory, the radius search over their poses,
+  // the warm-up (concatenation, grids, ground normals) and the swap; the library's codes are returned, not thrown
+  int submapCreate(const dddmr_submap_config& cfg) { return dddmr_rollout_submap_create(ctx_, &cfg); }
+  int submapAddKeyframe(const float* corner_xyz, size_t n_corner, size_t corner_stride_bytes, const float* ground_xyz, size_t n_ground,
+                        size_t ground_stride_bytes, const double T_map_base[12], const double position[3], int32_t* id_out = nullptr) {
+    return dddmr_rollout_submap_add_keyframe(ctx_, corner_xyz, n_corner, corner_stride_bytes, ground_xyz, n_ground, ground_stride_bytes, T_map_base,
+                                             position, id_out);
+  }
+  int submapSelect(const double position[3], double radius, std::vector<int32_t>& ids) {
+    size_t n = 0;
+    int rc = dddmr_rollout_submap_select(ctx_, position, radius, nullptr, 0, &n);
+    if (rc != DDDMR_OK) return rc;
+    std::vector<int32_t> out(n);
+    if (n) rc = dddmr_rollout_submap_select(ctx_, position, radius, out.data(), out.size(), &n);
+    if (rc != DDDMR_OK) return rc;
+    out.resize(n);
+    ids.swap(out);
+    return DDDMR_OK;
+  }
+  int submapWarmUp(const std::vector<int32_t>& ids, dddmr_submap_stats* stats = nullptr) {
+    return dddmr_rollout_submap_warm_up(ctx_, ids.data(), ids.size(), stats);
+  }
+  int submapSwap() { return dddmr_rollout_submap_swap(ctx_); }
   // prune plan poses, x y z qx qy qz qw each (output of Local_Planner::prunePlan)
   void setPlan(const double* poses_xyz_qxyzw, size_t n_poses) {
     check(dddmr_rollout_set_prune_plan(ctx_, poses_xyz_qxyzw, n_poses));
