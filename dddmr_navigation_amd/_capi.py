@@ -331,6 +331,25 @@ class SubmapStats(C.Structure):
     ]
 
 
+class StaticLayerConfig(C.Structure):
+    """dddmr_static_layer_config: static_layer.cpp's parameters, the two global radii and the capacities."""
+    _fields_ = [
+        ("max_ground_points", C.c_uint32), ("max_map_points", C.c_uint32), ("max_edges", C.c_uint32),
+        ("use_adaptive_connection", C.c_int32), ("adaptive_connection_number", C.c_uint32),
+        ("enable_edge_detection", C.c_int32), ("generate_static_graph", C.c_int32), ("reserved", C.c_uint32),
+        ("radius_of_ground_connection", C.c_double), ("static_imposing_radius", C.c_double),
+        ("inscribed_radius", C.c_double), ("max_obstacle_distance", C.c_double),
+    ]
+
+
+class StaticLayerStats(C.Structure):
+    _fields_ = [
+        ("n_edges", C.c_uint64), ("n_ground", C.c_uint32), ("n_map", C.c_uint32), ("max_degree", C.c_uint32), ("n_long_rows", C.c_uint32),
+        ("n_overhang", C.c_uint32), ("n_near_obstacle", C.c_uint32), ("n_zone_points", C.c_uint32), ("n_zone_nodes", C.c_uint32),
+        ("launches", C.c_uint32), ("host_waits", C.c_uint32),
+    ]
+
+
 MCL_BRANCH_CLUSTERS, MCL_BRANCH_X_DOMINANT, MCL_BRANCH_Y_DOMINANT = 0, 1, 2
 
 
@@ -348,7 +367,8 @@ class RolloutDebug(C.Structure):
 
 
 # the structs dddmr_rollout_sizeof knows, in its order (rollout_engine.hip: case 0 .. 22; the sub-map structs
-# are pinned by static_asserts in mcl_submap.hip.h and by tests/test_submap_cpu.py instead)
+# are pinned by static_asserts in mcl_submap.hip.h and by tests/test_submap_cpu.py instead, the static layer's by
+# static_layer.hip.h and tests/test_static_layer_cpu.py)
 SIZEOF_STRUCTS = (
     CriticConfig, TheoryConfig, RolloutConfig, TickInput, RolloutResult, RolloutDebug, MarkingConfig, MarkingStats,
     DepthSourceConfig, DepthImageConfig, DepthFrustumConfig, DepthMarkConfig, DepthMarkStats, DepthLayerConfig,
@@ -460,6 +480,13 @@ _TABLE = {
     "submap_warm_up": (_int, [_ctx, _vp, _sz, _P(SubmapStats)]),
     "submap_swap": _plain,
     "submap_get": (_int, [_ctx, _i32, _vp, _sz, _pn, _vp, _vp, _vp, _sz, _pn]),
+    "static_layer_create": (_int, [_ctx, _P(StaticLayerConfig)]),
+    "static_layer_build": (_int, [_ctx] + _cloud + _cloud + [_P(StaticLayerStats)]),
+    "static_layer_get_graph": (_int, [_ctx, _vp, _vp, _vp, _sz, _pn]),
+    "static_layer_get_dgraph": _fixed,
+    "static_layer_set_zones": (_int, [_ctx] + _cloud + [_dbl, _P(StaticLayerStats)]),
+    "static_layer_get_zone_dgraph": _fixed,
+    "static_layer_bind": (_int, [_ctx, _i32, _i32]),
     "stream_ceiling": (_int, [_ctx, _sz, _i32, _pd, _pd]),
     "selftest_sincos": (_int, [_ctx, _vp, _sz, _vp, _vp]),
     "last_error": (_str, [_ctx]),

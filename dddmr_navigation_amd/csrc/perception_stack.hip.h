@@ -113,6 +113,11 @@ double* stack_list_value(const StackState* s, char* base) { return reinterpret_c
 uint32_t* stack_list_node(const StackState* s, char* base) { return reinterpret_cast<uint32_t*>(base + 8 + 8 * stack_cap(s)); }
 uint8_t* stack_list_mask(const StackState* s, char* base) { return reinterpret_cast<uint8_t*>(base + 8 + 12 * stack_cap(s)); }
 
+// A host slot for a layer that fills it device to device (static_layer_bind): its array, null for a slot out of range;
+// and the mark stack_set_host_layer leaves once the values are in.
+double* stack_host_slot(StackState* s, int slot) { return slot >= 0 && slot < s->cfg.n_host_layers ? s->host_layer[slot] : nullptr; }
+void stack_host_slot_set(StackState* s, int slot) { s->host_set[slot] = true; }
+
 // The stacked arrays from the layers as they are now, on the context's stream, and the wait for it.  tick_mu held, and
 // producer_mu when the stack has a depth layer.  publish_only: after create / reset -- the change list comes out empty.
 int stack_recompute(dddmr_rollout_ctx* ctx, StackState* s, bool publish_only, uint32_t* ops) {

@@ -50,6 +50,7 @@ struct DepthMarkState;                     // the depth camera's selfMark, depth
 struct DepthLayerState;                    // the depth camera layer's store, dGraph and lethal set, depth_layer.hip.h
 struct StackState;                         // the perception stack over the two layers, perception_stack.hip.h
 struct MclState;                           // the particle filter's lidar likelihood, mcl_measure.hip.h
+struct StaticLayerState;                   // the static and no-entry layers' sGraph and dGraphs, static_layer.hip.h
 template <class T>
 using ModuleSlot = std::unique_ptr<T, LateDelete<T>>;   // enters its slot once complete (each module's create)
 
@@ -166,6 +167,7 @@ struct dddmr_rollout_ctx {
   ModuleSlot<DepthLayerState> dlayer; // dddmr_rollout_depth_layer_create
   ModuleSlot<StackState> stack;      // dddmr_rollout_stack_create (tick_mu)
   ModuleSlot<MclState> mcl;          // dddmr_rollout_mcl_create (tick_mu)
+  ModuleSlot<StaticLayerState> slayer; // dddmr_rollout_static_layer_create (tick_mu)
 
   std::mutex tick_mu;
   std::mutex err_mu;        // last_error is written by tick and sensor threads alike
@@ -388,6 +390,7 @@ void dddmr_rollout_destroy(dddmr_rollout_ctx* ctx) {
   ctx->stack.reset();
   ctx->dlayer.reset();
   ctx->mcl.reset();
+  ctx->slayer.reset();
   if (ctx->comm) (void)rccl().comm_destroy(ctx->comm);
   dev_free(ctx->mem);
   perception_free(ctx->feed);
@@ -1183,3 +1186,4 @@ int dddmr_rollout_get_best_cuboids(dddmr_rollout_ctx* ctx, float* vertices_out, 
 #include "mcl_measure.hip.h"
 #include "mcl_observation.hip.h"
 #include "mcl_submap.hip.h"
+#include "static_layer.hip.h"

@@ -1283,6 +1283,91 @@ int dddmr_rollout_submap_get(dddmr_rollout_ctx* ctx, int32_t which /* 0 current,
                              size_t* n_map, float* ground_xyz_out, float* normals_out,
                              int32_t* neighbours_out /* [n_ground][normal_k], -1 padded */, size_t ground_capacity, size_t* n_ground);
 
+/* ---- The static layer and the no-entry layer on the device: sGraph, dGraphs, stack slots (additions to ABI version 2;
+   no existing struct or entry changes).  src/dddmr_perception_3d/plugins/static_layer.cpp regenerates its graphs in
+   selfClear (:201-231) whenever the map and ground clouds are republished: one radius search per ground node for the
+   edges of sGraph (generateStaticGraph, :233-285), the nearest map point of every node (:275-282) and the overhang test
+   (radiusSearchConnection, :390-415) for its dGraph.  plugins/no_entry_layer.cpp inflates its enabled zones into a dGraph
+   of its own (:265-283).  DESIGN.md 4d-3 restates the arithmetic; in short: radiusSearch(p, r) keeps
+   l2_simple < float(double(r) * double(r)), strict, the query point included; an edge weight is sqrtf(d2), a dGraph value
+   double(sqrtf(d2)); setValue is a minimum.
+
+   dddmr_rollout_static_layer_create allocates two generations of the graph and the build's scratch.  DDDMR_ERR_BAD_ARG:
+   adaptive_connection_number outside 1 .. 32 in adaptive mode, a radius that is negative, not finite or above 1000 m,
+   max_ground_points 0; DDDMR_ERR_CAPACITY: more than 2^24 ground points, 2^26 map points or 2^30 edges.  A second create
+   replaces the state (graphs and dGraphs are gone); a refused one leaves it.
+
+   dddmr_rollout_static_layer_build is one selfClear regeneration (:201-231) from the two clouds (only x y z are read):
+     neighbourhood of node i (:240-261): radiusSearch(node, radius_of_ground_connection), or in adaptive mode
+       radiusSearch(node, double(0.5f) + 0.2 * k) for the first k in 1 .. 101 whose count reaches
+       adaptive_connection_number, else k = 101;
+     sGraph (:263-273, static_graph.cpp:46-48), when generate_static_graph: node i's edges are its neighbourhood with
+       weights sqrtf(d2), the self edge of weight 0 included, as CSR rows in ascending neighbour index (the std::set's
+       order); without generate_static_graph the graph has no edge (the reference does not call generateStaticGraph);
+     dGraph: n_ground + 1 doubles, all max_obstacle_distance (resetdGraph, :422-427), then minima: when
+       enable_edge_detection, 0.25 for a node whose neighbourhood holds at least 5 points and that has more than 10 map
+       points inside radiusSearch(node, static_imposing_radius) with node.z + 0.1 <= z <= node.z + 1.0 and x, y within
+       0.5 of the node's (pcl::PassThrough: float limits, both ends inclusive); when generate_static_graph,
+       double(sqrtf(d2)) of the nearest map point when that is below inscribed_radius.
+   The RANSAC plane, the ring probes and the node weights (:350-388, :417) stay with the caller.  The build goes into a
+   second generation and replaces the served one only on success.  DDDMR_ERR_CAPACITY: more points than created for, or
+   more edges than max_edges -- stats.n_edges is then the true count.  DDDMR_ERR_BAD_ARG: an empty ground, a coordinate
+   that is not finite or beyond 1e6 m, a cloud wider than 4096 m on an axis.  DDDMR_ERR_STATE: no static_layer_create.
+   A successful build drops the zones' dGraph (requestAllLayersToResetDGraph, :207): call set_zones again.  stats (may
+   be NULL): host_waits is 2 (the edge count, then the result); n_long_rows counts the rows longer than
+   DDDMR_STATIC_LAYER_ROW_LDS entries, which are ranked in global memory instead of LDS.
+
+   dddmr_rollout_static_layer_get_graph: row_start_out takes n_ground + 1 entries, neighbour_out and weight_out n_edges
+   each (edge_capacity entries are there).  Any output may be NULL; all NULL: the count only.  DDDMR_ERR_CAPACITY when
+   an edge output is wanted and edge_capacity is below the count.  dddmr_rollout_static_layer_get_dgraph: n_ground + 1
+   doubles (StaticLayer::get_dGraphValue, :429-434).
+
+   dddmr_rollout_static_layer_set_zones rebuilds the no-entry dGraph (no_entry_layer.cpp:265-283) over the last build's
+   ground from the concatenated points of the enabled zones: node i gets min(max_obstacle_distance, double(sqrtf(d2))) of
+   its nearest zone point when d2 < float(inflation_distance^2), which equals the reference's loop over the zone points
+   (l2_simple is symmetric, sqrtf monotone).  n_points = 0: every zone is off, every value max_obstacle_distance.
+   Reading zones.yaml and the .pcd files, the markers and the layer's lethal cloud stay with the caller.
+   DDDMR_ERR_STATE before the first build.  dddmr_rollout_static_layer_get_zone_dgraph: the same n_ground + 1 layout.
+
+   dddmr_rollout_static_layer_bind copies one of the two dGraphs device to device into a host slot of the perception
+   stack; the slot is then exactly as after dddmr_rollout_stack_set_host_layer with the same values: set, and shown by
+   the next stack_update's change list.  DDDMR_ERR_STATE without a stack or without that dGraph; DDDMR_ERR_BAD_ARG for a
+   slot out of range or a build whose n_ground differs from the stack's.
+
+   All seven run on the context's stream and answer DDDMR_ERR_STATE while a dddmr_rollout_tick_begin is pending.  A
+   refused or failed call leaves the previous build, dGraphs and slots as they were. */
+#define DDDMR_STATIC_LAYER_ROW_LDS 512                /* entries of a row the fill pass ranks in LDS */
+typedef struct {
+  uint32_t max_ground_points, max_map_points, max_edges;
+  int32_t use_adaptive_connection;                    /* static_layer.cpp:240 */
+  uint32_t adaptive_connection_number;                /* 1 .. 32 in adaptive mode */
+  int32_t enable_edge_detection;                      /* :215  the overhang part */
+  int32_t generate_static_graph;                      /* :218  sGraph and the nearest-obstacle part */
+  uint32_t reserved;
+  double radius_of_ground_connection, static_imposing_radius;
+  double inscribed_radius, max_obstacle_distance;     /* gbl_utils_->getInscribedRadius() / getMaxObstacleDistance() */
+} dddmr_static_layer_config;
+
+typedef struct {
+  uint64_t n_edges;
+  uint32_t n_ground, n_map;
+  uint32_t max_degree, n_long_rows;
+  uint32_t n_overhang, n_near_obstacle;               /* nodes set to 0.25 / to their nearest obstacle's distance */
+  uint32_t n_zone_points, n_zone_nodes;               /* set_zones: points given, nodes inside an inflation ball */
+  uint32_t launches, host_waits;
+} dddmr_static_layer_stats;
+
+int dddmr_rollout_static_layer_create(dddmr_rollout_ctx* ctx, const dddmr_static_layer_config* cfg);
+int dddmr_rollout_static_layer_build(dddmr_rollout_ctx* ctx, const float* ground_xyz, size_t n_ground, size_t ground_stride_bytes,
+                                     const float* map_xyz, size_t n_map, size_t map_stride_bytes, dddmr_static_layer_stats* stats);
+int dddmr_rollout_static_layer_get_graph(dddmr_rollout_ctx* ctx, uint32_t* row_start_out /* [n_ground + 1] */, uint32_t* neighbour_out,
+                                         float* weight_out, size_t edge_capacity, size_t* n_edges);
+int dddmr_rollout_static_layer_get_dgraph(dddmr_rollout_ctx* ctx, double* values_out, size_t capacity);
+int dddmr_rollout_static_layer_set_zones(dddmr_rollout_ctx* ctx, const float* zone_xyz, size_t n_points, size_t stride_bytes,
+                                         double inflation_distance, dddmr_static_layer_stats* stats);
+int dddmr_rollout_static_layer_get_zone_dgraph(dddmr_rollout_ctx* ctx, double* values_out, size_t capacity);
+int dddmr_rollout_static_layer_bind(dddmr_rollout_ctx* ctx, int32_t which /* 0 static, 1 no-entry */, int32_t slot);
+
 /* Measurement aid ("a measured stream-copy ceiling on the same GPU"): streams
    `bytes` (>= 1 GiB recommended: beyond the 256 MB of MALL) `reps` times through a float4 copy
    kernel and a read-only kernel on the context's device; *copy_gbps counts read + write bytes.

@@ -302,6 +302,33 @@ class LocalPlanner {
     return dddmr_rollout_submap_warm_up(ctx_, ids.data(), ids.size(), stats);
   }
   int submapSwap() { return dddmr_rollout_submap_swap(ctx_); }
+  // the static layer and the no-entry layer (static_layer.cpp:201-285, :390-415; no_entry_layer.cpp:265-283): sGraph as
+  // CSR rows, the two dGraphs and their binding to the stack's host slots; the library's codes are returned, not thrown
+  int staticLayerCreate(const dddmr_static_layer_config& cfg) { return dddmr_rollout_static_layer_create(ctx_, &cfg); }
+  int staticLayerBuild(const float* ground_xyz, size_t n_ground, size_t ground_stride_bytes, const float* map_xyz, size_t n_map,
+                       size_t map_stride_bytes, dddmr_static_layer_stats* stats = nullptr) {
+    return dddmr_rollout_static_layer_build(ctx_, ground_xyz, n_ground, ground_stride_bytes, map_xyz, n_map, map_stride_bytes, stats);
+  }
+  // row_start must hold n_ground + 1 entries on entry (the build's stats say how many nodes there are)
+  int staticLayerGraph(std::vector<uint32_t>& row_start, std::vector<uint32_t>& neighbour, std::vector<float>& weight) {
+    size_t n = 0;
+    int rc = dddmr_rollout_static_layer_get_graph(ctx_, nullptr, nullptr, nullptr, 0, &n);
+    if (rc != DDDMR_OK) return rc;
+    std::vector<uint32_t> nb(n);
+    std::vector<float> w(n);
+    rc = dddmr_rollout_static_layer_get_graph(ctx_, row_start.data(), n ? nb.data() : nullptr, n ? w.data() : nullptr, n, &n);
+    if (rc != DDDMR_OK) return rc;
+    neighbour.swap(nb);
+    weight.swap(w);
+    return DDDMR_OK;
+  }
+  int staticLayerDGraph(std::vector<double>& values) { return dddmr_rollout_static_layer_get_dgraph(ctx_, values.data(), values.size()); }
+  int staticLayerSetZones(const float* zone_xyz, size_t n_points, size_t stride_bytes, double inflation_distance,
+                          dddmr_static_layer_stats* stats = nullptr) {
+    return dddmr_rollout_static_layer_set_zones(ctx_, zone_xyz, n_points, stride_bytes, inflation_distance, stats);
+  }
+  int staticLayerZoneDGraph(std::vector<double>& values) { return dddmr_rollout_static_layer_get_zone_dgraph(ctx_, values.data(), values.size()); }
+  int staticLayerBind(int32_t which /* 0 static, 1 no-entry */, int32_t slot) { return dddmr_rollout_static_layer_bind(ctx_, which, slot); }
   // prune plan poses, x y z qx qy qz qw each (output of Local_Planner::prunePlan)
   void setPlan(const double* poses_xyz_qxyzw, size_t n_poses) {
     check(dddmr_rollout_set_prune_plan(ctx_, poses_xyz_qxyzw, n_poses));
