@@ -350,6 +350,26 @@ class StaticLayerStats(C.Structure):
     ]
 
 
+class GlobalPlanConfig(C.Structure):
+    """dddmr_global_plan_config: A_Star_on_PreGraph's parameters, where the dGraph comes from, and the capacities."""
+    _fields_ = [
+        ("turning_weight", C.c_double), ("a_star_expanding_radius", C.c_double), ("inscribed_radius", C.c_double),
+        ("inflation_descending_rate", C.c_double), ("dgraph_source", C.c_int32), ("max_queries", C.c_uint32),
+        ("max_open_entries", C.c_uint32), ("max_expansions", C.c_uint32),
+    ]
+
+
+class GlobalPlanResult(C.Structure):
+    _fields_ = [
+        ("status", C.c_uint32), ("path_offset", C.c_uint32), ("path_len", C.c_uint32), ("n_expanded", C.c_uint32), ("n_pushed", C.c_uint32),
+        ("n_discarded_closed", C.c_uint32), ("g_goal", C.c_float), ("host_waits", C.c_uint32),
+    ]
+
+
+GLOBAL_PLAN_MAX_QUERIES = 16
+GLOBAL_PLAN_FOUND, GLOBAL_PLAN_NO_PATH, GLOBAL_PLAN_BUDGET, GLOBAL_PLAN_OPEN_FULL = 0, 1, 2, 3
+GLOBAL_PLAN_NONE = 0xFFFFFFFF             # global_plan_nearest: no ground node inside the radius
+
 MCL_BRANCH_CLUSTERS, MCL_BRANCH_X_DOMINANT, MCL_BRANCH_Y_DOMINANT = 0, 1, 2
 
 
@@ -368,7 +388,8 @@ class RolloutDebug(C.Structure):
 
 # the structs dddmr_rollout_sizeof knows, in its order (rollout_engine.hip: case 0 .. 22; the sub-map structs
 # are pinned by static_asserts in mcl_submap.hip.h and by tests/test_submap_cpu.py instead, the static layer's by
-# static_layer.hip.h and tests/test_static_layer_cpu.py)
+# static_layer.hip.h and tests/test_static_layer_cpu.py, the global planner's by global_plan.hip.h and
+# tests/test_global_plan_cpu.py)
 SIZEOF_STRUCTS = (
     CriticConfig, TheoryConfig, RolloutConfig, TickInput, RolloutResult, RolloutDebug, MarkingConfig, MarkingStats,
     DepthSourceConfig, DepthImageConfig, DepthFrustumConfig, DepthMarkConfig, DepthMarkStats, DepthLayerConfig,
@@ -487,6 +508,11 @@ _TABLE = {
     "static_layer_set_zones": (_int, [_ctx] + _cloud + [_dbl, _P(StaticLayerStats)]),
     "static_layer_get_zone_dgraph": _fixed,
     "static_layer_bind": (_int, [_ctx, _i32, _i32]),
+    "global_plan_create": (_int, [_ctx, _P(GlobalPlanConfig)]),
+    "global_plan_set_node_weights": _fixed,
+    "global_plan_nearest": (_int, [_ctx, _vp, _sz, _vp]),
+    "global_plan_probe": (_int, [_ctx, _vp, _sz, _vp, _vp]),
+    "global_plan_plan": (_int, [_ctx, _vp, _vp, _sz, _vp, _sz, _P(GlobalPlanResult)]),
     "stream_ceiling": (_int, [_ctx, _sz, _i32, _pd, _pd]),
     "selftest_sincos": (_int, [_ctx, _vp, _sz, _vp, _vp]),
     "last_error": (_str, [_ctx]),

@@ -51,6 +51,7 @@ struct DepthLayerState;                    // the depth camera layer's store, dG
 struct StackState;                         // the perception stack over the two layers, perception_stack.hip.h
 struct MclState;                           // the particle filter's lidar likelihood, mcl_measure.hip.h
 struct StaticLayerState;                   // the static and no-entry layers' sGraph and dGraphs, static_layer.hip.h
+struct GlobalPlanState;                    // the pre-graph global planner's A* over them, global_plan.hip.h
 template <class T>
 using ModuleSlot = std::unique_ptr<T, LateDelete<T>>;   // enters its slot once complete (each module's create)
 
@@ -168,6 +169,7 @@ struct dddmr_rollout_ctx {
   ModuleSlot<StackState> stack;      // dddmr_rollout_stack_create (tick_mu)
   ModuleSlot<MclState> mcl;          // dddmr_rollout_mcl_create (tick_mu)
   ModuleSlot<StaticLayerState> slayer; // dddmr_rollout_static_layer_create (tick_mu)
+  ModuleSlot<GlobalPlanState> gplan;   // dddmr_rollout_global_plan_create (tick_mu)
 
   std::mutex tick_mu;
   std::mutex err_mu;        // last_error is written by tick and sensor threads alike
@@ -390,6 +392,7 @@ void dddmr_rollout_destroy(dddmr_rollout_ctx* ctx) {
   ctx->stack.reset();
   ctx->dlayer.reset();
   ctx->mcl.reset();
+  ctx->gplan.reset();
   ctx->slayer.reset();
   if (ctx->comm) (void)rccl().comm_destroy(ctx->comm);
   dev_free(ctx->mem);
@@ -1187,3 +1190,4 @@ int dddmr_rollout_get_best_cuboids(dddmr_rollout_ctx* ctx, float* vertices_out, 
 #include "mcl_observation.hip.h"
 #include "mcl_submap.hip.h"
 #include "static_layer.hip.h"
+#include "global_plan.hip.h"

@@ -352,6 +352,8 @@ struct StaticLayerState {
   int cur = -1;                              // the generation the getters serve, -1 before the first build
   double* zone_dgraph[2] = {nullptr, nullptr};   // [max_ground_points + 1]; [0] is served while has_zones
   bool has_zones = false;
+  bool grid_current = false;                 // `ground` is the grid of gen[cur]'s ground (a refused build leaves another one behind)
+  uint32_t ground_epoch = 0;                 // grows when a build's n_ground differs from the one before (the planner's node weights)
   // scratch of one build
   GridBuf ground, map;
   float4* map_pts = nullptr;
@@ -495,6 +497,7 @@ int dddmr_rollout_static_layer_build(dddmr_rollout_ctx* ctx, const float* ground
     HIPCHK(ctx, hipMemcpyAsync(m->map_pts, m->stage_map, (size_t)nm * sizeof(float4), hipMemcpyHostToDevice, st));
     ++launches;
   }
+  m->grid_current = false;
   const float gcell = sl_ground_cell(adaptive, c.radius_of_ground_connection), mcell = sl_map_cell(c.inscribed_radius);
   grid_shape(m->ground.g, lo[0], hi[0], gcell, gcell, m->ground.cap_cells);
   if (const int rc = grid_build(ctx, m->temp, m->temp_bytes, m->ground, g.ground_pts, ng, m->slot, st)) return rc;
@@ -544,9 +547,11 @@ int dddmr_rollout_static_layer_build(dddmr_rollout_ctx* ctx, const float* ground
   launches += 2;
   if (const int rc = feed_wait(st, &m->res_host->seq, seq, &waits)) return fail(ctx, DDDMR_ERR_HIP, "%s: launch or wait failed (%d)", what, rc);
   drain.armed = false;
+  if (m->cur < 0 || m->gen[m->cur].n_ground != ng) ++m->ground_epoch;
   g.n_ground = ng;
   g.n_edges = n_edges;
   m->cur = m->cur == 0 ? 1 : 0;
+  m->grid_current = true;
   m->has_zones = false;                                      // (requestAllLayersToResetDGraph, :207: the zones are inflated again)
   if (stats) {
     stats->n_overhang = m->res_host->n_overhang; stats->n_near_obstacle = m->res_host->n_near;

@@ -1368,6 +1368,72 @@ int dddmr_rollout_static_layer_set_zones(dddmr_rollout_ctx* ctx, const float* zo
 int dddmr_rollout_static_layer_get_zone_dgraph(dddmr_rollout_ctx* ctx, double* values_out, size_t capacity);
 int dddmr_rollout_static_layer_bind(dddmr_rollout_ctx* ctx, int32_t which /* 0 static, 1 no-entry */, int32_t slot);
 
+/* ---- The pre-graph global planner on the device graph (dddmr_rollout_global_plan_*; additions to version 2, no
+   existing struct or entry changes).  src/dddmr_global_planner/src/a_star_on_pre_graph.cpp's A_Star_on_PreGraph::getPath
+   (:191-289, use_pre_graph: true) reads two arrays that are already on the device: the static layer's sGraph
+   (dddmr_rollout_static_layer_build) and get_min_dGraphValue, the stack's stacked minimum.  These entries search them
+   where they are, so no graph and no dGraph crosses the bus for a plan.  DESIGN.md 4d-4 restates the arithmetic.
+
+   dddmr_rollout_global_plan_create needs a static_layer_create (DDDMR_ERR_STATE otherwise) and sizes the node records
+   of each of max_queries (1 .. DDDMR_GLOBAL_PLAN_MAX_QUERIES) query slots by that layer's max_ground_points.
+   dgraph_source 0: the perception stack's stacked minimum (dddmr_rollout_stack_get_min_dgraph's array); 1: the static
+   layer's own dGraph.  max_open_entries: the frontier entries a query may hold at once; max_expansions: the nodes a
+   query may close.  DDDMR_ERR_BAD_ARG: a parameter that is not finite, a count of 0, a dgraph_source other than 0 / 1.
+
+   dddmr_rollout_global_plan_set_node_weights uploads the ground cloud's `intensity` (getPath adds it at :246; the
+   device keeps none otherwise): n = the last build's n_ground, or 0 for all zero, which is also the default.  A weight
+   that is negative or not finite is DDDMR_ERR_BAD_ARG: a negative weight would let a node's self edge update the node
+   while it is expanded, which the device version excludes (a deliberate difference).  A later static_layer_build with
+   another n_ground drops the weights.
+
+   dddmr_rollout_global_plan_nearest is getStartGoalID's search (global_planner.cpp:407, :451) for n points
+   (xyz[n][3]): ids_out[i] = the nearest ground node of radiusSearch(p, 0.5), UINT32_MAX without one; equal distances
+   resolve to the lowest index.  dddmr_rollout_global_plan_probe is determineDWAPlan's goal test
+   (dynamic_window_aware_global_planner.cpp:248-270) for n points: the number of ground nodes in radiusSearch(p, 0.25)
+   and whether any of them has a dGraph value below inscribed_radius.  Both use the ground grid of the last build
+   (DDDMR_ERR_STATE when a build was refused since) and refuse a coordinate that is not finite.
+
+   dddmr_rollout_global_plan_plan runs n_queries <= max_queries independent searches in one launch, one workgroup per
+   query, with one host wait for the whole call.  Each query answers what getPath answers for it alone: results[i].status
+   FOUND with path_len node ids from start to goal at path_out + path_offset (the paths follow one another), or NO_PATH
+   (the frontier is exhausted, also where only entries of closed nodes remain: the reference reads begin() of an empty
+   set there, a deliberate difference), BUDGET (max_expansions nodes closed) or OPEN_FULL (then the call returns
+   DDDMR_ERR_CAPACITY), all three with an empty path.  n_expanded: nodes closed; n_pushed: entries the frontier set grew
+   by (the start's included); n_discarded_closed: entries of closed nodes taken off the frontier; g_goal: the goal's g.
+   start == goal gives the one-node path after one expansion.  DDDMR_ERR_STATE: no create, no build, a build without
+   generate_static_graph, dgraph_source 0 without a stack, a pending tick_begin.  DDDMR_ERR_BAD_ARG: an id >= n_ground,
+   a stack whose n_ground differs.  DDDMR_ERR_CAPACITY: more queries than max_queries, or paths beyond path_capacity
+   (results are filled in either case).
+
+   All five run on the context's stream and answer DDDMR_ERR_STATE while a dddmr_rollout_tick_begin is pending. */
+#define DDDMR_GLOBAL_PLAN_MAX_QUERIES 16
+#define DDDMR_GLOBAL_PLAN_FOUND 0
+#define DDDMR_GLOBAL_PLAN_NO_PATH 1
+#define DDDMR_GLOBAL_PLAN_BUDGET 2
+#define DDDMR_GLOBAL_PLAN_OPEN_FULL 3
+typedef struct {
+  double turning_weight;                              /* a_star_on_pre_graph.cpp:246 */
+  double a_star_expanding_radius;                     /* :222 */
+  double inscribed_radius, inflation_descending_rate; /* :209-210 */
+  int32_t dgraph_source;                              /* 0 the stack's minimum, 1 the static layer's dGraph */
+  uint32_t max_queries, max_open_entries, max_expansions;
+} dddmr_global_plan_config;
+
+typedef struct {
+  uint32_t status;                                    /* DDDMR_GLOBAL_PLAN_* */
+  uint32_t path_offset, path_len;
+  uint32_t n_expanded, n_pushed, n_discarded_closed;
+  float g_goal;
+  uint32_t host_waits;                                /* of the whole call */
+} dddmr_global_plan_result;
+
+int dddmr_rollout_global_plan_create(dddmr_rollout_ctx* ctx, const dddmr_global_plan_config* cfg);
+int dddmr_rollout_global_plan_set_node_weights(dddmr_rollout_ctx* ctx, const float* weights, size_t n);
+int dddmr_rollout_global_plan_nearest(dddmr_rollout_ctx* ctx, const float* xyz, size_t n, uint32_t* ids_out);
+int dddmr_rollout_global_plan_probe(dddmr_rollout_ctx* ctx, const float* xyz, size_t n, uint32_t* n_ground_near_out, uint8_t* blocked_out);
+int dddmr_rollout_global_plan_plan(dddmr_rollout_ctx* ctx, const uint32_t* start_id, const uint32_t* goal_id, size_t n_queries,
+                                   uint32_t* path_out, size_t path_capacity, dddmr_global_plan_result* results);
+
 /* Measurement aid ("a measured stream-copy ceiling on the same GPU"): streams
    `bytes` (>= 1 GiB recommended: beyond the 256 MB of MALL) `reps` times through a float4 copy
    kernel and a read-only kernel on the context's device; *copy_gbps counts read + write bytes.

@@ -329,6 +329,27 @@ class LocalPlanner {
   }
   int staticLayerZoneDGraph(std::vector<double>& values) { return dddmr_rollout_static_layer_get_zone_dgraph(ctx_, values.data(), values.size()); }
   int staticLayerBind(int32_t which /* 0 static, 1 no-entry */, int32_t slot) { return dddmr_rollout_static_layer_bind(ctx_, which, slot); }
+  // the pre-graph global planner on the device graph (a_star_on_pre_graph.cpp:191-289; global_planner.cpp:407, :451;
+  // dynamic_window_aware_global_planner.cpp:248-270); the library's codes are returned, not thrown
+  int globalPlanCreate(const dddmr_global_plan_config& cfg) { return dddmr_rollout_global_plan_create(ctx_, &cfg); }
+  int globalPlanSetNodeWeights(const std::vector<float>& w) { return dddmr_rollout_global_plan_set_node_weights(ctx_, w.empty() ? nullptr : w.data(), w.size()); }
+  // xyz: n points of 3 floats
+  int globalPlanNearest(const std::vector<float>& xyz, std::vector<uint32_t>& ids) {
+    ids.assign(xyz.size() / 3, 0xFFFFFFFFu);
+    return dddmr_rollout_global_plan_nearest(ctx_, xyz.data(), ids.size(), ids.data());
+  }
+  int globalPlanProbe(const std::vector<float>& xyz, std::vector<uint32_t>& n_ground_near, std::vector<uint8_t>& blocked) {
+    n_ground_near.assign(xyz.size() / 3, 0u);
+    blocked.assign(xyz.size() / 3, 0);
+    return dddmr_rollout_global_plan_probe(ctx_, xyz.data(), n_ground_near.size(), n_ground_near.data(), blocked.data());
+  }
+  // path must have room for the paths of all queries (at most n_ground nodes each); results: one per query
+  int globalPlanPlan(const std::vector<uint32_t>& start, const std::vector<uint32_t>& goal, std::vector<uint32_t>& path,
+                     std::vector<dddmr_global_plan_result>& results) {
+    if (start.size() != goal.size()) return DDDMR_ERR_BAD_ARG;
+    results.assign(start.size(), dddmr_global_plan_result{});
+    return dddmr_rollout_global_plan_plan(ctx_, start.data(), goal.data(), start.size(), path.data(), path.size(), results.data());
+  }
   // prune plan poses, x y z qx qy qz qw each (output of Local_Planner::prunePlan)
   void setPlan(const double* poses_xyz_qxyzw, size_t n_poses) {
     check(dddmr_rollout_set_prune_plan(ctx_, poses_xyz_qxyzw, n_poses));
