@@ -29,7 +29,7 @@
 
 #include <cmath>
 
-#include "marking.hip.h"
+#include "point_grid.hip.h"   // the observation grid and its walks; rocPRIM; Owned, dev_alloc (voxel_table.hip.h)
 
 #pragma clang fp contract(off)
 
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(256) void k_dc_bounds(const float4* __restrict__ pt
   }
 }
 
-// One lane: the grid's geometry from the box (grid_shape of the marking layer, on the device), into the header the
+// One lane: the grid's geometry from the box (point_grid_plan.hip.h's grid_shape, on the device), into the header the
 // other kernels read.  The header's cell_start / sorted pointers were set once by the host.
 __global__ void k_dc_shape(uint32_t* __restrict__ bounds, PointGrid* __restrict__ hdr, uint32_t n, uint32_t cap_cells) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;

@@ -24,7 +24,10 @@
 #include <stdint.h>
 
 #include "depth_clear.hip.h"
-#include "marking.hip.h"
+#include "marking.hip.h"           // the cluster kernels of the general route
+#include "marking_host.hip.h"      // ... and its host side: cluster_temp_bytes, the static grids, base_plane
+#include "point_grid_plan.hip.h"   // cloud_arg_ok
+#include "sensor_sources.hip.h"    // the depth sources' frustums and observation grid
 
 #pragma clang fp contract(off)
 

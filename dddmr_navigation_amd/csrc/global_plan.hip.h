@@ -24,7 +24,10 @@
 #include <stdint.h>
 
 #include "global_plan_plan.hip.h"
-#include "marking.hip.h"
+#include "perception_stack.hip.h"  // StackState: the stacked minimum dGraph (dgraph_source 0)
+#include "point_grid.hip.h"        // PointGrid, grid_for_each, grid_nearest_id
+#include "point_grid_plan.hip.h"   // HostCloud
+#include "static_layer.hip.h"      // StaticLayerState: the rows, the ground grid and the layer's own dGraph; kSlPad, sl_radius2
 
 #pragma clang fp contract(off)
 
@@ -215,15 +218,8 @@ __global__ __launch_bounds__(256) void k_gp_nearest(PointGrid g, const float4* _
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const float4 p = q[i];
-  float best = r2;                                                                   // radiusSearch keeps d2 < r2
-  uint32_t best_id = kGpNone;
-  grid_for_each(g, p.x, p.y, p.z, r_box, [&](const float4 c) {
-    const float d2 = l2_simple(c.x, c.y, c.z, p.x, p.y, p.z);
-    const uint32_t id = (uint32_t)__float_as_int(c.w);
-    if (d2 < r2 && (d2 < best || (d2 == best && id < best_id))) { best = d2; best_id = id; }
-    return false;
-  });
-  ids[i] = best_id;
+  static_assert(kGpNone == kGridNone, "ids_out's \"no node\" is the grid's");
+  ids[i] = grid_nearest_id(g, p.x, p.y, p.z, r_box, r2).id;
 }
 
 __global__ __launch_bounds__(256) void k_gp_probe(PointGrid g, const float4* __restrict__ q, uint32_t n, float r_box, float r2, const double* __restrict__ dgraph,
@@ -253,7 +249,7 @@ __global__ void k_gp_finish(uint32_t* __restrict__ word, uint32_t seq) {
 
 }  // namespace dddmr
 
-// ---- host (included by rollout_engine.hip after static_layer.hip.h) -----------------------------------------------
+// ---- host (included by rollout_engine.hip after the context) ---------------------------------------------------------
 namespace {
 
 struct GpOut {                               // host-mapped; seq is stored last, by k_gp_finish
@@ -304,17 +300,6 @@ int global_plan_state(dddmr_rollout_ctx* ctx, const char* what, bool need_graph,
   *p_out = p;
   *m_out = m;
   return DDDMR_OK;
-}
-
-// n points of the caller's into a temporary device array; false for a coordinate that is not finite
-bool global_plan_points(const float* xyz, size_t n, std::vector<float4>& pts) {
-  pts.resize(std::max<size_t>(n, 1));
-  for (size_t i = 0; i < n; ++i) {
-    for (int a = 0; a < 3; ++a)
-      if (!std::isfinite(xyz[3 * i + a])) return false;
-    pts[i] = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], 0.f);
-  }
-  return true;
 }
 
 }  // namespace
@@ -377,8 +362,8 @@ int dddmr_rollout_global_plan_nearest(dddmr_rollout_ctx* ctx, const float* xyz, 
   const char* what = "global_plan_nearest";
   if (n && (!xyz || !ids_out)) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: null argument", what);
   if (n > (1u << 24)) return fail(ctx, DDDMR_ERR_CAPACITY, "%s: at most 2^24 points", what);
-  std::vector<float4> pts;
-  if (!global_plan_points(xyz, n, pts)) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: a coordinate is not finite", what);
+  const HostCloud pts(xyz, n, 12);                           // packed points; their box goes unused
+  if (!pts.finite) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: a coordinate is not finite", what);
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   GlobalPlanState* p = nullptr;
   StaticLayerState* m = nullptr;
@@ -392,7 +377,7 @@ int dddmr_rollout_global_plan_nearest(dddmr_rollout_ctx* ctx, const float* xyz, 
   HIPCHK(ctx, dev_alloc(scope.mem, &ids, n));
   hipStream_t st = ctx->stream;
   Drain drain{st};                                           // behind `scope`: an error exit waits before the scratch is freed
-  HIPCHK(ctx, hipMemcpyAsync(q, pts.data(), n * sizeof(float4), hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(q, pts.pts.data(), n * sizeof(float4), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_gp_nearest, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, st, m->ground.g, q, (uint32_t)n, kGpNearestRadius + kSlPad,
                      sl_radius2(0.5), ids);
   HIPCHK(ctx, hipGetLastError());
@@ -407,8 +392,8 @@ int dddmr_rollout_global_plan_probe(dddmr_rollout_ctx* ctx, const float* xyz, si
   const char* what = "global_plan_probe";
   if (n && (!xyz || !n_ground_near_out || !blocked_out)) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: null argument", what);
   if (n > (1u << 24)) return fail(ctx, DDDMR_ERR_CAPACITY, "%s: at most 2^24 points", what);
-  std::vector<float4> pts;
-  if (!global_plan_points(xyz, n, pts)) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: a coordinate is not finite", what);
+  const HostCloud pts(xyz, n, 12);                           // packed points; their box goes unused
+  if (!pts.finite) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: a coordinate is not finite", what);
   std::lock_guard<std::mutex> tk(ctx->tick_mu);
   GlobalPlanState* p = nullptr;
   StaticLayerState* m = nullptr;
@@ -425,7 +410,7 @@ int dddmr_rollout_global_plan_probe(dddmr_rollout_ctx* ctx, const float* xyz, si
   HIPCHK(ctx, dev_alloc(scope.mem, &blocked, n));
   hipStream_t st = ctx->stream;
   Drain drain{st};
-  HIPCHK(ctx, hipMemcpyAsync(q, pts.data(), n * sizeof(float4), hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(q, pts.pts.data(), n * sizeof(float4), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_gp_probe, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, st, m->ground.g, q, (uint32_t)n, kGpProbeRadius + kSlPad, sl_radius2(0.25),
                      dgraph, p->cfg.inscribed_radius, cnt, blocked);
   HIPCHK(ctx, hipGetLastError());

@@ -1,26 +1,13 @@
-// marking_buffers.hip.h -- the building blocks the marking layers share, with their allocation: a grid's storage, the
-// static grids, the cluster pipeline's scratch and the marking store.  Nothing here needs a context: each alloc takes the
-// state and its sizes and returns 0 / -1 (the caller reports), and a state frees what it owns when it dies.
+// marking_buffers.hip.h -- the building blocks the marking layers share, with their allocation: the static grids (a grid's
+// storage is point_grid.hip.h's GridBuf), the cluster pipeline's scratch and the marking store.  Nothing here needs a
+// context: each alloc takes the state and its sizes and returns 0 / -1 (the caller reports), and a state frees what it
+// owns when it dies.
 #pragma once
 
 #include "marking.hip.h"
+#include "point_grid.hip.h"   // GridBuf, grid_alloc
 
 namespace dddmr {
-
-struct GridBuf {              // a PointGrid with its storage
-  PointGrid g;
-  uint32_t cap_cells = 0, cap_points = 0;
-  uint32_t max_row = 0;       // static grids: points of the fullest (y, z) row of cells
-};
-
-inline int grid_alloc(DevAllocs& mem, GridBuf& b, uint32_t cap_cells, uint32_t cap_points) {
-  b.cap_cells = cap_cells;
-  b.cap_points = cap_points;
-  return dev_alloc(mem, &b.g.cell_start, (size_t)cap_cells + 1) == hipSuccess &&
-                 dev_alloc(mem, &b.g.sorted, std::max<uint32_t>(cap_points, 1)) == hipSuccess
-             ? 0
-             : -1;
-}
 
 // The ground and the static map: the points and a grid over each, uploaded once (static_grids_upload).
 struct StaticGrids {

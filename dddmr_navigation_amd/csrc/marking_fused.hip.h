@@ -33,6 +33,7 @@
 // the contested-voxel priority looks at.
 #pragma once
 #include "marking.hip.h"
+#include "rollout_kernels.hip.h"   // wave_incl_scan_u32
 
 #pragma clang fp contract(off)
 

@@ -70,20 +70,6 @@ struct MarkingState {
 };
 static_assert(!std::is_copy_constructible_v<MarkingState>);
 
-// count -> exclusive scan (rocPRIM storage `temp`) -> scatter on `stream`; `counts` doubles as cell_start
-int grid_build(dddmr_rollout_ctx* ctx, void* temp, size_t temp_bytes, GridBuf& b, const float4* pts, uint32_t n, uint2* slot,
-               hipStream_t stream) {
-  PointGrid& g = b.g;
-  g.n = n;
-  const size_t cells = (size_t)g.nx * g.ny * g.nz;
-  HIPCHK(ctx, hipMemsetAsync(g.cell_start, 0, (cells + 1) * sizeof(uint32_t), stream));
-  if (n == 0) return DDDMR_OK;
-  hipLaunchKernelGGL(k_grid_count, dim3((n + 255) / 256), dim3(256), 0, stream, g, pts, g.cell_start, slot);
-  HIPCHK(ctx, rocprim::exclusive_scan(temp, temp_bytes, g.cell_start, g.cell_start, 0u, cells + 1, rocprim::plus<uint32_t>(), stream));
-  hipLaunchKernelGGL(k_grid_scatter, dim3((n + 255) / 256), dim3(256), 0, stream, g, pts, slot);
-  return DDDMR_OK;
-}
-
 int upload_static(dddmr_rollout_ctx* ctx, DevAllocs& mem, void* temp, size_t temp_bytes, GridBuf& b, float4** dev, const float* xyz, size_t n,
                   size_t stride_bytes, float cell_xy, float cell_z) {
   const HostCloud h(xyz, n, stride_bytes);

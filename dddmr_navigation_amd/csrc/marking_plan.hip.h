@@ -1,5 +1,5 @@
-// marking_plan.hip.h -- the host side of a marking update that is arithmetic alone: the grid geometry helpers, the
-// transforms and MarkParams of one update (make_update_frame) and plan_fused_update(): every number the kernels of
+// marking_plan.hip.h -- the host side of a marking update that is arithmetic alone: the transforms and MarkParams of one
+// update (make_update_frame) and plan_fused_update(): every number the kernels of
 // marking_fused.hip.h are launched with.  Host code only -- no HIP runtime call, no getenv, no context -- so that
 // tests/cpp/marking_plan_test.cpp can replay recorded updates through it on a machine without a GPU.
 //
@@ -9,31 +9,12 @@
 #include <cmath>
 
 #include "marking_fused.hip.h"
-#include "tick_plan.hip.h"   // quat_to_rot
+#include "point_grid_plan.hip.h"   // grid_shape, host_cx / host_cy
+#include "tick_plan.hip.h"         // quat_to_rot
 
 namespace {
 
 using namespace dddmr;
-
-// Grid geometry over [lo, hi] with the wanted cell sizes, coarsened until it fits `cap_cells`.
-void grid_shape(PointGrid& g, const float lo[3], const float hi[3], float cell_xy, float cell_z, uint32_t cap_cells) {
-  for (;;) {
-    g.nx = std::max(1, (int)std::ceil((hi[0] - lo[0]) / cell_xy) + 1);
-    g.ny = std::max(1, (int)std::ceil((hi[1] - lo[1]) / cell_xy) + 1);
-    g.nz = std::max(1, (int)std::ceil((hi[2] - lo[2]) / cell_z) + 1);
-    if ((uint64_t)g.nx * g.ny * g.nz <= cap_cells) break;
-    cell_xy *= 1.3f;
-    cell_z *= 1.3f;
-  }
-  g.ox = lo[0]; g.oy = lo[1]; g.oz = lo[2];
-  g.inv_xy = 1.0f / cell_xy;
-  g.inv_z = 1.0f / cell_z;
-}
-
-// grid_cx / grid_cy / grid_cz of marking.hip.h on the host (same float operations)
-int host_cx(const PointGrid& g, float x) { return std::min(std::max((int)std::floor((x - g.ox) * g.inv_xy), 0), g.nx - 1); }
-int host_cy(const PointGrid& g, float y) { return std::min(std::max((int)std::floor((y - g.oy) * g.inv_xy), 0), g.ny - 1); }
-int host_cz(const PointGrid& g, float z) { return std::min(std::max((int)std::floor((z - g.oz) * g.inv_z), 0), g.nz - 1); }
 
 void quat_rotate_z(const double q[4], double out[3]) {   // tf2::quatRotate(q, (0, 0, 1)); q = x y z w
   // q * v

@@ -6,7 +6,7 @@
 //   Quat::normalized / operator*    include/mcl_3dl/quat.h:87-93,131-143,175-178
 //   the lambda around measure()     src/mcl_3dl.cpp:476-498 (quality minimum / maximum) -> k_mcl_finish
 //
-// Both kd-trees become PointGrids (marking.hip.h): every radius query is answered with FLANN's float L2_Simple distance
+// Both kd-trees become PointGrids (point_grid.hip.h): every radius query is answered with FLANN's float L2_Simple distance
 // and its strict <.  What is summed in an order the result shows is summed in that order by ONE lane: score_like over
 // the flat points and then the less-sharp points, the normal averages over the ground neighbours in FLANN's sorted
 // order (ascending float d2; ties by ground index).  Everything else runs in parallel.
@@ -18,7 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "marking.hip.h"
+#include "point_grid.hip.h"
+#include "point_grid_plan.hip.h"   // grid_shape, HostCloud, cloud_arg_ok, cloud_coords_ok
 
 #pragma clang fp contract(off)
 
@@ -32,7 +33,7 @@ constexpr uint32_t kMclMaxParticles = 1u << 20;
 // cloud's extent plus the radius.  Below 8192 m an ulp is 4.9e-4 m and 1.5 of them stay under the pad, so set_map
 // refuses a cloud wider than kMclMaxExtent on any axis (radii are at most 1000 m).
 constexpr float kMclPad = 1e-3f;
-constexpr float kMclMaxExtent = 4096.0f;
+constexpr float kMclMaxExtent = kCloudMaxExtent;   // (the name the messages print)
 // The unhealthy branch's 1-NN has no radius in the reference.  sqrtf(d2) >= 1 gives a weight <= 0: exactly 0 stays 0,
 // anything below becomes 0.01, as "none found" does.  sqrtf rounds every d2 < 1.001f that is not 1.0f itself or its
 // successor to more than 1.0f, so searching to d2 < 1.001f loses nothing.
@@ -215,22 +216,13 @@ __global__ __launch_bounds__(64) void k_mcl_ground(MclParams k, PointGrid ground
   t.flags[p] = healthy ? kMclHealthy : 0u;
 }
 
-// FLANN's radiusSearch(p, match_dist_min_, id, sqdist, 1) keeps the nearest neighbour inside the radius: the smallest d2
-// among the candidate cells' points (3e38 when they hold none); the caller applies the radius
-__device__ __forceinline__ float mcl_nearest(const PointGrid& g, float x, float y, float z, float r) {
-  float best = 3.0e38f;
-  grid_for_each(g, x, y, z, r, [&](const float4 q) {
-    best = fminf(best, l2_simple(q.x, q.y, q.z, x, y, z));
-    return false;
-  });
-  return best;
-}
 // one point's term of score_like (:198-248); w = 1 for a flat point, the intensity for a less-sharp one (x / 1.0f is x)
 __device__ __forceinline__ float mcl_term(const MclParams& k, const PointGrid& g, float4 r, float tx, float ty, float tz, float4 o,
                                           uint32_t* cnt) {
   const float3 q = mcl_transform(r, o.x, o.y, o.z, tx, ty, tz);
   if (!mcl_finite3(q.x, q.y, q.z)) return 0.f;
-  const float d2 = mcl_nearest(g, q.x, q.y, q.z, k.mdm + kMclPad);
+  // FLANN's radiusSearch(p, match_dist_min_, id, sqdist, 1) keeps the nearest neighbour inside the radius
+  const float d2 = grid_nearest(g, q.x, q.y, q.z, k.mdm + kMclPad);
   if (!(d2 < k.r2_match)) return 0.f;
   const float dist = fsub(k.mdm, fmaxf(sqrtf(d2), k.mdf));
   if (dist < 0.0f) return 0.f;
@@ -323,7 +315,7 @@ __global__ __launch_bounds__(256) void k_mcl_finish(MclParams k, MclTerms t, con
 
 }  // namespace dddmr
 
-// ---- host (included by rollout_engine.hip after marking_host.hip.h, whose grid builder this uses) -------------------
+// ---- host (included by rollout_engine.hip after the context) ---------------------------------------------------------
 namespace {
 
 struct MclObs;                             // the prepared observation, mcl_observation.hip.h
@@ -420,18 +412,6 @@ int mcl_upload(dddmr_rollout_ctx* ctx, MclState* s, GridBuf& b, float4* dev, con
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   drain.armed = false;
   return rc;
-}
-
-// finite coordinates within 1e6 m, and a box the search pad covers (kMclMaxExtent)
-bool mcl_box_ok(const float lo[3], const float hi[3]) {
-  for (int a = 0; a < 3; ++a)
-    if (!(std::fabs(lo[a]) <= 1e6f) || !(std::fabs(hi[a]) <= 1e6f) || !(hi[a] - lo[a] <= kMclMaxExtent)) return false;
-  return true;
-}
-bool mcl_cloud_ok(const HostCloud& h, size_t n) {
-  for (size_t i = 0; i < n; ++i)
-    if (!(std::fabs(h.pts[i].x) <= 1e6f) || !(std::fabs(h.pts[i].y) <= 1e6f) || !(std::fabs(h.pts[i].z) <= 1e6f)) return false;
-  return mcl_box_ok(h.lo, h.hi);
 }
 
 // One measure over an observation the device can read (k_mcl_match's layout): the host-mapped staging of
@@ -531,7 +511,7 @@ int dddmr_rollout_mcl_set_map(dddmr_rollout_ctx* ctx, const float* map_xyz, size
     return fail(ctx, DDDMR_ERR_CAPACITY, "mcl_set_map: %zu map / %zu ground points, capacity %u / %u", n_map, n_ground, s->cfg.max_map_points,
                 s->cfg.max_ground_points);
   const HostCloud map_h(map_xyz, n_map, map_stride_bytes), ground_h(ground_xyz, n_ground, ground_stride_bytes);
-  if (!mcl_cloud_ok(map_h, n_map) || !mcl_cloud_ok(ground_h, n_ground))
+  if (!cloud_coords_ok(map_h) || !cloud_coords_ok(ground_h))
     return fail(ctx, DDDMR_ERR_BAD_ARG, "mcl_set_map: a map or ground coordinate is not finite or beyond 1e6 m, or a cloud is wider than %g m on an axis", (double)kMclMaxExtent);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   MclMap& m = s->maps[s->cur == 0 ? 1 : 0];              // beside the current one

@@ -22,9 +22,11 @@
 #include <limits.h>
 #include <stdint.h>
 
-#include "mcl_measure.hip.h"
+#include "mcl_measure.hip.h"       // MclState, mcl_run: the prepared observation is measured there
 #include "mcl_normal.hip.h"
 #include "mcl_observation_plan.hip.h"
+#include "point_grid_plan.hip.h"   // cloud_arg_ok
+#include "sensor_sources.hip.h"    // sweep_features_of: the features of a sweep source, on the device
 
 #pragma clang fp contract(off)
 
@@ -322,7 +324,7 @@ __global__ __launch_bounds__(256) void k_mclobs_pack(uint32_t n_ls, uint32_t n_l
 
 }  // namespace dddmr
 
-// ---- host (included by rollout_engine.hip after mcl_measure.hip.h) -------------------------------------------------
+// ---- host (included by rollout_engine.hip after the context) ---------------------------------------------------------
 namespace {
 
 struct MclObs {

@@ -23,9 +23,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mcl_measure.hip.h"
+#include "mcl_measure.hip.h"       // MclState, MclMap, mcl_grid: a warm-up is a generation of the measure's
 #include "mcl_normal.hip.h"
 #include "mcl_submap_plan.hip.h"
+#include "point_grid.hip.h"        // PointGrid, GridBuf, the cell walks
+#include "point_grid_plan.hip.h"   // stage_cloud, cloud_arg_ok, cloud_box_ok
 
 #pragma clang fp contract(off)
 
@@ -207,7 +209,7 @@ __global__ void k_submap_finish(const SubmapCounters* __restrict__ cnt, SubmapRe
 
 }  // namespace dddmr
 
-// ---- host (included by rollout_engine.hip after mcl_observation.hip.h) ---------------------------------------------
+// ---- host (included by rollout_engine.hip after the context) ---------------------------------------------------------
 namespace {
 
 struct SubMapKeyframe {
@@ -266,27 +268,6 @@ int submap_state(dddmr_rollout_ctx* ctx, const char* what, bool refuse_pending, 
   return DDDMR_OK;
 }
 
-// One cloud of a keyframe, transformed, checked and boxed: false for a coordinate that is not finite before or after.
-bool submap_stage(const float* xyz, size_t n, size_t stride_bytes, const double* T, std::vector<float4>& out, float lo[3], float hi[3]) {
-  const size_t sf = stride_bytes / sizeof(float);
-  out.resize(n);
-  for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0.f;
-  for (size_t i = 0; i < n; ++i) {
-    const float* p = xyz + i * sf;
-    if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) return false;
-    float v[3] = {p[0], p[1], p[2]};
-    if (T)
-      for (int a = 0; a < 3; ++a) v[a] = submap_transform_row(T, a, p[0], p[1], p[2]);
-    for (int a = 0; a < 3; ++a) {
-      if (!std::isfinite(v[a])) return false;
-      lo[a] = i ? std::min(lo[a], v[a]) : v[a];
-      hi[a] = i ? std::max(hi[a], v[a]) : v[a];
-    }
-    out[i] = make_float4(v[0], v[1], v[2], 0.f);
-  }
-  return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -333,9 +314,13 @@ int dddmr_rollout_submap_add_keyframe(dddmr_rollout_ctx* ctx, const float* corne
     return fail(ctx, DDDMR_ERR_CAPACITY, "%s: keyframe %zu with %zu + %zu points, the store holds %u / %u of %u / %u points and at most %u keyframes", what,
                 m->kf.size(), n[0], n[1], m->used[0], m->used[1], m->cfg.max_store_map_points, m->cfg.max_store_ground_points, m->cfg.max_keyframes);
   SubMapKeyframe k{};
-  std::vector<float4> pts[2];
-  if (!submap_stage(corner_xyz, n[0], corner_stride_bytes, T_map_base, pts[0], k.lo[0], k.hi[0]) ||
-      !submap_stage(ground_xyz, n[1], ground_stride_bytes, T_map_base, pts[1], k.lo[1], k.hi[1]))
+  const auto to_map = [T_map_base](float* v) {               // (null: as it is; nothing reads pts or k after a refusal)
+    const float x = v[0], y = v[1], z = v[2];
+    for (int a = 0; T_map_base && a < 3; ++a) v[a] = submap_transform_row(T_map_base, a, x, y, z);
+  };
+  std::vector<float4> pts[2] = {std::vector<float4>(n[0]), std::vector<float4>(n[1])};
+  if (!stage_cloud(corner_xyz, n[0], corner_stride_bytes, pts[0].data(), k.lo[0], k.hi[0], to_map) ||
+      !stage_cloud(ground_xyz, n[1], ground_stride_bytes, pts[1].data(), k.lo[1], k.hi[1], to_map))
     return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: a coordinate is not finite (before or after the transform)", what);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   for (int c = 0; c < 2; ++c) {              // (beyond used[]: nothing reads there until the keyframe is recorded below)
@@ -401,7 +386,7 @@ int dddmr_rollout_submap_warm_up(dddmr_rollout_ctx* ctx, const int32_t* ids, siz
   if (total[0] > s->cfg.max_map_points || total[1] > s->cfg.max_ground_points)
     return fail(ctx, DDDMR_ERR_CAPACITY, "%s: %zu map / %zu ground points, capacity %u / %u", what, total[0], total[1], s->cfg.max_map_points,
                 s->cfg.max_ground_points);
-  if (!mcl_box_ok(lo[0], hi[0]) || !mcl_box_ok(lo[1], hi[1]))
+  if (!cloud_box_ok(lo[0], hi[0]) || !cloud_box_ok(lo[1], hi[1]))
     return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: a map or ground coordinate is beyond 1e6 m, or a cloud is wider than %g m on an axis", what, (double)kMclMaxExtent);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   // from here on the earlier warm-up is overwritten: it stops being ready, and an error exit waits for what was enqueued

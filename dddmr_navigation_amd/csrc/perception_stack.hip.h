@@ -2,7 +2,7 @@
 // StackedPerception (src/dddmr_perception_3d/src/stacked_perception.cpp:72-90) with each layer on its own sensor's
 // observation, then the stacked minimum dGraph (get_min_dGraphValue, :114-126), the lethal masks (aggregateLethal,
 // :142-155) and the list of ground nodes whose stacked value or mask changed in this pass.  include/dddmr_rollout.h
-// restates the semantics.  Included by rollout_engine.hip after the two layers.
+// restates the semantics.
 //
 // The layers are not copied: the lidar pass is marking_update_on (marking_host.hip.h), the depth pass
 // depth_layer_update_locked (depth_layer.hip.h), the very functions the stand-alone entries call.
@@ -19,6 +19,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "depth_layer.hip.h"    // DepthLayerState, depth_layer_update_locked
+#include "marking_host.hip.h"   // MarkingState, marking_update_on
 
 namespace dddmr {
 

@@ -26,6 +26,18 @@
 #include <string>
 #include <vector>
 
+#include "../../include/dddmr_rollout.h"
+
+// fail() (below, behind the context) and HIPCHK, ahead of the headers: point_grid.hip.h's grid_build reports through them
+namespace { int fail(dddmr_rollout_ctx* ctx, int code, const char* fmt, ...); }
+#define HIPCHK(ctx, expr)                                                                   \
+  do {                                                                                      \
+    hipError_t e_ = (expr);                                                                 \
+    if (e_ != hipSuccess)                                                                   \
+      return fail(ctx, DDDMR_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
+                  __FILE__, __LINE__);                                                      \
+  } while (0)
+
 #include "rollout_kernels.hip.h"
 #include "tick_plan.hip.h"
 #include "perception_kernels.hip.h"
@@ -35,6 +47,7 @@
 #include "lidar_sweep.hip.h"
 #include "lidar_features.hip.h"
 #include "measure_kernels.hip.h"
+#include "point_grid_plan.hip.h"   // cloud_arg_ok
 #include "source_table.hip.h"
 
 using namespace dddmr;
@@ -275,14 +288,6 @@ int fail(dddmr_rollout_ctx* ctx, int code, const char* fmt, ...) {
   }
   return code;
 }
-
-#define HIPCHK(ctx, expr)                                                                   \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return fail(ctx, DDDMR_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                  __FILE__, __LINE__);                                                      \
-  } while (0)
 
 int refuse_pending(dddmr_rollout_ctx* ctx, const char* what) {
   return fail(ctx, DDDMR_ERR_STATE, "%s while a tick_begin is pending", what);

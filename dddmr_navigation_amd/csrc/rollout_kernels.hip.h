@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../include/dddmr_rollout.h"
+#include "exact_float.hip.h"   // fmul, fadd, fsub, l2_simple, dot3
 
 // The reference is an x86-64 build without FMA contraction: every multiply and add below
 // rounds separately, in float and in double (hipcc's default would fuse them).
@@ -236,39 +237,6 @@ __host__ __device__ inline unsigned long long pack_slot_word3(uint32_t w_bits, u
 __host__ __device__ inline uint32_t slot_w_bits(unsigned long long w3) { return (uint32_t)w3; }
 __host__ __device__ inline uint32_t slot_collided(unsigned long long w3) { return (uint32_t)(w3 >> 32) & 0xFFFFu; }
 __host__ __device__ inline uint32_t slot_generated(unsigned long long w3) { return (uint32_t)(w3 >> 48) & 0xFFFFu; }
-
-// ---------------------------------------------------------------------------
-// float helpers that must not be contracted into fma
-// ---------------------------------------------------------------------------
-// (HIP's __fmul_rn / __fadd_rn are plain operators compiled under the translation
-// unit's -ffp-contract=fast, i.e. they still carry the `contract` flag and the
-// backend may fuse them; the pragma below is what actually keeps them apart.)
-__device__ __forceinline__ float fmul(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ float fadd(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-__device__ __forceinline__ float fsub(float a, float b) {
-#pragma clang fp contract(off)
-  return a - b;
-}
-
-// FLANN L2_Simple<float>: result = 0; result += diff*diff per dimension.
-__device__ __forceinline__ float l2_simple(float ax, float ay, float az, float bx, float by, float bz) {
-  float d = fsub(ax, bx);
-  float r = fmul(d, d);
-  d = fsub(ay, by);
-  r = fadd(r, fmul(d, d));
-  d = fsub(az, bz);
-  r = fadd(r, fmul(d, d));
-  return r;
-}
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
-  return fadd(fadd(fmul(ax, bx), fmul(ay, by)), fmul(az, bz));
-}
 
 // Inclusive prefix sum over the 64 lanes of a wave with DPP moves (register-to-register, a few
 // cycles each) instead of LDS-crossbar shuffles: Hillis-Steele inside the 16-lane rows

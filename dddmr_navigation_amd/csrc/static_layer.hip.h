@@ -8,7 +8,7 @@
 //
 // A build goes into the generation that is not current and is swapped in on success, so a refused or failed build leaves
 // the previous graph and dGraph as they were:
-//   grid_build x 2      a grid over the ground and one over the map (marking_host.hip.h), on the state's own scratch
+//   grid_build x 2      a grid over the ground and one over the map (point_grid.hip.h), on the state's own scratch
 //   k_sl_degree         a lane per ground node, in the ground grid's sorted order (a wave's lanes share their cells): the
 //                       size of the node's neighbourhood, in adaptive mode also its radius index k
 //   rocPRIM scan        the degrees into row_start
@@ -24,7 +24,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "marking.hip.h"
+#include "perception_stack.hip.h"  // StackState: publish_to_stack writes a host slot of the stack
+#include "point_grid.hip.h"        // PointGrid and its walks, GridBuf, grid_build; rocPRIM
+#include "point_grid_plan.hip.h"   // grid_shape, stage_cloud, HostCloud, cloud_arg_ok, cloud_box_ok
 #include "static_layer_plan.hip.h"
 
 #pragma clang fp contract(off)
@@ -224,17 +226,6 @@ __global__ __launch_bounds__(256) void k_sl_fill_long(PointGrid g, SlSearch s, c
   }
 }
 
-// The smallest FLANN distance among the points of the cells the ball's box touches, +inf without one.  Whoever is nearer
-// than the ball's radius is among them, so a caller that only asks "below the radius?" has the exact nearest neighbour.
-__device__ __forceinline__ float sl_nearest(const PointGrid& g, float qx, float qy, float qz, float r_box) {
-  float best = __int_as_float(0x7F800000);
-  grid_for_each(g, qx, qy, qz, r_box, [&](const float4 p) {
-    best = fminf(best, l2_simple(p.x, p.y, p.z, qx, qy, qz));
-    return false;
-  });
-  return best;
-}
-
 struct SlDgraphArgs {
   double max_obstacle_distance, inscribed_radius;
   float r_imp_box, r_imp2;     // static_imposing_radius: float(r) + kSlPad, float(r * r)
@@ -278,7 +269,7 @@ __global__ __launch_bounds__(256) void k_sl_dgraph(PointGrid ground, PointGrid m
       }
     }
     if (a.static_graph && map.n) {
-      const float best = sl_nearest(map, q.x, q.y, q.z, a.r_ins_box);
+      const float best = grid_nearest(map, q.x, q.y, q.z, a.r_ins_box);
       if (best < __int_as_float(0x7F800000)) {
         const double d = (double)sqrtf(best);                      // :278  double distance_to_obstacle = sqrt(float)
         if (d < a.inscribed_radius) {
@@ -307,7 +298,7 @@ __global__ __launch_bounds__(256) void k_sl_zone(const float4* __restrict__ pts,
     double v = max_obstacle_distance;
     if (zones.n) {
       const float4 q = pts[i];
-      const float best = sl_nearest(zones, q.x, q.y, q.z, r_box);
+      const float best = grid_nearest(zones, q.x, q.y, q.z, r_box);
       if (best < r2) {
         const double d = (double)sqrtf(best);                      // no_entry_layer.cpp:277
         inside = true;
@@ -331,7 +322,7 @@ __global__ void k_sl_finish(const SlCounters* __restrict__ cnt, SlResult* __rest
 
 }  // namespace dddmr
 
-// ---- host (included by rollout_engine.hip after perception_stack.hip.h and mcl_measure.hip.h) ------------------------
+// ---- host (included by rollout_engine.hip after the context) ---------------------------------------------------------
 namespace {
 
 constexpr uint32_t kSlCells = 1u << 21;      // cells of each grid (grid_shape coarsens the cell until the cloud's box fits)
@@ -419,22 +410,6 @@ int static_layer_state(dddmr_rollout_ctx* ctx, const char* what, StaticLayerStat
   return DDDMR_OK;
 }
 
-// n records into pinned float4 staging with their box: false for a coordinate that is not finite
-bool static_layer_stage(const float* xyz, size_t n, size_t stride_bytes, float4* out, float lo[3], float hi[3]) {
-  const size_t sf = stride_bytes / sizeof(float);
-  for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0.f;
-  for (size_t i = 0; i < n; ++i) {
-    const float* p = xyz + i * sf;
-    for (int a = 0; a < 3; ++a) {
-      if (!std::isfinite(p[a])) return false;
-      lo[a] = i ? std::min(lo[a], p[a]) : p[a];
-      hi[a] = i ? std::max(hi[a], p[a]) : p[a];
-    }
-    out[i] = make_float4(p[0], p[1], p[2], 0.f);
-  }
-  return true;
-}
-
 bool static_layer_radius_ok(double r) { return std::isfinite(r) && r >= 0.0 && r <= kSlMaxRadius; }
 
 }  // namespace
@@ -476,13 +451,13 @@ int dddmr_rollout_static_layer_build(dddmr_rollout_ctx* ctx, const float* ground
   const dddmr_static_layer_config& c = m->cfg;
   if (n_ground > c.max_ground_points || n_map > c.max_map_points)
     return fail(ctx, DDDMR_ERR_CAPACITY, "%s: %zu ground / %zu map points, capacity %u / %u", what, n_ground, n_map, c.max_ground_points, c.max_map_points);
-  // (the stream is idle: every call of this layer ends with its wait, so the staging buffers are free)
+  // (the stream is idle: every call of this layer ends with its wait, so the staging buffers are free to be written)
   float lo[2][3], hi[2][3];
-  if (!static_layer_stage(ground_xyz, n_ground, ground_stride_bytes, m->stage_ground, lo[0], hi[0]) ||
-      !static_layer_stage(map_xyz, n_map, map_stride_bytes, m->stage_map, lo[1], hi[1]))
+  if (!stage_cloud(ground_xyz, n_ground, ground_stride_bytes, m->stage_ground, lo[0], hi[0]) ||
+      !stage_cloud(map_xyz, n_map, map_stride_bytes, m->stage_map, lo[1], hi[1]))
     return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: a coordinate is not finite", what);
-  if (!mcl_box_ok(lo[0], hi[0]) || !mcl_box_ok(lo[1], hi[1]))
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: a ground or map coordinate is beyond 1e6 m, or a cloud is wider than %g m on an axis", what, (double)kMclMaxExtent);
+  if (!cloud_box_ok(lo[0], hi[0]) || !cloud_box_ok(lo[1], hi[1]))
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: a ground or map coordinate is beyond 1e6 m, or a cloud is wider than %g m on an axis", what, (double)kCloudMaxExtent);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   SlGeneration& g = m->gen[m->cur == 0 ? 1 : 0];             // the generation nobody is served from
   const uint32_t ng = (uint32_t)n_ground, nm = (uint32_t)n_map;
@@ -616,11 +591,10 @@ int dddmr_rollout_static_layer_set_zones(dddmr_rollout_ctx* ctx, const float* zo
   if (m->cur < 0) return fail(ctx, DDDMR_ERR_STATE, "%s before the first build", what);
   const SlGeneration& g = m->gen[m->cur];
   const uint32_t nz = (uint32_t)n_points;
-  std::vector<float4> pts(std::max<size_t>(n_points, 1));
-  float lo[3], hi[3];
-  if (!static_layer_stage(zone_xyz, n_points, stride_bytes, pts.data(), lo, hi)) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: a coordinate is not finite", what);
-  if (!mcl_box_ok(lo, hi))
-    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: a zone coordinate is beyond 1e6 m, or the zones are wider than %g m on an axis", what, (double)kMclMaxExtent);
+  const HostCloud zones(zone_xyz, n_points, stride_bytes);
+  if (!zones.finite) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: a coordinate is not finite", what);
+  if (!cloud_box_ok(zones.lo, zones.hi))
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: a zone coordinate is beyond 1e6 m, or the zones are wider than %g m on an axis", what, (double)kCloudMaxExtent);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   // the zones' points and grid live for this call (zones change when an operator switches one)
   DevScope scope;
@@ -628,15 +602,15 @@ int dddmr_rollout_static_layer_set_zones(dddmr_rollout_ctx* ctx, const float* zo
   float4* zpts = nullptr;
   uint2* zslot = nullptr;
   const float cell = sl_zone_cell(inflation_distance);
-  grid_shape(zg.g, lo, hi, cell, cell, kSlCells);
+  grid_shape(zg.g, zones.lo, zones.hi, cell, cell, kSlCells);
   if (grid_alloc(scope.mem, zg, (uint32_t)((size_t)zg.g.nx * zg.g.ny * zg.g.nz), nz) != 0) return fail(ctx, DDDMR_ERR_HIP, "%s: grid storage", what);
-  HIPCHK(ctx, dev_alloc(scope.mem, &zpts, pts.size()));
-  HIPCHK(ctx, dev_alloc(scope.mem, &zslot, pts.size()));
+  HIPCHK(ctx, dev_alloc(scope.mem, &zpts, zones.pts.size()));
+  HIPCHK(ctx, dev_alloc(scope.mem, &zslot, zones.pts.size()));
   hipStream_t st = ctx->stream;
   Drain drain{st};                                           // behind `scope`: an error exit waits before the scratch is freed
   uint32_t launches = 0, waits = 0;
   HIPCHK(ctx, hipMemsetAsync(m->counters, 0, sizeof(SlCounters), st));
-  HIPCHK(ctx, hipMemcpyAsync(zpts, pts.data(), pts.size() * sizeof(float4), hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(zpts, zones.pts.data(), zones.pts.size() * sizeof(float4), hipMemcpyHostToDevice, st));
   if (const int rc = grid_build(ctx, m->temp, m->temp_bytes, zg, zpts, nz, zslot, st)) return rc;
   launches += 2 + (nz ? 4 : 1);
   hipLaunchKernelGGL(k_sl_zone, dim3((g.n_ground + 255) / 256), dim3(256), 0, st, g.ground_pts, g.n_ground, zg.g, (float)inflation_distance + kSlPad,

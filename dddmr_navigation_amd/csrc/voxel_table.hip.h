@@ -271,27 +271,6 @@ inline void pack_xyz_records(float* dst, const float* src, size_t n, size_t stri
   }
 }
 
-// n records narrowed to float4 (w = 0; one zero element without a point) with their box (zeros without a point)
-struct HostCloud {
-  std::vector<float4> pts;
-  float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-  HostCloud(const float* xyz, size_t n, size_t stride_bytes) : pts(std::max<size_t>(n, 1), make_float4(0.f, 0.f, 0.f, 0.f)) {
-    const size_t sf = stride_bytes / sizeof(float);
-    for (size_t i = 0; i < n; ++i) {
-      const float* p = xyz + i * sf;
-      pts[i] = make_float4(p[0], p[1], p[2], 0.f);
-      for (int a = 0; a < 3; ++a) {
-        lo[a] = i ? std::min(lo[a], p[a]) : p[a];
-        hi[a] = i ? std::max(hi[a], p[a]) : p[a];
-      }
-    }
-  }
-};
-// a caller's cloud argument: n records of at least x y z, float-aligned
-inline bool cloud_arg_ok(const float* xyz, size_t n, size_t stride_bytes) {
-  return !n || (xyz && stride_bytes >= 12 && stride_bytes % 4 == 0);
-}
-
 // Stages the caller's records for a kernel: 12- and 16-byte records go as they are, wider ones (PCL: 32 bytes) are
 // narrowed to 12 bytes on the way.  Returns the staged records' stride in floats.
 inline int stage_xyz_records(float* dst, const float* src, size_t n, size_t stride_bytes) {
