@@ -28,10 +28,17 @@ def _lattice_clouds(n=40):
     return g, m
 
 
-def _disc(ground, centre, radius):
-    """a stack-style layer: the distance to a disc of obstacle, 0 inside it (node n keeps the start value)"""
+RING = ((9.0, 3.0), 0.8)         # the floor's ring of obstacle: centre and radius
+
+
+def _disc(ground, centre, radius, ring=None):
+    """a stack-style layer: the distance to a disc of obstacle, 0 inside it (node n keeps the start value).  ring: also a
+    thin circle of obstacle; what lies within 0.5 m of it is lethal, so the few nodes around its centre are a component of
+    their own (the pocket)"""
     g = np.asarray(ground, D)
     d = np.maximum(np.hypot(g[:, 0] - centre[0], g[:, 1] - centre[1]) - radius, 0.0)
+    if ring is not None:
+        d = np.minimum(d, np.abs(np.hypot(g[:, 0] - ring[0][0], g[:, 1] - ring[0][1]) - ring[1]))
     return np.concatenate([d, [STACK_START]])
 
 
@@ -49,7 +56,7 @@ def case(name: str) -> dict:
     c["name"] = name
     c["shift"] = shift
     ref = static_ref(name)
-    c["disc"] = _disc(c["ground"].astype(D) - shift, centre, 0.6)
+    c["disc"] = _disc(c["ground"].astype(D) - shift, centre, 0.6, RING if name.startswith("floor") else None)
     # (long_row's random map leaves hardly a node clear of obstacles: there the disc is the only layer)
     c["dgraph"] = np.minimum(np.minimum(ref["dgraph"], c["disc"]), STACK_START) if name != "long_row" else np.minimum(c["disc"], STACK_START)
     c["weights"] = np.random.default_rng(9).uniform(0.0, 0.3, len(c["ground"])).astype(F)
@@ -100,6 +107,9 @@ def queries() -> tuple:
     q.append(("goal_in_disc", fl, hole[0], in_disc, 0.1, False))
     q.append(("start_in_disc", fl, at_rim, corner[0], 0.1, True))
     q.append(("back_across", fl, corner[1], hole[0], 0.1, False))
+    # no-path queries on which the reference is defined: its loop ends at :213 on a set that a pop of an open node left empty
+    q.append(("start_lone", fl, lone, corner[0], 0.1, False))                  # one pop, no successor but the node itself
+    q.append(("start_in_pocket", fl, node_at(fl, *RING[0]), corner[0], 0.1, False))  # the ring's inside, exhausted without an update
     sh = "floor_shifted"
     q.append(("shifted_corner", sh, node_at(sh, 1.0, 1.0), node_at(sh, 11.0, 13.0), 0.1, False))
     q.append(("shifted_hole", sh, node_at(sh, 2.6, 9.25), node_at(sh, 5.4, 9.6), 0.1, True))
@@ -136,7 +146,7 @@ def reference(label: str) -> dict:
 def check_cases() -> dict:
     """what the cases must hold (else the GPU tests prove less than they claim) -> the counts found"""
     found = dict(tie_pops=0, updates=0, discarded=0, radius_skipped=0, radius_equal_kept=0, theta_above_cap=0, theta_below_cap=0, rows_over_256=0,
-                 found=0, no_path=0)
+                 found=0, no_path=0, no_path_defined=0, no_path_on_emptied_set=0)
     for q in queries():
         r = reference(q[0])
         for k in ("tie_pops", "updates", "radius_skipped", "radius_equal_kept", "theta_above_cap", "theta_below_cap", "rows_over_256"):
@@ -144,6 +154,8 @@ def check_cases() -> dict:
         found["discarded"] += r["n_discarded_closed"]
         found["found"] += r["status"] == G.FOUND
         found["no_path"] += r["status"] == G.NO_PATH
+        found["no_path_defined"] += r["status"] == G.NO_PATH and not r["ended_on_emptied_set"]
+        found["no_path_on_emptied_set"] += r["status"] == G.NO_PATH and r["ended_on_emptied_set"]
     for k, v in found.items():
         assert v > 0, (k, found)
     return found

@@ -1,5 +1,6 @@
 """CPU tests of the pre-graph global planner's restatement, cases and pure arithmetic: the conditions the GPU tests
-(tests/test_global_plan_gpu.py) rest on.  The restatement (tests/helpers/global_plan_ref.py) is UNPINNED, see there."""
+(tests/test_global_plan_gpu.py) rest on.  The restatement (tests/helpers/global_plan_ref.py) is pinned to the reference's
+own compiled planner by tests/test_global_plan_pin_cpu.py, see there."""
 import ctypes as C
 import os
 import shutil
@@ -38,9 +39,17 @@ def test_cases_hold_what_the_gpu_tests_rely_on():
     print(found)
     labels = [q[0] for q in Cs.queries()]
     assert len(set(labels)) == len(labels)
-    want = {"same": G.FOUND, "goal_lone": G.NO_PATH, "goal_in_disc": G.NO_PATH, "start_in_disc": G.FOUND, "hole": G.FOUND, "ramp": G.FOUND}
+    want = {"same": G.FOUND, "goal_lone": G.NO_PATH, "goal_in_disc": G.NO_PATH, "start_in_disc": G.FOUND, "hole": G.FOUND, "ramp": G.FOUND,
+            "start_lone": G.NO_PATH, "start_in_pocket": G.NO_PATH}
     for k, v in want.items():
         assert Cs.reference(k)["status"] == v, k
+    # the two older no-path queries end on a set emptied by discards, where the reference has no defined answer; the two
+    # newer ones end on a set that a pop of an open node left empty (a_star_on_pre_graph.cpp:213), where it has
+    assert found["no_path_defined"] == 2 and found["no_path_on_emptied_set"] == 2
+    assert Cs.reference("goal_lone")["ended_on_emptied_set"] and Cs.reference("goal_in_disc")["ended_on_emptied_set"]
+    lone, pocket = Cs.reference("start_lone"), Cs.reference("start_in_pocket")
+    assert (lone["n_expanded"], lone["n_pushed"], lone["n_discarded_closed"], lone["set_size"]) == (1, 1, 0, 0)
+    assert 1 < pocket["n_expanded"] < 10 and pocket["stats"]["updates"] == 0 and pocket["n_discarded_closed"] == 0 and pocket["set_size"] == 0
     same = Cs.reference("same")
     assert len(same["path"]) == 1 and same["n_expanded"] == 1                      # start == goal: one node after one expansion
     # the start inside the disc is lethal itself; the goal inside it is never entered

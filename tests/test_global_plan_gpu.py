@@ -1,5 +1,6 @@
 """GPU tests of the pre-graph global planner on the device graph (dddmr_rollout_global_plan_*): status, path, counters and
-the goal's g bit for bit against tests/helpers/global_plan_ref.py (UNPINNED, see there), the nearest-node search and the
+the goal's g bit for bit against tests/helpers/global_plan_ref.py (pinned to the reference's own compiled planner by
+tests/test_global_plan_pin_cpu.py; tests/test_global_plan_pin_gpu.py holds the device to its answers), the nearest-node search and the
 goal probe against brute force in NumPy float32, batches, limits and refusals.  tests/test_global_plan_cpu.py holds the
 conditions on the cases that these tests rely on."""
 import os

@@ -443,7 +443,7 @@ def _ref_files():
     import glob
     import os
     files = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "REF_*.npz")))
-    return [f for f in files if not os.path.basename(f).startswith("REF_MCL_")]      # (the particle-measure pin's, a format of their own)
+    return [f for f in files if not os.path.basename(f).startswith(("REF_MCL_", "REF_GP_"))]      # (the particle-measure and planner pins', formats of their own)
 
 
 def test_oracle_reproduces_recorded_reference():

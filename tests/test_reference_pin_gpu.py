@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 TOL = 1e-4
 FILES = sorted(f for f in glob.glob(os.path.join(GOLD, "REF_*.npz"))
-               if not os.path.basename(f).startswith("REF_MCL_"))      # (the particle-measure pin's, a format of their own)
+               if not os.path.basename(f).startswith(("REF_MCL_", "REF_GP_")))      # (the particle-measure and planner pins', formats of their own)
 
 _spec = importlib.util.spec_from_file_location("make_ref_golden", os.path.join(GOLD, "make_ref_golden.py"))
 _mk = importlib.util.module_from_spec(_spec)
