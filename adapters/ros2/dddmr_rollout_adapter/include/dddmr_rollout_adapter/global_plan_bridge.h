@@ -5,6 +5,8 @@
 //                                                                   -> makePlanIds(start_xyz, goal_xyz)
 //   DWA_GlobalPlanner::determineDWAPlan's look-ahead loop          (dynamic_window_aware_global_planner.cpp:209-273)
 //                                                                   -> dwaGoalPivot(path, from, look_ahead), one probe call
+//   GlobalPlanner::getStartGoalID + A_Star_on_Graph::getPath      (a_star_on_pc.cpp:200-329, use_pre_graph: false, the default)
+//                                                                   -> planOnCloud(start, goal), setLethalCloud(host layers' lethal cloud)
 //   GlobalPlanner::getROSPath                                      (global_planner.cpp:313-391)
 //                                                                   -> pathPoses(ids, ground): rows x y z qx qy qz qw
 //
@@ -16,6 +18,7 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 #include <vector>
 
 #include "dddmr_rollout.h"
@@ -72,6 +75,53 @@ public:
     if (result) {*result = r;}
     if (rc != DDDMR_OK) {return rc;}
     ids.assign(path.begin() + r.path_offset, path.begin() + r.path_offset + r.path_len);
+    return DDDMR_OK;
+  }
+
+  // ---- use_pre_graph: false (global_planner.cpp:100, the default): A_Star_on_Graph::getPath, a_star_on_pc.cpp:200-329 ----
+  // sGraph_ptr_->getNodeWeight of every ground node (a_star_on_pc.cpp:287), after every regeneration of the static layer
+  template<class Weights>
+  int setGraphNodeWeights(const Weights & w)
+  {
+    if (!ctx_) {return DDDMR_ERR_STATE;}
+    return dddmr_rollout_global_plan_set_graph_node_weights(ctx_, w.empty() ? nullptr : w.data(), w.size());
+  }
+
+  // The lethal clouds of the plugins that stay on the host (the no-entry layer, a host-side plugin), appended as
+  // aggregateLethal appends them (stacked_perception.cpp:142-155); the device layers' lethal nodes are read where they are.
+  // lethal: anything with .points of records that begin with float x, y, z (a pcl::PointCloud); an empty one clears.
+  template<class Cloud>
+  int setLethalCloud(const Cloud & lethal)
+  {
+    if (!ctx_) {return DDDMR_ERR_STATE;}
+    if (lethal.points.empty()) {return dddmr_rollout_global_plan_set_lethal_points(ctx_, nullptr, 0, 12);}
+    typedef typename std::remove_reference<decltype(lethal.points[0])>::type PointT;
+    static_assert(sizeof(PointT) >= 12 && sizeof(PointT) % 4 == 0, "records of floats, x y z first");
+    return dddmr_rollout_global_plan_set_lethal_points(ctx_, &lethal.points[0].x, lethal.points.size(), sizeof(PointT));
+  }
+
+  // getStartGoalID, then A_Star_on_Graph::getPath: makePlanIds with the default search.  PointT: anything with .x .y .z.
+  template<class PointT>
+  int planOnCloud(const PointT & start, const PointT & goal, std::vector<uint32_t> & ids, dddmr_global_plan_cloud_result * result = nullptr,
+                  uint32_t * start_id = nullptr, uint32_t * goal_id = nullptr)
+  {
+    ids.clear();
+    if (!ctx_) {return DDDMR_ERR_STATE;}
+    const float xyz[6] = {(float)start.x, (float)start.y, (float)start.z, (float)goal.x, (float)goal.y, (float)goal.z};
+    uint32_t ends[2] = {UINT32_MAX, UINT32_MAX};
+    int rc = dddmr_rollout_global_plan_nearest(ctx_, xyz, 2, ends);
+    if (start_id) {*start_id = ends[0];}
+    if (goal_id) {*goal_id = ends[1];}
+    dddmr_global_plan_cloud_result r = dddmr_global_plan_cloud_result();
+    r.plan.status = DDDMR_GLOBAL_PLAN_NO_PATH;
+    if (result) {*result = r;}
+    if (rc != DDDMR_OK) {return rc;}
+    if (ends[0] == UINT32_MAX || ends[1] == UINT32_MAX) {return DDDMR_OK;}       // global_planner.cpp:408, :452
+    std::vector<uint32_t> path(max_nodes_ ? max_nodes_ : 1);
+    rc = dddmr_rollout_global_plan_plan_on_cloud(ctx_, &ends[0], &ends[1], 1, path.data(), path.size(), &r);
+    if (result) {*result = r;}
+    if (rc != DDDMR_OK) {return rc;}
+    ids.assign(path.begin() + r.plan.path_offset, path.begin() + r.plan.path_offset + r.plan.path_len);
     return DDDMR_OK;
   }
 

@@ -366,9 +366,19 @@ class GlobalPlanResult(C.Structure):
     ]
 
 
+class GlobalPlanCloudResult(C.Structure):
+    """dddmr_global_plan_cloud_result (56 bytes; pinned by global_plan_cloud.hip.h and tests/test_global_plan_cloud_cpu.py)"""
+    _fields_ = [
+        ("plan", GlobalPlanResult), ("n_knn_fallbacks", C.c_uint32), ("n_lethal_skipped", C.c_uint32), ("n_los_tested", C.c_uint32),
+        ("n_los_blocked", C.c_uint32), ("n_los_capped", C.c_uint32), ("max_successors", C.c_uint32),
+    ]
+
+
 GLOBAL_PLAN_MAX_QUERIES = 16
 GLOBAL_PLAN_FOUND, GLOBAL_PLAN_NO_PATH, GLOBAL_PLAN_BUDGET, GLOBAL_PLAN_OPEN_FULL = 0, 1, 2, 3
 GLOBAL_PLAN_NONE = 0xFFFFFFFF             # global_plan_nearest: no ground node inside the radius
+GLOBAL_PLAN_ROW_FULL = 4                  # global_plan_plan_on_cloud: a radius search found more than ..._CLOUD_MAX_SUCCESSORS
+GLOBAL_PLAN_CLOUD_MAX_SUCCESSORS, GLOBAL_PLAN_LOS_MAX_SAMPLES = 1024, 4096
 
 MCL_BRANCH_CLUSTERS, MCL_BRANCH_X_DOMINANT, MCL_BRANCH_Y_DOMINANT = 0, 1, 2
 
@@ -513,6 +523,9 @@ _TABLE = {
     "global_plan_nearest": (_int, [_ctx, _vp, _sz, _vp]),
     "global_plan_probe": (_int, [_ctx, _vp, _sz, _vp, _vp]),
     "global_plan_plan": (_int, [_ctx, _vp, _vp, _sz, _vp, _sz, _P(GlobalPlanResult)]),
+    "global_plan_set_graph_node_weights": _fixed,
+    "global_plan_set_lethal_points": (_int, [_ctx] + _cloud),
+    "global_plan_plan_on_cloud": (_int, [_ctx, _vp, _vp, _sz, _vp, _sz, _P(GlobalPlanCloudResult)]),
     "stream_ceiling": (_int, [_ctx, _sz, _i32, _pd, _pd]),
     "selftest_sincos": (_int, [_ctx, _vp, _sz, _vp, _vp]),
     "last_error": (_str, [_ctx]),

@@ -65,6 +65,7 @@ struct StackState;                         // the perception stack over the two 
 struct MclState;                           // the particle filter's lidar likelihood, mcl_measure.hip.h
 struct StaticLayerState;                   // the static and no-entry layers' sGraph and dGraphs, static_layer.hip.h
 struct GlobalPlanState;                    // the pre-graph global planner's A* over them, global_plan.hip.h
+struct GpCloudState;                       // what the default A* on the ground cloud keeps beside it, global_plan_cloud.hip.h
 template <class T>
 using ModuleSlot = std::unique_ptr<T, LateDelete<T>>;   // enters its slot once complete (each module's create)
 
@@ -183,6 +184,7 @@ struct dddmr_rollout_ctx {
   ModuleSlot<MclState> mcl;          // dddmr_rollout_mcl_create (tick_mu)
   ModuleSlot<StaticLayerState> slayer; // dddmr_rollout_static_layer_create (tick_mu)
   ModuleSlot<GlobalPlanState> gplan;   // dddmr_rollout_global_plan_create (tick_mu)
+  ModuleSlot<GpCloudState> gcloud;     // the first dddmr_rollout_global_plan_plan_on_cloud / set_lethal_points / set_graph_node_weights (tick_mu)
 
   std::mutex tick_mu;
   std::mutex err_mu;        // last_error is written by tick and sensor threads alike
@@ -397,6 +399,7 @@ void dddmr_rollout_destroy(dddmr_rollout_ctx* ctx) {
   ctx->stack.reset();
   ctx->dlayer.reset();
   ctx->mcl.reset();
+  ctx->gcloud.reset();
   ctx->gplan.reset();
   ctx->slayer.reset();
   if (ctx->comm) (void)rccl().comm_destroy(ctx->comm);
@@ -1196,3 +1199,4 @@ int dddmr_rollout_get_best_cuboids(dddmr_rollout_ctx* ctx, float* vertices_out, 
 #include "mcl_submap.hip.h"
 #include "static_layer.hip.h"
 #include "global_plan.hip.h"
+#include "global_plan_cloud.hip.h"

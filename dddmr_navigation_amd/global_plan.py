@@ -1,7 +1,8 @@
 """Host-side mirror of the pre-graph global planner on top of the C-ABI (dddmr_rollout_global_plan_*):
 A_Star_on_PreGraph::getPath (dddmr_global_planner/src/a_star_on_pre_graph.cpp:191-289) over the static layer's sGraph and a
 dGraph that is already on the device, getStartGoalID's nearest-node search (global_planner.cpp:407, :451) and
-determineDWAPlan's goal test (dynamic_window_aware_global_planner.cpp:248-270).  All compute and all state live in the HIP
+determineDWAPlan's goal test (dynamic_window_aware_global_planner.cpp:248-270); and of the default planner,
+A_Star_on_Graph::getPath with isLineOfSightClear (a_star_on_pc.cpp:168-329), on the ground cloud itself.  All compute and all state live in the HIP
 library; a plan returns node ids of the static layer's ground cloud."""
 from __future__ import annotations
 
@@ -31,6 +32,17 @@ class Plan:
     n_discarded_closed: int
     g_goal: np.float32
     host_waits: int
+
+
+@dataclass
+class CloudPlan(Plan):
+    """A plan of plan_on_cloud: Plan's fields, then what the search met on its way."""
+    n_knn_fallbacks: int        # expansions that took the 8 nearest nodes (fewer than 8 inside the radius)
+    n_lethal_skipped: int       # successors below inscribed_radius
+    n_los_tested: int           # edges of 2 * inscribed_radius or more: marched
+    n_los_blocked: int          # ... and refused by the march
+    n_los_capped: int           # ... of these, by the sample cap
+    max_successors: int         # the longest successor list
 
 
 class GlobalPlan:
@@ -85,6 +97,39 @@ class GlobalPlan:
 
     def plan(self, start: int, goal: int) -> Plan:
         return self.plan_many([start], [goal])[0]
+
+    # ---- the default A* on the ground cloud (A_Star_on_Graph::getPath, a_star_on_pc.cpp:200-329) ----
+    def set_graph_node_weights(self, weights):
+        """sGraph's node weights (static_graph.cpp:62, added at a_star_on_pc.cpp:288), one per ground node (None or empty:
+        all zero).  A second array beside set_node_weights' intensity."""
+        w = np.ascontiguousarray(np.zeros(0) if weights is None else weights, dtype=np.float32).ravel()
+        self._lp._call("global_plan_set_graph_node_weights", M.ptr(w) if w.size else None, w.size)
+
+    def set_lethal_points(self, xyz):
+        """The lethal points of the layers left on the host, [N,3] (None or empty: none); a duplicate is two points."""
+        p, pp = self._points(np.zeros((0, 3)) if xyz is None else xyz)
+        self._lp._call("global_plan_set_lethal_points", pp, len(p), 12)
+
+    def plan_many_on_cloud(self, starts, goals, path_capacity: int = 0) -> list:
+        """plan_many with A_Star_on_Graph::getPath: radius-search successors, line of sight against the lethal cloud -> a
+        CloudPlan per query.  `last_results` keeps the raw results, also when the call raises (OPEN_FULL, ROW_FULL)."""
+        s = np.ascontiguousarray(starts, dtype=np.uint32).ravel()
+        g = np.ascontiguousarray(goals, dtype=np.uint32).ravel()
+        if s.size != g.size or s.size == 0:
+            raise ValueError("as many starts as goals, at least one")
+        cap = int(path_capacity) or s.size * self.max_nodes
+        path = np.zeros(max(cap, 1), np.uint32)
+        res = (K.GlobalPlanCloudResult * s.size)()
+        rc = self._lp._rc("global_plan_plan_on_cloud", M.ptr(s), M.ptr(g), s.size, M.ptr(path), cap, res)
+        self.last_results = list(res)
+        self._lp._check(rc)
+        return [CloudPlan(int(r.plan.status), path[r.plan.path_offset: r.plan.path_offset + r.plan.path_len].copy(), int(r.plan.n_expanded),
+                          int(r.plan.n_pushed), int(r.plan.n_discarded_closed), np.float32(r.plan.g_goal), int(r.plan.host_waits),
+                          int(r.n_knn_fallbacks), int(r.n_lethal_skipped), int(r.n_los_tested), int(r.n_los_blocked), int(r.n_los_capped),
+                          int(r.max_successors)) for r in res]
+
+    def plan_on_cloud(self, start: int, goal: int) -> "CloudPlan":
+        return self.plan_many_on_cloud([start], [goal])[0]
 
     def close(self):
         pass      # the context owns the device state

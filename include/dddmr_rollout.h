@@ -1434,6 +1434,63 @@ int dddmr_rollout_global_plan_probe(dddmr_rollout_ctx* ctx, const float* xyz, si
 int dddmr_rollout_global_plan_plan(dddmr_rollout_ctx* ctx, const uint32_t* start_id, const uint32_t* goal_id, size_t n_queries,
                                    uint32_t* path_out, size_t path_capacity, dddmr_global_plan_result* results);
 
+/* ---- The global planner's default A* on the ground cloud (additions to version 2, no existing struct or entry
+   changes).  global_planner.cpp:100 declares use_pre_graph false, so a robot running the reference as shipped plans with
+   src/dddmr_global_planner/src/a_star_on_pc.cpp's A_Star_on_Graph::getPath (:200-329): the successors of a node are a
+   radius search of the ground (the 8 nearest nodes where fewer than 8 are found), and an edge of 2 * inscribed_radius
+   or more is marched by isLineOfSightClear (:168-198) against the aggregate lethal cloud.  These entries run that search
+   on the planner state of dddmr_rollout_global_plan_create, with its config and budgets, on what is resident: the static
+   layer's ground and grid, the stack's stacked minimum and lethal masks.  No sGraph is needed: a static layer built
+   without generate_static_graph is enough.  DESIGN.md 4d-5 restates the arithmetic; the restatement the device is tested
+   against is not pinned to compiled reference code yet.
+
+   The aggregate lethal cloud (stacked_perception.cpp:142-155) is the plugins' lethal clouds appended.  With
+   dgraph_source 0 the device layers' part is read where it is: a ground node counts once per device layer that holds it
+   lethal (dddmr_rollout_stack_get_lethal_mask's bits).  dddmr_rollout_global_plan_set_lethal_points hands in the lethal
+   points of the layers left on the host (the no-entry layer, a host-side plugin), n records of x y z stride_bytes apart:
+   they replace the ones set before, n == 0 clears them, a duplicate is two points.  DDDMR_ERR_BAD_ARG: a coordinate that
+   is not finite or beyond 1e6 m, a cloud wider than 4096 m; DDDMR_ERR_CAPACITY: more points than the static layer's
+   max_ground_points.  With dgraph_source 1 these points are the whole cloud.  Without any lethal point every edge is
+   clear, as in the reference, whose tree then has no cloud.
+
+   dddmr_rollout_global_plan_set_graph_node_weights uploads sGraph_ptr_->getNodeWeight (static_graph.cpp:62, added at
+   a_star_on_pc.cpp:287-288), a second per-node array beside set_node_weights' intensity, under the same rules: n = the
+   last build's n_ground or 0 for all zero (the default), negative or non-finite weights refused, dropped by a build
+   with another n_ground.  The intensity enters this search as avg_intensity (:248-252), the float sum over the
+   successor list in list order divided by its size.  Both arrays of this section belong to the context: a
+   global_plan_create keeps them unless the static layer's max_ground_points has changed since.
+
+   dddmr_rollout_global_plan_plan_on_cloud is global_plan_plan's twin: n_queries <= max_queries searches in one launch,
+   one workgroup per query, one host wait per call; results[i].plan is filled as global_plan_plan fills it.  The
+   successor list is ascending in distance and, among equal distances, in index (nanoflann orders equals by its tree
+   walk; the order shows only in which nodes make the 8 nearest and in avg_intensity's float sum).  Deliberate
+   differences: a ground of fewer than 8 nodes is DDDMR_ERR_STATE (nearestKSearch leaves entries unfilled there);
+   inscribed_radius <= 0 is DDDMR_ERR_BAD_ARG for this entry (the reference's march does not end), as is a negative
+   a_star_expanding_radius or a radius above 1000 m; an edge whose march would take more than
+   DDDMR_GLOBAL_PLAN_LOS_MAX_SAMPLES samples is blocked and counted in n_los_capped; a radius search that finds more than
+   DDDMR_GLOBAL_PLAN_CLOUD_MAX_SUCCESSORS nodes ends its query with status ROW_FULL and the call with
+   DDDMR_ERR_CAPACITY (results are filled); NO_PATH also where only entries of closed nodes remain, as global_plan_plan.
+   The two searches share the planner's records and stamps and may be called in any order.  Other errors as
+   global_plan_plan's, except that a build without generate_static_graph is accepted.
+
+   All three answer DDDMR_ERR_STATE while a dddmr_rollout_tick_begin is pending. */
+#define DDDMR_GLOBAL_PLAN_ROW_FULL 4
+#define DDDMR_GLOBAL_PLAN_CLOUD_MAX_SUCCESSORS 1024
+#define DDDMR_GLOBAL_PLAN_LOS_MAX_SAMPLES 4096
+typedef struct {
+  dddmr_global_plan_result plan;            /* as global_plan_plan fills it */
+  uint32_t n_knn_fallbacks;                 /* expansions that took the 8 nearest */
+  uint32_t n_lethal_skipped;                /* successors below inscribed_radius */
+  uint32_t n_los_tested, n_los_blocked;     /* edges marched / refused by the march */
+  uint32_t n_los_capped;                    /* of the blocked: by the sample cap */
+  uint32_t max_successors;                  /* longest successor list met */
+} dddmr_global_plan_cloud_result;
+
+int dddmr_rollout_global_plan_set_graph_node_weights(dddmr_rollout_ctx* ctx, const float* weights, size_t n);
+int dddmr_rollout_global_plan_set_lethal_points(dddmr_rollout_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes);
+int dddmr_rollout_global_plan_plan_on_cloud(dddmr_rollout_ctx* ctx, const uint32_t* start_id, const uint32_t* goal_id, size_t n_queries,
+                                            uint32_t* path_out, size_t path_capacity, dddmr_global_plan_cloud_result* results);
+
 /* Measurement aid ("a measured stream-copy ceiling on the same GPU"): streams
    `bytes` (>= 1 GiB recommended: beyond the 256 MB of MALL) `reps` times through a float4 copy
    kernel and a read-only kernel on the context's device; *copy_gbps counts read + write bytes.
