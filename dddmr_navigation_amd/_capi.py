@@ -316,6 +316,32 @@ class MclObservationStats(C.Structure):
     ]
 
 
+class MclFilterConfig(C.Structure):
+    """dddmr_mcl_filter_config: the motion model's time constants and the bias variances (doubles in mcl_3dl's Parameters)."""
+    _fields_ = [
+        ("max_particles", C.c_uint32), ("reserved", C.c_uint32),
+        ("odom_err_integ_lin_tc", C.c_double), ("odom_err_integ_ang_tc", C.c_double),
+        ("bias_var_dist", C.c_double), ("bias_var_ang", C.c_double),
+    ]
+
+
+class MclFilterEstimate(C.Structure):
+    """dddmr_mcl_filter_estimate: what MCL3dlNode::measure reads of the particle set after pf_->measure."""
+    _fields_ = [
+        ("mean_biased", C.c_float * 7), ("mean", C.c_float * 7), ("max_state", C.c_float * 13), ("max_index", C.c_uint32),
+        ("cov", C.c_float * 36), ("sums_biased", C.c_float * 10), ("sums", C.c_float * 10),
+        ("weight_sum", C.c_float), ("bias_sum", C.c_float), ("p_num", C.c_uint32), ("restored", C.c_uint32),
+        ("quality_min", C.c_float), ("quality_max", C.c_float), ("launches", C.c_uint32), ("host_waits", C.c_uint32),
+    ]
+
+
+class MclFilterResampleStats(C.Structure):
+    _fields_ = [
+        ("n_duplicates", C.c_uint32), ("n_at_end", C.c_uint32), ("n_ties", C.c_uint32),
+        ("launches", C.c_uint32), ("host_waits", C.c_uint32), ("reserved", C.c_uint32),
+    ]
+
+
 class SubmapConfig(C.Structure):
     """dddmr_submap_config: the keyframe store's capacities and NormalEstimation's setKSearch."""
     _fields_ = [
@@ -505,6 +531,15 @@ _TABLE = {
     "mcl_prepare_from_sweep": (_int, [_ctx, _i32, _pd, _P(MclObservationStats)]),
     "mcl_get_observation": (_int, [_ctx, _vp, _sz, _pn, _vp, _sz, _pn, _vp, _sz]),
     "mcl_measure_prepared": (_int, [_ctx, _vp, _sz, _vp, _vp, _P(MclStats)]),
+    "mcl_filter_create": (_int, [_ctx, _P(MclFilterConfig)]),
+    "mcl_filter_set_particles": (_int, [_ctx, _vp, _vp, _vp, _sz]),
+    "mcl_filter_get_particles": (_int, [_ctx, _vp, _vp, _vp, _vp, _sz, _pn]),
+    "mcl_filter_predict": (_int, [_ctx, _vp, _vp, _dbl]),
+    "mcl_filter_set_noise": (_int, [_ctx, _vp, _sz]),
+    "mcl_filter_measure": (_int, [_ctx, _vp, _vp, _sz, _vp, _P(MclFilterEstimate), _P(MclStats)]),
+    "mcl_filter_reset_integ": _plain,
+    "mcl_filter_resample": (_int, [_ctx, _dbl, _vp, _sz, _P(MclFilterResampleStats)]),
+    "mcl_filter_add_noise": (_int, [_ctx, _vp, _sz]),
     "submap_create": (_int, [_ctx, _P(SubmapConfig)]),
     "submap_add_keyframe": (_int, [_ctx] + _cloud + _cloud + [_pd, _pd, _vp]),
     "submap_select": (_int, [_ctx, _pd, _dbl, _vp, _sz, _pn]),

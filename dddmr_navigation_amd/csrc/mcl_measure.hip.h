@@ -320,6 +320,7 @@ namespace {
 
 struct MclObs;                             // the prepared observation, mcl_observation.hip.h
 struct SubMapState;                        // the keyframe store and the warm-up generation, mcl_submap.hip.h
+struct FilterState;                        // the resident particle set, mcl_filter.hip.h
 
 struct MclMap {                            // one swapKdTree generation
   GridBuf map, ground;
@@ -349,6 +350,7 @@ struct MclState {
   uint32_t last_n = 0;                     // particles of the last successful measure (get_terms)
   std::unique_ptr<MclObs, LateDelete<MclObs>> obs;   // dddmr_rollout_mcl_set_observation_config
   std::unique_ptr<SubMapState, LateDelete<SubMapState>> submap;   // dddmr_rollout_submap_create
+  std::unique_ptr<FilterState, LateDelete<FilterState>> filter;   // dddmr_rollout_mcl_filter_create
 };
 static_assert(!std::is_copy_constructible_v<MclState>);
 
@@ -414,6 +416,27 @@ int mcl_upload(dddmr_rollout_ctx* ctx, MclState* s, GridBuf& b, float4* dev, con
   return rc;
 }
 
+// The measure's three kernels over states the device can read ([n][7]: the host-mapped staging below, or the resident
+// particles of mcl_filter.hip.h), enqueued on the context's stream.  Likelihood and quality go to the two pointers given.
+// Returns the sequence number k_mcl_finish stores into the result word.
+uint32_t mcl_launch(dddmr_rollout_ctx* ctx, MclState* s, const float4* obs_dev, size_t n_flat, size_t n_less_sharp, const float* states_dev,
+                    uint32_t N, float* likelihood_dev, float* quality_dev) {
+  MclParams k = s->k;
+  k.n_flat = (uint32_t)n_flat;
+  k.n_ls = (uint32_t)n_less_sharp;
+  k.n_states = N;
+  const MclMap& m = s->maps[s->cur];
+  const uint32_t n_obs = k.n_flat + k.n_ls;
+  const uint32_t seq = next_seq(s->seq);
+  hipStream_t st = ctx->stream;
+  hipLaunchKernelGGL(k_mcl_ground, dim3(N), dim3(64), 0, st, k, m.ground.g, m.map.g, m.normals, states_dev, s->t);
+  const uint32_t blocks = std::min<uint32_t>((N + 3) / 4, 2048u);
+  hipLaunchKernelGGL(k_mcl_match, dim3(blocks), dim3(256), (size_t)n_obs * 32, st, k, m.ground.g, m.map.g, obs_dev, states_dev, s->t,
+                     s->qual_dev, likelihood_dev, quality_dev);
+  hipLaunchKernelGGL(k_mcl_finish, dim3(1), dim3(256), 0, st, k, s->t, s->qual_dev, s->res_dev, seq);
+  return seq;
+}
+
 // One measure over an observation the device can read (k_mcl_match's layout): the host-mapped staging of
 // dddmr_rollout_mcl_measure, or the prepared observation of mcl_observation.hip.h.  tick_mu held.
 int mcl_run(dddmr_rollout_ctx* ctx, const char* what, MclState* s, const float4* obs_dev, size_t n_flat, size_t n_less_sharp, const float* states,
@@ -428,19 +451,9 @@ int mcl_run(dddmr_rollout_ctx* ctx, const char* what, MclState* s, const float4*
   }
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::memcpy(s->states_host, states, n_states * 7 * sizeof(float));
-  MclParams k = s->k;
-  k.n_flat = (uint32_t)n_flat;
-  k.n_ls = (uint32_t)n_less_sharp;
-  k.n_states = (uint32_t)n_states;
-  const MclMap& m = s->maps[s->cur];
-  const uint32_t n_obs = k.n_flat + k.n_ls, N = k.n_states;
-  const uint32_t seq = next_seq(s->seq);
+  const uint32_t N = (uint32_t)n_states;
   hipStream_t st = ctx->stream;
-  hipLaunchKernelGGL(k_mcl_ground, dim3(N), dim3(64), 0, st, k, m.ground.g, m.map.g, m.normals, s->states_dev, s->t);
-  const uint32_t blocks = std::min<uint32_t>((N + 3) / 4, 2048u);
-  hipLaunchKernelGGL(k_mcl_match, dim3(blocks), dim3(256), (size_t)n_obs * 32, st, k, m.ground.g, m.map.g, obs_dev, s->states_dev, s->t,
-                     s->qual_dev, s->out_dev, s->out_dev + s->cfg.max_particles);
-  hipLaunchKernelGGL(k_mcl_finish, dim3(1), dim3(256), 0, st, k, s->t, s->qual_dev, s->res_dev, seq);
+  const uint32_t seq = mcl_launch(ctx, s, obs_dev, n_flat, n_less_sharp, s->states_dev, N, s->out_dev, s->out_dev + s->cfg.max_particles);
   uint32_t waits = 0;                                  // the spin on the result word, and the stream's when the spin ran out
   if (const int rc = feed_wait(st, &s->res_host->seq, seq, &waits)) return fail(ctx, DDDMR_ERR_HIP, "%s: launch or wait failed (%d)", what, rc);
   const MclResult r = *s->res_host;

@@ -1197,6 +1197,7 @@ int dddmr_rollout_get_best_cuboids(dddmr_rollout_ctx* ctx, float* vertices_out, 
 #include "mcl_measure.hip.h"
 #include "mcl_observation.hip.h"
 #include "mcl_submap.hip.h"
+#include "mcl_filter.hip.h"
 #include "static_layer.hip.h"
 #include "global_plan.hip.h"
 #include "global_plan_cloud.hip.h"

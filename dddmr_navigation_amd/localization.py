@@ -2,7 +2,9 @@
 mcl_3dl's LidarMeasurementModelLikelihood::measure for a batch of particles
 (dddmr_mcl_3dl/src/lidar_measurement_model_likelihood.cpp:86-252, src/mcl_3dl.cpp:466-503) and the preparation of its
 observation, MCL3dlNode::cbLeGoFeatureCloud (src/mcl_3dl.cpp:263-464).
-All compute and all state live in the HIP library; the filter itself (prediction, bias, resampling) stays on the host."""
+All compute and all state live in the HIP library.  ParticleFilter keeps the particle set itself in device memory
+(dddmr_rollout_mcl_filter_*): prediction, weighting, bias, estimate and resampling run there, on random numbers the
+caller draws."""
 from __future__ import annotations
 
 import ctypes as C
@@ -25,6 +27,12 @@ def shipped_observation_config(**kw) -> K.MclObservationConfig:
     """cbLeGoFeatureCloud's parameters as p2p_move_base_localization.yaml ships them, with room for a 16-ring sweep's lists."""
     return M.struct_from(K.MclObservationConfig, dict(
         euc_cluster_distance=0.8, euc_cluster_min_size=3, max_flat_points=400, max_less_sharp_points=1600), kw)
+
+
+def shipped_filter_config(**kw) -> K.MclFilterConfig:
+    """The filter block of the shipped mcl_3dl.yaml, with room for the particle counts this project measures at."""
+    return M.struct_from(K.MclFilterConfig, dict(
+        max_particles=1 << 14, odom_err_integ_lin_tc=5.0, odom_err_integ_ang_tc=10.0, bias_var_dist=2.0, bias_var_ang=1.57), kw)
 
 
 class ParticleMeasure:
@@ -120,3 +128,86 @@ class ParticleMeasure:
 
     def close(self):
         pass      # the context owns the device state
+
+
+def _f32(a, shape, name):
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.shape != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {a.shape}")
+    return a
+
+
+class ParticleFilter:
+    """mcl_3dl's particle set in device memory, beside a ParticleMeasure of the same context (its mcl_create comes first).
+    States are [N,13] float32 in State6DOF::operator[] order (pos xyz, rot xyzw, odom_err_integ_lin_ xyz,
+    odom_err_integ_ang_ xyz); noise4 rows are noise_ll_, noise_la_, noise_al_, noise_aa_; resample / add_noise rows are
+    [*,10]: pos xyz, rot xyzw, odom_err_integ_ang_ xyz of the noise state.  Every random number is the caller's."""
+
+    def __init__(self, lp, cfg: K.MclFilterConfig):
+        self._lp = lp
+        self.cfg = cfg
+        lp._call("mcl_filter_create", C.byref(cfg))
+        self.n = 0
+        self.last = None             # the last measure's MclStats (the lidar model's, when it ran)
+        self.last_resample = None
+
+    def set_particles(self, states, probability=None, noise4=None):
+        """probability None: float(1.0 / N) as pf::init computes it; noise4 None: zeros."""
+        states = np.ascontiguousarray(states, dtype=np.float32)
+        if states.ndim != 2 or states.shape[1] != 13:
+            raise ValueError("states: [N,13]")
+        n = states.shape[0]
+        p = None if probability is None else _f32(probability, (n,), "probability")
+        z = None if noise4 is None else _f32(noise4, (n, 4), "noise4")
+        self._lp._call("mcl_filter_set_particles", M.ptr(states), None if p is None else M.ptr(p), None if z is None else M.ptr(z), n)
+        self.n = n
+
+    def particles(self) -> dict:
+        """-> dict(states [N,13], probability [N], bias [N], noise4 [N,4]) as they lie on the device."""
+        n = C.c_size_t(0)
+        self._lp._call("mcl_filter_get_particles", None, None, None, None, 0, C.byref(n))
+        N = n.value
+        out = dict(states=np.zeros((N, 13), np.float32), probability=np.zeros(N, np.float32), bias=np.zeros(N, np.float32),
+                   noise4=np.zeros((N, 4), np.float32))
+        self._lp._call("mcl_filter_get_particles", M.ptr(out["states"]), M.ptr(out["probability"]), M.ptr(out["bias"]), M.ptr(out["noise4"]),
+                       N, C.byref(n))
+        return out
+
+    def predict(self, odom_prev, odom_cur, time_diff):
+        """setOdoms + predict: the two odometry poses as pos xyz, rot xyzw."""
+        a, b = _f32(odom_prev, (7,), "odom_prev"), _f32(odom_cur, (7,), "odom_cur")
+        self._lp._call("mcl_filter_predict", M.ptr(a), M.ptr(b), float(time_diff))
+
+    def set_noise(self, noise4):
+        z = _f32(noise4, (self.n, 4), "noise4")
+        self._lp._call("mcl_filter_set_noise", M.ptr(z), self.n)
+
+    def measure(self, likelihood=None, quality=None, state_prev=None) -> K.MclFilterEstimate:
+        """MCL3dlNode::measure up to the covariance.  likelihood None: the lidar model runs on the resident poses and the
+        prepared observation.  state_prev None: the bias is 1.  -> the call's MclFilterEstimate; self.last its MclStats."""
+        lk = None if likelihood is None else _f32(likelihood, (self.n,), "likelihood")
+        q = None if quality is None else _f32(quality, (self.n,), "quality")
+        sp = None if state_prev is None else _f32(state_prev, (7,), "state_prev")
+        est, st = K.MclFilterEstimate(), K.MclStats()
+        rc = self._lp._rc("mcl_filter_measure", None if lk is None else M.ptr(lk), None if q is None else M.ptr(q), self.n,
+                          None if sp is None else M.ptr(sp), C.byref(est), C.byref(st))
+        self.last = st
+        self._lp._check(rc)
+        return est
+
+    def reset_integ(self):
+        self._lp._call("mcl_filter_reset_integ")
+
+    def resample(self, u, noise_rows) -> K.MclFilterResampleStats:
+        """u: the canonical draw in [0, 1); noise_rows [R,10], one per duplicate in index order (R below the number of
+        duplicates is refused with the stats in self.last_resample and nothing changed)."""
+        rows = np.ascontiguousarray(noise_rows, dtype=np.float32).reshape(-1, 10)
+        st = K.MclFilterResampleStats()
+        rc = self._lp._rc("mcl_filter_resample", float(u), M.ptr(rows) if len(rows) else None, len(rows), C.byref(st))
+        self.last_resample = st
+        self._lp._check(rc)
+        return st
+
+    def add_noise(self, noise_rows):
+        rows = _f32(noise_rows, (self.n, 10), "noise_rows")
+        self._lp._call("mcl_filter_add_noise", M.ptr(rows), self.n)

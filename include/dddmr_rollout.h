@@ -1070,9 +1070,9 @@ int dddmr_rollout_stack_reset(dddmr_rollout_ctx* ctx);
 
 /* ---- Particle filter lidar likelihood: mcl_3dl's LidarMeasurementModelLikelihood::measure for a batch of particles ----
    (dddmr_mcl_3dl/src/lidar_measurement_model_likelihood.cpp:86-252, called once per particle by pf_->measure,
-   src/mcl_3dl.cpp:466-503).  The one function of the localiser that is a batch kernel; motion prediction, bias,
-   resampling, weight normalisation and sub-map loading stay on the host; the preparation of the observation
-   (cbLeGoFeatureCloud) is the block after this one.
+   src/mcl_3dl.cpp:466-503).  The localiser's one batch kernel; the preparation of the observation
+   (cbLeGoFeatureCloud) is the block after this one, motion prediction, weight normalisation, bias and resampling on a
+   particle set that stays in device memory are dddmr_rollout_mcl_filter_*, sub-map loading is dddmr_rollout_submap_*.
 
    dddmr_rollout_mcl_create takes the model's parameters (likelihood.match_dist_min / match_dist_flat /
    radius_of_ground_search / threshold_for_trusted_ground) and the capacities.  DDDMR_ERR_BAD_ARG: a distance that is
@@ -1209,6 +1209,107 @@ int dddmr_rollout_mcl_get_observation(dddmr_rollout_ctx* ctx, float* flat_xyz_ou
                                       float* normals_out /* [n_less_sharp_in][3], input order */, size_t normals_capacity);
 int dddmr_rollout_mcl_measure_prepared(dddmr_rollout_ctx* ctx, const float* states /* [n_states][7] */, size_t n_states,
                                        float* likelihood_out, float* quality_out, dddmr_mcl_stats* stats);
+
+/* ---- The localiser's particle set: mcl_3dl's filter step on the device, noise drawn by the caller (additions to ABI
+   version 2; no existing struct or entry changes).  The particles (pose, odom_err_integ_lin_ / _ang_, noise_ll_ / la_ /
+   al_ / aa_, probability_, probability_bias_) stay in device memory between the calls; what goes up per step is the
+   caller's random numbers, what comes down is one dddmr_mcl_filter_estimate.  Line numbers are
+   src/dddmr_mcl_3dl/include/mcl_3dl/pf.h's unless another file is named.  Float where the reference is float, double
+   where it is double, no fused multiply-add; every sum whose order the result shows is taken in index order by one
+   lane.  States are 13 floats in State6DOF::operator[] order (pos xyz, rot xyzw, integ_lin xyz, integ_ang xyz), noise4
+   rows are noise_ll_, noise_la_, noise_al_, noise_aa_.
+
+   dddmr_rollout_mcl_filter_create needs a dddmr_rollout_mcl_create first (DDDMR_ERR_STATE) with at least
+   max_particles (DDDMR_ERR_CAPACITY); a second mcl_create drops the filter.  DDDMR_ERR_BAD_ARG: a time constant or
+   variance that is not finite and positive (also once rounded to float, as the reference stores them), 0 particles.
+
+   _filter_set_particles: probability NULL = float(1.0 / n) as init (:164-176) computes it, noise4 NULL = zeros.
+   Deliberate difference: a negative or non-finite probability and a non-finite state or noise component are
+   DDDMR_ERR_BAD_ARG (resample's map rests on a non-decreasing accum_probability_).  _filter_get_particles is a two-call
+   getter: all outputs NULL reports *n; any output may be NULL; a capacity below the count is DDDMR_ERR_CAPACITY.
+
+   _filter_predict: setOdoms (motion_prediction_model_differential_drive.h:46-54) on the host, predict (:56-67) one lane
+   per particle; the device's transcendentals are sinf / cosf of yaw_diff / 2 (quat.h:216-225).  time_diff is rounded to
+   float.  DDDMR_ERR_BAD_ARG: a non-finite odometry component or time_diff.
+
+   _filter_set_noise: update_noise_func (src/mcl_3dl.cpp:221-229), the values already multiplied by odom_err_*.
+
+   _filter_measure is MCL3dlNode::measure up to the covariance (src/mcl_3dl.cpp:466-601).  likelihood NULL: the three
+   measure kernels run on the resident poses and the prepared observation (quality must be NULL too; the errors of
+   dddmr_rollout_mcl_measure_prepared apply, stats is filled as there).  Otherwise likelihood [n] is taken as given
+   (deliberate difference: a negative or non-finite one is DDDMR_ERR_BAD_ARG) and quality [n] or NULL feeds the
+   minimum / maximum (1 and 0 without).  Then: pf::measure (:247-268; the products' float sum in index order; divided
+   when sum > 0, else the old probabilities stay and `restored` is 1), the bias (src/mcl_3dl.cpp:518-530; 1.0f when
+   state_prev [7] is NULL, the branch for more particles than num_particles_), expectationBiased with
+   ParticleWeightedMeanQuat::add (state_6dof.h:303-315), max() (the first strict maximum), covariance(1.0, 1.0)
+   (:293-348): expectation(1.0) with its break after the first running sum above 1.0f, p_num from the same sum, the
+   elements of rows and columns 0 .. 5 as ((s[k] - e[k]) * (s[j] - e[j])) * p accumulated in float in index order and
+   divided by the float p_sum.  random_sample_ratio < 1, resizeParticle and appendParticle are not built.
+   mean_biased is raw as getMean returns it (the caller normalises its rotation as src/mcl_3dl.cpp:545 does).  The
+   device evaluates acosf / expf for the bias: DESIGN.md 4e has the measured distance to the host's.
+
+   _filter_reset_integ: integ_reset_func (src/mcl_3dl.cpp:570-575).
+
+   _filter_resample is resampleUsingNoiseGenerator (:182-220).  u is the canonical draw in [0, 1) (DDDMR_ERR_BAD_ARG
+   outside), rounded to float: initial_p = u * pstep in float, which is what libstdc++'s
+   uniform_real_distribution<float>(0, pstep) computes from it.  accum is a float prefix in index order; particle i picks
+   the first index with accum >= pstep * i + initial_p; past the end every later particle keeps the last valid pick; a
+   particle whose pick equals the previous particle's (for particle 0: pick 0) is a duplicate, and the k-th duplicate in
+   index order takes noise row k: state = pick's state + noise by State6DOF::operator+ (rot = noise.rot * rot, the
+   integrals add, noise_* become 0 as the operator's default-constructed result has them), then normalize().  A noise
+   row is pos xyz, rot xyzw, odom_err_integ_ang_ xyz of the state generateNoise builds (state_6dof.h:200-221; the linear
+   integral's noise equals pos).  Every probability becomes float(1.0 / n).  Deliberate difference: among EQUAL accum
+   values the lowest index is picked, where the reference's std::sort leaves an order of libstdc++'s making for more
+   than 16 particles (n_ties counts the equal neighbours; 0 means the picks are the reference's).  DDDMR_ERR_CAPACITY
+   with stats filled and nothing changed when rows < n_duplicates.
+
+   _filter_add_noise: pf::noise (:226-232), the same addition for every particle without normalize().
+
+   All entries run on the context's stream and answer DDDMR_ERR_STATE while a dddmr_rollout_tick_begin is pending, before
+   filter_create, and (all but create and set_particles) before the first set_particles.  A refused call changes nothing. */
+typedef struct {
+  uint32_t max_particles;                             /* <= dddmr_mcl_config.max_particles */
+  uint32_t reserved;
+  double odom_err_integ_lin_tc, odom_err_integ_ang_tc; /* mcl_3dl.yaml: 5.0, 10.0 (doubles in Parameters, floats in the model) */
+  double bias_var_dist, bias_var_ang;                 /* mcl_3dl.yaml: 2.0, 1.57 (doubles in Parameters, floats in NormalLikelihood) */
+} dddmr_mcl_filter_config;
+
+typedef struct {
+  float mean_biased[7];        /* expectationBiased(): e_.pos_ / p_sum_, Quat(front_sum_, up_sum_) */
+  float mean[7];               /* expectation(1.0), what covariance() subtracts */
+  float max_state[13];
+  uint32_t max_index;
+  float cov[36];               /* rows and columns 0 .. 5 */
+  float sums_biased[10];       /* p_sum_, e_.pos_, front_sum_, up_sum_ before getMean */
+  float sums[10];
+  float weight_sum;            /* pf::measure's sum */
+  float bias_sum;              /* == sums_biased[0] */
+  uint32_t p_num;
+  uint32_t restored;
+  float quality_min, quality_max;
+  uint32_t launches, host_waits;
+} dddmr_mcl_filter_estimate;
+
+typedef struct {
+  uint32_t n_duplicates, n_at_end, n_ties;
+  uint32_t launches, host_waits;
+  uint32_t reserved;
+} dddmr_mcl_filter_resample_stats;
+
+int dddmr_rollout_mcl_filter_create(dddmr_rollout_ctx* ctx, const dddmr_mcl_filter_config* cfg);
+int dddmr_rollout_mcl_filter_set_particles(dddmr_rollout_ctx* ctx, const float* states /* [n][13] */, const float* probability /* [n] or NULL */,
+                                           const float* noise4 /* [n][4] or NULL */, size_t n);
+int dddmr_rollout_mcl_filter_get_particles(dddmr_rollout_ctx* ctx, float* states_out /* [n][13] */, float* probability_out, float* bias_out,
+                                           float* noise4_out /* [n][4] */, size_t capacity, size_t* n);
+int dddmr_rollout_mcl_filter_predict(dddmr_rollout_ctx* ctx, const float odom_prev[7], const float odom_cur[7], double time_diff);
+int dddmr_rollout_mcl_filter_set_noise(dddmr_rollout_ctx* ctx, const float* noise4 /* [n][4] */, size_t n);
+int dddmr_rollout_mcl_filter_measure(dddmr_rollout_ctx* ctx, const float* likelihood /* [n] or NULL */, const float* quality /* [n] or NULL */,
+                                     size_t n, const float* state_prev /* [7] or NULL */, dddmr_mcl_filter_estimate* estimate,
+                                     dddmr_mcl_stats* stats);
+int dddmr_rollout_mcl_filter_reset_integ(dddmr_rollout_ctx* ctx);
+int dddmr_rollout_mcl_filter_resample(dddmr_rollout_ctx* ctx, double u, const float* noise /* [rows][10] */, size_t rows,
+                                      dddmr_mcl_filter_resample_stats* stats);
+int dddmr_rollout_mcl_filter_add_noise(dddmr_rollout_ctx* ctx, const float* noise /* [n][10] */, size_t n);
 
 /* ---- The localiser's sub-maps: mcl_3dl's SubMaps on the device (additions to ABI version 2; no existing struct or entry
    changes).  src/dddmr_mcl_3dl/src/sub_maps.cpp keeps the pose graph's keyframes, and every

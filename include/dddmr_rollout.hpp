@@ -279,6 +279,39 @@ class LocalPlanner {
     quality.swap(qual);
     return DDDMR_OK;
   }
+  // the localiser's particle set in device memory (mcl_3dl's filter step; every random number is the caller's): states
+  // [n][13] in State6DOF::operator[] order, noise4 [n][4], noise rows [*][10]; the library's codes are returned, not thrown
+  int mclFilterCreate(const dddmr_mcl_filter_config& cfg) { return dddmr_rollout_mcl_filter_create(ctx_, &cfg); }
+  int mclFilterSetParticles(const std::vector<float>& states, const float* probability = nullptr, const float* noise4 = nullptr) {
+    return dddmr_rollout_mcl_filter_set_particles(ctx_, states.data(), probability, noise4, states.size() / 13);
+  }
+  int mclFilterGetParticles(std::vector<float>& states, std::vector<float>& probability, std::vector<float>& bias, std::vector<float>& noise4) {
+    size_t n = 0;
+    int rc = dddmr_rollout_mcl_filter_get_particles(ctx_, nullptr, nullptr, nullptr, nullptr, 0, &n);
+    if (rc != DDDMR_OK) return rc;
+    std::vector<float> s(13 * n), p(n), b(n), z(4 * n);
+    rc = dddmr_rollout_mcl_filter_get_particles(ctx_, s.data(), p.data(), b.data(), z.data(), n, &n);
+    if (rc != DDDMR_OK) return rc;
+    states.swap(s); probability.swap(p); bias.swap(b); noise4.swap(z);
+    return DDDMR_OK;
+  }
+  int mclFilterPredict(const float odom_prev[7], const float odom_cur[7], double time_diff) {
+    return dddmr_rollout_mcl_filter_predict(ctx_, odom_prev, odom_cur, time_diff);
+  }
+  int mclFilterSetNoise(const std::vector<float>& noise4) { return dddmr_rollout_mcl_filter_set_noise(ctx_, noise4.data(), noise4.size() / 4); }
+  // likelihood empty: the lidar model runs on the resident poses and the prepared observation; state_prev NULL: bias 1
+  int mclFilterMeasure(const std::vector<float>& likelihood, const std::vector<float>& quality, const float* state_prev,
+                       dddmr_mcl_filter_estimate& estimate, dddmr_mcl_stats* stats = nullptr) {
+    return dddmr_rollout_mcl_filter_measure(ctx_, likelihood.empty() ? nullptr : likelihood.data(), quality.empty() ? nullptr : quality.data(),
+                                            likelihood.size(), state_prev, &estimate, stats);
+  }
+  int mclFilterResetInteg() { return dddmr_rollout_mcl_filter_reset_integ(ctx_); }
+  int mclFilterResample(double u, const std::vector<float>& noise_rows, dddmr_mcl_filter_resample_stats* stats = nullptr) {
+    return dddmr_rollout_mcl_filter_resample(ctx_, u, noise_rows.data(), noise_rows.size() / 10, stats);
+  }
+  int mclFilterAddNoise(const std::vector<float>& noise_rows) {
+    return dddmr_rollout_mcl_filter_add_noise(ctx_, noise_rows.data(), noise_rows.size() / 10);
+  }
   // the localiser's sub-maps (mcl_3dl's SubMaps): the keyframes in device memory, the radius search over their poses,
   // the warm-up (concatenation, grids, ground normals) and the swap; the library's codes are returned, not thrown
   int submapCreate(const dddmr_submap_config& cfg) { return dddmr_rollout_submap_create(ctx_, &cfg); }
