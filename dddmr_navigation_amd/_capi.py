@@ -563,6 +563,7 @@ _TABLE = {
     "global_plan_plan_on_cloud": (_int, [_ctx, _vp, _vp, _sz, _vp, _sz, _P(GlobalPlanCloudResult)]),
     "stream_ceiling": (_int, [_ctx, _sz, _i32, _pd, _pd]),
     "selftest_sincos": (_int, [_ctx, _vp, _sz, _vp, _vp]),
+    "selftest_wave_ops": (_int, [_ctx, _vp, _vp, _sz, _u32, _vp, _vp]),
     "last_error": (_str, [_ctx]),
     "version": (_str, []),
     "sizeof": (_sz, [_int]),                  # the layout self-check of the CPU tests

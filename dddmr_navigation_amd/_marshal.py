@@ -37,7 +37,7 @@ def transform(T):
 def cloud(a, name: str, min_cols: int = 3, cols: int = 0):
     """[N, >= min_cols] (cols given: [N, cols]) rows -> (float32 C-contiguous array, pointer, N, stride in bytes).
     Anything without an element is the empty cloud: null pointer, count 0, stride 12
-    (every entry point accepts that: cloud_arg_ok() in voxel_table.hip.h returns true at a count of 0)."""
+    (every entry point accepts that: cloud_arg_ok() in point_grid_plan.hip.h returns true at a count of 0)."""
     a = np.ascontiguousarray(a, dtype=np.float32)
     if a.size == 0:
         return a, None, 0, 12

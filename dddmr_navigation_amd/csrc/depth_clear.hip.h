@@ -29,7 +29,9 @@
 
 #include <cmath>
 
-#include "point_grid.hip.h"   // the observation grid and its walks; rocPRIM; Owned, dev_alloc (voxel_table.hip.h)
+#include "dev_memory.hip.h"   // Owned, dev_alloc
+#include "point_grid.hip.h"   // the observation grid and its walks; rocPRIM
+#include "wave_ops.hip.h"     // wave_min, wave_max
 
 #pragma clang fp contract(off)
 
@@ -189,10 +191,8 @@ __global__ __launch_bounds__(256) void k_dc_bounds(const float4* __restrict__ pt
   }
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    for (int off = 32; off > 0; off >>= 1) {
-      lo[a] = min(lo[a], (uint32_t)__shfl_xor((int)lo[a], off, 64));
-      hi[a] = max(hi[a], (uint32_t)__shfl_xor((int)hi[a], off, 64));
-    }
+    lo[a] = wave_min(lo[a]);
+    hi[a] = wave_max(hi[a]);
   }
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll

@@ -32,7 +32,10 @@
 #include <cstring>
 #include <vector>
 
+#include "dev_memory.hip.h"           // Owned, host_mapped_alloc, feed_wait
 #include "perception_kernels.hip.h"
+#include "point_grid_plan.hip.h"      // stage_xyz_records
+#include "wave_ops.hip.h"             // wave_append, last_block
 
 // Nothing may be fused: the reference is an x86-64 build without FMA contraction.
 #pragma clang fp contract(off)

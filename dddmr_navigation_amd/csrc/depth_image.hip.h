@@ -35,6 +35,8 @@
 #include <cstring>
 
 #include "depth_feed.hip.h"
+#include "dev_memory.hip.h"   // Owned, dev_alloc, feed_wait
+#include "wave_ops.hip.h"     // last_block
 
 // Nothing may be fused: the reference is an x86-64 build without FMA contraction.
 #pragma clang fp contract(off)

@@ -36,6 +36,8 @@
 #include <stdint.h>
 
 #include "depth_mark.hip.h"
+#include "dev_memory.hip.h"   // Owned, dev_alloc, Drain
+#include "wave_ops.hip.h"     // wave_append
 
 #pragma clang fp contract(off)
 
@@ -56,18 +58,6 @@ struct DlOut {                // host-mapped: what an update reports
   uint32_t mark_overflow;     // the cluster pipeline's capacity flag (VoxelGrid key range)
   uint32_t n_clusters;        // all clusters, the ones below the minimum size included (rows of the tie arrays)
 };
-
-// Appends one entry per lane with `pred` to a list: one atomic per wave.  Every lane of the wave must call it.
-__device__ __forceinline__ uint32_t dl_wave_append(uint32_t* counter, bool pred, int lane) {
-  const unsigned long long m = __ballot(pred);
-  uint32_t base = 0;
-  if (m) {
-    const int leader = __ffsll((long long)m) - 1;
-    if (lane == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
-    base = (uint32_t)__shfl((int)base, leader, 64);
-  }
-  return base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-}
 
 __global__ void k_dl_begin(MarkCounters* __restrict__ cnt, DlCounters* __restrict__ x) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
@@ -92,7 +82,7 @@ __global__ __launch_bounds__(256) void k_dl_window(MarkParams k, MarkStore s, Dl
       in = !(x < k.wx0 || x >= k.wx1 || y < k.wy0 || y >= k.wy1 || z < k.wz0 || z >= k.wz1);
     }
   }
-  const uint32_t at = dl_wave_append(&cnt->n_in_window, in, threadIdx.x & 63);
+  const uint32_t at = wave_append(in, &cnt->n_in_window);
   if (in) d.clear_list[at] = slot;
 }
 

@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "depth_clear.hip.h"
+#include "dev_memory.hip.h"        // Owned, dev_alloc
 #include "marking.hip.h"           // the cluster kernels of the general route
 #include "marking_host.hip.h"      // ... and its host side: cluster_temp_bytes, the static grids, base_plane
 #include "point_grid_plan.hip.h"   // cloud_arg_ok

@@ -23,17 +23,20 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dev_memory.hip.h"        // Owned, dev_alloc, Drain, feed_wait
 #include "global_plan_plan.hip.h"
 #include "perception_stack.hip.h"  // StackState: the stacked minimum dGraph (dgraph_source 0)
 #include "point_grid.hip.h"        // PointGrid, grid_for_each, grid_nearest_id
 #include "point_grid_plan.hip.h"   // HostCloud
 #include "static_layer.hip.h"      // StaticLayerState: the rows, the ground grid and the layer's own dGraph; kSlPad, sl_radius2
+#include "wave_ops.hip.h"          // wave_min, wave_append
 
 #pragma clang fp contract(off)
 
 namespace dddmr {
 
 constexpr uint32_t kGpThreads = 256;
+static_assert(kGpThreads % 64 == 0, "whole waves: the searches run the wave primitives");
 constexpr float kGpNearestRadius = 0.5f, kGpProbeRadius = 0.25f;       // global_planner.cpp:407, dynamic_window_...cpp:248
 
 struct GpGraph {
@@ -54,15 +57,6 @@ struct GpQueries { uint32_t start[DDDMR_GLOBAL_PLAN_MAX_QUERIES], goal[DDDMR_GLO
 
 // per node and query slot: x = stamp, y = g bits, z = f bits, w = parent
 __device__ __forceinline__ uint4 gp_record(uint32_t stamp, float g, float f, uint32_t parent) { return make_uint4(stamp, __float_as_uint(g), __float_as_uint(f), parent); }
-
-__device__ __forceinline__ unsigned long long gp_wave_min(unsigned long long v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const unsigned long long o = ((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
 
 // rec [queries][rec_stride], keys [queries][max_open], path [queries][path_stride] (host-mapped), res [queries] (host-mapped)
 __global__ __launch_bounds__(kGpThreads) void k_gp_plan(GpGraph G, GpParams P, GpQueries Q, uint4* __restrict__ rec_all, size_t rec_stride,
@@ -101,7 +95,7 @@ __global__ __launch_bounds__(kGpThreads) void k_gp_plan(GpGraph G, GpParams P, G
       const unsigned long long k = keys[i];
       if (k < best) { best = k; best_at = i; }
     }
-    const unsigned long long wmin = gp_wave_min(best);
+    const unsigned long long wmin = wave_min(best);
     if (lane == 0) s_wmin[wave] = wmin;
     __syncthreads();
     unsigned long long kmin = s_wmin[0];
@@ -162,10 +156,7 @@ __global__ __launch_bounds__(kGpThreads) void k_gp_plan(GpGraph G, GpParams P, G
         }
       }
       // one atomic per wave for its entries
-      const unsigned long long m = __ballot(file);
-      uint32_t at = 0;
-      if (lane == 0 && m) at = atomicAdd(&s_count, (uint32_t)__popcll(m));
-      at = (uint32_t)__shfl((int)at, 0, 64) + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      const uint32_t at = wave_append(file, &s_count);
       if (file) {
         if (at < P.max_open) keys[at] = key;
         else s_full = 1;                                                             // (every writer stores the same)

@@ -38,8 +38,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "global_plan.hip.h"             // GpParams, GpQueries, gp_record, gp_wave_min, GlobalPlanState, global_plan_state
+#include "dev_memory.hip.h"              // dev_alloc, Drain, feed_wait
+#include "global_plan.hip.h"             // GpParams, GpQueries, gp_record, GlobalPlanState, global_plan_state
 #include "global_plan_cloud_plan.hip.h"
+#include "wave_ops.hip.h"                // wave_min, wave_append, block_excl_scan
 
 #pragma clang fp contract(off)
 
@@ -181,7 +183,7 @@ __global__ __launch_bounds__(kGpThreads) void k_gp_plan_cloud(GpcArgs A_in, GpPa
       const unsigned long long k = keys[i];
       if (k < best) { best = k; best_at = i; }
     }
-    const unsigned long long wmin = gp_wave_min(best);
+    const unsigned long long wmin = wave_min(best);
     if (lane == 0) s_wmin[wave] = wmin;
     __syncthreads();
     unsigned long long kmin = s_wmin[0];
@@ -215,10 +217,7 @@ __global__ __launch_bounds__(kGpThreads) void k_gp_plan_cloud(GpcArgs A_in, GpPa
     gpc_walk(A.ground, gpc_box(A.ground, pc.x, pc.y, pc.z, A.r_box), false, s_rows, tid, [&](bool in, const float4 c) {
       const float d2 = l2_simple(c.x, c.y, c.z, pc.x, pc.y, pc.z);
       const bool hit = in && d2 < A.r2;                                              // RadiusResultSet::addPoint: strictly
-      const unsigned long long m = __ballot(hit);
-      uint32_t at = 0;
-      if (lane == 0 && m) at = atomicAdd(&s_n, (uint32_t)__popcll(m));
-      at = (uint32_t)__shfl((int)at, 0, 64) + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      const uint32_t at = wave_append(hit, &s_n);
       if (hit && at < kGpCloudMaxSuccessors) s_list[at] = gpc_key(d2, (uint32_t)__float_as_int(c.w));
     });
     __syncthreads();
@@ -254,7 +253,7 @@ __global__ __launch_bounds__(kGpThreads) void k_gp_plan_cloud(GpcArgs A_in, GpPa
           const unsigned long long k = gpc_key(l2_simple(c.x, c.y, c.z, pc.x, pc.y, pc.z), (uint32_t)__float_as_int(c.w));
           if (in && (j == 0 || k > prev) && k < lo) lo = k;
         });
-        const unsigned long long wlo = gp_wave_min(lo);
+        const unsigned long long wlo = wave_min(lo);
         if (lane == 0) s_wmin[wave] = wlo;
         __syncthreads();
         unsigned long long k8 = s_wmin[0];
@@ -322,21 +321,9 @@ __global__ __launch_bounds__(kGpThreads) void k_gp_plan_cloud(GpcArgs A_in, GpPa
       s_pe[tid] = pe;
       s_dt[tid] = dt;
       s_flag[tid] = capped ? 1u : 0u;
-      uint32_t inc = capped ? 0u : ns;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)inc, o, 64);
-        if ((int)lane >= o) inc += t;
-      }
-      if (lane == 63) s_wsum[wave] = inc;
-      __syncthreads();
-      uint32_t before = 0, total = 0;
-#pragma unroll
-      for (uint32_t w = 0; w < kGpThreads / 64; ++w) {
-        if (w < wave) before += s_wsum[w];
-        total += s_wsum[w];
-      }
-      s_prefix[tid + 1] = before + inc;
+      const uint32_t steps = capped ? 0u : ns;
+      uint32_t total;
+      s_prefix[tid + 1] = block_excl_scan<kGpThreads / 64>(steps, s_wsum, &total) + steps;
       if (tid == 0) s_prefix[0] = 0;
       __syncthreads();
       // ---- isLineOfSightClear (:168-198): a lane per (edge, sample) ----
@@ -375,10 +362,7 @@ __global__ __launch_bounds__(kGpThreads) void k_gp_plan_cloud(GpcArgs A_in, GpPa
           key = gp_key(new_f, nb);
         }
       }
-      const unsigned long long m = __ballot(file);
-      uint32_t at = 0;
-      if (lane == 0 && m) at = atomicAdd(&s_count, (uint32_t)__popcll(m));
-      at = (uint32_t)__shfl((int)at, 0, 64) + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      const uint32_t at = wave_append(file, &s_count);
       if (file) {
         if (at < P.max_open) keys[at] = key;
         else s_full = 1;

@@ -33,7 +33,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dev_memory.hip.h"    // Owned, dev_alloc
 #include "lidar_sweep.hip.h"
+#include "wave_ops.hip.h"      // block_rank, wave_sum
 
 #pragma clang fp contract(off)
 
@@ -101,7 +103,7 @@ __global__ __launch_bounds__(256) void k_feat_blocks(FeatParams k, const int32_t
   bool g;
   const bool keep = feat_keep(k, blockIdx.x * 256 + threadIdx.x, label_img, ground_img, &g);
   uint32_t total;
-  sweep_block_rank(keep, lds, &total);
+  block_rank<4>(keep, lds, &total);
   if (threadIdx.x == 0) block_cnt[blockIdx.x] = total;
 }
 
@@ -116,14 +118,13 @@ __global__ __launch_bounds__(256) void k_feat_segment(FeatParams k, const int32_
   const bool keep = feat_keep(k, p, label_img, ground_img, &g);
   uint32_t before = 0;
   for (uint32_t i = threadIdx.x; i < blockIdx.x; i += 256) before += block_cnt[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off, 64);
+  before = wave_sum(before);
   if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = before;
   __syncthreads();
   before = lds[0] + lds[1] + lds[2] + lds[3];
   __syncthreads();
   uint32_t total;
-  const uint32_t rank = before + sweep_block_rank(keep, lds, &total);
+  const uint32_t rank = before + block_rank<4>(keep, lds, &total);
   if (keep) {
     const float4 q = pts[p];
     seg_pt[rank] = make_float4(q.x, q.y, q.z, range_img[p]);
@@ -336,8 +337,7 @@ __global__ __launch_bounds__(256) void k_feat_emit(FeatParams k, const uint32_t*
   if (wave < 3) {
     uint32_t acc = 0;
     for (uint32_t r = lane; r < row; r += 64) acc += slot_cnt[3 * r + wave];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    acc = wave_sum(acc);
     if (lane == 0) {
       before[wave] = acc;
       if (row == k.V - 1) {

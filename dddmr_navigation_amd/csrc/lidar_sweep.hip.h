@@ -46,7 +46,10 @@
 #include <cstring>
 #include <memory>
 
+#include "dev_memory.hip.h"           // Owned, dev_alloc, feed_wait
 #include "perception_kernels.hip.h"
+#include "point_grid_plan.hip.h"      // stage_xyz_records
+#include "wave_ops.hip.h"             // block_rank, wave_sum
 
 // Nothing may be fused: the reference is an x86-64 build without FMA contraction.
 #pragma clang fp contract(off)
@@ -270,24 +273,6 @@ __device__ __forceinline__ bool sweep_valid(const SweepParams& k, uint32_t size,
   return lines >= k.valid_lines;
 }
 
-// exclusive rank of the flagged lanes of a 256-lane workgroup in lane order, and their number; lds: 4 words
-__device__ __forceinline__ uint32_t sweep_block_rank(bool flag, uint32_t* lds, uint32_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long m = __ballot(flag);
-  if (lane == 0) lds[wave] = (uint32_t)__popcll(m);
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const uint32_t c = lds[w];
-    if (w < wave) base += c;
-    tot += c;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-}
-
 __global__ __launch_bounds__(256) void k_sweep_blocks(SweepParams k, const uint32_t* __restrict__ parent, const uint32_t* __restrict__ size,
                                                       const uint32_t* __restrict__ rows, uint2* __restrict__ block_cnt) {
   __shared__ uint32_t lds[4];
@@ -295,8 +280,8 @@ __global__ __launch_bounds__(256) void k_sweep_blocks(SweepParams k, const uint3
   const uint32_t root = p < k.V * k.H ? parent[p] : kSweepNone;
   const bool valid = root != kSweepNone && sweep_valid(k, size[root], rows + 4u * (size_t)root);
   uint32_t n_roots, n_out;
-  sweep_block_rank(valid && root == p, lds, &n_roots);
-  sweep_block_rank(valid, lds, &n_out);
+  block_rank<4>(valid && root == p, lds, &n_roots);
+  block_rank<4>(valid, lds, &n_out);
   if (threadIdx.x == 0) block_cnt[blockIdx.x] = make_uint2(n_roots, n_out);
 }
 
@@ -308,11 +293,8 @@ __device__ __forceinline__ uint2 sweep_blocks_before(const uint2* __restrict__ b
     a += c.x;
     b += c.y;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    a += __shfl_xor(a, off, 64);
-    b += __shfl_xor(b, off, 64);
-  }
+  a = wave_sum(a);
+  b = wave_sum(b);
   if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = make_uint2(a, b);
   __syncthreads();
   const uint2 r = make_uint2(lds[0].x + lds[1].x + lds[2].x + lds[3].x, lds[0].y + lds[1].y + lds[2].y + lds[3].y);
@@ -336,7 +318,7 @@ __global__ __launch_bounds__(256) void k_sweep_number(SweepParams k, const uint3
   }
   const uint2 before = sweep_blocks_before(block_cnt, lds2);
   uint32_t total;
-  const uint32_t rank = sweep_block_rank(valid, lds, &total);
+  const uint32_t rank = block_rank<4>(valid, lds, &total);
   if (is_root) num[p] = valid ? before.x + rank + 1u : 0u;      // _label_count starts at 1
 }
 
@@ -358,7 +340,7 @@ __global__ __launch_bounds__(256) void k_sweep_output(SweepParams k, const uint3
   const bool out = label > 0 && label != kSweepInvalidLabel;      // :585
   const uint2 before = sweep_blocks_before(block_cnt, lds2);
   uint32_t total;
-  const uint32_t rank = sweep_block_rank(out, lds, &total);
+  const uint32_t rank = block_rank<4>(out, lds, &total);
   if (out) {
     const float4 q = pts[p];
     cloud[before.y + rank] = make_float4(q.x, q.y, q.z, (float)label);

@@ -4,6 +4,7 @@
 // owns when it dies.
 #pragma once
 
+#include "dev_memory.hip.h"   // DevAllocs, dev_alloc
 #include "marking.hip.h"
 #include "point_grid.hip.h"   // GridBuf, grid_alloc
 

@@ -33,7 +33,7 @@
 // the contested-voxel priority looks at.
 #pragma once
 #include "marking.hip.h"
-#include "rollout_kernels.hip.h"   // wave_incl_scan_u32
+#include "wave_ops.hip.h"   // block_excl_scan, lanes_below, wave_min / wave_max, ld_agent, wait_own_memory_ops
 
 #pragma clang fp contract(off)
 
@@ -100,42 +100,8 @@ struct FuseBufs {
   uint32_t* hi_rank;       // [8][kFuseMaxObs - kFuseRegObs] (cell, rank) of the points past kFuseRegObs, per grid workgroup
 };
 
-__device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned long long ld_agent(const unsigned long long* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// This wave's stores and atomics have been acknowledged (written through to the level every CU of the chip reads:
-// device-scope atomics and sc1 loads go there).  What a hand-off inside a launch needs here is exactly that plus a
-// barrier / ticket; an agent-scope fence (__threadfence) also writes the XCD's L2 back, which cost the last launch
-// 120 us when all 2090 workgroups issued one (profiles/r03_C5M_fused_kernel_stats.csv history in DESIGN.md).
-__device__ __forceinline__ void wait_own_memory_ops() { __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ uint32_t wave_last(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, 63); }
-__device__ __forceinline__ uint32_t lanes_below(unsigned long long m) {
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 __device__ __forceinline__ uint32_t part_of(uint32_t seed) { return (seed * 2654435761u) >> 26; }   // 64 partitions
 __device__ __forceinline__ int bits_for(int range) { return range <= 0 ? 1 : 32 - __clz(range); }
-
-// exclusive prefix of one value per lane over a block of W waves, in lane order (two barriers; wsum = W LDS words)
-template <int W>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum, uint32_t* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const uint32_t incl = wave_incl_scan_u32(v);
-  if (lane == 63) wsum[w] = incl;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int j = 0; j < W; ++j) {
-    const uint32_t x = wsum[j];
-    tot += x;
-    if (j < w) base += x;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + incl - v;
-}
 
 // ProjectInliers(SACMODEL_PLANE) of one point (cluster_marking.cpp:54-64; k_mk_proj_keys)
 __device__ __forceinline__ void project_on_base_plane(const MarkParams& k, float x, float y, float z, float* qx, float* qy, float* qz) {
@@ -709,11 +675,8 @@ __device__ __forceinline__ void block_minmax3(int (&mn)[3], int (&mx)[3], int* r
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      mn[a] = min(mn[a], __shfl_xor(mn[a], o, 64));
-      mx[a] = max(mx[a], __shfl_xor(mx[a], o, 64));
-    }
+    mn[a] = wave_min(mn[a]);
+    mx[a] = wave_max(mx[a]);
   }
   if (lane == 0) {
 #pragma unroll

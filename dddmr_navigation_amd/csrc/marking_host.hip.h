@@ -3,6 +3,7 @@
 // launch sequence and the dddmr_rollout_marking_* entry points of include/dddmr_rollout.h.
 #pragma once
 
+#include "dev_memory.hip.h"      // DevScope, Drain, wait_seq
 #include "marking.hip.h"
 #include "marking_fused.hip.h"
 #include "marking_plan.hip.h"

@@ -10,6 +10,7 @@
 
 #include <unordered_map>
 
+#include "dev_memory.hip.h"        // DevAllocs
 #include "marking_buffers.hip.h"   // StoreBuf and its allocation
 
 namespace {

@@ -19,9 +19,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dev_memory.hip.h"        // Owned, dev_alloc, Drain, feed_wait
+#include "mcl_filter_plan.hip.h"
 #include "mcl_measure.hip.h"
 #include "mcl_observation.hip.h"   // the prepared observation
-#include "mcl_filter_plan.hip.h"
 
 #pragma clang fp contract(off)
 

@@ -18,8 +18,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dev_memory.hip.h"        // Owned, dev_alloc, Drain, feed_wait
 #include "point_grid.hip.h"
 #include "point_grid_plan.hip.h"   // grid_shape, HostCloud, cloud_arg_ok, cloud_coords_ok
+#include "wave_ops.hip.h"          // wave_min, wave_sum
 
 #pragma clang fp contract(off)
 
@@ -185,8 +187,7 @@ __global__ __launch_bounds__(64) void k_mcl_ground(MclParams k, PointGrid ground
     grid_for_each_wave(G, px, py, pz, kMclNnRadius + kMclPad, lane, [&](const float4 g) {
       best = fminf(best, l2_simple(g.x, g.y, g.z, px, py, pz));
     });
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) best = fminf(best, __shfl_xor(best, m, 64));
+    best = wave_min(best);
   }
   __syncthreads();
   if (lane != 0) return;
@@ -257,8 +258,7 @@ __global__ __launch_bounds__(256) void k_mcl_match(MclParams k, PointGrid ground
       const PointGrid& gf = (flags & kMclHealthy) ? ground : map;
       for (uint32_t i = lane; i < k.n_flat; i += 64) term[i] = mcl_term(k, gf, r, tx, ty, tz, s_obs[i], &cnt);
       for (uint32_t i = k.n_flat + lane; i < n_obs; i += 64) term[i] = mcl_term(k, map, r, tx, ty, tz, s_obs[i], &cnt);
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m, 64);
+      cnt = wave_sum(cnt);
     }
     __syncthreads();
     if (valid && lane == 0) {

@@ -22,17 +22,20 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "dev_memory.hip.h"        // Owned, dev_alloc, Drain
 #include "mcl_measure.hip.h"       // MclState, mcl_run: the prepared observation is measured there
 #include "mcl_normal.hip.h"
 #include "mcl_observation_plan.hip.h"
 #include "point_grid_plan.hip.h"   // cloud_arg_ok
 #include "sensor_sources.hip.h"    // sweep_features_of: the features of a sweep source, on the device
+#include "wave_ops.hip.h"          // block_excl_scan
 
 #pragma clang fp contract(off)
 
 namespace dddmr {
 
 constexpr uint32_t kMclObsThreads = 1024;
+static_assert(kMclObsThreads % 64 == 0, "whole waves: the scans run the wave primitives");
 static_assert(kMclMaxObs <= 2 * kMclObsThreads, "two elements per lane in the scans and the root pass");
 constexpr uint32_t kMclObsNone = 0xFFFFFFFFu;
 
@@ -53,32 +56,12 @@ struct MclObsResult {            // host-mapped; seq is stored last
 
 // exclusive scan of a[0 .. n) in place, n <= 2 * kMclObsThreads; every lane of the workgroup calls it; returns the total
 __device__ inline uint32_t mclobs_scan(uint32_t* a, uint32_t n, uint32_t* s_w) {
-  const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-  const uint32_t i0 = 2 * t, i1 = 2 * t + 1;
+  const uint32_t i0 = 2 * threadIdx.x, i1 = i0 + 1;
   const uint32_t v0 = i0 < n ? a[i0] : 0u, v1 = i1 < n ? a[i1] : 0u;
-  const uint32_t sum = v0 + v1;
-  uint32_t incl = sum;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t u = __shfl_up(incl, d, 64);
-    if ((int)lane >= d) incl += u;
-  }
-  if (lane == 63) s_w[wave] = incl;
-  __syncthreads();
-  if (t == 0) {
-    uint32_t acc = 0;
-    for (uint32_t w = 0; w < kMclObsThreads / 64; ++w) {
-      const uint32_t x = s_w[w];
-      s_w[w] = acc;
-      acc += x;
-    }
-    s_w[kMclObsThreads / 64] = acc;
-  }
-  __syncthreads();
-  const uint32_t base = s_w[wave] + incl - sum;
+  uint32_t total;
+  const uint32_t base = block_excl_scan<kMclObsThreads / 64>(v0 + v1, s_w, &total);   // (ends with a barrier: a[] has been read)
   if (i0 < n) a[i0] = base;
   if (i1 < n) a[i1] = base + v0;
-  const uint32_t total = s_w[kMclObsThreads / 64];
   __syncthreads();
   return total;
 }
@@ -125,7 +108,7 @@ __global__ __launch_bounds__(kMclObsThreads) void k_mclobs_prepare(MclObsParams 
   __shared__ unsigned long long s_key[kMclMaxObs];       // flat: voxel index; less sharp: normal x, y, then (clusters) s_c
   __shared__ uint32_t s_a[kMclMaxObs];                   // flat: point by rank; less sharp: union-find parent
   __shared__ uint32_t s_b[kMclMaxObs];                   // flat: first of its voxel, scanned; less sharp: cluster size
-  __shared__ uint32_t s_w[kMclObsThreads / 64 + 1];
+  __shared__ uint32_t s_w[kMclObsThreads / 64];
   __shared__ int s_lo[3], s_hi[3];
   __shared__ double s_sum[2];
   __shared__ uint32_t s_cnt[4];                          // branch, NaN normals, kept points, small clusters

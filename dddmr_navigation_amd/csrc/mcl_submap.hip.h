@@ -23,11 +23,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dev_memory.hip.h"        // Owned, dev_alloc, Drain
 #include "mcl_measure.hip.h"       // MclState, MclMap, mcl_grid: a warm-up is a generation of the measure's
 #include "mcl_normal.hip.h"
 #include "mcl_submap_plan.hip.h"
 #include "point_grid.hip.h"        // PointGrid, GridBuf, the cell walks
 #include "point_grid_plan.hip.h"   // stage_cloud, cloud_arg_ok, cloud_box_ok
+#include "wave_ops.hip.h"          // wave_min, wave_max
 
 #pragma clang fp contract(off)
 
@@ -146,8 +148,7 @@ __global__ __launch_bounds__(64) void k_submap_knn(PointGrid g, uint32_t k, int3
       far_list[atomicAdd(&cnt->n_far, 1u)] = t;
     }
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) rings = max(rings, __shfl_xor(rings, m, 64));
+  rings = wave_max(rings);
   if (lane == 0 && rings > 0) atomicMax(&cnt->max_rings, (uint32_t)rings);
 }
 
@@ -170,13 +171,7 @@ __global__ __launch_bounds__(64) void k_submap_knn_far(PointGrid g, const float4
     uint32_t head = 0;
     for (uint32_t o = 0; o < k; ++o) {                                    // the 64 sorted columns merged: k rounds of a wave minimum
       const unsigned long long mine = head < have ? col[head * 64] : kSubmapNoKey;
-      unsigned long long best = mine;
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) {
-        const uint32_t hi = __shfl_xor((uint32_t)(best >> 32), m, 64), lo = __shfl_xor((uint32_t)best, m, 64);
-        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
-        best = other < best ? other : best;
-      }
+      const unsigned long long best = wave_min(mine);
       if (mine == best && best != kSubmapNoKey) ++head;                   // (keys are distinct: one lane advances)
       if (lane == 0) nb[(size_t)me * k + o] = best == kSubmapNoKey ? -1 : (int32_t)(uint32_t)best;
     }

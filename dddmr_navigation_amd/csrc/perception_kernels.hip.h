@@ -19,7 +19,10 @@
 #include <cstring>
 #include <deque>
 
+#include "dev_memory.hip.h"        // Owned, host_mapped_alloc, feed_wait
+#include "point_grid_plan.hip.h"   // pack_xyz_records, stage_xyz_records
 #include "voxel_table.hip.h"
+#include "wave_ops.hip.h"          // wave_append, last_block
 
 // The reference is an x86-64 build without FMA contraction: every multiply and add below
 // rounds separately, in float and in double (hipcc's default would fuse them).

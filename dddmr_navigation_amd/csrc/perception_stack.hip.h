@@ -21,7 +21,9 @@
 #include <stdint.h>
 
 #include "depth_layer.hip.h"    // DepthLayerState, depth_layer_update_locked
+#include "dev_memory.hip.h"     // Owned, dev_alloc, Drain
 #include "marking_host.hip.h"   // MarkingState, marking_update_on
+#include "wave_ops.hip.h"       // wave_append
 
 namespace dddmr {
 
@@ -69,17 +71,11 @@ __global__ __launch_bounds__(256) void k_stack_min(MinStackArgs a) {
         a.mask_pub[i] = (uint8_t)mask;
       }
     }
-    const unsigned long long m = __ballot(changed);
-    if (m) {
-      const int leader = __ffsll((long long)m) - 1;
-      uint32_t at = 0;
-      if (lane == leader) at = atomicAdd(a.n_changed, (uint32_t)__popcll(m));
-      at = (uint32_t)__shfl((int)at, leader, 64) + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      if (changed && at < a.cap) {
-        a.chg_node[at] = i;
-        a.chg_value[at] = v;
-        a.chg_mask[at] = (uint8_t)mask;
-      }
+    const uint32_t at = wave_append(changed, a.n_changed);
+    if (changed && at < a.cap) {
+      a.chg_node[at] = i;
+      a.chg_value[at] = v;
+      a.chg_mask[at] = (uint8_t)mask;
     }
   }
 }

@@ -9,8 +9,8 @@
 #include <cstring>             // (rocPRIM's texture_cache_iterator.hpp calls memset without it)
 #include <rocprim/rocprim.hpp>
 
+#include "dev_memory.hip.h"    // DevAllocs, dev_alloc
 #include "exact_float.hip.h"
-#include "voxel_table.hip.h"   // DevAllocs, dev_alloc
 
 #pragma clang fp contract(off)
 

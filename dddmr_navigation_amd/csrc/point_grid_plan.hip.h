@@ -1,10 +1,11 @@
 // point_grid_plan.hip.h -- the host arithmetic around a PointGrid (point_grid.hip.h): the grid's shape over a box, the
-// cell functions on the host, staging a caller's strided cloud as float4 records with their box, and the limits a cloud
+// cell functions on the host, staging a caller's strided cloud as float4 records with their box or as packed xyz, and the limits a cloud
 // has to keep for the search pads to hold.  Host code only -- no HIP runtime call, no context -- so that
 // tests/cpp/point_grid_plan_test.cpp runs it on a machine without a GPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 #include "point_grid.hip.h"
@@ -57,6 +58,27 @@ inline bool stage_cloud(const float* xyz, size_t n, size_t stride_bytes, float4*
     out[i] = make_float4(v[0], v[1], v[2], 0.f);
   }
   return finite;
+}
+
+// n records (stride_bytes apart, x y z first) narrowed to packed xyz
+inline void pack_xyz_records(float* dst, const float* src, size_t n, size_t stride_bytes) {
+  const size_t sf = stride_bytes / 4;
+  for (size_t i = 0; i < n; ++i) {
+    dst[3 * i + 0] = src[i * sf + 0];
+    dst[3 * i + 1] = src[i * sf + 1];
+    dst[3 * i + 2] = src[i * sf + 2];
+  }
+}
+
+// Stages the caller's records for a kernel: 12- and 16-byte records go as they are, wider ones (PCL: 32 bytes) are
+// narrowed to 12 bytes on the way.  Returns the staged records' stride in floats.
+inline int stage_xyz_records(float* dst, const float* src, size_t n, size_t stride_bytes) {
+  if (stride_bytes == 12 || stride_bytes == 16) {
+    std::memcpy(dst, src, n * stride_bytes);
+    return (int)(stride_bytes / 4);
+  }
+  pack_xyz_records(dst, src, n, stride_bytes);
+  return 3;
 }
 
 // A staged cloud that owns its records (one zero element without a point).  It refuses nothing: whoever has to looks at

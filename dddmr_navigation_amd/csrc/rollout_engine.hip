@@ -38,6 +38,7 @@ namespace { int fail(dddmr_rollout_ctx* ctx, int code, const char* fmt, ...); }
                   __FILE__, __LINE__);                                                      \
   } while (0)
 
+#include "dev_memory.hip.h"   // DevAllocs, DevScope, Drain: the context's memory, the diagnostics' temporaries
 #include "rollout_kernels.hip.h"
 #include "tick_plan.hip.h"
 #include "perception_kernels.hip.h"

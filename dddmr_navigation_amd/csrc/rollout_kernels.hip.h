@@ -26,6 +26,7 @@
 
 #include "../../include/dddmr_rollout.h"
 #include "exact_float.hip.h"   // fmul, fadd, fsub, l2_simple, dot3
+#include "wave_ops.hip.h"      // wave_incl_scan_u32
 
 // The reference is an x86-64 build without FMA contraction: every multiply and add below
 // rounds separately, in float and in double (hipcc's default would fuse them).
@@ -237,20 +238,6 @@ __host__ __device__ inline unsigned long long pack_slot_word3(uint32_t w_bits, u
 __host__ __device__ inline uint32_t slot_w_bits(unsigned long long w3) { return (uint32_t)w3; }
 __host__ __device__ inline uint32_t slot_collided(unsigned long long w3) { return (uint32_t)(w3 >> 32) & 0xFFFFu; }
 __host__ __device__ inline uint32_t slot_generated(unsigned long long w3) { return (uint32_t)(w3 >> 48) & 0xFFFFu; }
-
-// Inclusive prefix sum over the 64 lanes of a wave with DPP moves (register-to-register, a few
-// cycles each) instead of LDS-crossbar shuffles: Hillis-Steele inside the 16-lane rows
-// (row_shr 1, 2, 4, 8; lanes without a source add 0), then the row totals are carried over
-// with row_bcast:15 (into rows 1 and 3) and row_bcast:31 (into rows 2 and 3).
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);
-  return v;
-}
 
 // DPP row_shl:N (lane i reads lane i+N of its 16-lane row; lanes without a source keep their own
 // value) for 32- and 64-bit payloads: the building block of reductions towards lane 0 of a group.

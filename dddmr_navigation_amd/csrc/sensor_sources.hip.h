@@ -48,7 +48,7 @@ int read_back(dddmr_rollout_ctx* ctx, const char* what, void* out, const void* d
 }
 
 // How every module state below is made: in a unique_ptr of its own, which moves into its slot once the state is complete.
-// One that could not be allocated in full frees what it got as the pointer goes out of scope (Owned, voxel_table.hip.h);
+// One that could not be allocated in full frees what it got as the pointer goes out of scope (Owned, dev_memory.hip.h);
 // resetting the slot is the whole teardown.
 
 // the feed scratch (stitcher state, staging) of a scan source above 0, allocated on first use

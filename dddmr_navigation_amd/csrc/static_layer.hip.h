@@ -24,10 +24,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dev_memory.hip.h"        // Owned, dev_alloc, Drain, feed_wait
 #include "perception_stack.hip.h"  // StackState: publish_to_stack writes a host slot of the stack
 #include "point_grid.hip.h"        // PointGrid and its walks, GridBuf, grid_build; rocPRIM
 #include "point_grid_plan.hip.h"   // grid_shape, stage_cloud, HostCloud, cloud_arg_ok, cloud_box_ok
 #include "static_layer_plan.hip.h"
+#include "wave_ops.hip.h"          // wave_max, wave_sum, lanes_below
 
 #pragma clang fp contract(off)
 
@@ -56,12 +58,6 @@ struct SlSearch {
   int write_rows;              // generate_static_graph: the degrees become rows
 };
 __device__ __forceinline__ float sl_adaptive_box(int k) { return (float)sl_adaptive_radius(k) + kSlPad; }
-
-__device__ __forceinline__ uint32_t sl_wave_max(uint32_t v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, m, 64));
-  return v;
-}
 
 // row_start [n + 1]: the degrees (0 in entry n, and everywhere without write_rows); nb_count [n]: the neighbourhood's size
 // whether rows are written or not; kidx [n]: the radius index (0 in fixed mode); long_list: sorted positions of the rows
@@ -118,10 +114,8 @@ __global__ __launch_bounds__(64) void k_sl_degree(PointGrid g, SlSearch s, uint3
     row_start[me] = deg;
     if (deg > kSlRowLds) long_list[atomicAdd(&cnt->n_long, 1u)] = t;
   }
-  const uint32_t wmax = sl_wave_max(deg);
-  unsigned long long sum = deg;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) sum += ((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)(sum >> 32), m, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)sum, m, 64);
+  const uint32_t wmax = wave_max(deg);
+  const unsigned long long sum = wave_sum((unsigned long long)deg);
   if (lane == 0 && wmax) {
     atomicMax(&cnt->max_degree, wmax);
     atomicAdd(&cnt->n_edges, sum);
@@ -165,7 +159,7 @@ __global__ __launch_bounds__(64) void k_sl_fill(PointGrid g, SlSearch s, const u
           hit = d2 < r2;
         }
         const unsigned long long m = __ballot(hit);
-        const uint32_t pos = have + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        const uint32_t pos = have + lanes_below(m);
         if (hit && pos < kSlRowLds) { s_idx[pos] = idx; s_d2[pos] = d2; }
         have += (uint32_t)__popcll(m);
       }

@@ -523,6 +523,15 @@ class LocalPlanner:
         self._call("selftest_sincos", M.ptr(a), a.size, M.ptr(sn), M.ptr(cs))
         return sn, cs
 
+    def selftest_wave_ops(self, values, flags, append_base: int = 0):
+        """The wave primitives of csrc/wave_ops.hip.h over n <= 256 values (u32) and flags, one per lane of one workgroup
+        -> (out32[10, 256] u32, out64[2, 256] u64), rows as include/dddmr_rollout.h lists them"""
+        v = np.ascontiguousarray(values, dtype=np.uint32)
+        f = np.ascontiguousarray(flags, dtype=np.uint8)
+        out32, out64 = np.zeros((10, 256), dtype=np.uint32), np.zeros((2, 256), dtype=np.uint64)
+        self._call("selftest_wave_ops", M.ptr(v), M.ptr(f), v.size, int(append_base), M.ptr(out32), M.ptr(out64))
+        return out32, out64
+
     # -- per-trajectory outputs of the last tick -----------------------------
     def debug(self):
         """-> (costs[n_local] f64, steps[n_local] i32, samples[n_local,3] f32)"""

@@ -1606,6 +1606,23 @@ int dddmr_rollout_stream_ceiling(dddmr_rollout_ctx* ctx, size_t bytes, int32_t r
 int dddmr_rollout_selftest_sincos(dddmr_rollout_ctx* ctx, const double* angles, size_t n,
                                   double* sin_out, double* cos_out);
 
+/* Self-test aid: the library's wave and workgroup primitives (csrc/wave_ops.hip.h) over n <= 256 values and flags (a
+   flag is set when its byte is not 0; n = 0 is allowed), one per lane of a single workgroup of 256 lanes; the lanes at
+   or past n take part with value 0 and a clear flag.  With `lane` the thread's index modulo 64 and a wave 64 threads:
+     out32[0][t]  inclusive prefix sum of the values over t's wave       out32[5][t]  minimum of the values of t's wave
+     out32[1][t]  exclusive prefix sum over the workgroup                out32[6][t]  maximum
+     out32[2][t]  how many lanes below t have their flag set             out32[7][t]  sum (wrapping)
+     out32[3][t]  t's index from a wave-aggregated append, counter in    out32[8][t]  bits of the minimum of (float)value
+                  global memory (of no meaning where the flag is clear)  out64[0][t]  minimum of (value << 32) | lane
+     out32[4][t]  the same with the counter in LDS                       out64[1][t]  sum (wrapping) of the same
+     out32[9][0 .. 3]  the workgroup's sum, its number of flags, the final global and LDS counters (both start at
+                  append_base); the rest of row 9 is not written
+   Rows are 256 entries.  Not part of the reference's surface and not on the tick's path. */
+#define DDDMR_WAVE_OPS_OUT32 (10 * 256)
+#define DDDMR_WAVE_OPS_OUT64 (2 * 256)
+int dddmr_rollout_selftest_wave_ops(dddmr_rollout_ctx* ctx, const uint32_t* values, const uint8_t* flags, size_t n,
+                                    uint32_t append_base, uint32_t* out32, unsigned long long* out64);
+
 const char* dddmr_rollout_last_error(dddmr_rollout_ctx* ctx);
 const char* dddmr_rollout_version(void);
 

@@ -1,4 +1,4 @@
-// Who frees what in the sensor half of the library (csrc/voxel_table.hip.h's owners and the module states built on
+// Who frees what in the sensor half of the library (csrc/dev_memory.hip.h's owners and the module states built on
 // them) and in the marking layers' building blocks (csrc/marking_buffers.hip.h), on the CPU.  The HIP allocation calls are replaced by counting stand-ins on malloc, each of which can be told to
 // fail at the k-th call of a pass.  For every state: a clean alloc + free leaves nothing live; with the failure placed
 // at every call of the clean pass in turn, alloc reports failure and nothing stays live afterwards; and no pointer is
@@ -108,6 +108,7 @@ hipError_t fake_hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKin
 #define hipMemset fake_hipMemset
 #define hipMemcpy fake_hipMemcpy
 
+#include "dev_memory.hip.h"
 #include "depth_clear.hip.h"
 #include "depth_image.hip.h"
 #include "lidar_features.hip.h"

@@ -11,7 +11,7 @@ from conftest import ROOT
 # The only differences from the recording: an EMPTY cloud argument goes to the library as (null pointer, 0, stride 12)
 # whatever the method; the recording has a pointer to no element there, and a stride of 16 (set_cloud) or 0 (mcl_prepare).
 # function -> (positions of its cloud pointers in the call, the line of C that makes pointer and stride irrelevant at a
-# count of 0).  cloud_arg_ok is voxel_table.hip.h: `return !n || (xyz && stride_bytes >= 12 && stride_bytes % 4 == 0);`
+# count of 0).  cloud_arg_ok is point_grid_plan.hip.h: `return !n || (xyz && stride_bytes >= 12 && stride_bytes % 4 == 0);`
 # and no entry point reads a record or uses the stride outside a loop over the count.
 EMPTY_CLOUD = {
     "set_cloud": ((2,), "rollout_engine.hip: if (!cloud_arg_ok(xyzi, n_points, stride_bytes)) return fail(...)"),

@@ -1,4 +1,4 @@
-"""The context's buffers that are allocated again during its life (dev_realloc, csrc/voxel_table.hip.h): the rollout's state
+"""The context's buffers that are allocated again during its life (dev_realloc, csrc/dev_memory.hip.h): the rollout's state
 arrays, which grow when a tick's horizon needs more (trajectory, step) pairs than they hold, and the exchange buffers,
 which come back with every comm_init / comm_loopback after a comm_destroy.  In both cases the context must afterwards
 deliver, bit for bit, what a fresh context delivers that only ever saw the later state."""

@@ -1,4 +1,4 @@
-"""Who frees what in the sensor half of the library -- the owners of csrc/voxel_table.hip.h (DevAllocs, HostAllocs, Owned,
+"""Who frees what in the sensor half of the library -- the owners of csrc/dev_memory.hip.h (DevAllocs, HostAllocs, Owned,
 dev_realloc, host_mapped_reserve) and the module states built on them -- and in the building blocks of the marking
 layers (csrc/marking_buffers.hip.h), compiled into a stand-alone host program
 (tests/cpp/source_memory_test.cpp) in which the HIP allocation, memset and copy calls are counting stand-ins on malloc.

@@ -160,6 +160,7 @@ def record():
     lp.comm_destroy()
     lp.stream_ceiling(1 << 20, 3)
     lp.selftest_sincos([0.0, 0.5, 1.0])
+    lp.selftest_wave_ops([1, 2, 0xFFFFFFFF], [1, 0, 1], 5)
     lp.debug()
     lp.pose_arrays()
     lp.pose_arrays(accepted_only=True)
