@@ -564,6 +564,8 @@ _TABLE = {
     "stream_ceiling": (_int, [_ctx, _sz, _i32, _pd, _pd]),
     "selftest_sincos": (_int, [_ctx, _vp, _sz, _vp, _vp]),
     "selftest_wave_ops": (_int, [_ctx, _vp, _vp, _sz, _u32, _vp, _vp]),
+    "selftest_wave_wide": (_int, [_ctx, _vp, _sz, _vp, _u32, _vp, _vp, _vp]),
+    "selftest_point_grid": (_int, [_ctx, _vp, _sz, _vp, _vp, _vp, _u32, _vp, _sz, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "last_error": (_str, [_ctx]),
     "version": (_str, []),
     "sizeof": (_sz, [_int]),                  # the layout self-check of the CPU tests

@@ -40,7 +40,10 @@ namespace dddmr {
 constexpr int kDcMaxSources = 4;                 // == DDDMR_MAX_SOURCES
 constexpr uint32_t kDcCapCells = 1u << 21;       // cells of the observation grid; the cell grows from 0.05 m until the box fits
 constexpr float kDcCell = 0.05f;
-constexpr float kDcPad = 1e-4f;                  // the search boxes are widened by 0.1 mm, as the marking layer's are
+// The search boxes are widened by 0.1 mm, as the marking layer's are.  That covers half an ulp of extent + r_box, which is
+// all a neighbour can be lost to, while that sum is below 2048 m: static_grids_upload refuses a ground or map cloud wider
+// than kSmallPadMaxExtent (point_grid_plan.hip.h has the argument, the counter-example past the limit and the search).
+constexpr float kDcPad = 1e-4f;
 constexpr uint8_t kDcEmptyCluster = 0x80;        // verdict flag: a ratio branch met an empty cluster (1.0 * n / 0)
 
 // One camera's frustum in the global frame, as DepthCameraObservation holds it after bufferCloud.

@@ -74,6 +74,9 @@ static_assert(!std::is_copy_constructible_v<MarkingState>);
 int upload_static(dddmr_rollout_ctx* ctx, DevAllocs& mem, void* temp, size_t temp_bytes, GridBuf& b, float4** dev, const float* xyz, size_t n,
                   size_t stride_bytes, float cell_xy, float cell_z) {
   const HostCloud h(xyz, n, stride_bytes);
+  if (!small_pad_extent_ok(h.lo, h.hi))
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "static cloud of %zu points: wider than %g m on an axis, beyond what the search boxes' pad of 1e-4 m covers", n,
+                (double)kSmallPadMaxExtent);
   HIPCHK(ctx, dev_alloc(mem, dev, h.pts.size()));
   HIPCHK(ctx, hipMemcpy(*dev, h.pts.data(), h.pts.size() * sizeof(float4), hipMemcpyHostToDevice));
   grid_shape(b.g, h.lo, h.hi, cell_xy, cell_z, 1u << 22);
@@ -493,7 +496,7 @@ namespace {
 int marking_update_on(dddmr_rollout_ctx* ctx, MarkingState* m, const float4* obs, uint32_t n_obs, const double T_base_sensor[7],
                       const double T_gbl_base[7], dddmr_marking_stats* stats) {
   if (n_obs > m->max_obs) return fail(ctx, DDDMR_ERR_CAPACITY, "marking_update: observation of %u points, layer sized for %u", n_obs, m->max_obs);
-  float pad = 1e-4f;
+  float pad = 1e-4f;                           // half an ulp of extent + r_box below 2048 m: upload_static holds the clouds to kSmallPadMaxExtent
   if (const char* e = std::getenv("DDDMR_MK_PAD")) pad = (float)std::atof(e);      // (diagnosis)
   if (++m->seq == 0) m->seq = 1;
   const UpdateFrame f = make_update_frame(m->cfg, T_base_sensor, T_gbl_base, n_obs, m->prev >= 0 ? m->n_prev : 0, m->store.table,

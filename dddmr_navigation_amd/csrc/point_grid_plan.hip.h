@@ -100,6 +100,21 @@ inline bool cloud_box_ok(const float lo[3], const float hi[3]) {
     if (!(std::fabs(lo[a]) <= 1e6f) || !(std::fabs(hi[a]) <= 1e6f) || !(hi[a] - lo[a] <= kCloudMaxExtent)) return false;
   return true;
 }
+// The widest static cloud whose search boxes a pad of 1e-4 m covers (the marking and depth layers': kDcPad and the
+// marking layer's `pad`).  A neighbour with d2 < r2 can land in a cell outside the walked range only when
+// p - q > r_box - ulp / 2, the ulp being that of extent + r_box: the three roundings of (q - origin) + r_box and of
+// p - origin can add up to 1.5 ulp, and the float grid both sides land on takes a whole ulp of it back.  A pad of at least
+// half that ulp is therefore safe: 1e-4 m while extent + r_box stays below 2048 m (ulp 1.22e-4), and the widest box
+// half width of those layers (the inflation radius) has 48 m of room under this limit.  Past 2048 m it is not:
+// origin -1986.9237060546875, q = 61.126224517822266, p = 61.07622528076172 on the ground grid (0.5 m cells, r = 0.05)
+// have d2 < r2 with p in cell 4095 and the box starting at cell 4096 (tests/test_point_grid_cpu.py keeps the triple and
+// the search that found it; none was found below the limit).
+constexpr float kSmallPadMaxExtent = 2000.0f;
+inline bool small_pad_extent_ok(const float lo[3], const float hi[3]) {
+  for (int a = 0; a < 3; ++a)
+    if (hi[a] - lo[a] > kSmallPadMaxExtent) return false;      // (a NaN passes: these layers take a cloud as it is)
+  return true;
+}
 // every coordinate within the limits: the box is the cloud's only once nothing in it is NaN (std::min and max pass one by)
 inline bool cloud_coords_ok(const HostCloud& h) { return h.finite && cloud_box_ok(h.lo, h.hi); }
 

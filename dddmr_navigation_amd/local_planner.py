@@ -532,6 +532,41 @@ class LocalPlanner:
         self._call("selftest_wave_ops", M.ptr(v), M.ptr(f), v.size, int(append_base), M.ptr(out32), M.ptr(out64))
         return out32, out64
 
+    def selftest_wave_wide(self, values, lanes, n_groups: int):
+        """What selftest_wave_ops does not reach: block_excl_scan<16> and wave_last over n <= 1024 values (u32), the float
+        and int reductions over the 64 words of `lanes`, last_block among n_groups workgroups
+        -> (scan[2, 1024], reduce[4, 64], misc[4]) u32, rows as include/dddmr_rollout.h lists them"""
+        v = np.ascontiguousarray(values, dtype=np.uint32)
+        l = np.ascontiguousarray(lanes, dtype=np.uint32)
+        if l.size != 64:
+            raise ValueError("lanes: one word per lane of a wave, 64")
+        scan, red, misc = np.zeros((2, 1024), np.uint32), np.zeros((4, 64), np.uint32), np.zeros(4, np.uint32)
+        self._call("selftest_wave_wide", M.ptr(v), v.size, M.ptr(l), int(n_groups), M.ptr(scan), M.ptr(red), M.ptr(misc))
+        return scan, red, misc
+
+    def selftest_point_grid(self, points, lo, hi, cell_xy, cell_z, cap_cells: int, queries, r_box, r2, stop_at: int = 0x7fffffff):
+        """The point grid of csrc/point_grid.hip.h built over `points` [n, 3] in the box lo .. hi and walked for `queries`
+        [m, 3] -> dict of the grid (nx, ny, nz, and as float32 ox, oy, oz, inv_xy, inv_z), cell_start [cells + 1] u32,
+        sorted [n, 4] u32 (bits of x y z, original index), thread [m, 8] u32 and wave [m, 5] u32, columns as
+        include/dddmr_rollout.h lists them.  r_box and r2 go to the library as the float32 they round to."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 3)
+        box_lo, box_hi = np.ascontiguousarray(lo, dtype=np.float32), np.ascontiguousarray(hi, dtype=np.float32)
+        if box_lo.size != 3 or box_hi.size != 3:
+            raise ValueError("lo and hi: three coordinates each")
+        cell = np.array([cell_xy, cell_z], dtype=np.float32)
+        radius = np.array([r_box, r2], dtype=np.float32)
+        grid = np.zeros(8, np.uint32)
+        cell_start = np.zeros(max(int(cap_cells), 0) + 1, np.uint32)
+        srt, thr, wav = np.zeros((len(p), 4), np.uint32), np.zeros((len(q), 8), np.uint32), np.zeros((len(q), 5), np.uint32)
+        opt = lambda a: M.ptr(a) if a.size else None
+        self._call("selftest_point_grid", opt(p), len(p), M.ptr(box_lo), M.ptr(box_hi), M.ptr(cell), int(cap_cells), opt(q), len(q),
+                   M.ptr(radius), int(stop_at), M.ptr(grid), M.ptr(cell_start), opt(srt), opt(thr), opt(wav))
+        nx, ny, nz = (int(x) for x in grid[:3])
+        geom = grid[3:].view(np.float32)
+        return dict(nx=nx, ny=ny, nz=nz, ox=geom[0], oy=geom[1], oz=geom[2], inv_xy=geom[3], inv_z=geom[4],
+                    cell_start=cell_start[: nx * ny * nz + 1], sorted=srt, thread=thr, wave=wav)
+
     # -- per-trajectory outputs of the last tick -----------------------------
     def debug(self):
         """-> (costs[n_local] f64, steps[n_local] i32, samples[n_local,3] f32)"""

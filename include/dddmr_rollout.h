@@ -1623,6 +1623,48 @@ int dddmr_rollout_selftest_sincos(dddmr_rollout_ctx* ctx, const double* angles, 
 int dddmr_rollout_selftest_wave_ops(dddmr_rollout_ctx* ctx, const uint32_t* values, const uint8_t* flags, size_t n,
                                     uint32_t append_base, uint32_t* out32, unsigned long long* out64);
 
+/* Self-test aid: what dddmr_rollout_selftest_wave_ops does not reach, in three launches.
+     scan_out[0][t]  block_excl_scan<16> over one workgroup of 1024 lanes: the exclusive prefix sum of the n <= 1024 values
+                     (lanes at or past n take part with 0; n = 0 is allowed); misc_out[0] is the total it reports
+     scan_out[1][t]  wave_last of the inclusive prefix sum over t's wave: the wave's sum
+     reduce_out[0 .. 3][l]  over ONE wave whose lane l holds lanes[l] (64 words, never null): the bits of wave_min and of
+                     wave_max of the words read as float (feed no NaN), then wave_min and wave_max of the words read as int
+     misc_out[1], [2]  last_block among n_groups workgroups of 256 lanes (1 .. DDDMR_WAVE_WIDE_MAX_GROUPS): lane 63 of each
+                     wave stores the word n_groups * 0x9E3779B1 + i * i + 1 (wrapping) to slot i = 4 * workgroup + wave with a
+                     device-scope atomic; the workgroup last_block names reads all 4 * n_groups slots with ld_agent.
+                     [1] is how many workgroups were named, [2] the wrapping sum it read.  misc_out[3] stays 0.
+   Rows of scan_out are 1024 entries, of reduce_out 64.  Not part of the reference's surface and not on the tick's path. */
+#define DDDMR_WAVE_WIDE_SCAN (2 * 1024)
+#define DDDMR_WAVE_WIDE_REDUCE (4 * 64)
+#define DDDMR_WAVE_WIDE_MISC 4
+#define DDDMR_WAVE_WIDE_MAX_GROUPS 4096
+int dddmr_rollout_selftest_wave_wide(dddmr_rollout_ctx* ctx, const uint32_t* values, size_t n, const uint32_t* lanes,
+                                     uint32_t n_groups, uint32_t* scan_out, uint32_t* reduce_out, uint32_t* misc_out);
+
+/* Self-test aid: the uniform grid of csrc/point_grid.hip.h, built and walked as the modules do it.  The library's own
+   grid_shape(lo, hi, cell[0] = cell_xy, cell[1] = cell_z, cap_cells), grid_alloc and grid_build run over the n packed
+   xyz points (n = 0 is allowed; points outside the box are allowed and land in edge cells), then two kernels walk the
+   grid for each of the m packed xyz queries with the box half width radius[0] = r_box and the squared radius
+   radius[1] = r2.  Copied back, all as 32-bit words (floats as their bits):
+     grid_out[8]             nx, ny, nz, then ox, oy, oz, inv_xy, inv_z
+     cell_start_out          [nx * ny * nz + 1]; the caller provides cap_cells + 1 words
+     sorted_out[n][4]        the cell-sorted records: x, y, z, original index
+     thread_out[m][8]        from one thread per query: grid_radius_count with stop_at, grid_radius_count with 0x7fffffff,
+                             grid_nearest, grid_nearest_id's id and d2, and from a grid_for_each whose functor never stops
+                             the number of points visited, the wrapping sum and the xor of their original indices
+     wave_out[m][5]          from one wave per query over grid_for_each_wave: the same visited count, index sum and index
+                             xor, the number of points with d2 < r2, the minimum d2 (+inf without a point)
+   Refused with DDDMR_ERR_BAD_ARG: counts over the limits below, a null pointer with a nonzero count, cap_cells of 0,
+   stop_at below 1, a cell size outside 0.01 .. 1e6 m, r_box or r2 negative or not finite, lo > hi, and any coordinate
+   that is not finite within 1e6 m.  Not part of the reference's surface and not on the tick's path. */
+#define DDDMR_POINT_GRID_MAX_POINTS (1 << 16)
+#define DDDMR_POINT_GRID_MAX_QUERIES (1 << 16)
+#define DDDMR_POINT_GRID_MAX_CELLS (1 << 22)
+int dddmr_rollout_selftest_point_grid(dddmr_rollout_ctx* ctx, const float* xyz, size_t n, const float lo[3], const float hi[3],
+                                      const float cell[2], uint32_t cap_cells, const float* queries, size_t m,
+                                      const float radius[2], int32_t stop_at, uint32_t grid_out[8], uint32_t* cell_start_out,
+                                      uint32_t* sorted_out, uint32_t* thread_out, uint32_t* wave_out);
+
 const char* dddmr_rollout_last_error(dddmr_rollout_ctx* ctx);
 const char* dddmr_rollout_version(void);
 

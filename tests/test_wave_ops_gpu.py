@@ -4,7 +4,18 @@ Sums wrap as their integer type does.  The four waves race for the append's coun
 guaranteed is asserted: inside a wave the keeping lanes hold consecutive ascending indices, the waves' ranges are
 disjoint and tile [base, base + count), the final counter is base + count; a lane that does not keep is not looked at.
 
-Sizes: one lane, a wave less one, a wave, a wave and one, the workgroup less one, the workgroup, and nothing at all."""
+Sizes: one lane, a wave less one, a wave, a wave and one, the workgroup less one, the workgroup, and nothing at all.
+
+What that workgroup of 256 lanes with unsigned values cannot show goes through selftest_wave_wide: block_excl_scan<16>
+with wave_last in one workgroup of 1024 lanes, the reductions on the other types, and last_block's hand-off.  The
+(operation, type) pairs a kernel of csrc/ instantiates, by grep for wave_min / wave_max / wave_sum:
+    wave_min  float (mcl_measure, depth_clear: coordinates, negative too), int (marking_fused's block_minmax3),
+              unsigned long long (global_plan, global_plan_cloud, mcl_submap)
+    wave_max  uint32_t (static_layer), int (marking_fused, mcl_submap), float (depth_clear)
+    wave_sum  uint32_t (mcl_measure, lidar_sweep, lidar_features), unsigned long long (static_layer)
+selftest_wave_ops holds min / max / sum on uint32_t, min / sum on unsigned long long and min on float from unsigned
+values; the pairs it lacks are wave_max on float, wave_min on float over negative and mixed values, and wave_min /
+wave_max on int: test_wave_reductions_on_float_and_int.  (Nothing instantiates wave_max on unsigned long long.)"""
 import numpy as np
 import pytest
 
@@ -92,3 +103,86 @@ def test_wave_ops_against_numpy(lp, n):
 def test_wave_ops_refuses_more_than_a_workgroup(lp):
     with pytest.raises(RolloutError):
         lp.selftest_wave_ops(np.zeros(257, np.uint32), np.zeros(257, np.uint8))
+
+
+# ---- selftest_wave_wide ------------------------------------------------------------------------------------------------
+def _wide_values():
+    rng = np.random.default_rng(33)
+    return {"zero": np.zeros(1024, np.uint32), "ones": np.full(1024, 0xFFFFFFFF, np.uint32),
+            "random": rng.integers(0, 1 << 32, 1024, dtype=np.uint32)}
+
+
+WIDE_VALUES = _wide_values()
+LANES = np.arange(64, dtype=np.uint32)
+
+
+@pytest.mark.parametrize("n", [0, 1, 65, 960, 1023, 1024])
+def test_block_scan_of_sixteen_waves(lp, n):
+    for vname, values in WIDE_VALUES.items():
+        scan, _, misc = lp.selftest_wave_wide(values[:n], LANES, 1)
+        v = np.zeros(1024, np.uint64)
+        v[:n] = values[:n]
+        what = f"n={n} values={vname}"
+        assert np.array_equal(scan[0], (np.cumsum(v) - v) & M32), f"{what}: block_excl_scan<16>"
+        assert int(misc[0]) == int(v.sum()) & M32, f"{what}: block_excl_scan<16>'s total"
+        assert np.array_equal(scan[1], np.repeat(v.reshape(16, 64).sum(axis=1) & M32, 64)), f"{what}: wave_last of the inclusive scan"
+
+
+def _float_lanes():
+    rng = np.random.default_rng(34)
+    f = np.float32
+    fmax, tiny = np.finfo(f).max, np.float32(1e-45)                       # (the smallest denormal)
+    spread = lambda a: rng.permutation(np.resize(np.asarray(a, f), 64))
+    return {
+        "negatives": (-rng.uniform(0.5, 4000.0, 64)).astype(f),
+        "mixed signs": rng.uniform(-4000.0, 4000.0, 64).astype(f),
+        "FLT_MAX both ways": spread([fmax, -fmax, 1.0, -1.0, 3.5]),
+        "denormals": spread([tiny, -tiny, tiny * 3, -tiny * 7, np.float32(1e-39), np.float32(-1e-39)]),
+        "denormals and normals": spread([tiny, np.float32(1.1754944e-38), -tiny, np.float32(-1.1754944e-38)]),
+        "all equal": np.full(64, -12.625, f),
+        "one differs, lane 0": np.concatenate([[f(-3.0)], np.full(63, 2.0, f)]),
+        "one differs, lane 63": np.concatenate([np.full(63, 2.0, f), [f(-3.0)]]),
+        "zeros of both signs": spread([0.0, -0.0]),
+        "zeros among positives": spread([0.0, -0.0, 1.0, 2.0]),
+        "zeros among negatives": spread([0.0, -0.0, -1.0, -2.0]),
+    }
+
+
+@pytest.mark.parametrize("name", list(_float_lanes()))
+def test_wave_reductions_on_float_and_int(lp, name):
+    lanes = _float_lanes()[name]
+    words = lanes.view(np.uint32)
+    _, red, _ = lp.selftest_wave_wide([], words, 1)
+    fmin, fmax = red[0].view(np.float32), red[1].view(np.float32)
+    if "zero" in name:                                                   # -0 and +0 are one number: compared as numbers
+        assert np.array_equal(fmin, np.full(64, lanes.min())) and np.array_equal(fmax, np.full(64, lanes.max())), name
+    else:
+        assert np.array_equal(red[0], np.full(64, lanes.min().view(np.uint32))), f"{name}: wave_min float"
+        assert np.array_equal(red[1], np.full(64, lanes.max().view(np.uint32))), f"{name}: wave_max float"
+    ints = words.view(np.int32)                                          # the same words as int: both signs, the extremes
+    assert np.array_equal(red[2].view(np.int32), np.full(64, ints.min())), f"{name}: wave_min int"
+    assert np.array_equal(red[3].view(np.int32), np.full(64, ints.max())), f"{name}: wave_max int"
+
+
+def test_wave_reductions_on_int_extremes(lp):
+    rng = np.random.default_rng(35)
+    for ints in (rng.integers(-(1 << 31), 1 << 31, 64).astype(np.int32), np.array([-(1 << 31), (1 << 31) - 1, 0, -1] * 16, np.int32),
+                 np.full(64, -7, np.int32)):
+        _, red, _ = lp.selftest_wave_wide([], ints.view(np.uint32), 1)
+        assert np.array_equal(red[2].view(np.int32), np.full(64, ints.min())) and np.array_equal(red[3].view(np.int32), np.full(64, ints.max()))
+
+
+@pytest.mark.parametrize("groups", [1, 2, 64, 257, 2090])
+def test_last_block_names_one_workgroup_that_sees_every_word(lp, groups):
+    """one launch per size, no repetition: exactly one workgroup is named, and it reads what all the others stored"""
+    _, _, misc = lp.selftest_wave_wide([], LANES, groups)
+    i = np.arange(4 * groups, dtype=np.uint64)
+    want = int(((groups * 0x9E3779B1 + i * i + 1) & M32).sum()) & M32
+    assert int(misc[1]) == 1, f"{int(misc[1])} workgroups were named the last"
+    assert int(misc[2]) == want and int(misc[3]) == 0
+
+
+def test_wave_wide_refuses_what_it_cannot_hold(lp):
+    for values, groups in ((np.zeros(1025, np.uint32), 1), ([], 0), ([], 4097)):
+        with pytest.raises(RolloutError):
+            lp.selftest_wave_wide(values, LANES, groups)

@@ -161,6 +161,8 @@ def record():
     lp.stream_ceiling(1 << 20, 3)
     lp.selftest_sincos([0.0, 0.5, 1.0])
     lp.selftest_wave_ops([1, 2, 0xFFFFFFFF], [1, 0, 1], 5)
+    lp.selftest_wave_wide([3, 0xFFFFFFFE], np.arange(64), 2)
+    lp.selftest_point_grid(f32(2, 3), (0.0, 0.0, 0.0), (2.0, 2.0, 1.0), 0.25, 0.5, 4096, f32(1, 3, 1.0), 0.1001, 0.01, 2)
     lp.debug()
     lp.pose_arrays()
     lp.pose_arrays(accepted_only=True)
