@@ -9,6 +9,8 @@
 //                          (dddmr_lego_loam/lego_loam_bor/src/imageProjection.cpp:280-314, :582-592) -> feedSweep(), sweepCloud()
 //   mcl_feature_node's laser_cloud_sharp / _less_sharp / _flat
 //                          (lego_loam_bor/src/featureAssociation.cpp:318-491, :1384-1405)             -> sweepFeatures()
+//   the feature node's segmented_cloud_info orientation, its four clouds with point times and outlier_cloud
+//                          (imageProjection.cpp:391-406, :548-558; featureAssociation.cpp:281-314, :486-514) -> sweepAssociation()
 //   PathBlockedStrategy::selfMark                   (plugins/path_blocked_strategy.cpp:56-100)       -> pathBlocked()
 //   DepthCameraObservationBuffer::bufferCloud, local mode
 //                                    (plugins/depth_camera/depth_camera_observation_buffer.cpp:78-187) -> feedDepthFrame()
@@ -167,6 +169,53 @@ inline int sweepFeatures(dddmr_rollout_ctx * ctx, int source, int which, Cloud &
     out.points[i].z = xyzr[4 * i + 2];
     out.points[i].intensity = xyzr[4 * i + 3];
   }
+  return DDDMR_OK;
+}
+
+// What the host FeatureAssociation and mapOptimization take of the source's latest accepted sweep once
+// dddmr_rollout_set_lidar_sweep_association has switched the association on: cornerPointsSharp, cornerPointsLessSharp,
+// surfPointsFlat and surfPointsLessFlat with ring + scan_period * relTime in `intensity` (frame 0: the association frame
+// extractFeatures holds them in, what updateTransformation and publishCloudsLast read; frame 1: through the features'
+// T_out, what publishCloud publishes), the three orientation fields of the cloud_info message, and outlier_cloud
+// (pitch-removed frame; adjustOutlierCloud's axis change stays with the caller).  Everything is read before anything
+// is written: on any code but DDDMR_OK the outputs are what they were.
+template<class Cloud, class CloudInfo>
+inline int sweepAssociation(
+  dddmr_rollout_ctx * ctx, int source, int frame, Cloud & sharp, Cloud & less_sharp, Cloud & flat, Cloud & less_flat,
+  CloudInfo & seg_msg, Cloud & outliers)
+{
+  if (!ctx) {return DDDMR_ERR_BAD_ARG;}
+  float orient[3] = {0.f, 0.f, 0.f};
+  int rc = dddmr_rollout_get_lidar_sweep_orientation(ctx, source, orient, nullptr);
+  if (rc != DDDMR_OK) {return rc;}
+  std::vector<float> xyzi[5];                              // the four clouds, then the outliers
+  for (int which = 0; which < 5; ++which) {
+    size_t n = 0;
+    rc = which < 4 ? dddmr_rollout_get_lidar_sweep_association(ctx, source, which, frame, nullptr, nullptr, 0, &n) :
+      dddmr_rollout_get_lidar_sweep_outliers(ctx, source, nullptr, 0, &n);
+    if (rc != DDDMR_OK) {return rc;}
+    xyzi[which].resize(4 * n);
+    if (n) {
+      rc = which < 4 ? dddmr_rollout_get_lidar_sweep_association(ctx, source, which, frame, xyzi[which].data(), nullptr, n, &n) :
+        dddmr_rollout_get_lidar_sweep_outliers(ctx, source, xyzi[which].data(), n, &n);
+      if (rc != DDDMR_OK) {return rc;}
+      xyzi[which].resize(4 * n);
+    }
+  }
+  Cloud * const out[5] = {&sharp, &less_sharp, &flat, &less_flat, &outliers};
+  for (int which = 0; which < 5; ++which) {
+    const std::vector<float> & v = xyzi[which];
+    out[which]->points.resize(v.size() / 4);
+    for (size_t i = 0; i < v.size() / 4; ++i) {
+      out[which]->points[i].x = v[4 * i + 0];
+      out[which]->points[i].y = v[4 * i + 1];
+      out[which]->points[i].z = v[4 * i + 2];
+      out[which]->points[i].intensity = v[4 * i + 3];
+    }
+  }
+  seg_msg.start_orientation = orient[0];
+  seg_msg.end_orientation = orient[1];
+  seg_msg.orientation_diff = orient[2];
   return DDDMR_OK;
 }
 

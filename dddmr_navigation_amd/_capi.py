@@ -500,6 +500,11 @@ _TABLE = {
     "set_lidar_sweep_features": (_int, [_ctx, _i32, _P(LidarFeaturesConfig)]),
     "get_lidar_sweep_segmented": (_int, [_ctx, _i32] + [_vp] * 6 + [_sz, _pn]),
     "get_lidar_sweep_features": (_int, [_ctx, _i32, _int, _vp, _vp, _sz, _pn]),
+    "set_lidar_sweep_association": (_int, [_ctx, _i32, _i32, _dbl]),
+    "get_lidar_sweep_orientation": (_int, [_ctx, _i32, _vp, _P(_i32)]),
+    "get_lidar_sweep_times": _get_of,
+    "get_lidar_sweep_association": (_int, [_ctx, _i32, _int, _int, _vp, _vp, _sz, _pn]),
+    "get_lidar_sweep_outliers": _get_of,
     "set_depth_frustum": (_int, [_ctx, _i32, _P(DepthFrustumConfig), _pd]),
     "get_depth_frustum": (_int, [_ctx, _i32, _vp, _vp, _vp, _vp]),
     "depth_frustum_test": (_int, [_ctx] + _cloud + [_vp, _vp]),

@@ -4,7 +4,8 @@
 // ImageProjection::cloudSegmentation's segmented_cloud and seg_msg (dddmr_lego_loam/lego_loam_bor/src/imageProjection.cpp
 // :542-580), then FeatureAssociation::calculateSmoothness (src/featureAssociation.cpp:318-341), markOccludedPoints
 // (:343-379), extractFeatures (:381-491, without the cloudLabel / less-flat loop and its VoxelGrid), adjustDistortion's
-// axis change (:281-314, without relTime) and publishCloud's transform (:1384-1405).  Types as featureAssociation.h
+// axis change (:281-314, without relTime) and publishCloud's transform (:1384-1405).  What is left out here is in
+// sweep_association.hip.h, off unless asked for.  Types as featureAssociation.h
 // :62-63, :100-103 has them: the thresholds, ranges and curvatures are floats; the literals 0.3 and 0.02 are doubles.
 //
 // Every sweep behaves like the FIRST sweep of a freshly constructed FeatureAssociation (std::vector::resize leaves
@@ -57,8 +58,11 @@ struct FeatResult {            // host-mapped; written by k_feat_segment's last 
   uint32_t n_feat[3];
 };
 
+struct SweepAssoc;              // sweep_association.hip.h, included at the end of this file
+
 struct LidarFeatures {
   FeatParams p;
+  std::unique_ptr<SweepAssoc, LateDelete<SweepAssoc>> assoc;   // not null: the sweep association is on
   uint32_t* block_cnt = nullptr;       // [workgroups]
   uint32_t* n_dev = nullptr;           // [1] segmented points of the sweep being built
   float* curv = nullptr;               // [V H]
@@ -189,7 +193,8 @@ __global__ __launch_bounds__(256) void k_feat_curv(const float4* __restrict__ se
   meta[i] = (cr >> 31) | (marked ? kMetaPicked : 0u) | ((uint32_t)fwd << 2) | ((uint32_t)bwd << 5);
 }
 
-// ascending bitonic sort of n (a power of two, <= kFeatSortMax) keys in LDS by the workgroup
+// ascending bitonic sort of n (a power of two) keys in the caller's LDS array by the whole workgroup, whatever its size:
+// k_feat_sort has at most kFeatSortMax keys, k_assoc_ring (sweep_association.hip.h) up to 4096
 __device__ __forceinline__ void feat_sort(unsigned long long* key, uint32_t n) {
   for (uint32_t size = 2; size <= n; size <<= 1)
     for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
@@ -394,3 +399,5 @@ inline void features_launch(LidarFeatures& f, int b, const int32_t* label_img, c
 }
 
 }  // namespace dddmr
+
+#include "sweep_association.hip.h"   // SweepAssoc and its launches: what LidarFeatures::assoc points to

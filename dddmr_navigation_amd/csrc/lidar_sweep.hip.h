@@ -35,8 +35,8 @@
 // Differences from the reference, on purpose: a record with any non-finite coordinate is dropped
 // (removeNaNFromPointCloud trusts is_dense); a point whose row quotient is not a number (range 0) is dropped (the
 // reference converts NaN to int); an empty sweep yields an empty cloud (the reference reads points.front()).
-// Left out: the patched ground cloud and its VoxelGrid (:450-514), _seg_msg / findStartEndAngle / segmented_cloud /
-// outlier_cloud, the projected image.  (segmented_cloud and _seg_msg's arrays: lidar_features.hip.h, when switched on.)
+// Left out: the patched ground cloud and its VoxelGrid (:450-514), the projected image.  (segmented_cloud and _seg_msg's
+// arrays: lidar_features.hip.h; findStartEndAngle and outlier_cloud: sweep_association.hip.h; each when switched on.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -80,6 +80,9 @@ struct SweepResult {           // host-mapped, written by the last k_sweep_outpu
 struct LidarFeatures;           // lidar_features.hip.h
 inline void features_launch(LidarFeatures& f, int b, const int32_t* label_img, const uint8_t* ground_img, const float* range_img,
                             const float4* pts, hipStream_t stream);
+struct SweepParams;
+inline void association_launch(LidarFeatures& f, int b, const SweepParams& sweep, const float* raw, const float4* moved,
+                               const int32_t* label_img, const float4* pts, hipStream_t stream);   // sweep_association.hip.h
 
 struct LidarSweep {
   SweepParams p;
@@ -401,7 +404,10 @@ inline int sweep_feed(LidarSweep& s, FeedParams f, const float* raw, size_t n, s
   hipLaunchKernelGGL(k_sweep_number, per_pixel, block, 0, stream, k, s.parent, s.size, s.rows, s.block_cnt, s.num);
   hipLaunchKernelGGL(k_sweep_output, per_pixel, block, 0, stream, k, s.parent, s.num, s.pts, s.block_cnt, s.label_img[b], s.cloud[b],
                      s.n_dev, s.res_dev);
-  if (s.features) features_launch(*s.features, b, s.label_img[b], s.ground_img[b], s.range_img[b], s.pts, stream);
+  if (s.features) {
+    features_launch(*s.features, b, s.label_img[b], s.ground_img[b], s.range_img[b], s.pts, stream);
+    association_launch(*s.features, b, k, s.feed.stage_dev, s.moved, s.label_img[b], s.pts, stream);   // (nothing unless it is on)
+  }
   // stage two: cbSensor on the device cloud; at most one point per pixel reaches it
   PerceptionScratch& ps = s.feed;
   const VoxelView table = ps.table.view(voxel_slots_for(px), ps.counters + 2);

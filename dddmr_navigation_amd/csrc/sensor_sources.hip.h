@@ -498,6 +498,8 @@ int dddmr_rollout_set_lidar_sweep(dddmr_rollout_ctx* ctx, int32_t source_id, con
   if (rc != 0) return fail(ctx, DDDMR_ERR_HIP, "set_lidar_sweep: sweep feed failed (%d)", rc);
   FeatResult feat_counts{};
   if (sw->features) std::memcpy(&feat_counts, sw->features->res_host, sizeof(feat_counts));   // written before the feed's release
+  AssocResult assoc_res{};
+  if (sw->features && sw->features->assoc) std::memcpy(&assoc_res, sw->features->assoc->res_host, sizeof(assoc_res));
   uint32_t n_all = 0;
   if ((rc = commit_source(ctx, "set_lidar_sweep", source_id, sw->obs[sw->cur ^ 1], n_out, &n_all)) != DDDMR_OK) return rc;
   sw->cur ^= 1;                                        // committed: the buffers the sweep was built in become the current ones
@@ -507,6 +509,13 @@ int dddmr_rollout_set_lidar_sweep(dddmr_rollout_ctx* ctx, int32_t source_id, con
     lf->n_seg[sw->cur] = feat_counts.n_seg;
     for (int w = 0; w < 3; ++w) lf->n_feat[sw->cur][w] = feat_counts.n_feat[w];
     lf->have_sweep = true;
+    if (SweepAssoc* a = lf->assoc.get()) {
+      a->n_less_flat[sw->cur] = assoc_res.n_less_flat;
+      a->n_outliers[sw->cur] = assoc_res.n_outliers;
+      a->half_index[sw->cur] = assoc_res.i0;
+      a->have[sw->cur] = true;
+      for (int w = 0; w < 3; ++w) a->orientation[sw->cur][w] = assoc_res.orient[w];
+    }
   }
   if (n_segmented) *n_segmented = n_seg;
   if (n_source_points) *n_source_points = n_out;
@@ -669,6 +678,108 @@ int dddmr_rollout_get_lidar_sweep_features(dddmr_rollout_ctx* ctx, int32_t sourc
   if (count && (xyzr_out || seg_index_out)) HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
   drain.armed = false;
   return DDDMR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Lidar sweep association: the rest of the feature node's front half (sweep_association.hip.h)
+// ---------------------------------------------------------------------------
+int dddmr_rollout_set_lidar_sweep_association(dddmr_rollout_ctx* ctx, int32_t source_id, int32_t enable, double scan_period) {
+  if (!ctx) return DDDMR_ERR_BAD_ARG;
+  const char* what = "set_lidar_sweep_association";
+  if (const int arc = source_arg(ctx, what, source_id)) return arc;
+  if (enable && (!std::isfinite(scan_period) || scan_period < 0.0)) return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: scan_period %g", what, scan_period);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  LidarSweep* sw = nullptr;
+  if (const int rc = sweep_features_of(ctx, source_id, what, &sw)) return rc;
+  LidarFeatures& lf = *sw->features;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+  if (!enable) {
+    lf.assoc.reset();
+    return DDDMR_OK;
+  }
+  if (lf.assoc) {                                      // a new period holds from the next sweep on
+    lf.assoc->scan_period = scan_period;
+    return DDDMR_OK;
+  }
+  auto a = std::make_unique<SweepAssoc>();
+  a->scan_period = scan_period;
+  if (association_alloc(*a, sw->p.V, sw->p.H) != 0) return fail(ctx, DDDMR_ERR_HIP, "%s: scratch of source %d", what, source_id);
+  lf.assoc.reset(a.release());
+  return DDDMR_OK;
+}
+
+static int sweep_association_of(dddmr_rollout_ctx* ctx, int32_t source_id, const char* what, LidarSweep** out) {
+  if (const int rc = sweep_features_of(ctx, source_id, what, out)) return rc;
+  if (!(*out)->features->assoc) return fail(ctx, DDDMR_ERR_STATE, "%s: the association of source %d is off", what, source_id);
+  return DDDMR_OK;
+}
+
+int dddmr_rollout_get_lidar_sweep_orientation(dddmr_rollout_ctx* ctx, int32_t source_id, float out[3], int32_t* half_index) {
+  if (!ctx) return DDDMR_ERR_BAD_ARG;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  LidarSweep* sw = nullptr;
+  if (const int rc = sweep_association_of(ctx, source_id, "get_lidar_sweep_orientation", &sw)) return rc;
+  const SweepAssoc& a = *sw->features->assoc;
+  for (int w = 0; w < 3 && out; ++w) out[w] = a.orientation[sw->cur][w];
+  if (half_index) *half_index = (int32_t)a.half_index[sw->cur];
+  return DDDMR_OK;
+}
+
+// the tail of the association's getters: `count` records of the device arrays into the caller's, either of which may be null
+static int association_read(dddmr_rollout_ctx* ctx, const char* what, const void* rec, float* rec_out, const uint32_t* idx, uint32_t* idx_out,
+                            size_t count, size_t rec_bytes, size_t capacity, size_t* n) {
+  if ((rec_out || idx_out) && capacity < count) return fail(ctx, DDDMR_ERR_CAPACITY, "%s: capacity %zu < %zu", what, capacity, count);
+  *n = count;
+  Drain drain{ctx->copy_stream};
+  if (count && rec_out) HIPCHK(ctx, hipMemcpyAsync(rec_out, rec, count * rec_bytes, hipMemcpyDeviceToHost, ctx->copy_stream));
+  if (count && idx_out) HIPCHK(ctx, hipMemcpyAsync(idx_out, idx, count * 4, hipMemcpyDeviceToHost, ctx->copy_stream));
+  if (count && (rec_out || idx_out)) HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+  drain.armed = false;
+  return DDDMR_OK;
+}
+
+int dddmr_rollout_get_lidar_sweep_times(dddmr_rollout_ctx* ctx, int32_t source_id, float* intensity_out, size_t capacity, size_t* n) {
+  if (!ctx || !n) return DDDMR_ERR_BAD_ARG;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  LidarSweep* sw = nullptr;
+  if (const int rc = sweep_association_of(ctx, source_id, "get_lidar_sweep_times", &sw)) return rc;
+  const LidarFeatures& lf = *sw->features;
+  const int b = sw->cur;
+  const size_t count = lf.assoc->have[b] ? lf.n_seg[b] : 0;      // (the current sweep may be older than the association)
+  return association_read(ctx, "get_lidar_sweep_times", lf.assoc->times[b], intensity_out, nullptr, nullptr, count, sizeof(float), capacity, n);
+}
+
+int dddmr_rollout_get_lidar_sweep_association(dddmr_rollout_ctx* ctx, int32_t source_id, int which, int frame, float* xyzi_out,
+                                              uint32_t* seg_index_out, size_t capacity, size_t* n) {
+  if (!ctx || !n) return DDDMR_ERR_BAD_ARG;
+  const char* what = "get_lidar_sweep_association";
+  if (which < 0 || which > 3 || frame < 0 || frame > 1)
+    return fail(ctx, DDDMR_ERR_BAD_ARG, "%s: which %d (0 sharp, 1 less sharp, 2 flat, 3 less flat), frame %d (0 association, 1 through T_out)", what,
+                which, frame);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  LidarSweep* sw = nullptr;
+  if (const int rc = sweep_association_of(ctx, source_id, what, &sw)) return rc;
+  const LidarFeatures& lf = *sw->features;
+  const SweepAssoc& a = *lf.assoc;
+  const int b = sw->cur;
+  if (which == 3) return association_read(ctx, what, a.less_flat[b][frame], xyzi_out, a.less_flat_idx[b], seg_index_out, a.n_less_flat[b], sizeof(float4), capacity, n);
+  const size_t off = feat_offset(sw->p.V, which);
+  return association_read(ctx, what, a.list[b][frame] + off, xyzi_out, lf.feat_idx[b] + off, seg_index_out, a.have[b] ? lf.n_feat[b][which] : 0, sizeof(float4),
+                          capacity, n);
+}
+
+int dddmr_rollout_get_lidar_sweep_outliers(dddmr_rollout_ctx* ctx, int32_t source_id, float* xyzi_out, size_t capacity, size_t* n) {
+  if (!ctx || !n) return DDDMR_ERR_BAD_ARG;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> prod(ctx->producer_mu);
+  LidarSweep* sw = nullptr;
+  if (const int rc = sweep_association_of(ctx, source_id, "get_lidar_sweep_outliers", &sw)) return rc;
+  const SweepAssoc& a = *sw->features->assoc;
+  return association_read(ctx, "get_lidar_sweep_outliers", a.outliers[sw->cur], xyzi_out, nullptr, nullptr, a.n_outliers[sw->cur], sizeof(float4), capacity, n);
 }
 
 // ---------------------------------------------------------------------------

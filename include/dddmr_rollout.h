@@ -394,9 +394,10 @@ int dddmr_rollout_get_depth_image_cloud(dddmr_rollout_ctx* ctx, int32_t source_i
    Differences from the reference, on purpose: a record with ANY non-finite coordinate is dropped
    (removeNaNFromPointCloud trusts is_dense); a point whose row quotient is not a number (range 0) is dropped (the
    reference converts NaN to int); an empty sweep yields an empty cloud (the reference reads points.front()).
-   Left out: the patched ground cloud and its VoxelGrid (:450-514, it feeds mapping), findStartEndAngle, outlier_cloud,
-   the projected image, and the stitcher on sweep sources.  segmented_cloud and _seg_msg's arrays come with the
-   sweep's features (dddmr_rollout_set_lidar_sweep_features below), off unless asked for.
+   Left out: the patched ground cloud and its VoxelGrid (:450-514, it feeds mapping), the projected image, and the
+   stitcher on sweep sources.  segmented_cloud and _seg_msg's arrays come with the sweep's features
+   (dddmr_rollout_set_lidar_sweep_features below), findStartEndAngle and outlier_cloud with the sweep's association
+   (dddmr_rollout_set_lidar_sweep_association), each off unless asked for.
 
    A source is configured for scans, for sweeps or for depth; feeding it another kind is DDDMR_ERR_BAD_ARG, as are
    dddmr_rollout_set_stitcher_source on a sweep source (a limit of this version), V < 2, H < 4, ground_scan_index >= V,
@@ -468,9 +469,10 @@ int dddmr_rollout_get_lidar_sweep_image(dddmr_rollout_ctx* ctx, int32_t source_i
    FeatureAssociation: the reference never rewrites slot 4 of cloudSmoothness (ring 0's sp, below calculateSmoothness's
    range) and carries its sorted leftover from sweep to sweep; here slot 4 is {0.0f, ind 0} every time, so a ground
    point at segment index 0 is ring 0's first flat pick unless it is occlusion-marked.  Equal curvatures sort by
-   ascending index (std::sort leaves their order undefined).  The relTime part of the intensity and findStartEndAngle
-   are left out (mcl_3dl overwrites or ignores the intensity).  Sharp, less sharp and flat are produced; less flat is
-   not.  What cbLeGoFeatureCloud does with the lists (VoxelGrid, normals, clusters) is dddmr_rollout_mcl_prepare_from_sweep,
+   ascending index (std::sort leaves their order undefined).  Left out HERE: the relTime part of the intensity,
+   findStartEndAngle and less flat (mcl_3dl overwrites or ignores the intensity and never reads less flat); they come
+   with dddmr_rollout_set_lidar_sweep_association below, and these entries stay as they are with it on.  What
+   cbLeGoFeatureCloud does with the lists (VoxelGrid, normals, clusters) is dddmr_rollout_mcl_prepare_from_sweep,
    which reads them where they lie.
 
    The features are part of the sweep's double-buffered result: built beside the current one and swapped in only when
@@ -497,6 +499,64 @@ int dddmr_rollout_get_lidar_sweep_segmented(dddmr_rollout_ctx* ctx, int32_t sour
    the segmented cloud. */
 int dddmr_rollout_get_lidar_sweep_features(dddmr_rollout_ctx* ctx, int32_t source_id, int which, float* xyzr_out,
                                            uint32_t* seg_index_out, size_t capacity, size_t* n_points);
+
+/* Lidar sweep ASSOCIATION: the rest of the front half of LeGO-LOAM's feature node on a sweep source whose features
+   are on (additions to ABI version 2; no existing struct or entry changes; with the association off a sweep launches
+   exactly what it launched before and every other output is byte-equal).  It is what the host FeatureAssociation and
+   mapOptimization take besides the three feature lists when odom_type is "laser_odometry" or the node maps.  Line
+   numbers: dddmr_lego_loam/lego_loam_bor/src/imageProjection.cpp (ip) and src/featureAssociation.cpp (fa).
+     orientation (ip:391-406, findStartEndAngle)  start = -atan2f(y, x) of the first record of the pitch-removed cloud,
+                                end = -atan2f(y, x) of the last one + 2 * M_PI; end - start > 3 * M_PI takes 2 * M_PI off,
+                                < M_PI adds it; diff = end - start.  The three are float32 message fields: atan2f and
+                                the differences are float, M_PI sums and comparisons double, each stored back into the
+                                float.  First and last are the first and last records the ingest keeps as finite (it
+                                drops non-finite records on purpose).  An empty sweep: zeros.
+     point times (fa:281-314, adjustDistortion, the part the features leave out)  per segmented point, in index order:
+                                ori = -atan2f(seg.y, seg.x) in float; while halfPassed is false, ori < start - M_PI / 2
+                                adds 2 * M_PI, ori > start + M_PI * 3 / 2 takes it off (double comparisons, the sum
+                                rounded to float), and ori - start > M_PI sets halfPassed for the points BEHIND this one;
+                                then ori += 2 * M_PI, ori < end - M_PI * 3 / 2 adds 2 * M_PI, ori > end + M_PI / 2 takes
+                                it off.  relTime = (ori - start) / diff in float; intensity = float(double(ring) +
+                                scan_period * double(relTime)).  half_index is the index at which the flag flips
+                                (the last point of the first branch), the number of segmented points when it never does.
+     less flat (fa:486-514)     per ring the segment indices k of [sp, ep], ep included, of every sixth that was not
+                                skipped, with cloudLabel[k] <= 0 (not one of the ring's sharp or less-sharp picks; labels
+                                never written are 0, as for the features), ascending; then pcl::VoxelGrid, leaf 0.2
+                                (fa:124), on the ring's candidates in the association frame: inverse leaf 1 / 0.2f in
+                                float, floor, min_b from the ring's own candidates, output in voxel-index order
+                                x + y dx + z dx dy, points of a voxel summed in input order in float and divided by the
+                                count; the intensity is averaged the same way (an assumption).  PCL's
+                                overflow rule: with d = int64((max - min) * inverse_leaf) + 1 per axis, dx * dy * dz
+                                above INT32_MAX hands the ring's candidates through unchanged.  Rings in ring order.
+     outliers (ip:548-558)      pixels with label 999999, row > ground_scan_index and col % 5 == 0 in raster order: the
+                                pitch-removed point, intensity float(double(float(row)) + double(float(col)) / 10000.0)
+                                (ip:376).  adjustOutlierCloud's axis change stays with the caller.
+     the four clouds            sharp, less sharp, flat (the features' lists, the same points in the same order) and
+                                less flat, frame 0: the association frame, (y, z, x) of the segmented point untransformed,
+                                as extractFeatures holds them; frame 1: through the features' T_out as publishCloud
+                                publishes them (fa:1401-1404; transformPointCloud carries the intensity through).  The
+                                intensity is the point time; for less flat the voxel's average.
+   Left out: updateTransformation and everything behind it (the scan matcher), the patched ground, the projected image.
+
+   It is part of the sweep's double-buffered result as the features are: it holds from the next sweep, and after a
+   refused sweep the getters return the previous sweep's.  enable == 0, switching the features off and re-configuring
+   the source switch it off.  DDDMR_ERR_STATE: not a sweep source, its features are off, or (getters) the association
+   is off.  DDDMR_ERR_BAD_ARG: a scan_period that is negative or not finite, `which` outside 0 .. 3, `frame` outside
+   0 .. 1.  The getters follow the feature getters: NULL outputs only report the count, DDDMR_ERR_CAPACITY when an
+   output is wanted and capacity is below the count, a failed call changes nothing, before the first sweep zero points
+   (orientation: zeros, half_index 0).  get_lidar_sweep_times: one intensity per segmented point.  seg_index_out: the
+   point's index in the segmented cloud; for less flat the lowest index that went into the voxel.  16 bytes per point. */
+int dddmr_rollout_set_lidar_sweep_association(dddmr_rollout_ctx* ctx, int32_t source_id, int32_t enable,
+                                              double scan_period);
+int dddmr_rollout_get_lidar_sweep_orientation(dddmr_rollout_ctx* ctx, int32_t source_id, float out[3],
+                                              int32_t* half_index);
+int dddmr_rollout_get_lidar_sweep_times(dddmr_rollout_ctx* ctx, int32_t source_id, float* intensity_out,
+                                        size_t capacity, size_t* n);
+/* which: 0 sharp, 1 less sharp, 2 flat, 3 less flat; frame: 0 association, 1 through T_out */
+int dddmr_rollout_get_lidar_sweep_association(dddmr_rollout_ctx* ctx, int32_t source_id, int which, int frame,
+                                              float* xyzi_out, uint32_t* seg_index_out, size_t capacity, size_t* n);
+int dddmr_rollout_get_lidar_sweep_outliers(dddmr_rollout_ctx* ctx, int32_t source_id, float* xyzi_out, size_t capacity,
+                                           size_t* n);
 
 /* Depth camera frustums and selfClear's clearing verdicts: the global-mode side of DepthCameraLayer, first slice
    (additions to ABI version 2; no existing struct or entry changes).
